@@ -232,6 +232,14 @@ class ControlPlaneStandIn:
         pass
 
 
+def dump_outputs(out_dir, turns):
+    """the turns one timed step returned, as float64 arrays in the order the library returned them (a few hundred turns per hour: far below 64 MB)"""
+    os.makedirs(out_dir, exist_ok=True)
+    t = np.asarray([(s, e, k) for (s, e, k) in turns], np.float64).reshape(-1, 3)
+    for j, name in enumerate(("turns_start", "turns_end", "turns_label")):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(t[:, j]))
+
+
 def self_launch(n):
     """`python bench.py --gpus N` (no torchrun): start N ranks as child processes of this one, which never touches the GPU.
     stdout of rank 0 is relayed (the JSON line); every rank's stderr goes to this process's stderr with a rank prefix.  The first
@@ -337,7 +345,11 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="take the multi-rank code path (RCCL communicator inside the library, "
                     "all-gather, assembly) even with one rank")
     ap.add_argument("--opt", action="append", default=[], help="library option key=value (sd_set_option), e.g. emb_batch_items=1536; tuning only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned (the speaker "
+                    "turns) as DIR/turns_start.npy, DIR/turns_end.npy, DIR/turns_label.npy (float64): two builds compared output for output")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- N > 1 without a launcher: this process becomes the launcher.  It starts N fresh children (one rank per GPU) with
     # RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, BEFORE anything here touches the GPU (no torch.cuda call above this line), relays
@@ -520,6 +532,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     ms_per_step = dt / max(a.steps, 1) * 1e3
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, turns_box[0] or [])
     audio_s = n_total / SR
     stats_live = d.kernel_stats("items_live")
     live_local = stats_live["flops"] / max(stats_live["launches"], 1)

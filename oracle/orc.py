@@ -103,6 +103,177 @@ def lib():
     return L
 
 
+# ---- recorded answers of the reference's compiled code (tests/golden/ref_cpp_calls.npz)
+# oracle/_ref is built only where the reference tree lies; everywhere else the tests that pin the oracle and the HIP path on the
+# reference's own C++ replay the answers that build gave.  Every call is keyed by a hash of its method name and its inputs, so a
+# replayed answer is only ever returned for exactly the inputs it was recorded for; a call without a recorded answer raises.
+# tools/mint_reference_fixtures_cpp.py records them (SD_REF_RECORD=1, live oracle/_ref).
+REF_CALLS = os.path.join(os.path.dirname(_HERE), "tests", "golden", "ref_cpp_calls.npz")
+_RECORDING = {}
+_REPLAY = None
+
+
+def recording():
+    return os.environ.get("SD_REF_RECORD") == "1"
+
+
+def _canon(h, x):
+    if isinstance(x, np.ndarray):
+        x = np.ascontiguousarray(x)
+        h.update(b"A" + x.dtype.str.encode() + repr(x.shape).encode())
+        h.update(x.tobytes())
+    elif isinstance(x, (bool, np.bool_)):
+        h.update(b"B1" if x else b"B0")
+    elif isinstance(x, (int, np.integer)):
+        h.update(b"I" + str(int(x)).encode())
+    elif isinstance(x, (float, np.floating)):
+        h.update(b"F" + np.float64(x).tobytes())
+    elif isinstance(x, (list, tuple)):
+        h.update(b"L%d" % len(x))
+        for v in x:
+            _canon(h, v)
+    elif isinstance(x, (str, bytes)):
+        h.update(b"S" + (x.encode() if isinstance(x, str) else x))
+    elif x is None:
+        h.update(b"N")
+    else:
+        raise TypeError("cannot key a reference call on %r" % type(x))
+
+
+def call_key(name, *args):
+    import hashlib
+    h = hashlib.sha1(name.encode())
+    for a in args:
+        _canon(h, a)
+    return h.hexdigest()
+
+
+def _gather_runs(out, src):
+    """`out` (float32) as runs of elements of `src` (float32) and of zeros: (dst_start, src_start or -1, length) rows, or None when some
+    value of `out` is not in `src`.  The reference's crops and compacted signals are copies of its input samples: stored as positions
+    in the call's own input they take a few hundred bytes instead of megabytes of random samples."""
+    o, sr = out.reshape(-1).view(np.uint32), src.reshape(-1).view(np.uint32)
+    if len(sr) == 0:
+        return None
+    order = np.argsort(sr, kind="stable")
+    pos = np.minimum(np.searchsorted(sr[order], o), len(sr) - 1)
+    idx = order[pos].astype(np.int64)
+    nz = o != 0
+    if not np.array_equal(sr[idx[nz]], o[nz]):
+        return None
+    idx[o == 0] = -1
+    cont = np.zeros(len(o), bool)
+    cont[1:] = ((idx[1:] == idx[:-1] + 1) & (idx[:-1] >= 0)) | ((idx[1:] < 0) & (idx[:-1] < 0))
+    starts = np.flatnonzero(~cont)
+    lens = np.diff(np.append(starts, len(o)))
+    return np.stack([starts, idx[starts], lens], 1).astype(np.int64)
+
+
+def _from_runs(runs, src, dtype, shape):
+    sr = src.reshape(-1)
+    out = np.zeros(int(np.prod(shape, dtype=np.int64)), dtype)
+    for d0, s0, n in runs:
+        if s0 >= 0:
+            out[d0:d0 + n] = sr[s0:s0 + n]
+    return out.reshape(shape)
+
+
+class _Blob:
+    def __init__(self):
+        self.parts, self.size = [], 0
+
+    def add(self, b):
+        self.parts.append(b)
+        self.size += len(b)
+        return self.size - len(b)
+
+
+def _encode(v, blob, sources=()):
+    if isinstance(v, np.ndarray):
+        a = np.ascontiguousarray(v)
+        if a.dtype == np.float32 and a.size >= 1024:
+            for j, src in enumerate(sources):
+                runs = _gather_runs(a, src)
+                if runs is not None and np.array_equal(_from_runs(runs, src, a.dtype, a.shape).view(np.uint32), a.view(np.uint32)):
+                    return {"g": j, "a": a.dtype.str, "s": list(a.shape), "o": blob.add(runs.tobytes()), "n": len(runs)}
+        return {"a": a.dtype.str, "s": list(a.shape), "o": blob.add(a.tobytes())}
+    if isinstance(v, (bool, np.bool_)):
+        return {"b": bool(v)}
+    if isinstance(v, (int, np.integer)):
+        return {"i": int(v)}
+    if isinstance(v, (float, np.floating)):
+        return {"f": np.float64(v).tobytes().hex()}
+    if isinstance(v, tuple):
+        return {"t": [_encode(x, blob, sources) for x in v]}
+    if isinstance(v, list):
+        return {"l": [_encode(x, blob, sources) for x in v]}
+    raise TypeError("cannot record %r" % type(v))
+
+
+def _decode(e, blob, sources=()):
+    if "g" in e:
+        runs = np.frombuffer(blob[e["o"]:e["o"] + 24 * e["n"]].tobytes(), np.int64).reshape(-1, 3)
+        return _from_runs(runs, sources[e["g"]], np.dtype(e["a"]), e["s"])
+    if "a" in e:
+        dt = np.dtype(e["a"])
+        n = int(np.prod(e["s"], dtype=np.int64)) * dt.itemsize
+        return np.frombuffer(blob[e["o"]:e["o"] + n].tobytes(), dt).reshape(e["s"]).copy()
+    if "b" in e:
+        return e["b"]
+    if "i" in e:
+        return e["i"]
+    if "f" in e:
+        return float(np.frombuffer(bytes.fromhex(e["f"]), np.float64)[0])
+    if "t" in e:
+        return tuple(_decode(x, blob, sources) for x in e["t"])
+    return [_decode(x, blob, sources) for x in e["l"]]
+
+
+def _sources(args):
+    """the float32 inputs of a call, against which its float32 outputs may be stored as gathers"""
+    return [np.ascontiguousarray(a, np.float32) for a in args if isinstance(a, np.ndarray) and a.dtype == np.float32]
+
+
+def record(key, value, sources=()):
+    if recording():
+        _RECORDING[key] = (value, list(sources))
+    return value
+
+
+def save_recording(path=REF_CALLS):
+    import json
+    import lzma
+    blob, meta = _Blob(), {}
+    for k in sorted(_RECORDING):
+        v, src = _RECORDING[k]
+        meta[k] = _encode(v, blob, src)
+    xz = lambda b: np.frombuffer(lzma.compress(b, preset=9 | lzma.PRESET_EXTREME), np.uint8)
+    np.savez(path, meta=xz(json.dumps(meta, separators=(",", ":")).encode()), blob=xz(b"".join(blob.parts)))
+    return len(meta)
+
+
+def replay():
+    """the recorded answers (None when the fixture is absent)"""
+    global _REPLAY
+    if _REPLAY is None and os.path.exists(REF_CALLS):
+        import json
+        import lzma
+        z = np.load(REF_CALLS)
+        _REPLAY = (json.loads(lzma.decompress(z["meta"].tobytes())), np.frombuffer(lzma.decompress(z["blob"].tobytes()), np.uint8))
+    return _REPLAY
+
+
+def replayed(key, what, sources=()):
+    r = replay()
+    if r is None:
+        raise RuntimeError("oracle/_ref is absent and %s is missing" % os.path.relpath(REF_CALLS, os.path.dirname(_HERE)))
+    meta, blob = r
+    if key not in meta:
+        raise KeyError("no recorded answer of the reference build for this call of %s (inputs changed?): re-record with "
+                       "tools/mint_reference_fixtures_cpp.py where the reference tree exists" % what)
+    return _decode(meta[key], blob, sources)
+
+
 def ref():
     """the reference's own clustering.cpp (None when oracle/_ref is absent)"""
     global _REF
@@ -122,14 +293,17 @@ def ref():
 _REFWAV = None
 
 
-def ref_wav_read(path):
+def ref_wav_read(path, recorded=False):
     """the reference's own WavReader (frontend/wav.h, oracle/_ref/libref_wav.so): raw sample values as WavReader::data()
-    holds them (not yet divided by 32768), sample rate, channels, bits.  None when oracle/_ref is absent."""
+    holds them (not yet divided by 32768), sample rate, channels, bits.  None when oracle/_ref is absent -- unless `recorded`:
+    then the answer the reference build gave for a file of the same bytes (see REF_CALLS)."""
     global _REFWAV
+    with open(path, "rb") as f:
+        key = call_key("ref_wav_read", f.read())
     if _REFWAV is None:
         p = os.path.join(_HERE, "_ref", "libref_wav.so")
         if not os.path.exists(p):
-            return None
+            return replayed(key, "ref_wav_read") if recorded else None
         R = C.CDLL(p)
         R.ref_wav_read.restype = C.c_long
         R.ref_wav_read.argtypes = [C.c_char_p, C.c_void_p, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -140,7 +314,7 @@ def ref_wav_read(path):
         raise IOError("reference WavReader cannot open " + path)
     out = np.zeros(max(n, 1), np.float32)
     _REFWAV.ref_wav_read(path.encode(), out.ctypes.data_as(C.c_void_p), n, None, None, None)
-    return out[:n], sr.value, ch.value, bits.value
+    return record(key, (out[:n].copy(), sr.value, ch.value, bits.value))
 
 
 _REFGLUE = None
@@ -198,14 +372,21 @@ class RefGlue:
 
     def __init__(self):
         self.R = refglue()
-        if self.R is None:
-            raise RuntimeError("oracle/_ref/libref_glue.so is absent (built only where /root/reference exists)")
+        if self.R is None and replay() is None:
+            raise RuntimeError("oracle/_ref/libref_glue.so is absent (built only where /root/reference exists) and so are its recorded answers")
 
     def np_rint(self, v):
         return self.R.ref_np_rint(float(v))
 
     def closest_frame(self, t, start=0.0, step=FRAME_STEP, dur=FRAME_STEP):
         return self.R.ref_closest_frame(start, step, dur, float(t))
+
+    def np_rint_many(self, vs):
+        """np_rint of every value, one reference call each (one recorded answer for the lot)"""
+        return np.array([self.R.ref_np_rint(float(v)) for v in vs], np.int64)
+
+    def closest_frame_many(self, ts, start=0.0, step=FRAME_STEP, dur=FRAME_STEP):
+        return np.array([self.R.ref_closest_frame(start, step, dur, float(t)) for t in ts], np.int64)
 
     def argsort(self, v):
         v = np.ascontiguousarray(v, np.float64)
@@ -342,6 +523,60 @@ class RefGlue:
         n = self.R.ref_finalize(seg, c, F, S, emb, emb.shape[2], num_samples, buf, cap, C.byref(K))
         assert n <= cap
         return [(buf[i].start, buf[i].end, buf[i].label) for i in range(n)], K.value
+
+
+def _live_or_replayed(cls, prefix, names):
+    """every method in `names` answers from the live library (recording its answer under SD_REF_RECORD=1) or, when the library is
+    absent, from the recorded answers"""
+    import copy
+
+    def wrap(name, fn):
+        def w(self, *args, **kw):
+            key = call_key(prefix + name, list(args), sorted(kw.items()))
+            if self.R is None:
+                return replayed(key, prefix + name, _sources(args))
+            out = fn(self, *args, **kw)
+            record(key, copy.deepcopy(out), _sources(args))
+            return out
+        w.__name__, w.__doc__ = fn.__name__, fn.__doc__
+        return w
+    for n in names:
+        setattr(cls, n, wrap(n, getattr(cls, n)))
+    return cls
+
+
+_live_or_replayed(RefGlue, "RefGlue.", ["np_rint", "closest_frame", "np_rint_many", "closest_frame_many", "argsort", "argmax", "cosine_cdist", "binarize", "crop",
+                                        "clean_segmentations", "select_masks", "speaker_count", "aggregate", "embedding_inputs",
+                                        "cluster_embeddings", "clustering", "mark_inactive", "reconstruct", "to_annotation", "support",
+                                        "finalize"])
+
+
+def refglue_available():
+    return refglue() is not None or replay() is not None
+
+
+class RefClustering:
+    """the reference's own clustering.cpp (oracle/_ref/libref_clustering.so) at numpy level, live or replayed"""
+
+    def __init__(self):
+        self.R = ref()
+        if self.R is None and replay() is None:
+            raise RuntimeError("oracle/_ref/libref_clustering.so is absent and so are its recorded answers")
+
+    def linkage(self, X):
+        X = np.ascontiguousarray(X, np.float64)
+        Z = np.zeros((len(X) - 1, 4))
+        self.R.ref_linkage(X, len(X), X.shape[1], Z)
+        return Z
+
+    def cluster(self, X, threshold):
+        X = np.ascontiguousarray(X, np.float64)
+        T = np.zeros(len(X), np.int32)
+        self.R.ref_cluster(X, len(X), X.shape[1], threshold, T)
+        return T
+
+
+_live_or_replayed(RefClustering, "RefClustering.", ["linkage", "cluster"])
 
 
 def np_rint(v):
