@@ -578,13 +578,6 @@ __global__ __launch_bounds__(MWT_MAX) void k_linkage_mw(double* D, int n, int* s
         return __syncthreads_and(ok ? 1 : 0) != 0;
     };
     MinIdx none; none.v = INFINITY; none.i = -1;
-#ifdef SD_LINKAGE_STAMPS
-    unsigned long long tS = __builtin_amdgcn_s_memrealtime(), acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned fix_lanes = 0, fix_waves = 0;
-#define STAMP2(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memrealtime(); acc[i] += t_ - tS; tS = t_; } while (0)
-#else
-#define STAMP2(i) do { } while (0)
-#endif
 
     // local arg-min over the owned active rows, skipping the rows being refreshed this round
     auto local_argmin = [&](int nL, const int* L) -> Cand {
@@ -674,7 +667,6 @@ __global__ __launch_bounds__(MWT_MAX) void k_linkage_mw(double* D, int n, int* s
     // matrix, bounds): whoever sees the slot may read them.
     auto publish = [&](Min2 q, Cand m, int nL, const Min2* rows, int row_tie = 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        STAMP2(12);
         __syncthreads();
         ++bar;
         MwGran* sl = gran + ((size_t)par * G + g) * SLOT_WORDS;
@@ -841,21 +833,15 @@ __global__ __launch_bounds__(MWT_MAX) void k_linkage_mw(double* D, int n, int* s
             if (fresh && y >= 0) break;
             if (g == 0 && tid == 0) sync[2] += 1;            // diagnostic: retry rounds
             const int nL = s_nL[lp]; const int* L = s_L[lp];
-            STAMP2(5);
             scan_rows(nL, L, s_row);
-            STAMP2(0);
             Cand m = local_argmin(nL, L);
             publish(none2, m, nL, s_row);
-            STAMP2(1);
             if (!consume(nL > 0 ? 8 + 5 * nL : 11)) return;
-            STAMP2(2);
             digest(nL, L, -1, false);
             par ^= 1;
             best = d_best;
-            STAMP2(3);
             lp ^= 1;
             if (!((best.fresh & 1) && best.y >= 0)) pick_stale(nocand, lp);
-            STAMP2(4);
             x = best.i; dist = best.v; y = best.y; fresh = (best.fresh & 1) != 0;
             prefetch_pair();
         }
@@ -877,7 +863,6 @@ __global__ __launch_bounds__(MWT_MAX) void k_linkage_mw(double* D, int n, int* s
         if (k == n - 2) { write_Z(); break; }
         // ---- one pass over the owned active rows: Lance-Williams update + neighbour patches (cl.cpp:361-392),
         // NN(y) partial from the fresh distances (cl.cpp:395-404), next local arg-min
-        STAMP2(5);
         Min2 q = none2;
         Cand m; m.v = INFINITY; m.i = -1; m.y = -1; m.fresh = 0;
         int row_tie = 0;
@@ -912,20 +897,15 @@ __global__ __launch_bounds__(MWT_MAX) void k_linkage_mw(double* D, int n, int* s
                 }
                 nbz[u] = l_nb[pc]; mdz[u] = l_md[pc]; md2z[u] = l_md2[pc];
             }
-            STAMP2(8);
             if constexpr (SQ) {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     if (zz[u] < 0) continue;
                     const int tz = l_ty[zz[u] - z0];
-#ifdef SD_LINKAGE_STAMPS
-                    { const bool fx = (txm < tz) || (tym < tz); const unsigned long long bm = __ballot(fx); fix_lanes += fx ? 1u : 0u; if (lane == 0 && bm) fix_waves += 1; }
-#endif
                     if (txm < tz) dzx[u] = LDG(&D[(int64_t)zz[u] * N + x]);        // z's row was written after x's: the current {z, x} is there
                     if (tym < tz) dzy[u] = LDG(&D[(int64_t)zz[u] * N + y]);
                 }
             }
-            STAMP2(9);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int z = zz[u];
@@ -953,9 +933,7 @@ __global__ __launch_bounds__(MWT_MAX) void k_linkage_mw(double* D, int n, int* s
                 if (z < n - 1) cand_acc(m, mz, z, nz, fz);
             }
         }
-        STAMP2(6);
         block_min_qc(q, m, sh, shc, NW);
-        STAMP2(10);
         row_tie = __syncthreads_or(row_tie);
         write_Z();
         if (tid == 0) { size[x] = 0; size[y] = nx + ny; }     // (every thread is past the pass and has used the old sizes)
@@ -971,13 +949,9 @@ __global__ __launch_bounds__(MWT_MAX) void k_linkage_mw(double* D, int n, int* s
             act[p] = last; pos[last / G] = p; s_cnt = c2;
             l_md[p] = l_md[c2]; l_md2[p] = l_md2[c2]; l_nb[p] = l_nb[c2]; l_fr[p] = l_fr[c2];
         }
-        STAMP2(11);
         publish(q, m, 0, s_row, row_tie);
-        STAMP2(7);
         if (!consume(11)) return;
-        STAMP2(2);
         digest(0, s_L[lp], y, true);
-        STAMP2(3);
         par ^= 1;
         if (d_rowtie) { if (g == 0 && tid == 0) sync[5] = 1; return; }
         best = d_best;
@@ -1005,43 +979,9 @@ __global__ __launch_bounds__(MWT_MAX) void k_linkage_mw(double* D, int n, int* s
         }
         lp ^= 1;
         if (!((best.fresh & 1) && best.y >= 0)) pick_stale(cy, lp);
-        STAMP2(4);
         x = best.i; dist = best.v; y = best.y; fresh = (best.fresh & 1) != 0;
         prefetch_pair();
     }
-#ifdef SD_LINKAGE_STAMPS
-    if (g == 0 && tid == 0) for (int i = 0; i < 16; ++i) sync[8 + i] = (unsigned)(acc[i] / 100);   // microseconds
-    atomicAdd(&sync[24], fix_lanes); if (lane == 0) atomicAdd(&sync[25], fix_waves);
-#endif
-}
-
-// tuning hook: cost of the device-scope barrier alone (mode 0), or with each workgroup dirtying `dirty` doubles first
-__global__ __launch_bounds__(MWT) void k_barrier_bench(unsigned* sync, int iters, double* scratch, int dirty)
-{
-    unsigned bar = 0;
-    const int G = gridDim.x;
-    for (int it = 0; it < iters; ++it) {
-        for (int i = threadIdx.x; i < dirty; i += MWT) scratch[((size_t)blockIdx.x * 7919 + (size_t)i * 104729 + it) % (1 << 22)] = (double)it;
-        ++bar;
-        if (!mw_barrier(&sync[0], bar * (unsigned)G, &sync[1])) return;
-    }
-}
-extern "C" int sd_bench_barrier(sd_ctx* c, int G, int iters, int dirty, double* us_per_barrier)
-{
-    if (!c || !us_per_barrier || G < 1 || G > c->num_cu) return SD_ERR_ARG;
-    WS(c, unsigned, sync, "cl_sync", 4);
-    WS(c, double, scratch, "bb_scratch", 1 << 22);
-    HIPCHK(c, hipMemsetAsync(sync, 0, 4 * sizeof(unsigned), c->stream));
-    hipEvent_t e0, e1;
-    HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
-    HIPCHK(c, hipEventRecord(e0, c->stream));
-    hipLaunchKernelGGL(k_barrier_bench, dim3(G), dim3(MWT), 0, c->stream, sync, iters, scratch, dirty);
-    HIPCHK(c, hipEventRecord(e1, c->stream));
-    HIPCHK(c, hipEventSynchronize(e1));
-    float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-    *us_per_barrier = ms * 1e3 / iters;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return SD_OK;
 }
 
 __global__ void k_fill_i32(int* p, int v, int64_t n, int iota)
@@ -1225,19 +1165,6 @@ int run_linkage(sd_ctx* c, const double* d_X, int64_t N, int d, double* d_Z)
         HIPCHK(c, hipMemcpyAsync(h, sync, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->stats["linkage_retry_rounds"].flops += (double)h[2];
-#ifdef SD_LINKAGE_STAMPS
-        fprintf(stderr, "linkage stamps (us): retry-scan %u retry-argmin %u barrier %u digest %u pick %u bookkeeping %u lw-compute+stores %u publish-stores %u | lw-issue %u lw-fixup %u block-min %u tie+Z %u drain %u | fix-up lanes %u waves %u\n",
-                h[8], h[9], h[10], h[11], h[12], h[13], h[14], h[15], h[16], h[17], h[18], h[19], h[20], h[24], h[25]);
-        if (use_rg) {          // every workgroup's view of the enabled intervals (min / mean / max over the workgroups, ms)
-            std::vector<unsigned> hw((size_t)16 * G);
-            HIPCHK(c, hipMemcpy(hw.data(), sync + 32, hw.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-            for (int i = 0; i < 16; ++i) {
-                double mn = 1e30, mx = 0, sm = 0;
-                for (int q = 0; q < G; ++q) { const double v = hw[(size_t)q * 16 + i] * 1e-2; mn = v < mn ? v : mn; mx = v > mx ? v : mx; sm += v; }
-                if (mx > 0) fprintf(stderr, "  stamp %2d over %d workgroups: min %.2f mean %.2f max %.2f Mcycles (shader clock)\n", i, G, mn, sm / G, mx);
-            }
-        }
-#endif
         if (h[1] && onex) {
             // too few workgroups found themselves on XCC 0 (dispatch not round-robin?): never again in this context; the
             // multi-XCD form does the job (the distance matrix is rebuilt by the recursive call)

@@ -36,9 +36,6 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 #define G_BOFF 32768
 #define G_STRIP 4096           // epilogue strip per wave: 16 rows x 128 channels of fp16 (128 + 32 KB = all of the CU's LDS)
 
-#ifndef SD_G_ABLATE
-#define SD_G_ABLATE 0          // diagnostic builds only: 1 no output stores, 2 no DMA in the loop, 4 no MFMA, 8 no A-operand DMA, 16 no W-operand DMA, 32 no fragment reads, 64 the DMAs of a K-step issued by four waves instead of eight
-#endif
 typedef __attribute__((address_space(3))) char lds_char;
 typedef int v4i __attribute__((ext_vector_type(4)));
 
@@ -204,22 +201,10 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
     };
     auto dma = [&](int st) {
         const unsigned stb = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(st * G_STAGE));
-        if (SD_G_ABLATE & (64 | 128 | 256)) {   // ablation (diagnostic builds only; meaningful with 4 + 32): the 64 DMAs of a K-step issued by 4 / 2 / 1 waves instead of eight
-            constexpr int NW = (SD_G_ABLATE & 64) ? 4 : (SD_G_ABLATE & 128) ? 2 : 1;
-            if (wid < NW) {
-#pragma unroll
-                for (int it = 0; it < 4 * (8 / NW); ++it) {
-                    const int k = (SD_G_ABLATE & 512) ? it % (8 / NW) : it / 4, p = (SD_G_ABLATE & 512) ? it / (8 / NW) : it % 4;      // 512: piece-major order
-                    lds_dma_b128(rA, stb + a_off[p] + k * NW * 1024, voA[p] + (unsigned)(k * NW * 8) * (unsigned)a.x_ld * ES, sK);
-                    lds_dma_b128(rB, stb + b_off[p] + k * NW * 1024, voB[p] + (unsigned)(k * NW * 8) * (unsigned)a.w_ld * ES, sB + sK);
-                }
-            }
-            return;
-        }
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            if (!(SD_G_ABLATE & 8)) lds_dma_b128(rA, stb + a_off[p], voA[p], sK);
-            if (!(SD_G_ABLATE & 16)) lds_dma_b128(rB, stb + b_off[p], voB[p], sB + sK);
+            lds_dma_b128(rA, stb + a_off[p], voA[p], sK);
+            lds_dma_b128(rB, stb + b_off[p], voB[p], sB + sK);
         }
     };
 
@@ -252,7 +237,6 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
     const char* const Bfr16 = lds + G_BOFF + (wc * 128 + l15) * 128;
     float4 qa[2][4], qb[2][4];
     auto hfrag = [&](int st, int kb, int fbuf) {
-        if (SD_G_ABLATE & 32) return;   // ablation (diagnostic builds only): no fragment reads, the matrix pipe runs on whatever the registers hold
         if constexpr (P == 2) {
             const int g = kb >> 1, h = kb & 1;
             const int co = ((4 * g + l4) ^ ((l15 >> 1) & 7)) * 16 + st * G_STAGE;
@@ -272,23 +256,12 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
     };
     auto hmma = [&](int fbuf, int kb) {
         if constexpr (P == 2) {
-            if (SD_G_ABLATE & 4) {
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) { asm volatile("" :: "v"(qb[fbuf][jj].x), "v"(qb[fbuf][jj].w), "v"(qa[kb >> 1][jj].x), "v"(qa[kb >> 1][jj].w)); }
-                return;
-            }
             const int g = kb >> 1, h = kb & 1;
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj)
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     acc16[i][4 * h + jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, qa[g][i]), __builtin_bit_cast(half8, qb[fbuf][jj]), acc16[i][4 * h + jj], 0, 0, 0);
-            return;
-        }
-        if (SD_G_ABLATE & 4) {          // ablation (diagnostic builds only): fragment reads without the matrix pipe
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { asm volatile("" :: "v"(hb[fbuf][j].x), "v"(hb[fbuf][j].y), "v"(hb[fbuf][j].z), "v"(hb[fbuf][j].w)); }
-            asm volatile("" :: "v"(ha[fbuf][0].x), "v"(ha[fbuf][0].w), "v"(ha[fbuf][1].x), "v"(ha[fbuf][1].w));
             return;
         }
         if constexpr (P == 0) {
@@ -332,9 +305,6 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
     hfrag(0, 0, 0);
 
     int q = q0, s = 0, buf = 0;
-#ifdef SD_G_STAMPS        // diagnostic build only (make libsdhip_gstamps.so): where a workgroup's cycles go -- K-loop, epilogue -- printed by one workgroup
-    unsigned long long t_loop = 0, t_epi = 0, t_mark = __builtin_amdgcn_s_memtime(); int n_tiles_done = 0;
-#endif
     while (true) {
 #define W_PAIR(mask, n) do { _Pragma("unroll") for (int i_ = 0; i_ < (n); ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(mask, 1, 0); } } while (0)
         // K-groups 0..2 of step s from stage `buf`; each group's fragments were read while the group before ran
@@ -384,7 +354,7 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
                     if ((j & 1) == 1) { __builtin_amdgcn_sched_barrier(0); dma_piece(buf, e * 2 + (j >> 1)); __builtin_amdgcn_sched_barrier(0); }
                 }
         } else {
-            if (!(SD_G_ABLATE & 2)) dma(buf);            // step s + 2 into the stage just released
+            dma(buf);            // step s + 2 into the stage just released
             hfrag(buf ^ 1, 0, 0);
             hmma(1, 3);
         }
@@ -392,9 +362,6 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
         advance();
 
         if (s == S - 1) {
-#ifdef SD_G_STAMPS
-            { const unsigned long long t = __builtin_amdgcn_s_memtime(); t_loop += t - t_mark; t_mark = t; }
-#endif
             if constexpr (P == 0) {
             // ---- epilogue, f32.  Accumulator layout (weights first, see hmma): register r of acc[i][j], lane (li, lh) = row 32 i + li,
             // channel 32 j + 8 (r >> 2) + 4 lh + (r & 3): four registers = four consecutive channels of a row = one 16-byte store, 32
@@ -565,9 +532,6 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
                 }
             }
             }
-#ifdef SD_G_STAMPS
-            { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long t = __builtin_amdgcn_s_memtime(); t_epi += t - t_mark; t_mark = t; ++n_tiles_done; }
-#endif
             q = next_sb(q);
             if (q >= sb_end) break;
             { int j_, nt_; (void)sb_valid(q, j_, nt_); m0c = __builtin_amdgcn_readfirstlane((xcd + 8 * j_) * GM); n0c = __builtin_amdgcn_readfirstlane(nt_ * GN); }
@@ -577,11 +541,6 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
         }
         buf ^= 1;
     }
-#ifdef SD_G_STAMPS
-    if (blockIdx.x == 8 && tid == 0) printf("g256 M %d K %d N %d: %d tiles x %d steps; K-loop %llu cycles (%llu per step), epilogue %llu (%llu per tile = %.1f steps)\n", a.M, a.Cin * a.KT, a.Cout,
-                                            n_tiles_done, S, t_loop, t_loop / (unsigned long long)(n_tiles_done * S), t_epi, t_epi / (unsigned long long)n_tiles_done,
-                                            (double)t_epi / n_tiles_done / ((double)t_loop / (n_tiles_done * S)));
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the load stream runs past the last tile: nothing may be in flight when the LDS is given back
 }
 

@@ -268,19 +268,15 @@ __global__ __launch_bounds__(512) void k_conv_gemm_w256(ConvArgs a)
             // are read one group ahead into the registers the group before last released.  The load stream runs TWO steps ahead: on entry the
             // loader registers hold step s + 1 (restaged in groups 2 and 4, so that the LDS writes have landed long before the barrier behind
             // group 5), and each half of them is refilled with step s + 2 in the group after its restaging (five groups of latency budget).
-            // [measured, tools/x3_ablate.sh, MFA layer: 168 ms with loads in group 1 and all restaging in groups 4-5; 142 ms without the
+            // [measured with ablation builds, profiles/r03_x3_ablation.txt, MFA layer: 168 ms with loads in group 1 and all restaging in groups 4-5; 142 ms without the
             // global loads, 115 ms without restaging and barrier = the MFMA + fragment-read floor]
-            // SD_X3_ABLATE (tools/x3_ablate.sh, never in the product build): 1 = no global loads in the loop, 2 = no restaging / barrier, 3 = both
-#ifndef SD_X3_ABLATE
-#define SD_X3_ABLATE 0
-#endif
             afrag(buf, 2, 1);                      // lo block 0 of A
             xmma(0, 0);                            // hi0 * hi0
             W_PAIR(0x100, 2); __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
             __builtin_amdgcn_sched_barrier(0);
             bfrag(buf, 2, 1);                      // lo block 0 of W
             xmma(1, 0);                            // lo0 * hi0
-            if (!(SD_X3_ABLATE & 2)) lstore_part(buf ^ 1, 0);
+            lstore_part(buf ^ 1, 0);
             // the split of a row's eight channels is ~28 VALU instructions, and there are four LDS writes: left alone they all sit behind the
             // group's last MFMA
             W_PAIR(0x100, 4);
@@ -290,14 +286,14 @@ __global__ __launch_bounds__(512) void k_conv_gemm_w256(ConvArgs a)
             __builtin_amdgcn_sched_barrier(0);
             afrag(buf, 1, 1); bfrag(buf, 1, 0);    // hi block 1 of both
             xmma(0, 1);                            // hi0 * lo0
-            if (!(SD_X3_ABLATE & 1)) gload_half(0);
+            gload_half(0);
             W_PAIR(0x100, 6);
 #pragma unroll
             for (int i_ = 0; i_ < 2; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x020, 2, 0); }
             __builtin_amdgcn_sched_barrier(0);
             afrag(buf, 3, 0);                      // lo block 1 of A
             xmma(1, 0);                            // hi1 * hi1
-            if (!(SD_X3_ABLATE & 2)) lstore_part(buf ^ 1, 1);
+            lstore_part(buf ^ 1, 1);
             W_PAIR(0x100, 2);
 #pragma unroll
             for (int i_ = 0; i_ < 4; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 8, 0); }
@@ -306,13 +302,13 @@ __global__ __launch_bounds__(512) void k_conv_gemm_w256(ConvArgs a)
             __builtin_amdgcn_sched_barrier(0);
             bfrag(buf, 3, 1);                      // lo block 1 of W
             xmma(0, 0);                            // lo1 * hi1
-            if (!(SD_X3_ABLATE & 1)) gload_half(1);
+            gload_half(1);
             W_PAIR(0x100, 4);
 #pragma unroll
             for (int i_ = 0; i_ < 2; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x020, 2, 0); }
             __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
             __builtin_amdgcn_sched_barrier(0);
-            if (!(SD_X3_ABLATE & 2)) __syncthreads();
+            __syncthreads();
             afrag(buf ^ 1, 0, 0); bfrag(buf ^ 1, 0, 0);
             xmma(1, 1);                            // hi1 * lo1
             W_PAIR(0x100, 6); __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);

@@ -154,17 +154,6 @@ __device__ __forceinline__ unsigned rq_word(const RQ& q, int k)      // word k o
     return k == 0 ? lo32(q.v) : k == 1 ? hi32(q.v) : k == 2 ? (unsigned)q.i : k == 3 ? lo32(q.v2) : k == 4 ? hi32(q.v2) : k == 5 ? (unsigned)q.sz : (unsigned)q.ty;
 }
 
-#ifdef SD_LINKAGE_STAMPS
-#ifndef SD_LINKAGE_STAMP_MASK
-#define SD_LINKAGE_STAMP_MASK 0xffff
-#endif
-// (a stamp costs up to a few hundred ns -- it waits for the scalar / LDS queue: enable few at a time, -DSD_LINKAGE_STAMP_MASK=<bits>; an interval then runs from the previous ENABLED stamp)
-// s_memtime (shader clock), not s_memrealtime: one s_memrealtime per merge round alone cost 1.7 us per round here.  Units: kilo-cycles / 10 in the output.
-#define RSTAMP(i) do { if ((SD_LINKAGE_STAMP_MASK >> (i)) & 1) { const unsigned long long t_ = __builtin_readcyclecounter(); acc[i] += t_ - tS; tS = t_; } } while (0)
-#else
-#define RSTAMP(i) do { } while (0)
-#endif
-
 // TB = launch bound (256 / 512 / 1024 threads): the register budget follows it -- 128 VGPRs at 1024 threads spill part of the column state
 template <bool ONEX, int TB, int UU>
 __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, const int* nb0, const double* md0, const double* md20, double* Z,
@@ -212,10 +201,6 @@ __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, c
     const int zsafe = z0 < n ? z0 : 0;                       // a valid column for the loads of idle register slots
     unsigned bar = 0;
     int par = 0, lp = 0;
-#ifdef SD_LINKAGE_STAMPS
-    unsigned long long tS = __builtin_readcyclecounter(), acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned fix_lanes = 0, fix_waves = 0;
-#endif
 
     // ---- per-column state, registers
     int zc[UU], c_nb[UU], c_fl[UU], c_ty[UU], c_sz[UU], c_nbsz[UU], c_nbty[UU];
@@ -471,21 +456,15 @@ __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, c
             if ((best.fl & 1) && best.y >= 0) break;
             if (g == 0 && tid == 0) sync[2] += 1;            // diagnostic: retry rounds
             const int nL = s_nL[lp]; const int* L = s_L[lp];
-            RSTAMP(5);
             scan_rows(nL, L, s_Lty[lp], s_row);
-            RSTAMP(0);
             const RCand m = local_argmin(nL, L);
             publish(m, rq_none(), 0, nL, s_row);
-            RSTAMP(1);
             if (!consume(nL > 0 ? RG_CW + RG_QW * nL : RG_MW)) return;
-            RSTAMP(2);
             digest(nL, L, s_Lty[lp], s_Lsz[lp], false);
             par ^= 1;
             best = d_best;
-            RSTAMP(3);
             lp ^= 1;
             if (!((best.fl & 1) && best.y >= 0)) pick_stale(nocand, lp);
-            RSTAMP(4);
         }
         if (best.fl & CAND_TIE) {      // the closest pair is not unique: the heap decides (run_linkage); the height of the tie goes along
             if (g == 0 && tid == 0) { sync[5] = 1; sync[26] = lo32(best.v); sync[27] = hi32(best.v); }
@@ -509,7 +488,6 @@ __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, c
         if (k == n - 2) { write_Z(); break; }
         // ---- one pass over the owned active columns: Lance-Williams update + neighbour patches (cl.cpp:361-392), NN(y) partial
         // from the fresh distances (cl.cpp:395-404), next local arg-min
-        RSTAMP(5);
         RQ q = rq_none();
         RCand m = rc_none();
         int row_tie = 0;
@@ -526,18 +504,13 @@ __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, c
                 dzy[u] = LDG(&D[(int64_t)y * N + zl]);
             }
         }
-        RSTAMP(8);
 #pragma unroll
         for (int u = 0; u < UU; ++u) {
             if (u < nu && act[u]) {
-#ifdef SD_LINKAGE_STAMPS
-                { const bool fx = (txm < c_ty[u]) || (tym < c_ty[u]); fix_lanes += fx ? 1u : 0u; }
-#endif
                 if (txm < c_ty[u]) dzx[u] = LDG(&D[(int64_t)zc[u] * N + x]);        // z's row was written after x's: the current {z, x} is there
                 if (tym < c_ty[u]) dzy[u] = LDG(&D[(int64_t)zc[u] * N + y]);
             }
         }
-        RSTAMP(9);
 #pragma unroll
         for (int u = 0; u < UU; ++u) {
             if (!(u < nu && act[u])) continue;
@@ -563,7 +536,6 @@ __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, c
             if (z < n - 1) rc_acc(m, mz, z, nz, fz, c_sz[u], c_nbsz[u], c_ty[u], c_nbty[u]);
         }
         write_Z();
-        RSTAMP(6);
         // ---- the two reductions and the flag through ONE LDS exchange; the stores of this wave have landed before its record is visible
         q = wave_min_rq(q);
         m = wave_min_rc(m);
@@ -581,7 +553,6 @@ __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, c
             m = wave_min_rc(rc);
             row_tie = __ballot(rt != 0) != 0ull ? 1 : 0;
         }
-        RSTAMP(10);
         // ---- the pair's own columns: x is gone, y is the merged cluster, rewritten in this merge
 #pragma unroll
         for (int u = 0; u < UU; ++u) {
@@ -589,11 +560,8 @@ __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, c
             if (zc[u] == y) { c_sz[u] = nx + ny; c_ty[u] = k; l_sz[tid + u * T] = nx + ny; l_ty[tid + u * T] = k; }
         }
         publish(m, q, row_tie, 0, s_row);
-        RSTAMP(7);
         if (!consume(RG_MW)) return;
-        RSTAMP(2);
         digest(0, s_L[lp], s_Lty[lp], s_Lsz[lp], true);
-        RSTAMP(3);
         par ^= 1;
         if (d_rowtie) { if (g == 0 && tid == 0) { sync[5] = 1; sync[26] = lo32(dist); sync[27] = hi32(dist); } return; }     // (this merge's stores into row y are out, and so is row k of Z: run_linkage reads from Z's row 0 whether the matrix is still what linkage_prepare left)
         best = d_best;
@@ -634,14 +602,8 @@ __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, c
         }
         lp ^= 1;
         if (!((best.fl & 1) && best.y >= 0)) pick_stale(cy, lp);
-        RSTAMP(4);
     }
 
-#ifdef SD_LINKAGE_STAMPS
-    if (g == 0 && tid == 0) for (int i = 0; i < 16; ++i) sync[8 + i] = (unsigned)(acc[i] / 10000);   // 10 kilo-cycles
-    if (tid == 0) for (int i = 0; i < 16; ++i) sync[32 + g * 16 + i] = (unsigned)(acc[i] / 10000);   // every workgroup's own view
-    atomicAdd(&sync[24], fix_lanes);
-#endif
 }
 
 // launcher: false = the geometry does not fit this kernel (the caller takes k_linkage_mw)
@@ -670,162 +632,3 @@ hipError_t linkage_rg_launch(sd_ctx* c, bool onex, int G, int TH, double* D, int
     return hipLaunchCooperativeKernel(f, dim3(onex ? 8 * G : G), dim3(TT), args, dyn, c->stream);
 }
 int linkage_rg_slot_granules() { return RG_SLOT; }
-
-// ---------------------------------------------------------------- tuning hook: what a merge round is made of
-// A synthetic round with k_linkage_rg's geometry (G workgroups of T threads, one XCD when onex), its slot exchange and its memory
-// pattern, whose parts can be switched on one by one (bits of `parts`): 1 = the two row loads per column (rows picked by a generator every
-// workgroup runs alike), 2 = the Lance-Williams arithmetic, 4 = the row-y stores + drain, 8 = the workgroup's two reductions through LDS,
-// 16 = publish + consume + digest (the all-to-all of slots).  tools/linkage_parts.py prints the time per round of each combination.
-template <bool ONEX>
-__global__ __launch_bounds__(256) void k_rg_parts(double* D, int n, MwGran* gran, unsigned* sync, int cap, int G, int rounds, int parts, double* sink)
-{
-    __shared__ RQ sh_q[4];
-    __shared__ RCand sh_c[4];
-    __shared__ unsigned s_words[RG_GMAX][RG_SLOT + 1];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int T = blockDim.x, NW = T >> 6;
-    int g = blockIdx.x;
-    if constexpr (ONEX) {
-        __shared__ int s_ticket;
-        if (tid == 0) {
-            const unsigned xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));
-            s_ticket = (xcc == 0) ? (int)atomicAdd(&sync[6], 1u) : -1;
-        }
-        __syncthreads();
-        g = s_ticket;
-        if (g < 0 || g >= G) return;
-    }
-    const int64_t N = n;
-    const int colsB = cap - 1, z0 = g * colsB;
-    const int nown = n - z0 < colsB ? (n - z0 > 0 ? n - z0 : 0) : colsB;
-    const int nu = (nown + T - 1) / T;
-    const int zsafe = z0 < n ? z0 : 0;
-    unsigned bar = 0; int par = 0;
-    unsigned long long rngs = 88172645463325252ull;
-    double keep = 0.0;
-    int y = n / 2;
-    for (int r = 0; r < rounds; ++r) {
-        rngs ^= rngs << 13; rngs ^= rngs >> 7; rngs ^= rngs << 17;
-        const int x = (int)(rngs % (unsigned long long)n);                  // a cold row, as the chain's new partner is
-        RQ q = rq_none(); RCand m = rc_none();
-        double dzx[RG_U], dzy[RG_U];
-#pragma unroll
-        for (int u = 0; u < RG_U; ++u) {
-            dzx[u] = 1.0 + u; dzy[u] = 2.0 + u;
-            if (u < nu && (parts & 1)) {
-                const int p = tid + u * T;
-                const int zl = p < nown ? z0 + p : zsafe;
-                dzx[u] = LDG(&D[(int64_t)x * N + zl]);
-                dzy[u] = LDG(&D[(int64_t)y * N + zl]);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < RG_U; ++u) {
-            if (!(u < nu)) continue;
-            const int p = tid + u * T;
-            if (p >= nown) continue;
-            const int z = z0 + p;
-            double nd = dzx[u] + dzy[u];
-            if (parts & 2) nd = lw_centroid(dzx[u], dzy[u], 0.5 + 1e-3 * (r & 7), 3 + (r & 3), 5);
-            if (parts & 4) STX<ONEX>(&D[(int64_t)y * N + z], dzy[u]);     // (the loaded value goes back: the matrix stays what it was)
-            if (parts & 256) STX<ONEX>(&D[(int64_t)z * N + y], dzy[u]);   // the mirror of row y into column y: one scattered 8-byte store per column
-            rq_acc(q, nd, z, 1, -1);
-            rc_acc(m, nd + 1.0, z, z + 1, 1, 1, 1, -1, -1);
-        }
-        if (parts & 8) {
-            q = wave_min_rq(q);
-            m = wave_min_rc(m);
-        }
-        if (parts & 32) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0) { sh_q[wv] = q; sh_c[wv] = m; }
-            __syncthreads();
-            q = sh_q[0]; m = sh_c[0];
-            for (int w2 = 1; w2 < NW; ++w2) { q = rq_merge(q, sh_q[w2]); m = rc_better(m, sh_c[w2]); }
-        }
-        const int PW = (parts & 128) ? NW : 1;            // parts & 128: every WAVE publishes its own record (no LDS fold in front of the publish): G * NW slots
-        if (parts & 16) {
-            ++bar;
-            if (parts & 128) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (wv == 0 || (parts & 128)) {
-                MwGran* sl = gran + ((size_t)par * G * PW + (size_t)g * PW + ((parts & 128) ? wv : 0)) * RG_SLOT;
-                const MwGran tag = (MwGran)bar << 32;
-                unsigned w = 0; bool on = false;
-                if (lane < RG_CW) { on = true; w = lane == 0 ? lo32(m.v) : lane == 1 ? hi32(m.v) : lane == 2 ? (unsigned)m.i : lane == 3 ? (unsigned)m.y : 1u; }
-                else if (lane < RG_CW + RG_QW) { on = true; w = rq_word(q, lane - RG_CW); }
-                if (on) STX<ONEX>(&sl[lane], tag | (MwGran)w);
-            }
-            const MwGran* base = gran + (size_t)par * G * PW * RG_SLOT;
-            const int total = G * PW * RG_MW;
-            bool ok = true;
-            for (int i0 = tid; i0 < total; i0 += 4 * T) {
-                const MwGran* p[4]; MwGran v[4]; int sl[4], wd[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { const int idx = i0 + j * T; const int ic = idx < total ? idx : i0; sl[j] = ic / RG_MW; wd[j] = ic - sl[j] * RG_MW; p[j] = base + (size_t)sl[j] * RG_SLOT + wd[j]; }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = LDG(p[j]);
-                unsigned spins = 0;
-                for (;;) {
-                    bool pend = false;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) pend |= (unsigned)(v[j] >> 32) != bar;
-                    if (!pend) break;
-                    __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) if ((unsigned)(v[j] >> 32) != bar) v[j] = LDG(p[j]);
-                    if (++spins > (1u << 22)) { sync[1] = 1; ok = false; break; }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) if (i0 + j * T < total) s_words[sl[j]][wd[j]] = (unsigned)v[j];
-            }
-            if (!__syncthreads_and(ok ? 1 : 0)) return;
-            if (parts & 64) { par ^= 1; keep += (double)s_words[lane % G][2]; continue; }       // the hand-off alone, without the digest
-            RCand b = rc_none(); RQ a = rq_none();
-            for (int u = lane; u < G * PW; u += 64) {
-                RCand c; c.v = __longlong_as_double((long long)(((unsigned long long)s_words[u][1] << 32) | s_words[u][0])); c.i = (int)s_words[u][2]; c.y = (int)s_words[u][3]; c.fl = 1;
-                c.szi = c.szy = 1; c.tyi = c.tyy = -1;
-                b = rc_better(b, c);
-                RQ qq; qq.v = __longlong_as_double((long long)(((unsigned long long)s_words[u][RG_CW + 1] << 32) | s_words[u][RG_CW])); qq.i = (int)s_words[u][RG_CW + 2];
-                qq.v2 = __longlong_as_double((long long)(((unsigned long long)s_words[u][RG_CW + 4] << 32) | s_words[u][RG_CW + 3])); qq.sz = 1; qq.ty = -1;
-                a = rq_merge(a, qq);
-            }
-            m = wave_min_rc(b);
-            q = wave_min_rq(a);
-            par ^= 1;
-            if (m.i >= 0 && m.i < n) y = m.i;          // the next round's row y depends on the exchange, as the real one does
-        }
-        keep += q.v + m.v;
-    }
-    if (tid == 0) sink[g] = keep;
-}
-extern "C" int sd_bench_linkage_parts(sd_ctx* c, int64_t N, int G, int rounds, int parts, int onex, double* us_per_round)
-{
-    if (!c || !us_per_round || N < 64 || G < 2 || G > RG_GMAX || rounds < 1) return SD_ERR_ARG;
-    if (hipSetDevice(c->device) != hipSuccess) return SD_ERR_HIP;
-    const int cap = (int)((N + G - 1) / G) + 1;
-    if (cap - 1 > RG_U * 256) SD_FAIL(c, SD_ERR_ARG, "sd_bench_linkage_parts: %d columns per workgroup (limit %d)", cap - 1, RG_U * 256);
-    WS(c, double, D, "cl_Dsq", (size_t)N * N);
-    if ((parts & 128) && G * 4 > RG_GMAX) SD_FAIL(c, SD_ERR_ARG, "sd_bench_linkage_parts: per-wave slots need workgroups * 4 <= %d", RG_GMAX);
-    WS(c, MwGran, gran, "cl_gran", (int64_t)2 * G * 4 * RG_SLOT);
-    WS(c, unsigned, sync, "cl_sync", 32 + 16 * 256);
-    WS(c, double, sink, "bb_scratch", 1 << 22);
-    HIPCHK(c, hipMemsetAsync(gran, 0, (size_t)2 * G * 4 * RG_SLOT * sizeof(MwGran), c->stream));
-    HIPCHK(c, hipMemsetAsync(sync, 0, (32 + 16 * 256) * sizeof(unsigned), c->stream));
-    HIPCHK(c, hipMemsetAsync(D, 0x3f, (size_t)N * N * sizeof(double), c->stream));          // finite doubles
-    hipEvent_t e0, e1;
-    HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
-    int n = (int)N, cap_i = cap;
-    void* args[] = {&D, &n, &gran, &sync, &cap_i, &G, &rounds, &parts, &sink};
-    HIPCHK(c, hipEventRecord(e0, c->stream));
-    const void* f = onex ? (const void*)k_rg_parts<true> : (const void*)k_rg_parts<false>;
-    HIPCHK(c, hipLaunchCooperativeKernel(f, dim3(onex ? 8 * G : G), dim3(256), args, 0, c->stream));
-    HIPCHK(c, hipEventRecord(e1, c->stream));
-    HIPCHK(c, hipEventSynchronize(e1));
-    float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-    *us_per_round = ms * 1e3 / rounds;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    unsigned h[8];
-    HIPCHK(c, hipMemcpy(h, sync, sizeof(h), hipMemcpyDeviceToHost));
-    if (h[1]) SD_FAIL(c, SD_ERR_HIP, "sd_bench_linkage_parts: slot poll timed out");
-    return SD_OK;
-}

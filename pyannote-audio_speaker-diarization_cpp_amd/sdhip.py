@@ -34,11 +34,11 @@ EXPORTS = [
     "sd_postseg", "sd_count_frames", "sd_embed", "sd_embed_dev", "sd_frontend", "sd_ecapa", "sd_linkage", "sd_cluster",
     "sd_clustering", "sd_clustering_ex", "sd_reconstruct", "sd_diarize", "sd_diarize_dev", "sd_free_turns", "sd_shard_infer_dev",
     "sd_finalize_dev", "sd_read_wav", "sd_free_pcm", "sd_format_turn", "sd_stage_ms", "sd_kernel_stats",
-    "sd_reset_stats", "sd_set_option", "sd_bench_conv", "sd_bench_barrier", "sd_convert_onnx", "sd_convert_error", "sd_read_wav_f32", "sd_free_wav", "sd_diarize_f32",
+    "sd_reset_stats", "sd_set_option", "sd_bench_conv", "sd_convert_onnx", "sd_convert_error", "sd_read_wav_f32", "sd_free_wav", "sd_diarize_f32",
     "sd_write_rttm", "sd_set_planted", "sd_comm_unique_id", "sd_comm_init", "sd_comm_destroy", "sd_comm_info", "sd_shard_plan",
     "sd_diarize_sharded", "sd_diarize_sharded_dev", "sd_write_rttm_ex", "sd_relabel_turns", "sd_relabel_turns_ex", "sd_last_confidence",
     "sd_debug_read_ws", "sd_test_pack_split_weights", "sd_resample", "sd_resample_len", "sd_diarize_wav", "sd_set_dump_dir",
-    "sd_fcluster", "sd_segment_chunks", "sd_embed_signals", "sd_bench_linkage_parts",
+    "sd_fcluster", "sd_segment_chunks", "sd_embed_signals",
 ]
 COMM_ID_BYTES = 128
 
@@ -114,8 +114,6 @@ def lib():
     L.sd_convert_error.restype = C.c_char_p
     L.sd_debug_read_ws.argtypes = [vp, C.c_char_p, i64, vp, i64]
     L.sd_test_pack_split_weights.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
-    L.sd_bench_barrier.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(dbl)]
-    L.sd_bench_linkage_parts.argtypes = [vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(dbl)]
     L.sd_bench_conv.argtypes = [vp, i64] + [C.c_int] * 9 + [C.POINTER(dbl)]
     _lib = L
     return L
@@ -486,11 +484,6 @@ class Diarizer:
         ms, n, fl, by = C.c_double(0), C.c_int64(0), C.c_double(0), C.c_double(0)
         self._chk(lib().sd_kernel_stats(self._h, name.encode(), C.byref(ms), C.byref(n), C.byref(fl), C.byref(by)))
         return {"ms": ms.value, "launches": n.value, "flops": fl.value, "bytes": by.value}
-
-    def bench_barrier(self, G, iters=2000, dirty=0):
-        us = C.c_double(0)
-        self._chk(lib().sd_bench_barrier(self._h, G, iters, dirty, C.byref(us)))
-        return us.value
 
     def bench_conv(self, items, Tp, T, Cin, Cout, KT=1, dil=1, has_x2=0, dbg=0, reps=5):
         ms = C.c_double(0)

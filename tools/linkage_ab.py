@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B of the linkage kernels on ONE box in ONE process (VERDICT r05 #2a): the library as built (HEAD) and an older build loaded side by side
-(tools/bin/libsdhip_<rev>.so, see tools/linkage_ab.sh), k_linkage_rg (linkage_kernel = 1) and k_linkage_mw (= 0), on the clustering input of the
+(tools/bin/libsdhip_<rev>.so: check out revision <rev> in a second tree, run `make` there and copy its libsdhip.so), k_linkage_rg (linkage_kernel = 1) and k_linkage_mw (= 0), on the clustering input of the
 bench's own planted hour (N = 12 989 rows: the embeddings of a real job, NaN rows dropped, rows normalised as the pipeline does), `reps`
 interleaved rounds.  Prints every kernel time and the medians; Z must be the same array everywhere.
     python tools/linkage_ab.py [reps] [old library path ...]"""
