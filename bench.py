@@ -13,10 +13,16 @@ are then replaced by the schedule-derived scores and talker embeddings (sd_set_p
 60 % of the items are live, clustering sees 4 speakers, reconstruction emits hundreds of turns.  `--workload raw`
 gives the degenerate case of round 1 (K = 1, one turn) for comparison.
 
-Prints ONE JSON line on rank 0 (contract in the task brief) including
+Prints ONE JSON line on rank 0.  A plain run does what that line's headline needs and nothing else: set-up (weights, audio,
+planted outputs, sd_create, the cold first job), the W warm-up steps, the K timed steps, --dump-outputs, the line.  What it reports
+beside the headline comes from those jobs alone, e.g.
   roofline     : the dominant kernel (f32-MFMA conv_gemm) measured live with HIP events on the library's own
                  stream over the timed region
-  cpu_baseline : the oracle ("port") timed on this box's host cores on a bounded sample (N = 1 only)
+`--full` adds every leg that needs work of its own: the same job through the host-PCM entry and without kernel events, the fp16
+and x3 modes, the raw workload, the PMC recording quoted in `roofline`, and
+  cpu_baseline : the oracle ("port") timed on this box's host cores on a bounded sample, beside the reference's own compiled
+                 clustering / finalize (N = 1 only)
+and with N > 1 the single-job latency and the strong-scaling reading.
 """
 import argparse
 import hashlib
@@ -320,36 +326,41 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--hours-per-gpu", type=float, default=1.0)
-    ap.add_argument("--cpu-seconds", type=int, default=60, help="audio seconds for the cpu_baseline sample (0 = skip)")
-    ap.add_argument("--ref-finalize", type=int, default=1, help="N = 1, planted workload of at most 1 h: also run the REFERENCE's own compiled glue (oracle/_ref/"
+    ap.add_argument("--cpu-seconds", type=int, default=60, help="--full: audio seconds for the cpu_baseline sample (0 = skip)")
+    ap.add_argument("--ref-finalize", type=int, default=1, help="--full, N = 1, planted workload of at most 1 h: also run the REFERENCE's own compiled glue (oracle/_ref/"
                     "libref_glue.so) from scores + embeddings to turns on the timed job and report it under cpu_baseline.reference_finalize (~45 s of host time; 0 = skip)")
     ap.add_argument("--workload", default="planted", choices=["planted", "raw"], help="planted = SURVEY 8d (network outputs replaced by the "
                     "schedule-derived scores / talker embeddings after the networks ran); raw = whatever the random-weight networks say (K = 1)")
     ap.add_argument("--precision", default="f32", choices=["f32", "f16", "x3"], help="f32 = the measured configuration (f32 MFMA); f16 = "
                     "BASELINE configs[4]: ECAPA conv layers on the fp16 MFMA with f32 accumulation (secondary, tolerance-checked mode); x3 = f32 tensors, "
-                    "both operands of the ECAPA conv layers split into hi + lo fp16 halves on the fp16 MFMA (opt-in mode; the default run reports it in its `x3` object)")
+                    "both operands of the ECAPA conv layers split into hi + lo fp16 halves on the fp16 MFMA (opt-in mode; an f32 run with --full reports it in its `x3` object)")
     ap.add_argument("--rank0-share", type=float, default=-1.0, help="fraction of the chunks rank 0 infers itself (it also finalizes: count / "
                     "clustering / reconstruction).  The other ranks return from the sharded call once the exchange is done, so rank 0's "
                     "finalize(k) overlaps their inference(k+1); a smaller rank-0 share balances the two. -1 = measured: the warm-up job runs with equal "
                     "shares and its stage times give the balance point; 1/N = equal shares, 0 = rank 0 only finalizes")
-    ap.add_argument("--fp16-steps", type=int, default=3, help="N = 1, f32 run: also time this many steps in fp16 mode (BASELINE configs[4]) and put them, with the "
+    ap.add_argument("--fp16-steps", type=int, default=3, help="--full, N = 1, f32 run: also time this many steps in fp16 mode (BASELINE configs[4]) and put them, with the "
                     "cosine distances of the fp16 embeddings to the f32 ones, into the `fp16` object of the result line (0 = skip)")
-    ap.add_argument("--raw-steps", type=int, default=3, help="N = 1, planted run: also time this many jobs on the RAW network outputs (every item live and full length) -> workload_dependence.value_raw_workload")
-    ap.add_argument("--x3-steps", type=int, default=3, help="N = 1, f32 run: also time this many steps with ecapa_precision = 3 (f32 tensors, split fp16 operands on the "
+    ap.add_argument("--raw-steps", type=int, default=3, help="--full, N = 1, planted run: also time this many jobs on the RAW network outputs (every item live and full length) -> workload_dependence.value_raw_workload")
+    ap.add_argument("--x3-steps", type=int, default=3, help="--full, N = 1, f32 run: also time this many steps with ecapa_precision = 3 (f32 tensors, split fp16 operands on the "
                     "MFMA) and put them into the `x3` object of the result line (0 = skip)")
-    ap.add_argument("--strong-steps", type=int, default=3, help="N > 1: also time this many jobs of ONE hour in total sharded over the N GPUs (the strong reading of the "
+    ap.add_argument("--strong-steps", type=int, default=3, help="--full, N > 1: also time this many jobs of ONE hour in total sharded over the N GPUs (the strong reading of the "
                     "metric; 0 = skip); reported as `strong_scaling_reading`")
-    ap.add_argument("--strong-timeout", type=int, default=600, help="seconds the strong-scaling leg may take before the line is printed without it")
+    ap.add_argument("--strong-timeout", type=int, default=600, help="--full, N > 1: seconds the strong-scaling leg may take before the line is printed without it")
     ap.add_argument("--dry-run-control-plane", action="store_true", help="no GPU work: a stand-in for the library (ControlPlaneStandIn) lets the multi-rank control "
                     "flow of this script run on a box without GPUs; the line says dry-run and is not a measurement")
     ap.add_argument("--force-dist", action="store_true", help="take the multi-rank code path (RCCL communicator inside the library, "
                     "all-gather, assembly) even with one rank")
     ap.add_argument("--opt", action="append", default=[], help="library option key=value (sd_set_option), e.g. emb_batch_items=1536; tuning only")
+    ap.add_argument("--full", action="store_true", help="also run every leg that needs work of its own (the options marked --full; with N = 1 also the "
+                    "host-PCM entry and the job without kernel events, with N > 1 the single-job latency) and quote the PMC recording in `roofline`; "
+                    "a plain run does only set-up, warm-up and the timed steps")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned (the speaker "
                     "turns) as DIR/turns_start.npy, DIR/turns_end.npy, DIR/turns_label.npy (float64): two builds compared output for output")
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if not a.full:
+        a.cpu_seconds, a.fp16_steps, a.x3_steps, a.raw_steps, a.strong_steps = 0, 0, 0, 0, 0
 
     # ---- N > 1 without a launcher: this process becomes the launcher.  It starts N fresh children (one rank per GPU) with
     # RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, BEFORE anything here touches the GPU (no torch.cuda call above this line), relays
@@ -574,17 +585,18 @@ def main():
     # ---- one job at a time (no overlap between consecutive jobs): the latency a single recording sees on N GPUs
     single_job_ms = None
     if world > 1:
-        d.set_option("profile", 0)
-        lat = []
-        for _ in range(2):
-            fence()
-            t1 = time.perf_counter()
-            step()
-            fence()
-            tl = torch.tensor([time.perf_counter() - t1], dtype=torch.float64)
-            dist.all_reduce(tl, op=dist.ReduceOp.MAX)
-            lat.append(float(tl.item()) * 1e3)
-        single_job_ms = round(min(lat), 2)
+        if a.full:
+            d.set_option("profile", 0)
+            lat = []
+            for _ in range(2):
+                fence()
+                t1 = time.perf_counter()
+                step()
+                fence()
+                tl = torch.tensor([time.perf_counter() - t1], dtype=torch.float64)
+                dist.all_reduce(tl, op=dist.ReduceOp.MAX)
+                lat.append(float(tl.item()) * 1e3)
+            single_job_ms = round(min(lat), 2)
         ll = torch.tensor([live_local], dtype=torch.float64)
         dist.all_reduce(ll, op=dist.ReduceOp.SUM)
         live_total = float(ll.item())
@@ -674,25 +686,27 @@ def main():
     turns = turns_box[0] or []
     if world == 1 and not use_dist:
         d.set_option("profile", 0)
-        ts = []
-        for _ in range(2):
-            gpu_sync()
-            t1 = time.perf_counter()
-            th = d.diarize(pcm_host[:n_total])
-            ts.append(time.perf_counter() - t1)
-        extra_lines["value_host_pcm"] = {"value": round(audio_s / min(ts), 2), "ms": round(min(ts) * 1e3, 2), "same_turns": th == turns_box[0],
-                                         "what": "sd_diarize: int16 PCM in pageable host memory, the 2 * n byte H2D copy and its buffer inside the timed call"}
-        # the same job without the HIP-event pairs the timed region carries around every launch (option profile = 1): what the events cost
-        tp = []
-        for _ in range(3):
-            gpu_sync()
-            t1 = time.perf_counter()
-            tq = d.diarize_dev(d_pcm.data_ptr(), n_total)
-            gpu_sync()
-            tp.append(time.perf_counter() - t1)
-        extra_lines["ms_per_step_without_kernel_events"] = {"ms": round(min(tp) * 1e3, 2), "value": round(audio_s / min(tp), 2), "same_turns": tq == turns_box[0],
-                                                            "what": "sd_diarize_dev with profile = 0, best of 3; the timed region above runs with profile = 1 because the roofline "
-                                                                    "object is measured live over it"}
+        if a.full:
+            ts = []
+            for _ in range(2):
+                gpu_sync()
+                t1 = time.perf_counter()
+                th = d.diarize(pcm_host[:n_total])
+                ts.append(time.perf_counter() - t1)
+            extra_lines["value_host_pcm"] = {"value": round(audio_s / min(ts), 2), "ms": round(min(ts) * 1e3, 2), "same_turns": th == turns_box[0],
+                                             "what": "sd_diarize: int16 PCM in pageable host memory, the 2 * n byte H2D copy and its buffer inside the timed call"}
+            # the same job without the HIP-event pairs the timed region carries around every launch (option profile = 1): what the events cost
+            tp = []
+            for _ in range(3):
+                gpu_sync()
+                t1 = time.perf_counter()
+                tq = d.diarize_dev(d_pcm.data_ptr(), n_total)
+                gpu_sync()
+                tp.append(time.perf_counter() - t1)
+            extra_lines["ms_per_step_without_kernel_events"] = {"ms": round(min(tp) * 1e3, 2), "value": round(audio_s / min(tp), 2), "same_turns": tq == turns_box[0],
+                                                                "what": "sd_diarize_dev with profile = 0, best of 3; the timed region above runs with profile = 1 because the roofline "
+                                                                        "object is measured live over it"}
+        # (the set-up's cold job: no work of its own, so a plain run reports it too)
         extra_lines["value_cold"] = {"value": round(audio_s / (cold_ms / 1e3), 2), "ms": round(cold_ms, 1),
                                      "parts_ms": {"sd_create": round((t_created - t_cold) * 1e3, 1), "pcm_upload": round((t_uploaded - t_created) * 1e3, 1),
                                                   "first_job": round(cold_ms - (t_uploaded - t_cold) * 1e3, 1),
@@ -834,7 +848,7 @@ def main():
         # the run).  A recording is only quoted when it was made with the very kernel source that is running now.
         traffic, traffic_src, mfma_util, recorded = None, None, None, None
         pmc_path = os.path.join(ROOT, "profiles", "pmc_conv_gemm_bench.json")
-        if world == 1 and a.precision == "f32" and os.path.exists(pmc_path):
+        if a.full and world == 1 and a.precision == "f32" and os.path.exists(pmc_path):
             try:
                 pj = json.load(open(pmc_path))
                 cur = "+".join(git_blob_sha1(os.path.join(PKG, "csrc", f)) for f in ("conv_gemm.hip", "conv_gemm_h.hip", "conv_narrow.hip"))
@@ -874,7 +888,7 @@ def main():
                        "cold_ms": round(cold_ms, 1),
                        "cold_ms_covers": "sd_create (weights -> HBM; fp16 weight forms only when their mode is selected), PCM upload, %sfirst job with cold workspaces (hipMalloc of ~28 GB of workspaces, first launches)" % ("RCCL communicator, " if use_dist else ""),
                        "single_job_ms": single_job_ms,
-                       "single_job_note": None if world == 1 else "one recording at a time (barrier after every job): infer + all-gather + finalize in series; `value` is the "
+                       "single_job_note": None if single_job_ms is None else "one recording at a time (barrier after every job): infer + all-gather + finalize in series; `value` is the "
                                           "pipelined rate of back-to-back jobs (rank 0 finalizes job k while the others infer job k+1)"},
             "roofline": {"bound": "mfma", "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s",
                          "frac": round(ach / peak, 4), "traffic": traffic, "traffic_source": traffic_src,
@@ -935,7 +949,7 @@ def main():
         if world > 1:
             out["multi_gpu_note"] = ("no N > 1 number has been measured by the builder: the container has no GPU and gpurun boxes have one; the RCCL path has run as a "
                                      "world of one and as `virtual_world` on one GPU, the control flow of this script at N = 8 / 8 h against a stand-in on CPUs "
-                                     "(tests/test_distributed_cpu.py).  `value` = N x %g h on N GPUs (weak); `strong_scaling_reading.value` = one hour on N GPUs." % a.hours_per_gpu)
+                                     "(tests/test_distributed_cpu.py).  `value` = N x %g h on N GPUs (weak); `strong_scaling_reading.value` (--full) = one hour on N GPUs." % a.hours_per_gpu)
     # ---- the strong-scaling leg runs LAST, behind the complete headline numbers and under a watchdog: it is the one part of an N > 1 run that no box
     # available to the builder could exercise with more than one real rank.  If it raises on a rank or does not finish in time, rank 0 still prints the
     # line (with the reason in place of the reading) and every rank leaves at once instead of waiting in a collective.

@@ -164,7 +164,7 @@ def test_bench_multi_rank_control_flow_dry_run():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     for n, extra in ((3, []), (2, ["--rank0-share", "0.25"])):
         out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--dry-run-control-plane", "--hours-per-gpu", "0.05",
-                              "--steps", "2", "--warmup", "1"] + extra, capture_output=True, text=True, timeout=300, env=env)
+                              "--steps", "2", "--warmup", "1", "--full"] + extra, capture_output=True, text=True, timeout=300, env=env)
         assert out.returncode == 0, out.stderr[-2000:]
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
         assert len(lines) == 1
@@ -177,6 +177,38 @@ def test_bench_multi_rank_control_flow_dry_run():
             assert "measured on a warm job" in j["config"]["rank0_share"]
         else:
             assert j["config"]["rank0_share"] is None and "[(0, 192), (192, 711)]" in j["config"]["sharding"]     # 25 % of 711 chunks, rounded to 32
+
+
+def test_bench_plain_run_leaves_every_extra_leg_to_full():
+    """a plain `bench.py` run is set-up, warm-up, the timed steps and the line: every leg that needs work of its own -- with N = 1 the host-PCM
+    entry, the job without kernel events and the raw workload, with N > 1 the single-job latency and the strong-scaling reading -- runs only
+    with --full, and the headline fields are the same with and without it (stand-in for the library, as above)"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    head = ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "scaling", "data")
+    for n in (1, 2):
+        lines = []
+        for full in ([], ["--full"]):
+            out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--dry-run-control-plane", "--hours-per-gpu", "0.05",
+                                  "--steps", "2", "--warmup", "1"] + full, capture_output=True, text=True, timeout=300, env=env)
+            assert out.returncode == 0, out.stderr[-2000:]
+            got = [l for l in out.stdout.splitlines() if l.startswith("{")]
+            assert len(got) == 1
+            lines.append(json.loads(got[0]))
+        plain, full = lines
+        assert all(plain[k] == full[k] for k in head) and plain["value"] > 0 and plain["ms_per_step"] > 0
+        assert plain["cpu_baseline"] is None and plain["workload_dependence"]["value_raw_workload"] is None
+        assert plain["roofline"]["recorded_pmc"] is None and plain["roofline"]["mfma_utilisation_pmc"] is None
+        if n == 1:
+            assert "value_host_pcm" not in plain and "ms_per_step_without_kernel_events" not in plain and plain["value_cold"]["ms"] > 0
+            assert full["value_host_pcm"]["same_turns"] is True and full["ms_per_step_without_kernel_events"]["same_turns"] is True
+            assert full["workload_dependence"]["value_raw_workload"]["steps"] == 3
+        else:
+            assert plain["config"]["single_job_ms"] is None and plain["config"]["single_job_note"] is None and plain["strong_scaling_reading"] is None
+            assert full["config"]["single_job_ms"] > 0 and full["strong_scaling_reading"]["value"] > 0
 
 
 def test_bench_eight_rank_control_flow_at_the_eight_hour_size():
@@ -192,7 +224,7 @@ def test_bench_eight_rank_control_flow_at_the_eight_hour_size():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     t0 = time.time()
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--dry-run-control-plane", "--steps", "2", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--dry-run-control-plane", "--steps", "2", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=1500, env=env)
     wall = time.time() - t0
     assert out.returncode == 0, out.stderr[-2000:]
@@ -219,7 +251,7 @@ def test_bench_prints_its_line_even_if_the_strong_scaling_leg_cannot_finish():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run-control-plane", "--hours-per-gpu", "0.05", "--steps", "1", "--warmup", "0",
-                          "--strong-timeout", "0"], capture_output=True, text=True, timeout=300, env=env)
+                          "--full", "--strong-timeout", "0"], capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

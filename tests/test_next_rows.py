@@ -538,9 +538,10 @@ def test_sharded_entry_point_through_rccl_world_of_one(diarizer):
 def test_bench_line_contract_on_a_short_job():
     """the driver's contract for bench.py, on a 3-minute job: ONE JSON line with metric / value / unit / n_gpus / steps / warmup / ms_per_step /
     higher_is_better / scaling / vs_baseline / dtype / data / config.workload, a `roofline` object for the dominant kernel measured with HIP
-    events on the library's stream and a `cpu_baseline` object timed on this box's host cores; plus this round's additions"""
+    events on the library's stream and a `cpu_baseline` object timed on this box's host cores; plus this round's additions (the legs beyond the
+    headline run with --full)"""
     import json
-    out, _ = _run_bench(["--steps", "2", "--warmup", "1", "--hours-per-gpu", "0.05", "--cpu-seconds", "10", "--fp16-steps", "1", "--x3-steps", "1"], 600)
+    out, _ = _run_bench(["--full", "--steps", "2", "--warmup", "1", "--hours-per-gpu", "0.05", "--cpu-seconds", "10", "--fp16-steps", "1", "--x3-steps", "1"], 600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and out.stdout.strip().endswith(lines[0])
@@ -572,7 +573,7 @@ def test_bench_strong_scaling_leg_through_rccl_world_of_one():
     is run the only way it can be with the real library: `--force-dist` on one GPU -- RCCL communicator of one rank, a SECOND recording length (the
     leg's shorter job) through the same context and communicator, planted outputs re-pointed and restored.  Both jobs must give their known turns."""
     import json
-    out, _ = _run_bench(["--force-dist", "--hours-per-gpu", "0.1", "--steps", "1", "--warmup", "0", "--cpu-seconds", "0", "--fp16-steps", "0", "--x3-steps", "0",
+    out, _ = _run_bench(["--full", "--force-dist", "--hours-per-gpu", "0.1", "--steps", "1", "--warmup", "0", "--cpu-seconds", "0", "--fp16-steps", "0", "--x3-steps", "0",
                          "--strong-steps", "2"], 900)
     assert out.returncode == 0, out.stderr[-2000:]
     j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])

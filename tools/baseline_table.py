@@ -68,7 +68,7 @@ out["gpu_1min_wav_cli"] = {"process_wall_s": round(wall, 2), "time_cost_line": c
                            "turns": sum(1 for l in r.stdout.splitlines() if "--> Speaker_" in l)}
 print(json.dumps(out["gpu_1min_wav_cli"]), flush=True)
 for name, args in [("gpu_10min", ["--hours-per-gpu", str(600 / 3600.0)]), ("gpu_1h", []), ("gpu_1h_fp16", ["--precision", "f16"])]:
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--cpu-seconds", "0"] + args, capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup", "1", "--cpu-seconds", "0"] + args, capture_output=True, text=True)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     j = json.loads(line[-1]) if line else {"error": r.stderr[-500:]}
     out[name] = j
