@@ -542,7 +542,7 @@ __global__ __launch_bounds__(MWT_MAX) void k_linkage_mw(double* D, int n, int* s
         __shared__ int s_ticket;
         if (tid == 0) {
             const unsigned xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));       // HW_REG_XCC_ID[3:0]
-            s_ticket = (xcc == 0) ? (int)atomicAdd(&sync[6], 1u) : -1;
+            s_ticket = (xcc == 0) ? (int)atomicAdd(&sync[SYNC_TICKET], 1u) : -1;
         }
         __syncthreads();
         g = s_ticket;
@@ -571,7 +571,7 @@ __global__ __launch_bounds__(MWT_MAX) void k_linkage_mw(double* D, int n, int* s
             while ((unsigned)(v >> 32) != bar) {
                 __builtin_amdgcn_s_sleep(1);
                 v = LDG(p);
-                if (++spins > (1u << 24)) { sync[1] = 1; ok = false; break; }     // ~seconds: never in a healthy run
+                if (++spins > (1u << 24)) { sync[SYNC_TIMEOUT] = 1; ok = false; break; }     // ~seconds: never in a healthy run
             }
             s_words[sl][wd] = (unsigned)v;
         }
@@ -823,7 +823,7 @@ __global__ __launch_bounds__(MWT_MAX) void k_linkage_mw(double* D, int n, int* s
     // run_linkage repeats the job with k_linkage_heap, which owns the reference's tie order
     auto tie_stop = [&](int flags) -> bool {
         if (!(flags & CAND_TIE)) return false;
-        if (g == 0 && tid == 0) sync[5] = 1;
+        if (g == 0 && tid == 0) sync[SYNC_TIE] = 1;
         return true;
     };
 
@@ -831,7 +831,7 @@ __global__ __launch_bounds__(MWT_MAX) void k_linkage_mw(double* D, int n, int* s
         // ---- lazy validation (cl.cpp:323-339): cooperative refresh of the KR best stale candidates per round
         for (int guard = 0; guard <= n - k; ++guard) {
             if (fresh && y >= 0) break;
-            if (g == 0 && tid == 0) sync[2] += 1;            // diagnostic: retry rounds
+            if (g == 0 && tid == 0) sync[SYNC_ROUNDS] += 1;            // diagnostic: retry rounds
             const int nL = s_nL[lp]; const int* L = s_L[lp];
             scan_rows(nL, L, s_row);
             Cand m = local_argmin(nL, L);
@@ -953,7 +953,7 @@ __global__ __launch_bounds__(MWT_MAX) void k_linkage_mw(double* D, int n, int* s
         if (!consume(11)) return;
         digest(0, s_L[lp], y, true);
         par ^= 1;
-        if (d_rowtie) { if (g == 0 && tid == 0) sync[5] = 1; return; }
+        if (d_rowtie) { if (g == 0 && tid == 0) sync[SYNC_TIE] = 1; return; }
         best = d_best;
         const Min2 nn = d_nn;
         // row y: exact by construction when it has an active neighbour above (cl.cpp:395-404), else its old (stale) bound
@@ -990,47 +990,6 @@ __global__ void k_fill_i32(int* p, int v, int64_t n, int iota)
     if (i < n) p[i] = iota ? (int)i : v;
 }
 
-// X[N][d] (rows as given; Clustering::linkage does not normalise) -> Z[N-1][4] on the device
-//   N < 1500 (or option linkage_wgs = 0): k_linkage_heap, the reference's algorithm heap included.
-//   above: k_linkage_mw on G co-resident workgroups (cooperative launch: the runtime guarantees residency or refuses).  It
-//   takes a merge from its parallel arg-min only while the closest pair is unique; at the first exact tie (duplicate
-//   embeddings), on a refused launch or on a poll timeout the distance matrix is rebuilt and k_linkage_heap does the job.
-static int linkage_prepare(sd_ctx* c, const double* d_X, int64_t N, int d, double* D, int* size, int* cid, int* nb, double* md, double* md2, bool square = false)
-{
-    const int64_t m = N * (N - 1) / 2;
-    const int tiles = (int)((N + PT - 1) / PT);
-    {
-        ProfScope ps(c, "pdist", (double)m * d * 3.0, (double)m * 8.0 * (square ? 2 : 1) + (double)N * d * 8.0);
-        if (square) hipLaunchKernelGGL(k_pdist_sq, dim3(tiles, tiles), dim3(256), 0, c->stream, d_X, N, d, D);
-        else hipLaunchKernelGGL(k_pdist, dim3(tiles, tiles), dim3(256), 0, c->stream, d_X, N, d, D);
-        KCHECK(c);
-    }
-    hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, size, 1, N, 0);
-    hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, cid, 0, N, 1);
-    KCHECK(c);
-    {
-        ProfScope ps(c, "row_nn", 0, (double)m * 8.0);
-        hipLaunchKernelGGL(k_row_nn, dim3((unsigned)((N - 1 + 3) / 4)), dim3(256), 0, c->stream, D, N, nb, md, md2, square ? 1 : 0);
-        KCHECK(c);
-    }
-    return SD_OK;
-}
-
-static int linkage_heap(sd_ctx* c, int64_t N, double* D, int* size, int* cid, int* nb, double* md, double* d_Z)
-{
-    double* hval = nullptr; int* hkey = nullptr; int* hpos = nullptr;
-    if (N - 1 > HEAP_LDS) {
-        WS(c, double, hv, "cl_hval", N);
-        WS(c, int, hk, "cl_hkey", N);
-        WS(c, int, hp, "cl_hpos", N);
-        hval = hv; hkey = hk; hpos = hp;
-    }
-    ProfScope ps(c, "linkage_heap", 0, 24.0 * (double)N * (double)N);
-    hipLaunchKernelGGL(k_linkage_heap, dim3(1), dim3(LT), (size_t)((N + 31) / 32) * sizeof(unsigned), c->stream, D, (int)N, size, cid, nb, md, d_Z, hval, hkey, hpos);
-    KCHECK(c);
-    return SD_OK;
-}
-
 // per-workgroup private copies for k_linkage_mw: [G][n] sizes (all 1); square form: [G][2 n] = sizes (1) followed by ty (-1)
 __global__ void k_fill_size_ty(int* p, int64_t n, int64_t total, int with_ty)
 {
@@ -1038,27 +997,24 @@ __global__ void k_fill_size_ty(int* p, int64_t n, int64_t total, int with_ty)
     if (i < total) p[i] = (with_ty && ((i / n) & 1)) ? -1 : 1;
 }
 
-// linkage_rg.hip
-bool linkage_rg_fits(int64_t N, int G, int TH);
-hipError_t linkage_rg_launch(sd_ctx* c, bool onex, int G, int TH, double* D, int n, int* cid, const int* nb, const double* md, const double* md2,
-                             double* Z, MwGran* gran, unsigned* sync, int cap, int helper, int k0 = 0, const int* sz0 = nullptr, const int* ty0 = nullptr);
-int linkage_rg_slot_granules();
-// linkage_hx.hip
-bool linkage_hx_fits(int64_t N, int workers);
-int linkage_hx_run(sd_ctx* c, bool onex, int workers, double* D, int64_t N, int* cid, int* size, int* tyv, int* nb, double* md, double* d_Z, bool* stopped,
-                   double stop_above = (double)INFINITY, int64_t* merges_done = nullptr, bool* launched = nullptr);
-
-int run_linkage(sd_ctx* c, const double* d_X, int64_t N, int d, double* d_Z)
+// ---------------------------------------------------------------- run_linkage: the plan, then its steps
+// X[N][d] (rows as given; Clustering::linkage does not normalise) -> Z[N-1][4] on the device
+//   N < 1500 (or option linkage_wgs = 0): k_linkage_heap, the reference's algorithm heap included.
+//   above: k_linkage_rg / k_linkage_mw on G co-resident workgroups (cooperative launch: the runtime guarantees residency or refuses).  They
+//   take a merge from their parallel arg-min only while the closest pair is unique; at the first exact tie (duplicate embeddings), on a
+//   refused launch or on a poll timeout the heap replay k_linkage_hx takes the job (a tie at height 0: only up to the first merge above 0,
+//   then k_linkage_rg goes on), and k_linkage_heap where that cannot run.
+//
+// Geometry of one job, computed once from the size, the device and the linkage_* options.  The one input that is not arithmetic: whether the square
+// matrix could be allocated (`square_ok` = false: the job takes the condensed form).  G <= 1: the one-workgroup heap kernel, the other fields unused.
+struct LinkagePlan {
+    int G, TH, cap, slot_gran;          // cooperative workgroups, threads of each, rows a workgroup owns + 1, granules of a slot
+    bool square, use_rg, onex;          // full N x N matrix; k_linkage_rg (else k_linkage_mw); one XCD first
+    bool replay, hx_onex; int workers;  // a tie can go to k_linkage_hx (square matrix, option linkage_tie_kernel, a geometry that fits): one XCD first, worker workgroups
+};
+static LinkagePlan linkage_plan(const sd_ctx* c, int64_t N, bool square_ok)
 {
-    if (N < 2) return SD_OK;
-    const int64_t m = N * (N - 1) / 2;
-    if (N > 0x7fffffff / 4 || (double)m * 8.0 > 230e9) SD_FAIL(c, SD_ERR_ARG, "linkage: N=%lld needs a %.0f GB condensed matrix (limit 230 GB)", (long long)N, (double)m * 8e-9);
-    WS(c, int, size, "cl_size", N);
-    WS(c, int, cid, "cl_cid", N);
-    WS(c, int, nb, "cl_nb", N);
-    WS(c, double, md, "cl_md", N);
-    WS(c, double, md2, "cl_md2", N);
-    int rc;
+    LinkagePlan p = {};
     int G = (int)c->linkage_wgs;
     // auto geometry (measured on clustered data, profiles/r01_linkage_scaling.txt, r02_linkage_stamps.txt, r03_linkage_*.txt): up to N = 30 000
     // the one-XCD form with one workgroup on each of the XCD's 32 CUs; above, all XCDs
@@ -1074,19 +1030,10 @@ int run_linkage(sd_ctx* c, const double* d_X, int64_t N, int d, double* d_Z)
     // one XCD, larger N: 512 threads (N = 18 867: 121 ms against 126; N = 25 274: 170 against 179; N = 50 158: 384 against 465)
     if (TH <= 0) TH = auto_onex ? (N >= 16000 ? 512 : 256) : N >= 8000 ? 512 : 256;
     TH = TH >= 1024 ? 1024 : TH >= 512 ? 512 : TH >= 256 ? 256 : 128;      // (not below 128: the kernels fill their G <= 128 candidate slots with `tid < G`)
-    if (G <= 1) {
-        WS(c, double, D, "cl_D", m);
-        if ((rc = linkage_prepare(c, d_X, N, d, D, size, cid, nb, md, md2))) return rc;
-        return linkage_heap(c, N, D, size, cid, nb, md, d_Z);
-    }
+    p.G = G; p.TH = TH;
+    if (G <= 1) return p;
     // square form (full N x N matrix, row-only bulk accesses) while the square fits beside everything else; the condensed form above that
-    bool square = c->linkage_square < 0 ? (double)N * (double)N * 8.0 <= 170e9 : c->linkage_square != 0;
-    double* D = nullptr;
-    if (square) {
-        D = ws_get<double>(c, "cl_Dsq", (size_t)N * N);
-        if (!D) { (void)hipGetLastError(); square = false; c->stats["linkage_square_alloc_failed"].launches += 1; }      // no room for the square: the condensed form needs half
-    }
-    if (!square) { WS(c, double, Dc, "cl_D", m); D = Dc; }
+    const bool square = square_ok && (c->linkage_square < 0 ? (double)N * (double)N * 8.0 <= 170e9 : c->linkage_square != 0);
     // k_linkage_rg's own automatic geometry (r05, planted embeddings, 256 threads; profiles/r05_linkage_rg.txt): one XCD with 32 workgroups only while a thread
     // has one or two columns -- N = 12 602: 72.7 ms with 32 (one XCD), 72.6 with 64 (all XCDs); N = 18 867: 127.7 / 120.0; N = 25 274: 179.1 / 165.2 (128: 169.1;
     // k_linkage_mw 170.2); N = 50 158: 462.8 / 372.8 (128: 366.3; k_linkage_mw 381.8); N = 100 174: 128 workgroups 819 ms (64: 875; k_linkage_mw 996)
@@ -1095,11 +1042,8 @@ int run_linkage(sd_ctx* c, const double* d_X, int64_t N, int d, double* d_Z)
         if (G > c->num_cu) G = c->num_cu;
     }
     if ((N + G - 1) / G > 3400) G = (int)((N + 3399) / 3400);      // active-row lists and bounds live in LDS: 32 B per owned row (109 KB + 43 KB static)
-    if (G > c->num_cu || G > MWT) SD_FAIL(c, SD_ERR_ARG, "linkage: N=%lld needs %d cooperative workgroups", (long long)N, G);
-    int cap = (int)((N + G - 1) / G) + 1;
-    if ((rc = linkage_prepare(c, d_X, N, d, D, size, cid, nb, md, md2, square))) return rc;
     // one-XCD form while two workgroups per CU of one XCD (32 CUs) can hold the job; above, all XCDs' memory pipelines are worth more
-    bool onex = c->linkage_one_xcd != 0 && G <= 32 && c->num_cu >= 256;
+    const bool onex = c->linkage_one_xcd != 0 && G <= 32 && c->num_cu >= 256;
     // square form: k_linkage_rg (register state, sizes / ty in the slots) where its geometry fits -- at most 4 columns per thread -- else k_linkage_mw
     bool use_rg = square && c->linkage_kernel != 0;
     // measured (r05, planted embeddings): N = 12 602, one XCD, 32 workgroups: 256 threads 72.7 ms, 512 threads 81.2, 128 threads 76.6 (k_linkage_mw 76.7);
@@ -1110,159 +1054,249 @@ int run_linkage(sd_ctx* c, const double* d_X, int64_t N, int d, double* d_Z)
         while (t2 < 1024 && !linkage_rg_fits(N, G, t2)) t2 *= 2;
         if (linkage_rg_fits(N, G, t2) && (c->linkage_threads <= 0 || c->linkage_kernel > 0)) TH = t2; else use_rg = false;
     }
-    const int slot_gran = use_rg ? linkage_rg_slot_granules() : SLOT_WORDS;
-    WS(c, MwGran, gran, "cl_gran", (int64_t)2 * G * slot_gran);
-    HIPCHK(c, hipMemsetAsync(gran, 0, (size_t)2 * G * slot_gran * sizeof(MwGran), c->stream));
-    int* size_all = nullptr;
-    if (!use_rg) {
-        const int64_t priv = (int64_t)G * N * (square ? 2 : 1);
-        WS(c, int, sa, "cl_size_all", priv);
-        size_all = sa;
-        hipLaunchKernelGGL(k_fill_size_ty, dim3((unsigned)((priv + 255) / 256)), dim3(256), 0, c->stream, size_all, N, priv, square ? 1 : 0);
-        KCHECK(c);
-    }
-    WS(c, unsigned, sync, "cl_sync", 32 + 16 * 256);
-    HIPCHK(c, hipMemsetAsync(sync, 0, (32 + 16 * 256) * sizeof(unsigned), c->stream));
-    const char* why = nullptr;
-    bool launch_refused = false;
-    if (c->linkage_force_heap) why = "forced (option linkage_force_heap)";
-    else {
-        ProfScope ps(c, "linkage", 0, 24.0 * (double)N * (double)N);
-        int n_i = (int)N;
-        void* args[] = {&D, &n_i, &size_all, &cid, &nb, &md, &md2, &d_Z, &gran, &sync, &cap, &G};
-        // cooperative launch: all workgroups are resident together, or the launch is refused (they poll each other's slots)
-        hipError_t le = hipErrorUnknown;
-        const void* f_one = square ? (const void*)k_linkage_mw<true, true> : (const void*)k_linkage_mw<true, false>;
-        const void* f_all = square ? (const void*)k_linkage_mw<false, true> : (const void*)k_linkage_mw<false, false>;
-        if ((size_t)cap * 32 > 48 * 1024) {          // the row lists of a hand-set geometry may pass the default dynamic-LDS limit
-            (void)hipFuncSetAttribute(f_one, hipFuncAttributeMaxDynamicSharedMemorySize, cap * 32);
-            (void)hipFuncSetAttribute(f_all, hipFuncAttributeMaxDynamicSharedMemorySize, cap * 32);
-            (void)hipGetLastError();
-        }
-        if (use_rg) {
-            // "has the kernel written anything?" is read from Z itself: row 0 is zeroed here and written (size field >= 2) right behind the first merge's
-            // stores into D, before any later exit (linkage_rg.hip: write_Z follows the column pass, the row-tie check comes behind it).  Round 5 kept a
-            // merge counter in sync[28] instead; those two stores in the kernel's exit paths changed its register allocation and cost 9 ms per hour
-            // (profiles/r06_linkage_ab.txt: 76.2 -> 85.7 ms on one box, one process, interleaved).
-            HIPCHK(c, hipMemsetAsync(d_Z, 0, 4 * sizeof(double), c->stream));
-            if (onex) {
-                le = linkage_rg_launch(c, true, G, TH, D, n_i, cid, nb, md, md2, d_Z, gran, sync, cap, (int)c->linkage_prefetch);
-                if (le != hipSuccess) { (void)hipGetLastError(); onex = false; }
-            }
-            if (!onex) le = linkage_rg_launch(c, false, G, TH, D, n_i, cid, nb, md, md2, d_Z, gran, sync, cap, (int)c->linkage_prefetch);
-            c->stats["linkage_rg_launches"].launches += 1;
-        } else {
-        if (onex) {
-            le = hipLaunchCooperativeKernel(f_one, dim3(8 * G), dim3(TH), args, (size_t)cap * 32, c->stream);
-            if (le != hipSuccess) { (void)hipGetLastError(); onex = false; }
-        }
-        if (!onex) le = hipLaunchCooperativeKernel(f_all, dim3(G), dim3(TH), args, (size_t)cap * 32, c->stream);
-        }
-        if (le != hipSuccess) { (void)hipGetLastError(); why = "cooperative launch refused"; launch_refused = true; }
-    }
-    unsigned h[32] = {0};
-    if (!why) {
-        HIPCHK(c, hipMemcpyAsync(h, sync, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->stats["linkage_retry_rounds"].flops += (double)h[2];
-        if (h[1] && onex) {
-            // too few workgroups found themselves on XCC 0 (dispatch not round-robin?): never again in this context; the
-            // multi-XCD form does the job (the distance matrix is rebuilt by the recursive call)
-            c->linkage_one_xcd = 0;
-            c->stats["linkage_one_xcd_timeouts"].launches += 1;
-            return run_linkage(c, d_X, N, d, d_Z);
-        }
-        if (h[1]) why = "slot poll timed out";
-        else if (h[5]) { why = "exact tie"; c->stats["linkage_tie_fallbacks"].launches += 1; }
-    }
-    if (!why) return SD_OK;
-    c->stats["linkage_fallbacks"].launches += 1;
-    if (c->profile_detail) fprintf(stderr, "linkage: %s at N = %lld -> heap replay\n", why, (long long)N);
-    // the reference's heap replayed with the row work spread over worker workgroups (k_linkage_hx) on the square matrix, where it fits
-    // matrix, bounds and ids are still as linkage_prepare left them when nothing ran (forced replay, refused launch) or k_linkage_rg stopped in front of its
-    // first merge (Z's row 0, zeroed before the launch, is still zero; with two pairs of duplicates: always): the replay starts from them, no second pdist
-    bool untouched = c->linkage_force_heap != 0 || launch_refused;
-    if (!untouched && use_rg && h[5] && !h[1]) {
-        double z03 = 1.0;
-        HIPCHK(c, hipMemcpy(&z03, d_Z + 3, sizeof(double), hipMemcpyDeviceToHost));
-        untouched = z03 == 0.0;
-    }
+    p.G = G; p.TH = TH; p.cap = (int)((N + G - 1) / G) + 1;
+    p.square = square; p.use_rg = use_rg; p.onex = onex;
+    p.slot_gran = use_rg ? linkage_rg_slot_granules() : SLOT_WORDS;
     if (square && c->linkage_tie_kernel != 0) {
         bool hx_onex = c->linkage_one_xcd != 0 && c->num_cu >= 256 && linkage_hx_fits(N, 31);
         int workers = hx_onex ? 31 : (N >= 60000 ? 127 : 63);
         if (c->linkage_tie_kernel > 1) { workers = (int)c->linkage_tie_kernel; hx_onex = hx_onex && workers <= 31; }
         if (workers + 1 > c->num_cu) workers = c->num_cu - 1;
-        if (linkage_hx_fits(N, workers)) {
-            WS(c, int, tyv, "cl_ty", N);
-            // Ties at height 0 -- rows that occur twice, the usual reason for a tie -- end once the duplicates are merged.  The replay takes the merges at
-            // height 0 only, and k_linkage_rg continues from that state (exact bounds of the rows still there from k_row_nn_mid); a later tie sends the whole
-            // job through the replay, as before.  (Both kernels produce the reference's sequence: the replay always, k_linkage_rg while the closest pair is unique.)
-            double tie_h = 0.0;
-            { unsigned long long b = ((unsigned long long)h[27] << 32) | h[26]; memcpy(&tie_h, &b, 8); }
-            if (use_rg && h[5] && !h[1] && tie_h == 0.0 && c->linkage_zero_phase != 0) {
-                bool z_onex = hx_onex; int z_workers = workers;
-                for (int attempt = 0; attempt < 2; ++attempt) {
-                    if (!untouched && (rc = linkage_prepare(c, d_X, N, d, D, size, cid, nb, md, md2, true))) return rc;
-                    untouched = false;
-                    hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, tyv, -1, N, 0);
-                    KCHECK(c);
-                    bool stopped = false, launched = false; int64_t k_done = 0;
-                    if ((rc = linkage_hx_run(c, z_onex, z_workers, D, N, cid, size, tyv, nb, md, d_Z, &stopped, 0.0, &k_done, &launched))) return rc;
-                    if (!launched) untouched = true;      // a refused launch has not touched matrix, bounds or ids: the next attempt needs no second pdist
-                    if (stopped) {
-                        if (!z_onex) break;
-                        z_onex = false; z_workers = N >= 60000 ? 127 : 63;
-                        if (!linkage_hx_fits(N, z_workers)) break;
-                        continue;
-                    }
-                    c->stats["linkage_zero_phase_merges"].flops += (double)k_done;
-                    if (k_done >= N - 1) { c->stats["linkage_hx_jobs"].launches += 1; return SD_OK; }
-                    if (k_done == 0) break;
-                    {
-                        ProfScope ps(c, "row_nn", 0, (double)m * 8.0);
-                        hipLaunchKernelGGL(k_row_nn_mid, dim3((unsigned)((N - 1 + 3) / 4)), dim3(256), 0, c->stream, D, N, size, tyv, nb, md, md2);
-                        KCHECK(c);
-                    }
-                    HIPCHK(c, hipMemsetAsync(gran, 0, (size_t)2 * G * slot_gran * sizeof(MwGran), c->stream));
-                    HIPCHK(c, hipMemsetAsync(sync, 0, (32 + 16 * 256) * sizeof(unsigned), c->stream));
-                    hipError_t le;
-                    {
-                        ProfScope ps(c, "linkage", 0, 24.0 * (double)N * (double)N);
-                        le = linkage_rg_launch(c, onex, G, TH, D, (int)N, cid, nb, md, md2, d_Z, gran, sync, cap, (int)c->linkage_prefetch, (int)k_done, size, tyv);
-                        c->stats["linkage_rg_launches"].launches += 1;
-                    }
-                    if (le != hipSuccess) { (void)hipGetLastError(); break; }
-                    unsigned h2[32] = {0};
-                    HIPCHK(c, hipMemcpyAsync(h2, sync, sizeof(h2), hipMemcpyDeviceToHost, c->stream));
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    if (!h2[1] && !h2[5]) { c->stats["linkage_zero_phase_jobs"].launches += 1; return SD_OK; }
-                    if (c->profile_detail) fprintf(stderr, "linkage: zero phase (%lld merges), then %s -> whole replay\n", (long long)k_done, h2[5] ? "another tie" : "a poll timeout");
-                    break;
-                }
-            }
-            for (int attempt = 0; attempt < 2; ++attempt) {
-                if (!untouched && (rc = linkage_prepare(c, d_X, N, d, D, size, cid, nb, md, md2, true))) return rc;
-                untouched = false;
-                hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, tyv, -1, N, 0);
-                KCHECK(c);
-                bool stopped = false, launched = false;
-                if ((rc = linkage_hx_run(c, hx_onex, workers, D, N, cid, size, tyv, nb, md, d_Z, &stopped, (double)INFINITY, nullptr, &launched))) return rc;
-                if (!launched) { untouched = true; c->stats["linkage_hx_refused"].launches += 1; }
-                if (!stopped) { c->stats["linkage_hx_jobs"].launches += 1; return SD_OK; }
-                if (!hx_onex) break;
-                hx_onex = false;                 // one XCD refused or too few workgroups arrived there: all XCDs
-                workers = N >= 60000 ? 127 : 63;
-                if (!linkage_hx_fits(N, workers)) break;
-            }
-            c->stats["linkage_hx_failed"].launches += 1;
-        }
+        p.replay = linkage_hx_fits(N, workers); p.workers = workers; p.hx_onex = hx_onex;
     }
-    // the heap kernel works on the condensed matrix; the square one (up to 170 GB) is given back first, so that the fallback -- exact
+    return p;
+}
+
+// how the cooperative attempt ended
+enum CoopEnd { COOP_DONE, COOP_TIE, COOP_TIMEOUT, COOP_REFUSED, COOP_ONEX_TIMEOUT };
+struct CoopOutcome {
+    CoopEnd end;
+    bool onex;              // the form that ran: one XCD, or -- where that launch was refused -- all
+    double tie_h;           // COOP_TIE of k_linkage_rg: the height of the tie
+    bool untouched;         // matrix, bounds and ids are still as prepare() left them
+};
+
+// one job with its plan and its workspaces; the steps of run_linkage
+struct LinkageJob {
+    sd_ctx* c; const double* d_X; int64_t N; int d; double* d_Z;
+    LinkagePlan p;
+    int* size; int* cid; int* nb; double* md; double* md2;
+    double* D; MwGran* gran; unsigned* sync; int* size_all; int* tyv;
+
+    // distance matrix (condensed or square) into Dm, sizes = 1, ids = iota, exact nearest neighbours above each row
+    int prepare(double* Dm, bool square)
+    {
+        const int64_t m = N * (N - 1) / 2;
+        const int tiles = (int)((N + PT - 1) / PT);
+        {
+            ProfScope ps(c, "pdist", (double)m * d * 3.0, (double)m * 8.0 * (square ? 2 : 1) + (double)N * d * 8.0);
+            if (square) hipLaunchKernelGGL(k_pdist_sq, dim3(tiles, tiles), dim3(256), 0, c->stream, d_X, N, d, Dm);
+            else hipLaunchKernelGGL(k_pdist, dim3(tiles, tiles), dim3(256), 0, c->stream, d_X, N, d, Dm);
+            KCHECK(c);
+        }
+        hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, size, 1, N, 0);
+        hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, cid, 0, N, 1);
+        KCHECK(c);
+        ProfScope ps(c, "row_nn", 0, (double)m * 8.0);
+        hipLaunchKernelGGL(k_row_nn, dim3((unsigned)((N - 1 + 3) / 4)), dim3(256), 0, c->stream, Dm, N, nb, md, md2, square ? 1 : 0);
+        KCHECK(c);
+        return SD_OK;
+    }
+
+    // k_linkage_rg or k_linkage_mw on the plan's geometry: one XCD first where the plan says so, then all.  `o` comes in as "refused, nothing touched".
+    int coop(CoopOutcome& o)
+    {
+        {
+            ProfScope ps(c, "linkage", 0, 24.0 * (double)N * (double)N);
+            int n_i = (int)N;
+            void* args[] = {&D, &n_i, &size_all, &cid, &nb, &md, &md2, &d_Z, &gran, &sync, &p.cap, &p.G};
+            const void* f_one = p.square ? (const void*)k_linkage_mw<true, true> : (const void*)k_linkage_mw<true, false>;
+            const void* f_all = p.square ? (const void*)k_linkage_mw<false, true> : (const void*)k_linkage_mw<false, false>;
+            if ((size_t)p.cap * 32 > 48 * 1024) {          // the row lists of a hand-set geometry may pass the default dynamic-LDS limit
+                (void)hipFuncSetAttribute(f_one, hipFuncAttributeMaxDynamicSharedMemorySize, p.cap * 32);
+                (void)hipFuncSetAttribute(f_all, hipFuncAttributeMaxDynamicSharedMemorySize, p.cap * 32);
+                (void)hipGetLastError();
+            }
+            // "has the kernel written anything?" is read from Z itself: row 0 is zeroed here and written (size field >= 2) right behind the first merge's
+            // stores into D, before any later exit (linkage_rg.hip: write_Z follows the column pass, the row-tie check comes behind it).  Round 5 kept a
+            // merge counter in a sync word of its own instead; those two stores in the kernel's exit paths changed its register allocation and cost 9 ms per hour
+            // (profiles/r06_linkage_ab.txt: 76.2 -> 85.7 ms on one box, one process, interleaved).
+            if (p.use_rg) HIPCHK(c, hipMemsetAsync(d_Z, 0, 4 * sizeof(double), c->stream));
+            // cooperative launch: all workgroups are resident together, or the launch is refused (they poll each other's slots)
+            auto launch = [&](bool onex) {
+                return p.use_rg ? linkage_rg_launch(c, onex, p.G, p.TH, D, n_i, cid, nb, md, md2, d_Z, gran, sync, p.cap, (int)c->linkage_prefetch)
+                                : hipLaunchCooperativeKernel(onex ? f_one : f_all, dim3(onex ? 8 * p.G : p.G), dim3(p.TH), args, (size_t)p.cap * 32, c->stream);
+            };
+            hipError_t le = o.onex ? launch(true) : hipErrorUnknown;
+            if (o.onex && le != hipSuccess) { (void)hipGetLastError(); o.onex = false; }
+            if (!o.onex) le = launch(false);
+            if (p.use_rg) c->stats["linkage_rg_launches"].launches += 1;
+            if (le != hipSuccess) { (void)hipGetLastError(); return SD_OK; }
+        }
+        unsigned h[SYNC_HOST_WORDS] = {0};
+        HIPCHK(c, hipMemcpyAsync(h, sync, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->stats["linkage_retry_rounds"].flops += (double)h[SYNC_ROUNDS];
+        o.untouched = false;
+        o.end = h[SYNC_TIMEOUT] ? (o.onex ? COOP_ONEX_TIMEOUT : COOP_TIMEOUT) : h[SYNC_TIE] ? COOP_TIE : COOP_DONE;
+        if (o.end == COOP_TIE && p.use_rg) {      // stopped in front of its first merge (with two pairs of duplicates: always)?  Z's row 0, zeroed before the launch, is still zero
+            double z03 = 1.0;
+            HIPCHK(c, hipMemcpy(&z03, d_Z + 3, sizeof(double), hipMemcpyDeviceToHost));
+            o.untouched = z03 == 0.0;
+            const unsigned long long b = ((unsigned long long)h[SYNC_TIE_HI] << 32) | h[SYNC_TIE_LO];
+            memcpy(&o.tie_h, &b, 8);
+        }
+        return SD_OK;
+    }
+
+    // The reference's heap replayed with the row work spread over worker workgroups (k_linkage_hx) on the square matrix, up to the first merge above
+    // `stop_above`: one XCD first where the plan says so; refused there, or too few workgroups arrived: all XCDs, once.  *ran = false: stopped both times.
+    // `untouched` (matrix, bounds and ids as prepare() left them: no second pdist) is consumed and kept up to date for the caller's next step.
+    int replay(double stop_above, bool& untouched, bool* ran, int64_t* merges)
+    {
+        bool hx_onex = p.hx_onex; int workers = p.workers;
+        *ran = false;
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            if (int rc = untouched ? SD_OK : prepare(D, true)) return rc;
+            untouched = false;
+            hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, tyv, -1, N, 0);
+            KCHECK(c);
+            bool stopped = false, launched = false;
+            if (int rc = linkage_hx_run(c, hx_onex, workers, D, N, cid, size, tyv, nb, md, d_Z, &stopped, stop_above, merges, &launched)) return rc;
+            if (!launched) { untouched = true; c->stats["linkage_hx_refused"].launches += 1; }      // a refused launch has not touched matrix, bounds or ids
+            if (!stopped) { *ran = true; return SD_OK; }
+            if (!hx_onex) break;
+            hx_onex = false;                 // one XCD refused or too few workgroups arrived there: all XCDs
+            workers = N >= 60000 ? 127 : 63;
+            if (!linkage_hx_fits(N, workers)) break;
+        }
+        return SD_OK;
+    }
+
+    // after a zero phase of k_done merges: exact bounds of the rows still there (k_row_nn_mid), then k_linkage_rg continues from that state on the form the
+    // first attempt ran on.  *done = false: refused, another tie or a poll timeout -- the whole replay takes the job.
+    int continue_rg(bool onex, int64_t k_done, bool* done)
+    {
+        *done = false;
+        {
+            ProfScope ps(c, "row_nn", 0, (double)(N * (N - 1) / 2) * 8.0);
+            hipLaunchKernelGGL(k_row_nn_mid, dim3((unsigned)((N - 1 + 3) / 4)), dim3(256), 0, c->stream, D, N, size, tyv, nb, md, md2);
+            KCHECK(c);
+        }
+        HIPCHK(c, hipMemsetAsync(gran, 0, (size_t)2 * p.G * p.slot_gran * sizeof(MwGran), c->stream));
+        HIPCHK(c, hipMemsetAsync(sync, 0, SYNC_WORDS * sizeof(unsigned), c->stream));
+        hipError_t le;
+        {
+            ProfScope ps(c, "linkage", 0, 24.0 * (double)N * (double)N);
+            le = linkage_rg_launch(c, onex, p.G, p.TH, D, (int)N, cid, nb, md, md2, d_Z, gran, sync, p.cap, (int)c->linkage_prefetch, (int)k_done, size, tyv);
+            c->stats["linkage_rg_launches"].launches += 1;
+        }
+        if (le != hipSuccess) { (void)hipGetLastError(); return SD_OK; }
+        unsigned h[SYNC_HOST_WORDS] = {0};
+        HIPCHK(c, hipMemcpyAsync(h, sync, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (!h[SYNC_TIMEOUT] && !h[SYNC_TIE]) { c->stats["linkage_zero_phase_jobs"].launches += 1; *done = true; return SD_OK; }
+        if (c->profile_detail) fprintf(stderr, "linkage: zero phase (%lld merges), then %s -> whole replay\n", (long long)k_done, h[SYNC_TIE] ? "another tie" : "a poll timeout");
+        return SD_OK;
+    }
+
+    // k_linkage_heap, the reference's algorithm on one workgroup, on the condensed matrix
+    int one_workgroup()
+    {
+        WS(c, double, Dc, "cl_D", N * (N - 1) / 2);
+        if (int rc = prepare(Dc, false)) return rc;
+        double* hval = nullptr; int* hkey = nullptr; int* hpos = nullptr;
+        if (N - 1 > HEAP_LDS) {
+            WS(c, double, hv, "cl_hval", N);
+            WS(c, int, hk, "cl_hkey", N);
+            WS(c, int, hp, "cl_hpos", N);
+            hval = hv; hkey = hk; hpos = hp;
+        }
+        ProfScope ps(c, "linkage_heap", 0, 24.0 * (double)N * (double)N);
+        hipLaunchKernelGGL(k_linkage_heap, dim3(1), dim3(LT), (size_t)((N + 31) / 32) * sizeof(unsigned), c->stream, Dc, (int)N, size, cid, nb, md, d_Z, hval, hkey, hpos);
+        KCHECK(c);
+        return SD_OK;
+    }
+};
+
+int run_linkage(sd_ctx* c, const double* d_X, int64_t N, int d, double* d_Z)
+{
+    if (N < 2) return SD_OK;
+    const int64_t m = N * (N - 1) / 2;
+    if (N > 0x7fffffff / 4 || (double)m * 8.0 > 230e9) SD_FAIL(c, SD_ERR_ARG, "linkage: N=%lld needs a %.0f GB condensed matrix (limit 230 GB)", (long long)N, (double)m * 8e-9);
+    WS(c, int, size, "cl_size", N);
+    WS(c, int, cid, "cl_cid", N);
+    WS(c, int, nb, "cl_nb", N);
+    WS(c, double, md, "cl_md", N);
+    WS(c, double, md2, "cl_md2", N);
+    int rc;
+    LinkageJob j = {c, d_X, N, d, d_Z, linkage_plan(c, N, true), size, cid, nb, md, md2};
+    LinkagePlan& p = j.p;
+    if (p.G <= 1) return j.one_workgroup();
+    if (p.square && !(j.D = ws_get<double>(c, "cl_Dsq", (size_t)N * N))) {      // no room for the square: the condensed form needs half
+        (void)hipGetLastError(); c->stats["linkage_square_alloc_failed"].launches += 1;
+        p = linkage_plan(c, N, false);
+    }
+    if (!p.square) { WS(c, double, Dc, "cl_D", m); j.D = Dc; }
+    if (p.G > c->num_cu || p.G > MWT) SD_FAIL(c, SD_ERR_ARG, "linkage: N=%lld needs %d cooperative workgroups", (long long)N, p.G);
+    if ((rc = j.prepare(j.D, p.square))) return rc;
+    WS(c, MwGran, gran, "cl_gran", (int64_t)2 * p.G * p.slot_gran);
+    HIPCHK(c, hipMemsetAsync(gran, 0, (size_t)2 * p.G * p.slot_gran * sizeof(MwGran), c->stream));
+    j.gran = gran;
+    if (!p.use_rg) {          // k_linkage_mw: per-workgroup private copies of sizes (and ty)
+        const int64_t priv = (int64_t)p.G * N * (p.square ? 2 : 1);
+        WS(c, int, sa, "cl_size_all", priv);
+        j.size_all = sa;
+        hipLaunchKernelGGL(k_fill_size_ty, dim3((unsigned)((priv + 255) / 256)), dim3(256), 0, c->stream, sa, N, priv, p.square ? 1 : 0);
+        KCHECK(c);
+    }
+    WS(c, unsigned, sync, "cl_sync", SYNC_WORDS);
+    HIPCHK(c, hipMemsetAsync(sync, 0, SYNC_WORDS * sizeof(unsigned), c->stream));
+    j.sync = sync;
+
+    // 1. the cooperative kernel; a forced replay counts as a refused launch: nothing has run
+    CoopOutcome o = {COOP_REFUSED, p.onex, 0.0, true};
+    if (!c->linkage_force_heap && (rc = j.coop(o))) return rc;
+    if (o.end == COOP_DONE) return SD_OK;
+    if (o.end == COOP_ONEX_TIMEOUT) {
+        // too few workgroups found themselves on XCC 0 (dispatch not round-robin?): never again in this context; the
+        // multi-XCD form does the job (the distance matrix is rebuilt by the recursive call)
+        c->linkage_one_xcd = 0;
+        c->stats["linkage_one_xcd_timeouts"].launches += 1;
+        return run_linkage(c, d_X, N, d, d_Z);
+    }
+    if (o.end == COOP_TIE) c->stats["linkage_tie_fallbacks"].launches += 1;
+    c->stats["linkage_fallbacks"].launches += 1;
+    const char* why = c->linkage_force_heap ? "forced (option linkage_force_heap)" : o.end == COOP_REFUSED ? "cooperative launch refused" : o.end == COOP_TIMEOUT ? "slot poll timed out" : "exact tie";
+    if (c->profile_detail) fprintf(stderr, "linkage: %s at N = %lld -> heap replay\n", why, (long long)N);
+
+    if (p.replay) {
+        WS(c, int, tyv, "cl_ty", N);
+        j.tyv = tyv;
+        bool untouched = o.untouched, ran = false;
+        // 2. Ties at height 0 -- rows that occur twice, the usual reason for a tie -- end once the duplicates are merged.  The replay takes the merges at
+        // height 0 only, and k_linkage_rg continues from that state (exact bounds of the rows still there from k_row_nn_mid); a later tie sends the whole
+        // job through the replay, as before.  (Both kernels produce the reference's sequence: the replay always, k_linkage_rg while the closest pair is unique.)
+        if (p.use_rg && o.end == COOP_TIE && o.tie_h == 0.0 && c->linkage_zero_phase != 0) {
+            int64_t k_done = 0;
+            if ((rc = j.replay(0.0, untouched, &ran, &k_done))) return rc;
+            if (ran) {
+                c->stats["linkage_zero_phase_merges"].flops += (double)k_done;
+                if (k_done >= N - 1) { c->stats["linkage_hx_jobs"].launches += 1; return SD_OK; }
+                bool done = false;
+                if (k_done > 0 && (rc = j.continue_rg(o.onex, k_done, &done))) return rc;
+                if (done) return SD_OK;
+            }
+        }
+        // 3. the whole job through the replay
+        if ((rc = j.replay((double)INFINITY, untouched, &ran, nullptr))) return rc;
+        if (ran) { c->stats["linkage_hx_jobs"].launches += 1; return SD_OK; }
+        c->stats["linkage_hx_failed"].launches += 1;
+    }
+    // 4. last resort.  The heap kernel works on the condensed matrix; the square one (up to 170 GB) is given back first, so that the fallback -- exact
     // ties are its designed trigger -- also fits right below the auto-square limit (the stream is idle: it was synchronised above)
     { auto it = c->ws.find("cl_Dsq"); if (it != c->ws.end()) it->second.release(); }
-    WS(c, double, Dh, "cl_D", m);
-    if ((rc = linkage_prepare(c, d_X, N, d, Dh, size, cid, nb, md, md2))) return rc;
-    return linkage_heap(c, N, Dh, size, cid, nb, md, d_Z);
+    return j.one_workgroup();
 }
 
 // fcluster(criterion="distance"), cl.cpp:121-232 + 442-457.  Node ids grow with merge order, so the

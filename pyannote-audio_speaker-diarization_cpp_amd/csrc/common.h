@@ -10,6 +10,7 @@
 #include <set>
 #include <string>
 #include <functional>
+#include <initializer_list>
 #include <vector>
 #include "../../include/sdhip_test.h"
 
@@ -237,7 +238,48 @@ struct ProfScope {
 };
 void sd_flush_profile(sd_ctx* c);   // api.cpp: resolves pending event pairs into stats
 
-// ---- conv_gemm.hip
+// ---- the launch tail the conv_gemm*.hip launchers share (host only)
+// Tile counts and the persistent grid: wgs_per_cu workgroups on every CU, a multiple of 8 (an equal share per XCD), and
+// no more workgroups per XCD than the busiest XCD has tiles
+inline int conv_tiles_grid(const sd_ctx* c, ConvArgs& a, int tile_m, int tile_n, int wgs_per_cu)
+{
+    a.m_tiles = (a.M + tile_m - 1) / tile_m;
+    a.n_tiles = (a.Cout + tile_n - 1) / tile_n;
+    int g = (wgs_per_cu * c->num_cu / 8) * 8;
+    if (g < 8) g = 8;
+    const int lx_max = ((a.m_tiles + 7) / 8) * a.n_tiles;
+    if (g / 8 > lx_max) g = lx_max * 8;
+    return g;
+}
+// The FLOP / byte bill of a layer (bench.py's roofline figures): un-padded input channels, algorithmic taps (the lo planes of the split-weight mode
+// are overhead, not work); `rows` output rows that read `inputs` input tensors
+struct ConvBill { double flops, bytes; };
+inline ConvBill conv_bill(const ConvArgs& a, double rows, bool f16, int inputs = 1)
+{
+    const int cin = a.cin_real > 0 ? a.cin_real : a.Cin;
+    const int kt_alg = a.kt_real > 0 ? a.kt_real : a.KT;
+    return {2.0 * rows * a.Cout * cin * kt_alg, (f16 ? 2.0 : 4.0) * (rows * cin * inputs + rows * a.Cout + (double)a.Cout * cin * a.KT)};
+}
+// The dynamic-LDS attribute of a kernel family, set once per device (a second thread that gets here meanwhile sets the same values); false = refused
+inline bool conv_set_dyn_lds(const sd_ctx* c, std::atomic<unsigned>& mask, std::initializer_list<const void*> kernels, size_t lds_bytes)
+{
+    const unsigned dev_bit = 1u << (c->device & 31);
+    if (mask.load(std::memory_order_acquire) & dev_bit) return true;
+    for (const void* k : kernels)
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+    mask.fetch_or(dev_bit, std::memory_order_release);
+    return true;
+}
+// The stats one launch of a wide (256 x 256) kernel bills: all conv_gemm launches (per layer tag under profile_detail), per precision ("f16" | "x3" | "f32"),
+// the wide tile alone (bench.py's roofline object), and that split by caller (PyanNet's K = 256 projections / the ECAPA layers)
+struct ConvProfWide {
+    ProfScope all, prec, wide, caller;
+    ConvProfWide(sd_ctx* c, const char* tag, const char* p, const ConvBill& b)
+        : all(c, c->profile_detail ? std::string("conv_gemm:") + tag : std::string("conv_gemm"), b.flops, b.bytes),
+          prec(c, std::string("conv_gemm_") + p, b.flops, b.bytes), wide(c, std::string("conv_w256_") + p, b.flops, b.bytes),
+          caller(c, strcmp(tag, "lstm_ih") == 0 ? "conv_w256_seg" : "conv_w256_ecapa", b.flops, b.bytes) {}
+};
+// ---- conv_gemm.hip: picks the kernel (pp -> g256 -> w256 -> skinny -> 128 x 128); the launchers below are its steps and get `a` with w_ld already defaulted
 int launch_conv_gemm(sd_ctx* c, const ConvArgs& a, const char* tag);
 // ---- conv_gemm_h.hip (fp16 mode, Cout >= 256: 256 x 256 tile; returns 1 = not applicable)
 int launch_conv_gemm_h256(sd_ctx* c, const ConvArgs& a, const char* tag);

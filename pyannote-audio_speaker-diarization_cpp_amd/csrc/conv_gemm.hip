@@ -619,17 +619,6 @@ __global__ __launch_bounds__(256) void k_skinny_gemm(ConvArgs a)
     }
 }
 
-static int conv_grid(sd_ctx* c, const ConvArgs& a)
-{
-    int g = 2 * c->num_cu;
-    g = (g / 8) * 8;
-    if (g < 8) g = 8;
-    // no point launching more workgroups per XCD than the busiest XCD has tiles
-    const int lx_max = ((a.m_tiles + 7) / 8) * a.n_tiles;
-    if (g / 8 > lx_max) g = lx_max * 8;
-    return g;
-}
-
 int launch_conv_gemm(sd_ctx* c, const ConvArgs& in, const char* tag)
 {
     ConvArgs a = in;
@@ -658,20 +647,15 @@ int launch_conv_gemm(sd_ctx* c, const ConvArgs& in, const char* tag)
         KCHECK(c);
         return SD_OK;
     }
-    a.m_tiles = (a.M + BM - 1) / BM;
-    a.n_tiles = (a.Cout + BN - 1) / BN;
     a.sched = c->conv_pn128 > 0 ? 100 + c->conv_pn128 : SD_CONV_SCHED_DEFAULT;
     a.stagger = c->conv_stagger;
-    const int grid = conv_grid(c, a);
+    const int grid = conv_tiles_grid(c, a, BM, BN, 2);
     // algorithmic work: valid rows only (T of every TpOut), un-padded input channels
     const double rows = a.rowtab ? (double)a.M
                                  : (double)(a.M / a.TpOut) * a.T + (double)((a.M % a.TpOut) < a.T ? (a.M % a.TpOut) : a.T);
-    const int cin = a.cin_real > 0 ? a.cin_real : a.Cin;
-    const int kt_alg = a.kt_real > 0 ? a.kt_real : a.KT;          // algorithmic taps (the lo planes of the split-weight mode are overhead, not work)
-    const double flops = 2.0 * rows * a.Cout * cin * kt_alg;
-    const double bytes = (f16 ? 2.0 : 4.0) * (rows * cin * (a.X2 ? 2 : 1) + rows * a.Cout + (double)a.Cout * cin * a.KT);
-    ProfScope ps(c, c->profile_detail ? std::string("conv_gemm:") + tag : std::string("conv_gemm"), flops, bytes);
-    ProfScope ps16(c, f16 ? "conv_gemm_f16" : x3 ? "conv_gemm_x3" : "conv_gemm_f32", flops, bytes);        // per precision (bench: roofline of the fp16 instantiations alone)
+    const ConvBill bill = conv_bill(a, rows, f16, a.X2 ? 2 : 1);
+    ProfScope ps(c, c->profile_detail ? std::string("conv_gemm:") + tag : std::string("conv_gemm"), bill.flops, bill.bytes);
+    ProfScope ps16(c, f16 ? "conv_gemm_f16" : x3 ? "conv_gemm_x3" : "conv_gemm_f32", bill.flops, bill.bytes);        // per precision (bench: roofline of the fp16 instantiations alone)
     if (f16) {
         if (a.X2) hipLaunchKernelGGL((k_conv_gemm<true, 0, 1>), dim3(grid), dim3(256), 0, c->stream, a);
         else hipLaunchKernelGGL((k_conv_gemm<false, 0, 1>), dim3(grid), dim3(256), 0, c->stream, a);
@@ -716,10 +700,9 @@ extern "C" int sd_bench_conv(sd_ctx* c, int64_t items, int Tp, int T, int Cin, i
     a.X = X; a.x_ld = xld; a.X2 = has_x2 ? X2 : nullptr; a.x2_ld = xld; a.W = W; a.w_ld = wld; a.Y = Y; a.y_ld = yld;
     a.bias = B; a.scale = B + Cout; a.shift = B + 2 * Cout; a.act1 = 1;
     a.M = (int)M; a.TpIn = a.TpOut = Tp; a.Tin = a.T = T; a.Cin = Cin; a.Cout = Cout; a.KT = KT; a.dil = dil; a.pad_mode = 0;
-    a.m_tiles = (a.M + BM - 1) / BM; a.n_tiles = (a.Cout + BN - 1) / BN;
     a.sched = (dbg >= 10) ? (dbg / 10 - 1) : SD_CONV_SCHED_DEFAULT;   // dbg = 10*(sched+1) + ablation
     dbg %= 10;
-    const int grid = conv_grid(c, a);
+    const int grid = conv_tiles_grid(c, a, BM, BN, 2);
     hipEvent_t e0, e1;
     HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
 #define LAUNCH_V(X2, D) hipLaunchKernelGGL((k_conv_gemm<X2, D, 0>), dim3(grid), dim3(256), 0, c->stream, a)

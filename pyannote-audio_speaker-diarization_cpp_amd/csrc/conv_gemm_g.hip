@@ -554,30 +554,12 @@ int launch_conv_gemm_g256(sd_ctx* c, const ConvArgs& in, const char* tag)
     if ((int64_t)a.Cin * (a.kt_real > 0 ? a.kt_real : a.KT) < (c->conv_w256_kmin > 0 ? c->conv_w256_kmin : (h ? 256 : 128))) return 1;
     if (((size_t)a.X & 15) || ((size_t)(h ? a.W16 : (const void*)a.W) & 15)) return 1;
     const size_t lds_bytes = (size_t)2 * G_STAGE + 8 * G_STRIP;       // (f32: 3 KB of parameters where the fp16 form keeps its strips)
-    const unsigned dev_bit = 1u << (c->device & 31);
-    if (!(g_attr_g256.load(std::memory_order_acquire) & dev_bit)) {        // once per device (a second thread that gets here meanwhile sets the same values)
-        if (hipFuncSetAttribute((const void*)k_conv_gemm_g256<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_conv_gemm_g256<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_conv_gemm_g256<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) { (void)hipGetLastError(); return 1; }
-        g_attr_g256.fetch_or(dev_bit, std::memory_order_release);
-    }
-    if (a.w_ld <= 0) a.w_ld = a.Cin;
-    a.m_tiles = (a.M + GM - 1) / GM;
-    a.n_tiles = (a.Cout + GN - 1) / GN;
+    if (!conv_set_dyn_lds(c, g_attr_g256, {(const void*)k_conv_gemm_g256<1>, (const void*)k_conv_gemm_g256<2>, (const void*)k_conv_gemm_g256<0>}, lds_bytes)) return 1;
     a.sched = c->conv_pn;
     a.stagger = c->conv_rot;
-    int grid = (c->num_cu / 8) * 8;
-    if (grid < 8) grid = 8;
-    const int lx_max = ((a.m_tiles + 7) / 8) * a.n_tiles;
-    if (grid / 8 > lx_max) grid = lx_max * 8;
-    const int cin = a.cin_real > 0 ? a.cin_real : a.Cin;
-    const double flops = 2.0 * (double)a.M * a.Cout * cin * (a.kt_real > 0 ? a.kt_real : a.KT);
-    const double bytes = (h ? 2.0 : 4.0) * ((double)a.M * cin + (double)a.M * a.Cout + (double)a.Cout * cin * a.KT);
+    const int grid = conv_tiles_grid(c, a, GM, GN, 1);
     {
-        ProfScope ps(c, c->profile_detail ? std::string("conv_gemm:") + tag : std::string("conv_gemm"), flops, bytes);
-        ProfScope ps16(c, h ? "conv_gemm_f16" : "conv_gemm_f32", flops, bytes);
-        ProfScope psw(c, h ? "conv_w256_f16" : "conv_w256_f32", flops, bytes);         // this tile form alone (bench.py's roofline object)
-        ProfScope pss(c, strcmp(tag, "lstm_ih") == 0 ? "conv_w256_seg" : "conv_w256_ecapa", flops, bytes);
+        ConvProfWide prof(c, tag, h ? "f16" : "f32", conv_bill(a, (double)a.M, h));
         if (h && c->conv_mfma16 && ((int64_t)a.Cin * a.KT >= 1024 || c->conv_mfma16 == 2)) hipLaunchKernelGGL(k_conv_gemm_g256<2>, dim3(grid), dim3(512), lds_bytes, c->stream, a);
         else if (h) hipLaunchKernelGGL(k_conv_gemm_g256<1>         /* short contractions (block0, K = 640): 523 TF on this form against 486 */, dim3(grid), dim3(512), lds_bytes, c->stream, a);
         else hipLaunchKernelGGL(k_conv_gemm_g256<0>, dim3(grid), dim3(512), lds_bytes, c->stream, a);

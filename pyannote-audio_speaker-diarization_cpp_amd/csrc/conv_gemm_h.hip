@@ -448,30 +448,12 @@ int launch_conv_gemm_h256(sd_ctx* c, const ConvArgs& in, const char* tag)
     // K-groups are pinned (block0 K = 400: 92 -> 102 TF, ASP conv K = 128: 95 -> 105 TF)
     if (!x3 && (int64_t)a.Cin * (a.kt_real > 0 ? a.kt_real : a.KT) < (c->conv_w256_kmin > 0 ? c->conv_w256_kmin : (h ? 256 : 128))) return 1;
     const size_t lds_bytes = (size_t)2 * (HM + HN) * HLDP * sizeof(float);
-    const unsigned dev_bit = 1u << (c->device & 31);
-    if (!(g_attr_w256.load(std::memory_order_acquire) & dev_bit)) {        // once per device (a second thread that gets here meanwhile sets the same values)
-        if (hipFuncSetAttribute((const void*)k_conv_gemm_w256<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_conv_gemm_w256<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_conv_gemm_w256<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) { (void)hipGetLastError(); return 1; }
-        g_attr_w256.fetch_or(dev_bit, std::memory_order_release);
-    }
-    if (a.w_ld <= 0) a.w_ld = a.Cin;
+    if (!conv_set_dyn_lds(c, g_attr_w256, {(const void*)k_conv_gemm_w256<1>, (const void*)k_conv_gemm_w256<0>, (const void*)k_conv_gemm_w256<3>}, lds_bytes)) return 1;
     if (x3) a.w_ld = 2 * a.Cin;              // halves: eight hi, eight lo, eight hi, ... (weights.cpp)
-    a.m_tiles = (a.M + HM - 1) / HM;
-    a.n_tiles = (a.Cout + HN - 1) / HN;
     a.sched = c->conv_pn;
-    int grid = (c->num_cu / 8) * 8;
-    if (grid < 8) grid = 8;
-    const int lx_max = ((a.m_tiles + 7) / 8) * a.n_tiles;
-    if (grid / 8 > lx_max) grid = lx_max * 8;
-    const int cin = a.cin_real > 0 ? a.cin_real : a.Cin;
-    const double flops = 2.0 * (double)a.M * a.Cout * cin * (a.kt_real > 0 ? a.kt_real : a.KT);
-    const double bytes = (h ? 2.0 : 4.0) * ((double)a.M * cin + (double)a.M * a.Cout + (double)a.Cout * cin * a.KT);
+    const int grid = conv_tiles_grid(c, a, HM, HN, 1);
     {
-        ProfScope ps(c, c->profile_detail ? std::string("conv_gemm:") + tag : std::string("conv_gemm"), flops, bytes);
-        ProfScope ps16(c, h ? "conv_gemm_f16" : x3 ? "conv_gemm_x3" : "conv_gemm_f32", flops, bytes);
-        ProfScope psw(c, h ? "conv_w256_f16" : x3 ? "conv_w256_x3" : "conv_w256_f32", flops, bytes);         // this kernel alone (bench.py's roofline object)
-        ProfScope pss(c, strcmp(tag, "lstm_ih") == 0 ? "conv_w256_seg" : "conv_w256_ecapa", flops, bytes);   // ... split by caller (PyanNet's K = 256 projections / the ECAPA layers)
+        ConvProfWide prof(c, tag, h ? "f16" : x3 ? "x3" : "f32", conv_bill(a, (double)a.M, h));
         if (h) hipLaunchKernelGGL(k_conv_gemm_w256<1>, dim3(grid), dim3(512), lds_bytes, c->stream, a);
         else if (x3) hipLaunchKernelGGL(k_conv_gemm_w256<3>, dim3(grid), dim3(512), lds_bytes, c->stream, a);
         else hipLaunchKernelGGL(k_conv_gemm_w256<0>, dim3(grid), dim3(512), lds_bytes, c->stream, a);

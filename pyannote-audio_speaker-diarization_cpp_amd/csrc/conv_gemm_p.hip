@@ -345,33 +345,16 @@ int launch_conv_gemm_pp(sd_ctx* c, const ConvArgs& in, const char* tag)
     ConvArgs a = in;
     if (a.prec != 1 || !a.rowtab || !a.W16 || a.X2 || a.item_bias || a.R || a.act2 || a.pad_mode != 0 || a.y_f32 || !a.bias || !a.scale || !a.shift ||
         a.Cout < 256 || (a.Cout % 256) != 0 || (a.y_ld & 7) || a.Cin % 64 != 0 || a.M < 8 * 256 || (a.x_ld & 7)) return 1;
-    if (a.w_ld <= 0) a.w_ld = a.Cin;
     if ((a.w_ld & 7) || (int64_t)a.KT * (a.Cin / 64) < 2) return 1;
     // every layer this kernel takes gives the bits of k_conv_gemm_g256<2> (same products, same order) -- the two are compared bit for bit (tests/test_gpu_parity.py);
     // block0 (K = 5 x 128 = 640, ten K-tiles per tile) is taken too since the load stream is continuous (k_conv_gemm_g256 ran it on its 32x32x16 form: 490 TF)
     if ((int64_t)a.Cin * a.KT < 512 || !c->conv_mfma16) return 1;
     if (((size_t)a.X & 15) || ((size_t)a.W16 & 15) || ((size_t)a.Y & 15) || ((size_t)a.bias & 15) || ((size_t)a.scale & 15) || ((size_t)a.shift & 15) || ((size_t)a.rowtab & 15)) return 1;
-    const unsigned dev_bit = 1u << (c->device & 31);
-    if (!(g_attr_pp.load(std::memory_order_acquire) & dev_bit)) {
-        if (hipFuncSetAttribute((const void*)k_conv_gemm_pp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P_LDS) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_conv_gemm_pp<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P_LDS) != hipSuccess) { (void)hipGetLastError(); return 1; }
-        g_attr_pp.fetch_or(dev_bit, std::memory_order_release);
-    }
-    a.m_tiles = (a.M + 255) / 256;
-    a.n_tiles = a.Cout / 256;
+    if (!conv_set_dyn_lds(c, g_attr_pp, {(const void*)k_conv_gemm_pp<true>, (const void*)k_conv_gemm_pp<false>}, P_LDS)) return 1;
     a.sched = c->conv_pn;
-    int grid = (c->num_cu / 8) * 8;
-    if (grid < 8) grid = 8;
-    const int lx_max = ((a.m_tiles + 7) / 8) * a.n_tiles;
-    if (grid / 8 > lx_max) grid = lx_max * 8;
-    const int cin = a.cin_real > 0 ? a.cin_real : a.Cin;
-    const double flops = 2.0 * (double)a.M * a.Cout * cin * (a.kt_real > 0 ? a.kt_real : a.KT);
-    const double bytes = 2.0 * ((double)a.M * cin + (double)a.M * a.Cout + (double)a.Cout * cin * a.KT);
+    const int grid = conv_tiles_grid(c, a, 256, 256, 1);          // (Cout is a multiple of 256)
     {
-        ProfScope ps(c, c->profile_detail ? std::string("conv_gemm:") + tag : std::string("conv_gemm"), flops, bytes);
-        ProfScope ps16(c, "conv_gemm_f16", flops, bytes);
-        ProfScope psw(c, "conv_w256_f16", flops, bytes);
-        ProfScope pss(c, "conv_w256_ecapa", flops, bytes);
+        ConvProfWide prof(c, tag, "f16", conv_bill(a, (double)a.M, true));          // (ECAPA layers only: prec 1)
         if (a.act1 == 1) hipLaunchKernelGGL(k_conv_gemm_pp<true>, dim3(grid), dim3(512), P_LDS, c->stream, a);
         else hipLaunchKernelGGL(k_conv_gemm_pp<false>, dim3(grid), dim3(512), P_LDS, c->stream, a);
     }

@@ -1,4 +1,5 @@
-// linkage_dev.h -- device helpers shared by the linkage kernels (cluster.hip: k_linkage_heap, k_linkage_mw; linkage_rg.hip: k_linkage_rg).
+// linkage_dev.h -- device helpers shared by the linkage kernels (cluster.hip: k_linkage_heap, k_linkage_mw; linkage_rg.hip: k_linkage_rg; linkage_hx.hip:
+// k_linkage_hx), the words of the `sync` block they and the host talk through, and the launchers run_linkage drives.
 // Translation units that include this file are compiled with -ffp-contract=off (Makefile EXACT): fp64 results bit-identical to the reference's x86 build.
 #pragma once
 #include "common.h"
@@ -106,6 +107,16 @@ __device__ __forceinline__ double lw_centroid(double d_xi, double d_yi, double d
 // A slot is a set of 8-byte granules {32-bit payload word, 32-bit round tag}: a reader that sees the tag of the round it waits for has the
 // payload of that round (8-byte stores are single transactions), so publishing needs no separate "ready" flag and no counter.
 typedef unsigned long long MwGran;
+// The `sync` block (workspace cl_sync, zeroed before every cooperative launch): words the kernels raise and the host reads after the launch.
+// (SYNC_ROUNDS counts retry rounds in k_linkage_mw / k_linkage_rg, stale scans in k_linkage_hx.)
+constexpr int SYNC_TIMEOUT = 1;                  // a slot poll timed out (one XCD: too few workgroups found themselves on XCC 0)
+constexpr int SYNC_ROUNDS = 2;                   // diagnostic counter: retry rounds / stale scans
+constexpr int SYNC_MERGES = 3;                   // k_linkage_hx: merges done when it stopped
+constexpr int SYNC_TIE = 5;                      // the closest pair was not unique: nothing more was merged
+constexpr int SYNC_TICKET = 6;                   // one-XCD forms: next ticket of the workgroups that found themselves on XCC 0
+constexpr int SYNC_TIE_LO = 26, SYNC_TIE_HI = 27;      // k_linkage_rg: the tie's height (bits of the double)
+constexpr int SYNC_HOST_WORDS = 32;              // what the host copies back
+constexpr int SYNC_WORDS = 32 + 16 * 256;
 // arg-min candidate flags: bit 0 = the bound is exact; bit 1 (CAND_TIE) = some OTHER row holds exactly the same bound -- the case in which the
 // reference's heap, not the value, decides who comes first (k_linkage_heap)
 #define CAND_TIE 2
@@ -126,3 +137,14 @@ template <bool ONEX, class T> __device__ __forceinline__ void STX(T* p, T v)
     if constexpr (ONEX) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+
+// ---------------------------------------------------------------- launchers run_linkage (cluster.hip) drives
+// linkage_rg.hip
+bool linkage_rg_fits(int64_t N, int G, int TH);
+hipError_t linkage_rg_launch(sd_ctx* c, bool onex, int G, int TH, double* D, int n, int* cid, const int* nb, const double* md, const double* md2,
+                             double* Z, MwGran* gran, unsigned* sync, int cap, int helper, int k0 = 0, const int* sz0 = nullptr, const int* ty0 = nullptr);
+int linkage_rg_slot_granules();
+// linkage_hx.hip
+bool linkage_hx_fits(int64_t N, int workers);
+int linkage_hx_run(sd_ctx* c, bool onex, int workers, double* D, int64_t N, int* cid, int* size, int* tyv, int* nb, double* md, double* d_Z, bool* stopped,
+                   double stop_above = (double)INFINITY, int64_t* merges_done = nullptr, bool* launched = nullptr);

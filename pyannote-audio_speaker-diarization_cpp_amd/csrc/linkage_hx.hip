@@ -104,7 +104,7 @@ template <bool ONEX, bool S16>
 __global__ __launch_bounds__(HX_T) void k_linkage_hx(double* D, int n, int* cid, int* size, int* tyv, int* nb, double* md, double* Z,
                                                      double* g_hval, int* g_hkey, int* g_hpos, MwGran* cmd /*[16]*/, MwGran* rep /*[G][8]*/,
                                                      int* chg_z /*[G][cap]*/, double* chg_v /*[G][cap]*/, unsigned* sync, int cap, int G /*workers*/, int lc,
-                                                     double stop_above /*stop in front of the first merge higher than this (inf = never); sync[3] = merges done*/)
+                                                     double stop_above /*stop in front of the first merge higher than this (inf = never); sync[SYNC_MERGES] = merges done*/)
 {
     extern __shared__ __attribute__((aligned(16))) int dyn_lds[];     // master: heap tier [lc] doubles + [lc] ints
     __shared__ MinIdx sh[HX_T / 64];
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(HX_T) void k_linkage_hx(double* D, int n, int* cid,
         __shared__ int s_ticket;
         if (tid == 0) {
             const unsigned xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));       // HW_REG_XCC_ID[3:0]
-            s_ticket = (xcc == 0) ? (int)atomicAdd(&sync[6], 1u) : -1;
+            s_ticket = (xcc == 0) ? (int)atomicAdd(&sync[SYNC_TICKET], 1u) : -1;
         }
         __syncthreads();
         g = s_ticket;
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(HX_T) void k_linkage_hx(double* D, int n, int* cid,
         while ((unsigned)(v >> 32) != tag) {
             __builtin_amdgcn_s_sleep(1);
             v = LDG(p);
-            if (++spins > (1u << 24)) { sync[1] = 1; ok = false; break; }     // ~seconds: never in a healthy run
+            if (++spins > (1u << 24)) { sync[SYNC_TIMEOUT] = 1; ok = false; break; }     // ~seconds: never in a healthy run
         }
         return (unsigned)v;
     };
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(HX_T) void k_linkage_hx(double* D, int n, int* cid,
                 __syncthreads();
                 if (ok) break;
                 // stale candidate: row x's true nearest neighbour (cl.cpp:333-338), every worker scans its own columns
-                if (g == 0 && tid == 0) sync[2] += 1;
+                if (g == 0 && tid == 0) sync[SYNC_ROUNDS] += 1;
                 send(HX_OP_SCAN, x, 0, 0.0, 0, 0, tx, 0, k);
                 if (!recv()) return;
                 const MinIdx q = fold_nn();
@@ -212,9 +212,9 @@ __global__ __launch_bounds__(HX_T) void k_linkage_hx(double* D, int n, int* cid,
                 }
                 __syncthreads();
             }
-            if (y < 0) { if (tid == 0) { Z[(size_t)k * 4 + 3] = NAN; sync[1] = 1; } send(HX_OP_QUIT, 0, 0, 0.0, 0, 0, 0, 0, 0); return; }   // cannot happen while two clusters are active
+            if (y < 0) { if (tid == 0) { Z[(size_t)k * 4 + 3] = NAN; sync[SYNC_TIMEOUT] = 1; } send(HX_OP_QUIT, 0, 0, 0.0, 0, 0, 0, 0, 0); return; }   // cannot happen while two clusters are active
             if (dist > stop_above) {                 // the caller continues from here with the cooperative kernel (run_linkage: duplicates merged, the rest is tie-free)
-                if (tid == 0) sync[3] = (unsigned)k;
+                if (tid == 0) sync[SYNC_MERGES] = (unsigned)k;
                 send(HX_OP_QUIT, 0, 0, 0.0, 0, 0, 0, 0, 0);
                 return;
             }
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(HX_T) void k_linkage_hx(double* D, int n, int* cid,
             if (tid == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // nb / md of row y have landed before the next command is visible
             __syncthreads();
         }
-        if (tid == 0) sync[3] = (unsigned)(n - 1);
+        if (tid == 0) sync[SYNC_MERGES] = (unsigned)(n - 1);
         send(HX_OP_QUIT, 0, 0, 0.0, 0, 0, 0, 0, 0);
         return;
     }
@@ -439,9 +439,9 @@ int linkage_hx_run(sd_ctx* c, bool onex, int workers, double* D, int64_t N, int*
     WS(c, MwGran, cmd, "hx_cmd", 16 + (int64_t)8 * G);
     WS(c, int, chz, "hx_chg_z", (int64_t)G * cap);
     WS(c, double, chv, "hx_chg_v", (int64_t)G * cap);
-    WS(c, unsigned, sync, "cl_sync", 32 + 16 * 256);
+    WS(c, unsigned, sync, "cl_sync", SYNC_WORDS);
     HIPCHK(c, hipMemsetAsync(cmd, 0, (size_t)(16 + 8 * G) * sizeof(MwGran), c->stream));
-    HIPCHK(c, hipMemsetAsync(sync, 0, (32 + 16 * 256) * sizeof(unsigned), c->stream));
+    HIPCHK(c, hipMemsetAsync(sync, 0, SYNC_WORDS * sizeof(unsigned), c->stream));
     MwGran* rep = cmd + 16;
     const size_t dyn = (((size_t)lc * 8 + kp_bytes) + 15) & ~(size_t)15;
     const void* f = onex ? (s16 ? (const void*)k_linkage_hx<true, true> : (const void*)k_linkage_hx<true, false>)
@@ -460,8 +460,8 @@ int linkage_hx_run(sd_ctx* c, bool onex, int workers, double* D, int64_t N, int*
     unsigned h[8] = {0};
     HIPCHK(c, hipMemcpyAsync(h, sync, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->stats["linkage_hx_stale_scans"].flops += (double)h[2];
-    if (h[1]) *stopped = true;                  // a hand-off timed out (or, one XCD: too few workgroups found themselves on XCC 0)
-    if (merges_done) *merges_done = (int64_t)h[3];
+    c->stats["linkage_hx_stale_scans"].flops += (double)h[SYNC_ROUNDS];
+    if (h[SYNC_TIMEOUT]) *stopped = true;                  // a hand-off timed out (or, one XCD: too few workgroups found themselves on XCC 0)
+    if (merges_done) *merges_done = (int64_t)h[SYNC_MERGES];
     return SD_OK;
 }

@@ -15,7 +15,7 @@
 //     instead of four;
 //   * a row without an active column above it gets the exact bound +inf at once (columns are only ever removed) instead of a stale
 //     bound that costs a refresh round later.
-// Ties: as k_linkage_mw, a merge is taken only while the closest pair is unique; otherwise sync[5] is raised and run_linkage hands the
+// Ties: as k_linkage_mw, a merge is taken only while the closest pair is unique; otherwise sync[SYNC_TIE] is raised and run_linkage hands the
 // job to the kernel that replays the reference's heap.
 #include "common.h"
 #include "linkage_dev.h"
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, c
         __shared__ int s_ticket;
         if (tid == 0) {
             const unsigned xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));       // HW_REG_XCC_ID[3:0]
-            s_ticket = (xcc == 0) ? (int)atomicAdd(&sync[6], 1u) : -1;
+            s_ticket = (xcc == 0) ? (int)atomicAdd(&sync[SYNC_TICKET], 1u) : -1;
         }
         __syncthreads();
         g = s_ticket;
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, c
                 __builtin_amdgcn_s_sleep(1);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) if ((unsigned)(v[j] >> 32) != bar) v[j] = LDG(p[j]);
-                if (++spins > (1u << 24)) { sync[1] = 1; ok = false; break; }     // ~seconds: never in a healthy run
+                if (++spins > (1u << 24)) { sync[SYNC_TIMEOUT] = 1; ok = false; break; }     // ~seconds: never in a healthy run
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) if (i0 + j * T < total) s_words[sl[j]][wd[j]] = (unsigned)v[j];
@@ -454,7 +454,7 @@ __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, c
         // ---- lazy validation (cl.cpp:323-339): cooperative refresh of the best stale candidates
         for (int guard = 0; guard <= n - k; ++guard) {
             if ((best.fl & 1) && best.y >= 0) break;
-            if (g == 0 && tid == 0) sync[2] += 1;            // diagnostic: retry rounds
+            if (g == 0 && tid == 0) sync[SYNC_ROUNDS] += 1;            // diagnostic: retry rounds
             const int nL = s_nL[lp]; const int* L = s_L[lp];
             scan_rows(nL, L, s_Lty[lp], s_row);
             const RCand m = local_argmin(nL, L);
@@ -467,7 +467,7 @@ __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, c
             if (!((best.fl & 1) && best.y >= 0)) pick_stale(nocand, lp);
         }
         if (best.fl & CAND_TIE) {      // the closest pair is not unique: the heap decides (run_linkage); the height of the tie goes along
-            if (g == 0 && tid == 0) { sync[5] = 1; sync[26] = lo32(best.v); sync[27] = hi32(best.v); }
+            if (g == 0 && tid == 0) { sync[SYNC_TIE] = 1; sync[SYNC_TIE_LO] = lo32(best.v); sync[SYNC_TIE_HI] = hi32(best.v); }
             return;
         }
         // ---- merge (x, y) at height dist; everything about the pair came with the candidate
@@ -563,7 +563,7 @@ __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, c
         if (!consume(RG_MW)) return;
         digest(0, s_L[lp], s_Lty[lp], s_Lsz[lp], true);
         par ^= 1;
-        if (d_rowtie) { if (g == 0 && tid == 0) { sync[5] = 1; sync[26] = lo32(dist); sync[27] = hi32(dist); } return; }     // (this merge's stores into row y are out, and so is row k of Z: run_linkage reads from Z's row 0 whether the matrix is still what linkage_prepare left)
+        if (d_rowtie) { if (g == 0 && tid == 0) { sync[SYNC_TIE] = 1; sync[SYNC_TIE_LO] = lo32(dist); sync[SYNC_TIE_HI] = hi32(dist); } return; }     // (this merge's stores into row y are out, and so is row k of Z: run_linkage reads from Z's row 0 whether the matrix is still what linkage_prepare left)
         best = d_best;
         const RQ nn = d_nn;
         // row y: exact by construction (cl.cpp:395-404).  Without an active column above it the row has no pair left, now or later
