@@ -57,7 +57,8 @@ int sd_test_pack_split_weights(const float* w, int K, int Cout, int CinPad, int 
  * context pretends to have made, 0 = the next one plans the small first-job arena). */
 /* environment (diagnostic): SD_TRACE_CREATE=1 prints where sd_create's time goes; SD_TRACE_WS=1 makes sd_diarize_dev print the job's stage times and what the
  * process's workspace hipMalloc / hipFree calls have cost so far (count, GB, ms) with every workspace of 256 MB or more. */
-/* tuning hook (tools/): time one conv_gemm shape on scratch data (dbg selects an ablation) */
+/* tuning hook (tools/): time one conv_gemm shape on scratch data (dbg = 100 * pad_units + 10 * (sched + 1); a non-zero last digit,
+ * which chose an ablation build until those were retired, is SD_ERR_ARG) */
 int sd_bench_conv(sd_ctx*, int64_t items, int Tp, int T, int Cin, int Cout, int KT, int dil, int has_x2, int dbg, int reps, double* ms_per_launch);
 
 #ifdef __cplusplus

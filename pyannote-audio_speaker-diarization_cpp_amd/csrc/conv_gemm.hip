@@ -20,17 +20,16 @@
 // written to the other LDS buffer during the third; one barrier per K step, placed
 // before the fourth group, whose operands are already in registers.
 //
-// Persistent schedule: the grid is 2 workgroups per CU; the workgroups whose id is
-// equal mod 8 (one XCD under round-robin dispatch, a speed assumption only) walk
-// PM x PN super-blocks of tiles together (row panels m = xcd + 8j).  The K-step pipeline runs straight across tile
+// Persistent schedule: the grid is 2 workgroups per CU, which walk PM x PN super-blocks
+// of tiles (ConvSched, conv_dev.h).  The K-step pipeline runs straight across tile
 // boundaries: the first loads of tile i+1 are in flight while tile i's accumulators
 // go through the epilogue, so short-K layers (Res2Net K=384, ASP K=128) do not pay
 // a load-latency bubble per tile.
-#include "common.h"
+//
+// conv_dev.h holds what this kernel shares with its 256 x 256 siblings: the schedule, the
+// row map of a tap, the row-table cursor of the load stream and the epilogue pieces.
+#include "conv_dev.h"
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));   // 4-byte aligned float4 (x_ld may be 10)
 
 #define BM 128
 #define BN 128
@@ -38,53 +37,25 @@ typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));   // 4-byte a
 #define LDP 36
 #define SD_CONV_SCHED_DEFAULT 3
 
-// DBG (micro-benchmark ablations only, never used by the pipeline): 1 = no epilogue stores,
-// 2 = no global loads inside the K loop, 3 = no LDS restaging / barrier inside the K loop
 // F16 (BASELINE.json configs[4], option "ecapa_precision" = 1): fp16 end to end.  X, X2, W16 and Y hold _Float16 (leading
 // dimensions in elements), a K-step is 64 halves -- the same 128 bytes per row as 32 floats, so the load stream, the LDS tile
 // (144-byte rows) and the K-step pipeline are byte for byte the f32 ones -- and the MFMA is v_mfma_f32_32x32x16_f16 (f32
 // accumulation, f32 epilogue arithmetic, one rounding to fp16 at the store).  16x less MFMA time per K-step than f32.
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 // PR = 3 ("x3", option ecapa_precision = 3; the layers conv_gemm_h.hip's wide tile does not take: Res2Net, the attention's hidden layer): f32
 // tensors, both operands split into hi + lo fp16 halves -- the activations (X + X2, added in f32) when they are staged, the weights by
 // weights.cpp (W16x) -- and every 16-channel block runs hi*hi + lo*hi + hi*lo on v_mfma_f32_32x32x16_f16: 24 MFMAs of 32 cycles per wave and
 // 32-channel K-step instead of 64 of 64 cycles.  LDS row and fragment offsets: conv_gemm_h.hip.
-template <bool HAS_X2, int DBG, int PR>
+template <bool HAS_X2, int PR>
 __global__ __launch_bounds__(256, 2) void k_conv_gemm(ConvArgs a)
 {
     constexpr bool F16 = PR == 1, X3 = PR == 3;
     __shared__ __attribute__((aligned(16))) float As[2][BM * LDP];
     __shared__ __attribute__((aligned(16))) float Bs[2][BN * LDP];
 
-    const int w = blockIdx.x, G = gridDim.x;                 // G is a multiple of 8
-    const int xcd = w & 7, wl = w >> 3, wpx = G >> 3;
-    // row panels owned by this XCD: m = xcd + 8 j
-    const int mx = (a.m_tiles - xcd + 7) >> 3;
-    // Super-block schedule: the wpx workgroups of an XCD work at the same time on a PM x PN block of tiles
-    // (workgroup wl owns position (wl / PN, wl % PN) of every block).  They advance through K roughly in step,
-    // so each A and W K-slice is pulled into the XCD's L2 once per block and shared by PN resp. PM workgroups
-    // (measured before this order: 125 GB of fabric reads for the 3072x3072 layer against 4.9 GB algorithmic).
-    const int pnmax = a.sched >= 100 ? a.sched - 100 : 8;          // (tuning: conv_pn128)
-    const int PN = a.n_tiles < pnmax ? a.n_tiles : pnmax;
-    const int PM = wpx / PN > 0 ? wpx / PN : 1;
-    const int pm = wl / PN, pn = wl - pm * PN;
-    if (pm >= PM) return;
-    const int n_groups = (a.n_tiles + PN - 1) / PN, m_groups = (mx + PM - 1) / PM;
-    const int sb_end = n_groups * m_groups;
-    auto sb_valid = [&](int sb, int& j, int& nt) -> bool {
-        const int mg = sb / n_groups, ng = sb - mg * n_groups;
-        j = mg * PM + pm; nt = ng * PN + pn;
-        return j < mx && nt < a.n_tiles;
-    };
-    auto next_sb = [&](int sb) -> int {         // next super-block in which this workgroup has a tile, or sb_end
-        int j, nt;
-        for (++sb; sb < sb_end; ++sb) if (sb_valid(sb, j, nt)) return sb;
-        return sb_end;
-    };
-    const int q0 = next_sb(-1);
-    if (q0 >= sb_end) return;
+    ConvSched sch;
+    int q0;
+    if (!sch.init(a, a.sched >= 100 ? a.sched - 100 : 8 /* (tuning: conv_pn128) */, q0)) return;
+    const int wl = sch.wl, wpx = sch.wpx;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wid = tid >> 6;
@@ -108,45 +79,28 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm(ConvArgs a)
     // All global reads are buffer loads: a per-tile resource descriptor in SGPRs, a per-lane byte offset that only
     // changes with the tap, and the K position as the instruction's scalar offset -- moving to the next K-step is
     // one scalar add instead of twelve 64-bit vector pointer increments on the MFMA issue path.
-    int rrel[NPA], tt[NPA], nd[NPA];    // per part: item offset (rows) relative to the tile's first item, clamped frame, last stored frame
+    ConvRowTab<NPA> tab;                // per part: item offset (rows) relative to the tile's first item, clamped frame, last stored frame
     unsigned voA[NPA], voX[HAS_X2 ? NPA : 1], voB[4];
     const bool RT = a.rowtab != nullptr;                     // compact row space (see ConvArgs)
     const size_t in_rows = RT ? (size_t)(a.in_rows > 0 ? a.in_rows : a.M) : (size_t)((a.M + a.TpOut - 1) / a.TpOut) * a.TpIn;
-    // row-table entries of the tile the load stream visits NEXT: fetched one tile ahead, so a tile switch never waits for them
-    int2 pre[NPA]; int pre_base = 0;
-    auto prefetch_tab = [&](int sb) {
-        int j, nt;
-        (void)sb_valid(sb, j, nt);
-        const int m0 = __builtin_amdgcn_readfirstlane((xcd + 8 * j) * BM);
-        pre_base = a.rowtab[m0 < a.M ? m0 : a.M - 1].x;
-#pragma unroll
-        for (int p = 0; p < NPA; ++p) { int g = m0 + a_row(p); if (g > a.M - 1) g = a.M - 1; pre[p] = a.rowtab[g]; }
-    };
-    auto make_rsrc = [&](const void* base, size_t bytes) {
-        return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes > 0xffffffffull ? 0xffffffffu : (unsigned)bytes, 0x00020000);
-    };
-    __amdgpu_buffer_rsrc_t rA = make_rsrc(a.X, 0), rX = make_rsrc(a.X, 0);
-    const __amdgpu_buffer_rsrc_t rB = make_rsrc(X3 ? a.W16x : F16 ? a.W16 : (const void*)a.W, (size_t)a.KT * a.Cout * a.w_ld * ESB);
+    auto prefetch_tab = [&](int sb) { int m0, n0; sch.origin(a, sb, BM, BN, m0, n0); tab.prefetch(a, m0, a_row); };
+    __amdgpu_buffer_rsrc_t rA = conv_rsrc(a.X, 0), rX = conv_rsrc(a.X, 0);
+    const __amdgpu_buffer_rsrc_t rB = conv_rsrc(X3 ? a.W16x : F16 ? a.W16 : (const void*)a.W, (size_t)a.KT * a.Cout * a.w_ld * ESB);
 #pragma unroll
     for (int p = 0; p < 4; ++p) voB[p] = (unsigned)((r0 + 32 * p) * a.w_ld * ESB + c4 * 16);
-    int l_q = q0, l_kk = 0, l_kc = 0, m0l = 0, n0l = 0;
+    ConvLoadPos lp; lp.q = q0;
+    int m0l = 0, n0l = 0;
     // K always runs 0 .. Cin-1 in the same order for every tile: a row's result does not depend on where its tile sits
     // in the schedule (sharded and unsharded runs, full and dead-row-skipping runs stay bit-identical).  [Tried and
     // dropped: starting each workgroup of a super-block at a different K-chunk plus a per-tile rendezvous -- it lifts
     // the 3072x3072 layer's L2 hit rate from 27 % to 73 % (the L2 answers sharers that ask for a line at the same moment
     // with one miss each: fabric read requests == L2 misses) but not its speed, and it breaks that invariance.]
-    unsigned sK = 0, sB = 0;            // scalar byte offsets: K position, start of this tap's / tile's W rows
-    auto set_tile = [&](int sb) {
-        int j, nt;
-        (void)sb_valid(sb, j, nt);
-        m0l = __builtin_amdgcn_readfirstlane((xcd + 8 * j) * BM);   // wave-uniform: keeps the descriptors in SGPRs
-        n0l = __builtin_amdgcn_readfirstlane(nt * BN);
+    unsigned sB = 0;                    // scalar byte offset of this tap's / tile's W rows (the K position is lp.sK)
+    auto set_tile = [&](int sb) {         // the stream enters a tile (compact row space: its table entries were fetched a tile ago; asks for the next tile's)
+        sch.origin(a, sb, BM, BN, m0l, n0l);
         size_t row0;
         if (RT) {
-            const int base = __builtin_amdgcn_readfirstlane(pre_base);
-            row0 = (size_t)base;
-#pragma unroll
-            for (int p = 0; p < NPA; ++p) { rrel[p] = pre[p].x - base; tt[p] = ROWTAB_T(pre[p].y); nd[p] = ROWTAB_LAST(pre[p].y); }
+            row0 = (size_t)tab.enter();
         } else {
             const int b0 = m0l / a.TpOut;
             row0 = (size_t)b0 * a.TpIn;
@@ -157,57 +111,41 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm(ConvArgs a)
                 const int b = g / a.TpOut;
                 int t = g - b * a.TpOut;
                 if (t > a.T - 1) t = a.T - 1;
-                rrel[p] = (b - b0) * a.TpIn;
-                tt[p] = t; nd[p] = 0;
+                tab.rrel[p] = (b - b0) * a.TpIn;
+                tab.tt[p] = t; tab.nd[p] = 0x7fffffff;        // padded row space: every frame of an item is stored, nothing to clamp to
             }
         }
-        rA = make_rsrc((const char*)a.X + row0 * a.x_ld * ES, (in_rows - row0) * a.x_ld * ES);
-        if (HAS_X2) rX = make_rsrc((const char*)a.X2 + row0 * a.x2_ld * ES, (in_rows - row0) * a.x2_ld * ES);
+        rA = conv_rsrc((const char*)a.X + row0 * a.x_ld * ES, (in_rows - row0) * a.x_ld * ES);
+        if (HAS_X2) rX = conv_rsrc((const char*)a.X2 + row0 * a.x2_ld * ES, (in_rows - row0) * a.x2_ld * ES);
+        if (RT) { const int nq2 = sch.next(a, sb); if (nq2 < sch.sb_end) prefetch_tab(nq2); }
     };
     auto set_tap = [&](int kk) {          // per-lane offsets of tap kk (reflect / valid row map)
 #pragma unroll
         for (int p = 0; p < NPA; ++p) {
             int qr;
-            if (a.pad_mode == 0) {
-                qr = tt[p] + ((kk >= ktr ? kk - ktr : kk) - half) * a.dil;
-                if (qr < 0) qr = -qr;
-                if (qr >= a.Tin) qr = 2 * (a.Tin - 1) - qr;
-                if (qr < 0) qr = 0;
-                if (RT && qr > nd[p]) qr = nd[p];
-            } else {
-                qr = tt[p] + kk * a.dil;
+            if (a.pad_mode == 0) qr = conv_src_frame(tab.tt[p], kk, ktr, half, a.dil, a.Tin, tab.nd[p]);
+            else {                        // "valid": no padding, the tile's surplus rows read the last frame
+                qr = tab.tt[p] + kk * a.dil;
                 if (qr > a.Tin - 1) qr = a.Tin - 1;
             }
-            const unsigned row = (unsigned)(rrel[p] + qr);
+            const unsigned row = (unsigned)(tab.rrel[p] + qr);
             voA[p] = row * (unsigned)a.x_ld * ES + (X3 ? c8 * 32 : c4 * 16);
             if (HAS_X2) voX[p] = row * (unsigned)a.x2_ld * ES + (X3 ? c8 * 32 : c4 * 16);
         }
         sB = (unsigned)(((size_t)kk * a.Cout + n0l) * a.w_ld * ESB);
     };
-    auto advance = [&]() {                // move the load stream to the next K-step
-        if (++l_kc < kcs) { sK += 128; return; }
-        l_kc = 0; sK = 0;
-        if (++l_kk == a.KT) {
-            l_kk = 0;
-            const int nq = next_sb(l_q);
-            if (nq < sb_end) {                                           // else: stay on the last tile (dummy loads)
-                l_q = nq; set_tile(l_q);
-                if (RT) { const int nq2 = next_sb(l_q); if (nq2 < sb_end) prefetch_tab(nq2); }
-            }
-        }
-        set_tap(l_kk);
-    };
+    auto advance = [&]() { lp.advance(a, sch, kcs, set_tile, set_tap); };      // move the load stream to the next K-step
 
     f4u ra[4], rb[4], rx[HAS_X2 ? 4 : 1];
     auto gload_part = [&](int p) {
         if constexpr (X3) {
-            ra[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rA, voA[p >> 1] + (p & 1) * 16, sK, 0));
-            if (HAS_X2) rx[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rX, voX[p >> 1] + (p & 1) * 16, sK, 0));
+            ra[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rA, voA[p >> 1] + (p & 1) * 16, lp.sK, 0));
+            if (HAS_X2) rx[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rX, voX[p >> 1] + (p & 1) * 16, lp.sK, 0));
         } else {
-            ra[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rA, voA[p], sK, 0));
-            if (HAS_X2) rx[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rX, voX[p], sK, 0));
+            ra[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rA, voA[p], lp.sK, 0));
+            if (HAS_X2) rx[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rX, voX[p], lp.sK, 0));
         }
-        rb[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rB, voB[p], sB + sK, 0));
+        rb[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rB, voB[p], sB + lp.sK, 0));
     };
     auto lstore_x3 = [&](int buf, int p) {           // x3: row r8 + 64 p of A (X + X2 in f32, then the split), rows r0 + 32 (2 p), + 32 of W
         half8 hi, lo;
@@ -305,9 +243,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm(ConvArgs a)
     };
 
     // prologue: stage step 0 of the first tile
-    if (RT) prefetch_tab(l_q);
-    set_tile(l_q);
-    if (RT) { const int nq2 = next_sb(l_q); if (nq2 < sb_end) prefetch_tab(nq2); }
+    if (RT) prefetch_tab(q0);
+    set_tile(q0);
     set_tap(0);
     int m0c = m0l, n0c = n0l;
 #pragma unroll
@@ -334,7 +271,6 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm(ConvArgs a)
 
     int q = q0, s = 0, buf = 0;
     while (true) {
-        const int cb = (DBG == 3) ? 0 : buf;
         if constexpr (X3) {
             // six groups of 4 MFMAs per K-step (conv_gemm_h.hip's order: hi0*hi0, lo0*hi0, hi0*lo0, hi1*hi1, lo1*hi1, hi1*lo1); every group's
             // operands are read one group ahead; loads in group 1, the split and the restaging in groups 4 and 5
@@ -380,43 +316,40 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm(ConvArgs a)
             __builtin_amdgcn_sched_barrier(0);
         } else {
         // one K step.  On entry fragment set 0 holds K-group 0 of this step.  Inside each scheduling region the
-        // memory instructions are interleaved one by one with the MFMAs (sched_group_barrier: 0x008 MFMA, 0x020 VMEM
-        // read, 0x100 DS read, 0x200 DS write): a bunch of 4-8 back-to-back VMEM/DS issues takes longer than the 64
-        // cycles one MFMA keeps the pipe busy and leaves a bubble.
-#define SGB_PAIR(mask, n) do { _Pragma("unroll") for (int i_ = 0; i_ < (n); ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(mask, 1, 0); } } while (0)
-        lfrag(cb, 1, 1);
-        if (DBG < 2) { gload_part(0); gload_part(1); }
+        // memory instructions are interleaved one by one with the MFMAs (CONV_MFMA_PAIR).
+        lfrag(buf, 1, 1);
+        gload_part(0); gload_part(1);
         mma16(0);
-        SGB_PAIR(0x100, 4);
-        if (HAS_X2) { SGB_PAIR(0x020, 6); __builtin_amdgcn_sched_group_barrier(0x008, 6, 0); }
+        CONV_MFMA_PAIR(0x100, 4);
+        if (HAS_X2) { CONV_MFMA_PAIR(0x020, 6); __builtin_amdgcn_sched_group_barrier(0x008, 6, 0); }
         else {
 #pragma unroll
             for (int i_ = 0; i_ < 4; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 3, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); }
         }
         __builtin_amdgcn_sched_barrier(0);
-        lfrag(cb, 2, 0);
-        if (DBG < 2) { gload_part(2); gload_part(3); }
+        lfrag(buf, 2, 0);
+        gload_part(2); gload_part(3);
         mma16(1);
-        SGB_PAIR(0x100, 4);
-        if (HAS_X2) { SGB_PAIR(0x020, 6); __builtin_amdgcn_sched_group_barrier(0x008, 6, 0); }
+        CONV_MFMA_PAIR(0x100, 4);
+        if (HAS_X2) { CONV_MFMA_PAIR(0x020, 6); __builtin_amdgcn_sched_group_barrier(0x008, 6, 0); }
         else {
 #pragma unroll
             for (int i_ = 0; i_ < 4; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 3, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); }
         }
         __builtin_amdgcn_sched_barrier(0);
-        lfrag(cb, 3, 1);
-        if (DBG < 3) lstore(buf ^ 1);        // restage: the next step's tile slices go to the other LDS buffer
+        lfrag(buf, 3, 1);
+        lstore(buf ^ 1);                     // restage: the next step's tile slices go to the other LDS buffer
         mma16(0);
-        SGB_PAIR(0x100, 4);
-        SGB_PAIR(0x200, 8);
+        CONV_MFMA_PAIR(0x100, 4);
+        CONV_MFMA_PAIR(0x200, 8);
         __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
         __builtin_amdgcn_sched_barrier(0);
         // after the barrier the next step's K-group 0 is fetched while this step's last 16 MFMAs (operands already
         // in registers) run
-        if (DBG < 3) { __syncthreads(); lfrag(buf ^ 1, 0, 0); }
-        else lfrag(0, 0, 0);
+        __syncthreads();
+        lfrag(buf ^ 1, 0, 0);
         mma16(1);
-        SGB_PAIR(0x100, 4);
+        CONV_MFMA_PAIR(0x100, 4);
         __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
         __builtin_amdgcn_sched_barrier(0);
         }
@@ -429,16 +362,14 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm(ConvArgs a)
             // then each group of 4 registers (4 consecutive rows) is transposed inside its lane quad so
             // that a lane owns 4 consecutive columns of one row and stores one dwordx4 (16 wide stores
             // per lane and tile instead of 64 scalar ones).
-            float cb_[2] = {0.0f, 0.0f}, cs_[2] = {1.0f, 1.0f}, ch_[2] = {0.0f, 0.0f};
+            float cb_[2], cs_[2], ch_[2];
             int cco[2];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 cco[j] = n0c + wc * 64 + j * 32 + li;
-                const int cc = cco[j] < a.Cout ? cco[j] : a.Cout - 1;
-                if (a.bias) cb_[j] = a.bias[cc];
-                if (a.scale) { cs_[j] = a.scale[cc]; ch_[j] = a.shift[cc]; }
+                conv_col_params(a, cco[j] < a.Cout ? cco[j] : a.Cout - 1, cb_[j], cs_[j], ch_[j]);
             }
-            const float slope = (a.act1 == 1) ? 0.0f : ((a.act1 == 2) ? 0.01f : 1.0f);
+            const float slope = conv_act_slope(a.act1);
             const float as = X3 ? a.acc_scale : 1.0f;        // x3: the weights were scaled by a power of two (weights.cpp)
             const int b0 = RT ? 0 : m0c / a.TpOut, t0 = RT ? 0 : m0c - b0 * a.TpOut;      // wave-uniform
             const bool fast_rows = a.TpOut >= BM;
@@ -475,22 +406,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm(ConvArgs a)
                         if (wide) {
 #pragma unroll
                             for (int j = 0; j < 2; ++j) {
-                                // 4x4 transpose across the lane quad (two butterfly stages on DPP quad_perm)
-                                float s0 = (lq & 1) ? x[j][0] : x[j][1];
-                                float s1 = (lq & 1) ? x[j][2] : x[j][3];
-                                float r0_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s0), 0xB1, 0xF, 0xF, true));
-                                float r1_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s1), 0xB1, 0xF, 0xF, true));
-                                if (lq & 1) { x[j][0] = r0_; x[j][2] = r1_; } else { x[j][1] = r0_; x[j][3] = r1_; }
-                                s0 = (lq & 2) ? x[j][0] : x[j][2];
-                                s1 = (lq & 2) ? x[j][1] : x[j][3];
-                                r0_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s0), 0x4E, 0xF, 0xF, true));
-                                r1_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s1), 0x4E, 0xF, 0xF, true));
-                                if (lq & 2) { x[j][0] = r0_; x[j][1] = r1_; } else { x[j][2] = r0_; x[j][3] = r1_; }
+                                quad_transpose4(x[j][0], x[j][1], x[j][2], x[j][3], lq);
                                 const int g = m0c + wr * 64 + i * 32 + 8 * gq + 4 * lh + lq;
                                 const int co = n0c + wc * 64 + j * 32 + (li & ~3);
                                 if (g < a.M && co < a.Cout) {
-                                    if (DBG == 1) { if (x[j][0] == 12345.678f) a.Y[0] = x[j][1]; }
-                                    else if (F16 && !a.y_f32) {
+                                    if (F16 && !a.y_f32) {
                                         const half4 hv = {(_Float16)x[j][0], (_Float16)x[j][1], (_Float16)x[j][2], (_Float16)x[j][3]};
                                         *(half4*)((_Float16*)a.Y + (size_t)g * a.y_ld + co) = hv;
                                     } else *(float4*)(a.Y + (size_t)g * a.y_ld + co) = make_float4(x[j][0], x[j][1], x[j][2], x[j][3]);
@@ -515,38 +435,22 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm(ConvArgs a)
             };
             using T0 = std::integral_constant<int, 0>; using T1 = std::integral_constant<int, 1>; using T2 = std::integral_constant<int, 2>;
             // fast path (Res2Net, LSTM projections, linear layers): full column tiles, every row live, no per-item bias, no second
-            // activation -- each accumulator register is one output row for 32 consecutive columns across a half-wave and is stored as it
-            // lies (128 B per row and instruction, row term in the scalar offset, rows >= M dropped by the descriptor range): no lane
-            // transposes, no per-row index arithmetic (conv_gemm_h.hip's epilogue).  Same values as the general path.
-            if (DBG == 0 && wide && !a.item_bias && a.act2 == 0 && (a.Cout % BN) == 0 && (RT || a.T >= a.TpOut)) {
+            // activation -- rows stored as they lie (conv_store_rows, as in conv_gemm_h.hip).  Same values as the general path.
+            if (wide && !a.item_bias && a.act2 == 0 && (a.Cout % BN) == 0 && (RT || a.T >= a.TpOut)) {
                 const bool h16 = F16 && !a.y_f32;                    // fp16 mode: 2-byte elements (64 B per row and instruction)
                 const unsigned es = h16 ? 2u : 4u;
-                const int rows_left = a.M - m0c;
-                const __amdgpu_buffer_rsrc_t rY = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)a.Y + (size_t)m0c * a.y_ld * es), 0,
-                                                      (unsigned)((size_t)(rows_left < BM ? rows_left : BM) * a.y_ld * es), 0x00020000);
+                const __amdgpu_buffer_rsrc_t rY = conv_out_rsrc((char*)a.Y + (size_t)m0c * a.y_ld * es, a.M - m0c, BM, (size_t)a.y_ld * es);
                 const unsigned ybytes = (unsigned)a.y_ld * es;
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
+                for (int j = 0; j < 2; ++j)
 #pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        const unsigned vo = (unsigned)(wr * 64 + i * 32 + 4 * lh) * ybytes + (unsigned)cco[j] * es;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            float v = X3 ? acc[i][j][r] * as + cb_[j] : acc[i][j][r] + cb_[j];
-                            acc[i][j][r] = 0.0f;
-                            v = fmaxf(v, v * slope);
-                            v = v * cs_[j] + ch_[j];
-                            const unsigned so = (unsigned)((r & 3) + 8 * (r >> 2)) * ybytes;
-                            if (h16) __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (_Float16)v), rY, vo, so, 0);
-                            else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rY, vo, so, 0);
-                        }
-                    }
-                }
+                    for (int i = 0; i < 2; ++i)
+                        conv_store_rows<X3>(acc[i][j], rY, (unsigned)(wr * 64 + i * 32 + 4 * lh) * ybytes + (unsigned)cco[j] * es, ybytes, h16, as, cb_[j], slope, cs_[j], ch_[j]);
             } else
             if (a.item_bias) { if (a.act2 == 1) tile_out(std::true_type{}, T1{}); else if (a.act2 == 2) tile_out(std::true_type{}, T2{}); else tile_out(std::true_type{}, T0{}); }
             else { if (a.act2 == 1) tile_out(std::false_type{}, T1{}); else if (a.act2 == 2) tile_out(std::false_type{}, T2{}); else tile_out(std::false_type{}, T0{}); }
-            q = next_sb(q);
-            if (q >= sb_end) break;
+            q = sch.next(a, q);
+            if (q >= sch.sb_end) break;
             m0c = m0n; n0c = n0n; s = 0;
         } else {
             ++s;
@@ -605,7 +509,7 @@ __global__ __launch_bounds__(256) void k_skinny_gemm(ConvArgs a)
     const bool col_ok = co < a.Cout;
     const float cb = (a.bias && col_ok) ? a.bias[co] : 0.0f;
     const float cs = (a.scale && col_ok) ? a.scale[co] : 1.0f, ch = (a.scale && col_ok) ? a.shift[co] : 0.0f;
-    const float slope = (a.act1 == 1) ? 0.0f : ((a.act1 == 2) ? 0.01f : 1.0f);
+    const float slope = conv_act_slope(a.act1);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         float v = ((acc[r] + part[0][r][lane]) + part[1][r][lane]) + part[2][r][lane];      // fixed order: waves 0,1,2,3
@@ -657,13 +561,13 @@ int launch_conv_gemm(sd_ctx* c, const ConvArgs& in, const char* tag)
     ProfScope ps(c, c->profile_detail ? std::string("conv_gemm:") + tag : std::string("conv_gemm"), bill.flops, bill.bytes);
     ProfScope ps16(c, f16 ? "conv_gemm_f16" : x3 ? "conv_gemm_x3" : "conv_gemm_f32", bill.flops, bill.bytes);        // per precision (bench: roofline of the fp16 instantiations alone)
     if (f16) {
-        if (a.X2) hipLaunchKernelGGL((k_conv_gemm<true, 0, 1>), dim3(grid), dim3(256), 0, c->stream, a);
-        else hipLaunchKernelGGL((k_conv_gemm<false, 0, 1>), dim3(grid), dim3(256), 0, c->stream, a);
+        if (a.X2) hipLaunchKernelGGL((k_conv_gemm<true, 1>), dim3(grid), dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL((k_conv_gemm<false, 1>), dim3(grid), dim3(256), 0, c->stream, a);
     } else if (x3) {
-        if (a.X2) hipLaunchKernelGGL((k_conv_gemm<true, 0, 3>), dim3(grid), dim3(256), 0, c->stream, a);
-        else hipLaunchKernelGGL((k_conv_gemm<false, 0, 3>), dim3(grid), dim3(256), 0, c->stream, a);
-    } else if (a.X2) hipLaunchKernelGGL((k_conv_gemm<true, 0, 0>), dim3(grid), dim3(256), 0, c->stream, a);
-    else hipLaunchKernelGGL((k_conv_gemm<false, 0, 0>), dim3(grid), dim3(256), 0, c->stream, a);
+        if (a.X2) hipLaunchKernelGGL((k_conv_gemm<true, 3>), dim3(grid), dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL((k_conv_gemm<false, 3>), dim3(grid), dim3(256), 0, c->stream, a);
+    } else if (a.X2) hipLaunchKernelGGL((k_conv_gemm<true, 0>), dim3(grid), dim3(256), 0, c->stream, a);
+    else hipLaunchKernelGGL((k_conv_gemm<false, 0>), dim3(grid), dim3(256), 0, c->stream, a);
     KCHECK(c);
     return SD_OK;
 }
@@ -684,7 +588,10 @@ extern "C" int sd_bench_conv(sd_ctx* c, int64_t items, int Tp, int T, int Cin, i
     c->err.clear();
     if (hipSetDevice(c->device) != hipSuccess) return SD_ERR_HIP;
     const int64_t M = items * Tp;
-    const int pad = (dbg / 100) * 32;         // dbg = 100*pad_units + 10*(sched+1) + ablation: leading dimensions padded by pad floats
+    // dbg = 100 * pad_units + 10 * (sched + 1) + 0: leading dimensions padded by 32 * pad_units floats, schedule variant.  The last digit chose an ablation
+    // build of the kernel until those were retired; it has to be 0
+    if (dbg < 0 || dbg % 10 != 0) SD_FAIL(c, SD_ERR_ARG, "sd_bench_conv: ablation %d: the ablation builds of k_conv_gemm are retired", dbg % 10);
+    const int pad = (dbg / 100) * 32;
     dbg %= 100;
     const int xld = Cin + pad, wld = Cin + pad, yld = Cout + pad;
     WS(c, float, X, "bc_X", M * xld);
@@ -700,21 +607,14 @@ extern "C" int sd_bench_conv(sd_ctx* c, int64_t items, int Tp, int T, int Cin, i
     a.X = X; a.x_ld = xld; a.X2 = has_x2 ? X2 : nullptr; a.x2_ld = xld; a.W = W; a.w_ld = wld; a.Y = Y; a.y_ld = yld;
     a.bias = B; a.scale = B + Cout; a.shift = B + 2 * Cout; a.act1 = 1;
     a.M = (int)M; a.TpIn = a.TpOut = Tp; a.Tin = a.T = T; a.Cin = Cin; a.Cout = Cout; a.KT = KT; a.dil = dil; a.pad_mode = 0;
-    a.sched = (dbg >= 10) ? (dbg / 10 - 1) : SD_CONV_SCHED_DEFAULT;   // dbg = 10*(sched+1) + ablation
-    dbg %= 10;
+    a.sched = (dbg >= 10) ? (dbg / 10 - 1) : SD_CONV_SCHED_DEFAULT;
     const int grid = conv_tiles_grid(c, a, BM, BN, 2);
     hipEvent_t e0, e1;
     HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
-#define LAUNCH_V(X2, D) hipLaunchKernelGGL((k_conv_gemm<X2, D, 0>), dim3(grid), dim3(256), 0, c->stream, a)
-#ifdef SD_CONV_ABLATIONS      // make EXTRA=-DSD_CONV_ABLATIONS: 6 more instantiations of the kernel (minutes of compile time), tuning only
-#define LAUNCH_S(X2) do { if (dbg == 0) LAUNCH_V(X2, 0); else if (dbg == 1) LAUNCH_V(X2, 1); else if (dbg == 2) LAUNCH_V(X2, 2); else LAUNCH_V(X2, 3); } while (0)
-#else
-    if (dbg != 0) SD_FAIL(c, SD_ERR_ARG, "sd_bench_conv: ablation %d needs a build with -DSD_CONV_ABLATIONS", dbg);
-#define LAUNCH_S(X2) LAUNCH_V(X2, 0)
-#endif
     for (int r = -2; r < reps; ++r) {
         if (r == 0) HIPCHK(c, hipEventRecord(e0, c->stream));
-        if (has_x2) LAUNCH_S(true); else LAUNCH_S(false);
+        if (has_x2) hipLaunchKernelGGL((k_conv_gemm<true, 0>), dim3(grid), dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL((k_conv_gemm<false, 0>), dim3(grid), dim3(256), 0, c->stream, a);
     }
     HIPCHK(c, hipEventRecord(e1, c->stream));
     HIPCHK(c, hipEventSynchronize(e1));

@@ -23,36 +23,14 @@
 // then joins a raw s_barrier; the next buffer is read, and the released one re-filled, only behind that barrier.
 // Same arithmetic as the register-staged form: every output element sums the same products in the same order, so the two kernels
 // give the same bits (tests/test_gpu_parity.py::test_ecapa_fp16_lds_dma_staged_kernel_gives_the_same_bits).
-#include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+// Schedule, row map, row-table cursor, the LDS-DMA wrappers (and why they are inline assembly) and the epilogue pieces: conv_dev.h.
+#include "conv_dev.h"
 
 #define GM 256
 #define GN 256
 #define G_STAGE 65536          // bytes per stage: 256 A rows + 256 B rows of 128 B
 #define G_BOFF 32768
 #define G_STRIP 4096           // epilogue strip per wave: 16 rows x 128 channels of fp16 (128 + 32 KB = all of the CU's LDS)
-
-typedef __attribute__((address_space(3))) char lds_char;
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-// One LDS-DMA wave instruction: 64 x 16 bytes from the buffer `rs` (per-lane byte offset `vo`, scalar byte offset `so`) to the 1 KB of LDS at
-// `ldsaddr`.  Written as inline assembly on purpose: hipcc's waitcnt pass treats an LDS-DMA it knows about as a pending LDS store that ANY later
-// ds_read may alias and puts `s_waitcnt vmcnt(0)` in front of the next fragment read -- which would serialise exactly the overlap this
-// kernel exists for.  The waits that order these DMAs against the fragment reads are the explicit ones at the barrier (see the loop).
-// (`s_nop 4`: the descriptor words often come straight from v_readfirstlane, and an SGPR written by the vector ALU needs five wait states before a
-// vector-memory instruction reads it; hipcc counts them for its own instructions, not inside an asm string.)
-__device__ __forceinline__ void lds_dma_b32(v4i rs, unsigned ldsaddr, unsigned vo)       // 64 x 4 bytes -> 256 bytes of LDS
-{
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dword %1, %2, 0 offen lds" :: "s"(ldsaddr), "v"(vo), "s"(rs) : "memory");
-}
-__device__ __forceinline__ void lds_dma_b128(v4i rs, unsigned ldsaddr, unsigned vo, unsigned so)
-{
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(ldsaddr), "v"(vo), "s"(rs), "s"(so) : "memory");      // (m0 is reserved: the compiler does not keep values in it across statements)
-}
 
 // P = 1: fp16 tensors (v_mfma_f32_32x32x16_f16, a K-step is 64 halves).  P = 0: f32 tensors (v_mfma_f32_32x32x2_f32 over the k pairs (k, k + 16)
 // of a 32-float K-step, conv_gemm.hip's order: same bits as the 128 x 128 kernel and as conv_gemm_h.hip's register-staged form).  Either way a
@@ -63,28 +41,10 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
     constexpr int ES = P == 0 ? 4 : 2;               // bytes per element of X, W, Y
     extern __shared__ __attribute__((aligned(1024))) char lds[];
 
-    const int w = blockIdx.x, G = gridDim.x;         // G is a multiple of 8
-    const int xcd = w & 7, wl = w >> 3, wpx = G >> 3;
-    const int mx = (a.m_tiles - xcd + 7) >> 3;       // row panels of this XCD: m = xcd + 8 j
-    const int pnmax = a.sched > 0 ? a.sched : 4;
-    const int PN = a.n_tiles < pnmax ? a.n_tiles : pnmax;
-    const int PM = wpx / PN > 0 ? wpx / PN : 1;
-    const int pm = wl / PN, pn = wl - pm * PN;
-    if (pm >= PM) return;
-    const int n_groups = (a.n_tiles + PN - 1) / PN, m_groups = (mx + PM - 1) / PM;
-    const int sb_end = n_groups * m_groups;
-    auto sb_valid = [&](int sb, int& j, int& nt) -> bool {
-        const int mg = sb / n_groups, ng = sb - mg * n_groups;
-        j = mg * PM + pm; nt = ng * PN + pn;
-        return j < mx && nt < a.n_tiles;
-    };
-    auto next_sb = [&](int sb) -> int {
-        int j, nt;
-        for (++sb; sb < sb_end; ++sb) if (sb_valid(sb, j, nt)) return sb;
-        return sb_end;
-    };
-    const int q0 = next_sb(-1);
-    if (q0 >= sb_end) return;
+    ConvSched sch;
+    int q0;
+    if (!sch.init(a, a.sched > 0 ? a.sched : 4, q0)) return;
+    const int pm = sch.pm, pn = sch.pn;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wid = tid >> 6;
@@ -129,82 +89,45 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
     unsigned a_off[4], b_off[4];          // wave-uniform LDS offsets of the pieces inside a stage (SGPRs)
 #pragma unroll
     for (int p = 0; p < 4; ++p) { a_off[p] = __builtin_amdgcn_readfirstlane(a_lds(p)); b_off[p] = __builtin_amdgcn_readfirstlane((unsigned)G_BOFF + b_lds(p)); }
-    int rrel[4], tt[4], nd[4];
+    ConvRowTab<4> tab;
     unsigned voA[4], voB[4];
-    int2 pre[4]; int pre_base = 0;
-    auto prefetch_tab = [&](int sb) {
-        int j, nt;
-        (void)sb_valid(sb, j, nt);
-        const int m0 = __builtin_amdgcn_readfirstlane((xcd + 8 * j) * GM);
-        pre_base = a.rowtab[m0 < a.M ? m0 : a.M - 1].x;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) { int g = m0 + l_rowA(p); if (g > a.M - 1) g = a.M - 1; pre[p] = a.rowtab[g]; }
-    };
-    // raw buffer resource {base[31:0], base[47:32] (stride 0), bytes, flags} -- the words __builtin_amdgcn_make_buffer_rsrc builds
-    auto make_rsrc = [&](const void* base, size_t bytes) {
-        const unsigned long long b = (unsigned long long)base;
-        v4i r;
-        r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-        r[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)((b >> 32) & 0xffffu));
-        r[2] = __builtin_amdgcn_readfirstlane((int)(bytes > 0xffffffffull ? 0xffffffffu : (unsigned)bytes));
-        r[3] = 0x00020000;
-        return r;
-    };
-    v4i rA = make_rsrc(a.X, 0);
-    const v4i rB = make_rsrc(P == 0 ? (const void*)a.W : a.W16, (size_t)a.KT * a.Cout * a.w_ld * ES);
+    auto prefetch_tab = [&](int sb) { int m0, n0; sch.origin(a, sb, GM, GN, m0, n0); tab.prefetch(a, m0, l_rowA); };
+    v4i rA = conv_rsrc_sgpr(a.X, 0);
+    const v4i rB = conv_rsrc_sgpr(P == 0 ? (const void*)a.W : a.W16, (size_t)a.KT * a.Cout * a.w_ld * ES);
 #pragma unroll
     for (int p = 0; p < 4; ++p) voB[p] = (unsigned)(l_rowB(p) * a.w_ld * ES + l_chunkB(p) * 16);
-    int l_q = q0, l_kk = 0, l_kc = 0, m0l = 0, n0l = 0;
-    unsigned sK = 0, sB = 0;
-    auto set_tile = [&](int sb) {
-        int j, nt;
-        (void)sb_valid(sb, j, nt);
-        m0l = __builtin_amdgcn_readfirstlane((xcd + 8 * j) * GM);
-        n0l = __builtin_amdgcn_readfirstlane(nt * GN);
-        const int base = __builtin_amdgcn_readfirstlane(pre_base);
-#pragma unroll
-        for (int p = 0; p < 4; ++p) { rrel[p] = pre[p].x - base; tt[p] = ROWTAB_T(pre[p].y); nd[p] = ROWTAB_LAST(pre[p].y); }
-        rA = make_rsrc((const char*)a.X + (size_t)base * a.x_ld * ES, (in_rows - base) * a.x_ld * ES);
+    ConvLoadPos lp; lp.q = q0;
+    int m0l = 0, n0l = 0;
+    unsigned sB = 0;
+    auto set_tile = [&](int sb) {              // the stream enters a tile (its table entries were fetched a tile ago); asks for the next tile's
+        sch.origin(a, sb, GM, GN, m0l, n0l);
+        const int base = tab.enter();
+        rA = conv_rsrc_sgpr((const char*)a.X + (size_t)base * a.x_ld * ES, (in_rows - base) * a.x_ld * ES);
+        const int nq2 = sch.next(a, sb);
+        if (nq2 < sch.sb_end) prefetch_tab(nq2);
     };
     auto set_tap = [&](int kk) {
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            int qr = tt[p] + ((kk >= ktr ? kk - ktr : kk) - half) * a.dil;
-            if (qr < 0) qr = -qr;
-            if (qr >= a.Tin) qr = 2 * (a.Tin - 1) - qr;
-            if (qr < 0) qr = 0;
-            if (qr > nd[p]) qr = nd[p];
-            voA[p] = (unsigned)(rrel[p] + qr) * (unsigned)a.x_ld * ES + (unsigned)l_chunkA(p) * 16;
+            const int qr = conv_src_frame(tab.tt[p], kk, ktr, half, a.dil, a.Tin, tab.nd[p]);
+            voA[p] = (unsigned)(tab.rrel[p] + qr) * (unsigned)a.x_ld * ES + (unsigned)l_chunkA(p) * 16;
         }
         sB = (unsigned)(((size_t)kk * a.Cout + n0l) * a.w_ld * ES);
     };
-    auto advance = [&]() {
-        if (++l_kc < kcs) { sK += 128; return; }
-        l_kc = 0; sK = 0;
-        if (++l_kk == a.KT) {
-            l_kk = 0;
-            const int nq = next_sb(l_q);
-            if (nq < sb_end) {
-                l_q = nq; set_tile(l_q);
-                const int nq2 = next_sb(l_q);
-                if (nq2 < sb_end) prefetch_tab(nq2);
-            }
-        }
-        set_tap(l_kk);
-    };
+    auto advance = [&]() { lp.advance(a, sch, kcs, set_tile, set_tap); };
     // eight LDS-DMA instructions per wave and K-step: four 1 KB pieces of A, four of B
     const unsigned lds0 = (unsigned)(size_t)(lds_char*)lds;
     auto dma_piece = [&](int st, int p) {            // piece p of 8: A pieces 0..3, W pieces 4..7
         const unsigned stb = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(st * G_STAGE));
-        if (p < 4) lds_dma_b128(rA, stb + a_off[p], voA[p], sK);
-        else lds_dma_b128(rB, stb + b_off[p - 4], voB[p - 4], sB + sK);
+        if (p < 4) lds_dma_b128(rA, stb + a_off[p], voA[p], lp.sK);
+        else lds_dma_b128(rB, stb + b_off[p - 4], voB[p - 4], sB + lp.sK);
     };
     auto dma = [&](int st) {
         const unsigned stb = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(st * G_STAGE));
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            lds_dma_b128(rA, stb + a_off[p], voA[p], sK);
-            lds_dma_b128(rB, stb + b_off[p], voB[p], sB + sK);
+            lds_dma_b128(rA, stb + a_off[p], voA[p], lp.sK);
+            lds_dma_b128(rB, stb + b_off[p], voB[p], sB + lp.sK);
         }
     };
 
@@ -287,13 +210,12 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
     };
     // f32: the tile's 256 bias / BN scale / BN shift values go to LDS by LDS-DMA during the tile's LAST K-step (waves 0-3, 64 channels each, no
     // registers); that step's vmcnt(0) + barrier make them visible to the epilogue.  The area lies behind the stages (the fp16 form's strips).
-    const v4i rPb = make_rsrc(a.bias, (size_t)a.Cout * 4), rPs = make_rsrc(a.scale, (size_t)a.Cout * 4), rPh = make_rsrc(a.shift, (size_t)a.Cout * 4);
+    const v4i rPb = conv_rsrc_sgpr(a.bias, (size_t)a.Cout * 4), rPs = conv_rsrc_sgpr(a.scale, (size_t)a.Cout * 4), rPh = conv_rsrc_sgpr(a.shift, (size_t)a.Cout * 4);
     const float* const Ps = (const float*)(lds + 2 * G_STAGE);
 
     // prologue: steps 0 and 1 of the first tile are requested; step 0 has to be there
-    prefetch_tab(l_q);
-    set_tile(l_q);
-    { const int nq2 = next_sb(l_q); if (nq2 < sb_end) prefetch_tab(nq2); }
+    prefetch_tab(q0);
+    set_tile(q0);
     set_tap(0);
     int m0c = m0l, n0c = n0l;
     dma(0);
@@ -306,7 +228,6 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
 
     int q = q0, s = 0, buf = 0;
     while (true) {
-#define W_PAIR(mask, n) do { _Pragma("unroll") for (int i_ = 0; i_ < (n); ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(mask, 1, 0); } } while (0)
         // K-groups 0..2 of step s from stage `buf`; each group's fragments were read while the group before ran
         // MFMAs of a phase: the first carry the next phase's fragment reads (P = 2: four reads when the next phase keeps its activation fragments, eight otherwise)
         constexpr int NM = P == 0 ? 32 : P == 1 ? 8 : 16, NR_ODD = P == 2 ? 4 : 6, NR_EVEN = P == 2 ? 8 : 6;
@@ -320,15 +241,15 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
         }
         hfrag(buf, 1, 1);
         hmma(0, 0);
-        W_PAIR(0x100, NR_ODD); __builtin_amdgcn_sched_group_barrier(0x008, NM - NR_ODD, 0);
+        CONV_MFMA_PAIR(0x100, NR_ODD); __builtin_amdgcn_sched_group_barrier(0x008, NM - NR_ODD, 0);
         __builtin_amdgcn_sched_barrier(0);
         hfrag(buf, 2, 0);
         hmma(1, 1);
-        W_PAIR(0x100, NR_EVEN); __builtin_amdgcn_sched_group_barrier(0x008, NM - NR_EVEN, 0);
+        CONV_MFMA_PAIR(0x100, NR_EVEN); __builtin_amdgcn_sched_group_barrier(0x008, NM - NR_EVEN, 0);
         __builtin_amdgcn_sched_barrier(0);
         hfrag(buf, 3, 1);
         hmma(0, 2);
-        W_PAIR(0x100, NR_ODD); __builtin_amdgcn_sched_group_barrier(0x008, NM - NR_ODD, 0);
+        CONV_MFMA_PAIR(0x100, NR_ODD); __builtin_amdgcn_sched_group_barrier(0x008, NM - NR_ODD, 0);
         __builtin_amdgcn_sched_barrier(0);
         // stage `buf` has been read out (this wave's last fragments of it are in registers once lgkmcnt reaches 0) and this wave's
         // share of step s + 1 has landed in the other stage (vmcnt(0)): behind the barrier that holds for every wave
@@ -369,14 +290,10 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
             // wave, more than the 6-bit vmcnt can skip, so the next tile's first LDS restaging waits for all of them; here the stores stay
             // outstanding under the next tile's first K-step (vmcnt(32) at its barrier).]  Parameters come from LDS (Ps, filled by DMA).
             // The descriptor starts at the tile's first row and ends at the batch's last one: rows >= M are dropped by the range check.
-            const float slope = (a.act1 == 1) ? 0.0f : ((a.act1 == 2) ? 0.01f : 1.0f);
-            const int rows_left = a.M - m0c;
-            const __amdgpu_buffer_rsrc_t rY = __builtin_amdgcn_make_buffer_rsrc((void*)(a.Y + (size_t)m0c * a.y_ld), 0,
-                                                                               (unsigned)((size_t)(rows_left < GM ? rows_left : GM) * a.y_ld * 4), 0x00020000);
+            const float slope = conv_act_slope(a.act1);
+            const __amdgpu_buffer_rsrc_t rY = conv_out_rsrc(a.Y + (size_t)m0c * a.y_ld, a.M - m0c, GM, (size_t)a.y_ld * 4);
             const unsigned ybytes = (unsigned)a.y_ld * 4u;
             const bool hb_ = a.bias != nullptr, hs_ = a.scale != nullptr;
-            typedef unsigned u4 __attribute__((ext_vector_type(4)));
-            typedef float f4 __attribute__((ext_vector_type(4)));
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
 #pragma unroll
@@ -388,7 +305,7 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
                     const float cbv[4] = {cb.x, cb.y, cb.z, cb.w}, csv[4] = {cs.x, cs.y, cs.z, cs.w}, chv[4] = {ch.x, ch.y, ch.z, ch.w};
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {
-                        f4 o;
+                        f32x4 o;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             float v = acc[i][j][4 * gq + e] + cbv[e];
@@ -405,7 +322,7 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
             // ---- epilogue, 16 x 16 blocks.  C layout: register r of acc16[i][j], lane l = row 16 i + 4 (l >> 4) + r, column 16 j + (l & 15).
             // Same passage as the 32 x 32 form below: bias / activation / BatchNorm per value, a 4 x 4 transpose across the lane quad (four
             // consecutive columns of one row per lane), the wave's 4 KB strip sixteen rows (one i) at a time, whole rows back, 16-byte stores.
-            const float slope = (a.act1 == 1) ? 0.0f : ((a.act1 == 2) ? 0.01f : 1.0f);
+            const float slope = conv_act_slope(a.act1);
             const int lq = lane & 3;
             _Float16* const Y = (_Float16*)a.Y;
             char* const strip = lds + 2 * G_STAGE + wid * G_STRIP;               // [16 rows][256 bytes], 16-byte chunk c of row r at c ^ r
@@ -413,8 +330,7 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int cc = n0c + wc * 128 + j * 16 + l15;
-                cb[j] = a.bias ? a.bias[cc] : 0.0f;
-                cs[j] = a.scale ? a.scale[cc] : 1.0f; ch[j] = a.scale ? a.shift[cc] : 0.0f;
+                conv_col_params(a, cc, cb[j], cs[j], ch[j]);
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -428,16 +344,7 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
                         v = fmaxf(v, v * slope);
                         x[e] = v * cs[j] + ch[j];
                     }
-                    float s0 = (lq & 1) ? x[0] : x[1];
-                    float s1 = (lq & 1) ? x[2] : x[3];
-                    float r0_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s0), 0xB1, 0xF, 0xF, true));
-                    float r1_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s1), 0xB1, 0xF, 0xF, true));
-                    if (lq & 1) { x[0] = r0_; x[2] = r1_; } else { x[1] = r0_; x[3] = r1_; }
-                    s0 = (lq & 2) ? x[0] : x[2];
-                    s1 = (lq & 2) ? x[1] : x[3];
-                    r0_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s0), 0x4E, 0xF, 0xF, true));
-                    r1_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s1), 0x4E, 0xF, 0xF, true));
-                    if (lq & 2) { x[0] = r0_; x[1] = r1_; } else { x[2] = r0_; x[3] = r1_; }
+                    quad_transpose4(x[0], x[1], x[2], x[3], lq);
                     // the lane now holds row 4 (l >> 4) + lq of the block, columns 16 j + (l15 & ~3) .. + 3
                     const int sr = 4 * l4 + lq;
                     if (a.y_f32) {
@@ -467,7 +374,7 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
             // [Tried: the weight fragment as the MFMA's first operand, which hands every lane four consecutive channels of one row and
             // needs no cross-lane transposes -- but then a lane needs the bias / BatchNorm parameters of 64 channels instead of 4, and
             // fetching them inside the loop (3 dependent float4 loads per register group) cost more than the 3 VALU per value it saved.]
-            const float slope = (a.act1 == 1) ? 0.0f : ((a.act1 == 2) ? 0.01f : 1.0f);
+            const float slope = conv_act_slope(a.act1);
             const int lq = lane & 3;
             _Float16* const Y = (_Float16*)a.Y;
             char* const strip = lds + 2 * G_STAGE + wid * G_STRIP;               // [16 rows][256 bytes], 16-byte chunk c of row r at c ^ r
@@ -475,8 +382,7 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int cc = n0c + wc * 128 + j * 32 + li;
-                cb[j] = a.bias ? a.bias[cc] : 0.0f;
-                cs[j] = a.scale ? a.scale[cc] : 1.0f; ch[j] = a.scale ? a.shift[cc] : 0.0f;
+                conv_col_params(a, cc, cb[j], cs[j], ch[j]);
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -495,17 +401,7 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
                                 v = fmaxf(v, v * slope);
                                 x[e] = v * cs[j] + ch[j];
                             }
-                            // 4 x 4 transpose across the lane quad (two butterfly stages on DPP quad_perm)
-                            float s0 = (lq & 1) ? x[0] : x[1];
-                            float s1 = (lq & 1) ? x[2] : x[3];
-                            float r0_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s0), 0xB1, 0xF, 0xF, true));
-                            float r1_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s1), 0xB1, 0xF, 0xF, true));
-                            if (lq & 1) { x[0] = r0_; x[2] = r1_; } else { x[1] = r0_; x[3] = r1_; }
-                            s0 = (lq & 2) ? x[0] : x[2];
-                            s1 = (lq & 2) ? x[1] : x[3];
-                            r0_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s0), 0x4E, 0xF, 0xF, true));
-                            r1_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s1), 0x4E, 0xF, 0xF, true));
-                            if (lq & 2) { x[0] = r0_; x[1] = r1_; } else { x[2] = r0_; x[3] = r1_; }
+                            quad_transpose4(x[0], x[1], x[2], x[3], lq);
                             // the lane now holds row 8 g2 + 4 lh + lq of the strip, columns 32 j + (li & ~3) .. + 3
                             if (a.y_f32) {
                                 const int g = m0c + wr * 64 + i * 32 + 8 * gq + 4 * lh + lq;
@@ -532,9 +428,9 @@ __global__ __launch_bounds__(512) void k_conv_gemm_g256(ConvArgs a)
                 }
             }
             }
-            q = next_sb(q);
-            if (q >= sb_end) break;
-            { int j_, nt_; (void)sb_valid(q, j_, nt_); m0c = __builtin_amdgcn_readfirstlane((xcd + 8 * j_) * GM); n0c = __builtin_amdgcn_readfirstlane(nt_ * GN); }
+            q = sch.next(a, q);
+            if (q >= sch.sb_end) break;
+            sch.origin(a, q, GM, GN, m0c, n0c);
             s = 0;
         } else {
             ++s;

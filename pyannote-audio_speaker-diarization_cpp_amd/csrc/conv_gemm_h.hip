@@ -12,13 +12,9 @@
 // [tap][Cout][CinPad16] fp16, buffer loads with the K position as scalar offset, a load stream one K-step ahead that runs
 // across tile boundaries, persistent PM x PN super-blocks per XCD, f32 epilogue (bias, ReLU / leaky, folded BN) with the
 // 4 x 4 quad transpose and one rounding to fp16 at the store.  Only what the ECAPA layers need is implemented: compact row
-// space, "same" reflect padding, no second input, no per-item bias, no tanh / sigmoid.
-#include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+// space, "same" reflect padding, no second input, no per-item bias, no tanh / sigmoid.  Schedule, row map, row-table cursor and
+// the epilogue pieces are conv_dev.h's.
+#include "conv_dev.h"
 
 #define HM 256
 #define HN 256
@@ -41,30 +37,9 @@ __global__ __launch_bounds__(512) void k_conv_gemm_w256(ConvArgs a)
     float* const As0 = lds;                          // [2][HM * HLDP]
     float* const Bs0 = lds + 2 * HM * HLDP;          // [2][HN * HLDP]
 
-    const int w = blockIdx.x, G = gridDim.x;         // G is a multiple of 8
-    const int xcd = w & 7, wl = w >> 3, wpx = G >> 3;
-    const int mx = (a.m_tiles - xcd + 7) >> 3;       // row panels of this XCD: m = xcd + 8 j
-    // super-block shape (profiles/r02_layer_profile.txt): with 32 workgroups per XCD, 4 column tiles x 8 row panels beats 8 x 4 by a third
-    // on the 3072 x 3072 layer (each W K-slice is shared by 8 workgroups instead of 4; f32 137 vs 103 TF, fp16 962 vs 778 TF)
-    const int pnmax = a.sched > 0 ? a.sched : 4;
-    const int PN = a.n_tiles < pnmax ? a.n_tiles : pnmax;
-    const int PM = wpx / PN > 0 ? wpx / PN : 1;
-    const int pm = wl / PN, pn = wl - pm * PN;
-    if (pm >= PM) return;
-    const int n_groups = (a.n_tiles + PN - 1) / PN, m_groups = (mx + PM - 1) / PM;
-    const int sb_end = n_groups * m_groups;
-    auto sb_valid = [&](int sb, int& j, int& nt) -> bool {
-        const int mg = sb / n_groups, ng = sb - mg * n_groups;
-        j = mg * PM + pm; nt = ng * PN + pn;
-        return j < mx && nt < a.n_tiles;
-    };
-    auto next_sb = [&](int sb) -> int {
-        int j, nt;
-        for (++sb; sb < sb_end; ++sb) if (sb_valid(sb, j, nt)) return sb;
-        return sb_end;
-    };
-    const int q0 = next_sb(-1);
-    if (q0 >= sb_end) return;
+    ConvSched sch;
+    int q0;
+    if (!sch.init(a, a.sched > 0 ? a.sched : 4, q0)) return;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wid = tid >> 6;
@@ -83,77 +58,47 @@ __global__ __launch_bounds__(512) void k_conv_gemm_w256(ConvArgs a)
     constexpr int NPA = X ? 2 : 4;
     const int c8 = tid & 3, r8 = tid >> 2;
     auto a_row = [&](int p) { return X ? r8 + 128 * p : r0 + 64 * p; };
-    int rrel[NPA], tt[NPA], nd[NPA];
+    ConvRowTab<NPA> tab;
     unsigned voA[NPA], voB[4];
-    int2 pre[NPA]; int pre_base = 0;
-    auto prefetch_tab = [&](int sb) {
-        int j, nt;
-        (void)sb_valid(sb, j, nt);
-        const int m0 = __builtin_amdgcn_readfirstlane((xcd + 8 * j) * HM);
-        pre_base = a.rowtab[m0 < a.M ? m0 : a.M - 1].x;
-#pragma unroll
-        for (int p = 0; p < NPA; ++p) { int g = m0 + a_row(p); if (g > a.M - 1) g = a.M - 1; pre[p] = a.rowtab[g]; }
-    };
-    auto make_rsrc = [&](const void* base, size_t bytes) {
-        return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes > 0xffffffffull ? 0xffffffffu : (unsigned)bytes, 0x00020000);
-    };
-    __amdgpu_buffer_rsrc_t rA = make_rsrc(a.X, 0);
-    const __amdgpu_buffer_rsrc_t rB = make_rsrc(X ? a.W16x : H ? a.W16 : (const void*)a.W, (size_t)a.KT * a.Cout * a.w_ld * ESB);
+    auto prefetch_tab = [&](int sb) { int m0, n0; sch.origin(a, sb, HM, HN, m0, n0); tab.prefetch(a, m0, a_row); };
+    __amdgpu_buffer_rsrc_t rA = conv_rsrc(a.X, 0);
+    const __amdgpu_buffer_rsrc_t rB = conv_rsrc(X ? a.W16x : H ? a.W16 : (const void*)a.W, (size_t)a.KT * a.Cout * a.w_ld * ESB);
 #pragma unroll
     for (int p = 0; p < 4; ++p) voB[p] = (unsigned)((r0 + 64 * p) * a.w_ld * ESB + c4 * 16);
-    int l_q = q0, l_kk = 0, l_kc = 0, m0l = 0, n0l = 0;
-    unsigned sK = 0, sB = 0;
-    auto set_tile = [&](int sb) {
-        int j, nt;
-        (void)sb_valid(sb, j, nt);
-        m0l = __builtin_amdgcn_readfirstlane((xcd + 8 * j) * HM);
-        n0l = __builtin_amdgcn_readfirstlane(nt * HN);
-        const int base = __builtin_amdgcn_readfirstlane(pre_base);
-#pragma unroll
-        for (int p = 0; p < NPA; ++p) { rrel[p] = pre[p].x - base; tt[p] = ROWTAB_T(pre[p].y); nd[p] = ROWTAB_LAST(pre[p].y); }
-        rA = make_rsrc((const char*)a.X + (size_t)base * a.x_ld * ES, (in_rows - base) * a.x_ld * ES);
+    ConvLoadPos lp; lp.q = q0;
+    int m0l = 0, n0l = 0;
+    unsigned sB = 0;
+    auto set_tile = [&](int sb) {              // the stream enters a tile (its table entries were fetched a tile ago); asks for the next tile's
+        sch.origin(a, sb, HM, HN, m0l, n0l);
+        const int base = tab.enter();
+        rA = conv_rsrc((const char*)a.X + (size_t)base * a.x_ld * ES, (in_rows - base) * a.x_ld * ES);
+        const int nq2 = sch.next(a, sb);
+        if (nq2 < sch.sb_end) prefetch_tab(nq2);
     };
     auto set_tap = [&](int kk) {
 #pragma unroll
         for (int p = 0; p < NPA; ++p) {
-            int qr = tt[p] + ((kk >= ktr ? kk - ktr : kk) - half) * a.dil;
-            if (qr < 0) qr = -qr;
-            if (qr >= a.Tin) qr = 2 * (a.Tin - 1) - qr;
-            if (qr < 0) qr = 0;
-            if (qr > nd[p]) qr = nd[p];
-            voA[p] = (unsigned)(rrel[p] + qr) * (unsigned)a.x_ld * ES + (X ? c8 * 32 : c4 * 16);
+            const int qr = conv_src_frame(tab.tt[p], kk, ktr, half, a.dil, a.Tin, tab.nd[p]);
+            voA[p] = (unsigned)(tab.rrel[p] + qr) * (unsigned)a.x_ld * ES + (X ? c8 * 32 : c4 * 16);
         }
         // weight rows beyond Cout (a 256-wide tile over Cout = 1024 / 3072 never has any) are clamped by the descriptor
         sB = (unsigned)(((size_t)kk * a.Cout + n0l) * a.w_ld * ESB);
     };
-    auto advance = [&]() {
-        if (++l_kc < kcs) { sK += 128; return; }
-        l_kc = 0; sK = 0;
-        if (++l_kk == a.KT) {
-            l_kk = 0;
-            const int nq = next_sb(l_q);
-            if (nq < sb_end) {
-                l_q = nq; set_tile(l_q);
-                const int nq2 = next_sb(l_q);
-                if (nq2 < sb_end) prefetch_tab(nq2);
-            }
-        }
-        set_tap(l_kk);
-    };
+    auto advance = [&]() { lp.advance(a, sch, kcs, set_tile, set_tap); };
     f4u ra[4], rb[4];
     auto gload = [&]() {
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            if constexpr (X) ra[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rA, voA[p >> 1] + (p & 1) * 16, sK, 0));
-            else ra[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rA, voA[p], sK, 0));
-            rb[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rB, voB[p], sB + sK, 0));
+            if constexpr (X) ra[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rA, voA[p >> 1] + (p & 1) * 16, lp.sK, 0));
+            else ra[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rA, voA[p], lp.sK, 0));
+            rb[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rB, voB[p], sB + lp.sK, 0));
         }
     };
     auto gload_half = [&](int h) {                    // x3: the loader registers of restaging part h (row r8 + 128 h of A, two W rows)
 #pragma unroll
         for (int p = 2 * h; p < 2 * h + 2; ++p) {
-            ra[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rA, voA[p >> 1] + (p & 1) * 16, sK, 0));
-            rb[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rB, voB[p], sB + sK, 0));
+            ra[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rA, voA[p >> 1] + (p & 1) * 16, lp.sK, 0));
+            rb[p] = __builtin_bit_cast(f4u, __builtin_amdgcn_raw_buffer_load_b128(rB, voB[p], sB + lp.sK, 0));
         }
     };
     auto lstore_part = [&](int buf, int p) {          // x3: row r8 + 128 p of A (the split), rows r0 + 64 (2 p), r0 + 64 (2 p + 1) of W
@@ -241,9 +186,8 @@ __global__ __launch_bounds__(512) void k_conv_gemm_w256(ConvArgs a)
     };
 
     // prologue: stage step 0 of the first tile
-    prefetch_tab(l_q);
-    set_tile(l_q);
-    { const int nq2 = next_sb(l_q); if (nq2 < sb_end) prefetch_tab(nq2); }
+    prefetch_tab(q0);
+    set_tile(q0);
     set_tap(0);
     int m0c = m0l, n0c = n0l;
     gload();
@@ -261,8 +205,7 @@ __global__ __launch_bounds__(512) void k_conv_gemm_w256(ConvArgs a)
         // end of the region -- one MFMA in front of their first use -- and the eight ds_writes to the last three MFMAs in front of
         // the barrier, so every group boundary and every barrier waits on LDS latency with an empty matrix pipe (13 % of the
         // cycles, profiles/pmc_conv_gemm_bench.json).  sched_group_barrier pins them behind the FIRST MFMAs of the region, one
-        // memory instruction per MFMA (masks: 0x008 MFMA, 0x020 VMEM read, 0x100 DS read, 0x200 DS write).
-#define W_PAIR(mask, n) do { _Pragma("unroll") for (int i_ = 0; i_ < (n); ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(mask, 1, 0); } } while (0)
+        // memory instruction per MFMA (CONV_MFMA_PAIR).
         if constexpr (X) {
             // x3: six groups of 8 MFMAs per K-step.  Fragment registers A0 / W0 hold hi block 0 of this step on entry; every group's operands
             // are read one group ahead into the registers the group before last released.  The load stream runs TWO steps ahead: on entry the
@@ -272,14 +215,14 @@ __global__ __launch_bounds__(512) void k_conv_gemm_w256(ConvArgs a)
             // global loads, 115 ms without restaging and barrier = the MFMA + fragment-read floor]
             afrag(buf, 2, 1);                      // lo block 0 of A
             xmma(0, 0);                            // hi0 * hi0
-            W_PAIR(0x100, 2); __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
+            CONV_MFMA_PAIR(0x100, 2); __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
             __builtin_amdgcn_sched_barrier(0);
             bfrag(buf, 2, 1);                      // lo block 0 of W
             xmma(1, 0);                            // lo0 * hi0
             lstore_part(buf ^ 1, 0);
             // the split of a row's eight channels is ~28 VALU instructions, and there are four LDS writes: left alone they all sit behind the
             // group's last MFMA
-            W_PAIR(0x100, 4);
+            CONV_MFMA_PAIR(0x100, 4);
 #pragma unroll
             for (int i_ = 0; i_ < 3; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 10, 0); }
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x200, 4, 0);
@@ -287,14 +230,14 @@ __global__ __launch_bounds__(512) void k_conv_gemm_w256(ConvArgs a)
             afrag(buf, 1, 1); bfrag(buf, 1, 0);    // hi block 1 of both
             xmma(0, 1);                            // hi0 * lo0
             gload_half(0);
-            W_PAIR(0x100, 6);
+            CONV_MFMA_PAIR(0x100, 6);
 #pragma unroll
             for (int i_ = 0; i_ < 2; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x020, 2, 0); }
             __builtin_amdgcn_sched_barrier(0);
             afrag(buf, 3, 0);                      // lo block 1 of A
             xmma(1, 0);                            // hi1 * hi1
             lstore_part(buf ^ 1, 1);
-            W_PAIR(0x100, 2);
+            CONV_MFMA_PAIR(0x100, 2);
 #pragma unroll
             for (int i_ = 0; i_ < 4; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 8, 0); }
 #pragma unroll
@@ -303,7 +246,7 @@ __global__ __launch_bounds__(512) void k_conv_gemm_w256(ConvArgs a)
             bfrag(buf, 3, 1);                      // lo block 1 of W
             xmma(0, 0);                            // lo1 * hi1
             gload_half(1);
-            W_PAIR(0x100, 4);
+            CONV_MFMA_PAIR(0x100, 4);
 #pragma unroll
             for (int i_ = 0; i_ < 2; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x020, 2, 0); }
             __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
@@ -311,34 +254,34 @@ __global__ __launch_bounds__(512) void k_conv_gemm_w256(ConvArgs a)
             __syncthreads();
             afrag(buf ^ 1, 0, 0); bfrag(buf ^ 1, 0, 0);
             xmma(1, 1);                            // hi1 * lo1
-            W_PAIR(0x100, 6); __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            CONV_MFMA_PAIR(0x100, 6); __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
             __builtin_amdgcn_sched_barrier(0);
         } else {
         hfrag(buf, 1, 1);
         gload();
         hmma(0);
         if constexpr (!H) {
-            W_PAIR(0x100, 6);
+            CONV_MFMA_PAIR(0x100, 6);
 #pragma unroll
             for (int i_ = 0; i_ < 8; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); }
             __builtin_amdgcn_sched_group_barrier(0x008, 10, 0);
         } else {
             // fp16: a K-group is 8 MFMAs of 32 cycles; same rule, the eight loads / stores ride behind the last two MFMAs
-            W_PAIR(0x100, 6);
+            CONV_MFMA_PAIR(0x100, 6);
 #pragma unroll
             for (int i_ = 0; i_ < 2; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x020, 4, 0); }
         }
         __builtin_amdgcn_sched_barrier(0);
         hfrag(buf, 2, 0);
         hmma(1);
-        W_PAIR(0x100, 6); __builtin_amdgcn_sched_group_barrier(0x008, H ? 2 : 26, 0);
+        CONV_MFMA_PAIR(0x100, 6); __builtin_amdgcn_sched_group_barrier(0x008, H ? 2 : 26, 0);
         __builtin_amdgcn_sched_barrier(0);
         hfrag(buf, 3, 1);
         hmma(0);
         lstore(buf ^ 1);
-        if constexpr (!H) { W_PAIR(0x100, 6); W_PAIR(0x200, 8); __builtin_amdgcn_sched_group_barrier(0x008, 18, 0); }
+        if constexpr (!H) { CONV_MFMA_PAIR(0x100, 6); CONV_MFMA_PAIR(0x200, 8); __builtin_amdgcn_sched_group_barrier(0x008, 18, 0); }
         else {
-            W_PAIR(0x100, 6);
+            CONV_MFMA_PAIR(0x100, 6);
 #pragma unroll
             for (int i_ = 0; i_ < 2; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x200, 4, 0); }
         }
@@ -346,40 +289,27 @@ __global__ __launch_bounds__(512) void k_conv_gemm_w256(ConvArgs a)
         __syncthreads();
         hfrag(buf ^ 1, 0, 0);
         hmma(1);
-        W_PAIR(0x100, 6); __builtin_amdgcn_sched_group_barrier(0x008, H ? 2 : 26, 0);
+        CONV_MFMA_PAIR(0x100, 6); __builtin_amdgcn_sched_group_barrier(0x008, H ? 2 : 26, 0);
         __builtin_amdgcn_sched_barrier(0);
         }
         advance();            // (x3: the load stream now stands two steps ahead of the step that starts next)
 
         if (s == S - 1) {
             // ---- epilogue.  C layout: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5); see conv_gemm.hip
-            const float slope = (a.act1 == 1) ? 0.0f : ((a.act1 == 2) ? 0.01f : 1.0f);
+            const float slope = conv_act_slope(a.act1);
             if constexpr (!H) {
                 const float as = X ? a.acc_scale : 1.0f;
-                // f32 (and x3): every accumulator register is one output row for 32 consecutive columns across a half-wave: stored as it
-                // lies, 128 contiguous bytes per row and instruction, no lane transposes (half the epilogue's VALU work).  The
-                // descriptor starts at the tile's first row and ends at the batch's last one, so rows >= M are dropped by the range
-                // check; the row term travels in the scalar offset.
-                const int rows_left = a.M - m0c;
-                const __amdgpu_buffer_rsrc_t rY = make_rsrc(a.Y + (size_t)m0c * a.y_ld, (size_t)(rows_left < HM ? rows_left : HM) * a.y_ld * 4);
+                // f32 (and x3): rows stored as they lie (conv_store_rows: half the epilogue's VALU work of the transposing form)
+                const __amdgpu_buffer_rsrc_t rY = conv_out_rsrc(a.Y + (size_t)m0c * a.y_ld, a.M - m0c, HM, (size_t)a.y_ld * 4);
                 const unsigned ybytes = (unsigned)a.y_ld * 4u;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int cc = n0c + wc * 128 + j * 32 + li;
-                    const float cb = a.bias ? a.bias[cc] : 0.0f;
-                    const float cs = a.scale ? a.scale[cc] : 1.0f, ch = a.scale ? a.shift[cc] : 0.0f;
+                    float cb, cs, ch;
+                    conv_col_params(a, cc, cb, cs, ch);
 #pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        const unsigned vo = (unsigned)(wr * 64 + i * 32 + 4 * lh) * ybytes + (unsigned)cc * 4u;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            float v = X ? acc[i][j][r] * as + cb : acc[i][j][r] + cb;
-                            acc[i][j][r] = 0.0f;
-                            v = fmaxf(v, v * slope);
-                            v = v * cs + ch;
-                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rY, vo, (unsigned)((r & 3) + 8 * (r >> 2)) * ybytes, 0);
-                        }
-                    }
+                    for (int i = 0; i < 2; ++i)
+                        conv_store_rows<X>(acc[i][j], rY, (unsigned)(wr * 64 + i * 32 + 4 * lh) * ybytes + (unsigned)cc * 4u, ybytes, false, as, cb, slope, cs, ch);
                 }
             } else {
             const int lq = lane & 3;
@@ -388,8 +318,8 @@ __global__ __launch_bounds__(512) void k_conv_gemm_w256(ConvArgs a)
             for (int j = 0; j < 4; ++j) {
                 const int cc = n0c + wc * 128 + j * 32 + li;
                 const int ccl = cc < a.Cout ? cc : a.Cout - 1;
-                const float cb = a.bias ? a.bias[ccl] : 0.0f;
-                const float cs = a.scale ? a.scale[ccl] : 1.0f, ch = a.scale ? a.shift[ccl] : 0.0f;
+                float cb, cs, ch;
+                conv_col_params(a, ccl, cb, cs, ch);
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -402,17 +332,7 @@ __global__ __launch_bounds__(512) void k_conv_gemm_w256(ConvArgs a)
                             v = fmaxf(v, v * slope);
                             x[e] = v * cs + ch;
                         }
-                        // 4 x 4 transpose across the lane quad (two butterfly stages on DPP quad_perm)
-                        float s0 = (lq & 1) ? x[0] : x[1];
-                        float s1 = (lq & 1) ? x[2] : x[3];
-                        float r0_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s0), 0xB1, 0xF, 0xF, true));
-                        float r1_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s1), 0xB1, 0xF, 0xF, true));
-                        if (lq & 1) { x[0] = r0_; x[2] = r1_; } else { x[1] = r0_; x[3] = r1_; }
-                        s0 = (lq & 2) ? x[0] : x[2];
-                        s1 = (lq & 2) ? x[1] : x[3];
-                        r0_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s0), 0x4E, 0xF, 0xF, true));
-                        r1_ = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s1), 0x4E, 0xF, 0xF, true));
-                        if (lq & 2) { x[0] = r0_; x[1] = r1_; } else { x[2] = r0_; x[3] = r1_; }
+                        quad_transpose4(x[0], x[1], x[2], x[3], lq);
                         const int g = m0c + wr * 64 + i * 32 + 8 * gq + 4 * lh + lq;
                         const int co = n0c + wc * 128 + j * 32 + (li & ~3);
                         if (g < a.M && co < a.Cout) {
@@ -426,9 +346,9 @@ __global__ __launch_bounds__(512) void k_conv_gemm_w256(ConvArgs a)
                 }
             }
             }
-            q = next_sb(q);
-            if (q >= sb_end) break;
-            { int j_, nt_; (void)sb_valid(q, j_, nt_); m0c = __builtin_amdgcn_readfirstlane((xcd + 8 * j_) * HM); n0c = __builtin_amdgcn_readfirstlane(nt_ * HN); }
+            q = sch.next(a, q);
+            if (q >= sch.sb_end) break;
+            sch.origin(a, q, HM, HN, m0c, n0c);
             s = 0;
         } else {
             ++s;

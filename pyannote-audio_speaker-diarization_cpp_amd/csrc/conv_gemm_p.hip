@@ -34,35 +34,16 @@
 // kernels are compared bit for bit (tests/test_gpu_parity.py::test_ecapa_fp16_ping_pong_kernel_gives_the_same_bits).
 // Takes fp16 tensors only (prec 1), row-table layers without second input / per-item bias / residual / second activation; everything else stays
 // with conv_gemm_g.hip / conv_gemm_h.hip.
-#include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) char lds_char;
+//
+// From conv_dev.h this kernel takes the schedule, the row map of a tap and the buffer-resource / LDS-DMA wrappers only: its row table entries live in LDS, not in
+// a register cursor, and its register allocation does not survive reordering (see the spill notes below).
+#include "conv_dev.h"
 
 #define P_HALF 16384           // a half-tile: 128 rows x 128 B
 #define P_BUF 65536            // A half 0, A half 1, B half 0, B half 1
 #define P_PAR (2 * P_BUF)      // parameters: 8 waves x 2 areas x 1 KB ([bias | scale | shift][16 groups of 4 channels])
 #define P_TAB (P_PAR + 16384)  // row table entries: 8 waves x 2 slots x 256 B ([half][16 rows] int2)
 #define P_LDS (P_TAB + 4096)
-
-// One LDS-DMA wave instruction (inline assembly on purpose: see conv_gemm_g.hip -- hipcc would put vmcnt(0) in front of the next ds_read).
-__device__ __forceinline__ void pp_dma_b128(v4i rs, unsigned ldsaddr, unsigned vo)
-{
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" :: "s"(ldsaddr), "v"(vo), "s"(rs) : "memory");
-}
-__device__ __forceinline__ v4i pp_rsrc(const void* base, size_t bytes)
-{
-    const unsigned long long b = (unsigned long long)base;
-    v4i r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    r[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)((b >> 32) & 0xffffu));
-    r[2] = __builtin_amdgcn_readfirstlane((int)(bytes > 0xffffffffull ? 0xffffffffu : (unsigned)bytes));
-    r[3] = 0x00020000;
-    return r;
-}
 
 #define PP_FENCE() __builtin_amdgcn_sched_barrier(0)
 // Behind every 16-byte store of the epilogue: with an SGPR soffset (this kernel's stores have one for nh = 1) hipcc leaves NO wait state between the store
@@ -77,28 +58,9 @@ template <bool RELU>
 __global__ __launch_bounds__(512) void k_conv_gemm_pp(ConvArgs a)
 {
     extern __shared__ __attribute__((aligned(1024))) char lds[];
-    const int w = blockIdx.x, G = gridDim.x;         // G is a multiple of 8
-    const int xcd = w & 7, wl = w >> 3, wpx = G >> 3;
-    const int mx = (a.m_tiles - xcd + 7) >> 3;       // row panels of this XCD: m = xcd + 8 j
-    const int pnmax = a.sched > 0 ? a.sched : 4;
-    const int PN = a.n_tiles < pnmax ? a.n_tiles : pnmax;
-    const int PM = wpx / PN > 0 ? wpx / PN : 1;
-    const int pm = wl / PN, pn = wl - pm * PN;
-    if (pm >= PM) return;
-    const int n_groups = (a.n_tiles + PN - 1) / PN, m_groups = (mx + PM - 1) / PM;
-    const int sb_end = n_groups * m_groups;
-    auto sb_valid = [&](int sb, int& j, int& nt) -> bool {
-        const int mg = sb / n_groups, ng = sb - mg * n_groups;
-        j = mg * PM + pm; nt = ng * PN + pn;
-        return j < mx && nt < a.n_tiles;
-    };
-    auto next_sb = [&](int sb) -> int {
-        int j, nt;
-        for (++sb; sb < sb_end; ++sb) if (sb_valid(sb, j, nt)) return sb;
-        return sb_end;
-    };
-    const int q0 = next_sb(-1);
-    if (q0 >= sb_end) return;
+    ConvSched sch;
+    int q0;
+    if (!sch.init(a, a.sched > 0 ? a.sched : 4, q0)) return;
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = wid >> 2, wc = wid & 3;
@@ -128,7 +90,7 @@ __global__ __launch_bounds__(512) void k_conv_gemm_pp(ConvArgs a)
     const unsigned dstw = __builtin_amdgcn_readfirstlane((unsigned)(wid * 2048));
     const unsigned tab0 = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(P_TAB + wid * 512));
     const unsigned par0 = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(P_PAR + wid * 2048));
-    const v4i rTab = pp_rsrc(a.rowtab, (size_t)a.M * 8);      // rows >= M read as {0, 0}: any valid address will do, their outputs are never stored
+    const v4i rTab = conv_rsrc_sgpr(a.rowtab, (size_t)a.M * 8);      // rows >= M read as {0, 0}: any valid address will do, their outputs are never stored
 
     // Two cursors walk the workgroup's stream of K-tiles (tile, tap kk, channel chunk kc): cB = the K-tile after the one being multiplied (its B pieces
     // go out in phase X), cA = the one after that (its A pieces go out in phase Y; it keeps the row offsets of the A rows this wave stages).
@@ -136,10 +98,10 @@ __global__ __launch_bounds__(512) void k_conv_gemm_pp(ConvArgs a)
         int sb, kk, kc, m0, n0, base, tiles;         // base: first input row of the tile's first item (the buffer descriptor starts there)
         unsigned vo[4];                              // cA, per piece q = 2 h + p: byte offset of the row the lane stages, from the descriptor's base (cur_tap)
     };
-    auto tile_of = [&](int sb, int& m0, int& n0) { int j, nt; (void)sb_valid(sb, j, nt); m0 = __builtin_amdgcn_readfirstlane((xcd + 8 * j) * 256); n0 = __builtin_amdgcn_readfirstlane(nt * 256); };
+    auto tile_of = [&](int sb, int& m0, int& n0) { sch.origin(a, sb, 256, 256, m0, n0); };
     auto table_dma = [&](int m0, int slot) {         // this wave's 32 rows of tile m0: lanes 0-7 rows 16 wid .. + 15 of half 0 (two entries each), lanes 8-15 of half 1
         const unsigned dst = __builtin_amdgcn_readfirstlane(tab0 + (unsigned)(slot * 256));
-        if (lane < 16) pp_dma_b128(rTab, dst, (unsigned)(m0 + 128 * (lane >> 3) + 16 * wid + 2 * (lane & 7)) * 8u);
+        if (lane < 16) lds_dma_b128(rTab, dst, (unsigned)(m0 + 128 * (lane >> 3) + 16 * wid + 2 * (lane & 7)) * 8u);
     };
     auto cur_rows = [&](Cur& c) {                    // entries of the tile the cursor has just entered (its table slot was filled a tile ago)
         const int m0c = c.m0 < a.M ? c.m0 : a.M - 1;
@@ -157,12 +119,7 @@ __global__ __launch_bounds__(512) void k_conv_gemm_pp(ConvArgs a)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int2 e = tb[(q >> 1) * 16 + (q & 1) * 8 + prow];
-            int qr = ROWTAB_T(e.y) + ((c.kk >= ktr ? c.kk - ktr : c.kk) - half) * a.dil;
-            const int nd = ROWTAB_LAST(e.y);
-            if (qr < 0) qr = -qr;
-            if (qr >= a.Tin) qr = 2 * (a.Tin - 1) - qr;
-            if (qr < 0) qr = 0;
-            if (qr > nd) qr = nd;
+            const int qr = conv_src_frame(ROWTAB_T(e.y), c.kk, ktr, half, a.dil, a.Tin, ROWTAB_LAST(e.y));
             c.vo[q] = (unsigned)(e.x - c.base + qr) * (unsigned)a.x_ld * 2u + chk[q & 1];
         }
     };
@@ -172,8 +129,8 @@ __global__ __launch_bounds__(512) void k_conv_gemm_pp(ConvArgs a)
         c.kc = 0;
         if (++c.kk < a.KT) { if (is_a) cur_tap(c); return false; }
         c.kk = 0;
-        const int nq = next_sb(c.sb);
-        if (nq >= sb_end) { if (is_a) cur_tap(c); return false; }          // past the last tile: the stream re-reads the last tile (never multiplied)
+        const int nq = sch.next(a, c.sb);
+        if (nq >= sch.sb_end) { if (is_a) cur_tap(c); return false; }          // past the last tile: the stream re-reads the last tile (never multiplied)
         c.sb = nq; ++c.tiles;
         tile_of(nq, c.m0, c.n0);
         if (is_a) { cur_rows(c); cur_tap(c); }
@@ -181,24 +138,24 @@ __global__ __launch_bounds__(512) void k_conv_gemm_pp(ConvArgs a)
     };
     // piece q = 0 .. 3 of the wave's share of a K-tile's A (B): half q >> 1, piece q & 1
     auto dmaA = [&](const Cur& c, int buf, int q) {
-        const v4i rs = pp_rsrc(X + ((size_t)c.base * a.x_ld + (size_t)c.kc * 64), (in_rows - (size_t)c.base) * a.x_ld * 2);
+        const v4i rs = conv_rsrc_sgpr(X + ((size_t)c.base * a.x_ld + (size_t)c.kc * 64), (in_rows - (size_t)c.base) * a.x_ld * 2);
         const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(buf * P_BUF + (q >> 1) * P_HALF + (q & 1) * 1024) + dstw);
-        pp_dma_b128(rs, dst, c.vo[q]);
+        lds_dma_b128(rs, dst, c.vo[q]);
     };
     auto dmaB = [&](const Cur& c, int buf, int q) {
-        const v4i rs = pp_rsrc(W16 + (((size_t)c.kk * a.Cout + c.n0 + 128 * (q >> 1)) * a.w_ld + (size_t)c.kc * 64), 0xffffffffull);
+        const v4i rs = conv_rsrc_sgpr(W16 + (((size_t)c.kk * a.Cout + c.n0 + 128 * (q >> 1)) * a.w_ld + (size_t)c.kc * 64), 0xffffffffull);
         const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(buf * P_BUF + (2 + (q >> 1)) * P_HALF + (q & 1) * 1024) + dstw);
-        pp_dma_b128(rs, dst, voB[q & 1]);
+        lds_dma_b128(rs, dst, voB[q & 1]);
     };
     // parameters of the wave's 64 channels: lane k < 16 of DMA `arr` fetches channels 128 (k >> 3) + 32 wc + 4 (k & 7) .. + 3 -> floats [arr][k][4] of the area
     const unsigned voP = (unsigned)(128 * ((lane & 15) >> 3) + 32 * wc + 4 * (lane & 7)) * 4u;
     auto stageP = [&](int n0, int par) {
         const unsigned dst = __builtin_amdgcn_readfirstlane(par0 + (unsigned)(par * 1024));
-        const v4i rb = pp_rsrc(a.bias + n0, (size_t)(a.Cout - n0) * 4), rc = pp_rsrc(a.scale + n0, (size_t)(a.Cout - n0) * 4), rh = pp_rsrc(a.shift + n0, (size_t)(a.Cout - n0) * 4);
+        const v4i rb = conv_rsrc_sgpr(a.bias + n0, (size_t)(a.Cout - n0) * 4), rc = conv_rsrc_sgpr(a.scale + n0, (size_t)(a.Cout - n0) * 4), rh = conv_rsrc_sgpr(a.shift + n0, (size_t)(a.Cout - n0) * 4);
         if (lane < 16) {
-            pp_dma_b128(rb, dst, voP);
-            pp_dma_b128(rc, dst + 256, voP);
-            pp_dma_b128(rh, dst + 512, voP);
+            lds_dma_b128(rb, dst, voP);
+            lds_dma_b128(rc, dst + 256, voP);
+            lds_dma_b128(rh, dst + 512, voP);
         }
     };
 
@@ -229,7 +186,7 @@ __global__ __launch_bounds__(512) void k_conv_gemm_pp(ConvArgs a)
                 acc[2 * sg + r2][C] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, fb[ks][C]), __builtin_bit_cast(half8, fa[ks][2 * sg + r2]), acc[2 * sg + r2][C], 0, 0, 0);
     };
     // one epilogue chunk: row block R (rows 128 (R >> 2) + 64 g + 16 (R & 3) + l15), channels 128 nh + 32 wc + 8 l4 .. + 7 of the tile behind `rY` (rows >= M fall outside the descriptor)
-    const float slope = (a.act1 == 1) ? 0.0f : ((a.act1 == 2) ? 0.01f : 1.0f);
+    const float slope = conv_act_slope(a.act1);
     const unsigned ybytes = (unsigned)a.y_ld * 2u;
     const unsigned voY = (unsigned)(64 * g + l15) * ybytes + (unsigned)(32 * wc + 8 * l4) * 2u;
     auto chunk = [&](int R, int nh, int par, __amdgpu_buffer_rsrc_t rY) {
@@ -254,8 +211,7 @@ __global__ __launch_bounds__(512) void k_conv_gemm_pp(ConvArgs a)
     };
     _Float16* const Y = (_Float16*)a.Y;
     auto make_rY = [&](int m0, int n0) {
-        const int rows_left = a.M - m0;
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(Y + (size_t)m0 * a.y_ld + n0), 0, (unsigned)((size_t)(rows_left < 256 ? rows_left : 256) * a.y_ld * 2), 0x00020000);
+        return conv_out_rsrc(Y + (size_t)m0 * a.y_ld + n0, a.M - m0, 256, (size_t)a.y_ld * 2);
     };
 
 
@@ -263,14 +219,14 @@ __global__ __launch_bounds__(512) void k_conv_gemm_pp(ConvArgs a)
     Cur cA; cA.sb = q0; cA.kk = 0; cA.kc = 0; cA.tiles = 0;
     tile_of(q0, cA.m0, cA.n0);
     table_dma(cA.m0, 0);
-    { const int nq = next_sb(q0); if (nq < sb_end) { int m1, n1; tile_of(nq, m1, n1); table_dma(m1, 1); } }
+    { const int nq = sch.next(a, q0); if (nq < sch.sb_end) { int m1, n1; tile_of(nq, m1, n1); table_dma(m1, 1); } }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     cur_rows(cA); cur_tap(cA);
     Cur cB = cA;
     const int m0_first = cA.m0, n0_first = cA.n0;
     // (the cursor that enters a new tile asks for the row table entries of the tile AFTER it)
     auto lead_adv = [&]() {
-        if (cur_adv(cA, true)) { const int nq = next_sb(cA.sb); if (nq < sb_end) { int m1, n1; tile_of(nq, m1, n1); table_dma(m1, (cA.tiles + 1) & 1); } }
+        if (cur_adv(cA, true)) { const int nq = sch.next(a, cA.sb); if (nq < sch.sb_end) { int m1, n1; tile_of(nq, m1, n1); table_dma(m1, (cA.tiles + 1) & 1); } }
     };
 #pragma unroll
     for (int q = 0; q < 4; ++q) { dmaA(cA, 0, q); dmaB(cB, 0, q); }
@@ -325,9 +281,9 @@ __global__ __launch_bounds__(512) void k_conv_gemm_pp(ConvArgs a)
         lead_adv();
         buf ^= 1;
         if (t == S - 1) {
-            q = next_sb(q);
+            q = sch.next(a, q);
             rYp = rYc; have_prev = true; par ^= 1;
-            if (q >= sb_end) break;
+            if (q >= sch.sb_end) break;
             { int m0n; tile_of(q, m0n, n0c); rYc = make_rY(m0n, n0c); }
             t = 0;
         } else ++t;

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Time conv_gemm on the ECAPA layer shapes on the GPU: tools/tune_conv.py [items] [dbg,...]
-(ablations dbg 1-3 need the library built with `make EXTRA=-DSD_CONV_ABLATIONS`)"""
+dbg = 100 * pad_units + 10 * (sched + 1): leading dimensions padded by 32 * pad_units floats, schedule variant.  The last digit has to
+be 0: it chose an ablation build of k_conv_gemm (-DSD_CONV_ABLATIONS) until those were retired, and sd_bench_conv rejects it now."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "pyannote-audio_speaker-diarization_cpp_amd"))
