@@ -111,6 +111,21 @@ int sd_ecapa(sd_ctx*, const float* h_feats, const float* h_wav_lens, int64_t ite
 int sd_linkage(sd_ctx*, const double* h_X, int64_t N, int d, double* h_Z);
 /* ---- a12+a13: Clustering::cluster (cl.h:7, cl.cpp:459-468): 1-based labels */
 int sd_cluster(sd_ctx*, const double* h_X, int64_t N, int d, double cutoff, int32_t* h_labels1);
+/* ---- a12 / a12+a13 with the linkage method and the metric chosen by the caller: the `method` hyper-parameter of the clustering step
+ * (clustering/Clustering.py:251-276 / 317-333) and the metric its two branches use.  Method codes are scipy's; centroid, median or ward
+ * with the cosine metric returns SD_ERR_ARG (scipy refuses the combination; Clustering.py:317-321 normalises the rows and goes euclidean
+ * instead).  Cosine distance is 1 - dot / (sqrt(m1) * sqrt(m2)) with sequential sums, the reference's own rule (sd.cpp:476-498); a
+ * zero-norm row returns SD_ERR_NUMERIC.  Z is the dendrogram of scipy's generic algorithm (scipy.cluster._hierarchy.fast_linkage, the
+ * ancestor of cl.cpp:289-406), ties included.  sd_linkage / sd_cluster are the centroid + euclidean case. */
+enum {
+    SD_LINKAGE_SINGLE = 0, SD_LINKAGE_COMPLETE = 1, SD_LINKAGE_AVERAGE = 2, SD_LINKAGE_CENTROID = 3,
+    SD_LINKAGE_MEDIAN = 4, SD_LINKAGE_WARD = 5, SD_LINKAGE_WEIGHTED = 6
+};
+enum { SD_METRIC_EUCLIDEAN = 0, SD_METRIC_COSINE = 1 };
+int sd_linkage_ex(sd_ctx*, const double* h_X, int64_t N, int d, int method, int metric, double* h_Z);     /* Clustering.py:251-276 / 317-333 */
+int sd_cluster_ex(sd_ctx*, const double* h_X, int64_t N, int d, int method, int metric, double cutoff, int32_t* h_labels1);     /* Clustering.py:251-276 / 317-333 */
+/* host-only: "single", "complete", "average", "centroid", "median", "ward", "weighted" -> its code, anything else -> -1 (Clustering.py:251-276 / 317-333) */
+int sd_linkage_method_from_name(const char* name);
 /* ---- a13 alone: Clustering::fcluster (cl.h:9-10, cl.cpp:442-457; criterion "distance", cl.cpp:121-232): Z [N-1][4] of N observations
  * -> 1-based labels [N], numbered as the reference numbers them.  Host arithmetic only: no GPU work, the context may be NULL.  A Z that
  * is not a dendrogram of N observations (the reference indexes with its entries unchecked) returns SD_ERR_ARG. */
@@ -229,6 +244,10 @@ int sd_stage_ms(const sd_ctx*, double* ms4);
 /* ---- options.  Product keys (the knobs clustering/Clustering.py and the multi-GPU path expose; the reference hard-codes them):
  * "num_clusters", "min_clusters", "max_clusters" (-1 = unset; Clustering.py:21-43), "constrained_assignment" (1 = constrained_argmax of
  * Clustering.py:81-94: the local speakers of a chunk go to different clusters; applies to sd_clustering* and the whole path),
+ * "clustering_method" (SD_LINKAGE_*, default SD_LINKAGE_CENTROID = 3), "min_cluster_size" (>= 1, default 15) and, through sd_set_option_f64,
+ *   "clustering_threshold" (0 .. 2, default (double)0.7153814381597874f): the three hyper-parameters of Clustering.py:251-276 / 317-333, which the
+ *   reference hard-codes (sd.cpp:2049-2056).  Centroid, median and ward run on the unit-normalised rows with euclidean distances, the other four on
+ *   the rows as they are with the cosine metric.  They apply to sd_clustering*, the whole path, sd_finalize_dev and the sharded path,
  * "ecapa_precision" (0 = f32 MFMA = the reference's ORT precision (default); 1 = fp16 weights and activations on the fp16 MFMA with f32
  *   accumulation; 2 = the same with hi + lo fp16 weight planes; 3 = f32 tensors, both MFMA operands split into hi + lo fp16 halves, three
  *   products per multiply-add: f32-grade embeddings (<= 1e-7 cosine distance to mode 0) at about half of mode 0's time; a batch whose activations
@@ -244,6 +263,8 @@ int sd_stage_ms(const sd_ctx*, double* ms4);
  * "comm_timeout_ms" (deadline of the exchange step of a sharded job, default 600 000).
  * Test and tuning keys are listed in sdhip_test.h.  An unknown key returns SD_ERR_ARG. */
 int sd_set_option(sd_ctx*, const char* key, int64_t value);
+/* the real-valued keys: "clustering_threshold" (Clustering.py:251-276 / 317-333; outside [0, 2] or NaN: SD_ERR_ARG).  An unknown key returns SD_ERR_ARG. */
+int sd_set_option_f64(sd_ctx*, const char* key, double value);
 
 #ifdef __cplusplus
 }

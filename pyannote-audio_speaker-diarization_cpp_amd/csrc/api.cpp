@@ -144,12 +144,30 @@ extern "C" int sd_set_option(sd_ctx* c, const char* key, int64_t v)
     else if (k == "comm_timeout_ms") c->comm_timeout_ms = v;
     else if (k == "inject_fail_rank") c->inject_fail_rank = (int)v;
     else if (k == "constrained_assignment") c->constrained_assignment = v != 0;
+    else if (k == "clustering_method") { if (v < SD_LINKAGE_SINGLE || v > SD_LINKAGE_WEIGHTED) SD_FAIL(c, SD_ERR_ARG, "clustering_method must be one of SD_LINKAGE_SINGLE (0) .. SD_LINKAGE_WEIGHTED (6)"); c->clustering_method = (int)v; }
+    else if (k == "min_cluster_size") { if (v < 1 || v > 0x7fffffff) SD_FAIL(c, SD_ERR_ARG, "min_cluster_size must be at least 1"); c->min_cluster_size = (int)v; }
     else if (k == "num_clusters") c->num_clusters = (int)v;
     else if (k == "min_clusters") c->min_clusters = (int)v;
     else if (k == "max_clusters") c->max_clusters = (int)v;
     else if (k == "profile") { c->profile = v != 0; c->profile_detail = v >= 2; }
     else SD_FAIL(c, SD_ERR_ARG, "unknown option %s", key);
     return SD_OK;
+}
+
+extern "C" int sd_set_option_f64(sd_ctx* c, const char* key, double v)
+{
+    if (!c || !key) return SD_ERR_ARG;
+    std::string k(key);
+    if (k == "clustering_threshold") { if (!(v >= 0.0 && v <= 2.0)) SD_FAIL(c, SD_ERR_ARG, "clustering_threshold must lie in [0, 2]"); c->clustering_threshold = v; }
+    else SD_FAIL(c, SD_ERR_ARG, "unknown real-valued option %s", key);
+    return SD_OK;
+}
+extern "C" int sd_linkage_method_from_name(const char* name)
+{
+    static const char* const names[] = {"single", "complete", "average", "centroid", "median", "ward", "weighted"};      // scipy's codes = SD_LINKAGE_*
+    if (!name) return -1;
+    for (int i = 0; i < 7; ++i) if (std::string(name) == names[i]) return i;
+    return -1;
 }
 
 // ------------------------------------------------------------------ helpers

@@ -41,14 +41,19 @@ __global__ void k_gather_normalize(const double* __restrict__ X, const int* __re
 }
 
 // ---------------------------------------------------------------- k_pdist (cl.cpp:408-431)
+// COS: the cosine metric, 1 - dot / (sqrt(m1) * sqrt(m2)) with the three sums sequential in q -- the reference's own cosine rule (sd.cpp:476-498, the
+// formula k_assign uses; Clustering.py:317-333 runs the single / complete / average / weighted linkages on it).  m1 / m2 depend on one row each and are
+// kept once per row of the tile: the same sums a per-pair loop would form.  A zero-norm row raises *err (the reference throws, sd.cpp:493-495).
 #define PT 64
-__global__ __launch_bounds__(256) void k_pdist(const double* __restrict__ X, int64_t N, int d, double* __restrict__ D)
+template <bool COS>
+__global__ __launch_bounds__(256) void k_pdist(const double* __restrict__ X, int64_t N, int d, double* __restrict__ D, int* __restrict__ err)
 {
     const int ti = blockIdx.y, tj = blockIdx.x;
     if (tj < ti) return;
     __shared__ double Xi[PT][33], Xj[PT][33];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     double acc[4][4];
+    double ma[4] = {0.0, 0.0, 0.0, 0.0}, mb[4] = {0.0, 0.0, 0.0, 0.0};      // COS: squared norms of the tile's rows
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -67,10 +72,19 @@ __global__ __launch_bounds__(256) void k_pdist(const double* __restrict__ X, int
             double a[4], b[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) { a[u] = Xi[ty + 16 * u][q]; b[u] = Xj[tx + 16 * u][q]; }
+            if constexpr (COS) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
+                for (int u = 0; u < 4; ++u) { ma[u] += a[u] * a[u]; mb[u] += b[u] * b[u]; }
 #pragma unroll
-                for (int v = 0; v < 4; ++v) { const double df = a[u] - b[v]; acc[u][v] += df * df; }
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) acc[u][v] += a[u] * b[v];
+            } else {
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) { const double df = a[u] - b[v]; acc[u][v] += df * df; }
+            }
         }
         __syncthreads();
     }
@@ -79,13 +93,19 @@ __global__ __launch_bounds__(256) void k_pdist(const double* __restrict__ X, int
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
             const int64_t i = (int64_t)ti * PT + ty + 16 * u, j = (int64_t)tj * PT + tx + 16 * v;
-            if (i < j && j < N) D[cidx(N, i, j)] = sqrt(acc[u][v]);
+            if (i < j && j < N) {
+                if constexpr (COS) {
+                    if (ma[u] == 0.0 || mb[v] == 0.0) { *err = 1; D[cidx(N, i, j)] = NAN; }
+                    else D[cidx(N, i, j)] = 1.0 - (acc[u][v] / (sqrt(ma[u]) * sqrt(mb[v])));
+                } else D[cidx(N, i, j)] = sqrt(acc[u][v]);
+            }
         }
 }
 
 // the same distances as the full N x N square (k_linkage_mw<*, true>): tile (ti, tj), ti <= tj, is computed once and written twice, the
 // mirror through an LDS transpose so that both writes are row-contiguous.  D[i][j] and D[j][i] are the same bits; the diagonal is 0.
-__global__ __launch_bounds__(256) void k_pdist_sq(const double* __restrict__ X, int64_t N, int d, double* __restrict__ D)
+template <bool COS>
+__global__ __launch_bounds__(256) void k_pdist_sq(const double* __restrict__ X, int64_t N, int d, double* __restrict__ D, int* __restrict__ err)
 {
     const int ti = blockIdx.y, tj = blockIdx.x;
     if (tj < ti) return;
@@ -93,6 +113,7 @@ __global__ __launch_bounds__(256) void k_pdist_sq(const double* __restrict__ X, 
     __shared__ double Tt[PT][PT + 1];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     double acc[4][4];
+    double ma[4] = {0.0, 0.0, 0.0, 0.0}, mb[4] = {0.0, 0.0, 0.0, 0.0};      // COS: squared norms of the tile's rows
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -111,10 +132,19 @@ __global__ __launch_bounds__(256) void k_pdist_sq(const double* __restrict__ X, 
             double a[4], b[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) { a[u] = Xi[ty + 16 * u][q]; b[u] = Xj[tx + 16 * u][q]; }
+            if constexpr (COS) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
+                for (int u = 0; u < 4; ++u) { ma[u] += a[u] * a[u]; mb[u] += b[u] * b[u]; }
 #pragma unroll
-                for (int v = 0; v < 4; ++v) { const double df = a[u] - b[v]; acc[u][v] += df * df; }
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) acc[u][v] += a[u] * b[v];
+            } else {
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) { const double df = a[u] - b[v]; acc[u][v] += df * df; }
+            }
         }
         __syncthreads();
     }
@@ -124,7 +154,14 @@ __global__ __launch_bounds__(256) void k_pdist_sq(const double* __restrict__ X, 
         for (int v = 0; v < 4; ++v) {
             const int li = ty + 16 * u, lj = tx + 16 * v;
             const int64_t i = (int64_t)ti * PT + li, j = (int64_t)tj * PT + lj;
-            const double dv = (i == j) ? 0.0 : sqrt(acc[u][v]);
+            double dv;
+            if constexpr (COS) {
+                dv = 0.0;
+                if (i != j && i < N && j < N) {
+                    if (ma[u] == 0.0 || mb[v] == 0.0) { *err = 1; dv = NAN; }
+                    else dv = 1.0 - (acc[u][v] / (sqrt(ma[u]) * sqrt(mb[v])));
+                }
+            } else dv = (i == j) ? 0.0 : sqrt(acc[u][v]);
             Tt[li][lj] = dv;
             if (i < N && j < N && (ti != tj || i <= j)) D[(size_t)i * N + j] = dv;
         }
@@ -250,6 +287,7 @@ __device__ __forceinline__ void hp_change(HeapRef& h, int key, double v)        
     if (v < old) hp_up(h, idx); else hp_down(h, idx);
 }
 
+template <int METHOD>
 __global__ __launch_bounds__(LT) void k_linkage_heap(double* D, int n, int* size, int* cid, int* nb, double* md, double* Z,
                                                       double* g_hval, int* g_hkey, int* g_hpos)
 {
@@ -319,7 +357,7 @@ __global__ __launch_bounds__(LT) void k_linkage_heap(double* D, int n, int* size
             for (int u = 0; u < 4; ++u) {
                 const int z = z0 + u * LT;
                 if (z >= n || z == y || sz[u] == 0) continue;
-                const double nd = lw_centroid(dzx[u], dzy[u], dist, nx, ny);           // cl.cpp:367
+                const double nd = lw_update<METHOD>(dzx[u], dzy[u], dist, nx, ny, sz[u]);   // cl.cpp:367
                 D[izy[u]] = nd;
                 if (z < x && nbz[u] == x) nb[z] = y;                                    // cl.cpp:374-378
                 if (z < y && nd < mdz[u]) { nb[z] = y; md[z] = nd; atomicOr(&changed[z >> 5], 1u << (z & 31)); }   // cl.cpp:381-392
@@ -910,7 +948,7 @@ __global__ __launch_bounds__(MWT_MAX) void k_linkage_mw(double* D, int n, int* s
             for (int u = 0; u < 4; ++u) {
                 const int z = zz[u];
                 if (z < 0) continue;
-                const double nd = lw_centroid(dzx[u], dzy[u], dist, nx, ny);
+                const double nd = lw_update<LW_CENTROID>(dzx[u], dzy[u], dist, nx, ny, 0);
                 STX<ONEX>(&D[izy[u]], nd);
                 if (z > x && dzx[u] == dist) row_tie = 1;         // row x had a second neighbour at exactly the merge height
                 double mz = (z < n - 1) ? mdz[u] : INFINITY; int nz = nbz[u], fz = frz[u];
@@ -1079,6 +1117,7 @@ struct CoopOutcome {
 // one job with its plan and its workspaces; the steps of run_linkage
 struct LinkageJob {
     sd_ctx* c; const double* d_X; int64_t N; int d; double* d_Z;
+    int method, metric;             // SD_LINKAGE_* (= LW_*), SD_METRIC_*
     LinkagePlan p;
     int* size; int* cid; int* nb; double* md; double* md2;
     double* D; MwGran* gran; unsigned* sync; int* size_all; int* tyv;
@@ -1090,9 +1129,23 @@ struct LinkageJob {
         const int tiles = (int)((N + PT - 1) / PT);
         {
             ProfScope ps(c, "pdist", (double)m * d * 3.0, (double)m * 8.0 * (square ? 2 : 1) + (double)N * d * 8.0);
-            if (square) hipLaunchKernelGGL(k_pdist_sq, dim3(tiles, tiles), dim3(256), 0, c->stream, d_X, N, d, Dm);
-            else hipLaunchKernelGGL(k_pdist, dim3(tiles, tiles), dim3(256), 0, c->stream, d_X, N, d, Dm);
+            int* d_err = nullptr;
+            if (metric == SD_METRIC_COSINE) {
+                WS(c, int, e, "cl_err", 4);
+                d_err = e;
+                HIPCHK(c, hipMemsetAsync(d_err, 0, sizeof(int), c->stream));
+                if (square) hipLaunchKernelGGL(k_pdist_sq<true>, dim3(tiles, tiles), dim3(256), 0, c->stream, d_X, N, d, Dm, d_err);
+                else hipLaunchKernelGGL(k_pdist<true>, dim3(tiles, tiles), dim3(256), 0, c->stream, d_X, N, d, Dm, d_err);
+            }
+            else if (square) hipLaunchKernelGGL(k_pdist_sq<false>, dim3(tiles, tiles), dim3(256), 0, c->stream, d_X, N, d, Dm, d_err);
+            else hipLaunchKernelGGL(k_pdist<false>, dim3(tiles, tiles), dim3(256), 0, c->stream, d_X, N, d, Dm, d_err);
             KCHECK(c);
+            if (d_err) {            // no linkage kernel ever sees a NaN distance
+                int herr = 0;
+                HIPCHK(c, hipMemcpyAsync(&herr, d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                if (herr) SD_FAIL(c, SD_ERR_NUMERIC, "linkage: zero-norm row under the cosine metric (reference throws, sd.cpp:493-495)");
+            }
         }
         hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, size, 1, N, 0);
         hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, cid, 0, N, 1);
@@ -1124,7 +1177,7 @@ struct LinkageJob {
             if (p.use_rg) HIPCHK(c, hipMemsetAsync(d_Z, 0, 4 * sizeof(double), c->stream));
             // cooperative launch: all workgroups are resident together, or the launch is refused (they poll each other's slots)
             auto launch = [&](bool onex) {
-                return p.use_rg ? linkage_rg_launch(c, onex, p.G, p.TH, D, n_i, cid, nb, md, md2, d_Z, gran, sync, p.cap, (int)c->linkage_prefetch)
+                return p.use_rg ? linkage_rg_launch(c, method, onex, p.G, p.TH, D, n_i, cid, nb, md, md2, d_Z, gran, sync, p.cap, (int)c->linkage_prefetch)
                                 : hipLaunchCooperativeKernel(onex ? f_one : f_all, dim3(onex ? 8 * p.G : p.G), dim3(p.TH), args, (size_t)p.cap * 32, c->stream);
             };
             hipError_t le = o.onex ? launch(true) : hipErrorUnknown;
@@ -1162,7 +1215,7 @@ struct LinkageJob {
             hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, tyv, -1, N, 0);
             KCHECK(c);
             bool stopped = false, launched = false;
-            if (int rc = linkage_hx_run(c, hx_onex, workers, D, N, cid, size, tyv, nb, md, d_Z, &stopped, stop_above, merges, &launched)) return rc;
+            if (int rc = linkage_hx_run(c, method, hx_onex, workers, D, N, cid, size, tyv, nb, md, d_Z, &stopped, stop_above, merges, &launched)) return rc;
             if (!launched) { untouched = true; c->stats["linkage_hx_refused"].launches += 1; }      // a refused launch has not touched matrix, bounds or ids
             if (!stopped) { *ran = true; return SD_OK; }
             if (!hx_onex) break;
@@ -1188,7 +1241,7 @@ struct LinkageJob {
         hipError_t le;
         {
             ProfScope ps(c, "linkage", 0, 24.0 * (double)N * (double)N);
-            le = linkage_rg_launch(c, onex, p.G, p.TH, D, (int)N, cid, nb, md, md2, d_Z, gran, sync, p.cap, (int)c->linkage_prefetch, (int)k_done, size, tyv);
+            le = linkage_rg_launch(c, method, onex, p.G, p.TH, D, (int)N, cid, nb, md, md2, d_Z, gran, sync, p.cap, (int)c->linkage_prefetch, (int)k_done, size, tyv);
             c->stats["linkage_rg_launches"].launches += 1;
         }
         if (le != hipSuccess) { (void)hipGetLastError(); return SD_OK; }
@@ -1213,13 +1266,16 @@ struct LinkageJob {
             hval = hv; hkey = hk; hpos = hp;
         }
         ProfScope ps(c, "linkage_heap", 0, 24.0 * (double)N * (double)N);
-        hipLaunchKernelGGL(k_linkage_heap, dim3(1), dim3(LT), (size_t)((N + 31) / 32) * sizeof(unsigned), c->stream, Dc, (int)N, size, cid, nb, md, d_Z, hval, hkey, hpos);
+        const bool known = lw_dispatch(method, [&](auto M) {
+            hipLaunchKernelGGL(k_linkage_heap<M.value>, dim3(1), dim3(LT), (size_t)((N + 31) / 32) * sizeof(unsigned), c->stream, Dc, (int)N, size, cid, nb, md, d_Z, hval, hkey, hpos); });
+        if (!known) SD_FAIL(c, SD_ERR_ARG, "k_linkage_heap: no linkage method %d", method);
         KCHECK(c);
         return SD_OK;
     }
 };
 
-int run_linkage(sd_ctx* c, const double* d_X, int64_t N, int d, double* d_Z)
+// (method and metric are validated where they enter: sd_linkage_ex / sd_cluster_ex and the option keys)
+int run_linkage(sd_ctx* c, const double* d_X, int64_t N, int d, double* d_Z, int method, int metric)
 {
     if (N < 2) return SD_OK;
     const int64_t m = N * (N - 1) / 2;
@@ -1230,7 +1286,7 @@ int run_linkage(sd_ctx* c, const double* d_X, int64_t N, int d, double* d_Z)
     WS(c, double, md, "cl_md", N);
     WS(c, double, md2, "cl_md2", N);
     int rc;
-    LinkageJob j = {c, d_X, N, d, d_Z, linkage_plan(c, N, true), size, cid, nb, md, md2};
+    LinkageJob j = {c, d_X, N, d, d_Z, method, metric, linkage_plan(c, N, true), size, cid, nb, md, md2};
     LinkagePlan& p = j.p;
     if (p.G <= 1) return j.one_workgroup();
     if (p.square && !(j.D = ws_get<double>(c, "cl_Dsq", (size_t)N * N))) {      // no room for the square: the condensed form needs half
@@ -1240,34 +1296,41 @@ int run_linkage(sd_ctx* c, const double* d_X, int64_t N, int d, double* d_Z)
     if (!p.square) { WS(c, double, Dc, "cl_D", m); j.D = Dc; }
     if (p.G > c->num_cu || p.G > MWT) SD_FAIL(c, SD_ERR_ARG, "linkage: N=%lld needs %d cooperative workgroups", (long long)N, p.G);
     if ((rc = j.prepare(j.D, p.square))) return rc;
-    WS(c, MwGran, gran, "cl_gran", (int64_t)2 * p.G * p.slot_gran);
-    HIPCHK(c, hipMemsetAsync(gran, 0, (size_t)2 * p.G * p.slot_gran * sizeof(MwGran), c->stream));
-    j.gran = gran;
-    if (!p.use_rg) {          // k_linkage_mw: per-workgroup private copies of sizes (and ty)
-        const int64_t priv = (int64_t)p.G * N * (p.square ? 2 : 1);
-        WS(c, int, sa, "cl_size_all", priv);
-        j.size_all = sa;
-        hipLaunchKernelGGL(k_fill_size_ty, dim3((unsigned)((priv + 255) / 256)), dim3(256), 0, c->stream, sa, N, priv, p.square ? 1 : 0);
-        KCHECK(c);
+    // A method the cooperative kernel of this geometry is not built for counts as a refused launch: k_linkage_mw knows centroid only, k_linkage_rg the other
+    // six on its 256-thread, 4-column form (linkage_rg_has) -- the replay kernels (k_linkage_hx, k_linkage_heap) know all seven on every geometry, so no
+    // combination ever runs another method's formula.  Such a job needs none of the cooperative kernel's workspaces.
+    const bool coop_has = p.use_rg ? linkage_rg_has(method, p.onex, p.G, p.TH, p.cap, (int)c->linkage_prefetch) : method == LW_CENTROID;
+    if (!coop_has) c->stats["linkage_method_replays"].launches += 1;
+    if (coop_has) {
+        WS(c, MwGran, gran, "cl_gran", (int64_t)2 * p.G * p.slot_gran);
+        HIPCHK(c, hipMemsetAsync(gran, 0, (size_t)2 * p.G * p.slot_gran * sizeof(MwGran), c->stream));
+        j.gran = gran;
+        if (!p.use_rg) {          // k_linkage_mw: per-workgroup private copies of sizes (and ty)
+            const int64_t priv = (int64_t)p.G * N * (p.square ? 2 : 1);
+            WS(c, int, sa, "cl_size_all", priv);
+            j.size_all = sa;
+            hipLaunchKernelGGL(k_fill_size_ty, dim3((unsigned)((priv + 255) / 256)), dim3(256), 0, c->stream, sa, N, priv, p.square ? 1 : 0);
+            KCHECK(c);
+        }
+        WS(c, unsigned, sync, "cl_sync", SYNC_WORDS);
+        HIPCHK(c, hipMemsetAsync(sync, 0, SYNC_WORDS * sizeof(unsigned), c->stream));
+        j.sync = sync;
     }
-    WS(c, unsigned, sync, "cl_sync", SYNC_WORDS);
-    HIPCHK(c, hipMemsetAsync(sync, 0, SYNC_WORDS * sizeof(unsigned), c->stream));
-    j.sync = sync;
 
     // 1. the cooperative kernel; a forced replay counts as a refused launch: nothing has run
     CoopOutcome o = {COOP_REFUSED, p.onex, 0.0, true};
-    if (!c->linkage_force_heap && (rc = j.coop(o))) return rc;
+    if (!c->linkage_force_heap && coop_has && (rc = j.coop(o))) return rc;
     if (o.end == COOP_DONE) return SD_OK;
     if (o.end == COOP_ONEX_TIMEOUT) {
         // too few workgroups found themselves on XCC 0 (dispatch not round-robin?): never again in this context; the
         // multi-XCD form does the job (the distance matrix is rebuilt by the recursive call)
         c->linkage_one_xcd = 0;
         c->stats["linkage_one_xcd_timeouts"].launches += 1;
-        return run_linkage(c, d_X, N, d, d_Z);
+        return run_linkage(c, d_X, N, d, d_Z, method, metric);
     }
     if (o.end == COOP_TIE) c->stats["linkage_tie_fallbacks"].launches += 1;
     c->stats["linkage_fallbacks"].launches += 1;
-    const char* why = c->linkage_force_heap ? "forced (option linkage_force_heap)" : o.end == COOP_REFUSED ? "cooperative launch refused" : o.end == COOP_TIMEOUT ? "slot poll timed out" : "exact tie";
+    const char* why = c->linkage_force_heap ? "forced (option linkage_force_heap)" : !coop_has ? "method not built into the cooperative kernel of this geometry" : o.end == COOP_REFUSED ? "cooperative launch refused" : o.end == COOP_TIMEOUT ? "slot poll timed out" : "exact tie";
     if (c->profile_detail) fprintf(stderr, "linkage: %s at N = %lld -> heap replay\n", why, (long long)N);
 
     if (p.replay) {
@@ -1338,13 +1401,13 @@ void fcluster_host(const std::vector<double>& Z, int64_t n, double cutoff, std::
     }
 }
 
-int run_cluster_labels(sd_ctx* c, const double* d_Xn, int64_t N, int d, double cutoff, std::vector<int>& labels1, std::vector<double>* Zout)
+int run_cluster_labels(sd_ctx* c, const double* d_Xn, int64_t N, int d, double cutoff, std::vector<int>& labels1, std::vector<double>* Zout, int method, int metric)
 {
     labels1.assign((size_t)N, 0);
     if (N == 1) { labels1[0] = 1; return SD_OK; }
     if (N < 2) return SD_OK;
     WS(c, double, dZ, "cl_Z", (N - 1) * 4);
-    int rc = run_linkage(c, d_Xn, N, d, dZ);
+    int rc = run_linkage(c, d_Xn, N, d, dZ, method, metric);
     if (rc) return rc;
     std::vector<double> Z((size_t)(N - 1) * 4);
     HIPCHK(c, hipMemcpyAsync(Z.data(), dZ, Z.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1572,17 +1635,21 @@ int run_clustering(sd_ctx* c, const double* d_emb, int64_t M, int d, std::vector
     HIPCHK(c, hipMemcpyAsync(d_tidx, tidx.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_gather_normalize, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, c->stream, d_emb, d_tidx, N, d, X, Xn);
     KCHECK(c);
-    // a12+a13 with the reference's float-typed threshold (sd.cpp:2049) promoted to double
-    const float thr = 0.7153814381597874;
+    // a12+a13.  Method, threshold and minimum cluster size are the three hyper-parameters of Clustering.py:251-276; their defaults are the constants the
+    // reference hard-codes (sd.cpp:2049-2056: centroid, the float-typed threshold promoted to double, 15).  Clustering.py:317-333: centroid, median and ward
+    // are euclidean-only and run on the unit-normalised rows (Xn, with the port's f32 norm); the other four run on the rows as they are with the cosine metric.
+    const int method = c->clustering_method;
+    const bool euclid = method == SD_LINKAGE_CENTROID || method == SD_LINKAGE_MEDIAN || method == SD_LINKAGE_WARD;
+    const double thr = c->clustering_threshold;
     std::vector<int> lab;
     std::vector<double> Zh;
-    int rc = run_cluster_labels(c, Xn, N, d, (double)thr, lab, &Zh);
+    int rc = run_cluster_labels(c, euclid ? Xn : X, N, d, thr, lab, &Zh, method, euclid ? SD_METRIC_EUCLIDEAN : SD_METRIC_COSINE);
     if (rc) return rc;
     int nl = 0;
     for (auto& v : lab) { v -= 1; if (v + 1 > nl) nl = v + 1; }
     if (dumping) c->stash.clusters = lab;
     // a11: size split
-    size_t mcs = std::min<size_t>(15, std::max<size_t>(1, (size_t)std::round(0.1 * (double)N)));     // sd.cpp:2308
+    size_t mcs = std::min<size_t>((size_t)c->min_cluster_size, std::max<size_t>(1, (size_t)std::round(0.1 * (double)N)));     // sd.cpp:2308, Clustering.py:309-311
     std::vector<int> order, off;
     group_by_label(lab, nl, order, off);
     if (constrained) {
@@ -1592,7 +1659,7 @@ int run_clustering(sd_ctx* c, const double* d_emb, int64_t M, int d, std::vector
         if (nlarge0 < min_clusters) target = min_clusters;                                            // sd.cpp:2361-2366
         if (nlarge0 > max_clusters) target = max_clusters;
         if (target != -1) {
-            constrained_recut(Zh, N, (double)thr, mcs, target, lab);
+            constrained_recut(Zh, N, thr, mcs, target, lab);
             nl = 0;
             for (int v : lab) if (v + 1 > nl) nl = v + 1;
             group_by_label(lab, nl, order, off);

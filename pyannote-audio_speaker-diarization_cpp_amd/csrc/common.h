@@ -194,6 +194,10 @@ struct sd_ctx {
     int64_t linkage_threads = 0;               // 0 auto (256, or 1024 for N >= 60000), else 256 / 512 / 1024 threads per cooperative workgroup
     int num_cu = 256;
     bool constrained_assignment = false;        // Clustering.py:81-94 (one cluster per local speaker of a chunk)
+    // the three hyper-parameters of Clustering.py:251-276; defaults = what the reference hard-codes (sd.cpp:2049-2056)
+    int clustering_method = SD_LINKAGE_CENTROID;
+    double clustering_threshold = (double)0.7153814381597874f;      // the reference's float constant, widened
+    int min_cluster_size = 15;
     std::vector<double> last_conf;               // per-turn confidence of the last finalize (sd_last_confidence)
     int64_t fe_bill_samples = -1, fe_bill_frames = 0;   // profiling: selected samples / stored frames of the next k_stft_fbank launch (-1 = unknown)
     int64_t wav_origin = 0;                     // recording position of d_wav[0] for the current call (sharded entry points hold a slice)
@@ -335,8 +339,9 @@ int64_t count_frames_host(int64_t chunks);
 int sd_np_rint_host(double v);
 int64_t closest_frame_host(double w_start, double w_step, double w_dur, double t);
 // ---- cluster.hip
-int run_linkage(sd_ctx* c, const double* d_Xn, int64_t N, int d, double* d_Z);
-int run_cluster_labels(sd_ctx* c, const double* d_Xn, int64_t N, int d, double cutoff, std::vector<int>& labels1, std::vector<double>* Zout = nullptr);
+int run_linkage(sd_ctx* c, const double* d_X, int64_t N, int d, double* d_Z, int method = SD_LINKAGE_CENTROID, int metric = SD_METRIC_EUCLIDEAN);
+int run_cluster_labels(sd_ctx* c, const double* d_X, int64_t N, int d, double cutoff, std::vector<int>& labels1, std::vector<double>* Zout = nullptr,
+                       int method = SD_LINKAGE_CENTROID, int metric = SD_METRIC_EUCLIDEAN);
 int run_clustering(sd_ctx* c, const double* d_emb /*[M][d] f64*/, int64_t M, int d, std::vector<int>& hard, int* K,
                    int num_clusters = -1, int min_clusters = -1, int max_clusters = -1, std::vector<double>* soft_best = nullptr);
 void fcluster_host(const std::vector<double>& Z, int64_t n, double cutoff, std::vector<int>& T);

@@ -5,6 +5,7 @@
 #include "common.h"
 #include <cfloat>
 #include <cmath>
+#include <type_traits>
 
 __host__ __device__ __forceinline__ int64_t cidx(int64_t n, int64_t i, int64_t j)     // cl.cpp:236-242
 {
@@ -97,11 +98,42 @@ __device__ __forceinline__ Min2 wave_min2(Min2 m)
     return r;
 }
 
-// Lance-Williams centroid update with the reference's operation order, cl.cpp:250-256
-__device__ __forceinline__ double lw_centroid(double d_xi, double d_yi, double d_xy, int sx, int sy)
+// Lance-Williams update of the distance between cluster i and the merge of x and y, the linkage method a compile-time parameter
+// (clustering/Clustering.py:251-276 declares the seven; the codes are scipy's, also SD_LINKAGE_* in sdhip.h).  Formulas and operation order are
+// those of scipy's generic algorithm (_hierarchy_distance_update.pxi, one function per method behind fast_linkage); centroid is the
+// reference's cl.cpp:250-256, which restates the same expression.  Cluster sizes are ints there and enter every product as int -> double.
+constexpr int LW_SINGLE = 0, LW_COMPLETE = 1, LW_AVERAGE = 2, LW_CENTROID = 3, LW_MEDIAN = 4, LW_WARD = 5, LW_WEIGHTED = 6;
+template <int METHOD>
+__host__ __device__ __forceinline__ double lw_update(double d_xi, double d_yi, double d_xy, int sx, int sy, int si)
 {
-    return sqrt(((((double)sx * d_xi * d_xi) + ((double)sy * d_yi * d_yi)) -
-                 ((double)(sx * sy) * d_xy * d_xy) / (double)(sx + sy)) / (double)(sx + sy));
+    static_assert(METHOD >= LW_SINGLE && METHOD <= LW_WEIGHTED, "unknown linkage method");
+    if constexpr (METHOD == LW_SINGLE) return d_xi < d_yi ? d_xi : d_yi;               // fmin / fmax of two non-NaN distances
+    else if constexpr (METHOD == LW_COMPLETE) return d_xi > d_yi ? d_xi : d_yi;
+    else if constexpr (METHOD == LW_AVERAGE) return ((double)sx * d_xi + (double)sy * d_yi) / (double)(sx + sy);
+    else if constexpr (METHOD == LW_CENTROID)
+        return sqrt(((((double)sx * d_xi * d_xi) + ((double)sy * d_yi * d_yi)) -
+                     ((double)(sx * sy) * d_xy * d_xy) / (double)(sx + sy)) / (double)(sx + sy));
+    else if constexpr (METHOD == LW_MEDIAN) return sqrt(0.5 * (d_xi * d_xi + d_yi * d_yi) - 0.25 * d_xy * d_xy);
+    else if constexpr (METHOD == LW_WARD) {
+        const double t = 1.0 / (double)(sx + sy + si);
+        return sqrt((double)(si + sx) * t * d_xi * d_xi + (double)(si + sy) * t * d_yi * d_yi - (double)si * t * d_xy * d_xy);
+    }
+    else return 0.5 * (d_xi + d_yi);
+}
+
+// a runtime method code -> the compile-time parameter: calls f(std::integral_constant<int, METHOD>) for the seven codes; false (f not called) for any other
+template <class F> inline bool lw_dispatch(int method, F&& f)
+{
+    switch (method) {
+    case LW_SINGLE: f(std::integral_constant<int, LW_SINGLE>()); return true;
+    case LW_COMPLETE: f(std::integral_constant<int, LW_COMPLETE>()); return true;
+    case LW_AVERAGE: f(std::integral_constant<int, LW_AVERAGE>()); return true;
+    case LW_CENTROID: f(std::integral_constant<int, LW_CENTROID>()); return true;
+    case LW_MEDIAN: f(std::integral_constant<int, LW_MEDIAN>()); return true;
+    case LW_WARD: f(std::integral_constant<int, LW_WARD>()); return true;
+    case LW_WEIGHTED: f(std::integral_constant<int, LW_WEIGHTED>()); return true;
+    }
+    return false;
 }
 
 // A slot is a set of 8-byte granules {32-bit payload word, 32-bit round tag}: a reader that sees the tag of the round it waits for has the
@@ -141,10 +173,11 @@ template <bool ONEX, class T> __device__ __forceinline__ void STX(T* p, T v)
 // ---------------------------------------------------------------- launchers run_linkage (cluster.hip) drives
 // linkage_rg.hip
 bool linkage_rg_fits(int64_t N, int G, int TH);
-hipError_t linkage_rg_launch(sd_ctx* c, bool onex, int G, int TH, double* D, int n, int* cid, const int* nb, const double* md, const double* md2,
+bool linkage_rg_has(int method, bool onex, int G, int TH, int cap, int helper);
+hipError_t linkage_rg_launch(sd_ctx* c, int method, bool onex, int G, int TH, double* D, int n, int* cid, const int* nb, const double* md, const double* md2,
                              double* Z, MwGran* gran, unsigned* sync, int cap, int helper, int k0 = 0, const int* sz0 = nullptr, const int* ty0 = nullptr);
 int linkage_rg_slot_granules();
 // linkage_hx.hip
 bool linkage_hx_fits(int64_t N, int workers);
-int linkage_hx_run(sd_ctx* c, bool onex, int workers, double* D, int64_t N, int* cid, int* size, int* tyv, int* nb, double* md, double* d_Z, bool* stopped,
+int linkage_hx_run(sd_ctx* c, int method, bool onex, int workers, double* D, int64_t N, int* cid, int* size, int* tyv, int* nb, double* md, double* d_Z, bool* stopped,
                    double stop_above = (double)INFINITY, int64_t* merges_done = nullptr, bool* launched = nullptr);

@@ -100,7 +100,7 @@ template <bool S16> __device__ __forceinline__ void hx_decrease(HxHeap<S16>& h, 
     hx_up(h, idx);
 }
 
-template <bool ONEX, bool S16>
+template <bool ONEX, bool S16, int METHOD>
 __global__ __launch_bounds__(HX_T) void k_linkage_hx(double* D, int n, int* cid, int* size, int* tyv, int* nb, double* md, double* Z,
                                                      double* g_hval, int* g_hkey, int* g_hpos, MwGran* cmd /*[16]*/, MwGran* rep /*[G][8]*/,
                                                      int* chg_z /*[G][cap]*/, double* chg_v /*[G][cap]*/, unsigned* sync, int cap, int G /*workers*/, int lc,
@@ -296,8 +296,9 @@ __global__ __launch_bounds__(HX_T) void k_linkage_hx(double* D, int n, int* cid,
     const int nu = (nown + HX_T - 1) / HX_T;
     const int zsafe = z0 < n ? z0 : 0;
     int zc[HX_U], c_ty[HX_U]; bool c_dead[HX_U];
+    int c_sz[HX_U];                         // size of the column's cluster: the one method whose update needs it (ward) keeps it here, as k_linkage_rg does
 #pragma unroll
-    for (int u = 0; u < HX_U; ++u) { const int p = tid + u * HX_T; zc[u] = p < nown ? z0 + p : -1; c_ty[u] = -1; c_dead[u] = zc[u] < 0; }
+    for (int u = 0; u < HX_U; ++u) { const int p = tid + u * HX_T; zc[u] = p < nown ? z0 + p : -1; c_ty[u] = -1; c_dead[u] = zc[u] < 0; c_sz[u] = 1; }
     auto reply = [&](unsigned w0, unsigned w1, double v) {
         if (wv == 0 && lane < HX_REPW) {
             const unsigned w = lane == 0 ? w0 : lane == 1 ? w1 : lane == 2 ? (unsigned)__double2loint(v) : (unsigned)__double2hiint(v);
@@ -373,7 +374,7 @@ __global__ __launch_bounds__(HX_T) void k_linkage_hx(double* D, int n, int* cid,
         for (int u = 0; u < HX_U; ++u) {
             if (!(u < nu && act[u])) continue;
             const int z = zc[u];
-            const double nd = lw_centroid(dzx[u], dzy[u], dist, nx, ny);                                 // cl.cpp:367
+            const double nd = lw_update<METHOD>(dzx[u], dzy[u], dist, nx, ny, c_sz[u]);                  // cl.cpp:367
             STX<ONEX>(&D[(int64_t)y * N + z], nd);
             if (z < x && nbz[u] == x) STX<ONEX>(&nb[z], y);                                             // cl.cpp:374-378
             if (z < y && nd < mdz[u]) { STX<ONEX>(&nb[z], y); STX<ONEX>(&md[z], nd); chg[u] = true; ndv[u] = nd; }   // cl.cpp:381-392
@@ -382,7 +383,7 @@ __global__ __launch_bounds__(HX_T) void k_linkage_hx(double* D, int n, int* cid,
 #pragma unroll
         for (int u = 0; u < HX_U; ++u) {
             if (zc[u] == x && zc[u] >= 0) c_dead[u] = true;
-            if (zc[u] == y && zc[u] >= 0) c_ty[u] = k;
+            if (zc[u] == y && zc[u] >= 0) { c_ty[u] = k; if constexpr (METHOD == LW_WARD) c_sz[u] = nx + ny; }
         }
         // the changed rows in ascending z: column p = tid + u * T, so the order is u-major, then wave, then lane
         unsigned long long bm[HX_U];
@@ -413,7 +414,7 @@ bool linkage_hx_fits(int64_t N, int workers)
     return (N + workers - 1) / workers <= (int64_t)HX_U * HX_T;
 }
 // D: full N x N matrix, nb / md: exact nearest neighbours above each row (k_pdist_sq + k_row_nn); size = 1, cid = iota, tyv = -1
-int linkage_hx_run(sd_ctx* c, bool onex, int workers, double* D, int64_t N, int* cid, int* size, int* tyv, int* nb, double* md, double* d_Z, bool* stopped,
+int linkage_hx_run(sd_ctx* c, int method, bool onex, int workers, double* D, int64_t N, int* cid, int* size, int* tyv, int* nb, double* md, double* d_Z, bool* stopped,
                    double stop_above, int64_t* merges_done, bool* launched)
 {
     *stopped = false;
@@ -444,8 +445,12 @@ int linkage_hx_run(sd_ctx* c, bool onex, int workers, double* D, int64_t N, int*
     HIPCHK(c, hipMemsetAsync(sync, 0, SYNC_WORDS * sizeof(unsigned), c->stream));
     MwGran* rep = cmd + 16;
     const size_t dyn = (((size_t)lc * 8 + kp_bytes) + 15) & ~(size_t)15;
-    const void* f = onex ? (s16 ? (const void*)k_linkage_hx<true, true> : (const void*)k_linkage_hx<true, false>)
-                         : (s16 ? (const void*)k_linkage_hx<false, true> : (const void*)k_linkage_hx<false, false>);
+    const void* f = nullptr;
+    lw_dispatch(method, [&](auto M) {
+        f = onex ? (s16 ? (const void*)k_linkage_hx<true, true, M.value> : (const void*)k_linkage_hx<true, false, M.value>)
+                 : (s16 ? (const void*)k_linkage_hx<false, true, M.value> : (const void*)k_linkage_hx<false, false, M.value>);
+    });
+    if (!f) SD_FAIL(c, SD_ERR_ARG, "k_linkage_hx: no linkage method %d", method);
     (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
     (void)hipGetLastError();
     int n_i = (int)N, cap_i = cap, G_i = G, lc_i = lc;

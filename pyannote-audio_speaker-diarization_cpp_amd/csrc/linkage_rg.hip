@@ -155,7 +155,7 @@ __device__ __forceinline__ unsigned rq_word(const RQ& q, int k)      // word k o
 }
 
 // TB = launch bound (256 / 512 / 1024 threads): the register budget follows it -- 128 VGPRs at 1024 threads spill part of the column state
-template <bool ONEX, int TB, int UU>
+template <bool ONEX, int TB, int UU, int METHOD>
 __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, const int* nb0, const double* md0, const double* md20, double* Z,
                                                          MwGran* gran /*[2][G][RG_SLOT], zeroed*/, unsigned* sync, int cap /*columns per workgroup + 1*/, int G, int helper,
                                                          int k0 /*merges already done*/, const int* sz0, const int* ty0 /*cluster size (0 = gone) / last rewrite of every column after k0 merges; null: a fresh start*/)
@@ -515,7 +515,7 @@ __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, c
         for (int u = 0; u < UU; ++u) {
             if (!(u < nu && act[u])) continue;
             const int z = zc[u];
-            const double nd = lw_centroid(dzx[u], dzy[u], dist, nx, ny);
+            const double nd = lw_update<METHOD>(dzx[u], dzy[u], dist, nx, ny, c_sz[u]);
             STX<ONEX>(&D[(int64_t)y * N + z], nd);
             if (z > x && dzx[u] == dist) row_tie = 1;         // row x had a second neighbour at exactly the merge height
             double mz = (z < n - 1) ? c_md[u] : (double)INFINITY;
@@ -613,18 +613,39 @@ bool linkage_rg_fits(int64_t N, int G, int TH)
     const int64_t colsB = (N + G - 1) / G;
     return colsB <= (int64_t)(TH <= 512 ? 8 : RG_U) * TH && TH <= RG_T_MAX;         // (8 columns per thread: the <= 512-thread forms only -- register budget)
 }
-hipError_t linkage_rg_launch(sd_ctx* c, bool onex, int G, int TH, double* D, int n, int* cid, const int* nb, const double* md, const double* md2,
-                             double* Z, MwGran* gran, unsigned* sync, int cap, int helper, int k0, const int* sz0, const int* ty0)
+// The kernel for a method and a geometry, and the threads it is launched with (the helper wave included); null: not built.  Every (threads, columns per
+// thread) form exists for centroid, the default and the measured one; the other six methods are built for the 256-thread, 4-column form only (every
+// automatic geometry up to 131 072 rows), to bound build time -- run_linkage sends any other job of theirs to the heap replay.
+static const void* rg_kernel(int method, bool onex, int G, int TH, int cap, int& helper, int& TT)
 {
     if (helper && (TH > 448 || G > 64)) helper = 0;         // (one slot per lane in the helper's fold; 16 waves at most)
-    const int TT = TH + (helper ? 64 : 0);
-    const size_t dyn = (((size_t)cap * 9) + 15) & ~(size_t)15;
+    TT = TH + (helper ? 64 : 0);
     const bool wide = (int64_t)(cap - 1) > (int64_t)RG_U * TH;         // more than 4 columns per thread: the 8-column form
-    const void* f = wide ? (TT <= 256 ? (onex ? (const void*)k_linkage_rg<true, 256, 8> : (const void*)k_linkage_rg<false, 256, 8>)
-                                      : (onex ? (const void*)k_linkage_rg<true, 512, 8> : (const void*)k_linkage_rg<false, 512, 8>))
-                  : TT <= 256 ? (onex ? (const void*)k_linkage_rg<true, 256, RG_U> : (const void*)k_linkage_rg<false, 256, RG_U>)
-                  : TT <= 512 ? (onex ? (const void*)k_linkage_rg<true, 512, RG_U> : (const void*)k_linkage_rg<false, 512, RG_U>)
-                              : (onex ? (const void*)k_linkage_rg<true, 1024, RG_U> : (const void*)k_linkage_rg<false, 1024, RG_U>);
+    constexpr int CEN = LW_CENTROID;
+    if (method == LW_CENTROID)
+        return wide ? (TT <= 256 ? (onex ? (const void*)k_linkage_rg<true, 256, 8, CEN> : (const void*)k_linkage_rg<false, 256, 8, CEN>)
+                                 : (onex ? (const void*)k_linkage_rg<true, 512, 8, CEN> : (const void*)k_linkage_rg<false, 512, 8, CEN>))
+             : TT <= 256 ? (onex ? (const void*)k_linkage_rg<true, 256, RG_U, CEN> : (const void*)k_linkage_rg<false, 256, RG_U, CEN>)
+             : TT <= 512 ? (onex ? (const void*)k_linkage_rg<true, 512, RG_U, CEN> : (const void*)k_linkage_rg<false, 512, RG_U, CEN>)
+                         : (onex ? (const void*)k_linkage_rg<true, 1024, RG_U, CEN> : (const void*)k_linkage_rg<false, 1024, RG_U, CEN>);
+    const void* f = nullptr;
+    if (!wide && TT <= 256)
+        lw_dispatch(method, [&](auto M) {
+            f = onex ? (const void*)k_linkage_rg<true, 256, RG_U, M.value> : (const void*)k_linkage_rg<false, 256, RG_U, M.value>; });
+    return f;
+}
+bool linkage_rg_has(int method, bool onex, int G, int TH, int cap, int helper)
+{
+    int TT;
+    return rg_kernel(method, onex, G, TH, cap, helper, TT) != nullptr;
+}
+hipError_t linkage_rg_launch(sd_ctx* c, int method, bool onex, int G, int TH, double* D, int n, int* cid, const int* nb, const double* md, const double* md2,
+                             double* Z, MwGran* gran, unsigned* sync, int cap, int helper, int k0, const int* sz0, const int* ty0)
+{
+    int TT;
+    const void* f = rg_kernel(method, onex, G, TH, cap, helper, TT);
+    const size_t dyn = (((size_t)cap * 9) + 15) & ~(size_t)15;
+    if (!f) return hipErrorInvalidValue;          // (linkage_rg_has said so before)
     (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
     (void)hipGetLastError();
     void* args[] = {&D, &n, &cid, &nb, &md, &md2, &Z, &gran, &sync, &cap, &G, &helper, &k0, &sz0, &ty0};

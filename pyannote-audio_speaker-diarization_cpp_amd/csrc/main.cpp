@@ -21,6 +21,10 @@
 //   --downmix       average the channels of a multi-channel wav first (default: the reference's interleaved read, wav.h:95-97)
 //   --dump-steps DIR [--dump-level 2]   the reference's WRITE_DATA switch: DIR/cpp_<item>.txt for the items of script/verifyEveryStepResult.py
 //                   (sd_set_dump_dir; DIR = /tmp is what that script reads); single-GPU runs
+//   --clustering-method NAME, --clustering-threshold X, --min-cluster-size N   the three hyper-parameters of clustering/Clustering.py:251-276
+//                   (NAME: single | complete | average | centroid | median | ward | weighted; X in 0..2; N >= 1) = sd_set_option "clustering_method" /
+//                   "min_cluster_size" and sd_set_option_f64 "clustering_threshold"; defaults are the reference's constants (centroid, 0.7153814, 15).
+//                   A bad value is a usage error (exit 2) before anything touches the GPU
 //   --relabel       stdout / RTTM labels renumbered the way pyannote.audio names its output (the clusters that occur,
 //                   sorted by their string, become 0, 1, ... = SPEAKER_00, SPEAKER_01, ...); default = raw cluster ids (sd.cpp:3439)
 #include <cstdio>
@@ -34,7 +38,17 @@
 #include <unistd.h>
 #include "sdhip.h"
 
-struct Args { const char* seg = nullptr; const char* emb = nullptr; const char* wav = nullptr; const char* rttm = nullptr; int gpus = 1; bool relabel = false; int precision = 0; int wav_flags = 0; const char* dump_dir = nullptr; int dump_level = 1; };
+struct Args { const char* seg = nullptr; const char* emb = nullptr; const char* wav = nullptr; const char* rttm = nullptr; int gpus = 1; bool relabel = false; int precision = 0; int wav_flags = 0; const char* dump_dir = nullptr; int dump_level = 1;
+              int cl_method = -1; double cl_threshold = -1.0; long long cl_min_size = -1; };      // -1: leave the library's default
+
+// the clustering hyper-parameters the command line set; false (message printed) on a refusal
+static bool apply_clustering(sd_ctx* ctx, const Args& a)
+{
+    if (a.cl_method >= 0 && sd_set_option(ctx, "clustering_method", a.cl_method) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
+    if (a.cl_threshold >= 0.0 && sd_set_option_f64(ctx, "clustering_threshold", a.cl_threshold) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
+    if (a.cl_min_size >= 0 && sd_set_option(ctx, "min_cluster_size", a.cl_min_size) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
+    return true;
+}
 
 static void print_block(sd_ctx* ctx, sd_turn* turns, int64_t nt, const Args& a)
 {
@@ -71,6 +85,7 @@ static int run_single(const Args& a)
     if (a.precision && sd_set_option(ctx, "ecapa_precision", a.precision) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return 1; }
     if (a.precision == 3 && sd_set_option(ctx, "seg_precision", 3) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return 1; }
     if (a.dump_dir && sd_set_dump_dir(ctx, a.dump_dir, a.dump_level) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return 1; }
+    if (!apply_clustering(ctx, a)) return 1;
     sd_turn* turns = nullptr; int64_t nt = 0;
     const int rc = sd_diarize_wav(ctx, a.wav, a.wav_flags, &turns, &nt);      // 8 / 16 / 32-bit PCM like wav.h:99-122; rate and channels checked
     if (rc != SD_OK) { fprintf(stderr, "diarization failed (%d): %s\n", rc, sd_last_error(ctx)); return 1; }
@@ -109,6 +124,7 @@ static int run_rank(const Args& a, int rank, int world, int id_rd, const std::ve
     if (!ctx) { fprintf(stderr, "rank %d: sd_create failed: %s\n", rank, sd_create_error()); return 1; }
     if (a.precision && sd_set_option(ctx, "ecapa_precision", a.precision) != SD_OK) { fprintf(stderr, "rank %d: %s\n", rank, sd_last_error(ctx)); return 1; }
     if (a.precision == 3 && sd_set_option(ctx, "seg_precision", 3) != SD_OK) { fprintf(stderr, "rank %d: %s\n", rank, sd_last_error(ctx)); return 1; }
+    if (!apply_clustering(ctx, a)) return 1;
     unsigned char id[SD_COMM_ID_BYTES];
     if (rank == 0) {
         for (size_t q = 0; q < ready_rd.size(); ++q) {
@@ -159,6 +175,22 @@ int main(int argc, char* argv[])
             const std::string v(argv[++i]);
             if (v == "f32") a.precision = 0; else if (v == "f16") a.precision = 1; else if (v == "x3") a.precision = 3;
             else { fprintf(stderr, "--precision takes f32, f16 or x3\n"); return 2; }
+        }
+        else if (s == "--clustering-method" || s == "--clustering-threshold" || s == "--min-cluster-size") {
+            // checked here, before any context exists: a bad value never reaches the GPU
+            if (i + 1 >= argc) { fprintf(stderr, "usage: %s needs a value\n", s.c_str()); return 2; }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            if (s == "--clustering-method") {
+                a.cl_method = sd_linkage_method_from_name(v);
+                if (a.cl_method < 0) { fprintf(stderr, "usage: --clustering-method takes single, complete, average, centroid, median, ward or weighted (got '%s')\n", v); return 2; }
+            } else if (s == "--clustering-threshold") {
+                a.cl_threshold = strtod(v, &end);
+                if (end == v || *end || !(a.cl_threshold >= 0.0 && a.cl_threshold <= 2.0)) { fprintf(stderr, "usage: --clustering-threshold takes a number in [0, 2] (got '%s')\n", v); return 2; }
+            } else {
+                a.cl_min_size = strtoll(v, &end, 10);
+                if (end == v || *end || a.cl_min_size < 1 || a.cl_min_size > 0x7fffffff) { fprintf(stderr, "usage: --min-cluster-size takes an integer >= 1 (got '%s')\n", v); return 2; }
+            }
         }
         else pos.push_back(argv[i]);
     }

@@ -128,27 +128,49 @@ extern "C" int sd_postseg(sd_ctx* c, const float* h_seg, int64_t chunks, uint8_t
 }
 
 // ------------------------------------------------------------------ a12-a14
+// method / metric of the *_ex entries (Clustering.py:251-276 / 317-333); 0 = fine
+static int check_method_metric(sd_ctx* c, int method, int metric)
+{
+    if (method < SD_LINKAGE_SINGLE || method > SD_LINKAGE_WEIGHTED) SD_FAIL(c, SD_ERR_ARG, "unknown linkage method %d (SD_LINKAGE_SINGLE .. SD_LINKAGE_WEIGHTED)", method);
+    if (metric != SD_METRIC_EUCLIDEAN && metric != SD_METRIC_COSINE) SD_FAIL(c, SD_ERR_ARG, "unknown metric %d (SD_METRIC_EUCLIDEAN, SD_METRIC_COSINE)", metric);
+    if (metric == SD_METRIC_COSINE && (method == SD_LINKAGE_CENTROID || method == SD_LINKAGE_MEDIAN || method == SD_LINKAGE_WARD))
+        SD_FAIL(c, SD_ERR_ARG, "centroid, median and ward linkage are defined for the euclidean metric only");
+    return SD_OK;
+}
+
+extern "C" int sd_linkage_ex(sd_ctx* c, const double* h_X, int64_t N, int d, int method, int metric, double* h_Z);
 extern "C" int sd_linkage(sd_ctx* c, const double* h_X, int64_t N, int d, double* h_Z)
+{
+    return sd_linkage_ex(c, h_X, N, d, SD_LINKAGE_CENTROID, SD_METRIC_EUCLIDEAN, h_Z);
+}
+extern "C" int sd_linkage_ex(sd_ctx* c, const double* h_X, int64_t N, int d, int method, int metric, double* h_Z)
 {
     ENTER(c);
     if (!h_X || !h_Z || N < 2 || d <= 0) SD_FAIL(c, SD_ERR_ARG, "sd_linkage: need N >= 2");
+    if (int rc = check_method_metric(c, method, metric)) return rc;
     DTMP(c, dx, N * d * sizeof(double)); DTMP(c, dz, (N - 1) * 4 * sizeof(double));
     HIPCHK(c, hipMemcpy(dx.p, h_X, N * d * sizeof(double), hipMemcpyHostToDevice));
-    int rc = run_linkage(c, (const double*)dx.p, N, d, (double*)dz.p);
+    int rc = run_linkage(c, (const double*)dx.p, N, d, (double*)dz.p, method, metric);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(h_Z, dz.p, (N - 1) * 4 * sizeof(double), hipMemcpyDeviceToHost));
     return SD_OK;
 }
 
+extern "C" int sd_cluster_ex(sd_ctx* c, const double* h_X, int64_t N, int d, int method, int metric, double cutoff, int32_t* h_labels1);
 extern "C" int sd_cluster(sd_ctx* c, const double* h_X, int64_t N, int d, double cutoff, int32_t* h_labels1)
+{
+    return sd_cluster_ex(c, h_X, N, d, SD_LINKAGE_CENTROID, SD_METRIC_EUCLIDEAN, cutoff, h_labels1);
+}
+extern "C" int sd_cluster_ex(sd_ctx* c, const double* h_X, int64_t N, int d, int method, int metric, double cutoff, int32_t* h_labels1)
 {
     ENTER(c);
     if (!h_X || !h_labels1 || N < 1 || d <= 0) SD_FAIL(c, SD_ERR_ARG, "sd_cluster: bad argument");
+    if (int rc = check_method_metric(c, method, metric)) return rc;
     DTMP(c, dx, N * d * sizeof(double));
     HIPCHK(c, hipMemcpy(dx.p, h_X, N * d * sizeof(double), hipMemcpyHostToDevice));
     std::vector<int> lab;
-    int rc = run_cluster_labels(c, (const double*)dx.p, N, d, cutoff, lab);
+    int rc = run_cluster_labels(c, (const double*)dx.p, N, d, cutoff, lab, nullptr, method, metric);
     if (rc) return rc;
     for (int64_t i = 0; i < N; ++i) h_labels1[i] = lab[(size_t)i];
     return SD_OK;

@@ -39,7 +39,12 @@ EXPORTS = [
     "sd_diarize_sharded", "sd_diarize_sharded_dev", "sd_write_rttm_ex", "sd_relabel_turns", "sd_relabel_turns_ex", "sd_last_confidence",
     "sd_debug_read_ws", "sd_test_pack_split_weights", "sd_resample", "sd_resample_len", "sd_diarize_wav", "sd_set_dump_dir",
     "sd_fcluster", "sd_segment_chunks", "sd_embed_signals",
+    "sd_linkage_ex", "sd_cluster_ex", "sd_set_option_f64", "sd_linkage_method_from_name",
 ]
+# SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
+LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
+METRIC_EUCLIDEAN, METRIC_COSINE = 0, 1
+CLUSTERING_THRESHOLD_DEFAULT = float(np.float32(0.7153814381597874))      # the reference's float constant, widened (sd.cpp:2049)
 COMM_ID_BYTES = 128
 
 
@@ -79,6 +84,10 @@ def lib():
     L.sd_segment_chunks.argtypes = [vp, vp, i64, i64, vp, C.POINTER(i32)]
     L.sd_embed_signals.argtypes = [vp, vp, vp, i64, vp]
     L.sd_cluster.argtypes = [vp, vp, i64, C.c_int, dbl, vp]
+    L.sd_linkage_ex.argtypes = [vp, vp, i64, C.c_int, C.c_int, C.c_int, vp]
+    L.sd_cluster_ex.argtypes = [vp, vp, i64, C.c_int, C.c_int, C.c_int, dbl, vp]
+    L.sd_set_option_f64.argtypes = [vp, C.c_char_p, dbl]
+    L.sd_linkage_method_from_name.argtypes = [C.c_char_p]
     L.sd_clustering.argtypes = [vp, vp, i64, C.c_int, vp, C.POINTER(i32)]
     L.sd_clustering_ex.argtypes = [vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(i32)]
     L.sd_reconstruct.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, C.POINTER(C.POINTER(Turn)), C.POINTER(i64)]
@@ -117,6 +126,16 @@ def lib():
     L.sd_bench_conv.argtypes = [vp, i64] + [C.c_int] * 9 + [C.POINTER(dbl)]
     _lib = L
     return L
+
+
+def linkage_method_from_name(name):
+    """sd_linkage_method_from_name: scipy's method code of a linkage name, -1 for an unknown one.  Host-only."""
+    return int(lib().sd_linkage_method_from_name(str(name).encode()))
+
+
+def _method_code(method):
+    code = method if isinstance(method, (int, np.integer)) else linkage_method_from_name(method)
+    return int(code)
 
 
 def num_chunks(n):
@@ -278,6 +297,18 @@ class Diarizer:
     def set_option(self, key, value):
         self._chk(lib().sd_set_option(self._h, key.encode(), int(value)))
 
+    def set_option_f64(self, key, value):
+        self._chk(lib().sd_set_option_f64(self._h, key.encode(), float(value)))
+
+    def set_clustering(self, method="centroid", threshold=CLUSTERING_THRESHOLD_DEFAULT, min_cluster_size=15):
+        """the three hyper-parameters of clustering/Clustering.py:251-276; the defaults are the reference's constants"""
+        code = _method_code(method)
+        if not 0 <= code < len(LINKAGE_METHODS) or not 0.0 <= float(threshold) <= 2.0 or int(min_cluster_size) < 1:      # all three or none: the context is shared
+            raise SdError(1, "set_clustering: method %r, threshold %r, min_cluster_size %r" % (method, threshold, min_cluster_size))
+        self.set_option("clustering_method", code)
+        self.set_option_f64("clustering_threshold", threshold)
+        self.set_option("min_cluster_size", min_cluster_size)
+
     # ---- a2+a3
     def segment(self, wav):
         wav = np.ascontiguousarray(wav, np.float32)
@@ -357,6 +388,21 @@ class Diarizer:
         N, d = X.shape
         T = np.zeros(N, np.int32)
         self._chk(lib().sd_cluster(self._h, _ptr(X), N, d, float(cutoff), _ptr(T)))
+        return T
+
+    def linkage_ex(self, X, method, metric=METRIC_EUCLIDEAN):
+        """sd_linkage_ex: method = a name of LINKAGE_METHODS or its code; metric = METRIC_EUCLIDEAN / METRIC_COSINE"""
+        X = np.ascontiguousarray(X, np.float64)
+        N, d = X.shape
+        Z = np.zeros((max(N - 1, 0), 4), np.float64)
+        self._chk(lib().sd_linkage_ex(self._h, _ptr(X), N, d, _method_code(method), int(metric), _ptr(Z)))
+        return Z
+
+    def cluster_ex(self, X, method, metric, cutoff):
+        X = np.ascontiguousarray(X, np.float64)
+        N, d = X.shape
+        T = np.zeros(N, np.int32)
+        self._chk(lib().sd_cluster_ex(self._h, _ptr(X), N, d, _method_code(method), int(metric), float(cutoff), _ptr(T)))
         return T
 
     def clustering(self, emb, num_clusters=-1, min_clusters=-1, max_clusters=-1):
