@@ -61,6 +61,33 @@ int sd_test_pack_split_weights(const float* w, int K, int Cout, int CinPad, int 
  * which chose an ablation build until those were retired, is SD_ERR_ARG) */
 int sd_bench_conv(sd_ctx*, int64_t items, int Tp, int T, int Cin, int Cout, int KT, int dil, int has_x2, int dbg, int reps, double* ms_per_launch);
 
+/* ---- test hook (tests/test_conv_kernels.py): ONE conv / linear case through the product's dispatch (launch_conv_narrow when asked, then
+ * launch_conv_gemm), on operands the caller chooses, with guard regions round every buffer.  The hook uploads, launches and downloads; the
+ * row table, the fp16 / split weight forms and the fp16 activations are made by the product's own kernels.
+ * Row spaces.  dense = 0: compact spaces through a row table: item i stores n_in[i] input rows and n_out[i] output rows (1 .. 1024,
+ * n_out[i] <= tin); M = sum n_out, in_rows = sum n_in.  dense = 1: no row table; every item has tp_in input rows (tin valid) and tp_out
+ * output rows (t valid); M = items * tp_out, in_rows = items * tp_in; n_in / n_out are not read.
+ * Buffers.  shared = 0: X, X2 and Y each live in a buffer of their own: X at column x_col0 of [in_rows + 256][x_ld], X2 at column x2_col0 of
+ * a second buffer of that shape, Y at column y_col0 of [M + 256][y_ld].  shared = 1: all three are column slices of ONE [M + 256][y_ld]
+ * buffer (x_ld == y_ld, in_rows == M: the Res2Net pattern).  An X slice is cin_pad columns wide: cin operands, then zeros.  Everything else
+ * holds `canary`, except the 256 slack rows of the X / X2 slices, which hold NaN.  fp16 (prec 1): the buffers are built in f32 and rounded
+ * to fp16 by the product's conversion kernel.
+ * cin_pad = 0: the product's padding rule (a multiple of 32; of 64 for prec 1); else the padded channel count as given (contract tests).
+ * prec: 0 f32, 1 fp16 end to end (y_f32 = 1: Y stays float), 3 split operands.  act1: 0 none, 1 relu, 2 leaky; act2: 0 none, 1 tanh, 2 sigmoid. */
+typedef struct sd_conv_case {
+    int32_t items, dense, tin, t, tp_in, tp_out;
+    int32_t cin, cin_pad, cout, kt, dil, pad_mode;
+    int32_t shared, x_ld, x_col0, has_x2, x2_col0, y_ld, y_col0, y_f32;
+    int32_t act1, act2, prec, try_narrow;
+    float canary;
+} sd_conv_case;
+/* w [kt][cout][cin], x / x2 [in_rows][cin], bias / scale / shift [cout] (scale and shift come together), item_bias [items][cout]: host
+ * pointers, f32, each optional except w and x.  y_out [(M + 256) * y_ld] receives the WHOLE output buffer as f32, guards included;
+ * kernel_name (name_cap bytes) the name of the kernel the dispatch launched last ("" = none): pp_relu, pp, g256_m16, g256_m32, g256_f32,
+ * w256_f32, w256_f16, w256_x3, skinny, gemm128_{f32,f16,x3}[_x2], narrow2, narrow3. */
+int sd_test_conv(sd_ctx*, const sd_conv_case*, const int32_t* n_in, const int32_t* n_out, const float* w, const float* x, const float* x2,
+                 const float* bias, const float* scale, const float* shift, const float* item_bias, float* y_out, char* kernel_name, int name_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -212,6 +212,7 @@ struct sd_ctx {
     int dump_level = 0;
     StepStash stash;
     std::string ws_failed;                      // ws_get: name of the workspace whose allocation failed last ("" = none); the embedding stage's retry reads it
+    const char* last_conv_kernel = nullptr;     // test hook (sd_test_conv): which kernel the conv dispatch launched last; set by every launch site, host code only
     const float* planted_scores = nullptr;      // sd_set_planted: measurement / test hook
     const float* planted_emb = nullptr;
     int64_t planted_lo = 0, planted_n = 0;
@@ -305,6 +306,11 @@ int build_ecapa_weights(sd_ctx* c, const Pack& p);
 int build_seg_weights(sd_ctx* c, const Pack& p);
 void* weight_alloc(sd_ctx* c, size_t bytes);                      // weights.cpp: bump allocator over 64 MB device blocks (freed by sd_destroy)
 int ensure_ecapa_mode_weights(sd_ctx* c, int ecapa_precision);   // weights_gpu.hip: builds W16 (modes 1, 2) / W16x (mode 3) on first use
+// the two forms of ONE layer, into device memory the caller provides (conv_w16_bytes / conv_w16x_bytes; d_max: one unsigned of scratch); asynchronous on c->stream
+inline size_t conv_w16_bytes(const ConvLayer& L) { return (size_t)2 * L.KT * L.Cout * L.CinPad16 * 2; }
+inline size_t conv_w16x_bytes(const ConvLayer& L) { return (size_t)2 * L.KT * L.Cout * L.CinPad * 2; }
+int build_conv_w16(sd_ctx* c, ConvLayer& L, void* d);                      // sets L.W16
+int build_conv_w16x(sd_ctx* c, ConvLayer& L, void* d, unsigned* d_max);    // sets L.W16x, L.w16x_inv (synchronises the stream once: the exponent is chosen on the host)
 // ---- frontend.hip
 int frontend_prepare(sd_ctx* c, const float* d_masks, int64_t items, int64_t first_item, float* d_wav_lens, int* d_nnorm, int* d_nvalid,
                      int* d_flags, bool compact, int* h_n_active, int* d_cidx, std::vector<int>* h_nvalid = nullptr);
@@ -322,6 +328,9 @@ struct EcapaRowPlan {
     const int* d_off = nullptr;           // device copy [EC_SPACES][n + 1]
 };
 int ecapa_need_rows(int nvalid, bool skip_dead_rows);             // rows of an item in space 0
+// row table of `items` items (k_build_rowtab): d_off_out / d_off_in = device prefix sums [items + 1] of the rows per item in the output / input space
+int ecapa_build_rowtab(sd_ctx* c, const int* d_off_out, int base_out, const int* d_off_in, int base_in, int64_t items, int2* d_rowtab);
+int ecapa_rows_to_half(sd_ctx* c, const float* d_f32, void* d_f16, int64_t n4);      // k_rows_to_half: n4 groups of four floats -> fp16 (the fp16 mode's conversion)
 int ecapa_row_plan(sd_ctx* c, const int* h_nvalid, int64_t n, EcapaRowPlan& plan, int* d_off /*[EC_SPACES][n + 1]*/);
 // items [a0, a1) of the plan; d_feats = space-0 rows of ALL the plan's items
 int run_ecapa(sd_ctx* c, const float* d_feats, const int* d_nvalid /*[n]*/, const EcapaRowPlan& plan, int64_t a0, int64_t a1, float* d_emb /*[n][192]*/);

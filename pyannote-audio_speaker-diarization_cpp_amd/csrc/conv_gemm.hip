@@ -547,6 +547,7 @@ int launch_conv_gemm(sd_ctx* c, const ConvArgs& in, const char* tag)
         const int cinr = a.cin_real > 0 ? a.cin_real : a.Cin;
         ProfScope ps(c, c->profile_detail ? std::string("skinny_gemm:") + tag : std::string("skinny_gemm"), 2.0 * a.M * a.Cout * cinr,
                      4.0 * ((double)a.M * cinr + (double)a.M * a.Cout + (double)a.Cout * cinr));
+        c->last_conv_kernel = "skinny";
         hipLaunchKernelGGL(k_skinny_gemm, dim3((a.M + 31) / 32, (a.Cout + 31) / 32), dim3(256), 0, c->stream, a);
         KCHECK(c);
         return SD_OK;
@@ -560,6 +561,7 @@ int launch_conv_gemm(sd_ctx* c, const ConvArgs& in, const char* tag)
     const ConvBill bill = conv_bill(a, rows, f16, a.X2 ? 2 : 1);
     ProfScope ps(c, c->profile_detail ? std::string("conv_gemm:") + tag : std::string("conv_gemm"), bill.flops, bill.bytes);
     ProfScope ps16(c, f16 ? "conv_gemm_f16" : x3 ? "conv_gemm_x3" : "conv_gemm_f32", bill.flops, bill.bytes);        // per precision (bench: roofline of the fp16 instantiations alone)
+    c->last_conv_kernel = f16 ? (a.X2 ? "gemm128_f16_x2" : "gemm128_f16") : x3 ? (a.X2 ? "gemm128_x3_x2" : "gemm128_x3") : (a.X2 ? "gemm128_f32_x2" : "gemm128_f32");
     if (f16) {
         if (a.X2) hipLaunchKernelGGL((k_conv_gemm<true, 1>), dim3(grid), dim3(256), 0, c->stream, a);
         else hipLaunchKernelGGL((k_conv_gemm<false, 1>), dim3(grid), dim3(256), 0, c->stream, a);

@@ -456,7 +456,9 @@ int launch_conv_gemm_g256(sd_ctx* c, const ConvArgs& in, const char* tag)
     const int grid = conv_tiles_grid(c, a, GM, GN, 1);
     {
         ConvProfWide prof(c, tag, h ? "f16" : "f32", conv_bill(a, (double)a.M, h));
-        if (h && c->conv_mfma16 && ((int64_t)a.Cin * a.KT >= 1024 || c->conv_mfma16 == 2)) hipLaunchKernelGGL(k_conv_gemm_g256<2>, dim3(grid), dim3(512), lds_bytes, c->stream, a);
+        const bool m16 = h && c->conv_mfma16 && ((int64_t)a.Cin * a.KT >= 1024 || c->conv_mfma16 == 2);
+        c->last_conv_kernel = m16 ? "g256_m16" : h ? "g256_m32" : "g256_f32";
+        if (m16) hipLaunchKernelGGL(k_conv_gemm_g256<2>, dim3(grid), dim3(512), lds_bytes, c->stream, a);
         else if (h) hipLaunchKernelGGL(k_conv_gemm_g256<1>         /* short contractions (block0, K = 640): 523 TF on this form against 486 */, dim3(grid), dim3(512), lds_bytes, c->stream, a);
         else hipLaunchKernelGGL(k_conv_gemm_g256<0>, dim3(grid), dim3(512), lds_bytes, c->stream, a);
     }

@@ -374,6 +374,7 @@ int launch_conv_gemm_h256(sd_ctx* c, const ConvArgs& in, const char* tag)
     const int grid = conv_tiles_grid(c, a, HM, HN, 1);
     {
         ConvProfWide prof(c, tag, h ? "f16" : x3 ? "x3" : "f32", conv_bill(a, (double)a.M, h));
+        c->last_conv_kernel = h ? "w256_f16" : x3 ? "w256_x3" : "w256_f32";
         if (h) hipLaunchKernelGGL(k_conv_gemm_w256<1>, dim3(grid), dim3(512), lds_bytes, c->stream, a);
         else if (x3) hipLaunchKernelGGL(k_conv_gemm_w256<3>, dim3(grid), dim3(512), lds_bytes, c->stream, a);
         else hipLaunchKernelGGL(k_conv_gemm_w256<0>, dim3(grid), dim3(512), lds_bytes, c->stream, a);

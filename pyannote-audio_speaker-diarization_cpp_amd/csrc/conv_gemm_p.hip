@@ -311,6 +311,7 @@ int launch_conv_gemm_pp(sd_ctx* c, const ConvArgs& in, const char* tag)
     const int grid = conv_tiles_grid(c, a, 256, 256, 1);          // (Cout is a multiple of 256)
     {
         ConvProfWide prof(c, tag, "f16", conv_bill(a, (double)a.M, true));          // (ECAPA layers only: prec 1)
+        c->last_conv_kernel = a.act1 == 1 ? "pp_relu" : "pp";
         if (a.act1 == 1) hipLaunchKernelGGL(k_conv_gemm_pp<true>, dim3(grid), dim3(512), P_LDS, c->stream, a);
         else hipLaunchKernelGGL(k_conv_gemm_pp<false>, dim3(grid), dim3(512), P_LDS, c->stream, a);
     }

@@ -163,6 +163,7 @@ int launch_conv_narrow(sd_ctx* c, const ConvArgs& in, const char* tag)
     const double bytes = 4.0 * ((double)a.M * cin + (double)a.M * a.Cout + (double)a.Cout * cin * a.KT);
     ProfScope ps(c, c->profile_detail ? std::string("conv_gemm:") + tag : std::string("conv_gemm"), flops, bytes);
     ProfScope ps32(c, "conv_gemm_f32", flops, bytes);
+    c->last_conv_kernel = a.Cout > 64 ? "narrow3" : "narrow2";
     if (a.Cout > 64) hipLaunchKernelGGL((k_conv_narrow<3>), dim3(grid), dim3(256), 0, c->stream, a);
     else hipLaunchKernelGGL((k_conv_narrow<2>), dim3(grid), dim3(256), 0, c->stream, a);
     KCHECK(c);

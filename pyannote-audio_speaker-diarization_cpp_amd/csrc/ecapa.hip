@@ -156,6 +156,19 @@ __global__ void k_rows_to_half(const float* __restrict__ f, _Float16* __restrict
     st4(h + idx * 4, *(const float4*)(f + idx * 4));
 }
 
+int ecapa_build_rowtab(sd_ctx* c, const int* d_off_out, int base_out, const int* d_off_in, int base_in, int64_t items, int2* d_rowtab)
+{
+    hipLaunchKernelGGL(k_build_rowtab, dim3((unsigned)items), dim3(256), 0, c->stream, d_off_out, base_out, d_off_in, base_in, d_rowtab);
+    KCHECK(c);
+    return SD_OK;
+}
+int ecapa_rows_to_half(sd_ctx* c, const float* d_f32, void* d_f16, int64_t n4)
+{
+    hipLaunchKernelGGL(k_rows_to_half, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, c->stream, d_f32, (_Float16*)d_f16, n4);
+    KCHECK(c);
+    return SD_OK;
+}
+
 // prec 0: f32 MFMA, float buffers.  prec 1 (ecapa_precision): fp16 MFMA, _Float16 buffers (X / Y leading dimensions in elements)
 static ConvArgs conv_args(const ConvLayer& L, const void* X, int x_ld, void* Y, int y_ld, int64_t M, bool per_item, int prec = 0)
 {
@@ -248,7 +261,7 @@ static int run_ecapa_t(sd_ctx* c, const float* d_feats_all, const int* d_nvalid_
         char key[32]; snprintf(key, sizeof(key), "ec_rowtab_%d%d", so, si);
         int2* p = ws_get<int2>(c, key, (size_t)R[so] + 128);
         if (!p) return nullptr;
-        hipLaunchKernelGGL(k_build_rowtab, dim3((unsigned)items), dim3(256), 0, st, ro[so], rbase[so], ro[si], rbase[si], p);
+        if (ecapa_build_rowtab(c, ro[so], rbase[so], ro[si], rbase[si], items, p)) return nullptr;
         tabs[so][si] = p;
         return p;
     };
@@ -312,8 +325,7 @@ static int run_ecapa_t(sd_ctx* c, const float* d_feats_all, const int* d_nvalid_
         if ((rc = launch_conv_gemm(c, a, "mfa"))) return rc;
     }
     if (mfa32 && !(hp & 2)) {
-        hipLaunchKernelGGL(k_rows_to_half, GRID1(MN * LD3 / 4), 0, st, mfa32, (_Float16*)mfa, MN * LD3 / 4);
-        KCHECK(c);
+        if ((rc = ecapa_rows_to_half(c, mfa32, mfa, MN * LD3 / 4))) return rc;
     }
     // ASP with global context: cat[x, mean, std] @ W == x @ Wx + (mean,std) @ Wms  (per-item bias)
     {

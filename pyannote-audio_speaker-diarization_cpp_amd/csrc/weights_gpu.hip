@@ -46,6 +46,39 @@ __global__ void k_w16x(const float* __restrict__ W, _Float16* __restrict__ out, 
     out[at + 8] = (_Float16)(v - (float)hi);
 }
 
+// fp16 planes of one layer into d (conv_w16_bytes): hi planes, then the residue planes
+int build_conv_w16(sd_ctx* c, ConvLayer& L, void* d)
+{
+    const size_t rows = (size_t)L.KT * L.Cout, n = rows * (size_t)L.Cin;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    HIPCHK(c, hipMemsetAsync(d, 0, conv_w16_bytes(L), c->stream));
+    hipLaunchKernelGGL(k_w16_planes, grid, block, 0, c->stream, L.W, (_Float16*)d, L.KT, L.Cout, L.CinPad, L.CinPad16, L.Cin);
+    KCHECK(c);
+    L.W16 = d;
+    return SD_OK;
+}
+// split weights of one layer into d (conv_w16x_bytes)
+int build_conv_w16x(sd_ctx* c, ConvLayer& L, void* d, unsigned* d_max)
+{
+    const size_t rows = (size_t)L.KT * L.Cout, n = rows * (size_t)L.Cin;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    // 2^e puts the layer's largest weight into [2^13, 2^14) (pack_split_weights above: same rule, same bits)
+    HIPCHK(c, hipMemsetAsync(d_max, 0, sizeof(unsigned), c->stream));
+    hipLaunchKernelGGL(k_w_absmax, grid, block, 0, c->stream, L.W, rows, L.CinPad, L.Cin, d_max);
+    KCHECK(c);
+    unsigned bits = 0;
+    HIPCHK(c, hipMemcpyAsync(&bits, d_max, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float wmax; memcpy(&wmax, &bits, 4);
+    int e = 0;
+    if (wmax > 0.0f) { (void)frexpf(wmax, &e); e = 14 - e; }
+    HIPCHK(c, hipMemsetAsync(d, 0, conv_w16x_bytes(L), c->stream));
+    hipLaunchKernelGGL(k_w16x, grid, block, 0, c->stream, L.W, (_Float16*)d, L.KT, L.Cout, L.CinPad, L.Cin, ldexpf(1.0f, e));
+    KCHECK(c);
+    L.W16x = d; L.w16x_inv = ldexpf(1.0f, -e);
+    return SD_OK;
+}
+
 int ensure_ecapa_mode_weights(sd_ctx* c, int mode)
 {
     EcapaWeights& E = c->ew;
@@ -54,37 +87,18 @@ int ensure_ecapa_mode_weights(sd_ctx* c, int mode)
     if (!need16 && !need16x) return SD_OK;
     unsigned* d_max = nullptr;
     if (need16x) { d_max = (unsigned*)weight_alloc(c, sizeof(unsigned)); if (!d_max) return SD_ERR_HIP; }
+    int rc;
     for (ConvLayer* Lp : E.conv16) {
         ConvLayer& L = *Lp;
-        const size_t rows = (size_t)L.KT * L.Cout, n = rows * (size_t)L.Cin;
-        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
         if (need16) {
-            const size_t bytes = (size_t)2 * rows * L.CinPad16 * sizeof(_Float16);
-            _Float16* d = (_Float16*)weight_alloc(c, bytes);
+            void* d = weight_alloc(c, conv_w16_bytes(L));
             if (!d) return SD_ERR_HIP;
-            HIPCHK(c, hipMemsetAsync(d, 0, bytes, c->stream));
-            hipLaunchKernelGGL(k_w16_planes, grid, block, 0, c->stream, L.W, d, L.KT, L.Cout, L.CinPad, L.CinPad16, L.Cin);
-            KCHECK(c);
-            L.W16 = d;
+            if ((rc = build_conv_w16(c, L, d))) return rc;
         }
         if (need16x) {
-            // 2^e puts the layer's largest weight into [2^13, 2^14) (pack_split_weights above: same rule, same bits)
-            HIPCHK(c, hipMemsetAsync(d_max, 0, sizeof(unsigned), c->stream));
-            hipLaunchKernelGGL(k_w_absmax, grid, block, 0, c->stream, L.W, rows, L.CinPad, L.Cin, d_max);
-            KCHECK(c);
-            unsigned bits = 0;
-            HIPCHK(c, hipMemcpyAsync(&bits, d_max, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            float wmax; memcpy(&wmax, &bits, 4);
-            int e = 0;
-            if (wmax > 0.0f) { (void)frexpf(wmax, &e); e = 14 - e; }
-            const size_t bytes = (size_t)2 * rows * L.CinPad * sizeof(_Float16);
-            _Float16* d = (_Float16*)weight_alloc(c, bytes);
+            void* d = weight_alloc(c, conv_w16x_bytes(L));
             if (!d) return SD_ERR_HIP;
-            HIPCHK(c, hipMemsetAsync(d, 0, bytes, c->stream));
-            hipLaunchKernelGGL(k_w16x, grid, block, 0, c->stream, L.W, d, L.KT, L.Cout, L.CinPad, L.Cin, ldexpf(1.0f, e));
-            KCHECK(c);
-            L.W16x = d; L.w16x_inv = ldexpf(1.0f, -e);
+            if ((rc = build_conv_w16x(c, L, d, d_max))) return rc;
         }
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -92,4 +106,3 @@ int ensure_ecapa_mode_weights(sd_ctx* c, int mode)
     if (need16x) E.have16x = true;
     return SD_OK;
 }
-

@@ -20,6 +20,16 @@ class Turn(C.Structure):
     _fields_ = [("start", C.c_double), ("end", C.c_double), ("label", C.c_int32), ("_pad", C.c_int32)]
 
 
+class ConvCase(C.Structure):
+    """sd_conv_case of include/sdhip_test.h"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "items", "dense", "tin", "t", "tp_in", "tp_out", "cin", "cin_pad", "cout", "kt", "dil", "pad_mode",
+        "shared", "x_ld", "x_col0", "has_x2", "x2_col0", "y_ld", "y_col0", "y_f32", "act1", "act2", "prec", "try_narrow")] + [("canary", C.c_float)]
+
+
+CONV_SLACK_ROWS = 256      # guard rows behind the buffers of Diarizer.conv_case
+
+
 class SdError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libsdhip error %d: %s" % (code, msg))
@@ -39,7 +49,7 @@ EXPORTS = [
     "sd_diarize_sharded", "sd_diarize_sharded_dev", "sd_write_rttm_ex", "sd_relabel_turns", "sd_relabel_turns_ex", "sd_last_confidence",
     "sd_debug_read_ws", "sd_test_pack_split_weights", "sd_resample", "sd_resample_len", "sd_diarize_wav", "sd_set_dump_dir",
     "sd_fcluster", "sd_segment_chunks", "sd_embed_signals",
-    "sd_linkage_ex", "sd_cluster_ex", "sd_set_option_f64", "sd_linkage_method_from_name",
+    "sd_linkage_ex", "sd_cluster_ex", "sd_set_option_f64", "sd_linkage_method_from_name", "sd_test_conv",
 ]
 # SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
 LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
@@ -124,6 +134,7 @@ def lib():
     L.sd_debug_read_ws.argtypes = [vp, C.c_char_p, i64, vp, i64]
     L.sd_test_pack_split_weights.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     L.sd_bench_conv.argtypes = [vp, i64] + [C.c_int] * 9 + [C.POINTER(dbl)]
+    L.sd_test_conv.argtypes = [vp, C.POINTER(ConvCase)] + [vp] * 10 + [C.c_char_p, C.c_int]
     _lib = L
     return L
 
@@ -535,6 +546,53 @@ class Diarizer:
         ms = C.c_double(0)
         self._chk(lib().sd_bench_conv(self._h, items, Tp, T, Cin, Cout, KT, dil, has_x2, dbg, reps, C.byref(ms)))
         return ms.value
+
+    def conv_case(self, w, x, *, n_in=None, n_out=None, tin=None, dense=None, dil=1, pad_mode=0, x2=None, bias=None, scale=None, shift=None,
+                  item_bias=None, act1=0, act2=0, prec=0, y_f32=False, try_narrow=False, shared=False, x_ld=None, x_col0=0, x2_col0=0,
+                  y_ld=None, y_col0=0, cin_pad=0, canary=-7776.0):
+        """sd_test_conv: one conv case through the product's dispatch.  w [kt][cout][cin], x / x2 [in_rows][cin]; compact row spaces
+        (n_in, n_out per item, tin) or dense=(items, tp_in, tin, tp_out, t).  Returns (the WHOLE [M + CONV_SLACK_ROWS][y_ld] output buffer
+        as f32, guards included; the name of the kernel that ran).  On an error the SdError carries the kernel name ("" = nothing launched)
+        as .kernel."""
+        w = np.ascontiguousarray(w, np.float32)
+        kt, cout, cin = w.shape
+        x = np.ascontiguousarray(x, np.float32)
+        k = ConvCase()
+        if dense is not None:
+            k.dense = 1
+            k.items, k.tp_in, k.tin, k.tp_out, k.t = [int(v) for v in dense]
+            M, in_rows = k.items * k.tp_out, k.items * k.tp_in
+            ni = no = None
+        else:
+            ni, no = np.ascontiguousarray(n_in, np.int32), np.ascontiguousarray(n_out, np.int32)
+            assert ni.shape == no.shape and ni.ndim == 1
+            k.items, k.tin = len(ni), int(tin)
+            M, in_rows = int(no.sum()), int(ni.sum())
+        assert x.shape == (in_rows, cin), (x.shape, in_rows, cin)
+        cpad = cin_pad or (-(-cin // 64) * 64 if prec == 1 else -(-cin // 32) * 32)
+        k.cin, k.cin_pad, k.cout, k.kt, k.dil, k.pad_mode = cin, cin_pad, cout, kt, dil, pad_mode
+        k.shared, k.x_col0, k.x2_col0, k.y_col0 = int(shared), x_col0, x2_col0, y_col0
+        k.y_ld = int(y_ld) if y_ld is not None else y_col0 + cout
+        k.x_ld = int(x_ld) if x_ld is not None else (k.y_ld if shared else x_col0 + cpad)
+        k.act1, k.act2, k.prec, k.y_f32, k.try_narrow, k.canary = act1, act2, prec, int(y_f32), int(try_narrow), canary
+        opt = {}
+        for name, arr, shape in (("x2", x2, (in_rows, cin)), ("bias", bias, (cout,)), ("scale", scale, (cout,)), ("shift", shift, (cout,)),
+                                 ("item_bias", item_bias, (k.items, cout))):
+            if arr is not None:
+                arr = np.ascontiguousarray(arr, np.float32)
+                assert arr.shape == shape, (name, arr.shape, shape)
+            opt[name] = arr
+        k.has_x2 = int(x2 is not None)
+        y = np.zeros((M + CONV_SLACK_ROWS, k.y_ld), np.float32)
+        name = C.create_string_buffer(32)
+        p = lambda a: _ptr(a) if a is not None else None
+        rc = lib().sd_test_conv(self._h, C.byref(k), p(ni), p(no), _ptr(w), _ptr(x), p(opt["x2"]), p(opt["bias"]), p(opt["scale"]), p(opt["shift"]),
+                                p(opt["item_bias"]), _ptr(y), name, 32)
+        if rc:
+            e = SdError(rc, lib().sd_last_error(self._h).decode())
+            e.kernel = name.value.decode()
+            raise e
+        return y, name.value.decode()
 
     def read_ws(self, name, dtype, count, offset=0):
         """test hook: `count` elements of the named device workspace"""
