@@ -184,14 +184,14 @@ struct sd_ctx {
     bool skip_dead_rows = true;                 // ECAPA: skip row panels beyond nvalid + receptive field
     int64_t linkage_wgs = -1;                  // -1 auto, 0/1 single workgroup, else cooperative workgroups
     int64_t linkage_square = -1;               // -1 auto (full N x N distance matrix while it fits), 0 condensed, 1 square
-    int64_t linkage_one_xcd = 1;               // 1 = k_linkage_mw<true> (all workgroups on one XCD) when G <= 64
+    int64_t linkage_one_xcd = 1;               // 1 = the one-XCD forms (every workgroup on XCC 0) on a device with >= 256 CUs: the cooperative kernel where the plan has G <= 32 workgroups, k_linkage_hx where 31 workers fit; run_linkage clears it after a one-XCD poll timeout
     int64_t linkage_zero_phase = 1;            // a tie at height 0 (duplicate rows): the heap replay takes the merges at height 0, k_linkage_rg the rest (0 = whole replay)
     int64_t linkage_tie_kernel = 1;            // what finishes a job with exact ties: 1 = k_linkage_hx (heap replay, row work on worker workgroups; > 1 = that many workers), 0 = k_linkage_heap (one workgroup)
     int64_t linkage_prefetch = 0;              // k_linkage_rg: 1 = a helper wave per workgroup requests the rows of the runner-up neighbours ahead of time
     bool linkage_hx_wide = false;              // test: k_linkage_hx with 32-bit heap keys / positions in global memory (the form of N > 65 535) on any size
     bool linkage_force_heap = false;           // test / measurement: skip the cooperative kernel, go straight to the heap replay
-    int64_t linkage_kernel = -1;               // -1 auto / 1: k_linkage_rg (linkage_rg.hip) for the square form where its geometry fits; 0: k_linkage_mw
-    int64_t linkage_threads = 0;               // 0 auto (256, or 1024 for N >= 60000), else 256 / 512 / 1024 threads per cooperative workgroup
+    int64_t linkage_kernel = -1;               // -1 auto / 1: k_linkage_rg (linkage_rg.hip) for the square form where its geometry fits (1: with more threads than linkage_threads asks for where that makes it fit), else k_linkage_mw (linkage_mw.hip); 0: k_linkage_mw
+    int64_t linkage_threads = 0;               // 0 auto (linkage_plan: k_linkage_rg 256, doubled until its geometry fits; k_linkage_mw 512 for N >= 8000 -- one XCD: N >= 16000 --, else 256), else rounded down to 128 / 256 / 512 / 1024 threads per cooperative workgroup
     int num_cu = 256;
     bool constrained_assignment = false;        // Clustering.py:81-94 (one cluster per local speaker of a chunk)
     // the three hyper-parameters of Clustering.py:251-276; defaults = what the reference hard-codes (sd.cpp:2049-2056)
@@ -347,7 +347,7 @@ int write_step_dumps(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t 
 int64_t count_frames_host(int64_t chunks);
 int sd_np_rint_host(double v);
 int64_t closest_frame_host(double w_start, double w_step, double w_dur, double t);
-// ---- cluster.hip
+// ---- linkage.hip
 int run_linkage(sd_ctx* c, const double* d_X, int64_t N, int d, double* d_Z, int method = SD_LINKAGE_CENTROID, int metric = SD_METRIC_EUCLIDEAN);
 int run_cluster_labels(sd_ctx* c, const double* d_X, int64_t N, int d, double cutoff, std::vector<int>& labels1, std::vector<double>* Zout = nullptr,
                        int method = SD_LINKAGE_CENTROID, int metric = SD_METRIC_EUCLIDEAN);

@@ -1,8 +1,10 @@
-// linkage_dev.h -- device helpers shared by the linkage kernels (cluster.hip: k_linkage_heap, k_linkage_mw; linkage_rg.hip: k_linkage_rg; linkage_hx.hip:
-// k_linkage_hx), the words of the `sync` block they and the host talk through, and the launchers run_linkage drives.
-// Translation units that include this file are compiled with -ffp-contract=off (Makefile EXACT): fp64 results bit-identical to the reference's x86 build.
+// linkage_dev.h -- device helpers shared by the linkage kernels (k_linkage_rg, k_linkage_mw, k_linkage_hx, k_linkage_heap: one file each, linkage_<name>.hip)
+// and the preparation kernels (linkage.hip), the words of the `sync` block they and the host talk through, and the launchers run_linkage (linkage.hip) drives.
+// Translation units that include this file are compiled with -ffp-contract=off (Makefile EXACT; exact_fp.h refuses any other build): fp64 results
+// bit-identical to the reference's x86 build.
 #pragma once
 #include "common.h"
+#include "exact_fp.h"
 #include <cfloat>
 #include <cmath>
 #include <type_traits>
@@ -159,7 +161,6 @@ constexpr int SYNC_WORDS = 32 + 16 * 256;
 // slot, so no agent-scope release / acquire -- an L2 write-back and a full L2 invalidate per merge -- is needed, and
 // each workgroup's private state (cluster sizes, freshness flags) stays cached.
 template <class T> __device__ __forceinline__ T LDG(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <class T> __device__ __forceinline__ void STG(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // One-XCD form (k_linkage_mw<true>): every participating workgroup sits on the SAME XCD (checked in the kernel from
 // HW_REG_XCC_ID, not assumed), so that XCD's L2 is the point of coherence: stores stay plain -- they write through the CU's L1
 // and KEEP the line in the L2 (an sc1 store drops it, and even a same-XCD reader then pays the cross-XCD round trip) -- while
@@ -170,14 +171,23 @@ template <bool ONEX, class T> __device__ __forceinline__ void STX(T* p, T v)
     else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// ---------------------------------------------------------------- launchers run_linkage (cluster.hip) drives
+// ---------------------------------------------------------------- launchers run_linkage (linkage.hip) drives
 // linkage_rg.hip
 bool linkage_rg_fits(int64_t N, int G, int TH);
 bool linkage_rg_has(int method, bool onex, int G, int TH, int cap, int helper);
 hipError_t linkage_rg_launch(sd_ctx* c, int method, bool onex, int G, int TH, double* D, int n, int* cid, const int* nb, const double* md, const double* md2,
                              double* Z, MwGran* gran, unsigned* sync, int cap, int helper, int k0 = 0, const int* sz0 = nullptr, const int* ty0 = nullptr);
 int linkage_rg_slot_granules();
+// linkage_mw.hip: centroid only; at most linkage_mw_max_workgroups() workgroups; size_all = what linkage_mw_prepare set up (workspace cl_size_all)
+bool linkage_mw_has(int method);
+int linkage_mw_max_workgroups();
+int linkage_mw_slot_granules();
+int linkage_mw_prepare(sd_ctx* c, int64_t N, int G, bool square, int** size_all);
+hipError_t linkage_mw_launch(sd_ctx* c, bool onex, bool square, int G, int TH, double* D, int n, int* size_all, int* cid, int* nb, double* md, const double* md2,
+                             double* Z, MwGran* gran, unsigned* sync, int cap);
 // linkage_hx.hip
 bool linkage_hx_fits(int64_t N, int workers);
 int linkage_hx_run(sd_ctx* c, int method, bool onex, int workers, double* D, int64_t N, int* cid, int* size, int* tyv, int* nb, double* md, double* d_Z, bool* stopped,
                    double stop_above = (double)INFINITY, int64_t* merges_done = nullptr, bool* launched = nullptr);
+// linkage_heap.hip: the condensed matrix Dc with exact nb / md, size = 1, cid = iota; every method
+int linkage_heap_run(sd_ctx* c, int method, double* Dc, int64_t N, int* size, int* cid, int* nb, double* md, double* d_Z);

@@ -16,6 +16,7 @@
 // Hand-offs are k_linkage_rg's 8-byte {payload, tag} granules: one command record master -> workers, one reply record per worker.
 // Z is bit-identical to the reference for every input (tests/test_gpu_parity.py: ties, lattices, duplicates).
 #include "common.h"
+#include "exact_fp.h"
 #include "linkage_dev.h"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -407,7 +408,7 @@ __global__ __launch_bounds__(HX_T) void k_linkage_hx(double* D, int n, int* cid,
     }
 }
 
-// ---------------------------------------------------------------- launcher (run_linkage, cluster.hip)
+// ---------------------------------------------------------------- launcher (run_linkage, linkage.hip)
 bool linkage_hx_fits(int64_t N, int workers)
 {
     if (workers < 1 || workers > HX_GMAX || N < 3) return false;

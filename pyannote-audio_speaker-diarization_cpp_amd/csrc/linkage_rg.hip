@@ -1,7 +1,7 @@
 // linkage_rg.hip -- k_linkage_rg: the cooperative centroid linkage (Clustering::linkage's fast_linkage, cl.cpp:289-406) with the
 // per-column state in REGISTERS and everything a merge needs travelling in the slots.
 //
-// Same algorithm, same matrix layout and same exchange as k_linkage_mw<*, true> (cluster.hip: full N x N distance matrix, a workgroup
+// Same algorithm, same matrix layout and same exchange as k_linkage_mw<*, true> (linkage_mw.hip: full N x N distance matrix, a workgroup
 // owns a contiguous range of COLUMNS, row y is rewritten and not mirrored, the current copy of an entry lives in the row of the cluster
 // that was a merge's survivor last -- index `ty` --, two-level lower bounds, cooperative refresh of stale rows, 8-byte tagged granules),
 // so Z is the same bit for bit.  What differs is where a merge round spends its time (profiles/r05_linkage_*.txt):
@@ -18,6 +18,7 @@
 // Ties: as k_linkage_mw, a merge is taken only while the closest pair is unique; otherwise sync[SYNC_TIE] is raised and run_linkage hands the
 // job to the kernel that replays the reference's heap.
 #include "common.h"
+#include "exact_fp.h"
 #include "linkage_dev.h"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -40,7 +41,7 @@ struct RQ { double v; int i; double v2; int sz, ty; };
 __device__ __forceinline__ RCand rc_none() { RCand c; c.v = INFINITY; c.i = -1; c.y = -1; c.fl = 0; c.szi = 0; c.szy = 0; c.tyi = -1; c.tyy = -1; return c; }
 __device__ __forceinline__ RQ rq_none() { RQ q; q.v = INFINITY; q.i = -1; q.v2 = INFINITY; q.sz = 0; q.ty = -1; return q; }
 
-// sequential accumulation of one row into a thread's running candidate (rules of cand_acc / cbetter, cluster.hip)
+// sequential accumulation of one row into a thread's running candidate (rules of cand_acc / cbetter, linkage_mw.hip)
 __device__ __forceinline__ void rc_acc(RCand& m, double v, int z, int y, int fl, int szi, int szy, int tyi, int tyy)
 {
     if (m.i < 0 || v < m.v) { m.v = v; m.i = z; m.y = y; m.fl = fl; m.szi = szi; m.szy = szy; m.tyi = tyi; m.tyy = tyy; }

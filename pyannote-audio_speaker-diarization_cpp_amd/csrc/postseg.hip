@@ -7,6 +7,7 @@
 // vectors for a5; here a4+a6 are one wave per chunk and a5 is a deterministic gather
 // (each output frame reads the <= 9 chunks that cover it; no atomics).
 #include "common.h"
+#include "exact_fp.h"
 #include <cfloat>
 #include <cmath>
 

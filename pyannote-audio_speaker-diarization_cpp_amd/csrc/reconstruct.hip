@@ -7,6 +7,7 @@
 // cover it straight from the raw f32 scores (deterministic chunk order, no atomics), and a second
 // kernel picks the count[t] most active clusters per frame.
 #include "common.h"
+#include "exact_fp.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>

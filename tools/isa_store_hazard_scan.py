@@ -12,7 +12,7 @@ tmp = tempfile.mkdtemp(prefix="isa_")
 bad = 0
 for src in srcs:
     out = os.path.join(tmp, os.path.basename(src) + ".s")
-    exact = ["-ffp-contract=off"] if os.path.basename(src) in ("postseg.hip", "cluster.hip", "reconstruct.hip", "linkage_rg.hip", "linkage_hx.hip") else []
+    exact = ["-ffp-contract=off", "-DSD_EXACT_FP"] if os.path.basename(src) in ("postseg.hip", "cluster.hip", "reconstruct.hip", "linkage.hip", "linkage_rg.hip", "linkage_mw.hip", "linkage_hx.hip", "linkage_heap.hip") else []
     r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"),
                         "-S", "--cuda-device-only", "-o", out, src] + exact, capture_output=True, text=True)
     if r.returncode != 0:
