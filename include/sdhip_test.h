@@ -33,6 +33,13 @@ int sd_debug_read_ws(sd_ctx*, const char* name, int64_t offset, void* h_out, int
  * multiple of 32, channels >= cin ignored), out_halves = 2 * K * Cout * CinPad fp16 bit patterns: per 32-channel chunk of a row
  * [hi 0..7 | lo 0..7 | hi 8..15 | ...] of w * 2^e; *inv_scale = 2^-e */
 int sd_test_pack_split_weights(const float* w, int K, int Cout, int CinPad, int cin, uint16_t* out_halves, float* inv_scale);
+/* host only, no context: the batches the embedding stage forms for n items of nvalid[i] valid frames (1 .. 501) at option emb_batch_items =
+ * batch_items (rounded as the stage rounds it: down to a multiple of 96, at least 96) and option skip_dead_rows.  balance = 0: the greedy
+ * rule of sd_ecapa / sd_embed_signals (whole items while batch_items * 501 rows of the widest row space and 4 095 items hold them);
+ * balance = 1: the rule of the whole path, boundaries moved to where the wide-tile launches waste the least (ecapa.hip).  Writes the end
+ * index (exclusive) of every batch to bounds[0 .. cap) and returns the number of batches, or -SD_ERR_ARG (n < 0, cap < 0, a null pointer
+ * with n > 0, more batches than cap, or a row space of more than 0x7fffffff / 4 rows, which the stage's int offsets refuse too). */
+int64_t sd_test_emb_batches(const int32_t* nvalid, int64_t n, int64_t batch_items, int skip_dead_rows, int balance, int64_t* bounds, int64_t cap);
 /* test / tuning keys of sd_set_option (defaults are the measured optimum; results do not depend on the tuning keys):
  * "profile", "emb_batch_items", "seg_batch_chunks", "linkage_wgs" (-1 auto, 0 one workgroup), "linkage_threads", "linkage_one_xcd",
  * "skip_dead_rows", "virtual_world" (test mode: a communicator of ONE rank plays all W ranks of the plan in turn, slot by slot, so plan +

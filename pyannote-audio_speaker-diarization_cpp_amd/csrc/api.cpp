@@ -1,9 +1,8 @@
-// api.cpp -- the C ABI of libsdhip.so (include/sdhip.h): context, host-buffer wrappers
-// around the device pipelines, whole-path driver (speakerDiarization(), sd.cpp:2937-3234),
-// wav reader (wav.h:62-126) and the measurement hooks.
+// api.cpp -- the C ABI of libsdhip.so (include/sdhip.h): context and options, host-buffer wrappers
+// around the embedding stage, wav reader (wav.h:62-126), output formats and the measurement hooks.
+// (The other stage wrappers and the whole-path driver are in pipeline.cpp.)
 #include "common.h"
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 
@@ -28,22 +27,21 @@ extern "C" sd_ctx* sd_create(const char* seg_path, const char* emb_path, int dev
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { g_create_err = "hipStreamCreate failed"; delete c; return nullptr; }
     auto fail = [&](const std::string& m) { g_create_err = m; sd_destroy(c); return (sd_ctx*)nullptr; };
     const bool trace = getenv("SD_TRACE_CREATE") != nullptr;          // where the start-up time goes (tools/cold_start.py)
-    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t0 = now();
+    double t0 = now_ms();
     if (seg_path && seg_path[0]) {
         Pack p; std::string e;
         if (load_model_any(seg_path, 0, p, e)) return fail(e);
-        const double t1 = now();
+        const double t1 = now_ms();
         if (build_seg_weights(c, p)) return fail(c->err);
-        if (trace) fprintf(stderr, "sd_create: segmentation model read %.1f ms, layouts + upload %.1f ms\n", t1 - t0, now() - t1);
+        if (trace) fprintf(stderr, "sd_create: segmentation model read %.1f ms, layouts + upload %.1f ms\n", t1 - t0, now_ms() - t1);
     }
-    t0 = now();
+    t0 = now_ms();
     if (emb_path && emb_path[0]) {
         Pack p; std::string e;
         if (load_model_any(emb_path, 1, p, e)) return fail(e);
-        const double t1 = now();
+        const double t1 = now_ms();
         if (build_ecapa_weights(c, p)) return fail(c->err);
-        if (trace) fprintf(stderr, "sd_create: embedding model read %.1f ms, layouts + upload %.1f ms\n", t1 - t0, now() - t1);
+        if (trace) fprintf(stderr, "sd_create: embedding model read %.1f ms, layouts + upload %.1f ms\n", t1 - t0, now_ms() - t1);
     }
     c->err.clear();
     return c;
@@ -181,14 +179,6 @@ extern "C" int64_t sd_num_chunks(int64_t n, int64_t* last_len)
     return cnt;
 }
 
-struct DevTmp {   // RAII device scratch for the host-pointer wrappers
-    void* p = nullptr;
-    ~DevTmp() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16) == hipSuccess ? 0 : 1; }
-};
-#define DTMP(ctx, var, bytes) DevTmp var; if (var.alloc(bytes)) SD_FAIL(ctx, SD_ERR_HIP, "hipMalloc(%zu) failed", (size_t)(bytes))
-#define ENTER(ctx) do { if (!(ctx)) return SD_ERR_ARG; (ctx)->err.clear(); if (hipSetDevice((ctx)->device) != hipSuccess) SD_FAIL(ctx, SD_ERR_HIP, "hipSetDevice failed"); } while (0)
-
 // ------------------------------------------------------------------ embedding path
 extern "C" int sd_embed_dev(sd_ctx* c, const float* d_wav, int64_t n, const float* d_masks, int64_t items, int64_t first_item, float* d_emb)
 {
@@ -264,20 +254,7 @@ extern "C" int sd_ecapa(sd_ctx* c, const float* h_feats, const float* h_lens, in
     DTMP(c, df, tmp.size() * sizeof(float));
     HIPCHK(c, hipMemcpy(df.p, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(dv.p, nv.data(), items * sizeof(int), hipMemcpyHostToDevice));
-    int64_t nb = (c->emb_batch_items / 96) * 96; if (nb < 96) nb = 96;
-    const int64_t cap_rows = nb * SD_TP;
-    rc = ecapa_run_batches(c, [&]() -> int {
-        for (int64_t a0 = 0; a0 < items;) {
-            int64_t a1 = a0;
-            while (a1 < items && a1 - a0 < ROWTAB_MAX_ITEMS && rowoff[(size_t)a1 + 1] - rowoff[(size_t)a0] <= cap_rows) ++a1;
-            if (a1 == a0) a1 = a0 + 1;
-            const int r = run_ecapa(c, (const float*)df.p, (const int*)dv.p, plan, a0, a1, (float*)de.p);
-            if (r) return r;
-            a0 = a1;
-        }
-        return SD_OK;
-    });
-    if (rc) return rc;
+    if ((rc = ecapa_run_items(c, (const float*)df.p, (const int*)dv.p, plan, c->emb_batch_items, false, (float*)de.p))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(h_emb, de.p, items * SD_EMB_DIM * sizeof(float), hipMemcpyDeviceToHost));
     return SD_OK;
@@ -302,42 +279,26 @@ extern "C" int sd_embed_signals(sd_ctx* c, const float* h_signals, const float* 
     }
     const int64_t ns = B * (int64_t)SD_CHUNK;
     // persistent workspaces, not per-call allocations: the reference calls infer once per batch of 32 items (677 times per hour of audio)
-    WS(c, float, dw_p, "sig_wav", ns + 512); WS(c, int, dv_p, "sig_nvalid", B); WS(c, int, dn_p, "sig_nnorm", B);
-    WS(c, int, dr_p, "sig_rowoff", EC_SPACES * (B + 1)); WS(c, float, de_p, "sig_emb", B * SD_EMB_DIM);
-    struct { void* p; } dw{dw_p}, dv{dv_p}, dn{dn_p}, dr{dr_p}, de{de_p};
-    HIPCHK(c, hipMemcpyAsync(dw.p, h_signals, ns * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync((float*)dw.p + ns, 0, 512 * sizeof(float), c->stream));
-    HIPCHK(c, hipMemcpyAsync(dv.p, nv.data(), B * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dn.p, nn.data(), B * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    WS(c, float, dw, "sig_wav", ns + 512); WS(c, int, dv, "sig_nvalid", B); WS(c, int, dn, "sig_nnorm", B);
+    WS(c, int, dr, "sig_rowoff", EC_SPACES * (B + 1)); WS(c, float, de, "sig_emb", B * SD_EMB_DIM);
+    HIPCHK(c, hipMemcpyAsync(dw, h_signals, ns * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(dw + ns, 0, 512 * sizeof(float), c->stream));
+    HIPCHK(c, hipMemcpyAsync(dv, nv.data(), B * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dn, nn.data(), B * sizeof(int), hipMemcpyHostToDevice, c->stream));
     EcapaRowPlan plan;
-    int rc = ecapa_row_plan(c, nv.data(), B, plan, (int*)dr.p);          // (synchronises the stream: the host vectors above may go)
+    int rc = ecapa_row_plan(c, nv.data(), B, plan, dr);          // (synchronises the stream: the host vectors above may go)
     if (rc) return rc;
-    const std::vector<int>& rowoff = plan.off[0];
-    WS(c, float, df_p, "sig_feats", (size_t)rowoff[(size_t)B] * SD_FEAT_LD);
-    struct { void* p; } df{df_p};
+    WS(c, float, df, "sig_feats", (size_t)plan.off[0][(size_t)B] * SD_FEAT_LD);
     if ((rc = frontend_prepare_signals(c, B))) return rc;
     const int64_t origin = c->wav_origin;
     c->wav_origin = 0; c->fe_bill_samples = -1;
-    rc = frontend_features(c, (const float*)dw.p, ns, 0, B, false, (const int*)dn.p, (const int*)dr.p, (float*)df.p, true);
+    rc = frontend_features(c, dw, ns, 0, B, false, dn, dr, df, true);
     c->wav_origin = origin;
     if (rc) return rc;
-    int64_t nb = (c->emb_batch_items / 96) * 96; if (nb < 96) nb = 96;
-    if (nb > 768 && !c->emb_batch_explicit) nb = 768;                        // an operator-level call: the small arena
-    const int64_t cap_rows = nb * SD_TP;
-    rc = ecapa_run_batches(c, [&]() -> int {
-        for (int64_t a0 = 0; a0 < B;) {
-            int64_t a1 = a0;
-            while (a1 < B && a1 - a0 < ROWTAB_MAX_ITEMS && rowoff[(size_t)a1 + 1] - rowoff[(size_t)a0] <= cap_rows) ++a1;
-            if (a1 == a0) a1 = a0 + 1;
-            const int r = run_ecapa(c, (const float*)df.p, (const int*)dv.p, plan, a0, a1, (float*)de.p);
-            if (r) return r;
-            a0 = a1;
-        }
-        return SD_OK;
-    });
-    if (rc) return rc;
+    const int64_t nb = c->emb_batch_explicit ? c->emb_batch_items : std::min<int64_t>(c->emb_batch_items, 768);      // an operator-level call: the small arena
+    if ((rc = ecapa_run_items(c, df, dv, plan, nb, false, de))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(h_emb, de.p, B * SD_EMB_DIM * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(h_emb, de, B * SD_EMB_DIM * sizeof(float), hipMemcpyDeviceToHost));
     return SD_OK;
 }
 

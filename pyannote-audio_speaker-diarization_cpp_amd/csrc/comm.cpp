@@ -11,19 +11,12 @@
 #include "common.h"
 #include <rccl/rccl.h>
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <unistd.h>
 
-#define ENTER(ctx) do { if (!(ctx)) return SD_ERR_ARG; (ctx)->err.clear(); if (hipSetDevice((ctx)->device) != hipSuccess) SD_FAIL(ctx, SD_ERR_HIP, "hipSetDevice failed"); } while (0)
 #define NCCLCHK(ctx, expr) do { ncclResult_t _r = (expr); if (_r != ncclSuccess) SD_FAIL(ctx, SD_ERR_HIP, "%s failed: %s", #expr, ncclGetErrorString(_r)); } while (0)
 
 static_assert(SD_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "sdhip.h and rccl.h disagree on the size of the rendezvous id");
-
-static double now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // contiguous chunk ranges, every one starting on a multiple of 32 chunks.  rank0_permille < 0: equal shares; otherwise
 // rank 0 (which also finalizes) infers that share of the chunks and the others split the rest evenly.

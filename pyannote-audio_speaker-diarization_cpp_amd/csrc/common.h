@@ -230,6 +230,17 @@ template <class T> inline T* ws_get(sd_ctx* c, const char* name, size_t count) {
 }
 #define WS(ctx, T, var, name, count) T* var = ws_get<T>(ctx, name, (size_t)(count)); if (!var) SD_FAIL(ctx, SD_ERR_HIP, "hipMalloc of workspace %s (%zu bytes) failed", name, (size_t)(count) * sizeof(T))
 
+// ---- helpers of the host wrappers (api.cpp, pipeline.cpp, comm.cpp) and of the one-dimensional launches
+struct DevTmp {   // RAII device scratch for the host-pointer wrappers
+    void* p = nullptr;
+    ~DevTmp() { if (p) (void)hipFree(p); }
+    int alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16) == hipSuccess ? 0 : 1; }
+};
+#define DTMP(ctx, var, bytes) DevTmp var; if (var.alloc(bytes)) SD_FAIL(ctx, SD_ERR_HIP, "hipMalloc(%zu) failed", (size_t)(bytes))
+#define ENTER(ctx) do { if (!(ctx)) return SD_ERR_ARG; (ctx)->err.clear(); if (hipSetDevice((ctx)->device) != hipSuccess) SD_FAIL(ctx, SD_ERR_HIP, "hipSetDevice failed"); } while (0)
+#define GRID1(n) dim3((unsigned)(((n) + 255) / 256)), dim3(256)
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
 // profiling bracket: records events around one launch when ctx->profile is set
 struct ProfScope {
     sd_ctx* c; std::string name; hipEvent_t e0 = nullptr, e1 = nullptr; double flops, bytes;
@@ -334,7 +345,13 @@ int ecapa_rows_to_half(sd_ctx* c, const float* d_f32, void* d_f16, int64_t n4); 
 int ecapa_row_plan(sd_ctx* c, const int* h_nvalid, int64_t n, EcapaRowPlan& plan, int* d_off /*[EC_SPACES][n + 1]*/);
 // items [a0, a1) of the plan; d_feats = space-0 rows of ALL the plan's items
 int run_ecapa(sd_ctx* c, const float* d_feats, const int* d_nvalid /*[n]*/, const EcapaRowPlan& plan, int64_t a0, int64_t a1, float* d_emb /*[n][192]*/);
-int ecapa_run_batches(sd_ctx* c, const std::function<int()>& batches);      // x3 mode: repeats the batches on the f32 kernels if an embedding came out non-finite
+// end index of every batch of the plan's items: whole items, at most cap_rows space-0 rows and ROWTAB_MAX_ITEMS items each (a single item always
+// fits); balance = boundaries moved to where the wide-tile launches waste the least (ecapa.hip).  Pure host arithmetic on the prefix sums
+std::vector<int64_t> ecapa_plan_batches(const EcapaRowPlan& plan, int64_t cap_rows, bool balance);
+int64_t ecapa_round_items(int64_t nb);      // the item budget of a batch as it is used: a multiple of 96, at least 96
+// all the plan's items in planned batches of a row budget of nb full-length items (run_ecapa per batch); x3 mode: repeats the batches on the f32
+// kernels if an embedding came out non-finite
+int ecapa_run_items(sd_ctx* c, const float* d_feats, const int* d_nvalid, const EcapaRowPlan& plan, int64_t nb, bool balance, float* d_emb);
 int run_embed(sd_ctx* c, const float* d_wav, int64_t n, const float* d_masks, int64_t items, int64_t first_item, float* d_emb);
 // ---- pyannet.hip
 int run_segment(sd_ctx* c, const float* d_wav, int64_t n, int64_t chunk_lo, int64_t chunk_hi, float* d_seg);

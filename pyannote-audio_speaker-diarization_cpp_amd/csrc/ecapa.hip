@@ -188,8 +188,6 @@ static ConvArgs conv_args(const ConvLayer& L, const void* X, int x_ld, void* Y, 
     return a;
 }
 
-#define GRID1(n) dim3((unsigned)(((n) + 255) / 256)), dim3(256)
-
 // One-sided reach of the network: 2 (block0, k5) + 7 * (2 + 3 + 4) (each Res2Net block chains 7 k3 convs of dilation 2 / 3 / 4;
 // the 1x1 convs and the SE gate add none) = 65 frames.  Frames >= nvalid are excluded from every statistic (SE mean, ASP),
 // so frames at or beyond min(501, nvalid + 65) cannot influence the embedding and are not stored at all.  The margin shrinks
@@ -381,7 +379,7 @@ int run_ecapa(sd_ctx* c, const float* d_feats, const int* d_nvalid, const EcapaR
 
 // runs `batches` (a sequence of run_ecapa calls over one set of items); in x3 mode it runs them again on the f32 kernels when the flag says that an
 // embedding came out non-finite (one stream synchronisation per call of this function, x3 mode only)
-int ecapa_run_batches(sd_ctx* c, const std::function<int()>& batches)
+static int ecapa_run_batches(sd_ctx* c, const std::function<int()>& batches)
 {
     if (c->ecapa_precision != 3) return batches();
     WS(c, int, flag, "ec_x3_flag", 1);
@@ -399,20 +397,121 @@ int ecapa_run_batches(sd_ctx* c, const std::function<int()>& batches)
     return rc;
 }
 
-// host side of the compact row plan: first row of every item in each space, from the items' nvalid (uploaded to d_off)
-int ecapa_row_plan(sd_ctx* c, const int* h_nvalid, int64_t n, EcapaRowPlan& plan, int* d_off)
+// host side of the compact row plan: first row of every item in each space, from the items' nvalid.  Returns 0, or the row count of a space
+// that is beyond what the int offsets are allowed to hold
+static int64_t ec_fill_offsets(const int* h_nvalid, int64_t n, bool skip_dead_rows, EcapaRowPlan& plan)
 {
-    plan.n = n; plan.d_off = d_off;
+    plan.n = n;
     for (int sp = 0; sp < EC_SPACES; ++sp) {
         std::vector<int>& off = plan.off[sp];
         off.assign((size_t)n + 1, 0);
         int64_t acc = 0;
-        for (int64_t i = 0; i < n; ++i) { off[(size_t)i] = (int)acc; acc += ec_space_rows(h_nvalid[i], c->skip_dead_rows, sp); }
-        if (acc > 0x7fffffff / 4) SD_FAIL(c, SD_ERR_ARG, "embedding stage: %lld feature rows in one shard (limit %d)", (long long)acc, 0x7fffffff / 4);
+        for (int64_t i = 0; i < n; ++i) { off[(size_t)i] = (int)acc; acc += ec_space_rows(h_nvalid[i], skip_dead_rows, sp); }
+        if (acc > 0x7fffffff / 4) return acc;
         off[(size_t)n] = (int)acc;
-        HIPCHK(c, hipMemcpyAsync(d_off + (size_t)sp * (n + 1), off.data(), (size_t)(n + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     }
+    return 0;
+}
+// ... and its upload to d_off
+int ecapa_row_plan(sd_ctx* c, const int* h_nvalid, int64_t n, EcapaRowPlan& plan, int* d_off)
+{
+    plan.d_off = d_off;
+    if (const int64_t over = ec_fill_offsets(h_nvalid, n, c->skip_dead_rows, plan))
+        SD_FAIL(c, SD_ERR_ARG, "embedding stage: %lld feature rows in one shard (limit %d)", (long long)over, 0x7fffffff / 4);
+    for (int sp = 0; sp < EC_SPACES; ++sp)
+        HIPCHK(c, hipMemcpyAsync(d_off + (size_t)sp * (n + 1), plan.off[sp].data(), (size_t)(n + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SD_OK;
+}
+
+int64_t ecapa_round_items(int64_t nb) { nb = (nb / 96) * 96; return nb < 96 ? 96 : nb; }
+
+// Batches by row budget: whole items, at most what fits the activation workspaces of cap_rows / 501 full-length items and what a row table can
+// number (ROWTAB_MAX_ITEMS), and always at least one item.  balance = false stops there (the greedy maximum).  balance = true: within that the
+// boundary is placed where the wide-tile launches of the batch waste the least: a launch over M rows runs
+// ceil(ceil(M / 256) / 64) rounds of 64 row panels (8 XCDs x 8 panels per super-block) per group of column tiles, and the
+// last round is only as full as M happens to leave it; the four row spaces have different M, so the best compromise is
+// searched over the last few dozen items (results do not depend on the batching: every row's bits are placement-free).
+// The last batch -- a greedy maximum that reaches the end -- is taken as it is.
+std::vector<int64_t> ecapa_plan_batches(const EcapaRowPlan& plan, int64_t cap_rows, bool balance)
+{
+    const std::vector<int>& rowoff = plan.off[0];
+    const int64_t n = plan.n, rows_all = rowoff[(size_t)n];
+    auto batch_efficiency = [&](int64_t a0, int64_t a1) -> double {
+        // {row space, weight = K x groups of 4 column tiles} of the 256 x 256 launches: block0, tdnn1 / tdnn2 of the three blocks, MFA,
+        // ASP conv; 16 384 rows (64 panels) per round.  (Adding the 128 x 128 launches -- 65 536 rows per round -- to the model measured
+        // the same: their period is longer than the window searched.)
+        static const int L[9][2] = {{0, 400}, {0, 1024}, {1, 1024}, {1, 1024}, {2, 1024}, {2, 1024}, {3, 1024}, {3, 3 * 3072}, {3, 2 * 128}};
+        double ideal = 0.0, actual = 0.0;
+        for (int l = 0; l < 9; ++l) {
+            const int64_t M = plan.off[L[l][0]][(size_t)a1] - plan.off[L[l][0]][(size_t)a0];
+            ideal += (double)L[l][1] * (double)M / 16384.0;
+            actual += (double)L[l][1] * (double)((M + 16383) / 16384);
+        }
+        return actual > 0.0 ? ideal / actual : 0.0;
+    };
+    const int64_t n_batches = (rows_all + cap_rows - 1) / cap_rows;
+    std::vector<int64_t> ends;
+    for (int64_t a0 = 0, k = 1; a0 < n; ++k) {
+        int64_t a_max = a0;                                   // the most the workspaces take
+        while (a_max < n && a_max - a0 < ROWTAB_MAX_ITEMS && rowoff[(size_t)a_max + 1] - rowoff[(size_t)a0] <= cap_rows) ++a_max;
+        if (a_max == a0) a_max = a0 + 1;
+        int64_t a1 = a_max;
+        if (a_max < n && balance) {
+            // aim at equal shares of what is left, then look for the best boundary among 160 items around the aim
+            const int64_t left_batches = n_batches - k + 1 > 1 ? n_batches - k + 1 : 1;
+            const int64_t aim_rows = rowoff[(size_t)a0] + (rows_all - rowoff[(size_t)a0] + left_batches - 1) / left_batches;
+            int64_t aim = a0 + 1;
+            while (aim < a_max && rowoff[(size_t)aim + 1] <= aim_rows) ++aim;
+            if (aim + 80 < a_max) aim += 80; else aim = a_max;
+            double best = -1.0;
+            for (int64_t cand = aim; cand > a0 && cand + 160 > aim; --cand) {
+                const double e = batch_efficiency(a0, cand);
+                if (e > best) { best = e; a1 = cand; }
+            }
+        }
+        ends.push_back(a1);
+        a0 = a1;
+    }
+    return ends;
+}
+
+int ecapa_run_items(sd_ctx* c, const float* d_feats, const int* d_nvalid, const EcapaRowPlan& plan, int64_t nb, bool balance, float* d_emb)
+{
+    const std::vector<int64_t> ends = ecapa_plan_batches(plan, ecapa_round_items(nb) * SD_TP, balance);
+    return ecapa_run_batches(c, [&]() -> int {
+        int64_t a0 = 0;
+        for (const int64_t a1 : ends) {
+            if (const int rc = run_ecapa(c, d_feats, d_nvalid, plan, a0, a1, d_emb)) return rc;
+            a0 = a1;
+        }
+        return SD_OK;
+    });
+}
+
+// test hook (sdhip_test.h): the batches ecapa_run_items would form for these items; host arithmetic only
+extern "C" int64_t sd_test_emb_batches(const int32_t* nvalid, int64_t n, int64_t batch_items, int skip_dead_rows, int balance, int64_t* bounds, int64_t cap)
+{
+    if (n < 0 || cap < 0 || (n > 0 && (!nvalid || !bounds))) return -SD_ERR_ARG;
+    EcapaRowPlan plan;
+    if (ec_fill_offsets(nvalid, n, skip_dead_rows != 0, plan)) return -SD_ERR_ARG;
+    const std::vector<int64_t> ends = ecapa_plan_batches(plan, ecapa_round_items(batch_items) * SD_TP, balance != 0);
+    if ((int64_t)ends.size() > cap) return -SD_ERR_ARG;
+    for (size_t b = 0; b < ends.size(); ++b) bounds[b] = ends[b];
+    return (int64_t)ends.size();
+}
+
+// profile only: bills the front end what it really reads and writes -- the selected samples of the live items, the stored frames
+static int bill_frontend(sd_ctx* c, const int* d_cidx, int64_t items, int64_t rows_all)
+{
+    const int* d_counts = c->ws["fe_counts"].as<int>();
+    std::vector<int> h_cnt((size_t)items), h_cidx((size_t)items);
+    HIPCHK(c, hipMemcpyAsync(h_cnt.data(), d_counts, (size_t)items * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_cidx.data(), d_cidx, (size_t)items * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int64_t tot = 0;
+    for (int64_t i = 0; i < items; ++i) if (h_cidx[(size_t)i] >= 0) tot += h_cnt[(size_t)i];
+    c->fe_bill_samples = tot; c->fe_bill_frames = rows_all;
     return SD_OK;
 }
 
@@ -422,7 +521,7 @@ int run_embed(sd_ctx* c, const float* d_wav, int64_t n, const float* d_masks, in
     int64_t nb = c->emb_batch_items;
     if (!c->emb_batch_explicit && c->embed_calls == 0 && nb > 768) nb = 768;      // first call of a context: the small arena (common.h)
     c->embed_calls++;
-    nb = (nb / 96) * 96; if (nb < 96) nb = 96;
+    nb = ecapa_round_items(nb);                                                   // (the retry ladder below steps on the budget as it is used)
     int rc;
     // front end for the whole range first: items that are NaN by rule (sd.cpp:2479-2549) are dropped here, so the
     // network always runs on full batches of live items (the reference computes the dead ones and overwrites them)
@@ -440,76 +539,21 @@ int run_embed(sd_ctx* c, const float* d_wav, int64_t n, const float* d_masks, in
     if (n_active > 0) {
         EcapaRowPlan plan;
         if ((rc = ecapa_row_plan(c, h_nvalid.data(), n_active, plan, d_rowoff))) return rc;
-        const std::vector<int>& rowoff = plan.off[0];
-        const int64_t rows_all = rowoff[(size_t)n_active];
+        const int64_t rows_all = plan.off[0][(size_t)n_active];
         WS(c, float, feats, "emb_feats", rows_all * SD_FEAT_LD);
         c->fe_bill_samples = -1;
-        if (c->profile) {               // bill the front end what it really reads and writes: selected samples of the live items, stored frames
-            const int* d_counts = c->ws["fe_counts"].as<int>();
-            std::vector<int> h_cnt((size_t)items), h_cidx((size_t)items);
-            HIPCHK(c, hipMemcpyAsync(h_cnt.data(), d_counts, (size_t)items * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(h_cidx.data(), cidx, (size_t)items * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            int64_t tot = 0;
-            for (int64_t i = 0; i < items; ++i) if (h_cidx[(size_t)i] >= 0) tot += h_cnt[(size_t)i];
-            c->fe_bill_samples = tot; c->fe_bill_frames = rows_all;
-        }
+        if (c->profile && (rc = bill_frontend(c, cidx, items, rows_all))) return rc;
         rc = frontend_features(c, d_wav, n, first_item, n_active, true, nnorm, d_rowoff, feats);
         c->fe_bill_samples = -1;
         if (rc) return rc;
-        // batches by row budget: whole items, at most what fits the activation workspaces of nb full-length items.  Within that the
-        // boundary is placed where the wide-tile launches of the batch waste the least: a launch over M rows runs
-        // ceil(ceil(M / 256) / 64) rounds of 64 row panels (8 XCDs x 8 panels per super-block) per group of column tiles, and the
-        // last round is only as full as M happens to leave it; the four row spaces have different M, so the best compromise is
-        // searched over the last few dozen items (results do not depend on the batching: every row's bits are placement-free).
         // A batch plan whose activation arena cannot be allocated (a second context on the GPU, an 8-h job beside the 80 GB distance matrix: the
         // default plan asks for ~57 GB at the 1-h size) is repeated with a smaller one -- 768 items (16 GB), then 96: every row's bits are
-        // batch-independent (tests/test_planted.py), so only time is lost.  Any other failure is returned as it is.
+        // batch-independent (tests/test_planted.py), so only time is lost.  Out of memory in the arena = a workspace named ec_*, recorded by
+        // ws_get (not recognised by the wording of the message): every ec_* buffer is released first.  Any other failure is returned as it is.
         for (;;) {
-        const int64_t cap_rows = nb * SD_TP;
-        auto batch_efficiency = [&](int64_t a0, int64_t a1) -> double {
-            // {row space, weight = K x groups of 4 column tiles} of the 256 x 256 launches: block0, tdnn1 / tdnn2 of the three blocks, MFA,
-            // ASP conv; 16 384 rows (64 panels) per round.  (Adding the 128 x 128 launches -- 65 536 rows per round -- to the model measured
-            // the same: their period is longer than the window searched.)
-            static const int L[9][2] = {{0, 400}, {0, 1024}, {1, 1024}, {1, 1024}, {2, 1024}, {2, 1024}, {3, 1024}, {3, 3 * 3072}, {3, 2 * 128}};
-            double ideal = 0.0, actual = 0.0;
-            for (int l = 0; l < 9; ++l) {
-                const int64_t M = plan.off[L[l][0]][(size_t)a1] - plan.off[L[l][0]][(size_t)a0];
-                ideal += (double)L[l][1] * (double)M / 16384.0;
-                actual += (double)L[l][1] * (double)((M + 16383) / 16384);
-            }
-            return actual > 0.0 ? ideal / actual : 0.0;
-        };
-        const int64_t n_batches = (rows_all + cap_rows - 1) / cap_rows;
-        c->ws_failed.clear();
-        rc = ecapa_run_batches(c, [&]() -> int {
-        int rc = SD_OK;
-        for (int64_t a0 = 0, k = 1; a0 < n_active; ++k) {
-            int64_t a_max = a0;                                   // the most the workspaces take
-            while (a_max < n_active && a_max - a0 < ROWTAB_MAX_ITEMS && rowoff[(size_t)a_max + 1] - rowoff[(size_t)a0] <= cap_rows) ++a_max;
-            if (a_max == a0) a_max = a0 + 1;
-            int64_t a1 = a_max;
-            if (a_max < n_active && c->skip_dead_rows) {
-                // aim at equal shares of what is left, then look for the best boundary among 160 items around the aim
-                const int64_t left_batches = n_batches - k + 1 > 1 ? n_batches - k + 1 : 1;
-                const int64_t aim_rows = rowoff[(size_t)a0] + (rows_all - rowoff[(size_t)a0] + left_batches - 1) / left_batches;
-                int64_t aim = a0 + 1;
-                while (aim < a_max && rowoff[(size_t)aim + 1] <= aim_rows) ++aim;
-                if (aim + 80 < a_max) aim += 80; else aim = a_max;
-                double best = -1.0;
-                for (int64_t cand = aim; cand > a0 && cand + 160 > aim; --cand) {
-                    const double e = batch_efficiency(a0, cand);
-                    if (e > best) { best = e; a1 = cand; }
-                }
-            }
-            if ((rc = run_ecapa(c, feats, nvalid, plan, a0, a1, emb_c))) return rc;
-            a0 = a1;
-        }
-        return rc;
-        });
-        // out of memory in the activation arena (a workspace named ec_*, recorded by ws_get -- not recognised by the wording of the message): every
-        // ec_* buffer is released and the batches are made smaller.  A failure of any other workspace is not retried
-        if (rc == SD_ERR_HIP && nb > 96 && c->ws_failed.rfind("ec_", 0) == 0) {
+            c->ws_failed.clear();
+            rc = ecapa_run_items(c, feats, nvalid, plan, nb, c->skip_dead_rows, emb_c);
+            if (rc != SD_ERR_HIP || nb <= 96 || c->ws_failed.rfind("ec_", 0) != 0) break;
             (void)hipStreamSynchronize(c->stream);
             (void)hipGetLastError();
             for (auto& kv : c->ws) if (kv.first.rfind("ec_", 0) == 0) kv.second.release();
@@ -517,9 +561,6 @@ int run_embed(sd_ctx* c, const float* d_wav, int64_t n, const float* d_masks, in
             nb = nb > 768 ? 768 : 96;
             c->stats["emb_arena_retries"].launches += 1;
             c->err.clear();
-            continue;
-        }
-        break;
         }
         if (rc) return rc;
     }

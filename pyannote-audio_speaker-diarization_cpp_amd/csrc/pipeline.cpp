@@ -3,18 +3,8 @@
 // embeddings -> [multi-GPU: all-gather here] -> count, clustering, reconstruction, annotation.
 #include "common.h"
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
-
-struct DevTmp {
-    void* p = nullptr;
-    ~DevTmp() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16) == hipSuccess ? 0 : 1; }
-};
-#define DTMP(ctx, var, bytes) DevTmp var; if (var.alloc(bytes)) SD_FAIL(ctx, SD_ERR_HIP, "hipMalloc(%zu) failed", (size_t)(bytes))
-#define ENTER(ctx) do { if (!(ctx)) return SD_ERR_ARG; (ctx)->err.clear(); if (hipSetDevice((ctx)->device) != hipSuccess) SD_FAIL(ctx, SD_ERR_HIP, "hipSetDevice failed"); } while (0)
-#define GRID1(n) dim3((unsigned)(((n) + 255) / 256)), dim3(256)
 
 // a1 tail: input_wav[i] = sample * 1.0f / 32768.0 (sd.cpp:2948-2951); division by 2^15 is exact in f32
 __global__ void k_pcm_to_f32(const int16_t* __restrict__ pcm, float* __restrict__ wav, int64_t n)
@@ -44,11 +34,6 @@ __global__ void k_plant_emb(float* __restrict__ emb, const float* __restrict__ p
     const float v = planted[i];
     __syncthreads();
     if (first == first) emb[i] = v;
-}
-
-static double now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 // ------------------------------------------------------------------ a2+a3
@@ -89,18 +74,17 @@ extern "C" int sd_segment_chunks(sd_ctx* c, const float* h_chunks, int64_t rows,
     ENTER(c);
     if (!h_chunks || !h_out || rows <= 0 || T < 1 || T > SD_CHUNK) SD_FAIL(c, SD_ERR_ARG, "sd_segment_chunks: bad argument (rows >= 1, 1 <= T <= %d)", SD_CHUNK);
     // persistent workspaces, not per-call allocations: slide() calls infer once per batch of 32 chunks (225 times per hour of audio)
-    WS(c, float, dw_p, "rows_wav", rows * T + 512); WS(c, float, ds_p, "rows_seg", rows * SD_FRAMES * 3);
-    struct { void* p; } dw{dw_p}, ds{ds_p};
-    HIPCHK(c, hipMemcpyAsync(dw.p, h_chunks, rows * T * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync((float*)dw.p + rows * T, 0, 512 * sizeof(float), c->stream));
+    WS(c, float, dw, "rows_wav", rows * T + 512); WS(c, float, ds, "rows_seg", rows * SD_FRAMES * 3);
+    HIPCHK(c, hipMemcpyAsync(dw, h_chunks, rows * T * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(dw + rows * T, 0, 512 * sizeof(float), c->stream));
     const bool padded = c->wav_padded;
     c->wav_padded = true;
     int fr = 0;
-    const int rc = run_segment_rows(c, (const float*)dw.p, rows, (int)T, (float*)ds.p, &fr);
+    const int rc = run_segment_rows(c, dw, rows, (int)T, ds, &fr);
     c->wav_padded = padded;
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(h_out, ds.p, rows * SD_FRAMES * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(h_out, ds, rows * SD_FRAMES * 3 * sizeof(float), hipMemcpyDeviceToHost));
     if (frames) *frames = fr;
     return SD_OK;
 }
@@ -394,23 +378,33 @@ extern "C" int sd_set_planted(sd_ctx* c, const float* d_scores, const float* d_e
     return SD_OK;
 }
 
+// The whole path behind the entries that hold the padded f32 waveform on the device (sd_diarize_dev, sd_diarize_f32, the resample branch of
+// sd_diarize_wav): chunks, both networks, finalize -> turns; stage_ms[3] = the time since t0, the entry's own start
+static int diarize_wav_dev(sd_ctx* c, const float* d_wav, int64_t n, double t0, std::vector<sd_turn>& v)
+{
+    const int64_t chunks = sd_num_chunks(n, nullptr);
+    if (chunks <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)n);
+    WS(c, float, d_seg, "dz_seg", chunks * SD_FRAMES * 3);
+    WS(c, float, d_emb, "dz_emb", chunks * 3 * SD_EMB_DIM);
+    int rc;
+    if ((rc = shard_infer(c, d_wav, n, 0, chunks, d_seg, d_emb))) return rc;
+    if ((rc = finalize(c, d_seg, d_emb, chunks, n, v))) return rc;
+    c->stage_ms[3] = now_ms() - t0;
+    return SD_OK;
+}
+
 extern "C" int sd_diarize_dev(sd_ctx* c, const int16_t* d_pcm, int64_t n, sd_turn** turns, int64_t* n_turns)
 {
     ENTER(c);
     if (!d_pcm || !turns || !n_turns) SD_FAIL(c, SD_ERR_ARG, "sd_diarize_dev: bad argument");
+    if (n <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)n);      // this entry's only guard on n: nothing is uploaded from a count that is not one
     const double t0 = now_ms();
-    const int64_t chunks = sd_num_chunks(n, nullptr);
-    if (chunks <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)n);
     for (int i = 0; i < 4; ++i) c->stage_ms[i] = 0;
     float* d_wav = nullptr;
     int rc = pcm_to_wav(c, d_pcm, n, &d_wav);
     if (rc) return rc;
-    WS(c, float, d_seg, "dz_seg", chunks * SD_FRAMES * 3);
-    WS(c, float, d_emb, "dz_emb", chunks * 3 * SD_EMB_DIM);
-    if ((rc = shard_infer(c, d_wav, n, 0, chunks, d_seg, d_emb))) return rc;
     std::vector<sd_turn> v;
-    if ((rc = finalize(c, d_seg, d_emb, chunks, n, v))) return rc;
-    c->stage_ms[3] = now_ms() - t0;
+    if ((rc = diarize_wav_dev(c, d_wav, n, t0, v))) return rc;
     if (getenv("SD_TRACE_WS")) {
         fprintf(stderr, "[sdhip] job %.1f ms (segmentation %.1f, embedding %.1f, finalize %.1f); workspace allocations so far in this process: %zu hipMalloc, %.2f GB, %.1f ms (+ %.1f ms hipFree)\n",
                 c->stage_ms[3], c->stage_ms[0], c->stage_ms[1], c->stage_ms[2], g_ws_allocs.load(), (double)g_ws_alloc_bytes.load() / 1e9, (double)g_ws_alloc_us.load() * 1e-3, (double)g_ws_free_us.load() * 1e-3);
@@ -435,20 +429,13 @@ extern "C" int sd_diarize_f32(sd_ctx* c, const float* h_wav, int64_t n, sd_turn*
     ENTER(c);
     if (!h_wav || n <= 0 || !turns || !n_turns) SD_FAIL(c, SD_ERR_ARG, "sd_diarize_f32: bad argument");
     const double t0 = now_ms();
-    const int64_t chunks = sd_num_chunks(n, nullptr);
-    if (chunks <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)n);
     for (int i = 0; i < 4; ++i) c->stage_ms[i] = 0;
     WS(c, float, d_wav, "wav_f32", n + 512);
     HIPCHK(c, hipMemcpyAsync(d_wav, h_wav, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_wav + n, 0, 512 * sizeof(float), c->stream));
     c->wav_padded = true;
-    WS(c, float, d_seg, "dz_seg", chunks * SD_FRAMES * 3);
-    WS(c, float, d_emb, "dz_emb", chunks * 3 * SD_EMB_DIM);
-    int rc;
-    if ((rc = shard_infer(c, d_wav, n, 0, chunks, d_seg, d_emb))) return rc;
     std::vector<sd_turn> v;
-    if ((rc = finalize(c, d_seg, d_emb, chunks, n, v))) return rc;
-    c->stage_ms[3] = now_ms() - t0;
+    if (int rc = diarize_wav_dev(c, d_wav, n, t0, v)) return rc;
     return turns_out(c, v, turns, n_turns);
 }
 
@@ -486,8 +473,6 @@ extern "C" int sd_diarize_wav(sd_ctx* c, const char* path, int flags, sd_turn** 
     const double t0 = now_ms();
     const int64_t no = sd_resample_len(n, sr, 16000);
     if (no <= 0) SD_FAIL(c, SD_ERR_SHORT, "%s: %lld samples at %d Hz give no 16 kHz sample", path, (long long)n, sr);
-    const int64_t chunks = sd_num_chunks(no, nullptr);
-    if (chunks <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)no);
     for (int i = 0; i < 4; ++i) c->stage_ms[i] = 0;
     WS(c, float, d_in, "rs_in", n);
     WS(c, float, d_wav, "wav_f32", no + 512);
@@ -496,11 +481,7 @@ extern "C" int sd_diarize_wav(sd_ctx* c, const char* path, int flags, sd_turn** 
     int rc;
     if ((rc = resample_dev(c, d_in, n, sr, 16000, d_wav, no))) return rc;
     c->wav_padded = true;
-    WS(c, float, d_seg, "dz_seg", chunks * SD_FRAMES * 3);
-    WS(c, float, d_emb, "dz_emb", chunks * 3 * SD_EMB_DIM);
-    if ((rc = shard_infer(c, d_wav, no, 0, chunks, d_seg, d_emb))) return rc;
     std::vector<sd_turn> v;
-    if ((rc = finalize(c, d_seg, d_emb, chunks, no, v))) return rc;
-    c->stage_ms[3] = now_ms() - t0;
+    if ((rc = diarize_wav_dev(c, d_wav, no, t0, v))) return rc;
     return turns_out(c, v, turns, n_turns);
 }

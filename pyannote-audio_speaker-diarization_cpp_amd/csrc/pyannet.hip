@@ -16,8 +16,6 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#define GRID1(n) dim3((unsigned)(((n) + 255) / 256)), dim3(256)
-
 // ---------------------------------------------------------------- k_chunk_norm
 // xn[chunk][j] = (x - mean) / sqrt(var + 1e-5) * w + b  for j < L, 0 beyond
 __global__ __launch_bounds__(256) void k_chunk_norm(const float* __restrict__ wav, int64_t origin, int64_t first_chunk, int64_t hop, int L,

@@ -49,7 +49,7 @@ EXPORTS = [
     "sd_diarize_sharded", "sd_diarize_sharded_dev", "sd_write_rttm_ex", "sd_relabel_turns", "sd_relabel_turns_ex", "sd_last_confidence",
     "sd_debug_read_ws", "sd_test_pack_split_weights", "sd_resample", "sd_resample_len", "sd_diarize_wav", "sd_set_dump_dir",
     "sd_fcluster", "sd_segment_chunks", "sd_embed_signals",
-    "sd_linkage_ex", "sd_cluster_ex", "sd_set_option_f64", "sd_linkage_method_from_name", "sd_test_conv",
+    "sd_linkage_ex", "sd_cluster_ex", "sd_set_option_f64", "sd_linkage_method_from_name", "sd_test_conv", "sd_test_emb_batches",
 ]
 # SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
 LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
@@ -135,6 +135,8 @@ def lib():
     L.sd_test_pack_split_weights.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     L.sd_bench_conv.argtypes = [vp, i64] + [C.c_int] * 9 + [C.POINTER(dbl)]
     L.sd_test_conv.argtypes = [vp, C.POINTER(ConvCase)] + [vp] * 10 + [C.c_char_p, C.c_int]
+    L.sd_test_emb_batches.restype = i64
+    L.sd_test_emb_batches.argtypes = [vp, i64, i64, C.c_int, C.c_int, vp, i64]
     _lib = L
     return L
 
@@ -164,6 +166,16 @@ def fcluster(Z, cutoff):
     if rc:
         raise SdError(rc, "sd_fcluster: Z is not a dendrogram")
     return T
+
+
+def emb_batches(nvalid, batch_items=3072, skip_dead_rows=True, balance=False):
+    """sd_test_emb_batches: end index of every batch the embedding stage forms for items of `nvalid` valid frames.  Host-only, no context."""
+    nv = np.ascontiguousarray(nvalid, np.int32)
+    bounds = np.zeros(max(len(nv), 1), np.int64)
+    nb = lib().sd_test_emb_batches(_ptr(nv), len(nv), int(batch_items), int(bool(skip_dead_rows)), int(bool(balance)), _ptr(bounds), len(bounds))
+    if nb < 0:
+        raise SdError(-nb, "sd_test_emb_batches: bad argument")
+    return [int(b) for b in bounds[:nb]]
 
 
 def shard_plan(n_total, world, rank0_permille=-1):
