@@ -95,6 +95,27 @@ typedef struct sd_conv_case {
 int sd_test_conv(sd_ctx*, const sd_conv_case*, const int32_t* n_in, const int32_t* n_out, const float* w, const float* x, const float* x2,
                  const float* bias, const float* scale, const float* shift, const float* item_bias, float* y_out, char* kernel_name, int name_cap);
 
+/* ---- test hooks (tests/test_seg_kernels.py): ONE launch of one kernel of the segmentation network (csrc/pyannet.hip) on operands the caller chooses,
+ * through the launcher the product's seg_batch calls (grid, block and template choice are the product's).  Host pointers, f32.  A hook uploads,
+ * launches and downloads; it restates no kernel logic.  Guards: every input is followed by NaN (256 rows of the operand's row width behind an
+ * activation, 256 floats behind a parameter vector); every output buffer is filled with `canary` and has 256 slack rows behind it, and comes back
+ * WHOLE, slack included.  A case whose defined reads do not lie inside the operand given is refused with SD_ERR_ARG before anything is launched.
+ *
+ * sd_test_lstm_rec: k_lstm_rec (prec 0) / k_lstm_rec_x3 (prec 3: the split planes of W_hh are made by the loader's own function).  G [B][F][1024]:
+ * per direction 512 = gates i, f, g, o x 128 units (the input projection plus both biases); whh_f / whh_b [512][128].  h_out [(B * F + 256)][256].
+ * sd_test_pool_norm: k_pool_norm; stage 0 (C = 80 channels, rows of 96, |.| first), 1 or 2 (C = 60, rows of 64).  in [in_rows][C], in_rows =
+ * chunks * Lc; gw / gb [C].  cst != NULL (stage 0 only) selects the shared form: cst [chunks][2] = (a, c) of k_chunk_stats, wsum [80], chunk ck
+ * starts at row ck * chunk_rows, in_rows = (chunks - 1) * chunk_rows + Lc.  out [(chunks * (Lc / 3) + 256)][96 or 64].
+ * sd_test_chunk_norm: k_chunk_norm (stats_only = 0): chunk ck = samples [(first_chunk + ck) * hop - origin, + L) of wav [n_wav];
+ * out [chunks * 80000 + 1024].  stats_only = 1: k_chunk_stats (hop must be 8000); out [(chunks + 256)][2] = (a, c).
+ * sd_test_classifier: k_classifier; y [chunks * F][128], W [3][128], bias [3], F <= 293; seg_out [(chunks * 293 + 256)][3]. */
+int sd_test_lstm_rec(sd_ctx*, const float* G, const float* whh_f, const float* whh_b, int64_t B, int F, int prec, float canary, float* h_out);
+int sd_test_pool_norm(sd_ctx*, const float* in, int64_t in_rows, int64_t chunks, int Lc, int stage, const float* gw, const float* gb,
+                      const float* cst, const float* wsum, int chunk_rows, float canary, float* out);
+int sd_test_chunk_norm(sd_ctx*, const float* wav, int64_t n_wav, int64_t origin, int64_t first_chunk, int64_t hop, int L, int64_t chunks,
+                       float w, float b, int stats_only, float canary, float* out);
+int sd_test_classifier(sd_ctx*, const float* y, const float* W, const float* bias, int64_t chunks, int F, float canary, float* seg_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -315,6 +315,7 @@ int load_pack(const char* path, Pack& out, std::string& err);
 int load_model_any(const char* path, int kind, Pack& out, std::string& err);   // onnx_reader.cpp: .sdw pack or .onnx (kind 0 seg, 1 emb)
 int build_ecapa_weights(sd_ctx* c, const Pack& p);
 int build_seg_weights(sd_ctx* c, const Pack& p);
+float lstm_whh_split(const float* whh /*[512][128]*/, _Float16* planes /*[hi | lo][512][128]*/);   // option seg_precision = 3: fp16 planes of W_hh * 2^e; returns 2^-e
 void* weight_alloc(sd_ctx* c, size_t bytes);                      // weights.cpp: bump allocator over 64 MB device blocks (freed by sd_destroy)
 int ensure_ecapa_mode_weights(sd_ctx* c, int ecapa_precision);   // weights_gpu.hip: builds W16 (modes 1, 2) / W16x (mode 3) on first use
 // the two forms of ONE layer, into device memory the caller provides (conv_w16_bytes / conv_w16x_bytes; d_max: one unsigned of scratch); asynchronous on c->stream
@@ -356,6 +357,18 @@ int run_embed(sd_ctx* c, const float* d_wav, int64_t n, const float* d_masks, in
 // ---- pyannet.hip
 int run_segment(sd_ctx* c, const float* d_wav, int64_t n, int64_t chunk_lo, int64_t chunk_hi, float* d_seg);
 int run_segment_rows(sd_ctx* c, const float* d_rows, int64_t rows, int T, float* d_seg, int* frames);   // SegmentModel::infer as declared (sd.cpp:1352)
+// the launches of pyannet.hip's kernels, asynchronous on c->stream: grid, block and k_pool_norm's template choice are computed here; seg_batch and the test
+// hooks of seg_test.hip call the same ones.  chunk_norm: xn [chunks][80000]; chunk_stats: st [chunks] (a, c), hop = 8000;
+// pool_norm: stage 0 (C 80, pad 96, abs; cst != null: the shared form, chunk ck starts at row ck * chunk_rows of `in`), 1 or 2 (C 60, pad 64), Lp = Lc / 3;
+// lstm_rec: G [B][F][1024] -> H [B][F][256], whx_f and whx_b non-null: k_lstm_rec_x3 on the split planes of lstm_whh_split, else k_lstm_rec;
+// classifier: y [chunks * F][128] -> seg [chunks][293][3]
+int launch_chunk_norm(sd_ctx* c, const float* d_wav, int64_t origin, int64_t first_chunk, int64_t hop, int L, int64_t chunks, float w, float b, float* xn);
+int launch_chunk_stats(sd_ctx* c, const float* d_wav, int64_t origin, int64_t first_chunk, int L, int64_t chunks, float w, float b, float2* st);
+int launch_pool_norm(sd_ctx* c, int stage, const float* in, int64_t chunks, int Lc, const float* gw, const float* gb, float* out,
+                     const float2* cst, const float* wsum, int chunk_rows);
+int launch_lstm_rec(sd_ctx* c, const float* G, const float* whh_f, const float* whh_b, const void* whx_f, const void* whx_b, float inv_f, float inv_b,
+                    float* H, int64_t B, int F);
+int launch_classifier(sd_ctx* c, const float* y, const float* W, const float* bias, float* seg, int64_t chunks, int F);
 // ---- postseg.hip
 int run_postseg(sd_ctx* c, const float* d_seg, int64_t chunks, uint8_t* d_bin, float* d_masks, int* d_nact);
 int run_count(sd_ctx* c, const uint8_t* d_bin, int64_t chunks, int32_t* d_count, int64_t n_count, double* d_avg = nullptr);

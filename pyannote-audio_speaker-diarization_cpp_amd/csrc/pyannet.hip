@@ -378,6 +378,60 @@ __global__ void k_dense_rowtab(int2* __restrict__ rowtab, int64_t M)
     if (g < M) rowtab[g] = make_int2((int)((g >> 9) << 9), (int)(g & 511) | (511 << 10) | ((int)(g >> 9) << 20));
 }
 
+// ---------------------------------------------------------------- the launches of this file's kernels
+// Grid, block and -- for k_pool_norm -- the template choice of every launch live here and nowhere else: seg_batch below and the test hooks of
+// seg_test.hip (sd_test_lstm_rec, sd_test_pool_norm, sd_test_chunk_norm, sd_test_classifier) call the same launchers.
+int launch_chunk_norm(sd_ctx* c, const float* d_wav, int64_t origin, int64_t first_chunk, int64_t hop, int L, int64_t chunks, float w, float b, float* xn)
+{
+    hipLaunchKernelGGL(k_chunk_norm, dim3((unsigned)chunks), dim3(256), 0, c->stream, d_wav, origin, first_chunk, hop, L, w, b, xn);
+    KCHECK(c);
+    return SD_OK;
+}
+
+int launch_chunk_stats(sd_ctx* c, const float* d_wav, int64_t origin, int64_t first_chunk, int L, int64_t chunks, float w, float b, float2* st)
+{
+    hipLaunchKernelGGL(k_chunk_stats, dim3((unsigned)chunks), dim3(256), 0, c->stream, d_wav, origin, first_chunk, L, w, b, st);
+    KCHECK(c);
+    return SD_OK;
+}
+
+int launch_pool_norm(sd_ctx* c, int stage, const float* in, int64_t chunks, int Lc, const float* gw, const float* gb, float* out,
+                     const float2* cst, const float* wsum, int chunk_rows)
+{
+    const int Lp = Lc / 3;
+    const dim3 grid((unsigned)chunks), block(PN_T);
+    if (stage == 0 && cst)
+        hipLaunchKernelGGL((k_pool_norm<80, 96, true, true>), grid, block, 0, c->stream, in, Lc, Lp, gw, gb, out, cst, wsum, chunk_rows);
+    else if (stage == 0)
+        hipLaunchKernelGGL((k_pool_norm<80, 96, true, false>), grid, block, 0, c->stream, in, Lc, Lp, gw, gb, out, nullptr, nullptr, 0);
+    else if ((stage == 1 || stage == 2) && !cst)
+        hipLaunchKernelGGL((k_pool_norm<60, 64, false, false>), grid, block, 0, c->stream, in, Lc, Lp, gw, gb, out, nullptr, nullptr, 0);
+    else
+        SD_FAIL(c, SD_ERR_ARG, "k_pool_norm: stage %d%s", stage, cst ? " (shared form)" : "");
+    KCHECK(c);
+    return SD_OK;
+}
+
+int launch_lstm_rec(sd_ctx* c, const float* G, const float* whh_f, const float* whh_b, const void* whx_f, const void* whx_b, float inv_f, float inv_b,
+                    float* H, int64_t B, int F)
+{
+    ProfScope ps(c, "lstm_rec", 2.0 * B * F * 2 * 512 * 128, 0);
+    const dim3 grid((unsigned)((B + 31) / 32), 2), block(512);
+    if (whx_f && whx_b)
+        hipLaunchKernelGGL(k_lstm_rec_x3, grid, block, 0, c->stream, G, (const _Float16*)whx_f, (const _Float16*)whx_b, inv_f, inv_b, H, (int)B, F);
+    else
+        hipLaunchKernelGGL(k_lstm_rec, grid, block, 0, c->stream, G, whh_f, whh_b, H, (int)B, F);
+    KCHECK(c);
+    return SD_OK;
+}
+
+int launch_classifier(sd_ctx* c, const float* y, const float* W, const float* bias, float* seg, int64_t chunks, int F)
+{
+    hipLaunchKernelGGL(k_classifier, GRID1(chunks * SD_FRAMES), 0, c->stream, y, W, bias, seg, chunks, F);
+    KCHECK(c);
+    return SD_OK;
+}
+
 static ConvArgs gemm_args(const ConvLayer& L, const float* X, int x_ld, float* Y, int y_ld, int64_t M)
 {
     ConvArgs a;
@@ -425,21 +479,18 @@ static int seg_batch(sd_ctx* c, const float* d_wav, int64_t n, int64_t first_chu
         const int64_t MY = (int64_t)hop_rows * (CB - 1) + L0;
         WS(c, float2, cst, "sg_cst", CB);
         WS(c, float, c0s, "sg_c0s", MY * 80);
-        hipLaunchKernelGGL(k_chunk_stats, dim3((unsigned)CB), dim3(256), 0, st, d_wav, c->wav_origin, first_chunk, L, S.wn_w, S.wn_b, cst);
-        KCHECK(c);
+        if ((rc = launch_chunk_stats(c, d_wav, c->wav_origin, first_chunk, L, CB, S.wn_w, S.wn_b, cst))) return rc;
         ConvArgs a; memset(&a, 0, sizeof(a));
         a.X = d_wav + (first_chunk * (int64_t)SD_HOP - c->wav_origin); a.x_ld = 10; a.W = S.conv0.W; a.Y = c0s; a.y_ld = 80;
         a.M = (int)MY; a.TpIn = a.TpOut = a.Tin = a.T = (int)MY;
         a.Cin = 256; a.cin_real = 251; a.Cout = 80; a.KT = 1; a.dil = 1; a.pad_mode = 1;
         if ((rc = launch_conv_narrow(c, a, "sinc0")) == 1) rc = launch_conv_gemm(c, a, "sinc0");
         if (rc) return rc;
-        hipLaunchKernelGGL((k_pool_norm<80, 96, true, true>), dim3((unsigned)CB), dim3(PN_T), 0, st, c0s, L0, P0, S.in_w[0], S.in_b[0], p0, cst, S.conv0_wsum, hop_rows);
-        KCHECK(c);
+        if ((rc = launch_pool_norm(c, 0, c0s, CB, L0, S.in_w[0], S.in_b[0], p0, cst, S.conv0_wsum, hop_rows))) return rc;
     } else {
         WS(c, float, xn, "sg_xn", CB * SD_CHUNK + 512);
         WS(c, float, c0, "sg_c0", CB * L0 * 80);
-        hipLaunchKernelGGL(k_chunk_norm, dim3((unsigned)CB), dim3(256), 0, st, d_wav, c->wav_origin, first_chunk, hop, L, S.wn_w, S.wn_b, xn);
-        KCHECK(c);
+        if ((rc = launch_chunk_norm(c, d_wav, c->wav_origin, first_chunk, hop, L, CB, S.wn_w, S.wn_b, xn))) return rc;
         {   // conv0: rows = output positions, row r reads xn[10 r .. 10 r + 256)
             ConvArgs a; memset(&a, 0, sizeof(a));
             a.X = xn; a.x_ld = 10; a.W = S.conv0.W; a.Y = c0; a.y_ld = 80;
@@ -448,8 +499,7 @@ static int seg_batch(sd_ctx* c, const float* d_wav, int64_t n, int64_t first_chu
             if ((rc = launch_conv_narrow(c, a, "sinc0")) == 1) rc = launch_conv_gemm(c, a, "sinc0");
             if (rc) return rc;
         }
-        hipLaunchKernelGGL((k_pool_norm<80, 96, true, false>), dim3((unsigned)CB), dim3(PN_T), 0, st, c0, L0, P0, S.in_w[0], S.in_b[0], p0, nullptr, nullptr, 0);
-        KCHECK(c);
+        if ((rc = launch_pool_norm(c, 0, c0, CB, L0, S.in_w[0], S.in_b[0], p0, nullptr, nullptr, 0))) return rc;
     }
     {
         ConvArgs a; memset(&a, 0, sizeof(a));
@@ -459,8 +509,7 @@ static int seg_batch(sd_ctx* c, const float* d_wav, int64_t n, int64_t first_chu
         if ((rc = launch_conv_narrow(c, a, "sinc1")) == 1) rc = launch_conv_gemm(c, a, "sinc1");
         if (rc) return rc;
     }
-    hipLaunchKernelGGL((k_pool_norm<60, 64, false, false>), dim3((unsigned)CB), dim3(PN_T), 0, st, c1, L1, P1, S.in_w[1], S.in_b[1], p1, nullptr, nullptr, 0);
-    KCHECK(c);
+    if ((rc = launch_pool_norm(c, 1, c1, CB, L1, S.in_w[1], S.in_b[1], p1, nullptr, nullptr, 0))) return rc;
     {
         ConvArgs a; memset(&a, 0, sizeof(a));
         a.X = p1; a.x_ld = 64; a.W = S.conv2.W; a.bias = S.conv2.bias; a.Y = c2; a.y_ld = 60;
@@ -469,8 +518,7 @@ static int seg_batch(sd_ctx* c, const float* d_wav, int64_t n, int64_t first_chu
         if ((rc = launch_conv_narrow(c, a, "sinc2")) == 1) rc = launch_conv_gemm(c, a, "sinc2");
         if (rc) return rc;
     }
-    hipLaunchKernelGGL((k_pool_norm<60, 64, false, false>), dim3((unsigned)CB), dim3(PN_T), 0, st, c2, L2, P2, S.in_w[2], S.in_b[2], p2, nullptr, nullptr, 0);
-    KCHECK(c);
+    if ((rc = launch_pool_norm(c, 2, c2, CB, L2, S.in_w[2], S.in_b[2], p2, nullptr, nullptr, 0))) return rc;
     // if P2 > 293 (cannot happen for L <= 80000) only the first F frames would be used
     const float* lin = p2; int lin_ld = 64; int lin_rows_per_chunk = P2;
     float* hout = Ha;
@@ -494,22 +542,16 @@ static int seg_batch(sd_ctx* c, const float* d_wav, int64_t n, int64_t first_chu
             if ((rc = launch_conv_gemm(c, a, "lstm_ih"))) return rc;
         }
         {
-            ProfScope ps(c, "lstm_rec", 2.0 * CB * F * 2 * 512 * 128, 0);
-            if (seg_prec(c) == 3 && S.lstm_hh_x[l][0] && S.lstm_hh_x[l][1])
-                hipLaunchKernelGGL(k_lstm_rec_x3, dim3((unsigned)((CB + 31) / 32), 2), dim3(512), 0, st, G, (const _Float16*)S.lstm_hh_x[l][0], (const _Float16*)S.lstm_hh_x[l][1],
-                                   S.lstm_hh_inv[l][0], S.lstm_hh_inv[l][1], hout, (int)CB, F);
-            else
-                hipLaunchKernelGGL(k_lstm_rec, dim3((unsigned)((CB + 31) / 32), 2), dim3(512), 0, st, G, S.lstm_hh[l][0], S.lstm_hh[l][1], hout, (int)CB, F);
-            KCHECK(c);
+            const bool x3 = seg_prec(c) == 3 && S.lstm_hh_x[l][0] && S.lstm_hh_x[l][1];
+            if ((rc = launch_lstm_rec(c, G, S.lstm_hh[l][0], S.lstm_hh[l][1], x3 ? S.lstm_hh_x[l][0] : nullptr, x3 ? S.lstm_hh_x[l][1] : nullptr,
+                                      S.lstm_hh_inv[l][0], S.lstm_hh_inv[l][1], hout, CB, F))) return rc;
         }
         lin = hout; lin_ld = 256; lin_rows_per_chunk = F;
         hout = (hout == Ha) ? Hb : Ha;
     }
     { ConvArgs a = gemm_args(S.lin0, lin, 256, y0, 128, CB * F); a.act1 = 2; if ((rc = launch_conv_gemm(c, a, "lin0"))) return rc; }
     { ConvArgs a = gemm_args(S.lin1, y0, 128, y1, 128, CB * F); a.act1 = 2; if ((rc = launch_conv_gemm(c, a, "lin1"))) return rc; }
-    hipLaunchKernelGGL(k_classifier, GRID1(CB * SD_FRAMES), 0, st, y1, S.cls_w, S.cls_b, d_seg, CB, F);
-    KCHECK(c);
-    return SD_OK;
+    return launch_classifier(c, y1, S.cls_w, S.cls_b, d_seg, CB, F);
 }
 
 // chunks [chunk_lo, chunk_hi) of the n-sample waveform -> d_seg [hi-lo][293][3]

@@ -238,6 +238,24 @@ int build_ecapa_weights(sd_ctx* c, const Pack& p)
     return SD_OK;
 }
 
+// option seg_precision = 3: hi and lo fp16 planes of W_hh * 2^e, e chosen so that the largest weight lands in [2^13, 2^14) (k_lstm_rec_x3).
+// whh [512][128] -> planes [hi | lo][512][128]; returns 2^-e
+float lstm_whh_split(const float* whh, _Float16* planes)
+{
+    const size_t n = (size_t)512 * 128;
+    float wmax = 0.0f;
+    for (size_t q = 0; q < n; ++q) if (std::isfinite(whh[q])) wmax = fmaxf(wmax, fabsf(whh[q]));
+    int e = 0;
+    if (wmax > 0.0f) { (void)frexpf(wmax, &e); e = 14 - e; }
+    const float sc = ldexpf(1.0f, e);
+    for (size_t q = 0; q < n; ++q) {
+        const float v = whh[q] * sc;
+        const _Float16 hi = (_Float16)v;
+        planes[q] = hi; planes[n + q] = (_Float16)(v - (float)hi);
+    }
+    return ldexpf(1.0f, -e);
+}
+
 int build_seg_weights(sd_ctx* c, const Pack& p)
 {
     SegWeights& S = c->sw;
@@ -282,20 +300,10 @@ int build_seg_weights(sd_ctx* c, const Pack& p)
             S.lstm_hh[l][d] = upload(c, whh->data);
             if (!S.lstm_hh[l][d]) return SD_ERR_HIP;
             if (whh->data.size() == (size_t)512 * 128) {        // option seg_precision = 3: hi and lo planes of W_hh * 2^e (k_lstm_rec_x3)
-                float wmax = 0.0f;
-                for (float v : whh->data) if (std::isfinite(v)) wmax = fmaxf(wmax, fabsf(v));
-                int e = 0;
-                if (wmax > 0.0f) { (void)frexpf(wmax, &e); e = 14 - e; }
-                const float sc = ldexpf(1.0f, e);
                 std::vector<_Float16> hx((size_t)2 * 512 * 128);
-                for (size_t q = 0; q < (size_t)512 * 128; ++q) {
-                    const float v = whh->data[q] * sc;
-                    const _Float16 hi = (_Float16)v;
-                    hx[q] = hi; hx[(size_t)512 * 128 + q] = (_Float16)(v - (float)hi);
-                }
+                S.lstm_hh_inv[l][d] = lstm_whh_split(whh->data.data(), hx.data());
                 S.lstm_hh_x[l][d] = upload(c, hx);
                 if (!S.lstm_hh_x[l][d]) return SD_ERR_HIP;
-                S.lstm_hh_inv[l][d] = ldexpf(1.0f, -e);
             }
         }
         const int nin = (int)wih[0]->dims[1];

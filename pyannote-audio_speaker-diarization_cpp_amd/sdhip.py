@@ -28,6 +28,7 @@ class ConvCase(C.Structure):
 
 
 CONV_SLACK_ROWS = 256      # guard rows behind the buffers of Diarizer.conv_case
+SEG_SLACK_ROWS = 256       # ... and behind those of Diarizer.lstm_rec_case / pool_norm_case / chunk_norm_case / classifier_case
 
 
 class SdError(RuntimeError):
@@ -50,6 +51,7 @@ EXPORTS = [
     "sd_debug_read_ws", "sd_test_pack_split_weights", "sd_resample", "sd_resample_len", "sd_diarize_wav", "sd_set_dump_dir",
     "sd_fcluster", "sd_segment_chunks", "sd_embed_signals",
     "sd_linkage_ex", "sd_cluster_ex", "sd_set_option_f64", "sd_linkage_method_from_name", "sd_test_conv", "sd_test_emb_batches",
+    "sd_test_lstm_rec", "sd_test_pool_norm", "sd_test_chunk_norm", "sd_test_classifier",
 ]
 # SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
 LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
@@ -135,6 +137,10 @@ def lib():
     L.sd_test_pack_split_weights.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     L.sd_bench_conv.argtypes = [vp, i64] + [C.c_int] * 9 + [C.POINTER(dbl)]
     L.sd_test_conv.argtypes = [vp, C.POINTER(ConvCase)] + [vp] * 10 + [C.c_char_p, C.c_int]
+    L.sd_test_lstm_rec.argtypes = [vp, vp, vp, vp, i64, C.c_int, C.c_int, C.c_float, vp]
+    L.sd_test_pool_norm.argtypes = [vp, vp, i64, i64, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, vp]
+    L.sd_test_chunk_norm.argtypes = [vp, vp, i64, i64, i64, i64, C.c_int, i64, C.c_float, C.c_float, C.c_int, C.c_float, vp]
+    L.sd_test_classifier.argtypes = [vp, vp, vp, vp, i64, C.c_int, C.c_float, vp]
     L.sd_test_emb_batches.restype = i64
     L.sd_test_emb_batches.argtypes = [vp, i64, i64, C.c_int, C.c_int, vp, i64]
     _lib = L
@@ -605,6 +611,48 @@ class Diarizer:
             e.kernel = name.value.decode()
             raise e
         return y, name.value.decode()
+
+    # ---- one kernel of the segmentation network alone (sdhip_test.h); each returns the WHOLE output buffer, SEG_SLACK_ROWS guard rows included
+    def lstm_rec_case(self, G, whh_f, whh_b, prec=0, canary=-7776.0):
+        """sd_test_lstm_rec: G [B][F][1024], whh_f / whh_b [512][128] -> H [B * F + SEG_SLACK_ROWS][256]; prec 0 = k_lstm_rec, 3 = k_lstm_rec_x3"""
+        G = np.ascontiguousarray(G, np.float32)
+        B, F, w = G.shape
+        whh_f, whh_b = np.ascontiguousarray(whh_f, np.float32), np.ascontiguousarray(whh_b, np.float32)
+        assert w == 1024 and whh_f.shape == (512, 128) and whh_b.shape == (512, 128)
+        H = np.zeros((B * F + SEG_SLACK_ROWS, 256), np.float32)
+        self._chk(lib().sd_test_lstm_rec(self._h, _ptr(G), _ptr(whh_f), _ptr(whh_b), B, F, int(prec), canary, _ptr(H)))
+        return H
+
+    def pool_norm_case(self, x, chunks, Lc, stage, gw, gb, cst=None, wsum=None, chunk_rows=0, canary=-7776.0):
+        """sd_test_pool_norm: x [in_rows][C] (C = 80 at stage 0, 60 at stages 1 and 2) -> out [chunks * (Lc // 3) + SEG_SLACK_ROWS][96 or 64].
+        cst [chunks][2] + wsum [80] + chunk_rows: the shared form of stage 0 (chunk ck starts at row ck * chunk_rows)"""
+        C_, cpad = (80, 96) if stage == 0 else (60, 64)
+        x = np.ascontiguousarray(x, np.float32)
+        gw, gb = np.ascontiguousarray(gw, np.float32), np.ascontiguousarray(gb, np.float32)
+        assert x.ndim == 2 and x.shape[1] == C_ and gw.shape == (C_,) and gb.shape == (C_,)
+        if cst is not None:
+            cst, wsum = np.ascontiguousarray(cst, np.float32), np.ascontiguousarray(wsum, np.float32)
+            assert cst.shape == (chunks, 2) and wsum.shape == (80,)
+        out = np.zeros((chunks * (Lc // 3) + SEG_SLACK_ROWS, cpad), np.float32)
+        self._chk(lib().sd_test_pool_norm(self._h, _ptr(x), x.shape[0], chunks, Lc, stage, _ptr(gw), _ptr(gb), _ptr(cst) if cst is not None else None,
+                                          _ptr(wsum) if cst is not None else None, int(chunk_rows), canary, _ptr(out)))
+        return out
+
+    def chunk_norm_case(self, wav, origin, first_chunk, hop, L, chunks, w, b, stats_only=False, canary=-7776.0):
+        """sd_test_chunk_norm: chunk ck = wav[(first_chunk + ck) * hop - origin :][:L] -> xn [chunks * 80000 + 4 * SEG_SLACK_ROWS] (k_chunk_norm), or
+        with stats_only (a, c) [chunks + SEG_SLACK_ROWS][2] (k_chunk_stats, hop = 8000)"""
+        wav = np.ascontiguousarray(wav, np.float32)
+        out = np.zeros((chunks + SEG_SLACK_ROWS, 2) if stats_only else (chunks * CHUNK + 4 * SEG_SLACK_ROWS,), np.float32)
+        self._chk(lib().sd_test_chunk_norm(self._h, _ptr(wav), len(wav), origin, first_chunk, hop, L, chunks, w, b, int(bool(stats_only)), canary, _ptr(out)))
+        return out
+
+    def classifier_case(self, y, W, b, chunks, F, canary=-7776.0):
+        """sd_test_classifier: y [chunks * F][128], W [3][128], b [3] -> seg [chunks * 293 + SEG_SLACK_ROWS][3]"""
+        y, W, b = np.ascontiguousarray(y, np.float32), np.ascontiguousarray(W, np.float32), np.ascontiguousarray(b, np.float32)
+        assert y.shape == (chunks * F, 128) and W.shape == (3, 128) and b.shape == (3,)
+        seg = np.zeros((chunks * FRAMES + SEG_SLACK_ROWS, 3), np.float32)
+        self._chk(lib().sd_test_classifier(self._h, _ptr(y), _ptr(W), _ptr(b), chunks, F, canary, _ptr(seg)))
+        return seg
 
     def read_ws(self, name, dtype, count, offset=0):
         """test hook: `count` elements of the named device workspace"""
