@@ -235,11 +235,36 @@ int sd_relabel_turns_ex(sd_turn* turns, int64_t n_turns, int mode);
  * items assigned to the turn's cluster whose chunk overlaps the turn; NaN when no such item has an embedding */
 int sd_last_confidence(const sd_ctx*, double* conf, int64_t cap, int64_t* n);
 
+/* ---- speech / overlapped-speech regions from the segmentation stage alone: what pyannote's VoiceActivityDetection and
+ * OverlappedSpeechDetection pipelines compute, with the reference's own two building blocks -- PipelineHelper::aggregate (sd.cpp:1167-1311,
+ * skip_average = false, missing = 0.0) over the per-chunk largest (SD_ACTIVITY_SPEECH) or second largest (SD_ACTIVITY_OVERLAP) of the three
+ * scores, then to_annotation (sd.cpp:2852-2935) on that one-column timeline with window start 0.0.  A chunk frame with a NaN score is masked
+ * out.  Results are bit-identical to those two functions, Track::support (collar = min_duration_off, when > 0) and Track::removeShort
+ * (min_duration_on, when > 0; it never removes the first region, sd.cpp:943-953) included.  Options, through sd_set_option_f64:
+ * "activity_onset", "activity_offset" (defaults 0.5, in [0, 1]; comparisons are strict, offset > onset is legal: a score strictly between
+ * the two toggles the state), "activity_min_duration_on", "activity_min_duration_off" (defaults 0.0, >= 0); through sd_set_option:
+ * "activity_hamming" (1 = every contribution and every count weighted by np.hamming(293): the branch sd.cpp:1211-1215 names and leaves
+ * unimplemented; default 0).  Nothing of the embedding, clustering or reconstruction stages runs. */
+enum { SD_ACTIVITY_SPEECH = 0, SD_ACTIVITY_OVERLAP = 1 };
+/* the stage alone, sd.cpp:1167-1311: seg [chunks][293][3] f32 -> the aggregated timeline, all *n_frames frames of it (f64); h_scores == NULL: only the count */
+int sd_activity_scores(sd_ctx*, const float* h_seg, int64_t chunks, int kind, double* h_scores, int64_t cap, int64_t* n_frames);
+/* the stage alone, sd.cpp:2852-2935: a timeline -> malloc'd regions (sd_free_turns) by the context's four options; label 0 */
+int sd_activity_regions(sd_ctx*, const double* h_scores, int64_t n_frames, sd_turn** turns, int64_t* n_turns);
+/* whole path, sd.cpp:1167-1311 / 2852-2935 behind the head of speakerDiarization(): samples as for sd_diarize / _dev / _f32 / _wav (same SD_WAV_* flags,
+ * same refusals, SD_ERR_SHORT where they return it) -> regions with label = kind.  The timeline keeps the frames up to the one closest to the end of
+ * the audio: those that lie wholly in the zero padding of the last chunk are dropped. */
+int sd_activity(sd_ctx*, const int16_t* h_pcm, int64_t n, int kind, sd_turn** turns, int64_t* n_turns);
+int sd_activity_dev(sd_ctx*, const int16_t* d_pcm, int64_t n, int kind, sd_turn** turns, int64_t* n_turns);
+int sd_activity_f32(sd_ctx*, const float* h_wav, int64_t n, int kind, sd_turn** turns, int64_t* n_turns);
+int sd_activity_wav(sd_ctx*, const char* path, int flags, int kind, sd_turn** turns, int64_t* n_turns);
+/* the timeline (sd.cpp:1167-1311, cropped as above) of the last whole-path sd_activity* call of this ctx */
+int sd_last_activity_scores(const sd_ctx*, double* scores, int64_t cap, int64_t* n);
+
 /* ---- a18: the reference's output line (sd.cpp:3439) */
 int sd_format_turn(const sd_turn* t, char* buf, int cap);
 
 /* ---- the reference's four stage timers (sd.cpp:53-60; labels of sd.cpp:3028, 3110, 3231, 3434): wall ms of the last
- * sd_diarize* call, [0]=segmentation [1]=embedding [2]=clustering [3]=total */
+ * sd_diarize* call, [0]=segmentation [1]=embedding [2]=clustering [3]=total; after a whole-path sd_activity* call [0] and [3], the others 0 */
 int sd_stage_ms(const sd_ctx*, double* ms4);
 /* ---- options.  Product keys (the knobs clustering/Clustering.py and the multi-GPU path expose; the reference hard-codes them):
  * "num_clusters", "min_clusters", "max_clusters" (-1 = unset; Clustering.py:21-43), "constrained_assignment" (1 = constrained_argmax of
@@ -260,10 +285,12 @@ int sd_stage_ms(const sd_ctx*, double* ms4);
  *   else 0; 0 = f32 MFMA; 3 = the same operand split for PyanNet's LSTM: input projections of layers 1-3 and the recurrence; scores within 2e-6 of
  *   mode 0, identical turns on the planted hour and on the reference's 1-min wav),
  * "rank0_permille" (sd_diarize_sharded: share of the chunks rank 0 infers itself, -1 = equal),
- * "comm_timeout_ms" (deadline of the exchange step of a sharded job, default 600 000).
+ * "comm_timeout_ms" (deadline of the exchange step of a sharded job, default 600 000),
+ * "activity_hamming" (0 / 1, see sd_activity* above).
  * Test and tuning keys are listed in sdhip_test.h.  An unknown key returns SD_ERR_ARG. */
 int sd_set_option(sd_ctx*, const char* key, int64_t value);
-/* the real-valued keys: "clustering_threshold" (Clustering.py:251-276 / 317-333; outside [0, 2] or NaN: SD_ERR_ARG).  An unknown key returns SD_ERR_ARG. */
+/* the real-valued keys: "clustering_threshold" (Clustering.py:251-276 / 317-333; outside [0, 2] or NaN: SD_ERR_ARG) and the four "activity_*" keys of
+ * sd_activity* above (NaN or out of range: SD_ERR_ARG).  An unknown key returns SD_ERR_ARG. */
 int sd_set_option_f64(sd_ctx*, const char* key, double value);
 
 #ifdef __cplusplus

@@ -147,6 +147,7 @@ extern "C" int sd_set_option(sd_ctx* c, const char* key, int64_t v)
     else if (k == "num_clusters") c->num_clusters = (int)v;
     else if (k == "min_clusters") c->min_clusters = (int)v;
     else if (k == "max_clusters") c->max_clusters = (int)v;
+    else if (k == "activity_hamming") { if (v != 0 && v != 1) SD_FAIL(c, SD_ERR_ARG, "activity_hamming must be 0 or 1"); c->activity_hamming = v != 0; }
     else if (k == "profile") { c->profile = v != 0; c->profile_detail = v >= 2; }
     else SD_FAIL(c, SD_ERR_ARG, "unknown option %s", key);
     return SD_OK;
@@ -157,6 +158,10 @@ extern "C" int sd_set_option_f64(sd_ctx* c, const char* key, double v)
     if (!c || !key) return SD_ERR_ARG;
     std::string k(key);
     if (k == "clustering_threshold") { if (!(v >= 0.0 && v <= 2.0)) SD_FAIL(c, SD_ERR_ARG, "clustering_threshold must lie in [0, 2]"); c->clustering_threshold = v; }
+    else if (k == "activity_onset") { if (!(v >= 0.0 && v <= 1.0)) SD_FAIL(c, SD_ERR_ARG, "activity_onset must lie in [0, 1]"); c->activity_onset = v; }
+    else if (k == "activity_offset") { if (!(v >= 0.0 && v <= 1.0)) SD_FAIL(c, SD_ERR_ARG, "activity_offset must lie in [0, 1]"); c->activity_offset = v; }
+    else if (k == "activity_min_duration_on") { if (!(v >= 0.0)) SD_FAIL(c, SD_ERR_ARG, "activity_min_duration_on must be >= 0"); c->activity_min_on = v; }
+    else if (k == "activity_min_duration_off") { if (!(v >= 0.0)) SD_FAIL(c, SD_ERR_ARG, "activity_min_duration_off must be >= 0"); c->activity_min_off = v; }
     else SD_FAIL(c, SD_ERR_ARG, "unknown real-valued option %s", key);
     return SD_OK;
 }
@@ -449,6 +454,14 @@ extern "C" int sd_last_confidence(const sd_ctx* c, double* conf, int64_t cap, in
     if (!c) return SD_ERR_ARG;
     if (n) *n = (int64_t)c->last_conf.size();
     if (conf) for (int64_t i = 0; i < cap && i < (int64_t)c->last_conf.size(); ++i) conf[i] = c->last_conf[(size_t)i];
+    return SD_OK;
+}
+
+extern "C" int sd_last_activity_scores(const sd_ctx* c, double* scores, int64_t cap, int64_t* n)
+{
+    if (!c) return SD_ERR_ARG;
+    if (n) *n = (int64_t)c->last_activity.size();
+    if (scores) for (int64_t i = 0; i < cap && i < (int64_t)c->last_activity.size(); ++i) scores[i] = c->last_activity[(size_t)i];
     return SD_OK;
 }
 

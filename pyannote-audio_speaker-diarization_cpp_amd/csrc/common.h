@@ -199,6 +199,10 @@ struct sd_ctx {
     double clustering_threshold = (double)0.7153814381597874f;      // the reference's float constant, widened
     int min_cluster_size = 15;
     std::vector<double> last_conf;               // per-turn confidence of the last finalize (sd_last_confidence)
+    // the activity stage (activity.hip): pyannote's Binarize parameters for the speech / overlap timeline, and the timeline of the last whole-path call
+    double activity_onset = 0.5, activity_offset = 0.5, activity_min_on = 0.0, activity_min_off = 0.0;
+    bool activity_hamming = false;              // aggregate()'s Hamming-weighted branch (sd.cpp:1211-1215)
+    std::vector<double> last_activity;           // cropped scores of the last sd_activity* call (sd_last_activity_scores)
     int64_t fe_bill_samples = -1, fe_bill_frames = 0;   // profiling: selected samples / stored frames of the next k_stft_fbank launch (-1 = unknown)
     int64_t wav_origin = 0;                     // recording position of d_wav[0] for the current call (sharded entry points hold a slice)
     void* comm = nullptr;                       // ncclComm_t (comm.cpp), null = single GPU
@@ -384,6 +388,11 @@ int run_cluster_labels(sd_ctx* c, const double* d_X, int64_t N, int d, double cu
 int run_clustering(sd_ctx* c, const double* d_emb /*[M][d] f64*/, int64_t M, int d, std::vector<int>& hard, int* K,
                    int num_clusters = -1, int min_clusters = -1, int max_clusters = -1, std::vector<double>* soft_best = nullptr);
 void fcluster_host(const std::vector<double>& Z, int64_t n, double cutoff, std::vector<int>& T);
+// ---- activity.hip
+int64_t activity_frames_host(int64_t chunks);                     // frames aggregate() yields for `chunks` chunks (sd.cpp:1232-1234)
+int64_t activity_rows_host(int64_t nf, int64_t n_samples);        // ... without those that lie wholly in the last chunk's zero padding
+int run_activity_scores(sd_ctx* c, const float* d_seg, int64_t chunks, int kind, double* d_scores, int64_t nf);
+int run_activity_regions(sd_ctx* c, const double* d_scores, int64_t rows, int label, std::vector<sd_turn>& turns);
 // ---- reconstruct.hip
 int run_reconstruct(sd_ctx* c, const float* d_seg, const int* d_nact, const int* d_hard, const int32_t* d_count,
                     int64_t n_count, int64_t chunks, int64_t n_samples, int K, std::vector<sd_turn>& turns);

@@ -25,6 +25,12 @@
 //                   (NAME: single | complete | average | centroid | median | ward | weighted; X in 0..2; N >= 1) = sd_set_option "clustering_method" /
 //                   "min_cluster_size" and sd_set_option_f64 "clustering_threshold"; defaults are the reference's constants (centroid, 0.7153814, 15).
 //                   A bad value is a usage error (exit 2) before anything touches the GPU
+//   --activity speech|overlap   regions of speech / of overlapped speech from the segmentation network alone (sd_activity_wav: pyannote's
+//                   VoiceActivityDetection / OverlappedSpeechDetection on the reference's aggregate + to_annotation, sd.cpp:1167-1311 / 2852-2935) instead of
+//                   speaker turns: lines [start -- end] --> SPEECH or OVERLAP; --rttm writes them as SPEAKER_00 / SPEAKER_01.  With it
+//                   --activity-onset X, --activity-offset X (in [0, 1], default 0.5), --activity-min-on S, --activity-min-off S (seconds >= 0, default 0)
+//                   and --activity-hamming (Hamming-weighted aggregation) = the "activity_*" options.  A bad value is a usage error (exit 2) before
+//                   anything touches the GPU; single-GPU only (--gpus N is refused)
 //   --relabel       stdout / RTTM labels renumbered the way pyannote.audio names its output (the clusters that occur,
 //                   sorted by their string, become 0, 1, ... = SPEAKER_00, SPEAKER_01, ...); default = raw cluster ids (sd.cpp:3439)
 #include <cstdio>
@@ -39,7 +45,8 @@
 #include "sdhip.h"
 
 struct Args { const char* seg = nullptr; const char* emb = nullptr; const char* wav = nullptr; const char* rttm = nullptr; int gpus = 1; bool relabel = false; int precision = 0; int wav_flags = 0; const char* dump_dir = nullptr; int dump_level = 1;
-              int cl_method = -1; double cl_threshold = -1.0; long long cl_min_size = -1; };      // -1: leave the library's default
+              int cl_method = -1; double cl_threshold = -1.0; long long cl_min_size = -1;         // -1: leave the library's default
+              int activity = -1; double act[4] = {-1.0, -1.0, -1.0, -1.0}; bool act_hamming = false; };      // --activity: SD_ACTIVITY_*; onset, offset, min on, min off (-1: default)
 
 // the clustering hyper-parameters the command line set; false (message printed) on a refusal
 static bool apply_clustering(sd_ctx* ctx, const Args& a)
@@ -47,6 +54,15 @@ static bool apply_clustering(sd_ctx* ctx, const Args& a)
     if (a.cl_method >= 0 && sd_set_option(ctx, "clustering_method", a.cl_method) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
     if (a.cl_threshold >= 0.0 && sd_set_option_f64(ctx, "clustering_threshold", a.cl_threshold) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
     if (a.cl_min_size >= 0 && sd_set_option(ctx, "min_cluster_size", a.cl_min_size) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
+    return true;
+}
+
+static const char* const kActivityKeys[4] = {"activity_onset", "activity_offset", "activity_min_duration_on", "activity_min_duration_off"};
+static bool apply_activity(sd_ctx* ctx, const Args& a)
+{
+    for (int q = 0; q < 4; ++q)
+        if (a.act[q] >= 0.0 && sd_set_option_f64(ctx, kActivityKeys[q], a.act[q]) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
+    if (a.act_hamming && sd_set_option(ctx, "activity_hamming", 1) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
     return true;
 }
 
@@ -59,9 +75,13 @@ static void print_block(sd_ctx* ctx, sd_turn* turns, int64_t nt, const Args& a)
     printf("-----------\nClustering time: %lldms\n", (long long)ms[2]);
     printf("\n----Summary----\n-----------\nTime cost: %lldms\n", (long long)ms[3]);
     printf("----------------------------------------------------\n");
-    if (a.relabel) sd_relabel_turns(turns, nt);
+    if (a.relabel && a.activity < 0) sd_relabel_turns(turns, nt);
     char line[160];
-    for (int64_t i = 0; i < nt; ++i) { sd_format_turn(&turns[i], line, sizeof(line)); printf("%s\n", line); }
+    for (int64_t i = 0; i < nt; ++i) {
+        if (a.activity >= 0) snprintf(line, sizeof(line), "[%g -- %g] --> %s", turns[i].start, turns[i].end, turns[i].label == SD_ACTIVITY_OVERLAP ? "OVERLAP" : "SPEECH");
+        else sd_format_turn(&turns[i], line, sizeof(line));
+        printf("%s\n", line);
+    }
     printf("----------------------------------------------------\n");
     if (a.rttm) sd_write_rttm(a.rttm, a.wav, turns, nt);
     fflush(stdout);
@@ -85,10 +105,11 @@ static int run_single(const Args& a)
     if (a.precision && sd_set_option(ctx, "ecapa_precision", a.precision) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return 1; }
     if (a.precision == 3 && sd_set_option(ctx, "seg_precision", 3) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return 1; }
     if (a.dump_dir && sd_set_dump_dir(ctx, a.dump_dir, a.dump_level) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return 1; }
-    if (!apply_clustering(ctx, a)) return 1;
+    if (!apply_clustering(ctx, a) || !apply_activity(ctx, a)) return 1;
     sd_turn* turns = nullptr; int64_t nt = 0;
-    const int rc = sd_diarize_wav(ctx, a.wav, a.wav_flags, &turns, &nt);      // 8 / 16 / 32-bit PCM like wav.h:99-122; rate and channels checked
-    if (rc != SD_OK) { fprintf(stderr, "diarization failed (%d): %s\n", rc, sd_last_error(ctx)); return 1; }
+    const int rc = a.activity >= 0 ? sd_activity_wav(ctx, a.wav, a.wav_flags, a.activity, &turns, &nt)
+                                   : sd_diarize_wav(ctx, a.wav, a.wav_flags, &turns, &nt);      // 8 / 16 / 32-bit PCM like wav.h:99-122; rate and channels checked
+    if (rc != SD_OK) { fprintf(stderr, "%s failed (%d): %s\n", a.activity >= 0 ? "activity detection" : "diarization", rc, sd_last_error(ctx)); return 1; }
     TRACE("sd_diarize_wav done");
     print_block(ctx, turns, nt, a);
     sd_free_turns(turns);
@@ -192,8 +213,26 @@ int main(int argc, char* argv[])
                 if (end == v || *end || a.cl_min_size < 1 || a.cl_min_size > 0x7fffffff) { fprintf(stderr, "usage: --min-cluster-size takes an integer >= 1 (got '%s')\n", v); return 2; }
             }
         }
+        else if (s == "--activity-hamming") a.act_hamming = true;
+        else if (s == "--activity" || s == "--activity-onset" || s == "--activity-offset" || s == "--activity-min-on" || s == "--activity-min-off") {
+            // checked here too: a usage error before any context is created
+            if (i + 1 >= argc) { fprintf(stderr, "usage: %s needs a value\n", s.c_str()); return 2; }
+            const char* v = argv[++i];
+            if (s == "--activity") {
+                if (std::string(v) == "speech") a.activity = SD_ACTIVITY_SPEECH; else if (std::string(v) == "overlap") a.activity = SD_ACTIVITY_OVERLAP;
+                else { fprintf(stderr, "usage: --activity takes speech or overlap (got '%s')\n", v); return 2; }
+            } else {
+                const int q = s == "--activity-onset" ? 0 : s == "--activity-offset" ? 1 : s == "--activity-min-on" ? 2 : 3;
+                char* end = nullptr;
+                a.act[q] = strtod(v, &end);
+                if (end == v || *end || !(a.act[q] >= 0.0) || (q < 2 && a.act[q] > 1.0) || a.act[q] > 1e300) {
+                    fprintf(stderr, "usage: %s takes %s (got '%s')\n", s.c_str(), q < 2 ? "a number in [0, 1]" : "a number of seconds >= 0", v); return 2;
+                }
+            }
+        }
         else pos.push_back(argv[i]);
     }
+    if (a.activity >= 0 && a.gpus > 1) { fprintf(stderr, "usage: --activity runs on one GPU; --gpus %d is refused\n", a.gpus); return 2; }
     if (pos.size() < 3) {
         printf("program [segment model file] [embeding model file] [wave file]\n");   // sd.cpp:3423
         return 0;

@@ -253,6 +253,16 @@ int pcm_to_wav(sd_ctx* c, const int16_t* d_pcm, int64_t n, float** d_wav)
     return SD_OK;
 }
 
+// planted workload (sd_set_planted): chunks [pa, pb) of the scores of chunks [lo, hi) are taken from the caller's buffer
+static int plant_scores(sd_ctx* c, int64_t lo, int64_t hi, float* d_seg)
+{
+    const int64_t pa = std::max(lo, c->planted_lo), pb = std::min(hi, c->planted_lo + c->planted_n);
+    if (pb > pa && c->planted_scores)
+        HIPCHK(c, hipMemcpyAsync(d_seg + (size_t)(pa - lo) * SD_FRAMES * 3, c->planted_scores + (size_t)(pa - c->planted_lo) * SD_FRAMES * 3,
+                                 (size_t)(pb - pa) * SD_FRAMES * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    return SD_OK;
+}
+
 int shard_infer(sd_ctx* c, const float* d_wav, int64_t n, int64_t lo, int64_t hi, float* d_seg, float* d_emb)
 {
     const int64_t nc = hi - lo;
@@ -262,11 +272,8 @@ int shard_infer(sd_ctx* c, const float* d_wav, int64_t n, int64_t lo, int64_t hi
     int rc;
     const double t0 = now_ms();
     if ((rc = run_segment(c, d_wav, n, lo, hi, d_seg))) return rc;
-    // planted workload: chunks [pa, pb) of this shard take their scores / embeddings from the caller's buffers
+    if ((rc = plant_scores(c, lo, hi, d_seg))) return rc;
     const int64_t pa = std::max(lo, c->planted_lo), pb = std::min(hi, c->planted_lo + c->planted_n);
-    if (pb > pa && c->planted_scores)
-        HIPCHK(c, hipMemcpyAsync(d_seg + (size_t)(pa - lo) * SD_FRAMES * 3, c->planted_scores + (size_t)(pa - c->planted_lo) * SD_FRAMES * 3,
-                                 (size_t)(pb - pa) * SD_FRAMES * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     WS(c, float, d_masks, "sh_masks", nc * 3 * SD_FRAMES);
     if ((rc = run_postseg(c, d_seg, nc, nullptr, d_masks, nullptr))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -442,16 +449,21 @@ extern "C" int sd_diarize_f32(sd_ctx* c, const float* h_wav, int64_t n, sd_turn*
 // ------------------------------------------------------------------ wav file entry: reader + rate / channel handling + the path
 int resample_dev(sd_ctx* c, const float* d_in, int64_t n, int32_t in_sr, int32_t out_sr, float* d_out, int64_t n_out);   // resample.hip
 
-extern "C" int sd_diarize_wav(sd_ctx* c, const char* path, int flags, sd_turn** turns, int64_t* n_turns)
+// what a wav-file entry runs once the samples are read, in the three forms the reader hands them over: 16-bit samples, host floats already
+// divided by 32768, or -- behind the resampler -- the padded f32 waveform on the device (t0 = the entry's own start)
+struct WavJob {
+    std::function<int(const int16_t*, int64_t)> pcm;
+    std::function<int(const float*, int64_t)> f32;
+    std::function<int(const float*, int64_t, double)> dev;
+};
+
+static int run_wav_file(sd_ctx* c, const char* path, int flags, const WavJob& job)
 {
-    ENTER(c);
-    if (!path || !turns || !n_turns || (flags & ~(SD_WAV_RESAMPLE | SD_WAV_DOWNMIX | SD_WAV_ASSUME_16K))) SD_FAIL(c, SD_ERR_ARG, "sd_diarize_wav: bad argument");
-    *turns = nullptr; *n_turns = 0;
     {   // the common case -- 16-bit, 16 kHz, nothing to mix -- stays int16 up to the GPU (k_pcm_to_f32 does the reference's / 32768 there)
         int16_t* pcm = nullptr; int64_t np = 0; int32_t sr16 = 0, ch16 = 0;
         if (sd_read_wav(path, &pcm, &np, &sr16, &ch16) == SD_OK) {
             struct FreePcm { int16_t* p; ~FreePcm() { sd_free_pcm(p); } } g{pcm};
-            if ((sr16 == 16000 || (flags & SD_WAV_ASSUME_16K)) && !(ch16 > 1 && (flags & SD_WAV_DOWNMIX))) return sd_diarize(c, pcm, np, turns, n_turns);
+            if ((sr16 == 16000 || (flags & SD_WAV_ASSUME_16K)) && !(ch16 > 1 && (flags & SD_WAV_DOWNMIX))) return job.pcm(pcm, np);
         }
     }
     float* wav = nullptr; int64_t n = 0; int32_t sr = 0, ch = 0, bits = 0;
@@ -465,7 +477,7 @@ extern "C" int sd_diarize_wav(sd_ctx* c, const char* path, int flags, sd_turn** 
             wav[i] = s / (float)ch;
         }
     }
-    if (sr == 16000 || (flags & SD_WAV_ASSUME_16K)) return sd_diarize_f32(c, wav, n, turns, n_turns);      // ASSUME_16K: the reference's behaviour (sd.cpp:2940-2942)
+    if (sr == 16000 || (flags & SD_WAV_ASSUME_16K)) return job.f32(wav, n);      // ASSUME_16K: the reference's behaviour (sd.cpp:2940-2942)
     if (!(flags & SD_WAV_RESAMPLE))
         SD_FAIL(c, SD_ERR_ARG, "%s: sample rate %d Hz; the pipeline needs 16000 (README.md:37 of the reference, which would process the file as if it "
                                "were 16 kHz: SD_WAV_ASSUME_16K / --assume-16k does the same) -- pass SD_WAV_RESAMPLE / --resample", path, sr);
@@ -478,10 +490,142 @@ extern "C" int sd_diarize_wav(sd_ctx* c, const char* path, int flags, sd_turn** 
     WS(c, float, d_wav, "wav_f32", no + 512);
     HIPCHK(c, hipMemcpyAsync(d_in, wav, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_wav + no, 0, 512 * sizeof(float), c->stream));
+    if (int rc = resample_dev(c, d_in, n, sr, 16000, d_wav, no)) return rc;
+    c->wav_padded = true;
+    return job.dev(d_wav, no, t0);
+}
+
+extern "C" int sd_diarize_wav(sd_ctx* c, const char* path, int flags, sd_turn** turns, int64_t* n_turns)
+{
+    ENTER(c);
+    if (!path || !turns || !n_turns || (flags & ~(SD_WAV_RESAMPLE | SD_WAV_DOWNMIX | SD_WAV_ASSUME_16K))) SD_FAIL(c, SD_ERR_ARG, "sd_diarize_wav: bad argument");
+    *turns = nullptr; *n_turns = 0;
+    return run_wav_file(c, path, flags, {
+        [&](const int16_t* pcm, int64_t n) { return sd_diarize(c, pcm, n, turns, n_turns); },
+        [&](const float* wav, int64_t n) { return sd_diarize_f32(c, wav, n, turns, n_turns); },
+        [&](const float* d_wav, int64_t n, double t0) {
+            std::vector<sd_turn> v;
+            if (int rc = diarize_wav_dev(c, d_wav, n, t0, v)) return rc;
+            return turns_out(c, v, turns, n_turns);
+        }});
+}
+
+// ------------------------------------------------------------------ speech / overlapped-speech regions (activity.hip)
+// the stage alone: scores [chunks][293][3] -> the aggregated timeline of all its frames (sd.cpp:1167-1311)
+extern "C" int sd_activity_scores(sd_ctx* c, const float* h_seg, int64_t chunks, int kind, double* h_scores, int64_t cap, int64_t* n_frames)
+{
+    ENTER(c);
+    if (chunks <= 0 || (kind != SD_ACTIVITY_SPEECH && kind != SD_ACTIVITY_OVERLAP)) SD_FAIL(c, SD_ERR_ARG, "sd_activity_scores: bad argument (kind = SD_ACTIVITY_SPEECH or SD_ACTIVITY_OVERLAP)");
+    const int64_t nf = activity_frames_host(chunks);
+    if (n_frames) *n_frames = nf;
+    if (!h_scores) return SD_OK;
+    if (!h_seg) SD_FAIL(c, SD_ERR_ARG, "sd_activity_scores: bad argument");
+    if (cap < nf) SD_FAIL(c, SD_ERR_ARG, "sd_activity_scores: capacity %lld < %lld", (long long)cap, (long long)nf);
+    const int64_t ne = chunks * SD_FRAMES * 3;
+    DTMP(c, ds, ne * sizeof(float)); DTMP(c, dsc, nf * sizeof(double));
+    HIPCHK(c, hipMemcpy(ds.p, h_seg, ne * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = run_activity_scores(c, (const float*)ds.p, chunks, kind, (double*)dsc.p, nf)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(h_scores, dsc.p, nf * sizeof(double), hipMemcpyDeviceToHost));
+    return SD_OK;
+}
+
+// the stage alone: a timeline -> regions by the context's activity_onset / _offset / _min_duration_on / _min_duration_off (sd.cpp:2852-2935); label 0
+extern "C" int sd_activity_regions(sd_ctx* c, const double* h_scores, int64_t n_frames, sd_turn** turns, int64_t* n_turns)
+{
+    ENTER(c);
+    if (!h_scores || n_frames <= 0 || !turns || !n_turns) SD_FAIL(c, SD_ERR_ARG, "sd_activity_regions: bad argument");
+    *turns = nullptr; *n_turns = 0;
+    DTMP(c, dsc, n_frames * sizeof(double));
+    HIPCHK(c, hipMemcpy(dsc.p, h_scores, n_frames * sizeof(double), hipMemcpyHostToDevice));
+    std::vector<sd_turn> v;
+    if (int rc = run_activity_regions(c, (const double*)dsc.p, n_frames, 0, v)) return rc;
+    return turns_out(c, v, turns, n_turns);
+}
+
+// The whole path behind the sd_activity* entries that hold the padded f32 waveform on the device: chunks, PyanNet, the activity stage -> turns
+// labelled `kind`.  Nothing of the embedding, clustering or reconstruction stages runs.  stage_ms[0] = segmentation, [3] = the time since t0
+static int activity_wav_dev(sd_ctx* c, const float* d_wav, int64_t n, int kind, double t0, std::vector<sd_turn>& v)
+{
+    c->last_activity.clear();
+    const int64_t chunks = sd_num_chunks(n, nullptr);
+    if (chunks <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)n);
+    WS(c, float, d_seg, "dz_seg", chunks * SD_FRAMES * 3);
     int rc;
-    if ((rc = resample_dev(c, d_in, n, sr, 16000, d_wav, no))) return rc;
+    const double t1 = now_ms();
+    if ((rc = run_segment(c, d_wav, n, 0, chunks, d_seg))) return rc;
+    if ((rc = plant_scores(c, 0, chunks, d_seg))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->stage_ms[0] += now_ms() - t1;
+    const int64_t nf = activity_frames_host(chunks), rows = activity_rows_host(nf, n);
+    WS(c, double, d_scores, "act_scores", nf);
+    if ((rc = run_activity_scores(c, d_seg, chunks, kind, d_scores, nf))) return rc;
+    c->last_activity.resize((size_t)rows);
+    HIPCHK(c, hipMemcpyAsync(c->last_activity.data(), d_scores, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = run_activity_regions(c, d_scores, rows, kind, v))) return rc;      // (synchronises the stream)
+    c->stage_ms[3] = now_ms() - t0;
+    return SD_OK;
+}
+
+static int check_activity_args(sd_ctx* c, const void* in, int kind, sd_turn** turns, int64_t* n_turns, const char* who)
+{
+    if (!in || !turns || !n_turns || (kind != SD_ACTIVITY_SPEECH && kind != SD_ACTIVITY_OVERLAP))
+        SD_FAIL(c, SD_ERR_ARG, "%s: bad argument (kind = SD_ACTIVITY_SPEECH or SD_ACTIVITY_OVERLAP)", who);
+    return SD_OK;
+}
+
+extern "C" int sd_activity_dev(sd_ctx* c, const int16_t* d_pcm, int64_t n, int kind, sd_turn** turns, int64_t* n_turns)
+{
+    ENTER(c);
+    if (int rc = check_activity_args(c, d_pcm, kind, turns, n_turns, "sd_activity_dev")) return rc;
+    if (n <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)n);
+    const double t0 = now_ms();
+    for (int i = 0; i < 4; ++i) c->stage_ms[i] = 0;
+    float* d_wav = nullptr;
+    int rc = pcm_to_wav(c, d_pcm, n, &d_wav);
+    if (rc) return rc;
+    std::vector<sd_turn> v;
+    if ((rc = activity_wav_dev(c, d_wav, n, kind, t0, v))) return rc;
+    return turns_out(c, v, turns, n_turns);
+}
+
+extern "C" int sd_activity(sd_ctx* c, const int16_t* h_pcm, int64_t n, int kind, sd_turn** turns, int64_t* n_turns)
+{
+    ENTER(c);
+    if (!h_pcm || n <= 0) SD_FAIL(c, SD_ERR_ARG, "sd_activity: bad argument");
+    DTMP(c, dp, n * sizeof(int16_t));
+    HIPCHK(c, hipMemcpy(dp.p, h_pcm, n * sizeof(int16_t), hipMemcpyHostToDevice));
+    return sd_activity_dev(c, (const int16_t*)dp.p, n, kind, turns, n_turns);
+}
+
+extern "C" int sd_activity_f32(sd_ctx* c, const float* h_wav, int64_t n, int kind, sd_turn** turns, int64_t* n_turns)
+{
+    ENTER(c);
+    if (int rc = check_activity_args(c, h_wav, kind, turns, n_turns, "sd_activity_f32")) return rc;
+    if (n <= 0) SD_FAIL(c, SD_ERR_ARG, "sd_activity_f32: bad argument");
+    const double t0 = now_ms();
+    for (int i = 0; i < 4; ++i) c->stage_ms[i] = 0;
+    WS(c, float, d_wav, "wav_f32", n + 512);
+    HIPCHK(c, hipMemcpyAsync(d_wav, h_wav, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_wav + n, 0, 512 * sizeof(float), c->stream));
     c->wav_padded = true;
     std::vector<sd_turn> v;
-    if ((rc = diarize_wav_dev(c, d_wav, no, t0, v))) return rc;
+    if (int rc = activity_wav_dev(c, d_wav, n, kind, t0, v)) return rc;
     return turns_out(c, v, turns, n_turns);
+}
+
+extern "C" int sd_activity_wav(sd_ctx* c, const char* path, int flags, int kind, sd_turn** turns, int64_t* n_turns)
+{
+    ENTER(c);
+    if (int rc = check_activity_args(c, path, kind, turns, n_turns, "sd_activity_wav")) return rc;
+    if (flags & ~(SD_WAV_RESAMPLE | SD_WAV_DOWNMIX | SD_WAV_ASSUME_16K)) SD_FAIL(c, SD_ERR_ARG, "sd_activity_wav: bad argument");
+    *turns = nullptr; *n_turns = 0;
+    return run_wav_file(c, path, flags, {
+        [&](const int16_t* pcm, int64_t n) { return sd_activity(c, pcm, n, kind, turns, n_turns); },
+        [&](const float* wav, int64_t n) { return sd_activity_f32(c, wav, n, kind, turns, n_turns); },
+        [&](const float* d_wav, int64_t n, double t0) {
+            std::vector<sd_turn> v;
+            if (int rc = activity_wav_dev(c, d_wav, n, kind, t0, v)) return rc;
+            return turns_out(c, v, turns, n_turns);
+        }});
 }

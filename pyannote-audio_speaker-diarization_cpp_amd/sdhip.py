@@ -52,12 +52,15 @@ EXPORTS = [
     "sd_fcluster", "sd_segment_chunks", "sd_embed_signals",
     "sd_linkage_ex", "sd_cluster_ex", "sd_set_option_f64", "sd_linkage_method_from_name", "sd_test_conv", "sd_test_emb_batches",
     "sd_test_lstm_rec", "sd_test_pool_norm", "sd_test_chunk_norm", "sd_test_classifier",
+    "sd_activity_scores", "sd_activity_regions", "sd_activity", "sd_activity_dev", "sd_activity_f32", "sd_activity_wav", "sd_last_activity_scores",
 ]
 # SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
 LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
 METRIC_EUCLIDEAN, METRIC_COSINE = 0, 1
 CLUSTERING_THRESHOLD_DEFAULT = float(np.float32(0.7153814381597874))      # the reference's float constant, widened (sd.cpp:2049)
 COMM_ID_BYTES = 128
+ACTIVITY_SPEECH, ACTIVITY_OVERLAP = 0, 1      # SD_ACTIVITY_*
+ACTIVITY_KINDS = ("speech", "overlap")
 
 
 def lib():
@@ -126,6 +129,14 @@ def lib():
     L.sd_relabel_turns.argtypes = [C.POINTER(Turn), i64]
     L.sd_relabel_turns_ex.argtypes = [C.POINTER(Turn), i64, C.c_int]
     L.sd_last_confidence.argtypes = [vp, C.POINTER(dbl), i64, C.POINTER(i64)]
+    tpp = C.POINTER(C.POINTER(Turn))
+    L.sd_activity_scores.argtypes = [vp, vp, i64, C.c_int, vp, i64, C.POINTER(i64)]
+    L.sd_activity_regions.argtypes = [vp, vp, i64, tpp, C.POINTER(i64)]
+    L.sd_activity.argtypes = [vp, vp, i64, C.c_int, tpp, C.POINTER(i64)]
+    L.sd_activity_dev.argtypes = [vp, vp, i64, C.c_int, tpp, C.POINTER(i64)]
+    L.sd_activity_f32.argtypes = [vp, vp, i64, C.c_int, tpp, C.POINTER(i64)]
+    L.sd_activity_wav.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, tpp, C.POINTER(i64)]
+    L.sd_last_activity_scores.argtypes = [vp, C.POINTER(dbl), i64, C.POINTER(i64)]
     L.sd_format_turn.argtypes = [C.POINTER(Turn), C.c_char_p, C.c_int]
     L.sd_stage_ms.argtypes = [vp, C.POINTER(dbl)]
     L.sd_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
@@ -150,6 +161,13 @@ def lib():
 def linkage_method_from_name(name):
     """sd_linkage_method_from_name: scipy's method code of a linkage name, -1 for an unknown one.  Host-only."""
     return int(lib().sd_linkage_method_from_name(str(name).encode()))
+
+
+def _activity_kind(kind):
+    """'speech' / 'overlap' or SD_ACTIVITY_* -> the code (an unknown name -> -1, which the library refuses)"""
+    if isinstance(kind, (int, np.integer)):
+        return int(kind)
+    return ACTIVITY_KINDS.index(kind) if kind in ACTIVITY_KINDS else -1
 
 
 def _method_code(method):
@@ -536,6 +554,70 @@ class Diarizer:
         self._chk(lib().sd_last_confidence(self._h, None, 0, C.byref(n)))
         buf = (C.c_double * max(n.value, 1))()
         self._chk(lib().sd_last_confidence(self._h, buf, n.value, C.byref(n)))
+        return np.array(buf[:n.value], np.float64)
+
+    # ---- speech / overlapped-speech regions (sd_activity*)
+    def set_activity(self, onset=0.5, offset=0.5, min_duration_on=0.0, min_duration_off=0.0, hamming=False):
+        """pyannote's Binarize parameters of the activity timeline and the Hamming-weighted aggregation; the defaults are the library's"""
+        vals = (float(onset), float(offset), float(min_duration_on), float(min_duration_off))
+        if not (0.0 <= vals[0] <= 1.0 and 0.0 <= vals[1] <= 1.0 and vals[2] >= 0.0 and vals[3] >= 0.0):      # all five or none: the context is shared
+            raise SdError(1, "set_activity: onset %r, offset %r, min_duration_on %r, min_duration_off %r" % vals)
+        for key, v in zip(("activity_onset", "activity_offset", "activity_min_duration_on", "activity_min_duration_off"), vals):
+            self.set_option_f64(key, v)
+        self.set_option("activity_hamming", int(bool(hamming)))
+
+    def activity_scores(self, seg, kind):
+        """sd_activity_scores: [chunks][293][3] scores -> the aggregated speech / overlap timeline (float64, every frame)"""
+        seg = np.ascontiguousarray(seg, np.float32)
+        c = seg.shape[0]
+        assert seg.shape == (c, FRAMES, SPEAKERS)
+        nf = C.c_int64(0)
+        self._chk(lib().sd_activity_scores(self._h, None, c, _activity_kind(kind), None, 0, C.byref(nf)))
+        out = np.zeros(nf.value, np.float64)
+        self._chk(lib().sd_activity_scores(self._h, _ptr(seg), c, _activity_kind(kind), _ptr(out), len(out), C.byref(nf)))
+        return out
+
+    def activity_regions(self, scores):
+        """sd_activity_regions: a timeline -> [(start, end, 0)] by the context's activity options"""
+        scores = np.ascontiguousarray(scores, np.float64).reshape(-1)
+        p = C.POINTER(Turn)()
+        n = C.c_int64(0)
+        self._chk(lib().sd_activity_regions(self._h, _ptr(scores), len(scores), C.byref(p), C.byref(n)))
+        return self._turns(p, n)
+
+    def activity(self, pcm, kind):
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        p = C.POINTER(Turn)()
+        n = C.c_int64(0)
+        self._chk(lib().sd_activity(self._h, _ptr(pcm), len(pcm), _activity_kind(kind), C.byref(p), C.byref(n)))
+        return self._turns(p, n)
+
+    def activity_dev(self, d_pcm_ptr, n_samples, kind):
+        p = C.POINTER(Turn)()
+        n = C.c_int64(0)
+        self._chk(lib().sd_activity_dev(self._h, C.c_void_p(d_pcm_ptr), n_samples, _activity_kind(kind), C.byref(p), C.byref(n)))
+        return self._turns(p, n)
+
+    def activity_f32(self, wav, kind):
+        wav = np.ascontiguousarray(wav, np.float32)
+        p = C.POINTER(Turn)()
+        n = C.c_int64(0)
+        self._chk(lib().sd_activity_f32(self._h, _ptr(wav), len(wav), _activity_kind(kind), C.byref(p), C.byref(n)))
+        return self._turns(p, n)
+
+    def activity_wav(self, path, kind, resample=False, downmix=False, assume_16k=False):
+        p = C.POINTER(Turn)()
+        n = C.c_int64(0)
+        flags = (1 if resample else 0) | (2 if downmix else 0) | (4 if assume_16k else 0)
+        self._chk(lib().sd_activity_wav(self._h, str(path).encode(), flags, _activity_kind(kind), C.byref(p), C.byref(n)))
+        return self._turns(p, n)
+
+    def last_activity_scores(self):
+        """the cropped timeline of the last whole-path activity call"""
+        n = C.c_int64(0)
+        self._chk(lib().sd_last_activity_scores(self._h, None, 0, C.byref(n)))
+        buf = (C.c_double * max(n.value, 1))()
+        self._chk(lib().sd_last_activity_scores(self._h, buf, n.value, C.byref(n)))
         return np.array(buf[:n.value], np.float64)
 
     def finalize_dev(self, d_seg_ptr, d_emb_ptr, chunks, n_samples):
