@@ -260,6 +260,35 @@ int sd_activity_wav(sd_ctx*, const char* path, int flags, int kind, sd_turn** tu
 /* the timeline (sd.cpp:1167-1311, cropped as above) of the last whole-path sd_activity* call of this ctx */
 int sd_last_activity_scores(const sd_ctx*, double* scores, int64_t cap, int64_t* n);
 
+/* ---- a recording that is still growing: replaces calling speakerDiarization() (sd.cpp:2937-3234) again on everything heard so far.  After any
+ * sequence of pushes sd_stream_turns returns what sd_diarize returns on the concatenation of what was pushed -- turns, order, labels and confidences,
+ * bit for bit -- without running either network twice on a chunk that is complete.  With n samples pushed, chunk k is FULL when k * 8000 + 80000 < n
+ * (the chunk that ends exactly at n goes through the reference's "last chunk" branch, sd.cpp:1457) and the first 32 * (full / 32) chunks are SEALED:
+ * 96 items = three whole reference embedding batches (sd.cpp:2429), so their scores and embeddings can never change again, whatever is pushed later.
+ * A push appends the samples to the stream's f32 tail on the device, runs both networks on the blocks that have just become sealed, into the
+ * stream's own cache, and drops the audio in front of sample sealed * 8000; it computes no turns.  Any size is legal, 16-bit and float pushes may be
+ * mixed.  sd_stream_turns infers the pending chunks [sealed, total) behind the sealed rows and finalizes all of them under the context's current
+ * clustering options; it keeps the pending rows, so a second call with nothing pushed in between runs no inference.  sd_last_confidence and
+ * sd_stage_ms describe it ([0], [1] = the pending inference, [2] = the finalize, [3] = the call; after a push [0], [1], [3] = the sealing);
+ * SD_ERR_SHORT where sd_diarize returns it; SD_ERR_ARG while a dump directory is set (the step files describe one whole-path inference).
+ * A stream owns its device memory and uses the context's workspaces only inside a call: other entry points and other streams of the context may be
+ * called between its calls; sd_destroy closes the streams still open.  "ecapa_precision" and "seg_precision" are fixed when the stream is opened: a
+ * push or turns call under other values returns SD_ERR_ARG.  An argument error leaves the stream as it was; after SD_ERR_HIP every further
+ * call returns SD_ERR_ARG until the stream is closed.  One GPU: the sharded path has no streams. */
+typedef struct sd_stream sd_stream;
+int sd_stream_open(sd_ctx*, sd_stream** s);                                    /* sd.cpp:2937-3234, repeated */
+int sd_stream_push(sd_stream*, const int16_t* h_pcm, int64_t n);               /* samples as for sd_diarize (wav.h:107-111, sd.cpp:2950) */
+int sd_stream_push_dev(sd_stream*, const int16_t* d_pcm, int64_t n);
+int sd_stream_push_f32(sd_stream*, const float* h_wav, int64_t n);             /* samples as for sd_diarize_f32 */
+int sd_stream_turns(sd_stream*, sd_turn** turns, int64_t* n_turns);            /* == sd_diarize of everything pushed so far; free with sd_free_turns */
+int sd_stream_info(const sd_stream*, int64_t* n_samples, int64_t* chunks_sealed, int64_t* chunks_total);      /* any pointer may be NULL */
+/* cached rows of chunks [chunk_lo, chunk_hi) inside [0, total): h_seg [hi-lo][293][3] and / or h_emb [(hi-lo)*3][192] (either may be NULL).  Pending
+ * rows are those the last sd_stream_turns computed; SD_ERR_ARG when samples were pushed since, or when the range leaves [0, total) */
+int sd_stream_read(sd_stream*, int64_t chunk_lo, int64_t chunk_hi, float* h_seg, float* h_emb);
+void sd_stream_close(sd_stream*);
+/* host-only: the sealed chunks of an n_samples-sample recording, 32 * (full / 32) as above (slide()'s chunk rule, sd.cpp:1419, 1457) */
+int64_t sd_stream_sealed_chunks(int64_t n_samples);
+
 /* ---- a18: the reference's output line (sd.cpp:3439) */
 int sd_format_turn(const sd_turn* t, char* buf, int cap);
 

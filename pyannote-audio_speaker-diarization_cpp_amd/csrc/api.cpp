@@ -54,6 +54,7 @@ extern "C" void sd_destroy(sd_ctx* c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     sd_flush_profile(c);
     (void)sd_comm_destroy(c);
+    while (!c->streams.empty()) sd_stream_close(c->streams.back());      // streams still open own device memory of their own
     for (void* p : c->owned) (void)hipFree(p);
     for (auto& kv : c->ws) kv.second.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);

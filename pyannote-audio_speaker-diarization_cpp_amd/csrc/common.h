@@ -99,6 +99,10 @@ struct ConvArgs {
 #define ROWTAB_LAST(y) (((y) >> 10) & 1023)
 #define ROWTAB_ITEM(y) ((int)((unsigned)(y) >> 20))
 #define ROWTAB_MAX_ITEMS 4095
+// launch_conv_gemm (conv_gemm.hip): a plain f32 GEMM of at most this many rows goes to k_skinny_gemm, a larger one to the 128 x 128 tile, whose K order differs in
+// the last bits.  >= ROWTAB_MAX_ITEMS, so the per-utterance layers of an ECAPA batch always take the skinny kernel; PyanNet's dense layers have 293 rows per
+// chunk, so a batch of up to 13 chunks takes it too -- the stream's pending batch (stream.hip: segment_pending) reads this constant to stay on the whole path's kernel
+#define SD_SKINNY_MAX_ROWS 4096
 
 struct EcapaWeights {
     bool loaded = false;
@@ -220,6 +224,7 @@ struct sd_ctx {
     const float* planted_scores = nullptr;      // sd_set_planted: measurement / test hook
     const float* planted_emb = nullptr;
     int64_t planted_lo = 0, planted_n = 0;
+    std::vector<sd_stream*> streams;            // open sd_stream objects of this context (stream.hip); sd_destroy closes what is left
 };
 
 #define SD_FAIL(ctx, code, ...) do { char _b[512]; snprintf(_b, sizeof(_b), __VA_ARGS__); (ctx)->err = _b; return (code); } while (0)

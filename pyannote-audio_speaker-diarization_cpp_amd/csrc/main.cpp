@@ -31,8 +31,13 @@
 //                   --activity-onset X, --activity-offset X (in [0, 1], default 0.5), --activity-min-on S, --activity-min-off S (seconds >= 0, default 0)
 //                   and --activity-hamming (Hamming-weighted aggregation) = the "activity_*" options.  A bad value is a usage error (exit 2) before
 //                   anything touches the GPU; single-GPU only (--gpus N is refused)
+//   --stream SECONDS [--stream-updates]   feed the recording through an sd_stream in pieces of SECONDS (> 0) as if it were still arriving: both networks run once
+//                   per chunk as the audio comes in, the final turns are those of the run without the flag, bit for bit.  --stream-updates also prints,
+//                   after each piece, "== <seconds pushed> s, <sealed>/<total> chunks" and the turns so far.  With - as the wav path, headerless s16le
+//                   16 kHz mono samples are read from stdin until end of file (needs --stream).  Single GPU; not with --activity or --dump-steps
 //   --relabel       stdout / RTTM labels renumbered the way pyannote.audio names its output (the clusters that occur,
 //                   sorted by their string, become 0, 1, ... = SPEAKER_00, SPEAKER_01, ...); default = raw cluster ids (sd.cpp:3439)
+#include <cerrno>
 #include <cstdio>
 #include <ctime>
 #include <cstdlib>
@@ -46,7 +51,8 @@
 
 struct Args { const char* seg = nullptr; const char* emb = nullptr; const char* wav = nullptr; const char* rttm = nullptr; int gpus = 1; bool relabel = false; int precision = 0; int wav_flags = 0; const char* dump_dir = nullptr; int dump_level = 1;
               int cl_method = -1; double cl_threshold = -1.0; long long cl_min_size = -1;         // -1: leave the library's default
-              int activity = -1; double act[4] = {-1.0, -1.0, -1.0, -1.0}; bool act_hamming = false; };      // --activity: SD_ACTIVITY_*; onset, offset, min on, min off (-1: default)
+              int activity = -1; double act[4] = {-1.0, -1.0, -1.0, -1.0}; bool act_hamming = false;      // --activity: SD_ACTIVITY_*; onset, offset, min on, min off (-1: default)
+              long long stream_piece = 0; bool stream_updates = false; };      // --stream: samples per piece (0: off)
 
 // the clustering hyper-parameters the command line set; false (message printed) on a refusal
 static bool apply_clustering(sd_ctx* ctx, const Args& a)
@@ -66,10 +72,10 @@ static bool apply_activity(sd_ctx* ctx, const Args& a)
     return true;
 }
 
-static void print_block(sd_ctx* ctx, sd_turn* turns, int64_t nt, const Args& a)
+static void print_block(sd_ctx* ctx, sd_turn* turns, int64_t nt, const Args& a, const double* ms_sum = nullptr)
 {
     double ms[4];
-    sd_stage_ms(ctx, ms);
+    if (ms_sum) memcpy(ms, ms_sum, sizeof(ms)); else sd_stage_ms(ctx, ms);
     printf("-----------\nSegmenations time: %lldms\n", (long long)ms[0]);      // labels of sd.cpp:3028, 3110, 3231
     printf("-----------\nEmbedding time: %lldms\n", (long long)ms[1]);
     printf("-----------\nClustering time: %lldms\n", (long long)ms[2]);
@@ -116,6 +122,125 @@ static int run_single(const Args& a)
     sd_destroy(ctx);
     TRACE("sd_destroy done");
     return 0;
+}
+
+// ---- --stream: the recording goes through an sd_stream piece by piece
+struct StreamRun {
+    sd_ctx* ctx; sd_stream* st; const Args& a;
+    double ms[4] = {0, 0, 0, 0};                    // stage times summed over every call of the run
+    sd_turn* turns = nullptr; int64_t nt = 0;
+    void bill() { double m[4]; sd_stage_ms(ctx, m); for (int q = 0; q < 4; ++q) ms[q] += m[q]; }
+    // turns of what has been pushed; too little audio for a chunk is no turns yet, not a failure
+    bool ask()
+    {
+        sd_free_turns(turns); turns = nullptr; nt = 0;
+        const int rc = sd_stream_turns(st, &turns, &nt);
+        if (rc == SD_ERR_SHORT) return true;
+        if (rc != SD_OK) { fprintf(stderr, "diarization failed (%d): %s\n", rc, sd_last_error(ctx)); return false; }
+        bill();
+        return true;
+    }
+    // one push call; a piece may take several (stdin arrives in smaller reads)
+    bool part(int rc)
+    {
+        if (rc != SD_OK) { fprintf(stderr, "sd_stream_push failed (%d): %s\n", rc, sd_last_error(ctx)); return false; }
+        bill();
+        return true;
+    }
+    // a whole piece is in: the update block, if asked for
+    bool piece_done()
+    {
+        if (!a.stream_updates) return true;
+        if (!ask()) return false;
+        int64_t n = 0, sealed = 0, total = 0;
+        sd_stream_info(st, &n, &sealed, &total);
+        printf("== %g s, %lld/%lld chunks\n", (double)n / SD_SAMPLE_RATE, (long long)sealed, (long long)total);
+        if (a.relabel) sd_relabel_turns(turns, nt);
+        char line[160];
+        for (int64_t i = 0; i < nt; ++i) { sd_format_turn(&turns[i], line, sizeof(line)); printf("%s\n", line); }
+        fflush(stdout);
+        return true;
+    }
+    bool feed_pcm(const int16_t* p, int64_t n) { for (int64_t i = 0; i < n; i += a.stream_piece) if (!part(sd_stream_push(st, p + i, n - i < a.stream_piece ? n - i : a.stream_piece)) || !piece_done()) return false; return true; }
+    bool feed_f32(const float* p, int64_t n) { for (int64_t i = 0; i < n; i += a.stream_piece) if (!part(sd_stream_push_f32(st, p + i, n - i < a.stream_piece ? n - i : a.stream_piece)) || !piece_done()) return false; return true; }
+};
+
+// the samples sd_diarize_wav would diarize (same reader, same --resample / --downmix / --assume-16k rules), pushed in pieces
+static bool stream_file(StreamRun& r)
+{
+    const Args& a = r.a;
+    {
+        int16_t* pcm = nullptr; int64_t np = 0; int32_t sr16 = 0, ch16 = 0;
+        if (sd_read_wav(a.wav, &pcm, &np, &sr16, &ch16) == SD_OK) {
+            const bool take = (sr16 == 16000 || (a.wav_flags & SD_WAV_ASSUME_16K)) && !(ch16 > 1 && (a.wav_flags & SD_WAV_DOWNMIX));
+            const bool ok = take ? r.feed_pcm(pcm, np) : true;
+            sd_free_pcm(pcm);
+            if (take) return ok;
+        }
+    }
+    float* wav = nullptr; int64_t n = 0; int32_t sr = 0, ch = 0, bits = 0;
+    if (sd_read_wav_f32(a.wav, &wav, &n, &sr, &ch, &bits) != SD_OK) { fprintf(stderr, "cannot read PCM wav: %s\n", a.wav); return false; }
+    if (ch > 1 && (a.wav_flags & SD_WAV_DOWNMIX))
+        for (int64_t i = 0; i < n; ++i) {
+            float s = 0.0f;
+            for (int q = 0; q < ch; ++q) s += wav[i * ch + q];
+            wav[i] = s / (float)ch;
+        }
+    bool ok;
+    if (sr == 16000 || (a.wav_flags & SD_WAV_ASSUME_16K)) ok = r.feed_f32(wav, n);
+    else if (!(a.wav_flags & SD_WAV_RESAMPLE)) { fprintf(stderr, "%s: sample rate %d Hz; the pipeline needs 16000 -- pass --resample (or --assume-16k for the reference's behaviour)\n", a.wav, sr); ok = false; }
+    else {
+        int64_t no = 0;
+        std::vector<float> out((size_t)(sd_resample_len(n, sr, 16000) > 0 ? sd_resample_len(n, sr, 16000) : 1));
+        const int rc = sd_resample(r.ctx, wav, n, sr, 16000, out.data(), (int64_t)out.size(), &no);
+        if (rc != SD_OK) { fprintf(stderr, "resampling failed (%d): %s\n", rc, sd_last_error(r.ctx)); ok = false; }
+        else ok = r.feed_f32(out.data(), no);
+    }
+    sd_free_wav(wav);
+    return ok;
+}
+
+// headerless s16le 16 kHz mono samples from stdin, pushed as they arrive: reads of at most 2 MiB, an update block whenever a piece is complete
+static bool stream_stdin(StreamRun& r)
+{
+    const long long piece = r.a.stream_piece;
+    std::vector<int16_t> buf((size_t)(piece < (1 << 20) ? piece : (1 << 20)));
+    size_t have = 0;                                 // bytes of buf filled
+    long long in_piece = 0;                          // samples of the current piece pushed so far
+    for (;;) {
+        const long long room = piece - in_piece;     // samples the current piece still takes
+        const size_t want = (size_t)(room < (long long)buf.size() ? room : (long long)buf.size()) * 2;
+        const ssize_t got = read(0, (char*)buf.data() + have, want - have);
+        if (got < 0) { if (errno == EINTR) continue; perror("stdin"); return false; }
+        have += (size_t)got;
+        if (have == want || (got == 0 && have >= 2)) {
+            const long long m = (long long)(have / 2);
+            if (!r.part(sd_stream_push(r.st, buf.data(), m))) return false;
+            in_piece += m; have = 0;                 // (an odd byte at the end of the input is dropped)
+            if (in_piece == piece) { if (!r.piece_done()) return false; in_piece = 0; }
+        }
+        if (got == 0) return in_piece == 0 || r.piece_done();      // end of input: the last piece is a partial one
+    }
+}
+
+static int run_stream(const Args& a)
+{
+    sd_ctx* ctx = sd_create(a.seg, a.emb, 0);
+    if (!ctx) { fprintf(stderr, "sd_create failed: %s\n", sd_create_error()); return 1; }
+    sd_stream* st = nullptr;
+    StreamRun r{ctx, st, a};
+    auto leave = [&](int rc) { sd_free_turns(r.turns); sd_stream_close(r.st); sd_destroy(ctx); return rc; };      // every way out gives back what it holds
+    if (a.precision && sd_set_option(ctx, "ecapa_precision", a.precision) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
+    if (a.precision == 3 && sd_set_option(ctx, "seg_precision", 3) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
+    if (!apply_clustering(ctx, a)) return leave(1);
+    if (sd_stream_open(ctx, &r.st) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
+    const bool fed = std::string(a.wav) == "-" ? stream_stdin(r) : stream_file(r);
+    if (!fed || !r.ask()) return leave(1);
+    int64_t n = 0, total = 0;
+    sd_stream_info(r.st, &n, nullptr, &total);
+    if (total <= 0) { fprintf(stderr, "diarization failed (%d): audio of %lld samples yields no chunk\n", SD_ERR_SHORT, (long long)n); return leave(1); }
+    print_block(ctx, r.turns, r.nt, a, r.ms);
+    return leave(0);
 }
 
 static bool read_all(int fd, void* buf, size_t n)
@@ -213,6 +338,15 @@ int main(int argc, char* argv[])
                 if (end == v || *end || a.cl_min_size < 1 || a.cl_min_size > 0x7fffffff) { fprintf(stderr, "usage: --min-cluster-size takes an integer >= 1 (got '%s')\n", v); return 2; }
             }
         }
+        else if (s == "--stream-updates") a.stream_updates = true;
+        else if (s == "--stream") {
+            if (i + 1 >= argc) { fprintf(stderr, "usage: --stream needs a value\n"); return 2; }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            const double sec = strtod(v, &end);
+            if (end == v || *end || !(sec > 0.0) || !(sec * SD_SAMPLE_RATE >= 1.0) || sec > 86400.0) { fprintf(stderr, "usage: --stream takes a number of seconds > 0, at least one sample and at most a day (got '%s')\n", v); return 2; }
+            a.stream_piece = (long long)(sec * SD_SAMPLE_RATE + 0.5);
+        }
         else if (s == "--activity-hamming") a.act_hamming = true;
         else if (s == "--activity" || s == "--activity-onset" || s == "--activity-offset" || s == "--activity-min-on" || s == "--activity-min-off") {
             // checked here too: a usage error before any context is created
@@ -233,11 +367,17 @@ int main(int argc, char* argv[])
         else pos.push_back(argv[i]);
     }
     if (a.activity >= 0 && a.gpus > 1) { fprintf(stderr, "usage: --activity runs on one GPU; --gpus %d is refused\n", a.gpus); return 2; }
+    if (a.stream_piece > 0 && a.gpus > 1) { fprintf(stderr, "usage: --stream runs on one GPU; --gpus %d is refused\n", a.gpus); return 2; }
+    if (a.stream_piece > 0 && a.activity >= 0) { fprintf(stderr, "usage: --stream gives speaker turns; --activity is refused with it\n"); return 2; }
+    if (a.stream_piece > 0 && a.dump_dir) { fprintf(stderr, "usage: --dump-steps describes one whole-path inference; --stream is refused with it\n"); return 2; }
+    if (a.stream_updates && a.stream_piece <= 0) { fprintf(stderr, "usage: --stream-updates needs --stream SECONDS\n"); return 2; }
+    if (pos.size() >= 3 && std::string(pos[2]) == "-" && a.stream_piece <= 0) { fprintf(stderr, "usage: samples from stdin (-) need --stream SECONDS\n"); return 2; }
     if (pos.size() < 3) {
         printf("program [segment model file] [embeding model file] [wave file]\n");   // sd.cpp:3423
         return 0;
     }
     a.seg = pos[0]; a.emb = pos[1]; a.wav = pos[2];
+    if (a.stream_piece > 0) return run_stream(a);
     if (a.gpus <= 1) return run_single(a);
 
     // ---- launcher: nothing below touches HIP in this process.  id pipes carry the rendezvous id from rank 0 to rank r,

@@ -263,7 +263,9 @@ static int plant_scores(sd_ctx* c, int64_t lo, int64_t hi, float* d_seg)
     return SD_OK;
 }
 
-int shard_infer(sd_ctx* c, const float* d_wav, int64_t n, int64_t lo, int64_t hi, float* d_seg, float* d_emb)
+// seg_done: d_seg already holds the scores of chunks [lo, hi) (stream.hip computes those of a small pending batch itself, on the kernels the whole
+// path takes for them); everything behind the segmentation step is the same
+int shard_infer_ex(sd_ctx* c, const float* d_wav, int64_t n, int64_t lo, int64_t hi, float* d_seg, float* d_emb, bool seg_done)
 {
     const int64_t nc = hi - lo;
     c->stash.infer_items = nc > 0 ? nc * SD_SPEAKERS : 0;
@@ -271,7 +273,7 @@ int shard_infer(sd_ctx* c, const float* d_wav, int64_t n, int64_t lo, int64_t hi
     if ((lo * SD_SPEAKERS) % SD_EMB_BATCH != 0) SD_FAIL(c, SD_ERR_ARG, "shard start %lld must be a multiple of 32 chunks", (long long)lo);
     int rc;
     const double t0 = now_ms();
-    if ((rc = run_segment(c, d_wav, n, lo, hi, d_seg))) return rc;
+    if (!seg_done && (rc = run_segment(c, d_wav, n, lo, hi, d_seg))) return rc;
     if ((rc = plant_scores(c, lo, hi, d_seg))) return rc;
     const int64_t pa = std::max(lo, c->planted_lo), pb = std::min(hi, c->planted_lo + c->planted_n);
     WS(c, float, d_masks, "sh_masks", nc * 3 * SD_FRAMES);
@@ -288,6 +290,11 @@ int shard_infer(sd_ctx* c, const float* d_wav, int64_t n, int64_t lo, int64_t hi
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->stage_ms[1] += now_ms() - t1;
     return SD_OK;
+}
+
+int shard_infer(sd_ctx* c, const float* d_wav, int64_t n, int64_t lo, int64_t hi, float* d_seg, float* d_emb)
+{
+    return shard_infer_ex(c, d_wav, n, lo, hi, d_seg, d_emb, false);
 }
 
 int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, std::vector<sd_turn>& v)

@@ -53,6 +53,8 @@ EXPORTS = [
     "sd_linkage_ex", "sd_cluster_ex", "sd_set_option_f64", "sd_linkage_method_from_name", "sd_test_conv", "sd_test_emb_batches",
     "sd_test_lstm_rec", "sd_test_pool_norm", "sd_test_chunk_norm", "sd_test_classifier",
     "sd_activity_scores", "sd_activity_regions", "sd_activity", "sd_activity_dev", "sd_activity_f32", "sd_activity_wav", "sd_last_activity_scores",
+    "sd_stream_open", "sd_stream_push", "sd_stream_push_dev", "sd_stream_push_f32", "sd_stream_turns", "sd_stream_info", "sd_stream_read",
+    "sd_stream_close", "sd_stream_sealed_chunks",
 ]
 # SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
 LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
@@ -137,6 +139,17 @@ def lib():
     L.sd_activity_f32.argtypes = [vp, vp, i64, C.c_int, tpp, C.POINTER(i64)]
     L.sd_activity_wav.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, tpp, C.POINTER(i64)]
     L.sd_last_activity_scores.argtypes = [vp, C.POINTER(dbl), i64, C.POINTER(i64)]
+    L.sd_stream_open.argtypes = [vp, C.POINTER(vp)]
+    L.sd_stream_push.argtypes = [vp, vp, i64]
+    L.sd_stream_push_dev.argtypes = [vp, vp, i64]
+    L.sd_stream_push_f32.argtypes = [vp, vp, i64]
+    L.sd_stream_turns.argtypes = [vp, tpp, C.POINTER(i64)]
+    L.sd_stream_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.sd_stream_read.argtypes = [vp, i64, i64, vp, vp]
+    L.sd_stream_close.argtypes = [vp]
+    L.sd_stream_close.restype = None
+    L.sd_stream_sealed_chunks.restype = i64
+    L.sd_stream_sealed_chunks.argtypes = [i64]
     L.sd_format_turn.argtypes = [C.POINTER(Turn), C.c_char_p, C.c_int]
     L.sd_stage_ms.argtypes = [vp, C.POINTER(dbl)]
     L.sd_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
@@ -179,6 +192,11 @@ def num_chunks(n):
     ll = C.c_int64(0)
     c = lib().sd_num_chunks(n, C.byref(ll))
     return int(c), int(ll.value)
+
+
+def sealed_chunks(n):
+    """sd_stream_sealed_chunks: chunks of an n-sample recording whose scores and embeddings are final, 32 * (full / 32).  Host-only."""
+    return int(lib().sd_stream_sealed_chunks(int(n)))
 
 
 def fcluster(Z, cutoff):
@@ -315,6 +333,70 @@ def comm_unique_id():
     if rc:
         raise SdError(rc, "sd_comm_unique_id failed (RCCL needs a GPU)")
     return buf.raw
+
+
+class Stream:
+    """sd_stream_*: a recording that is still growing.  push* appends samples (and infers the blocks of 32 chunks that became final),
+    turns() == Diarizer.diarize of everything pushed so far.  Made by Diarizer.stream(); also a context manager."""
+
+    def __init__(self, diarizer):
+        self._d = diarizer
+        h = C.c_void_p(None)
+        diarizer._chk(lib().sd_stream_open(diarizer._h, C.byref(h)))
+        self._s = h
+
+    def close(self):
+        if self._s and self._d._h:              # a closed Diarizer has closed its streams (sd_destroy)
+            lib().sd_stream_close(self._s)
+        self._s = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._s or not self._d._h:
+            raise SdError(1, "the stream is closed")
+        return self._s
+
+    def push(self, pcm):
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        self._d._chk(lib().sd_stream_push(self._handle(), _ptr(pcm), len(pcm)))
+
+    def push_f32(self, wav):
+        wav = np.ascontiguousarray(wav, np.float32)
+        self._d._chk(lib().sd_stream_push_f32(self._handle(), _ptr(wav), len(wav)))
+
+    def push_dev(self, d_pcm_ptr, n_samples):
+        self._d._chk(lib().sd_stream_push_dev(self._handle(), C.c_void_p(d_pcm_ptr or None), n_samples))
+
+    def turns(self):
+        p = C.POINTER(Turn)()
+        n = C.c_int64(0)
+        self._d._chk(lib().sd_stream_turns(self._handle(), C.byref(p), C.byref(n)))
+        return self._d._turns(p, n)
+
+    def info(self):
+        """(samples pushed, chunks sealed, chunks in all)"""
+        n, sealed, total = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._d._chk(lib().sd_stream_info(self._handle(), C.byref(n), C.byref(sealed), C.byref(total)))
+        return int(n.value), int(sealed.value), int(total.value)
+
+    def read(self, lo, hi, seg=True, emb=True):
+        """cached rows of chunks [lo, hi): (scores [hi-lo][293][3] or None, embeddings [(hi-lo)*3][192] or None)"""
+        rows = max(int(hi) - int(lo), 0)
+        s = np.zeros((rows, FRAMES, SPEAKERS), np.float32) if seg else None
+        e = np.zeros((rows * SPEAKERS, EMB_DIM), np.float32) if emb else None
+        self._d._chk(lib().sd_stream_read(self._handle(), int(lo), int(hi), _ptr(s) if seg else None, _ptr(e) if emb else None))
+        return s, e
 
 
 class Diarizer:
@@ -548,6 +630,10 @@ class Diarizer:
         n = C.c_int64(0)
         self._chk(lib().sd_diarize_sharded(self._h, _ptr(pcm_shard), first_sample, len(pcm_shard), n_total, C.byref(p), C.byref(n)))
         return self._turns(p, n)
+
+    def stream(self):
+        """sd_stream_open: incremental diarization of a growing recording on this context"""
+        return Stream(self)
 
     def last_confidence(self):
         n = C.c_int64(0)
