@@ -190,7 +190,7 @@ extern "C" int sd_embed_dev(sd_ctx* c, const float* d_wav, int64_t n, const floa
 {
     ENTER(c);
     if (!d_wav || !d_masks || !d_emb || n <= 0 || items < 0) SD_FAIL(c, SD_ERR_ARG, "sd_embed_dev: bad argument");
-    int rc = run_embed(c, d_wav, n, d_masks, items, first_item, d_emb);
+    int rc = run_embed(c, DevWav{d_wav, n}, d_masks, items, first_item, d_emb);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SD_OK;
@@ -203,7 +203,7 @@ extern "C" int sd_embed(sd_ctx* c, const float* h_wav, int64_t n, const float* h
     DTMP(c, dw, n * sizeof(float)); DTMP(c, dm, items * SD_FRAMES * sizeof(float)); DTMP(c, de, items * SD_EMB_DIM * sizeof(float));
     HIPCHK(c, hipMemcpy(dw.p, h_wav, n * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(dm.p, h_masks, items * SD_FRAMES * sizeof(float), hipMemcpyHostToDevice));
-    int rc = run_embed(c, (const float*)dw.p, n, (const float*)dm.p, items, 0, (float*)de.p);
+    int rc = run_embed(c, DevWav{(const float*)dw.p, n}, (const float*)dm.p, items, 0, (float*)de.p);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(h_emb, de.p, items * SD_EMB_DIM * sizeof(float), hipMemcpyDeviceToHost));
@@ -224,7 +224,7 @@ extern "C" int sd_frontend(sd_ctx* c, const float* h_wav, int64_t n, const float
     HIPCHK(c, hipMemcpy(dr.p, ro.data(), ro.size() * sizeof(int), hipMemcpyHostToDevice));
     int rc = frontend_prepare(c, (const float*)dm.p, items, 0, (float*)dl.p, (int*)dn.p, (int*)dv.p, (int*)dg.p, false, nullptr, nullptr);
     if (rc) return rc;
-    if ((rc = frontend_features(c, (const float*)dw.p, n, 0, items, false, (const int*)dn.p, (const int*)dr.p, (float*)df.p))) return rc;
+    if ((rc = frontend_features(c, DevWav{(const float*)dw.p, n}, 0, items, false, (const int*)dn.p, (const int*)dr.p, (float*)df.p))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (h_feats) {
         std::vector<float> tmp((size_t)items * SD_TP * SD_FEAT_LD);
@@ -285,10 +285,10 @@ extern "C" int sd_embed_signals(sd_ctx* c, const float* h_signals, const float* 
     }
     const int64_t ns = B * (int64_t)SD_CHUNK;
     // persistent workspaces, not per-call allocations: the reference calls infer once per batch of 32 items (677 times per hour of audio)
-    WS(c, float, dw, "sig_wav", ns + 512); WS(c, int, dv, "sig_nvalid", B); WS(c, int, dn, "sig_nnorm", B);
+    WS(c, float, dw, "sig_wav", ns + SD_WAV_PAD); WS(c, int, dv, "sig_nvalid", B); WS(c, int, dn, "sig_nnorm", B);
     WS(c, int, dr, "sig_rowoff", EC_SPACES * (B + 1)); WS(c, float, de, "sig_emb", B * SD_EMB_DIM);
     HIPCHK(c, hipMemcpyAsync(dw, h_signals, ns * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(dw + ns, 0, 512 * sizeof(float), c->stream));
+    HIPCHK(c, hipMemsetAsync(dw + ns, 0, SD_WAV_PAD * sizeof(float), c->stream));
     HIPCHK(c, hipMemcpyAsync(dv, nv.data(), B * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(dn, nn.data(), B * sizeof(int), hipMemcpyHostToDevice, c->stream));
     EcapaRowPlan plan;
@@ -296,11 +296,8 @@ extern "C" int sd_embed_signals(sd_ctx* c, const float* h_signals, const float* 
     if (rc) return rc;
     WS(c, float, df, "sig_feats", (size_t)plan.off[0][(size_t)B] * SD_FEAT_LD);
     if ((rc = frontend_prepare_signals(c, B))) return rc;
-    const int64_t origin = c->wav_origin;
-    c->wav_origin = 0; c->fe_bill_samples = -1;
-    rc = frontend_features(c, dw, ns, 0, B, false, dn, dr, df, true);
-    c->wav_origin = origin;
-    if (rc) return rc;
+    c->fe_bill_samples = -1;
+    if ((rc = frontend_features(c, DevWav{dw, ns, 0, true}, 0, B, false, dn, dr, df, true))) return rc;
     const int64_t nb = c->emb_batch_explicit ? c->emb_batch_items : std::min<int64_t>(c->emb_batch_items, 768);      // an operator-level call: the small arena
     if ((rc = ecapa_run_items(c, df, dv, plan, nb, false, de))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));

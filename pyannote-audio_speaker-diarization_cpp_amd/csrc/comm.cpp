@@ -101,11 +101,6 @@ extern "C" int sd_comm_info(const sd_ctx* c, int* rank, int* world)
     return SD_OK;
 }
 
-int shard_infer(sd_ctx* c, const float* d_wav, int64_t n, int64_t lo, int64_t hi, float* d_seg, float* d_emb);     // pipeline.cpp
-int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, std::vector<sd_turn>& v);
-int turns_out(sd_ctx* c, const std::vector<sd_turn>& v, sd_turn** turns, int64_t* n_turns);
-int pcm_to_wav(sd_ctx* c, const int16_t* d_pcm, int64_t n, float** d_wav);
-
 // ---- failure handling of the collective step
 // A rank that fails locally (bad samples, a HIP error in its inference) must not return before the all-gather: its peers would
 // block in the collective forever.  Every rank therefore ALWAYS reaches the exchange and contributes a status record
@@ -179,7 +174,7 @@ extern "C" int sd_diarize_sharded_dev(sd_ctx* c, const int16_t* d_pcm_shard, int
     std::vector<int64_t> lo, hi;
     const int64_t per = plan_ranges(n, W, c->rank0_permille, lo, hi);
     const int64_t mylo = virt ? 0 : lo[(size_t)c->rank], myhi = virt ? C : hi[(size_t)c->rank];
-    for (int i = 0; i < 4; ++i) c->stage_ms[i] = 0;
+    clear_stage_ms(c);
     const size_t seg_slot = (size_t)per * SD_FRAMES * 3, emb_slot = (size_t)per * 3 * SD_EMB_DIM;
     WS(c, float, s_seg, "mg_send_seg", seg_slot);
     WS(c, float, s_emb, "mg_send_emb", emb_slot);
@@ -199,7 +194,7 @@ extern "C" int sd_diarize_sharded_dev(sd_ctx* c, const int16_t* d_pcm_shard, int
     if (myhi > mylo) {
         const int64_t need_lo = mylo * SD_HOP;
         int64_t need_hi = (myhi - 1) * SD_HOP + SD_CHUNK; if (need_hi > n) need_hi = n;
-        float* w = nullptr;
+        DevWav w;
         bool played = false;                          // virt: the per-rank loop was reached (every played rank then has its own record)
         auto local = [&]() -> int {
             if (!d_pcm_shard || first_sample < 0 || shard_samples < 0 || first_sample > need_lo || first_sample + shard_samples < need_hi)
@@ -207,22 +202,21 @@ extern "C" int sd_diarize_sharded_dev(sd_ctx* c, const int16_t* d_pcm_shard, int
                         (long long)(first_sample + shard_samples), (long long)mylo, (long long)myhi);
             int r;
             if ((r = pcm_to_wav(c, d_pcm_shard, shard_samples, &w))) return r;
-            c->wav_origin = first_sample;             // kernels index the recording with absolute sample positions
+            w.n = n; w.origin = first_sample;         // a slice of the recording: kernels index it with absolute sample positions
             r = SD_OK;
             if (!virt) { if (c->inject_fail_rank == c->rank) SD_FAIL(c, SD_ERR_ARG, "rank %d: injected failure (option inject_fail_rank)", c->rank);
-                         r = shard_infer(c, w, n, mylo, myhi, s_seg, s_emb); }
+                         r = shard_infer(c, w, mylo, myhi, s_seg, s_emb); }
             else for (int q = 0; q < W; ++q) {
                 played = true;
                 int rq = SD_OK;
                 if (q == c->inject_fail_rank) rq = SD_ERR_ARG;            // the played rank q "fails": what the real rank 0 would see of it
-                else if (hi[(size_t)q] > lo[(size_t)q] && !r) rq = shard_infer(c, w, n, lo[(size_t)q], hi[(size_t)q], g_seg + (size_t)q * seg_slot, g_emb + (size_t)q * emb_slot);
+                else if (hi[(size_t)q] > lo[(size_t)q] && !r) rq = shard_infer(c, w, lo[(size_t)q], hi[(size_t)q], g_seg + (size_t)q * seg_slot, g_emb + (size_t)q * emb_slot);
                 record(q, rq);
                 if (rq && !r && q != c->inject_fail_rank) r = rq;         // a real failure of the one physical rank
             }
             return r;
         };
         rc = local();
-        c->wav_origin = 0;
         if (rc) my_err = c->err;
         // a failure in front of the loop (samples that do not cover the chunks, pcm_to_wav) is every played rank's failure: without a
         // record the digest would read sequence number 0 and report "rank 0 is in another job" instead of the real code and message

@@ -20,6 +20,15 @@
 #define SD_NMELS 80
 #define SD_FEAT_LD 96     // mel channels padded to a multiple of 32
 
+// The waveform a stage reads, on the device.  It travels as a value from the entry that knows the buffer to the launches: nothing about it is kept in the context
+#define SD_WAV_PAD 512      // zeroed floats the library leaves behind the last sample it holds: SincNet's 256-tap rows read 4 samples past the last window
+struct DevWav {
+    const float* p;         // p[0] = sample `origin` of the recording
+    int64_t n;              // samples of the whole recording (not of the slice held)
+    int64_t origin = 0;     // > 0: the sharded entries and a stream hold a slice
+    bool padded = false;    // SD_WAV_PAD zeroed floats follow the last held sample (library-allocated buffers only); the shared-conv0 path of PyanNet needs them
+};
+
 struct KernelStat { double ms = 0; int64_t launches = 0; double flops = 0, bytes = 0; };
 
 // SD_TRACE_WS=1 (diagnostic): what the workspace allocations of a job cost -- hipMalloc / hipFree time and bytes, printed by sd_diarize*
@@ -173,7 +182,6 @@ struct sd_ctx {
     bool conv_w256_f32 = true;                  // f32: the same 256 x 256 kernel for the wide, long-K ECAPA layers (TDNN, MFA)
     int conv_pn128 = 0;                         // 128 x 128 kernel: column tiles per super-block (0 = 8); tuning
     int ecapa_ld_pad = 0;                       // elements added to the leading dimensions of the ECAPA activation buffers (multiple of 8)
-    bool wav_padded = false;                    // the waveform buffer in use was allocated by the library with 512 zeroed floats behind the samples
     bool seg_wide_ih = true;                    // LSTM input projections of layers 1-3 on the 256 x 256 tile (identity row table); tuning
     bool seg_shared_conv0 = true;               // SincNet conv0 once over the waveform instead of once per (90 % overlapping) chunk
     int conv_w256_kmin = 0;                     // 256 x 256 kernel: shortest contraction Cin * KT it takes (0 = built-in: 1024 f32, 256 fp16); tuning
@@ -208,7 +216,6 @@ struct sd_ctx {
     bool activity_hamming = false;              // aggregate()'s Hamming-weighted branch (sd.cpp:1211-1215)
     std::vector<double> last_activity;           // cropped scores of the last sd_activity* call (sd_last_activity_scores)
     int64_t fe_bill_samples = -1, fe_bill_frames = 0;   // profiling: selected samples / stored frames of the next k_stft_fbank launch (-1 = unknown)
-    int64_t wav_origin = 0;                     // recording position of d_wav[0] for the current call (sharded entry points hold a slice)
     void* comm = nullptr;                       // ncclComm_t (comm.cpp), null = single GPU
     int rank = 0, world = 1;
     int virtual_world = 0;                      // test mode of sd_diarize_sharded on one rank (comm.cpp)
@@ -335,7 +342,7 @@ int build_conv_w16x(sd_ctx* c, ConvLayer& L, void* d, unsigned* d_max);    // se
 // ---- frontend.hip
 int frontend_prepare(sd_ctx* c, const float* d_masks, int64_t items, int64_t first_item, float* d_wav_lens, int* d_nnorm, int* d_nvalid,
                      int* d_flags, bool compact, int* h_n_active, int* d_cidx, std::vector<int>* h_nvalid = nullptr);
-int frontend_features(sd_ctx* c, const float* d_wav, int64_t n, int64_t first_item, int64_t run_items, bool compact, const int* d_nnorm,
+int frontend_features(sd_ctx* c, const DevWav& w, int64_t first_item, int64_t run_items, bool compact, const int* d_nnorm,
                       const int* d_rowoff, float* d_feats /*[rowoff[run_items]][96]*/, bool sig_mode = false);
 int frontend_prepare_signals(sd_ctx* c, int64_t items);       // sd_embed_signals: identity gather tables for [items][80000] signal rows
 // ---- ecapa.hip
@@ -362,10 +369,11 @@ int64_t ecapa_round_items(int64_t nb);      // the item budget of a batch as it 
 // all the plan's items in planned batches of a row budget of nb full-length items (run_ecapa per batch); x3 mode: repeats the batches on the f32
 // kernels if an embedding came out non-finite
 int ecapa_run_items(sd_ctx* c, const float* d_feats, const int* d_nvalid, const EcapaRowPlan& plan, int64_t nb, bool balance, float* d_emb);
-int run_embed(sd_ctx* c, const float* d_wav, int64_t n, const float* d_masks, int64_t items, int64_t first_item, float* d_emb);
+int run_embed(sd_ctx* c, const DevWav& w, const float* d_masks, int64_t items, int64_t first_item, float* d_emb);
 // ---- pyannet.hip
-int run_segment(sd_ctx* c, const float* d_wav, int64_t n, int64_t chunk_lo, int64_t chunk_hi, float* d_seg);
-int run_segment_rows(sd_ctx* c, const float* d_rows, int64_t rows, int T, float* d_seg, int* frames);   // SegmentModel::infer as declared (sd.cpp:1352)
+int run_segment(sd_ctx* c, const DevWav& w, int64_t chunk_lo, int64_t chunk_hi, float* d_seg);
+// SegmentModel::infer as declared (sd.cpp:1352): rows = {rows.n / T separate waveforms of T samples, back to back; origin 0}
+int run_segment_rows(sd_ctx* c, const DevWav& rows, int T, float* d_seg, int* frames);
 // the launches of pyannet.hip's kernels, asynchronous on c->stream: grid, block and k_pool_norm's template choice are computed here; seg_batch and the test
 // hooks of seg_test.hip call the same ones.  chunk_norm: xn [chunks][80000]; chunk_stats: st [chunks] (a, c), hop = 8000;
 // pool_norm: stage 0 (C 80, pad 96, abs; cst != null: the shared form, chunk ck starts at row ck * chunk_rows of `in`), 1 or 2 (C 60, pad 64), Lp = Lc / 3;
@@ -378,6 +386,18 @@ int launch_pool_norm(sd_ctx* c, int stage, const float* in, int64_t chunks, int 
 int launch_lstm_rec(sd_ctx* c, const float* G, const float* whh_f, const float* whh_b, const void* whx_f, const void* whx_b, float inv_f, float inv_b,
                     float* H, int64_t B, int F);
 int launch_classifier(sd_ctx* c, const float* y, const float* W, const float* bias, float* seg, int64_t chunks, int F);
+// ---- pipeline.cpp
+__global__ void k_pcm_to_f32(const int16_t* __restrict__ pcm, float* __restrict__ dst, int64_t n);   // dst[0, n) = pcm / 32768, dst[n, n + SD_WAV_PAD) = 0; grid GRID1(n + SD_WAV_PAD)
+// the two producers of workspace "wav_f32": *out = {n samples, origin 0, padded}; a caller that uploaded a slice of a longer recording sets n and origin itself
+int pcm_to_wav(sd_ctx* c, const int16_t* d_pcm, int64_t n, DevWav* out);
+int f32_to_wav(sd_ctx* c, const float* h_wav, int64_t n, DevWav* out);
+inline void clear_stage_ms(sd_ctx* c) { for (double& ms : c->stage_ms) ms = 0; }
+// both networks on chunks [lo, hi) -> d_seg [hi-lo][293][3], d_emb [(hi-lo)*3][192]; seg_done: d_seg already holds the scores (stream.hip)
+int shard_infer(sd_ctx* c, const DevWav& w, int64_t lo, int64_t hi, float* d_seg, float* d_emb, bool seg_done = false);
+int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, std::vector<sd_turn>& v);
+int turns_out(sd_ctx* c, const std::vector<sd_turn>& v, sd_turn** turns, int64_t* n_turns);
+// ---- resample.hip
+int resample_dev(sd_ctx* c, const float* d_in, int64_t n, int32_t in_sr, int32_t out_sr, float* d_out, int64_t n_out);
 // ---- postseg.hip
 int run_postseg(sd_ctx* c, const float* d_seg, int64_t chunks, uint8_t* d_bin, float* d_masks, int* d_nact);
 int run_count(sd_ctx* c, const uint8_t* d_bin, int64_t chunks, int32_t* d_count, int64_t n_count, double* d_avg = nullptr);

@@ -515,7 +515,7 @@ static int bill_frontend(sd_ctx* c, const int* d_cidx, int64_t items, int64_t ro
     return SD_OK;
 }
 
-int run_embed(sd_ctx* c, const float* d_wav, int64_t n, const float* d_masks, int64_t items, int64_t first_item, float* d_emb)
+int run_embed(sd_ctx* c, const DevWav& w, const float* d_masks, int64_t items, int64_t first_item, float* d_emb)
 {
     if (items <= 0) return SD_OK;
     int64_t nb = c->emb_batch_items;
@@ -543,7 +543,7 @@ int run_embed(sd_ctx* c, const float* d_wav, int64_t n, const float* d_masks, in
         WS(c, float, feats, "emb_feats", rows_all * SD_FEAT_LD);
         c->fe_bill_samples = -1;
         if (c->profile && (rc = bill_frontend(c, cidx, items, rows_all))) return rc;
-        rc = frontend_features(c, d_wav, n, first_item, n_active, true, nnorm, d_rowoff, feats);
+        rc = frontend_features(c, w, first_item, n_active, true, nnorm, d_rowoff, feats);
         c->fe_bill_samples = -1;
         if (rc) return rc;
         // A batch plan whose activation arena cannot be allocated (a second context on the GPU, an 8-h job beside the 80 GB distance matrix: the

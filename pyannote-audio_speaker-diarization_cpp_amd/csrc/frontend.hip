@@ -324,7 +324,7 @@ int frontend_prepare(sd_ctx* c, const float* d_masks, int64_t items, int64_t fir
 
 // Phase B: compaction gather + STFT + mel + dB, then top-dB clamp and mean normalisation into the compact feature rows
 // d_feats [rowoff[run_items]][96] (item's frame t at row d_rowoff[item] + t; frames beyond an item's rows are not computed).
-int frontend_features(sd_ctx* c, const float* d_wav, int64_t n, int64_t first_item, int64_t run_items, bool compact, const int* d_nnorm,
+int frontend_features(sd_ctx* c, const DevWav& w, int64_t first_item, int64_t run_items, bool compact, const int* d_nnorm,
                       const int* d_rowoff, float* d_feats, bool sig_mode)
 {
     if (run_items <= 0) return SD_OK;
@@ -345,7 +345,7 @@ int frontend_features(sd_ctx* c, const float* d_wav, int64_t n, int64_t first_it
                                                   : (double)run_items * (321172.0 + 160320.0);
         const double fr = c->fe_bill_samples >= 0 ? (double)c->fe_bill_frames : (double)run_items * SD_T;
         ProfScope ps(c, "stft_mel", fr * (15000.0 + 201.0 * 80 * 2), by);
-        hipLaunchKernelGGL(k_stft_fbank, dim3(grid), dim3(256), 0, c->stream, d_wav, c->wav_origin, n, d_prefix, d_counts, first_item, E.window, E.tw_cos, E.tw_nsin,
+        hipLaunchKernelGGL(k_stft_fbank, dim3(grid), dim3(256), 0, c->stream, w.p, w.origin, w.n, d_prefix, d_counts, first_item, E.window, E.tw_cos, E.tw_nsin,
                            E.mel_w, E.mel_lo, E.mel_cnt, E.mel_off, E.mel_nnz, alist, d_rowoff, d_nnorm, (int)run_items, d_scratch, d_feats, sig_mode ? 1 : 0);
         KCHECK(c);
     }

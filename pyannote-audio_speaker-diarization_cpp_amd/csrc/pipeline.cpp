@@ -7,11 +7,11 @@
 #include <cstdlib>
 
 // a1 tail: input_wav[i] = sample * 1.0f / 32768.0 (sd.cpp:2948-2951); division by 2^15 is exact in f32
-__global__ void k_pcm_to_f32(const int16_t* __restrict__ pcm, float* __restrict__ wav, int64_t n)
+__global__ void k_pcm_to_f32(const int16_t* __restrict__ pcm, float* __restrict__ dst, int64_t n)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) wav[i] = (float)pcm[i] * (1.0f / 32768.0f);
-    else if (i < n + 512) wav[i] = 0.0f;          // padding: SincNet's 256-tap rows read 4 samples past the last window (zero weights, finite data)
+    if (i < n) dst[i] = (float)pcm[i] * (1.0f / 32768.0f);
+    else if (i < n + SD_WAV_PAD) dst[i] = 0.0f;   // padding: SincNet's 256-tap rows read 4 samples past the last window (zero weights, finite data)
 }
 // embeddings are widened to double before clustering (sd.cpp:2555)
 __global__ void k_f32_to_f64(const float* __restrict__ a, double* __restrict__ b, int64_t n)
@@ -42,8 +42,7 @@ extern "C" int sd_segment_dev(sd_ctx* c, const float* d_wav, int64_t n, float* d
     ENTER(c);
     if (!d_wav || !d_out || n <= 1) SD_FAIL(c, SD_ERR_ARG, "sd_segment_dev: bad argument");
     if (chunks != sd_num_chunks(n, nullptr)) SD_FAIL(c, SD_ERR_ARG, "sd_segment_dev: chunks must equal sd_num_chunks(n)");
-    c->wav_padded = false;                   // the caller's buffer: nothing is known about the bytes behind sample n
-    int rc = run_segment(c, d_wav, n, 0, chunks, d_out);
+    int rc = run_segment(c, DevWav{d_wav, n, 0, false}, 0, chunks, d_out);      // the caller's buffer: nothing is known about the bytes behind sample n
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SD_OK;
@@ -56,11 +55,10 @@ extern "C" int sd_segment(sd_ctx* c, const float* h_wav, int64_t n, float* h_out
     const int64_t nc = sd_num_chunks(n, nullptr);
     *chunks = nc;
     if (nc <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)n);
-    DTMP(c, dw, (n + 512) * sizeof(float)); DTMP(c, ds, nc * SD_FRAMES * 3 * sizeof(float));
+    DTMP(c, dw, (n + SD_WAV_PAD) * sizeof(float)); DTMP(c, ds, nc * SD_FRAMES * 3 * sizeof(float));
     HIPCHK(c, hipMemcpy(dw.p, h_wav, n * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemset((float*)dw.p + n, 0, 512 * sizeof(float)));
-    c->wav_padded = true;
-    int rc = run_segment(c, (const float*)dw.p, n, 0, nc, (float*)ds.p);
+    HIPCHK(c, hipMemset((float*)dw.p + n, 0, SD_WAV_PAD * sizeof(float)));
+    int rc = run_segment(c, DevWav{(const float*)dw.p, n, 0, true}, 0, nc, (float*)ds.p);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(h_out, ds.p, nc * SD_FRAMES * 3 * sizeof(float), hipMemcpyDeviceToHost));
@@ -74,15 +72,11 @@ extern "C" int sd_segment_chunks(sd_ctx* c, const float* h_chunks, int64_t rows,
     ENTER(c);
     if (!h_chunks || !h_out || rows <= 0 || T < 1 || T > SD_CHUNK) SD_FAIL(c, SD_ERR_ARG, "sd_segment_chunks: bad argument (rows >= 1, 1 <= T <= %d)", SD_CHUNK);
     // persistent workspaces, not per-call allocations: slide() calls infer once per batch of 32 chunks (225 times per hour of audio)
-    WS(c, float, dw, "rows_wav", rows * T + 512); WS(c, float, ds, "rows_seg", rows * SD_FRAMES * 3);
+    WS(c, float, dw, "rows_wav", rows * T + SD_WAV_PAD); WS(c, float, ds, "rows_seg", rows * SD_FRAMES * 3);
     HIPCHK(c, hipMemcpyAsync(dw, h_chunks, rows * T * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(dw + rows * T, 0, 512 * sizeof(float), c->stream));
-    const bool padded = c->wav_padded;
-    c->wav_padded = true;
+    HIPCHK(c, hipMemsetAsync(dw + rows * T, 0, SD_WAV_PAD * sizeof(float), c->stream));
     int fr = 0;
-    const int rc = run_segment_rows(c, dw, rows, (int)T, ds, &fr);
-    c->wav_padded = padded;
-    if (rc) return rc;
+    if (int rc = run_segment_rows(c, DevWav{dw, rows * T, 0, true}, (int)T, ds, &fr)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(h_out, ds, rows * SD_FRAMES * 3 * sizeof(float), hipMemcpyDeviceToHost));
     if (frames) *frames = fr;
@@ -243,13 +237,22 @@ extern "C" int sd_reconstruct(sd_ctx* c, const float* h_seg, const uint8_t* h_bi
 }
 
 // ------------------------------------------------------------------ sharded inference + finalize
-int pcm_to_wav(sd_ctx* c, const int16_t* d_pcm, int64_t n, float** d_wav)
+int pcm_to_wav(sd_ctx* c, const int16_t* d_pcm, int64_t n, DevWav* out)
 {
-    WS(c, float, w, "wav_f32", n + 512);
-    hipLaunchKernelGGL(k_pcm_to_f32, GRID1(n + 512), 0, c->stream, d_pcm, w, n);
+    WS(c, float, w, "wav_f32", n + SD_WAV_PAD);
+    hipLaunchKernelGGL(k_pcm_to_f32, GRID1(n + SD_WAV_PAD), 0, c->stream, d_pcm, w, n);
     KCHECK(c);
-    c->wav_padded = true;
-    *d_wav = w;
+    *out = DevWav{w, n, 0, true};
+    return SD_OK;
+}
+
+// host floats already divided by 32768 (sd.cpp:2948-2951)
+int f32_to_wav(sd_ctx* c, const float* h_wav, int64_t n, DevWav* out)
+{
+    WS(c, float, w, "wav_f32", n + SD_WAV_PAD);
+    HIPCHK(c, hipMemcpyAsync(w, h_wav, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(w + n, 0, SD_WAV_PAD * sizeof(float), c->stream));
+    *out = DevWav{w, n, 0, true};
     return SD_OK;
 }
 
@@ -265,7 +268,7 @@ static int plant_scores(sd_ctx* c, int64_t lo, int64_t hi, float* d_seg)
 
 // seg_done: d_seg already holds the scores of chunks [lo, hi) (stream.hip computes those of a small pending batch itself, on the kernels the whole
 // path takes for them); everything behind the segmentation step is the same
-int shard_infer_ex(sd_ctx* c, const float* d_wav, int64_t n, int64_t lo, int64_t hi, float* d_seg, float* d_emb, bool seg_done)
+int shard_infer(sd_ctx* c, const DevWav& w, int64_t lo, int64_t hi, float* d_seg, float* d_emb, bool seg_done)
 {
     const int64_t nc = hi - lo;
     c->stash.infer_items = nc > 0 ? nc * SD_SPEAKERS : 0;
@@ -273,7 +276,7 @@ int shard_infer_ex(sd_ctx* c, const float* d_wav, int64_t n, int64_t lo, int64_t
     if ((lo * SD_SPEAKERS) % SD_EMB_BATCH != 0) SD_FAIL(c, SD_ERR_ARG, "shard start %lld must be a multiple of 32 chunks", (long long)lo);
     int rc;
     const double t0 = now_ms();
-    if (!seg_done && (rc = run_segment(c, d_wav, n, lo, hi, d_seg))) return rc;
+    if (!seg_done && (rc = run_segment(c, w, lo, hi, d_seg))) return rc;
     if ((rc = plant_scores(c, lo, hi, d_seg))) return rc;
     const int64_t pa = std::max(lo, c->planted_lo), pb = std::min(hi, c->planted_lo + c->planted_n);
     WS(c, float, d_masks, "sh_masks", nc * 3 * SD_FRAMES);
@@ -281,7 +284,7 @@ int shard_infer_ex(sd_ctx* c, const float* d_wav, int64_t n, int64_t lo, int64_t
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const double t1 = now_ms();
     c->stage_ms[0] += t1 - t0;
-    if ((rc = run_embed(c, d_wav, n, d_masks, nc * 3, lo * 3, d_emb))) return rc;
+    if ((rc = run_embed(c, w, d_masks, nc * 3, lo * 3, d_emb))) return rc;
     if (pb > pa && c->planted_emb) {
         hipLaunchKernelGGL(k_plant_emb, dim3((unsigned)((pb - pa) * 3)), dim3(SD_EMB_DIM), 0, c->stream,
                            d_emb + (size_t)(pa - lo) * 3 * SD_EMB_DIM, c->planted_emb + (size_t)(pa - c->planted_lo) * 3 * SD_EMB_DIM);
@@ -290,11 +293,6 @@ int shard_infer_ex(sd_ctx* c, const float* d_wav, int64_t n, int64_t lo, int64_t
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->stage_ms[1] += now_ms() - t1;
     return SD_OK;
-}
-
-int shard_infer(sd_ctx* c, const float* d_wav, int64_t n, int64_t lo, int64_t hi, float* d_seg, float* d_emb)
-{
-    return shard_infer_ex(c, d_wav, n, lo, hi, d_seg, d_emb, false);
 }
 
 int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, std::vector<sd_turn>& v)
@@ -362,14 +360,11 @@ extern "C" int sd_shard_infer_dev(sd_ctx* c, const int16_t* d_pcm_shard, int64_t
     int64_t need_hi = (chunk_hi - 1) * SD_HOP + SD_CHUNK; if (need_hi > n) need_hi = n;
     if (chunk_hi > chunk_lo && (first_sample > need_lo || first_sample + shard_samples < need_hi))
         SD_FAIL(c, SD_ERR_ARG, "shard samples [%lld,%lld) do not cover chunks [%lld,%lld)", (long long)first_sample, (long long)(first_sample + shard_samples), (long long)chunk_lo, (long long)chunk_hi);
-    float* w = nullptr;
-    int rc0 = pcm_to_wav(c, d_pcm_shard, shard_samples, &w);
-    if (rc0) return rc0;
-    for (int i = 0; i < 4; ++i) c->stage_ms[i] = 0;
-    c->wav_origin = first_sample;                 // kernels index the recording with absolute sample positions
-    const int rc = shard_infer(c, w, n, chunk_lo, chunk_hi, d_seg, d_emb);
-    c->wav_origin = 0;
-    return rc;
+    DevWav w;
+    if (int rc = pcm_to_wav(c, d_pcm_shard, shard_samples, &w)) return rc;
+    clear_stage_ms(c);
+    w.n = n; w.origin = first_sample;             // a slice of the recording: kernels index it with absolute sample positions
+    return shard_infer(c, w, chunk_lo, chunk_hi, d_seg, d_emb);
 }
 
 extern "C" int sd_finalize_dev(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, sd_turn** turns, int64_t* n_turns)
@@ -392,85 +387,79 @@ extern "C" int sd_set_planted(sd_ctx* c, const float* d_scores, const float* d_e
     return SD_OK;
 }
 
-// The whole path behind the entries that hold the padded f32 waveform on the device (sd_diarize_dev, sd_diarize_f32, the resample branch of
-// sd_diarize_wav): chunks, both networks, finalize -> turns; stage_ms[3] = the time since t0, the entry's own start
-static int diarize_wav_dev(sd_ctx* c, const float* d_wav, int64_t n, double t0, std::vector<sd_turn>& v)
+// ------------------------------------------------------------------ the whole-path entries: sd_diarize* and sd_activity*
+// Each entry is its own argument checks around the driver of its source form (device pcm, host pcm, host f32, wav file); a driver brings the
+// samples into a padded DevWav and hands it to the family's tail -- diarize_wav_dev, or activity_wav_dev (below) of a kind -- with t0, the
+// entry's own start: the tail sets stage_ms[3] = the time since then
+typedef std::function<int(sd_ctx*, const DevWav&, double, std::vector<sd_turn>&)> WavTail;
+
+// chunks, both networks, finalize -> turns
+static int diarize_wav_dev(sd_ctx* c, const DevWav& w, double t0, std::vector<sd_turn>& v)
 {
-    const int64_t chunks = sd_num_chunks(n, nullptr);
-    if (chunks <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)n);
+    const int64_t chunks = sd_num_chunks(w.n, nullptr);
+    if (chunks <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)w.n);
     WS(c, float, d_seg, "dz_seg", chunks * SD_FRAMES * 3);
     WS(c, float, d_emb, "dz_emb", chunks * 3 * SD_EMB_DIM);
     int rc;
-    if ((rc = shard_infer(c, d_wav, n, 0, chunks, d_seg, d_emb))) return rc;
-    if ((rc = finalize(c, d_seg, d_emb, chunks, n, v))) return rc;
+    if ((rc = shard_infer(c, w, 0, chunks, d_seg, d_emb))) return rc;
+    if ((rc = finalize(c, d_seg, d_emb, chunks, w.n, v))) return rc;
     c->stage_ms[3] = now_ms() - t0;
-    return SD_OK;
-}
-
-extern "C" int sd_diarize_dev(sd_ctx* c, const int16_t* d_pcm, int64_t n, sd_turn** turns, int64_t* n_turns)
-{
-    ENTER(c);
-    if (!d_pcm || !turns || !n_turns) SD_FAIL(c, SD_ERR_ARG, "sd_diarize_dev: bad argument");
-    if (n <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)n);      // this entry's only guard on n: nothing is uploaded from a count that is not one
-    const double t0 = now_ms();
-    for (int i = 0; i < 4; ++i) c->stage_ms[i] = 0;
-    float* d_wav = nullptr;
-    int rc = pcm_to_wav(c, d_pcm, n, &d_wav);
-    if (rc) return rc;
-    std::vector<sd_turn> v;
-    if ((rc = diarize_wav_dev(c, d_wav, n, t0, v))) return rc;
     if (getenv("SD_TRACE_WS")) {
         fprintf(stderr, "[sdhip] job %.1f ms (segmentation %.1f, embedding %.1f, finalize %.1f); workspace allocations so far in this process: %zu hipMalloc, %.2f GB, %.1f ms (+ %.1f ms hipFree)\n",
                 c->stage_ms[3], c->stage_ms[0], c->stage_ms[1], c->stage_ms[2], g_ws_allocs.load(), (double)g_ws_alloc_bytes.load() / 1e9, (double)g_ws_alloc_us.load() * 1e-3, (double)g_ws_free_us.load() * 1e-3);
         for (const auto& kv : c->ws) if (kv.second.cap >= ((size_t)256 << 20)) fprintf(stderr, "[sdhip]   %-16s %8.2f GB\n", kv.first.c_str(), (double)kv.second.cap / 1e9);
     }
+    return SD_OK;
+}
+
+static int run_tail(sd_ctx* c, const DevWav& w, double t0, const WavTail& tail, sd_turn** turns, int64_t* n_turns)
+{
+    std::vector<sd_turn> v;
+    if (int rc = tail(c, w, t0, v)) return rc;
     return turns_out(c, v, turns, n_turns);
 }
 
-extern "C" int sd_diarize(sd_ctx* c, const int16_t* h_pcm, int64_t n, sd_turn** turns, int64_t* n_turns)
+// device pcm.  n <= 0 is this form's only guard on n: nothing is uploaded from a count that is not one
+static int whole_dev(sd_ctx* c, const int16_t* d_pcm, int64_t n, const WavTail& tail, sd_turn** turns, int64_t* n_turns)
 {
-    ENTER(c);
-    if (!h_pcm || n <= 0) SD_FAIL(c, SD_ERR_ARG, "sd_diarize: bad argument");
+    if (n <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)n);
+    const double t0 = now_ms();
+    clear_stage_ms(c);
+    DevWav w;
+    if (int rc = pcm_to_wav(c, d_pcm, n, &w)) return rc;
+    return run_tail(c, w, t0, tail, turns, n_turns);
+}
+
+// host pcm: uploaded, then the family's device-pcm entry with its own checks
+static int whole_pcm(sd_ctx* c, const int16_t* h_pcm, int64_t n, const char* who, const std::function<int(const int16_t*)>& dev_entry)
+{
+    if (!h_pcm || n <= 0) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument", who);
     DTMP(c, dp, n * sizeof(int16_t));
     HIPCHK(c, hipMemcpy(dp.p, h_pcm, n * sizeof(int16_t), hipMemcpyHostToDevice));
-    return sd_diarize_dev(c, (const int16_t*)dp.p, n, turns, n_turns);
+    return dev_entry((const int16_t*)dp.p);
 }
 
-// ------------------------------------------------------------------ float-sample entry (8 / 32-bit wavs)
-// `wav` holds samples already divided by 32768 exactly as the reference's loop does for every bit depth (sd.cpp:2948-2951)
-extern "C" int sd_diarize_f32(sd_ctx* c, const float* h_wav, int64_t n, sd_turn** turns, int64_t* n_turns)
+// host floats (8 / 32-bit wavs): samples already divided by 32768 exactly as the reference's loop does for every bit depth (sd.cpp:2948-2951)
+static int whole_f32(sd_ctx* c, const float* h_wav, int64_t n, const WavTail& tail, sd_turn** turns, int64_t* n_turns)
 {
-    ENTER(c);
-    if (!h_wav || n <= 0 || !turns || !n_turns) SD_FAIL(c, SD_ERR_ARG, "sd_diarize_f32: bad argument");
     const double t0 = now_ms();
-    for (int i = 0; i < 4; ++i) c->stage_ms[i] = 0;
-    WS(c, float, d_wav, "wav_f32", n + 512);
-    HIPCHK(c, hipMemcpyAsync(d_wav, h_wav, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_wav + n, 0, 512 * sizeof(float), c->stream));
-    c->wav_padded = true;
-    std::vector<sd_turn> v;
-    if (int rc = diarize_wav_dev(c, d_wav, n, t0, v)) return rc;
-    return turns_out(c, v, turns, n_turns);
+    clear_stage_ms(c);
+    DevWav w;
+    if (int rc = f32_to_wav(c, h_wav, n, &w)) return rc;
+    return run_tail(c, w, t0, tail, turns, n_turns);
 }
 
-// ------------------------------------------------------------------ wav file entry: reader + rate / channel handling + the path
-int resample_dev(sd_ctx* c, const float* d_in, int64_t n, int32_t in_sr, int32_t out_sr, float* d_out, int64_t n_out);   // resample.hip
-
-// what a wav-file entry runs once the samples are read, in the three forms the reader hands them over: 16-bit samples, host floats already
-// divided by 32768, or -- behind the resampler -- the padded f32 waveform on the device (t0 = the entry's own start)
-struct WavJob {
-    std::function<int(const int16_t*, int64_t)> pcm;
-    std::function<int(const float*, int64_t)> f32;
-    std::function<int(const float*, int64_t, double)> dev;
-};
-
-static int run_wav_file(sd_ctx* c, const char* path, int flags, const WavJob& job)
+// wav file: reader + rate / channel handling, then the family's host-pcm entry, its host-f32 entry or -- behind the resampler -- its tail
+typedef std::function<int(const int16_t*, int64_t)> PcmEntry;
+typedef std::function<int(const float*, int64_t)> F32Entry;
+static int whole_wav(sd_ctx* c, const char* path, int flags, const PcmEntry& pcm_entry, const F32Entry& f32_entry, const WavTail& tail, sd_turn** turns, int64_t* n_turns)
 {
+    *turns = nullptr; *n_turns = 0;
     {   // the common case -- 16-bit, 16 kHz, nothing to mix -- stays int16 up to the GPU (k_pcm_to_f32 does the reference's / 32768 there)
         int16_t* pcm = nullptr; int64_t np = 0; int32_t sr16 = 0, ch16 = 0;
         if (sd_read_wav(path, &pcm, &np, &sr16, &ch16) == SD_OK) {
             struct FreePcm { int16_t* p; ~FreePcm() { sd_free_pcm(p); } } g{pcm};
-            if ((sr16 == 16000 || (flags & SD_WAV_ASSUME_16K)) && !(ch16 > 1 && (flags & SD_WAV_DOWNMIX))) return job.pcm(pcm, np);
+            if ((sr16 == 16000 || (flags & SD_WAV_ASSUME_16K)) && !(ch16 > 1 && (flags & SD_WAV_DOWNMIX))) return pcm_entry(pcm, np);
         }
     }
     float* wav = nullptr; int64_t n = 0; int32_t sr = 0, ch = 0, bits = 0;
@@ -484,7 +473,7 @@ static int run_wav_file(sd_ctx* c, const char* path, int flags, const WavJob& jo
             wav[i] = s / (float)ch;
         }
     }
-    if (sr == 16000 || (flags & SD_WAV_ASSUME_16K)) return job.f32(wav, n);      // ASSUME_16K: the reference's behaviour (sd.cpp:2940-2942)
+    if (sr == 16000 || (flags & SD_WAV_ASSUME_16K)) return f32_entry(wav, n);      // ASSUME_16K: the reference's behaviour (sd.cpp:2940-2942)
     if (!(flags & SD_WAV_RESAMPLE))
         SD_FAIL(c, SD_ERR_ARG, "%s: sample rate %d Hz; the pipeline needs 16000 (README.md:37 of the reference, which would process the file as if it "
                                "were 16 kHz: SD_WAV_ASSUME_16K / --assume-16k does the same) -- pass SD_WAV_RESAMPLE / --resample", path, sr);
@@ -492,29 +481,41 @@ static int run_wav_file(sd_ctx* c, const char* path, int flags, const WavJob& jo
     const double t0 = now_ms();
     const int64_t no = sd_resample_len(n, sr, 16000);
     if (no <= 0) SD_FAIL(c, SD_ERR_SHORT, "%s: %lld samples at %d Hz give no 16 kHz sample", path, (long long)n, sr);
-    for (int i = 0; i < 4; ++i) c->stage_ms[i] = 0;
+    clear_stage_ms(c);
     WS(c, float, d_in, "rs_in", n);
-    WS(c, float, d_wav, "wav_f32", no + 512);
+    WS(c, float, d_wav, "wav_f32", no + SD_WAV_PAD);
     HIPCHK(c, hipMemcpyAsync(d_in, wav, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_wav + no, 0, 512 * sizeof(float), c->stream));
+    HIPCHK(c, hipMemsetAsync(d_wav + no, 0, SD_WAV_PAD * sizeof(float), c->stream));
     if (int rc = resample_dev(c, d_in, n, sr, 16000, d_wav, no)) return rc;
-    c->wav_padded = true;
-    return job.dev(d_wav, no, t0);
+    return run_tail(c, DevWav{d_wav, no, 0, true}, t0, tail, turns, n_turns);
+}
+
+extern "C" int sd_diarize_dev(sd_ctx* c, const int16_t* d_pcm, int64_t n, sd_turn** turns, int64_t* n_turns)
+{
+    ENTER(c);
+    if (!d_pcm || !turns || !n_turns) SD_FAIL(c, SD_ERR_ARG, "sd_diarize_dev: bad argument");
+    return whole_dev(c, d_pcm, n, diarize_wav_dev, turns, n_turns);
+}
+
+extern "C" int sd_diarize(sd_ctx* c, const int16_t* h_pcm, int64_t n, sd_turn** turns, int64_t* n_turns)
+{
+    ENTER(c);
+    return whole_pcm(c, h_pcm, n, "sd_diarize", [&](const int16_t* d_pcm) { return sd_diarize_dev(c, d_pcm, n, turns, n_turns); });
+}
+
+extern "C" int sd_diarize_f32(sd_ctx* c, const float* h_wav, int64_t n, sd_turn** turns, int64_t* n_turns)
+{
+    ENTER(c);
+    if (!h_wav || n <= 0 || !turns || !n_turns) SD_FAIL(c, SD_ERR_ARG, "sd_diarize_f32: bad argument");
+    return whole_f32(c, h_wav, n, diarize_wav_dev, turns, n_turns);
 }
 
 extern "C" int sd_diarize_wav(sd_ctx* c, const char* path, int flags, sd_turn** turns, int64_t* n_turns)
 {
     ENTER(c);
     if (!path || !turns || !n_turns || (flags & ~(SD_WAV_RESAMPLE | SD_WAV_DOWNMIX | SD_WAV_ASSUME_16K))) SD_FAIL(c, SD_ERR_ARG, "sd_diarize_wav: bad argument");
-    *turns = nullptr; *n_turns = 0;
-    return run_wav_file(c, path, flags, {
-        [&](const int16_t* pcm, int64_t n) { return sd_diarize(c, pcm, n, turns, n_turns); },
-        [&](const float* wav, int64_t n) { return sd_diarize_f32(c, wav, n, turns, n_turns); },
-        [&](const float* d_wav, int64_t n, double t0) {
-            std::vector<sd_turn> v;
-            if (int rc = diarize_wav_dev(c, d_wav, n, t0, v)) return rc;
-            return turns_out(c, v, turns, n_turns);
-        }});
+    return whole_wav(c, path, flags, [&](const int16_t* pcm, int64_t n) { return sd_diarize(c, pcm, n, turns, n_turns); },
+                     [&](const float* wav, int64_t n) { return sd_diarize_f32(c, wav, n, turns, n_turns); }, diarize_wav_dev, turns, n_turns);
 }
 
 // ------------------------------------------------------------------ speech / overlapped-speech regions (activity.hip)
@@ -550,21 +551,21 @@ extern "C" int sd_activity_regions(sd_ctx* c, const double* h_scores, int64_t n_
     return turns_out(c, v, turns, n_turns);
 }
 
-// The whole path behind the sd_activity* entries that hold the padded f32 waveform on the device: chunks, PyanNet, the activity stage -> turns
-// labelled `kind`.  Nothing of the embedding, clustering or reconstruction stages runs.  stage_ms[0] = segmentation, [3] = the time since t0
-static int activity_wav_dev(sd_ctx* c, const float* d_wav, int64_t n, int kind, double t0, std::vector<sd_turn>& v)
+// The tail of the sd_activity* entries: chunks, PyanNet, the activity stage -> turns labelled `kind`.  Nothing of the embedding, clustering or
+// reconstruction stages runs.  stage_ms[0] = segmentation, [3] = the time since t0
+static int activity_wav_dev(sd_ctx* c, const DevWav& w, int kind, double t0, std::vector<sd_turn>& v)
 {
     c->last_activity.clear();
-    const int64_t chunks = sd_num_chunks(n, nullptr);
-    if (chunks <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)n);
+    const int64_t chunks = sd_num_chunks(w.n, nullptr);
+    if (chunks <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)w.n);
     WS(c, float, d_seg, "dz_seg", chunks * SD_FRAMES * 3);
     int rc;
     const double t1 = now_ms();
-    if ((rc = run_segment(c, d_wav, n, 0, chunks, d_seg))) return rc;
+    if ((rc = run_segment(c, w, 0, chunks, d_seg))) return rc;
     if ((rc = plant_scores(c, 0, chunks, d_seg))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->stage_ms[0] += now_ms() - t1;
-    const int64_t nf = activity_frames_host(chunks), rows = activity_rows_host(nf, n);
+    const int64_t nf = activity_frames_host(chunks), rows = activity_rows_host(nf, w.n);
     WS(c, double, d_scores, "act_scores", nf);
     if ((rc = run_activity_scores(c, d_seg, chunks, kind, d_scores, nf))) return rc;
     c->last_activity.resize((size_t)rows);
@@ -572,6 +573,10 @@ static int activity_wav_dev(sd_ctx* c, const float* d_wav, int64_t n, int kind, 
     if ((rc = run_activity_regions(c, d_scores, rows, kind, v))) return rc;      // (synchronises the stream)
     c->stage_ms[3] = now_ms() - t0;
     return SD_OK;
+}
+static WavTail activity_tail(int kind)
+{
+    return [kind](sd_ctx* c, const DevWav& w, double t0, std::vector<sd_turn>& v) { return activity_wav_dev(c, w, kind, t0, v); };
 }
 
 static int check_activity_args(sd_ctx* c, const void* in, int kind, sd_turn** turns, int64_t* n_turns, const char* who)
@@ -585,24 +590,13 @@ extern "C" int sd_activity_dev(sd_ctx* c, const int16_t* d_pcm, int64_t n, int k
 {
     ENTER(c);
     if (int rc = check_activity_args(c, d_pcm, kind, turns, n_turns, "sd_activity_dev")) return rc;
-    if (n <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)n);
-    const double t0 = now_ms();
-    for (int i = 0; i < 4; ++i) c->stage_ms[i] = 0;
-    float* d_wav = nullptr;
-    int rc = pcm_to_wav(c, d_pcm, n, &d_wav);
-    if (rc) return rc;
-    std::vector<sd_turn> v;
-    if ((rc = activity_wav_dev(c, d_wav, n, kind, t0, v))) return rc;
-    return turns_out(c, v, turns, n_turns);
+    return whole_dev(c, d_pcm, n, activity_tail(kind), turns, n_turns);
 }
 
 extern "C" int sd_activity(sd_ctx* c, const int16_t* h_pcm, int64_t n, int kind, sd_turn** turns, int64_t* n_turns)
 {
     ENTER(c);
-    if (!h_pcm || n <= 0) SD_FAIL(c, SD_ERR_ARG, "sd_activity: bad argument");
-    DTMP(c, dp, n * sizeof(int16_t));
-    HIPCHK(c, hipMemcpy(dp.p, h_pcm, n * sizeof(int16_t), hipMemcpyHostToDevice));
-    return sd_activity_dev(c, (const int16_t*)dp.p, n, kind, turns, n_turns);
+    return whole_pcm(c, h_pcm, n, "sd_activity", [&](const int16_t* d_pcm) { return sd_activity_dev(c, d_pcm, n, kind, turns, n_turns); });
 }
 
 extern "C" int sd_activity_f32(sd_ctx* c, const float* h_wav, int64_t n, int kind, sd_turn** turns, int64_t* n_turns)
@@ -610,15 +604,7 @@ extern "C" int sd_activity_f32(sd_ctx* c, const float* h_wav, int64_t n, int kin
     ENTER(c);
     if (int rc = check_activity_args(c, h_wav, kind, turns, n_turns, "sd_activity_f32")) return rc;
     if (n <= 0) SD_FAIL(c, SD_ERR_ARG, "sd_activity_f32: bad argument");
-    const double t0 = now_ms();
-    for (int i = 0; i < 4; ++i) c->stage_ms[i] = 0;
-    WS(c, float, d_wav, "wav_f32", n + 512);
-    HIPCHK(c, hipMemcpyAsync(d_wav, h_wav, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_wav + n, 0, 512 * sizeof(float), c->stream));
-    c->wav_padded = true;
-    std::vector<sd_turn> v;
-    if (int rc = activity_wav_dev(c, d_wav, n, kind, t0, v)) return rc;
-    return turns_out(c, v, turns, n_turns);
+    return whole_f32(c, h_wav, n, activity_tail(kind), turns, n_turns);
 }
 
 extern "C" int sd_activity_wav(sd_ctx* c, const char* path, int flags, int kind, sd_turn** turns, int64_t* n_turns)
@@ -626,13 +612,6 @@ extern "C" int sd_activity_wav(sd_ctx* c, const char* path, int flags, int kind,
     ENTER(c);
     if (int rc = check_activity_args(c, path, kind, turns, n_turns, "sd_activity_wav")) return rc;
     if (flags & ~(SD_WAV_RESAMPLE | SD_WAV_DOWNMIX | SD_WAV_ASSUME_16K)) SD_FAIL(c, SD_ERR_ARG, "sd_activity_wav: bad argument");
-    *turns = nullptr; *n_turns = 0;
-    return run_wav_file(c, path, flags, {
-        [&](const int16_t* pcm, int64_t n) { return sd_activity(c, pcm, n, kind, turns, n_turns); },
-        [&](const float* wav, int64_t n) { return sd_activity_f32(c, wav, n, kind, turns, n_turns); },
-        [&](const float* d_wav, int64_t n, double t0) {
-            std::vector<sd_turn> v;
-            if (int rc = activity_wav_dev(c, d_wav, n, kind, t0, v)) return rc;
-            return turns_out(c, v, turns, n_turns);
-        }});
+    return whole_wav(c, path, flags, [&](const int16_t* pcm, int64_t n) { return sd_activity(c, pcm, n, kind, turns, n_turns); },
+                     [&](const float* wav, int64_t n) { return sd_activity_f32(c, wav, n, kind, turns, n_turns); }, activity_tail(kind), turns, n_turns);
 }

@@ -443,8 +443,8 @@ static ConvArgs gemm_args(const ConvLayer& L, const float* X, int x_ld, float* Y
 }
 
 // one batch of `cnt` chunks that all have L samples
-// hop = samples between the starts of consecutive chunks in d_wav: SD_HOP for the sliding window, the row length for separate rows
-static int seg_batch(sd_ctx* c, const float* d_wav, int64_t n, int64_t first_chunk, int64_t cnt, int L, float* d_seg, int64_t hop = SD_HOP)
+// hop = samples between the starts of consecutive chunks in the waveform: SD_HOP for the sliding window, the row length for separate rows
+static int seg_batch(sd_ctx* c, const DevWav& w, int64_t first_chunk, int64_t cnt, int L, float* d_seg, int64_t hop = SD_HOP)
 {
     const SegWeights& S = c->sw;
     hipStream_t st = c->stream;
@@ -471,7 +471,7 @@ static int seg_batch(sd_ctx* c, const float* d_wav, int64_t n, int64_t first_chu
     WS(c, float, y0, "sg_y0", CB * F * 128);
     WS(c, float, y1, "sg_y1", CB * F * 128);
     int rc;
-    if (c->seg_shared_conv0 && c->wav_padded && hop == SD_HOP && S.conv0.Cout == 80 && S.conv0_wsum) {
+    if (c->seg_shared_conv0 && w.padded && hop == SD_HOP && S.conv0.Cout == 80 && S.conv0_wsum) {
         // conv0 once over the batch's stretch of the waveform: rows 0 .. 800 (CB - 1) + L0 (chunk ck's frames start at row 800 ck;
         // the last window ends 4 samples behind the last chunk, inside the waveform's padding), then the chunk's normalisation as an
         // affine map inside the pooling kernel.  10x fewer FLOPs and 10x less output than one conv per chunk.
@@ -479,18 +479,18 @@ static int seg_batch(sd_ctx* c, const float* d_wav, int64_t n, int64_t first_chu
         const int64_t MY = (int64_t)hop_rows * (CB - 1) + L0;
         WS(c, float2, cst, "sg_cst", CB);
         WS(c, float, c0s, "sg_c0s", MY * 80);
-        if ((rc = launch_chunk_stats(c, d_wav, c->wav_origin, first_chunk, L, CB, S.wn_w, S.wn_b, cst))) return rc;
+        if ((rc = launch_chunk_stats(c, w.p, w.origin, first_chunk, L, CB, S.wn_w, S.wn_b, cst))) return rc;
         ConvArgs a; memset(&a, 0, sizeof(a));
-        a.X = d_wav + (first_chunk * (int64_t)SD_HOP - c->wav_origin); a.x_ld = 10; a.W = S.conv0.W; a.Y = c0s; a.y_ld = 80;
+        a.X = w.p + (first_chunk * (int64_t)SD_HOP - w.origin); a.x_ld = 10; a.W = S.conv0.W; a.Y = c0s; a.y_ld = 80;
         a.M = (int)MY; a.TpIn = a.TpOut = a.Tin = a.T = (int)MY;
         a.Cin = 256; a.cin_real = 251; a.Cout = 80; a.KT = 1; a.dil = 1; a.pad_mode = 1;
         if ((rc = launch_conv_narrow(c, a, "sinc0")) == 1) rc = launch_conv_gemm(c, a, "sinc0");
         if (rc) return rc;
         if ((rc = launch_pool_norm(c, 0, c0s, CB, L0, S.in_w[0], S.in_b[0], p0, cst, S.conv0_wsum, hop_rows))) return rc;
     } else {
-        WS(c, float, xn, "sg_xn", CB * SD_CHUNK + 512);
+        WS(c, float, xn, "sg_xn", CB * SD_CHUNK + SD_WAV_PAD);
         WS(c, float, c0, "sg_c0", CB * L0 * 80);
-        if ((rc = launch_chunk_norm(c, d_wav, c->wav_origin, first_chunk, hop, L, CB, S.wn_w, S.wn_b, xn))) return rc;
+        if ((rc = launch_chunk_norm(c, w.p, w.origin, first_chunk, hop, L, CB, S.wn_w, S.wn_b, xn))) return rc;
         {   // conv0: rows = output positions, row r reads xn[10 r .. 10 r + 256)
             ConvArgs a; memset(&a, 0, sizeof(a));
             a.X = xn; a.x_ld = 10; a.W = S.conv0.W; a.Y = c0; a.y_ld = 80;
@@ -554,12 +554,12 @@ static int seg_batch(sd_ctx* c, const float* d_wav, int64_t n, int64_t first_chu
     return launch_classifier(c, y1, S.cls_w, S.cls_b, d_seg, CB, F);
 }
 
-// chunks [chunk_lo, chunk_hi) of the n-sample waveform -> d_seg [hi-lo][293][3]
-int run_segment(sd_ctx* c, const float* d_wav, int64_t n, int64_t chunk_lo, int64_t chunk_hi, float* d_seg)
+// chunks [chunk_lo, chunk_hi) of the w.n-sample recording -> d_seg [hi-lo][293][3]
+int run_segment(sd_ctx* c, const DevWav& w, int64_t chunk_lo, int64_t chunk_hi, float* d_seg)
 {
     if (!c->sw.loaded) SD_FAIL(c, SD_ERR_MODEL, "segmentation model not loaded");
     int64_t last_len = 0;
-    const int64_t total = sd_num_chunks(n, &last_len);
+    const int64_t total = sd_num_chunks(w.n, &last_len);
     if (chunk_lo < 0 || chunk_hi > total || chunk_lo > chunk_hi) SD_FAIL(c, SD_ERR_ARG, "chunk range [%lld,%lld) outside [0,%lld)", (long long)chunk_lo, (long long)chunk_hi, (long long)total);
     // chunks < total-1 are full; the final ("last chunk" branch, sd.cpp:1457-1480) one may be shorter
     int64_t full_hi = chunk_hi;
@@ -570,17 +570,17 @@ int run_segment(sd_ctx* c, const float* d_wav, int64_t n, int64_t chunk_lo, int6
     int rc;
     for (int64_t k = chunk_lo; k < full_hi; k += cb) {
         const int64_t cnt = (full_hi - k < cb) ? full_hi - k : cb;
-        if ((rc = seg_batch(c, d_wav, n, k, cnt, SD_CHUNK, d_seg + (size_t)(k - chunk_lo) * SD_FRAMES * 3))) return rc;
+        if ((rc = seg_batch(c, w, k, cnt, SD_CHUNK, d_seg + (size_t)(k - chunk_lo) * SD_FRAMES * 3))) return rc;
     }
     if (has_short_tail && chunk_lo <= total - 1)
-        if ((rc = seg_batch(c, d_wav, n, total - 1, 1, (int)last_len, d_seg + (size_t)(total - 1 - chunk_lo) * SD_FRAMES * 3))) return rc;
+        if ((rc = seg_batch(c, w, total - 1, 1, (int)last_len, d_seg + (size_t)(total - 1 - chunk_lo) * SD_FRAMES * 3))) return rc;
     return SD_OK;
 }
 
-// SegmentModel::infer as the reference declares it (sd.cpp:1352-1404): `rows` separate waveforms of T samples each, [rows][T] -> [rows][293][3]
+// SegmentModel::infer as the reference declares it (sd.cpp:1352-1404): w holds rows = w.n / T separate waveforms of T samples each, [rows][T] -> [rows][293][3]
 // (frames beyond the *frames the network yields for T samples are zero, as slide() pads them, sd.cpp:1473-1479).  Same kernels as run_segment
-// with the chunk stride T instead of SD_HOP (the shared-conv0 shortcut needs overlapping chunks and is off).
-int run_segment_rows(sd_ctx* c, const float* d_rows, int64_t rows, int T, float* d_seg, int* frames)
+// with the chunk stride T instead of SD_HOP (the shared-conv0 shortcut needs overlapping chunks: T = SD_HOP and padded rows).
+int run_segment_rows(sd_ctx* c, const DevWav& w, int T, float* d_seg, int* frames)
 {
     if (!c->sw.loaded) SD_FAIL(c, SD_ERR_MODEL, "segmentation model not loaded");
     if (T < 1 || T > SD_CHUNK) SD_FAIL(c, SD_ERR_ARG, "sd_segment_chunks: T = %d samples per row (1 .. %d)", T, SD_CHUNK);
@@ -589,11 +589,9 @@ int run_segment_rows(sd_ctx* c, const float* d_rows, int64_t rows, int T, float*
     if (frames) *frames = (L0 <= 0 || P0 <= 0 || L1 <= 0 || P1 <= 0 || L2 <= 0 || P2 <= 0) ? 0 : (P2 > SD_FRAMES ? SD_FRAMES : P2);
     int64_t cb = c->seg_batch_chunks;
     if (cb < 1) cb = 1;
-    const int64_t origin = c->wav_origin;
-    c->wav_origin = 0;
+    const int64_t rows = w.n / T;
     int rc = SD_OK;
     for (int64_t k = 0; k < rows && rc == SD_OK; k += cb)
-        rc = seg_batch(c, d_rows, rows * (int64_t)T, k, rows - k < cb ? rows - k : cb, T, d_seg + (size_t)k * SD_FRAMES * 3, T);
-    c->wav_origin = origin;
+        rc = seg_batch(c, w, k, rows - k < cb ? rows - k : cb, T, d_seg + (size_t)k * SD_FRAMES * 3, T);
     return rc;
 }

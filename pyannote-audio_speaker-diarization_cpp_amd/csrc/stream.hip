@@ -2,22 +2,13 @@
 // (sd.cpp:2937-3234) again on everything heard so far: a stream keeps the scores and embeddings of the chunks that can never change
 // again (stream_book.h: blocks of 32 chunks whose every chunk ends in front of the last sample), the audio behind them as f32 on the
 // device, and at sd_stream_turns infers only the chunks behind the sealed part before the usual finalize.  The networks run through
-// shard_infer on sub-ranges (pipeline.cpp); the device code here is the tail: append and compaction.
+// shard_infer on sub-ranges (pipeline.cpp); the device code here is the tail's compaction (16-bit pushes are appended by k_pcm_to_f32).
 #include "common.h"
 #include "stream_book.h"
 #include <algorithm>
 
-int shard_infer_ex(sd_ctx* c, const float* d_wav, int64_t n, int64_t lo, int64_t hi, float* d_seg, float* d_emb, bool seg_done);     // pipeline.cpp
-int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, std::vector<sd_turn>& v);
-int turns_out(sd_ctx* c, const std::vector<sd_turn>& v, sd_turn** turns, int64_t* n_turns);
+static_assert(SD_TAIL_PAD == SD_WAV_PAD, "the tail's padding is what DevWav::padded promises");
 
-// m appended 16-bit samples -> f32 with k_pcm_to_f32's arithmetic (pipeline.cpp; sd.cpp:2948-2951), and the zeros behind them
-__global__ void k_tail_append_pcm(const int16_t* __restrict__ pcm, float* __restrict__ dst, int64_t m)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) dst[i] = (float)pcm[i] * (1.0f / 32768.0f);
-    else if (i < m + SD_TAIL_PAD) dst[i] = 0.0f;
-}
 // compaction into the second buffer: dst[0, len) = src[0, len), zeros behind; four floats per thread (src sits a multiple of 8000 floats
 // behind its allocation's start, dst at the start of its own: both 16-byte aligned)
 __global__ void k_tail_move(const float* __restrict__ src, float* __restrict__ dst, int64_t len)
@@ -69,7 +60,7 @@ enum { PUSH_PCM_HOST, PUSH_PCM_DEV, PUSH_F32_HOST };
 // a scratch waveform with the pending full chunks' audio and zeros behind it, as a recording just long enough for 14 full chunks from lo on.  A row's
 // bits depend on its own chunk and on the kernels alone, so the real rows are the whole path's; the padding rows are thrown away.  The short last
 // chunk is a batch of one in both paths.
-int segment_pending(sd_stream* s, int64_t lo, int64_t hi)
+int segment_pending(sd_stream* s, const DevWav& tail, int64_t lo, int64_t hi)
 {
     sd_ctx* c = s->c;
     const StreamBook& b = s->b;
@@ -80,7 +71,7 @@ int segment_pending(sd_stream* s, int64_t lo, int64_t hi)
     const int64_t full_hi = short_tail ? hi - 1 : hi, mine = full_hi - lo;
     const int64_t cb = c->seg_batch_chunks;
     const int64_t whole = (cb >= SD_SEAL_CHUNKS && cb % SD_SEAL_CHUNKS == 0) ? full_hi - cb * (lo / cb) : mine;      // (a tuning value of seg_batch_chunks that cuts blocks: no promise)
-    if (mine <= 0 || mine > SD_SEG_SKINNY_CHUNKS || whole <= SD_SEG_SKINNY_CHUNKS) return run_segment(c, b.tail_now(), b.n, lo, hi, d_seg);
+    if (mine <= 0 || mine > SD_SEG_SKINNY_CHUNKS || whole <= SD_SEG_SKINNY_CHUNKS) return run_segment(c, tail, lo, hi, d_seg);
     const int64_t pad_hi = lo + SD_SEG_SKINNY_CHUNKS + 1;
     const int64_t n_pad = (pad_hi - 1) * SD_HOP + SD_CHUNK + 1;                      // the shortest recording whose chunks [lo, pad_hi) are all full
     const int64_t have = (full_hi - 1) * SD_HOP + SD_CHUNK - lo * SD_HOP;            // samples of the pending full chunks: all in the tail
@@ -90,9 +81,9 @@ int segment_pending(sd_stream* s, int64_t lo, int64_t hi)
     HIPCHK(c, hipMemcpyAsync(w, b.tail_now(), (size_t)have * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(w + have, 0, (size_t)(len + SD_TAIL_PAD - have) * sizeof(float), c->stream));
     int rc;
-    if ((rc = run_segment(c, w, n_pad, lo, pad_hi, sg))) return rc;
+    if ((rc = run_segment(c, DevWav{w, n_pad, lo * SD_HOP, true}, lo, pad_hi, sg))) return rc;
     HIPCHK(c, hipMemcpyAsync(d_seg, sg, (size_t)(mine * SD_SEG_ROW) * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    if (short_tail) return run_segment(c, b.tail_now(), b.n, hi - 1, hi, d_seg + mine * SD_SEG_ROW);
+    if (short_tail) return run_segment(c, tail, hi - 1, hi, d_seg + mine * SD_SEG_ROW);
     return SD_OK;
 }
 
@@ -101,19 +92,15 @@ int infer_rows(sd_stream* s, int64_t lo, int64_t hi, bool pending)
 {
     sd_ctx* c = s->c;
     StreamBook& b = s->b;
-    const bool padded = c->wav_padded;
-    c->wav_origin = b.sealed * SD_HOP;            // kernels index the recording with absolute sample positions
-    c->wav_padded = true;                         // every append and every compaction leaves SD_TAIL_PAD zeros behind sample n
-    int rc = SD_OK;
-    if (pending) {      // its launches are timed with the segmentation stage: shard_infer_ex synchronises behind the masks
+    // kernels index the recording with absolute sample positions; every append and every compaction leaves SD_TAIL_PAD zeros behind sample n
+    const DevWav tail{b.tail_now(), b.n, b.sealed * SD_HOP, true};
+    if (pending) {      // its launches are timed with the segmentation stage: shard_infer synchronises behind the masks
         const double t0 = now_ms();
-        rc = segment_pending(s, lo, hi);
+        const int rc = segment_pending(s, tail, lo, hi);
         c->stage_ms[0] += now_ms() - t0;
+        if (rc) return rc;
     }
-    if (!rc) rc = shard_infer_ex(c, b.tail_now(), b.n, lo, hi, b.seg + lo * SD_SEG_ROW, b.emb + lo * SD_EMB_ROW, pending);
-    c->wav_origin = 0;
-    c->wav_padded = padded;
-    return rc;
+    return shard_infer(c, tail, lo, hi, b.seg + lo * SD_SEG_ROW, b.emb + lo * SD_EMB_ROW, pending);
 }
 
 // the blocks that have become sealed: inferred once, then their audio is dropped
@@ -146,7 +133,7 @@ int push_impl(sd_stream* s, const void* src, int64_t m, int kind, const char* wh
     if (int rc = check_call(s, who)) return rc;
     if (m == 0) return SD_OK;
     const double t0 = now_ms();
-    for (int i = 0; i < 4; ++i) c->stage_ms[i] = 0;
+    clear_stage_ms(c);
     StreamBook& b = s->b;
     HipDev dev{c};
     int rc;
@@ -162,7 +149,7 @@ int push_impl(sd_stream* s, const void* src, int64_t m, int kind, const char* wh
             HIPCHK(c, hipMemcpyAsync(stage, src, (size_t)m * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
             d_pcm = stage;
         }
-        hipLaunchKernelGGL(k_tail_append_pcm, GRID1(m + SD_TAIL_PAD), 0, c->stream, d_pcm, dst, m);
+        hipLaunchKernelGGL(k_pcm_to_f32, GRID1(m + SD_TAIL_PAD), 0, c->stream, d_pcm, dst, m);
         KCHECK(c);
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));      // the caller's buffer may go
@@ -183,7 +170,7 @@ int turns_impl(sd_stream* s, sd_turn** turns, int64_t* n_turns)
     const int64_t total = sd_num_chunks(b.n, nullptr);
     if (total <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)b.n);
     const double t0 = now_ms();
-    for (int i = 0; i < 4; ++i) c->stage_ms[i] = 0;
+    clear_stage_ms(c);
     int rc;
     if ((rc = seal_blocks(s))) return rc;            // (nothing to do unless an earlier push failed half way)
     if (b.pending_n != b.n) {

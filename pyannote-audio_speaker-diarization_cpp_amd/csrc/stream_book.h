@@ -6,7 +6,7 @@
 #include <cstdint>
 #include "../../include/sdhip.h"
 
-#define SD_TAIL_PAD 512                                    // zeroed floats behind the last sample: what wav_padded promises (common.h)
+#define SD_TAIL_PAD 512                                    // zeroed floats behind the last sample: SD_WAV_PAD, what DevWav::padded promises (common.h; stream.hip asserts the two agree)
 #define SD_SEAL_CHUNKS 32                                  // 96 items = three whole reference embedding batches (sd.cpp:2429)
 #define SD_SEG_ROW ((int64_t)SD_FRAMES * SD_SPEAKERS)      // floats of one chunk in the score cache
 #define SD_EMB_ROW ((int64_t)SD_SPEAKERS * SD_EMB_DIM)     // ... in the embedding cache

@@ -1044,3 +1044,99 @@ def test_full_size_one_hour_whole_path_properties(diarizer):
     assert np.array_equal(np.isnan(emb.cpu().numpy()[:, 0]), bad)
     cnt, _, _ = orc.speaker_count(b)
     assert len(cnt) == int(sdhip.lib().sd_count_frames(C))
+
+
+# ------------------------------------------------------------------ the device waveform is a value: no entry leaves anything behind for the next one
+ORDER_SECONDS, ORDER_SEED = 25.3, 17      # 404 800 samples: 42 chunks (a shard can start at chunk 32), the last one 76 800 samples
+ORDER_ENTRIES = ("segment", "segment_dev", "segment_chunks_8000", "segment_chunks_80000", "embed_dev", "shard_infer_dev", "diarize_f32", "activity")
+
+
+def entry_calls(d, pcm, masks):
+    """name -> call of that entry on context d, all on the one recording `pcm` (masks [chunks * 3][293]: sd_embed_dev's input); arrays and turn lists as they come back"""
+    L = sdhip.lib()
+    dev = torch.device("cuda", 0)
+    n = len(pcm)
+    wav = pcm.astype(np.float32) / 32768.0
+    total, _ = sdhip.num_chunks(n)
+    d_pcm, d_wav, d_masks = torch.from_numpy(pcm).to(dev), torch.from_numpy(wav).to(dev), torch.from_numpy(np.ascontiguousarray(masks, np.float32)).to(dev)
+
+    def segment_dev():
+        out = torch.zeros((total, 293, 3), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        d._chk(L.sd_segment_dev(d._h, d_wav.data_ptr(), n, out.data_ptr(), total))
+        return out.cpu().numpy()
+
+    def embed_dev():
+        out = torch.zeros((total * 3, 192), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        d._chk(L.sd_embed_dev(d._h, d_wav.data_ptr(), n, d_masks.data_ptr(), total * 3, 0, out.data_ptr()))
+        return out.cpu().numpy()
+
+    def shard_infer_dev(first_sample=32 * 8000):
+        seg = torch.zeros((total - 32, 293, 3), dtype=torch.float32, device=dev)
+        emb = torch.zeros(((total - 32) * 3, 192), dtype=torch.float32, device=dev)
+        shard = d_pcm[first_sample:].contiguous()
+        torch.cuda.synchronize()
+        d.shard_infer_dev(shard.data_ptr(), first_sample, n - first_sample, n, 32, total, seg.data_ptr(), emb.data_ptr())
+        return np.concatenate([seg.cpu().numpy().ravel(), emb.cpu().numpy().ravel()])
+
+    return {"segment": lambda: d.segment(wav), "segment_dev": segment_dev,
+            "segment_chunks_8000": lambda: d.segment_chunks(wav[:5 * 8000].reshape(5, 8000))[0],
+            "segment_chunks_80000": lambda: d.segment_chunks(wav[:3 * 80000].reshape(3, 80000))[0],
+            "embed_dev": embed_dev, "shard_infer_dev": shard_infer_dev, "diarize_f32": lambda: d.diarize_f32(wav),
+            "activity": lambda: d.activity(pcm, sdhip.ACTIVITY_SPEECH), "shard_not_covered": lambda: shard_infer_dev(33 * 8000),
+            "segment_chunks_80001": lambda: d.segment_chunks(np.zeros((1, 80001), np.float32))}
+
+
+def same_bits(a, b):
+    """turn lists, or arrays bit for bit (NaN rows of the embeddings included)"""
+    if isinstance(a, list):
+        return a == b
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def test_an_entry_does_not_depend_on_the_entries_that_ran_before_it(weights):
+    """Every entry describes the waveform it reads itself (common.h: DevWav -- origin of a slice, zero padding behind the samples): nothing of it stays
+    in the context.  The same calls on two fresh contexts, in opposite orders -- the second with a stream (whose tail is a slice with an origin), a shard
+    that does not cover its chunks and rows one sample too long in the middle -- give the same bits: sd_segment_dev (unpadded caller's buffer: one conv0
+    per chunk) next to sd_segment (padded: the shared conv0), sd_segment_chunks with rows of 8000 (the shared conv0) and 80000 samples, sd_embed_dev and
+    sd_segment_dev behind a shard at sample 256 000, and the whole-path entries.  No tolerance: the same code on the same data."""
+    import synth
+    pcm = synth.make_pcm(ORDER_SECONDS, seed=ORDER_SEED)
+    n = len(pcm)
+    total, last = sdhip.num_chunks(n)
+    assert n % 8000 != 0 and total > 32 and 0 < last < 80000
+    a, b = sdhip.Diarizer(weights[0], weights[1]), sdhip.Diarizer(weights[0], weights[1])
+    try:
+        first = a.segment(pcm.astype(np.float32) / 32768.0)
+        masks = a.postseg(first)[1]
+        assert np.isfinite(first).all() and first.any() and masks.any()
+        ca, cb = entry_calls(a, pcm, masks), entry_calls(b, pcm, masks)
+        ra = {"segment": first}
+        for name in ORDER_ENTRIES[1:]:
+            ra[name] = ca[name]()
+        rb, again = {}, {}
+        for name in ORDER_ENTRIES[:3:-1]:
+            rb[name] = cb[name]()
+        with b.stream() as st:
+            st.push(pcm[:350001])                 # 34 full chunks: 32 are sealed, the tail starts at sample 256 000
+            st.push(pcm[350001:])
+            assert st.info()[1] == 32
+            streamed = st.turns()
+        for name in ("shard_not_covered", "segment_chunks_80001"):
+            with pytest.raises(sdhip.SdError) as e:
+                cb[name]()
+            assert e.value.code == 1, (name, str(e.value))          # SD_ERR_ARG
+        for name in ("segment_dev", "embed_dev"):
+            again[name] = cb[name]()
+        for name in ORDER_ENTRIES[3::-1]:
+            rb[name] = cb[name]()
+    finally:
+        a.close()
+        b.close()
+    for name in ORDER_ENTRIES:
+        assert same_bits(ra[name], rb[name]), name
+    for name in again:
+        assert same_bits(ra[name], again[name]), name + " after the failures"
+    assert streamed == ra["diarize_f32"]
+    assert not same_bits(ra["segment"], ra["segment_dev"])           # the two conv0 forms: `padded` reached seg_batch from each entry
