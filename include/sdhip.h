@@ -289,6 +289,50 @@ void sd_stream_close(sd_stream*);
 /* host-only: the sealed chunks of an n_samples-sample recording, 32 * (full / 32) as above (slide()'s chunk rule, sd.cpp:1419, 1457) */
 int64_t sd_stream_sealed_chunks(int64_t n_samples);
 
+/* ---- known speakers: cluster numbers mean nothing outside one call; these entries give the clusters an identity that lasts.  The centroids that
+ * assign_embeddings builds (sd.cpp:2149-2167; what pyannote hands out with return_embeddings=True, Clustering.py:97-164) come out of the last job, a
+ * voiceprint of a known person is computed from regions of a recording exactly as the diarizer computes its own embeddings, and centroids are matched
+ * against a gallery of voiceprints by the reference's cosine distance (sd.cpp:476-498).
+ * sd_last_speakers: the K final centroids of the last call of this ctx that clustered -- sd_clustering*, sd_diarize*, sd_finalize_dev, sd_stream_turns,
+ * sd_diarize_sharded* on rank 0 -- and the number of train rows (sd.cpp:2224) of each: means of the un-normalised train rows, members in ascending row
+ * order, sequential f64 sums.  Row k is the cluster whose turns carry raw label k (before any sd_relabel_turns).  Rows have the d of that call: 192 on every
+ * whole path.  At most cap rows are written; either pointer may be NULL; *K = 0 before any clustering call.  Where the reference computes no centroid
+ * (fewer than two train rows, or max_clusters < 2; sd.cpp:2081-2088) K = 1: the single train row or the mean of the train rows, with its count -- a NaN row
+ * with count 0 when there is no train row at all, so "row index = label" always holds. */
+int sd_last_speakers(const sd_ctx*, double* h_centroids /*[cap][192] or NULL*/, int64_t cap, int64_t* K, int64_t* h_counts /*[cap] or NULL*/);     /* sd.cpp:2149-2167 */
+/* sd_voiceprint*: the embedding of the samples that lie in `spans` -- those with spans[i].label == label, all of them when label < 0; spans == NULL, or no
+ * span at all with label < 0: the whole recording.  A span covers samples [llrint(start * 16000), llrint(end * 16000)) clamped to [0, n); overlapping spans
+ * are merged.  Same chunks as the diarizer (sd_num_chunks), same item grid, same batches of 32 (sd.cpp:2429): item 3c carries the mask "mask frame f of
+ * chunk c is 1.0 iff its first sample c * 8000 + ceil(80000 f / 293) lies in a span and before n", items 3c + 1 and 3c + 2 are empty.  h_emb = the f64 mean
+ * of the rows 3c that are not NaN (a window with fewer than 640 selected samples is, sd.cpp:44), ascending c, sequential sums; *n_windows = their number.
+ * One label per call: a voiceprint never depends on what else is in the list.  No window at all: SD_ERR_SHORT (*n_windows = 0).  A span with end < start, a
+ * NaN or a negative time: SD_ERR_ARG before anything is touched.  No segmentation network runs: a caller who wants silence removed passes the regions of
+ * sd_activity* as spans.  Samples as for sd_diarize / _dev / _f32 / _wav (same SD_WAV_* flags, same refusals).  sd_span_masks is the mask stage alone. */
+int sd_span_masks(sd_ctx*, int64_t n_samples, const sd_turn* spans, int64_t n_spans, int32_t label, float* h_masks /*[chunks*3][293]*/);     /* sd.cpp:3047-3078, 1641-1662 */
+int sd_voiceprint(sd_ctx*, const int16_t* h_pcm, int64_t n, const sd_turn* spans, int64_t n_spans, int32_t label, double* h_emb /*[192]*/, int64_t* n_windows);     /* sd.cpp:2436-2561, 2149-2167 */
+int sd_voiceprint_dev(sd_ctx*, const int16_t* d_pcm, int64_t n, const sd_turn* spans, int64_t n_spans, int32_t label, double* h_emb /*[192]*/, int64_t* n_windows);     /* sd.cpp:2436-2561, 2149-2167 */
+int sd_voiceprint_f32(sd_ctx*, const float* h_wav, int64_t n, const sd_turn* spans, int64_t n_spans, int32_t label, double* h_emb /*[192]*/, int64_t* n_windows);     /* sd.cpp:2436-2561, 2149-2167 */
+int sd_voiceprint_wav(sd_ctx*, const char* path, int flags, const sd_turn* spans, int64_t n_spans, int32_t label, double* h_emb /*[192]*/, int64_t* n_windows);     /* sd.cpp:2937-2951, 2436-2561 */
+/* sd_speaker_distances: h_dist[k][m] = 1 - dot / (sqrt(m1) * sqrt(m2)) of centroid k and gallery row m, dot, m1 and m2 each a sequential sum over the d
+ * dimensions (sd.cpp:476-498: the bits of the assignment step).  h_cen == NULL: the last job's centroids (K and d must be theirs).  A centroid row whose
+ * first element is NaN (count 0) is skipped: NaN distances.  A zero-norm row among the others or anywhere in the gallery: SD_ERR_NUMERIC (the reference
+ * throws, sd.cpp:493-495).
+ * sd_match_speakers: the pairs with distance <= threshold (NaN = option "speaker_match_threshold", sd_set_option_f64, in [0, 2]; default t * t / 2 with
+ * t = (double)0.7153814381597874f, the cosine distance at which the default clustering stops merging two unit vectors; a constant, it does not follow
+ * "clustering_threshold") sorted by (distance, k, m); a pair is taken when both sides are still free: greedy, deterministic, one-to-one.
+ * h_match[k] = the gallery row of centroid k or -1, h_dist_best[k] (may be NULL) = its distance or NaN. */
+int sd_speaker_distances(sd_ctx*, const double* h_cen /*[K][d] or NULL*/, int64_t K, const double* h_gallery /*[M][d]*/, int64_t M, int d, double* h_dist /*[K][M]*/);     /* sd.cpp:476-498 */
+int sd_match_speakers(sd_ctx*, const double* h_cen, int64_t K, const double* h_gallery, int64_t M, int d, double threshold, int32_t* h_match /*[K]*/, double* h_dist_best /*[K] or NULL*/);     /* sd.cpp:476-498, 293-316 */
+/* host-only: voiceprint files -- text, one speaker per line: a name without white space, then 192 values printed with %.17g (read -> write -> read is
+ * bit-exact); # starts a comment.  A malformed line (wrong number of values, not a finite number, a name twice) returns SD_ERR_ARG with the line number in
+ * sd_voiceprints_error().  sd_read_voiceprints returns malloc'd names [M] and emb [M][192]: free both with sd_free_voiceprints. */
+int sd_read_voiceprints(const char* path, char*** names, double** emb, int64_t* M);     /* no counterpart: the reference keeps no speaker between calls (sd.cpp:3433-3441) */
+int sd_write_voiceprints(const char* path, const char* const* names, const double* emb, int64_t M);     /* no counterpart (sd.cpp:3433-3441) */
+void sd_free_voiceprints(char** names, double* emb, int64_t M);
+const char* sd_voiceprints_error(void);     /* reason for the last non-OK return of the two calls above */
+/* sd_write_rttm_ex with names: the speaker field of a turn with label k is names[k] where 0 <= k < K and names[k] != NULL, SPEAKER_kk otherwise */
+int sd_write_rttm_named(const char* path, const char* uri, const sd_turn* turns, int64_t n_turns, const double* conf /* or NULL */, const char* const* names /*[K]*/, int64_t K);     /* sd.cpp:3433-3441 */
+
 /* ---- a18: the reference's output line (sd.cpp:3439) */
 int sd_format_turn(const sd_turn* t, char* buf, int cap);
 
@@ -319,7 +363,8 @@ int sd_stage_ms(const sd_ctx*, double* ms4);
  * Test and tuning keys are listed in sdhip_test.h.  An unknown key returns SD_ERR_ARG. */
 int sd_set_option(sd_ctx*, const char* key, int64_t value);
 /* the real-valued keys: "clustering_threshold" (Clustering.py:251-276 / 317-333; outside [0, 2] or NaN: SD_ERR_ARG) and the four "activity_*" keys of
- * sd_activity* above (NaN or out of range: SD_ERR_ARG).  An unknown key returns SD_ERR_ARG. */
+ * sd_activity* above (NaN or out of range: SD_ERR_ARG), and "speaker_match_threshold" of sd_match_speakers above (outside [0, 2] or NaN: SD_ERR_ARG).
+ * An unknown key returns SD_ERR_ARG. */
 int sd_set_option_f64(sd_ctx*, const char* key, double value);
 
 #ifdef __cplusplus

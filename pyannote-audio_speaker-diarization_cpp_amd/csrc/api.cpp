@@ -5,6 +5,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <fstream>
+#include <tuple>
 
 static std::string g_create_err;
 
@@ -163,6 +165,7 @@ extern "C" int sd_set_option_f64(sd_ctx* c, const char* key, double v)
     else if (k == "activity_offset") { if (!(v >= 0.0 && v <= 1.0)) SD_FAIL(c, SD_ERR_ARG, "activity_offset must lie in [0, 1]"); c->activity_offset = v; }
     else if (k == "activity_min_duration_on") { if (!(v >= 0.0)) SD_FAIL(c, SD_ERR_ARG, "activity_min_duration_on must be >= 0"); c->activity_min_on = v; }
     else if (k == "activity_min_duration_off") { if (!(v >= 0.0)) SD_FAIL(c, SD_ERR_ARG, "activity_min_duration_off must be >= 0"); c->activity_min_off = v; }
+    else if (k == "speaker_match_threshold") { if (!(v >= 0.0 && v <= 2.0)) SD_FAIL(c, SD_ERR_ARG, "speaker_match_threshold must lie in [0, 2]"); c->speaker_match_threshold = v; }
     else SD_FAIL(c, SD_ERR_ARG, "unknown real-valued option %s", key);
     return SD_OK;
 }
@@ -481,4 +484,164 @@ extern "C" int sd_write_rttm_ex(const char* path, const char* uri, const sd_turn
 extern "C" int sd_write_rttm(const char* path, const char* uri, const sd_turn* turns, int64_t n_turns)
 {
     return sd_write_rttm_ex(path, uri, turns, n_turns, nullptr);
+}
+
+// ------------------------------------------------------------------ known speakers: centroids out, gallery matching, voiceprint files
+// the K final centroids of the last clustering call of this ctx and the train rows of each (run_clustering keeps them; sd.cpp:2149-2167)
+extern "C" int sd_last_speakers(const sd_ctx* c, double* h_centroids, int64_t cap, int64_t* K, int64_t* h_counts)
+{
+    if (!c || cap < 0) return SD_ERR_ARG;
+    const int64_t k = c->last_cen_K, d = c->last_cen_d;
+    if (K) *K = k;
+    for (int64_t i = 0; i < k && i < cap; ++i) {
+        if (h_centroids) memcpy(h_centroids + i * d, &c->last_cen[(size_t)(i * d)], (size_t)d * sizeof(double));
+        if (h_counts) h_counts[i] = c->last_cen_counts[(size_t)i];
+    }
+    return SD_OK;
+}
+
+// h_cen (NULL = the last job's centroids, K and d must be theirs) against the gallery -> dist [K][M] in `dist`
+static int speaker_dist_host(sd_ctx* c, const double* h_cen, int64_t K, const double* h_gallery, int64_t M, int d, std::vector<double>& dist, const char* who)
+{
+    if (!h_gallery || K < 1 || M < 1 || d < 1) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument (K, M, d >= 1)", who);
+    if (!h_cen) {
+        if (c->last_cen_K < 1) SD_FAIL(c, SD_ERR_ARG, "%s: no clustering call on this context yet", who);
+        if (K != c->last_cen_K || d != c->last_cen_d) SD_FAIL(c, SD_ERR_ARG, "%s: the last job has %d centroids of %d dimensions, not %lld of %d", who, c->last_cen_K, c->last_cen_d, (long long)K, d);
+        h_cen = c->last_cen.data();
+    }
+    if ((double)K * (double)M > 4e9) SD_FAIL(c, SD_ERR_ARG, "%s: a %lld x %lld table is out of range", who, (long long)K, (long long)M);
+    dist.resize((size_t)K * (size_t)M);
+    WS(c, double, d_cen, "spk_cen", K * d); WS(c, double, d_gal, "spk_gallery", M * d); WS(c, double, d_dist, "spk_dist", K * M);
+    HIPCHK(c, hipMemcpy(d_cen, h_cen, (size_t)K * d * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_gal, h_gallery, (size_t)M * d * sizeof(double), hipMemcpyHostToDevice));
+    return run_speaker_dist(c, d_cen, K, d_gal, M, d, d_dist, dist.data());
+}
+
+extern "C" int sd_speaker_distances(sd_ctx* c, const double* h_cen, int64_t K, const double* h_gallery, int64_t M, int d, double* h_dist)
+{
+    ENTER(c);
+    if (!h_dist) SD_FAIL(c, SD_ERR_ARG, "sd_speaker_distances: bad argument");
+    std::vector<double> dist;
+    if (int rc = speaker_dist_host(c, h_cen, K, h_gallery, M, d, dist, "sd_speaker_distances")) return rc;
+    memcpy(h_dist, dist.data(), dist.size() * sizeof(double));
+    return SD_OK;
+}
+
+// greedy one-to-one matching: the pairs with dist <= threshold in (dist, k, m) order, a pair taken when both sides are still free
+extern "C" int sd_match_speakers(sd_ctx* c, const double* h_cen, int64_t K, const double* h_gallery, int64_t M, int d, double threshold,
+                                 int32_t* h_match, double* h_dist_best)
+{
+    ENTER(c);
+    if (!h_match) SD_FAIL(c, SD_ERR_ARG, "sd_match_speakers: bad argument");
+    if (threshold != threshold) threshold = c->speaker_match_threshold;
+    else if (!(threshold >= 0.0 && threshold <= 2.0)) SD_FAIL(c, SD_ERR_ARG, "sd_match_speakers: threshold must lie in [0, 2] (NaN = option speaker_match_threshold)");
+    if (M > 0x7fffffff) SD_FAIL(c, SD_ERR_ARG, "sd_match_speakers: gallery too long");
+    std::vector<double> dist;
+    if (int rc = speaker_dist_host(c, h_cen, K, h_gallery, M, d, dist, "sd_match_speakers")) return rc;
+    std::vector<std::tuple<double, int64_t, int64_t>> pairs;
+    for (int64_t k = 0; k < K; ++k)
+        for (int64_t m = 0; m < M; ++m) { const double v = dist[(size_t)(k * M + m)]; if (v <= threshold) pairs.emplace_back(v, k, m); }
+    std::sort(pairs.begin(), pairs.end());
+    std::vector<char> taken((size_t)M, 0);
+    for (int64_t k = 0; k < K; ++k) { h_match[k] = -1; if (h_dist_best) h_dist_best[k] = NAN; }
+    for (const auto& p : pairs) {
+        const int64_t k = std::get<1>(p), m = std::get<2>(p);
+        if (h_match[k] >= 0 || taken[(size_t)m]) continue;
+        h_match[k] = (int32_t)m; taken[(size_t)m] = 1;
+        if (h_dist_best) h_dist_best[k] = std::get<0>(p);
+    }
+    return SD_OK;
+}
+
+// voiceprint file: text, one speaker per line -- a name without white space, then SD_EMB_DIM values (%.17g: the round trip is bit-exact); # starts a comment
+static std::string g_vp_err;
+extern "C" const char* sd_voiceprints_error(void) { return g_vp_err.c_str(); }
+static bool vp_name_ok(const char* s)
+{
+    if (!s || !s[0]) return false;
+    for (const char* p = s; *p; ++p) if (*p == '#' || *p == ' ' || (*p >= '\t' && *p <= '\r')) return false;
+    return true;
+}
+extern "C" void sd_free_voiceprints(char** names, double* emb, int64_t M)
+{
+    if (names) for (int64_t i = 0; i < M; ++i) free(names[i]);
+    free(names); free(emb);
+}
+extern "C" int sd_read_voiceprints(const char* path, char*** names, double** emb, int64_t* M)
+{
+    g_vp_err.clear();
+    if (!path || !names || !emb || !M) { g_vp_err = "sd_read_voiceprints: bad argument"; return SD_ERR_ARG; }
+    *names = nullptr; *emb = nullptr; *M = 0;
+    std::ifstream in(path);
+    if (!in) { g_vp_err = std::string("cannot open ") + path; return SD_ERR_ARG; }
+    std::vector<std::string> nm;
+    std::vector<double> val;
+    std::string line;
+    auto bad = [&](int64_t no, const std::string& why) { char b[64]; snprintf(b, sizeof(b), ": line %lld: ", (long long)no); g_vp_err = std::string(path) + b + why; return (int)SD_ERR_ARG; };
+    for (int64_t no = 1; std::getline(in, line); ++no) {
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos) line.resize(hash);
+        std::vector<std::string> tok;
+        for (size_t i = 0; i < line.size();) {
+            while (i < line.size() && (line[i] == ' ' || (line[i] >= '\t' && line[i] <= '\r'))) ++i;
+            size_t j = i;
+            while (j < line.size() && !(line[j] == ' ' || (line[j] >= '\t' && line[j] <= '\r'))) ++j;
+            if (j > i) tok.push_back(line.substr(i, j - i));
+            i = j;
+        }
+        if (tok.empty()) continue;
+        if (tok.size() != (size_t)SD_EMB_DIM + 1) return bad(no, "a name and " + std::to_string(SD_EMB_DIM) + " values expected, " + std::to_string(tok.size() - 1) + " values found");
+        if (std::find(nm.begin(), nm.end(), tok[0]) != nm.end()) return bad(no, "name " + tok[0] + " occurs twice");
+        nm.push_back(tok[0]);
+        for (size_t q = 1; q < tok.size(); ++q) {
+            char* end = nullptr;
+            const double v = strtod(tok[q].c_str(), &end);
+            if (end == tok[q].c_str() || *end || !std::isfinite(v)) return bad(no, "'" + tok[q] + "' is not a finite number");
+            val.push_back(v);
+        }
+    }
+    const size_t n = nm.size();
+    char** pn = (char**)malloc(sizeof(char*) * (n ? n : 1));
+    double* pe = (double*)malloc(sizeof(double) * SD_EMB_DIM * (n ? n : 1));
+    if (!pn || !pe) { free(pn); free(pe); g_vp_err = "out of host memory"; return SD_ERR_ARG; }
+    for (size_t i = 0; i < n; ++i) pn[i] = strdup(nm[i].c_str());
+    if (n) memcpy(pe, val.data(), val.size() * sizeof(double));
+    *names = pn; *emb = pe; *M = (int64_t)n;
+    return SD_OK;
+}
+extern "C" int sd_write_voiceprints(const char* path, const char* const* names, const double* emb, int64_t M)
+{
+    g_vp_err.clear();
+    if (!path || M < 0 || (M > 0 && (!names || !emb))) { g_vp_err = "sd_write_voiceprints: bad argument"; return SD_ERR_ARG; }
+    for (int64_t i = 0; i < M; ++i) {
+        if (!vp_name_ok(names[i])) { g_vp_err = "sd_write_voiceprints: a name must be non-empty, without white space or #"; return SD_ERR_ARG; }
+        for (int64_t j = 0; j < i; ++j) if (strcmp(names[i], names[j]) == 0) { g_vp_err = std::string("sd_write_voiceprints: name ") + names[i] + " occurs twice"; return SD_ERR_ARG; }
+        for (int q = 0; q < SD_EMB_DIM; ++q) if (!std::isfinite(emb[i * SD_EMB_DIM + q])) { g_vp_err = std::string("sd_write_voiceprints: the voiceprint of ") + names[i] + " is not finite"; return SD_ERR_ARG; }
+    }
+    FILE* f = fopen(path, "w");
+    if (!f) { g_vp_err = std::string("cannot write ") + path; return SD_ERR_ARG; }
+    for (int64_t i = 0; i < M; ++i) {
+        fputs(names[i], f);
+        for (int q = 0; q < SD_EMB_DIM; ++q) fprintf(f, " %.17g", emb[i * SD_EMB_DIM + q]);
+        fputc('\n', f);
+    }
+    if (fclose(f) != 0) { g_vp_err = std::string("cannot write ") + path; return SD_ERR_ARG; }
+    return SD_OK;
+}
+
+// sd_write_rttm_ex with names: the speaker field of a turn with label k is names[k] where 0 <= k < K and names[k] != NULL, SPEAKER_kk otherwise
+extern "C" int sd_write_rttm_named(const char* path, const char* uri, const sd_turn* turns, int64_t n_turns, const double* conf, const char* const* names, int64_t K)
+{
+    if (!path || (n_turns > 0 && !turns) || n_turns < 0 || K < 0 || (K > 0 && !names)) return SD_ERR_ARG;
+    for (int64_t k = 0; k < K; ++k) if (names[k] && !vp_name_ok(names[k])) return SD_ERR_ARG;
+    FILE* f = fopen(path, "w");
+    if (!f) return SD_ERR_ARG;
+    for (int64_t i = 0; i < n_turns; ++i) {
+        const int32_t k = turns[i].label;
+        fprintf(f, "SPEAKER %s 1 %.3f %.3f <NA> <NA> ", (uri && uri[0]) ? uri : "audio", turns[i].start, turns[i].end - turns[i].start);
+        if (k >= 0 && k < K && names[k]) fprintf(f, "%s <NA> ", names[k]); else fprintf(f, "SPEAKER_%02d <NA> ", k);
+        if (conf && conf[i] == conf[i]) fprintf(f, "%.4f\n", conf[i]); else fprintf(f, "<NA>\n");
+    }
+    fclose(f);
+    return SD_OK;
 }

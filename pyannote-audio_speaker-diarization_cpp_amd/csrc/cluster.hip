@@ -279,6 +279,7 @@ int run_clustering(sd_ctx* c, const double* d_emb, int64_t M, int d, std::vector
     if (Kout) *Kout = 1;
     const bool dumping = !c->dump_dir.empty();
     c->stash.clustered = false;
+    c->last_cen_K = 0;                                              // sd_last_speakers describes this call from its successful end on
     if (M <= 0) return SD_OK;
     // a10: rows whose first element is not NaN (sd.cpp:2224)
     std::vector<double> first((size_t)M);
@@ -297,7 +298,26 @@ int run_clustering(sd_ctx* c, const double* d_emb, int64_t M, int d, std::vector
     max_clusters = std::max(1, std::min((int)N, max_clusters));
     if (min_clusters > max_clusters) min_clusters = max_clusters;
     if (min_clusters == max_clusters) num_clusters = min_clusters;
-    if (N < 2 || max_clusters < 2) return SD_OK;                    // all zeros (sd.cpp:2081-2088)
+    if (N < 2 || max_clusters < 2) {                                // all zeros (sd.cpp:2081-2088)
+        // one cluster, label 0: its centroid is the mean of the train rows by the rule of a14 below (the single row itself; a NaN row with count 0 when there is none)
+        c->last_cen.assign((size_t)d, NAN);
+        c->last_cen_counts.assign(1, N);
+        c->last_cen_d = d;
+        if (N > 0) {
+            const int off1[2] = {0, (int)N};
+            WS(c, int, d_order1, "cl_order", N);
+            WS(c, int, d_off1, "cl_off", 2);
+            WS(c, double, d_cen1, "cl_cen", (size_t)d);
+            HIPCHK(c, hipMemcpyAsync(d_order1, tidx.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(d_off1, off1, sizeof(off1), hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(k_cluster_means, dim3(1), dim3(((d + 63) / 64) * 64), 0, c->stream, d_emb, d, d_order1, d_off1, d_cen1);
+            KCHECK(c);
+            HIPCHK(c, hipMemcpyAsync(c->last_cen.data(), d_cen1, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        c->last_cen_K = 1;
+        return SD_OK;
+    }
     WS(c, int, d_tidx, "cl_tidx", N);
     WS(c, double, X, "cl_X", N * d);
     WS(c, double, Xn, "cl_Xn", N * d);
@@ -399,6 +419,8 @@ int run_clustering(sd_ctx* c, const double* d_emb, int64_t M, int d, std::vector
     HIPCHK(c, hipMemcpyAsync(hard.data(), d_hard, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&herr, d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (soft_best) HIPCHK(c, hipMemcpyAsync(soft_best->data(), d_best, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    c->last_cen.resize((size_t)nl * d);                             // the centroids ride this synchronisation (sd_last_speakers)
+    HIPCHK(c, hipMemcpyAsync(c->last_cen.data(), d_cen2, c->last_cen.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (herr) SD_FAIL(c, SD_ERR_NUMERIC, "zero-magnitude embedding or centroid in assignment (reference throws, sd.cpp:493-495)");
     if (constrained_assign) {
@@ -419,6 +441,10 @@ int run_clustering(sd_ctx* c, const double* d_emb, int64_t M, int d, std::vector
             for (int64_t i = 0; i < M; ++i) (*soft_best)[(size_t)i] = hard[(size_t)i] >= 0 ? hs[(size_t)i * nl + hard[(size_t)i]] : NAN;
     }
     if (Kout) *Kout = nl;
+    c->last_cen_counts.resize((size_t)nl);
+    for (int k = 0; k < nl; ++k) c->last_cen_counts[(size_t)k] = off[(size_t)k + 1] - off[(size_t)k];
+    c->last_cen_d = d;
+    c->last_cen_K = nl;
     if (dumping) {
         StepStash& S = c->stash;
         S.clustered = true; S.N = N; S.K = nl; S.cluster_res = lab; S.hard_pre = hard;

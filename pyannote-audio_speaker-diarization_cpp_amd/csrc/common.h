@@ -211,6 +211,11 @@ struct sd_ctx {
     double clustering_threshold = (double)0.7153814381597874f;      // the reference's float constant, widened
     int min_cluster_size = 15;
     std::vector<double> last_conf;               // per-turn confidence of the last finalize (sd_last_confidence)
+    // the last clustering call (run_clustering): its K final centroids [K][last_cen_d] -- row k = raw label k -- and the train rows of each (sd_last_speakers); last_cen_K = 0 before any
+    std::vector<double> last_cen;
+    std::vector<int64_t> last_cen_counts;
+    int last_cen_K = 0, last_cen_d = 0;
+    double speaker_match_threshold = (double)0.7153814381597874f * (double)0.7153814381597874f / 2;      // sd_match_speakers: t * t / 2, the cosine distance at which the default clustering stops merging two unit vectors
     // the activity stage (activity.hip): pyannote's Binarize parameters for the speech / overlap timeline, and the timeline of the last whole-path call
     double activity_onset = 0.5, activity_offset = 0.5, activity_min_on = 0.0, activity_min_off = 0.0;
     bool activity_hamming = false;              // aggregate()'s Hamming-weighted branch (sd.cpp:1211-1215)
@@ -418,6 +423,12 @@ int64_t activity_frames_host(int64_t chunks);                     // frames aggr
 int64_t activity_rows_host(int64_t nf, int64_t n_samples);        // ... without those that lie wholly in the last chunk's zero padding
 int run_activity_scores(sd_ctx* c, const float* d_seg, int64_t chunks, int kind, double* d_scores, int64_t nf);
 int run_activity_regions(sd_ctx* c, const double* d_scores, int64_t rows, int label, std::vector<sd_turn>& turns);
+// ---- speakers.hip
+int check_spans(sd_ctx* c, const sd_turn* spans, int64_t n_spans, const char* who);      // 0 <= start <= end, numbers; touches nothing but c->err
+void spans_to_samples(const sd_turn* spans, int64_t n_spans, int32_t label, int64_t n, std::vector<int64_t>& out);      // -> sorted, merged [first, end) sample pairs
+int run_span_masks(sd_ctx* c, const std::vector<int64_t>& spans, int64_t chunks, int64_t n, float* d_masks /*[chunks * 3][293]*/);
+int run_voiceprint_mean(sd_ctx* c, const float* d_emb /*[chunks * 3][192]*/, int64_t chunks, double* h_mean /*[192]*/, int64_t* n_live);      // synchronises
+int run_speaker_dist(sd_ctx* c, const double* d_cen, int64_t K, const double* d_gal, int64_t M, int d, double* d_dist, double* h_dist /*[K][M]*/);      // synchronises
 // ---- reconstruct.hip
 int run_reconstruct(sd_ctx* c, const float* d_seg, const int* d_nact, const int* d_hard, const int32_t* d_count,
                     int64_t n_count, int64_t chunks, int64_t n_samples, int K, std::vector<sd_turn>& turns);

@@ -35,9 +35,17 @@
 //                   per chunk as the audio comes in, the final turns are those of the run without the flag, bit for bit.  --stream-updates also prints,
 //                   after each piece, "== <seconds pushed> s, <sealed>/<total> chunks" and the turns so far.  With - as the wav path, headerless s16le
 //                   16 kHz mono samples are read from stdin until end of file (needs --stream).  Single GPU; not with --activity or --dump-steps
+//   --speakers FILE [--speakers-threshold X]   after the diarization, match the centroids of the job's clusters (sd_last_speakers) against the voiceprints of
+//                   FILE (sd_read_voiceprints, sd_match_speakers): a matched cluster prints as [start -- end] --> NAME and goes into the RTTM under its name, an
+//                   unmatched one prints as without the flag.  X in [0, 2] = the largest cosine distance that still matches (option "speaker_match_threshold").
+//                   Works with --stream; refused with --activity and with --gpus N > 1
+//   --enroll NAME --speakers FILE [--enroll-span START END]...   no diarization: the voiceprint of the wav -- all of it, or the given spans in seconds --
+//                   (sd_voiceprint_wav) replaces or is appended as NAME in FILE (created when absent); prints "enrolled NAME from N windows".
+//                   A bad value of any of these is a usage error (exit 2) before anything touches the GPU
 //   --relabel       stdout / RTTM labels renumbered the way pyannote.audio names its output (the clusters that occur,
 //                   sorted by their string, become 0, 1, ... = SPEAKER_00, SPEAKER_01, ...); default = raw cluster ids (sd.cpp:3439)
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <ctime>
 #include <cstdlib>
@@ -52,7 +60,8 @@
 struct Args { const char* seg = nullptr; const char* emb = nullptr; const char* wav = nullptr; const char* rttm = nullptr; int gpus = 1; bool relabel = false; int precision = 0; int wav_flags = 0; const char* dump_dir = nullptr; int dump_level = 1;
               int cl_method = -1; double cl_threshold = -1.0; long long cl_min_size = -1;         // -1: leave the library's default
               int activity = -1; double act[4] = {-1.0, -1.0, -1.0, -1.0}; bool act_hamming = false;      // --activity: SD_ACTIVITY_*; onset, offset, min on, min off (-1: default)
-              long long stream_piece = 0; bool stream_updates = false; };      // --stream: samples per piece (0: off)
+              long long stream_piece = 0; bool stream_updates = false;         // --stream: samples per piece (0: off)
+              const char* speakers = nullptr; double speakers_threshold = -1.0; const char* enroll = nullptr; std::vector<sd_turn> enroll_spans; };      // --speakers FILE, its threshold (-1: default), --enroll NAME and its spans
 
 // the clustering hyper-parameters the command line set; false (message printed) on a refusal
 static bool apply_clustering(sd_ctx* ctx, const Args& a)
@@ -72,7 +81,30 @@ static bool apply_activity(sd_ctx* ctx, const Args& a)
     return true;
 }
 
-static void print_block(sd_ctx* ctx, sd_turn* turns, int64_t nt, const Args& a, const double* ms_sum = nullptr)
+// a voiceprint file in memory (--speakers)
+struct Gallery {
+    char** names = nullptr; double* emb = nullptr; int64_t M = 0;
+    ~Gallery() { sd_free_voiceprints(names, emb, M); }
+    bool read(const char* path) { if (sd_read_voiceprints(path, &names, &emb, &M) == SD_OK) return true; fprintf(stderr, "%s\n", sd_voiceprints_error()); return false; }
+};
+
+// --speakers: names[k] = the name of the voiceprint that the centroid of raw label k matched, or null; false (message printed) on a failure
+static bool match_clusters(sd_ctx* ctx, const Args& a, const Gallery& g, std::vector<const char*>& names)
+{
+    names.clear();
+    int64_t K = 0;
+    if (sd_last_speakers(ctx, nullptr, 0, &K, nullptr) != SD_OK) return false;
+    names.assign((size_t)K, nullptr);
+    if (K == 0 || g.M == 0) return true;
+    if (a.speakers_threshold >= 0.0 && sd_set_option_f64(ctx, "speaker_match_threshold", a.speakers_threshold) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
+    std::vector<int32_t> match((size_t)K);
+    const int rc = sd_match_speakers(ctx, nullptr, K, g.emb, g.M, SD_EMB_DIM, NAN, match.data(), nullptr);
+    if (rc != SD_OK) { fprintf(stderr, "matching against %s failed (%d): %s\n", a.speakers, rc, sd_last_error(ctx)); return false; }
+    for (int64_t k = 0; k < K; ++k) if (match[(size_t)k] >= 0) names[(size_t)k] = g.names[match[(size_t)k]];
+    return true;
+}
+
+static void print_block(sd_ctx* ctx, sd_turn* turns, int64_t nt, const Args& a, const double* ms_sum = nullptr, const std::vector<const char*>* names = nullptr)
 {
     double ms[4];
     if (ms_sum) memcpy(ms, ms_sum, sizeof(ms)); else sd_stage_ms(ctx, ms);
@@ -81,15 +113,24 @@ static void print_block(sd_ctx* ctx, sd_turn* turns, int64_t nt, const Args& a, 
     printf("-----------\nClustering time: %lldms\n", (long long)ms[2]);
     printf("\n----Summary----\n-----------\nTime cost: %lldms\n", (long long)ms[3]);
     printf("----------------------------------------------------\n");
+    // the name of every turn by its raw label, before --relabel renumbers the labels
+    std::vector<const char*> turn_name((size_t)nt, nullptr);
+    if (names) for (int64_t i = 0; i < nt; ++i) if (turns[i].label >= 0 && (size_t)turns[i].label < names->size()) turn_name[(size_t)i] = (*names)[(size_t)turns[i].label];
     if (a.relabel && a.activity < 0) sd_relabel_turns(turns, nt);
     char line[160];
     for (int64_t i = 0; i < nt; ++i) {
+        if (turn_name[(size_t)i]) { printf("[%g -- %g] --> %s\n", turns[i].start, turns[i].end, turn_name[(size_t)i]); continue; }
         if (a.activity >= 0) snprintf(line, sizeof(line), "[%g -- %g] --> %s", turns[i].start, turns[i].end, turns[i].label == SD_ACTIVITY_OVERLAP ? "OVERLAP" : "SPEECH");
         else sd_format_turn(&turns[i], line, sizeof(line));
         printf("%s\n", line);
     }
     printf("----------------------------------------------------\n");
-    if (a.rttm) sd_write_rttm(a.rttm, a.wav, turns, nt);
+    if (a.rttm && names) {
+        std::vector<const char*> by_label;                      // names by the labels as they are now
+        for (int64_t i = 0; i < nt; ++i) if (turns[i].label >= 0) { if ((size_t)turns[i].label >= by_label.size()) by_label.resize((size_t)turns[i].label + 1, nullptr); by_label[(size_t)turns[i].label] = turn_name[(size_t)i]; }
+        sd_write_rttm_named(a.rttm, a.wav, turns, nt, nullptr, by_label.data(), (int64_t)by_label.size());
+    }
+    else if (a.rttm) sd_write_rttm(a.rttm, a.wav, turns, nt);
     fflush(stdout);
 }
 
@@ -102,9 +143,38 @@ static const bool g_trace = getenv("SD_TRACE_CREATE") != nullptr;     // start-u
 static double g_t_main = 0;
 #define TRACE(what) do { if (g_trace) fprintf(stderr, "cli: +%.1f ms %s\n", wall_ms() - g_t_main, what); } while (0)
 
+// --enroll: the voiceprint of the wav (of its spans) into the voiceprint file under a.enroll
+static int run_enroll(const Args& a)
+{
+    Gallery g;
+    if (access(a.speakers, F_OK) == 0 && !g.read(a.speakers)) return 1;      // an existing file must be a voiceprint file; an absent one is created
+    sd_ctx* ctx = sd_create(nullptr, a.emb, 0);
+    if (!ctx) { fprintf(stderr, "sd_create failed: %s\n", sd_create_error()); return 1; }
+    if (a.precision && sd_set_option(ctx, "ecapa_precision", a.precision) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); sd_destroy(ctx); return 1; }
+    double emb[SD_EMB_DIM]; int64_t nw = 0;
+    const int rc = sd_voiceprint_wav(ctx, a.wav, a.wav_flags, a.enroll_spans.empty() ? nullptr : a.enroll_spans.data(), (int64_t)a.enroll_spans.size(), -1, emb, &nw);
+    if (rc != SD_OK) { fprintf(stderr, "enrolment failed (%d): %s\n", rc, sd_last_error(ctx)); sd_destroy(ctx); return 1; }
+    sd_destroy(ctx);
+    std::vector<const char*> names; std::vector<double> all;
+    bool replaced = false;
+    for (int64_t i = 0; i < g.M; ++i) {
+        names.push_back(g.names[i]);
+        const bool same = strcmp(g.names[i], a.enroll) == 0;
+        const double* src = same ? emb : g.emb + i * SD_EMB_DIM;
+        all.insert(all.end(), src, src + SD_EMB_DIM);
+        replaced |= same;
+    }
+    if (!replaced) { names.push_back(a.enroll); all.insert(all.end(), emb, emb + SD_EMB_DIM); }
+    if (sd_write_voiceprints(a.speakers, names.data(), all.data(), (int64_t)names.size()) != SD_OK) { fprintf(stderr, "%s\n", sd_voiceprints_error()); return 1; }
+    printf("enrolled %s from %lld windows\n", a.enroll, (long long)nw);
+    return 0;
+}
+
 static int run_single(const Args& a)
 {
     TRACE("run_single");
+    Gallery g;
+    if (a.speakers && !g.read(a.speakers)) return 1;
     sd_ctx* ctx = sd_create(a.seg, a.emb, 0);
     if (!ctx) { fprintf(stderr, "sd_create failed: %s\n", sd_create_error()); return 1; }
     TRACE("sd_create done");
@@ -117,7 +187,9 @@ static int run_single(const Args& a)
                                    : sd_diarize_wav(ctx, a.wav, a.wav_flags, &turns, &nt);      // 8 / 16 / 32-bit PCM like wav.h:99-122; rate and channels checked
     if (rc != SD_OK) { fprintf(stderr, "%s failed (%d): %s\n", a.activity >= 0 ? "activity detection" : "diarization", rc, sd_last_error(ctx)); return 1; }
     TRACE("sd_diarize_wav done");
-    print_block(ctx, turns, nt, a);
+    std::vector<const char*> names;
+    if (a.speakers && !match_clusters(ctx, a, g, names)) return 1;
+    print_block(ctx, turns, nt, a, nullptr, a.speakers ? &names : nullptr);
     sd_free_turns(turns);
     sd_destroy(ctx);
     TRACE("sd_destroy done");
@@ -225,6 +297,8 @@ static bool stream_stdin(StreamRun& r)
 
 static int run_stream(const Args& a)
 {
+    Gallery g;
+    if (a.speakers && !g.read(a.speakers)) return 1;
     sd_ctx* ctx = sd_create(a.seg, a.emb, 0);
     if (!ctx) { fprintf(stderr, "sd_create failed: %s\n", sd_create_error()); return 1; }
     sd_stream* st = nullptr;
@@ -239,7 +313,9 @@ static int run_stream(const Args& a)
     int64_t n = 0, total = 0;
     sd_stream_info(r.st, &n, nullptr, &total);
     if (total <= 0) { fprintf(stderr, "diarization failed (%d): audio of %lld samples yields no chunk\n", SD_ERR_SHORT, (long long)n); return leave(1); }
-    print_block(ctx, r.turns, r.nt, a, r.ms);
+    std::vector<const char*> names;
+    if (a.speakers && !match_clusters(ctx, a, g, names)) return leave(1);
+    print_block(ctx, r.turns, r.nt, a, r.ms, a.speakers ? &names : nullptr);
     return leave(0);
 }
 
@@ -347,6 +423,31 @@ int main(int argc, char* argv[])
             if (end == v || *end || !(sec > 0.0) || !(sec * SD_SAMPLE_RATE >= 1.0) || sec > 86400.0) { fprintf(stderr, "usage: --stream takes a number of seconds > 0, at least one sample and at most a day (got '%s')\n", v); return 2; }
             a.stream_piece = (long long)(sec * SD_SAMPLE_RATE + 0.5);
         }
+        else if (s == "--speakers" || s == "--speakers-threshold" || s == "--enroll" || s == "--enroll-span") {
+            // checked here as well: a usage error before any context is created
+            const int need = s == "--enroll-span" ? 2 : 1;
+            if (i + need >= argc) { fprintf(stderr, "usage: %s needs %s\n", s.c_str(), need == 2 ? "START END" : "a value"); return 2; }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            if (s == "--speakers") {
+                if (!v[0]) { fprintf(stderr, "usage: --speakers takes a file name\n"); return 2; }
+                a.speakers = v;
+            } else if (s == "--speakers-threshold") {
+                a.speakers_threshold = strtod(v, &end);
+                if (end == v || *end || !(a.speakers_threshold >= 0.0 && a.speakers_threshold <= 2.0)) { fprintf(stderr, "usage: --speakers-threshold takes a number in [0, 2] (got '%s')\n", v); return 2; }
+            } else if (s == "--enroll") {
+                bool ok = v[0] != 0;
+                for (const char* p = v; *p; ++p) if (*p == '#' || *p == ' ' || (*p >= '\t' && *p <= '\r')) ok = false;
+                if (!ok) { fprintf(stderr, "usage: --enroll takes a name without white space or # (got '%s')\n", v); return 2; }
+                a.enroll = v;
+            } else {
+                const char* v2 = argv[++i];
+                char* end2 = nullptr;
+                const double t0 = strtod(v, &end), t1 = strtod(v2, &end2);
+                if (end == v || *end || end2 == v2 || *end2 || !(t0 >= 0.0) || !(t1 >= t0) || t1 > 1e300) { fprintf(stderr, "usage: --enroll-span takes START END in seconds, 0 <= START <= END (got '%s' '%s')\n", v, v2); return 2; }
+                a.enroll_spans.push_back(sd_turn{t0, t1, 0, 0});
+            }
+        }
         else if (s == "--activity-hamming") a.act_hamming = true;
         else if (s == "--activity" || s == "--activity-onset" || s == "--activity-offset" || s == "--activity-min-on" || s == "--activity-min-off") {
             // checked here too: a usage error before any context is created
@@ -372,11 +473,18 @@ int main(int argc, char* argv[])
     if (a.stream_piece > 0 && a.dump_dir) { fprintf(stderr, "usage: --dump-steps describes one whole-path inference; --stream is refused with it\n"); return 2; }
     if (a.stream_updates && a.stream_piece <= 0) { fprintf(stderr, "usage: --stream-updates needs --stream SECONDS\n"); return 2; }
     if (pos.size() >= 3 && std::string(pos[2]) == "-" && a.stream_piece <= 0) { fprintf(stderr, "usage: samples from stdin (-) need --stream SECONDS\n"); return 2; }
+    if (a.enroll && !a.speakers) { fprintf(stderr, "usage: --enroll NAME needs --speakers FILE, the voiceprint file to write\n"); return 2; }
+    if (!a.enroll && !a.enroll_spans.empty()) { fprintf(stderr, "usage: --enroll-span needs --enroll NAME\n"); return 2; }
+    if (a.speakers_threshold >= 0.0 && (!a.speakers || a.enroll)) { fprintf(stderr, "usage: --speakers-threshold needs --speakers FILE (and no --enroll)\n"); return 2; }
+    if (a.speakers && a.activity >= 0) { fprintf(stderr, "usage: --speakers names the clusters of a diarization; --activity is refused with it\n"); return 2; }
+    if (a.speakers && a.gpus > 1) { fprintf(stderr, "usage: --speakers runs on one GPU; --gpus %d is refused\n", a.gpus); return 2; }
+    if (a.enroll && (a.stream_piece > 0 || a.dump_dir)) { fprintf(stderr, "usage: --enroll runs no diarization; --stream and --dump-steps are refused with it\n"); return 2; }
     if (pos.size() < 3) {
         printf("program [segment model file] [embeding model file] [wave file]\n");   // sd.cpp:3423
         return 0;
     }
     a.seg = pos[0]; a.emb = pos[1]; a.wav = pos[2];
+    if (a.enroll) return run_enroll(a);
     if (a.stream_piece > 0) return run_stream(a);
     if (a.gpus <= 1) return run_single(a);
 

@@ -615,3 +615,100 @@ extern "C" int sd_activity_wav(sd_ctx* c, const char* path, int flags, int kind,
     return whole_wav(c, path, flags, [&](const int16_t* pcm, int64_t n) { return sd_activity(c, pcm, n, kind, turns, n_turns); },
                      [&](const float* wav, int64_t n) { return sd_activity_f32(c, wav, n, kind, turns, n_turns); }, activity_tail(kind), turns, n_turns);
 }
+
+// ------------------------------------------------------------------ voiceprint of a speaker from regions of a recording (speakers.hip)
+// the stage alone: spans -> the mask rows sd_voiceprint* hands to the embedding stage, [chunks * 3][293] with chunks = sd_num_chunks(n_samples)
+extern "C" int sd_span_masks(sd_ctx* c, int64_t n_samples, const sd_turn* spans, int64_t n_spans, int32_t label, float* h_masks)
+{
+    ENTER(c);
+    if (!h_masks || n_samples <= 0) SD_FAIL(c, SD_ERR_ARG, "sd_span_masks: bad argument");
+    if (int rc = check_spans(c, spans, n_spans, "sd_span_masks")) return rc;
+    const int64_t chunks = sd_num_chunks(n_samples, nullptr);
+    if (chunks <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)n_samples);
+    std::vector<int64_t> ss;
+    spans_to_samples(spans, n_spans, label, n_samples, ss);
+    const size_t bytes = (size_t)chunks * SD_SPEAKERS * SD_FRAMES * sizeof(float);
+    DTMP(c, dm, bytes);
+    if (int rc = run_span_masks(c, ss, chunks, n_samples, (float*)dm.p)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(h_masks, dm.p, bytes, hipMemcpyDeviceToHost));
+    return SD_OK;
+}
+
+// The tail of the sd_voiceprint* entries: chunks, span masks, the embedding stage over all items, the mean of the live rows 3c.  No segmentation
+// network runs and nothing is clustered.  stage_ms[1] = the embedding stage, [3] = the time since t0
+struct VoiceprintArgs { const sd_turn* spans; int64_t n_spans; int32_t label; double* h_emb; int64_t* n_windows; };
+static int voiceprint_wav_dev(sd_ctx* c, const DevWav& w, const VoiceprintArgs& a, double t0)
+{
+    if (!c->ew.loaded) SD_FAIL(c, SD_ERR_MODEL, "embedding model not loaded");
+    const int64_t chunks = sd_num_chunks(w.n, nullptr);
+    if (chunks <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)w.n);
+    std::vector<int64_t> ss;
+    spans_to_samples(a.spans, a.n_spans, a.label, w.n, ss);
+    const int64_t items = chunks * SD_SPEAKERS;
+    WS(c, float, d_masks, "vp_masks", items * SD_FRAMES);
+    WS(c, float, d_emb, "vp_emb", items * SD_EMB_DIM);
+    int rc;
+    const double t1 = now_ms();
+    if ((rc = run_span_masks(c, ss, chunks, w.n, d_masks))) return rc;
+    if ((rc = run_embed(c, w, d_masks, items, 0, d_emb))) return rc;
+    double mean[SD_EMB_DIM];
+    int64_t live = 0;
+    if ((rc = run_voiceprint_mean(c, d_emb, chunks, mean, &live))) return rc;      // (synchronises the stream)
+    c->stage_ms[1] += now_ms() - t1;
+    c->stage_ms[3] = now_ms() - t0;
+    if (a.n_windows) *a.n_windows = live;
+    if (live <= 0) SD_FAIL(c, SD_ERR_SHORT, "no window of the recording holds 640 selected samples (sd.cpp:44): no voiceprint");
+    memcpy(a.h_emb, mean, sizeof(mean));
+    return SD_OK;
+}
+static WavTail voiceprint_tail(const VoiceprintArgs& a)
+{
+    return [a](sd_ctx* c, const DevWav& w, double t0, std::vector<sd_turn>&) { return voiceprint_wav_dev(c, w, a, t0); };
+}
+// the whole_* drivers end in turns_out: a voiceprint has none, the empty list is given back at once
+static int no_turns(int rc, sd_turn* t) { sd_free_turns(t); return rc; }
+
+static int check_voiceprint_args(sd_ctx* c, const void* in, const VoiceprintArgs& a, const char* who)
+{
+    if (!in || !a.h_emb) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument", who);
+    return check_spans(c, a.spans, a.n_spans, who);
+}
+
+extern "C" int sd_voiceprint_dev(sd_ctx* c, const int16_t* d_pcm, int64_t n, const sd_turn* spans, int64_t n_spans, int32_t label, double* h_emb, int64_t* n_windows)
+{
+    ENTER(c);
+    const VoiceprintArgs a{spans, n_spans, label, h_emb, n_windows};
+    if (int rc = check_voiceprint_args(c, d_pcm, a, "sd_voiceprint_dev")) return rc;
+    sd_turn* t = nullptr; int64_t nt = 0;
+    return no_turns(whole_dev(c, d_pcm, n, voiceprint_tail(a), &t, &nt), t);
+}
+
+extern "C" int sd_voiceprint(sd_ctx* c, const int16_t* h_pcm, int64_t n, const sd_turn* spans, int64_t n_spans, int32_t label, double* h_emb, int64_t* n_windows)
+{
+    ENTER(c);
+    const VoiceprintArgs a{spans, n_spans, label, h_emb, n_windows};
+    if (int rc = check_voiceprint_args(c, h_pcm, a, "sd_voiceprint")) return rc;
+    return whole_pcm(c, h_pcm, n, "sd_voiceprint", [&](const int16_t* d_pcm) { return sd_voiceprint_dev(c, d_pcm, n, spans, n_spans, label, h_emb, n_windows); });
+}
+
+extern "C" int sd_voiceprint_f32(sd_ctx* c, const float* h_wav, int64_t n, const sd_turn* spans, int64_t n_spans, int32_t label, double* h_emb, int64_t* n_windows)
+{
+    ENTER(c);
+    const VoiceprintArgs a{spans, n_spans, label, h_emb, n_windows};
+    if (int rc = check_voiceprint_args(c, h_wav, a, "sd_voiceprint_f32")) return rc;
+    if (n <= 0) SD_FAIL(c, SD_ERR_ARG, "sd_voiceprint_f32: bad argument");
+    sd_turn* t = nullptr; int64_t nt = 0;
+    return no_turns(whole_f32(c, h_wav, n, voiceprint_tail(a), &t, &nt), t);
+}
+
+extern "C" int sd_voiceprint_wav(sd_ctx* c, const char* path, int flags, const sd_turn* spans, int64_t n_spans, int32_t label, double* h_emb, int64_t* n_windows)
+{
+    ENTER(c);
+    const VoiceprintArgs a{spans, n_spans, label, h_emb, n_windows};
+    if (int rc = check_voiceprint_args(c, path, a, "sd_voiceprint_wav")) return rc;
+    if (flags & ~(SD_WAV_RESAMPLE | SD_WAV_DOWNMIX | SD_WAV_ASSUME_16K)) SD_FAIL(c, SD_ERR_ARG, "sd_voiceprint_wav: bad argument");
+    sd_turn* t = nullptr; int64_t nt = 0;
+    return no_turns(whole_wav(c, path, flags, [&](const int16_t* pcm, int64_t n) { return sd_voiceprint(c, pcm, n, spans, n_spans, label, h_emb, n_windows); },
+                              [&](const float* wav, int64_t n) { return sd_voiceprint_f32(c, wav, n, spans, n_spans, label, h_emb, n_windows); }, voiceprint_tail(a), &t, &nt), t);
+}

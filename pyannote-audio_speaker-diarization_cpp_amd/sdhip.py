@@ -55,6 +55,8 @@ EXPORTS = [
     "sd_activity_scores", "sd_activity_regions", "sd_activity", "sd_activity_dev", "sd_activity_f32", "sd_activity_wav", "sd_last_activity_scores",
     "sd_stream_open", "sd_stream_push", "sd_stream_push_dev", "sd_stream_push_f32", "sd_stream_turns", "sd_stream_info", "sd_stream_read",
     "sd_stream_close", "sd_stream_sealed_chunks",
+    "sd_last_speakers", "sd_span_masks", "sd_voiceprint", "sd_voiceprint_dev", "sd_voiceprint_f32", "sd_voiceprint_wav", "sd_speaker_distances",
+    "sd_match_speakers", "sd_read_voiceprints", "sd_write_voiceprints", "sd_free_voiceprints", "sd_voiceprints_error", "sd_write_rttm_named",
 ]
 # SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
 LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
@@ -63,6 +65,7 @@ CLUSTERING_THRESHOLD_DEFAULT = float(np.float32(0.7153814381597874))      # the 
 COMM_ID_BYTES = 128
 ACTIVITY_SPEECH, ACTIVITY_OVERLAP = 0, 1      # SD_ACTIVITY_*
 ACTIVITY_KINDS = ("speech", "overlap")
+SPEAKER_MATCH_THRESHOLD_DEFAULT = CLUSTERING_THRESHOLD_DEFAULT * CLUSTERING_THRESHOLD_DEFAULT / 2      # option "speaker_match_threshold": t * t / 2
 
 
 def lib():
@@ -150,6 +153,20 @@ def lib():
     L.sd_stream_close.restype = None
     L.sd_stream_sealed_chunks.restype = i64
     L.sd_stream_sealed_chunks.argtypes = [i64]
+    L.sd_last_speakers.argtypes = [vp, vp, i64, C.POINTER(i64), vp]
+    L.sd_span_masks.argtypes = [vp, i64, vp, i64, i32, vp]
+    L.sd_voiceprint.argtypes = [vp, vp, i64, vp, i64, i32, vp, C.POINTER(i64)]
+    L.sd_voiceprint_dev.argtypes = [vp, vp, i64, vp, i64, i32, vp, C.POINTER(i64)]
+    L.sd_voiceprint_f32.argtypes = [vp, vp, i64, vp, i64, i32, vp, C.POINTER(i64)]
+    L.sd_voiceprint_wav.argtypes = [vp, C.c_char_p, C.c_int, vp, i64, i32, vp, C.POINTER(i64)]
+    L.sd_speaker_distances.argtypes = [vp, vp, i64, vp, i64, C.c_int, vp]
+    L.sd_match_speakers.argtypes = [vp, vp, i64, vp, i64, C.c_int, dbl, vp, vp]
+    L.sd_read_voiceprints.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(dbl)), C.POINTER(i64)]
+    L.sd_write_voiceprints.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), vp, i64]
+    L.sd_free_voiceprints.argtypes = [C.POINTER(C.c_char_p), C.POINTER(dbl), i64]
+    L.sd_free_voiceprints.restype = None
+    L.sd_voiceprints_error.restype = C.c_char_p
+    L.sd_write_rttm_named.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Turn), i64, C.POINTER(dbl), C.POINTER(C.c_char_p), i64]
     L.sd_format_turn.argtypes = [C.POINTER(Turn), C.c_char_p, C.c_int]
     L.sd_stage_ms.argtypes = [vp, C.POINTER(dbl)]
     L.sd_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
@@ -318,6 +335,50 @@ def write_rttm(path, uri, turns, conf=None):
         raise SdError(rc, "cannot write " + path)
 
 
+def read_voiceprints(path):
+    """sd_read_voiceprints: a voiceprint file -> (names, emb [M][192] float64).  Host-only; a malformed line raises with its line number."""
+    names, emb, M = C.POINTER(C.c_char_p)(), C.POINTER(C.c_double)(), C.c_int64(0)
+    rc = lib().sd_read_voiceprints(str(path).encode(), C.byref(names), C.byref(emb), C.byref(M))
+    if rc:
+        raise SdError(rc, lib().sd_voiceprints_error().decode())
+    out_names = [names[i].decode() for i in range(M.value)]
+    out = np.ctypeslib.as_array(emb, shape=(M.value, EMB_DIM)).copy() if M.value else np.zeros((0, EMB_DIM), np.float64)
+    lib().sd_free_voiceprints(names, emb, M)
+    return out_names, out
+
+
+def write_voiceprints(path, names, emb):
+    """sd_write_voiceprints: names [M] (no white space), emb [M][192] -> the text file (%.17g: reads back bit for bit).  Host-only."""
+    emb = np.ascontiguousarray(emb, np.float64).reshape(-1, EMB_DIM)
+    names = [str(n).encode() for n in names]
+    if len(names) != len(emb):
+        raise SdError(1, "write_voiceprints: %d names for %d voiceprints" % (len(names), len(emb)))
+    arr = (C.c_char_p * max(len(names), 1))(*names)
+    rc = lib().sd_write_voiceprints(str(path).encode(), arr, _ptr(emb), len(names))
+    if rc:
+        raise SdError(rc, lib().sd_voiceprints_error().decode())
+
+
+def write_rttm_named(path, uri, turns, names, conf=None):
+    """sd_write_rttm_named: names[k] (None = SPEAKER_kk) is the speaker field of the turns with label k"""
+    arr = _turn_array(turns)
+    nm = (C.c_char_p * max(len(names), 1))(*[None if n is None else str(n).encode() for n in names])
+    cc = None if conf is None else (C.c_double * max(len(turns), 1))(*[float(x) for x in conf])
+    rc = lib().sd_write_rttm_named(str(path).encode(), uri.encode(), arr, len(turns), cc, nm, len(names))
+    if rc:
+        raise SdError(rc, "cannot write " + str(path))
+
+
+def _span_array(spans):
+    """[(start, end[, label])] or None -> (Turn array or None, count)"""
+    if spans is None:
+        return None, 0
+    arr = (Turn * max(len(spans), 1))()
+    for i, t in enumerate(spans):
+        arr[i] = Turn(float(t[0]), float(t[1]), int(t[2]) if len(t) > 2 else 0, 0)
+    return arr, len(spans)
+
+
 def relabel_turns(turns, mode="pyannote"):
     """'pyannote': labels that occur, sorted by their string, -> 0, 1, ... (SPEAKER_00 ...); 'first': order of first appearance"""
     arr = _turn_array(turns)
@@ -382,7 +443,7 @@ class Stream:
         p = C.POINTER(Turn)()
         n = C.c_int64(0)
         self._d._chk(lib().sd_stream_turns(self._handle(), C.byref(p), C.byref(n)))
-        return self._d._turns(p, n)
+        return self._d._clustered(p, n)
 
     def info(self):
         """(samples pushed, chunks sealed, chunks in all)"""
@@ -541,7 +602,72 @@ class Diarizer:
         hard = np.zeros((c, S), np.int32)
         K = C.c_int32(0)
         self._chk(lib().sd_clustering_ex(self._h, _ptr(emb), c, d, num_clusters, min_clusters, max_clusters, _ptr(hard), C.byref(K)))
+        self._last_d = d
         return hard, int(K.value)
+
+    # ---- known speakers (sd_last_speakers, sd_span_masks, sd_voiceprint*, sd_speaker_distances, sd_match_speakers)
+    def last_speakers(self):
+        """sd_last_speakers: (centroids [K][d] float64, counts [K] int64) of the last call that clustered; row k = raw label k.  d = 192 unless the last
+        call was clustering() on rows of another length"""
+        K = C.c_int64(0)
+        self._chk(lib().sd_last_speakers(self._h, None, 0, C.byref(K), None))
+        d = getattr(self, "_last_d", EMB_DIM)
+        cen, cnt = np.zeros((K.value, d), np.float64), np.zeros(K.value, np.int64)
+        self._chk(lib().sd_last_speakers(self._h, _ptr(cen), K.value, C.byref(K), _ptr(cnt)))
+        return cen, cnt
+
+    def span_masks(self, n_samples, spans, label=-1):
+        """sd_span_masks: the mask rows [chunks * 3][293] sd_voiceprint* gives the embedding stage for spans [(start, end[, label])] (None = everything)"""
+        arr, ns = _span_array(spans)
+        c, _ = num_chunks(int(n_samples))
+        out = np.zeros((max(c, 0) * SPEAKERS, FRAMES), np.float32)
+        self._chk(lib().sd_span_masks(self._h, int(n_samples), arr, ns, int(label), _ptr(out) if out.size else None))
+        return out
+
+    def _voiceprint(self, call, spans, label):
+        arr, ns = _span_array(spans)
+        emb, nw = np.zeros(EMB_DIM, np.float64), C.c_int64(0)
+        self._chk(call(arr, ns, int(label), _ptr(emb), C.byref(nw)))
+        return emb, int(nw.value)
+
+    def voiceprint(self, pcm, spans=None, label=-1):
+        """sd_voiceprint: (embedding [192] float64, windows averaged) of the samples of `pcm` inside the spans with this label (label < 0: all)"""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        return self._voiceprint(lambda *a: lib().sd_voiceprint(self._h, _ptr(pcm), len(pcm), *a), spans, label)
+
+    def voiceprint_dev(self, d_pcm_ptr, n_samples, spans=None, label=-1):
+        return self._voiceprint(lambda *a: lib().sd_voiceprint_dev(self._h, C.c_void_p(d_pcm_ptr or None), n_samples, *a), spans, label)
+
+    def voiceprint_f32(self, wav, spans=None, label=-1):
+        wav = np.ascontiguousarray(wav, np.float32)
+        return self._voiceprint(lambda *a: lib().sd_voiceprint_f32(self._h, _ptr(wav), len(wav), *a), spans, label)
+
+    def voiceprint_wav(self, path, spans=None, label=-1, resample=False, downmix=False, assume_16k=False):
+        flags = (1 if resample else 0) | (2 if downmix else 0) | (4 if assume_16k else 0)
+        return self._voiceprint(lambda *a: lib().sd_voiceprint_wav(self._h, str(path).encode(), flags, *a), spans, label)
+
+    def speaker_distances(self, gallery, centroids=None):
+        """sd_speaker_distances: [K][M] cosine distances (sequential sums) of the centroids (None = the last job's) to the gallery rows"""
+        gal = np.ascontiguousarray(gallery, np.float64)
+        M, d = gal.shape
+        cen = None if centroids is None else np.ascontiguousarray(centroids, np.float64)
+        K = self.last_speakers()[0].shape[0] if cen is None else cen.shape[0]
+        assert cen is None or cen.shape == (K, d)
+        out = np.zeros((K, M), np.float64)
+        self._chk(lib().sd_speaker_distances(self._h, None if cen is None else _ptr(cen), K, _ptr(gal), M, d, _ptr(out)))
+        return out
+
+    def match_speakers(self, gallery, centroids=None, threshold=None):
+        """sd_match_speakers: (match [K] int32: gallery row or -1, distance [K] or NaN); threshold None = option "speaker_match_threshold" """
+        gal = np.ascontiguousarray(gallery, np.float64)
+        M, d = gal.shape
+        cen = None if centroids is None else np.ascontiguousarray(centroids, np.float64)
+        K = self.last_speakers()[0].shape[0] if cen is None else cen.shape[0]
+        assert cen is None or cen.shape == (K, d)
+        match, best = np.zeros(K, np.int32), np.zeros(K, np.float64)
+        self._chk(lib().sd_match_speakers(self._h, None if cen is None else _ptr(cen), K, _ptr(gal), M, d,
+                                          float("nan") if threshold is None else float(threshold), _ptr(match), _ptr(best)))
+        return match, best
 
     # ---- a15-a17
     def reconstruct(self, seg, binarized, hard, count, n_samples):
@@ -561,20 +687,25 @@ class Diarizer:
             lib().sd_free_turns(p)
         return out
 
+    def _clustered(self, p, n):
+        """turns of a call that clustered 192-dimensional embeddings (last_speakers reads the row length)"""
+        self._last_d = EMB_DIM
+        return self._turns(p, n)
+
     # ---- whole path
     def diarize(self, pcm):
         pcm = np.ascontiguousarray(pcm, np.int16)
         p = C.POINTER(Turn)()
         n = C.c_int64(0)
         self._chk(lib().sd_diarize(self._h, _ptr(pcm), len(pcm), C.byref(p), C.byref(n)))
-        return self._turns(p, n)
+        return self._clustered(p, n)
 
     def diarize_f32(self, wav):
         wav = np.ascontiguousarray(wav, np.float32)
         p = C.POINTER(Turn)()
         n = C.c_int64(0)
         self._chk(lib().sd_diarize_f32(self._h, _ptr(wav), len(wav), C.byref(p), C.byref(n)))
-        return self._turns(p, n)
+        return self._clustered(p, n)
 
     def set_dump_dir(self, path, level=1):
         """sd_set_dump_dir: the reference's WRITE_DATA items as <path>/cpp_<item>.txt from the next whole-path call on (None = off)"""
@@ -585,7 +716,7 @@ class Diarizer:
         p = C.POINTER(Turn)()
         n = C.c_int64(0)
         self._chk(lib().sd_diarize_wav(self._h, str(path).encode(), (1 if resample else 0) | (2 if downmix else 0) | (4 if assume_16k else 0), C.byref(p), C.byref(n)))
-        return self._turns(p, n)
+        return self._clustered(p, n)
 
     def resample(self, wav, in_sr, out_sr=16000):
         wav = np.ascontiguousarray(wav, np.float32)
@@ -599,7 +730,7 @@ class Diarizer:
         p = C.POINTER(Turn)()
         n = C.c_int64(0)
         self._chk(lib().sd_diarize_dev(self._h, C.c_void_p(d_pcm_ptr), n_samples, C.byref(p), C.byref(n)))
-        return self._turns(p, n)
+        return self._clustered(p, n)
 
     def shard_infer_dev(self, d_pcm_shard_ptr, first_sample, shard_samples, n_total, chunk_lo, chunk_hi, d_seg_ptr, d_emb_ptr):
         self._chk(lib().sd_shard_infer_dev(self._h, C.c_void_p(d_pcm_shard_ptr), first_sample, shard_samples, n_total,
@@ -622,14 +753,14 @@ class Diarizer:
         p = C.POINTER(Turn)()
         n = C.c_int64(0)
         self._chk(lib().sd_diarize_sharded_dev(self._h, C.c_void_p(d_pcm_shard_ptr or None), first_sample, shard_samples, n_total, C.byref(p), C.byref(n)))
-        return self._turns(p, n)
+        return self._clustered(p, n)
 
     def diarize_sharded(self, pcm_shard, first_sample, n_total):
         pcm_shard = np.ascontiguousarray(pcm_shard, np.int16)
         p = C.POINTER(Turn)()
         n = C.c_int64(0)
         self._chk(lib().sd_diarize_sharded(self._h, _ptr(pcm_shard), first_sample, len(pcm_shard), n_total, C.byref(p), C.byref(n)))
-        return self._turns(p, n)
+        return self._clustered(p, n)
 
     def stream(self):
         """sd_stream_open: incremental diarization of a growing recording on this context"""
@@ -711,7 +842,7 @@ class Diarizer:
         n = C.c_int64(0)
         self._chk(lib().sd_finalize_dev(self._h, C.c_void_p(d_seg_ptr), C.c_void_p(d_emb_ptr), chunks, n_samples,
                                         C.byref(p), C.byref(n)))
-        return self._turns(p, n)
+        return self._clustered(p, n)
 
     def set_planted(self, d_scores_ptr, d_emb_ptr, chunk_lo, chunks):
         """planted workload hook: device pointers (0 = none) for chunks [chunk_lo, chunk_lo + chunks)"""
