@@ -333,6 +333,39 @@ const char* sd_voiceprints_error(void);     /* reason for the last non-OK return
 /* sd_write_rttm_ex with names: the speaker field of a turn with label k is names[k] where 0 <= k < K and names[k] != NULL, SPEAKER_kk otherwise */
 int sd_write_rttm_named(const char* path, const char* uri, const sd_turn* turns, int64_t n_turns, const double* conf /* or NULL */, const char* const* names /*[K]*/, int64_t K);     /* sd.cpp:3433-3441 */
 
+/* ---- enrolled speakers: the clustering itself knows the people the caller has enrolled.  With a gallery V [M][d] set, every following call of this
+ * ctx that clusters -- sd_clustering (not with num_clusters / min_clusters / max_clusters), the whole path, sd_finalize_dev, sd_stream_turns, rank 0 of a
+ * sharded job -- follows this rule; E = the [rows][d] embeddings, its N train rows those whose first element is not NaN (sd.cpp:2224), ascending;
+ * t = option "speaker_match_threshold":
+ *  1 nearest: dist(x, m) = 1 - dot / (sqrt(m1) * sqrt(m2)), three sequential f64 sums (sd.cpp:476-498); g(x) = the smallest m that attains the minimum.
+ *    A zero-norm train row: SD_ERR_NUMERIC.
+ *  2 claim: x is claimed by g(x) iff dist <= t (inclusive, as sd_match_speakers); t = 2 claims every row: closed-set operation.
+ *  3 used speakers: U = the distinct g of the claimed rows, ascending; G = |U|.  G = 0: the plain job, bit for bit.
+ *  4 size rule: R = the unclaimed train rows, N' = |R|; mcs = min(min_cluster_size, max(1, round(0.1 * N))) -- from N, not N'.
+ *  5 the rows of R are clustered as the plain job clusters its rows (f32-rounded norm, "clustering_method" / "clustering_threshold"); N' = 1: one
+ *    cluster of one row; N' = 0: none.
+ *  6 size split with mcs: candidates = V[U[0]] .. V[U[G-1]], then the means (un-normalised rows, member order) of the large clusters in ascending id;
+ *    every small cluster goes to the nearest candidate (float minVal, dd < minVal, sd.cpp:2396, in that order).  One that goes to an enrolled candidate
+ *    contributes to no mean; one that goes to a large cluster joins it.
+ *  7 the surviving new clusters are renumbered 0 .. L-1 in sorted-id order (sd.cpp:519-548), their means recomputed over the merged membership in
+ *    ascending row order (sd.cpp:2149-2167).
+ *  8 assignment: ALL rows of E over the table [V[U[0]], .., V[U[G-1]], mean_0, .., mean_{L-1}], K = G + L, first maximum wins (sd.cpp:293-316), or
+ *    the constrained arg-max under "constrained_assignment".  A label is a row of this table: enrolled people first in gallery order, then strangers.
+ *  9 sd_last_speakers returns this table; the count of an enrolled row = the train rows it claimed in step 2, of a new row = its members.
+ *    sd_last_enrolled returns [U[0], .., U[G-1], -1 x L].  sd_last_confidence works unchanged.
+ * Refused with SD_ERR_ARG before anything is touched: a gallery together with any of the three cluster-count constraints, a gallery while a dump
+ * directory is set (the step files describe the reference's flow), a clustering call whose d is not the gallery's. */
+/* enrol a gallery for every following call of this ctx that clusters; h_gallery == NULL or M == 0 clears it.  The ctx keeps its own device copy.
+ * A non-finite value: SD_ERR_ARG; a zero-norm row: SD_ERR_NUMERIC; the previous gallery stays in both cases. */
+int sd_set_enrolled(sd_ctx*, const double* h_gallery /*[M][d]*/, int64_t M, int d);     /* sd.cpp:476-498 / 2149-2212 */
+int sd_enrolled_info(const sd_ctx*, int64_t* M, int* d);     /* 0, 0 when none; sd.cpp:476-498 / 2149-2212 */
+/* step 1 alone: h_gallery == NULL = the enrolled one (M and d must be its).  h_best [N], h_dist [N] (either may be NULL): the bits of sd_speaker_distances for
+ * the same pair, the first minimum.  No N x M table exists: device memory beyond the operands is O(N + M). */
+int sd_nearest_speakers(sd_ctx*, const double* h_X /*[N][d], no NaN rows*/, int64_t N, const double* h_gallery, int64_t M, int d,
+                        int32_t* h_best, double* h_dist);     /* sd.cpp:476-498 / 2149-2212 */
+/* gallery row of every label of the last call that clustered, -1 for a speaker nobody enrolled; all -1 without a gallery */
+int sd_last_enrolled(const sd_ctx*, int32_t* h_rows /*[cap]*/, int64_t cap, int64_t* K);     /* sd.cpp:476-498 / 2149-2212 */
+
 /* ---- a18: the reference's output line (sd.cpp:3439) */
 int sd_format_turn(const sd_turn* t, char* buf, int cap);
 

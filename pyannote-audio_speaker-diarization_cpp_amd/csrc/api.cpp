@@ -59,6 +59,7 @@ extern "C" void sd_destroy(sd_ctx* c)
     while (!c->streams.empty()) sd_stream_close(c->streams.back());      // streams still open own device memory of their own
     for (void* p : c->owned) (void)hipFree(p);
     for (auto& kv : c->ws) kv.second.release();
+    c->enr_gal.release(); c->enr_m2.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -550,6 +551,87 @@ extern "C" int sd_match_speakers(sd_ctx* c, const double* h_cen, int64_t K, cons
         h_match[k] = (int32_t)m; taken[(size_t)m] = 1;
         if (h_dist_best) h_dist_best[k] = std::get<0>(p);
     }
+    return SD_OK;
+}
+
+// ------------------------------------------------------------------ enrolled speakers: the gallery run_clustering consults (cluster.hip), and its first step alone
+// every value a number (SD_ERR_ARG), every row with a non-zero sequential sum of squares (SD_ERR_NUMERIC; the reference throws, sd.cpp:493-495)
+static int check_gallery(sd_ctx* c, const double* g, int64_t M, int d, const char* who)
+{
+    for (int64_t m = 0; m < M; ++m) {
+        double s = 0.0;
+        for (int i = 0; i < d; ++i) { const double v = g[m * d + i]; if (!std::isfinite(v)) SD_FAIL(c, SD_ERR_ARG, "%s: gallery row %lld holds a value that is not a finite number", who, (long long)m); s += v * v; }
+        if (s == 0.0) SD_FAIL(c, SD_ERR_NUMERIC, "%s: gallery row %lld has zero magnitude (reference throws, sd.cpp:493-495)", who, (long long)m);
+        if (!std::isfinite(s)) SD_FAIL(c, SD_ERR_ARG, "%s: the squared norm of gallery row %lld overflows", who, (long long)m);
+    }
+    return SD_OK;
+}
+
+extern "C" int sd_set_enrolled(sd_ctx* c, const double* h_gallery, int64_t M, int d)
+{
+    ENTER(c);
+    if (!h_gallery || M == 0) {                                              // clear
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->enr_gal.release(); c->enr_m2.release(); c->enr_host.clear(); c->enr_host.shrink_to_fit();
+        c->enr_M = 0; c->enr_d = 0;
+        return SD_OK;
+    }
+    if (M < 0 || M > 0x7fffffff || d < 1) SD_FAIL(c, SD_ERR_ARG, "sd_set_enrolled: bad argument (1 <= M < 2^31, d >= 1)");
+    if (int rc = check_gallery(c, h_gallery, M, d, "sd_set_enrolled")) return rc;
+    DevBuf gal, m2;                                                          // the previous gallery stays until the new one is complete
+    if (gal.reserve((size_t)M * d * sizeof(double)) || m2.reserve((size_t)M * sizeof(double))) { gal.release(); m2.release(); SD_FAIL(c, SD_ERR_HIP, "sd_set_enrolled: hipMalloc of the gallery failed"); }
+    int rc = SD_OK;
+    if (hipMemcpyAsync(gal.p, h_gallery, (size_t)M * d * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) { c->err = "sd_set_enrolled: upload failed"; rc = SD_ERR_HIP; }
+    if (!rc) rc = run_gallery_norms(c, gal.as<double>(), M, d, m2.as<double>());
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "sd_set_enrolled: hipStreamSynchronize failed"; rc = SD_ERR_HIP; }
+    if (rc) { gal.release(); m2.release(); return rc; }
+    c->enr_gal.release(); c->enr_m2.release();
+    c->enr_gal = gal; c->enr_m2 = m2;
+    c->enr_host.assign(h_gallery, h_gallery + (size_t)M * d);
+    c->enr_M = M; c->enr_d = d;
+    return SD_OK;
+}
+
+extern "C" int sd_enrolled_info(const sd_ctx* c, int64_t* M, int* d)
+{
+    if (!c) return SD_ERR_ARG;
+    if (M) *M = c->enr_M;
+    if (d) *d = c->enr_d;
+    return SD_OK;
+}
+
+extern "C" int sd_nearest_speakers(sd_ctx* c, const double* h_X, int64_t N, const double* h_gallery, int64_t M, int d, int32_t* h_best, double* h_dist)
+{
+    ENTER(c);
+    if (!h_X || N < 1 || d < 1) SD_FAIL(c, SD_ERR_ARG, "sd_nearest_speakers: bad argument (N, d >= 1)");
+    const double* d_gal; const double* d_m2;
+    if (!h_gallery) {
+        if (c->enr_M < 1) SD_FAIL(c, SD_ERR_ARG, "sd_nearest_speakers: no gallery is enrolled on this context");
+        if (M != c->enr_M || d != c->enr_d) SD_FAIL(c, SD_ERR_ARG, "sd_nearest_speakers: the enrolled gallery has %lld rows of %d dimensions, not %lld of %d", (long long)c->enr_M, c->enr_d, (long long)M, d);
+        d_gal = c->enr_gal.as<double>(); d_m2 = c->enr_m2.as<double>();
+    } else {
+        if (M < 1 || M > 0x7fffffff) SD_FAIL(c, SD_ERR_ARG, "sd_nearest_speakers: bad argument (1 <= M < 2^31)");
+        if (int rc = check_gallery(c, h_gallery, M, d, "sd_nearest_speakers")) return rc;
+        WS(c, double, t_gal, "spk_gallery", M * d); WS(c, double, t_m2, "ng_m2", M);
+        HIPCHK(c, hipMemcpyAsync(t_gal, h_gallery, (size_t)M * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (int rc = run_gallery_norms(c, t_gal, M, d, t_m2)) return rc;
+        d_gal = t_gal; d_m2 = t_m2;
+    }
+    WS(c, double, d_X, "ng_X", N * d); WS(c, int, d_best, "ng_best", N); WS(c, double, d_dist, "ng_dist", N);
+    HIPCHK(c, hipMemcpyAsync(d_X, h_X, (size_t)N * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (int rc = run_nearest_gallery(c, d_X, nullptr, N, d_gal, d_m2, M, d, d_best, d_dist)) return rc;
+    static_assert(sizeof(int) == sizeof(int32_t), "labels are 32-bit");
+    if (h_best) HIPCHK(c, hipMemcpy(h_best, d_best, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (h_dist) HIPCHK(c, hipMemcpy(h_dist, d_dist, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+    return SD_OK;
+}
+
+extern "C" int sd_last_enrolled(const sd_ctx* c, int32_t* h_rows, int64_t cap, int64_t* K)
+{
+    if (!c || cap < 0) return SD_ERR_ARG;
+    const int64_t k = c->last_cen_K;
+    if (K) *K = k;
+    for (int64_t i = 0; i < k && i < cap; ++i) if (h_rows) h_rows[i] = i < (int64_t)c->last_enrolled.size() ? c->last_enrolled[(size_t)i] : -1;
     return SD_OK;
 }
 

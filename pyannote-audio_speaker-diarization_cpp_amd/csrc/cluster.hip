@@ -226,15 +226,15 @@ static double cos_dist_host(const double* a, const double* b, int d, bool* err) 
     return 1.0 - (dot / (sqrt(m1) * sqrt(m2)));
 }
 
-// group rows by label (ascending row order inside each group)
+// group rows by label (ascending row order inside each group); a row with a negative label belongs to no group
 static void group_by_label(const std::vector<int>& lab, int nl, std::vector<int>& order, std::vector<int>& off)
 {
     off.assign((size_t)nl + 1, 0);
-    for (int v : lab) off[(size_t)v + 1]++;
+    for (int v : lab) if (v >= 0) off[(size_t)v + 1]++;
     for (int k = 0; k < nl; ++k) off[(size_t)k + 1] += off[(size_t)k];
-    order.resize(lab.size());
+    order.resize((size_t)off[(size_t)nl]);
     std::vector<int> pos(off.begin(), off.end() - 1);
-    for (size_t i = 0; i < lab.size(); ++i) order[(size_t)pos[(size_t)lab[i]]++] = (int)i;
+    for (size_t i = 0; i < lab.size(); ++i) if (lab[i] >= 0) order[(size_t)pos[(size_t)lab[i]]++] = (int)i;
 }
 
 // Constrained number of clusters -- the branch the reference leaves unimplemented (assert(false), sd.cpp:2368-2369);
@@ -270,16 +270,232 @@ static void constrained_recut(const std::vector<double>& Z, int64_t N, double th
     for (int64_t i = 0; i < N; ++i) lab[(size_t)i] = t1[(size_t)i] - 1;
 }
 
+// ---------------------------------------------------------------- the steps of run_clustering: the plain flow and the enrolled flow call the same ones
+// a10 / a11 / a12 / a13: rows idx[0 .. N) of d_emb gathered (X) and normalised with the f32 norm (Xn), then the labels of the dendrogram cut, 0-based, nl of them.
+// Method, threshold and minimum cluster size are the three hyper-parameters of Clustering.py:251-276; their defaults are the constants the
+// reference hard-codes (sd.cpp:2049-2056: centroid, the float-typed threshold promoted to double, 15).  Clustering.py:317-333: centroid, median and ward
+// are euclidean-only and run on the unit-normalised rows (Xn, with the port's f32 norm); the other four run on the rows as they are with the cosine metric.
+static int cluster_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, int d, double** Xout, double** Xnout, std::vector<int>& lab, int* nlout,
+                        std::vector<double>* Zh)
+{
+    const int64_t N = (int64_t)idx.size();
+    WS(c, int, d_tidx, "cl_tidx", N);
+    WS(c, double, X, "cl_X", N * d);
+    WS(c, double, Xn, "cl_Xn", N * d);
+    HIPCHK(c, hipMemcpyAsync(d_tidx, idx.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_gather_normalize, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, c->stream, d_emb, d_tidx, N, d, X, Xn);
+    KCHECK(c);
+    const int method = c->clustering_method;
+    const bool euclid = method == SD_LINKAGE_CENTROID || method == SD_LINKAGE_MEDIAN || method == SD_LINKAGE_WARD;
+    int rc = run_cluster_labels(c, euclid ? Xn : X, N, d, c->clustering_threshold, lab, Zh, method, euclid ? SD_METRIC_EUCLIDEAN : SD_METRIC_COSINE);
+    if (rc) return rc;
+    int nl = 0;
+    for (auto& v : lab) { v -= 1; if (v + 1 > nl) nl = v + 1; }
+    *Xout = X; *Xnout = Xn; *nlout = nl;
+    return SD_OK;
+}
+
+// a11: which clusters reach mcs rows (clusters without a row are neither)
+static void split_by_size(const std::vector<int>& off, int nl, size_t mcs, std::vector<int>& large, std::vector<int>& small)
+{
+    large.clear(); small.clear();
+    for (int k = 0; k < nl; ++k) {
+        const size_t cnt = (size_t)(off[(size_t)k + 1] - off[(size_t)k]);
+        if (cnt == 0) continue;
+        if (cnt >= mcs) large.push_back(k); else small.push_back(k);
+    }
+}
+
+// a11: every small cluster goes to the nearest candidate -- first the G rows of `enrolled` (host, [G][d]; the enrolled flow), then the large clusters in
+// ascending id -- by the cosine distance of the means of the UN-normalised rows (sd.cpp:2386), the reference's float minVal loop (sd.cpp:2396).  The rows of a
+// cluster that goes to an enrolled candidate get label -1; the labels that survive are renumbered 0 .. nl - 1 in sorted-id order (findUniqueClusters,
+// sd.cpp:519-548).
+static int reassign_small(sd_ctx* c, const double* X, int d, const std::vector<int>& order, const std::vector<int>& off, const std::vector<int>& large,
+                          const std::vector<int>& small, const double* enrolled, int G, std::vector<int>& lab, int& nl)
+{
+    const size_t N = order.size();
+    WS(c, int, d_order, "cl_order", N);
+    WS(c, int, d_off, "cl_off", nl + 1);
+    WS(c, double, d_cen, "cl_cen", (size_t)nl * d);
+    HIPCHK(c, hipMemcpyAsync(d_order, order.data(), N * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_off, off.data(), (size_t)(nl + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_cluster_means, dim3(nl), dim3(((d + 63) / 64) * 64), 0, c->stream, X, d, d_order, d_off, d_cen);   // means of UN-normalised rows (sd.cpp:2386)
+    KCHECK(c);
+    std::vector<double> cen((size_t)nl * d);
+    HIPCHK(c, hipMemcpyAsync(cen.data(), d_cen, cen.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    bool err = false;
+    std::vector<int> remap((size_t)nl);
+    for (int k = 0; k < nl; ++k) remap[(size_t)k] = k;
+    for (int sk : small) {
+        float minVal = FLT_MAX; int best = -1;                                      // float accumulator, sd.cpp:2396
+        for (size_t a = 0; a < (size_t)G + large.size(); ++a) {
+            const double* cand = a < (size_t)G ? enrolled + a * (size_t)d : &cen[(size_t)large[a - (size_t)G] * d];
+            const double dd = cos_dist_host(cand, &cen[(size_t)sk * d], d, &err);
+            if (dd < minVal) { minVal = (float)dd; best = (int)a; }
+        }
+        if (best >= 0) remap[(size_t)sk] = best < G ? -1 : large[(size_t)(best - G)];
+    }
+    if (err) SD_FAIL(c, SD_ERR_NUMERIC, "zero-magnitude cluster centroid (reference throws, sd.cpp:493-495)");
+    for (auto& v : lab) v = remap[(size_t)v];
+    // findUniqueClusters: renumber 0..K-1 in sorted-id order (sd.cpp:519-548)
+    std::vector<int> seen((size_t)nl, -1);
+    for (int v : lab) if (v >= 0) seen[(size_t)v] = 0;
+    int nk = 0;
+    for (int k = 0; k < nl; ++k) if (seen[(size_t)k] == 0) seen[(size_t)k] = nk++;
+    for (auto& v : lab) if (v >= 0) v = seen[(size_t)v];
+    nl = nk;
+    return SD_OK;
+}
+
+// a14, first half: the means of the nl final clusters (un-normalised rows of X, members in ascending row order) into rows [G, G + nl) of the centroid table
+// "cl_cen"; rows [0, G) are left to the caller (the enrolled flow's voiceprints).  order / off describe the membership afterwards.
+static int final_means(sd_ctx* c, const double* X, int d, const std::vector<int>& lab, int nl, int G, std::vector<int>& order, std::vector<int>& off, double** cen_out)
+{
+    group_by_label(lab, nl, order, off);
+    WS(c, int, d_order2, "cl_order", std::max<size_t>(order.size(), 1));      // (no new cluster at all: the enrolled flow with every row claimed)
+    WS(c, int, d_off2, "cl_off", nl + 1);
+    WS(c, double, d_cen2, "cl_cen", (size_t)(G + nl) * d);
+    HIPCHK(c, hipMemcpyAsync(d_order2, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_off2, off.data(), (size_t)(nl + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (nl > 0) {
+        hipLaunchKernelGGL(k_cluster_means, dim3(nl), dim3(((d + 63) / 64) * 64), 0, c->stream, X, d, d_order2, d_off2, d_cen2 + (size_t)G * d);
+        KCHECK(c);
+    }
+    *cen_out = d_cen2;
+    return SD_OK;
+}
+
+// a14, second half: cosine cdist of ALL M rows to the K centroids, arg-max (or the constrained arg-max); the centroids and their counts become what
+// sd_last_speakers describes.  *soft_out (may be NULL) = the [M][K] score table where one was written, else null.
+static int assign_all(sd_ctx* c, const double* d_emb, int64_t M, int d, const double* d_cen2, int K, const std::vector<int64_t>& counts,
+                      std::vector<int>& hard, int* Kout, std::vector<double>* soft_best, double** soft_out)
+{
+    const bool dumping = !c->dump_dir.empty();
+    WS(c, int, d_hard, "cl_hard", M);
+    WS(c, int, d_err, "cl_err", 4);
+    HIPCHK(c, hipMemsetAsync(d_err, 0, sizeof(int), c->stream));
+    const bool constrained_assign = c->constrained_assignment && (M % SD_SPEAKERS) == 0;
+    // the full [M][K] score table only for the constrained assignment (it needs every score); the confidence needs the best score alone
+    double* d_soft = nullptr; double* d_best = nullptr;
+    if (constrained_assign || dumping) { WS(c, double, t_soft, "cl_soft", (size_t)M * K); d_soft = t_soft; }
+    if (constrained_assign || soft_best) { WS(c, double, t_best, "cl_best", M); d_best = t_best; }
+    hipLaunchKernelGGL(k_assign, dim3((unsigned)M), dim3(64), 0, c->stream, d_emb, M, d, d_cen2, K, d_hard, d_err, d_soft, d_best);
+    KCHECK(c);
+    int herr = 0;
+    HIPCHK(c, hipMemcpyAsync(hard.data(), d_hard, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&herr, d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (soft_best) HIPCHK(c, hipMemcpyAsync(soft_best->data(), d_best, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    c->last_cen.resize((size_t)K * d);                              // the centroids ride this synchronisation (sd_last_speakers)
+    HIPCHK(c, hipMemcpyAsync(c->last_cen.data(), d_cen2, c->last_cen.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (herr) SD_FAIL(c, SD_ERR_NUMERIC, "zero-magnitude embedding or centroid in assignment (reference throws, sd.cpp:493-495)");
+    if (constrained_assign) {
+        // Clustering.py:83: NaN (rows without an embedding) -> the smallest soft score of the whole recording
+        std::vector<double> hs((size_t)M * K);
+        HIPCHK(c, hipMemcpy(hs.data(), d_soft, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
+        double fill = INFINITY;
+        for (double x : hs) if (x == x && x < fill) fill = x;
+        if (fill == INFINITY) fill = 0.0;
+        const int64_t chunks = M / SD_SPEAKERS;
+        if (K <= LSAP_MAXC) {
+            hipLaunchKernelGGL(k_constrained_argmax, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, c->stream, d_soft, chunks, K, fill, d_hard);
+            KCHECK(c);
+            HIPCHK(c, hipMemcpyAsync(hard.data(), d_hard, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        } else SD_FAIL(c, SD_ERR_ARG, "constrained assignment supports up to %d clusters (found %d)", LSAP_MAXC, K);
+        if (soft_best)                                             // confidence follows the cluster actually assigned
+            for (int64_t i = 0; i < M; ++i) (*soft_best)[(size_t)i] = hard[(size_t)i] >= 0 ? hs[(size_t)i * K + hard[(size_t)i]] : NAN;
+    }
+    if (Kout) *Kout = K;
+    c->last_cen_counts = counts;
+    c->last_cen_d = d;
+    c->last_cen_K = K;
+    if (soft_out) *soft_out = d_soft;
+    return SD_OK;
+}
+
+// the refusals of a call that clusters under an enrolled gallery (sdhip.h); nothing is touched
+int enrolled_refusal(sd_ctx* c, int d, int num_clusters, int min_clusters, int max_clusters)
+{
+    if (c->enr_M <= 0) return SD_OK;
+    if (num_clusters != -1 || min_clusters != -1 || max_clusters != -1)
+        SD_FAIL(c, SD_ERR_ARG, "a gallery is enrolled: num_clusters / min_clusters / max_clusters have no meaning next to enrolled speakers (clear one of the two)");
+    if (!c->dump_dir.empty()) SD_FAIL(c, SD_ERR_ARG, "a gallery is enrolled: the step files describe the reference's flow (clear the gallery or the dump directory)");
+    if (d != c->enr_d) SD_FAIL(c, SD_ERR_ARG, "the enrolled gallery has rows of %d dimensions, this call clusters rows of %d", c->enr_d, d);
+    return SD_OK;
+}
+
+// The enrolled flow (sdhip.h, "enrolled speakers", steps 1 - 9).  tidx = the N >= 1 train rows.  *taken = false: no row was claimed (G = 0), nothing of the
+// context's results has been written and the caller goes on with the plain flow.
+static int clustering_enrolled(sd_ctx* c, const double* d_emb, int64_t M, int d, const std::vector<int>& tidx, std::vector<int>& hard, int* Kout,
+                               std::vector<double>* soft_best, bool* taken)
+{
+    *taken = false;
+    const int64_t N = (int64_t)tidx.size();
+    // 1 nearest
+    WS(c, int, d_tidx, "ng_tidx", N);
+    WS(c, int, d_best, "ng_best", N);
+    WS(c, double, d_dist, "ng_dist", N);
+    HIPCHK(c, hipMemcpyAsync(d_tidx, tidx.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    int rc = run_nearest_gallery(c, d_emb, d_tidx, N, c->enr_gal.as<double>(), c->enr_m2.as<double>(), c->enr_M, d, d_best, d_dist);
+    if (rc) return rc;
+    std::vector<int> g((size_t)N);
+    std::vector<double> gd((size_t)N);
+    HIPCHK(c, hipMemcpy(g.data(), d_best, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(gd.data(), d_dist, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+    // 2 claim, 3 used speakers
+    const double t = c->speaker_match_threshold;
+    std::vector<int> U;
+    for (int64_t i = 0; i < N; ++i) if (gd[(size_t)i] <= t) U.push_back(g[(size_t)i]);
+    std::sort(U.begin(), U.end());
+    U.erase(std::unique(U.begin(), U.end()), U.end());
+    const int G = (int)U.size();
+    if (G == 0) return SD_OK;
+    *taken = true;
+    std::vector<int64_t> counts((size_t)G, 0);
+    std::vector<int> ridx;                                                   // 4: R, the unclaimed train rows (row numbers of d_emb)
+    for (int64_t i = 0; i < N; ++i) {
+        if (gd[(size_t)i] <= t) counts[(size_t)(std::lower_bound(U.begin(), U.end(), g[(size_t)i]) - U.begin())]++;
+        else ridx.push_back(tidx[(size_t)i]);
+    }
+    const size_t mcs = std::min<size_t>((size_t)c->min_cluster_size, std::max<size_t>(1, (size_t)std::round(0.1 * (double)N)));     // from N, not N'
+    std::vector<double> cand((size_t)G * d);
+    for (int a = 0; a < G; ++a) memcpy(&cand[(size_t)a * d], &c->enr_host[(size_t)U[(size_t)a] * d], (size_t)d * sizeof(double));
+    // 5 - 7: the new clusters of R
+    std::vector<int> lab, order, off;
+    int L = 0;
+    double* X = nullptr; double* Xn = nullptr;
+    if (!ridx.empty()) {
+        if ((rc = cluster_rows(c, d_emb, ridx, d, &X, &Xn, lab, &L, nullptr))) return rc;
+        group_by_label(lab, L, order, off);
+        std::vector<int> large, small;
+        split_by_size(off, L, mcs, large, small);
+        if (!small.empty() && (rc = reassign_small(c, X, d, order, off, large, small, cand.data(), G, lab, L))) return rc;
+    }
+    double* d_cen2 = nullptr;
+    if ((rc = final_means(c, X, d, lab, L, G, order, off, &d_cen2))) return rc;
+    // 8: the table [V[U[0]] .. V[U[G-1]], mean_0 .. mean_{L-1}]
+    HIPCHK(c, hipMemcpyAsync(d_cen2, cand.data(), cand.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    for (int k = 0; k < L; ++k) counts.push_back(off[(size_t)k + 1] - off[(size_t)k]);
+    if ((rc = assign_all(c, d_emb, M, d, d_cen2, G + L, counts, hard, Kout, soft_best, nullptr))) return rc;
+    c->last_enrolled.assign((size_t)(G + L), -1);                           // 9
+    for (int a = 0; a < G; ++a) c->last_enrolled[(size_t)a] = U[(size_t)a];
+    return SD_OK;
+}
+
 // d_emb: [M][d] f64 (NaN rows = no embedding), M = chunks*3.  hard: [M]
 int run_clustering(sd_ctx* c, const double* d_emb, int64_t M, int d, std::vector<int>& hard, int* Kout,
                    int num_clusters, int min_clusters, int max_clusters, std::vector<double>* soft_best)
 {
+    if (int rf = enrolled_refusal(c, d, num_clusters, min_clusters, max_clusters)) return rf;
     hard.assign((size_t)M, 0);
     if (soft_best) soft_best->assign((size_t)M, NAN);
     if (Kout) *Kout = 1;
     const bool dumping = !c->dump_dir.empty();
     c->stash.clustered = false;
     c->last_cen_K = 0;                                              // sd_last_speakers describes this call from its successful end on
+    c->last_enrolled.clear();                                       // ... and sd_last_enrolled: -1 for every label unless the enrolled flow says otherwise
     if (M <= 0) return SD_OK;
     // a10: rows whose first element is not NaN (sd.cpp:2224)
     std::vector<double> first((size_t)M);
@@ -288,6 +504,11 @@ int run_clustering(sd_ctx* c, const double* d_emb, int64_t M, int d, std::vector
     std::vector<int> tidx;
     for (int64_t i = 0; i < M; ++i) if (!std::isnan(first[(size_t)i])) tidx.push_back((int)i);
     const int64_t N = (int64_t)tidx.size();
+    if (c->enr_M > 0 && N > 0) {                                    // enrolled speakers claim their rows first; no row claimed: the plain flow, untouched
+        bool taken = false;
+        int rce = clustering_enrolled(c, d_emb, M, d, tidx, hard, Kout, soft_best, &taken);
+        if (rce || taken) return rce;
+    }
     // set_num_clusters (sd.cpp:2261-2296; with num_clusters given, max = num_clusters as in Clustering.py:27-41 --
     // the port's `max_clusters == num_clusters;` is a no-op typo, sd.cpp:2278)
     const bool constrained = (num_clusters != -1) || (min_clusters != -1) || (max_clusters != -1);
@@ -318,24 +539,14 @@ int run_clustering(sd_ctx* c, const double* d_emb, int64_t M, int d, std::vector
         c->last_cen_K = 1;
         return SD_OK;
     }
-    WS(c, int, d_tidx, "cl_tidx", N);
-    WS(c, double, X, "cl_X", N * d);
-    WS(c, double, Xn, "cl_Xn", N * d);
-    HIPCHK(c, hipMemcpyAsync(d_tidx, tidx.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_gather_normalize, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, c->stream, d_emb, d_tidx, N, d, X, Xn);
-    KCHECK(c);
-    // a12+a13.  Method, threshold and minimum cluster size are the three hyper-parameters of Clustering.py:251-276; their defaults are the constants the
-    // reference hard-codes (sd.cpp:2049-2056: centroid, the float-typed threshold promoted to double, 15).  Clustering.py:317-333: centroid, median and ward
-    // are euclidean-only and run on the unit-normalised rows (Xn, with the port's f32 norm); the other four run on the rows as they are with the cosine metric.
-    const int method = c->clustering_method;
-    const bool euclid = method == SD_LINKAGE_CENTROID || method == SD_LINKAGE_MEDIAN || method == SD_LINKAGE_WARD;
+    // a12+a13
     const double thr = c->clustering_threshold;
     std::vector<int> lab;
     std::vector<double> Zh;
-    int rc = run_cluster_labels(c, euclid ? Xn : X, N, d, thr, lab, &Zh, method, euclid ? SD_METRIC_EUCLIDEAN : SD_METRIC_COSINE);
-    if (rc) return rc;
+    double* X = nullptr; double* Xn = nullptr;
     int nl = 0;
-    for (auto& v : lab) { v -= 1; if (v + 1 > nl) nl = v + 1; }
+    int rc = cluster_rows(c, d_emb, tidx, d, &X, &Xn, lab, &nl, &Zh);
+    if (rc) return rc;
     if (dumping) c->stash.clusters = lab;
     // a11: size split
     size_t mcs = std::min<size_t>((size_t)c->min_cluster_size, std::max<size_t>(1, (size_t)std::round(0.1 * (double)N)));     // sd.cpp:2308, Clustering.py:309-311
@@ -355,96 +566,20 @@ int run_clustering(sd_ctx* c, const double* d_emb, int64_t M, int d, std::vector
         }
     }
     std::vector<int> large, small;
-    for (int k = 0; k < nl; ++k) {
-        const size_t cnt = (size_t)(off[(size_t)k + 1] - off[(size_t)k]);
-        if (cnt == 0) continue;
-        if (cnt >= mcs) large.push_back(k); else small.push_back(k);
-    }
+    split_by_size(off, nl, mcs, large, small);
     if (large.empty()) {
         // reference: assert(false) in assert-enabled builds (sd.cpp:2368), all-zero labels otherwise (sd.cpp:2371-2375)
         std::fill(lab.begin(), lab.end(), 0);
         nl = 1;
     } else if (!small.empty()) {
-        WS(c, int, d_order, "cl_order", N);
-        WS(c, int, d_off, "cl_off", nl + 1);
-        WS(c, double, d_cen, "cl_cen", (size_t)nl * d);
-        HIPCHK(c, hipMemcpyAsync(d_order, order.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_off, off.data(), (size_t)(nl + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_cluster_means, dim3(nl), dim3(((d + 63) / 64) * 64), 0, c->stream, X, d, d_order, d_off, d_cen);   // means of UN-normalised rows (sd.cpp:2386)
-        KCHECK(c);
-        std::vector<double> cen((size_t)nl * d);
-        HIPCHK(c, hipMemcpyAsync(cen.data(), d_cen, cen.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        bool err = false;
-        std::vector<int> remap((size_t)nl);
-        for (int k = 0; k < nl; ++k) remap[(size_t)k] = k;
-        for (int sk : small) {
-            float minVal = FLT_MAX; int best = -1;                                      // float accumulator, sd.cpp:2396
-            for (size_t a = 0; a < large.size(); ++a) {
-                const double dd = cos_dist_host(&cen[(size_t)large[a] * d], &cen[(size_t)sk * d], d, &err);
-                if (dd < minVal) { minVal = (float)dd; best = (int)a; }
-            }
-            if (best >= 0) remap[(size_t)sk] = large[(size_t)best];
-        }
-        if (err) SD_FAIL(c, SD_ERR_NUMERIC, "zero-magnitude cluster centroid (reference throws, sd.cpp:493-495)");
-        for (auto& v : lab) v = remap[(size_t)v];
-        // findUniqueClusters: renumber 0..K-1 in sorted-id order (sd.cpp:519-548)
-        std::vector<int> seen((size_t)nl, -1);
-        for (int v : lab) seen[(size_t)v] = 0;
-        int nk = 0;
-        for (int k = 0; k < nl; ++k) if (seen[(size_t)k] == 0) seen[(size_t)k] = nk++;
-        for (auto& v : lab) v = seen[(size_t)v];
-        nl = nk;
+        if ((rc = reassign_small(c, X, d, order, off, large, small, nullptr, 0, lab, nl))) return rc;
     }
     // a14: centroids of the final clusters (un-normalised train rows), cosine cdist of ALL rows, argmax
-    group_by_label(lab, nl, order, off);
-    WS(c, int, d_order2, "cl_order", N);
-    WS(c, int, d_off2, "cl_off", nl + 1);
-    WS(c, double, d_cen2, "cl_cen", (size_t)nl * d);
-    WS(c, int, d_hard, "cl_hard", M);
-    WS(c, int, d_err, "cl_err", 4);
-    HIPCHK(c, hipMemcpyAsync(d_order2, order.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_off2, off.data(), (size_t)(nl + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_err, 0, sizeof(int), c->stream));
-    hipLaunchKernelGGL(k_cluster_means, dim3(nl), dim3(((d + 63) / 64) * 64), 0, c->stream, X, d, d_order2, d_off2, d_cen2);
-    KCHECK(c);
-    const bool constrained_assign = c->constrained_assignment && (M % SD_SPEAKERS) == 0;
-    // the full [M][K] score table only for the constrained assignment (it needs every score); the confidence needs the best score alone
-    double* d_soft = nullptr; double* d_best = nullptr;
-    if (constrained_assign || dumping) { WS(c, double, t_soft, "cl_soft", (size_t)M * nl); d_soft = t_soft; }
-    if (constrained_assign || soft_best) { WS(c, double, t_best, "cl_best", M); d_best = t_best; }
-    hipLaunchKernelGGL(k_assign, dim3((unsigned)M), dim3(64), 0, c->stream, d_emb, M, d, d_cen2, nl, d_hard, d_err, d_soft, d_best);
-    KCHECK(c);
-    int herr = 0;
-    HIPCHK(c, hipMemcpyAsync(hard.data(), d_hard, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&herr, d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (soft_best) HIPCHK(c, hipMemcpyAsync(soft_best->data(), d_best, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    c->last_cen.resize((size_t)nl * d);                             // the centroids ride this synchronisation (sd_last_speakers)
-    HIPCHK(c, hipMemcpyAsync(c->last_cen.data(), d_cen2, c->last_cen.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (herr) SD_FAIL(c, SD_ERR_NUMERIC, "zero-magnitude embedding or centroid in assignment (reference throws, sd.cpp:493-495)");
-    if (constrained_assign) {
-        // Clustering.py:83: NaN (rows without an embedding) -> the smallest soft score of the whole recording
-        std::vector<double> hs((size_t)M * nl);
-        HIPCHK(c, hipMemcpy(hs.data(), d_soft, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
-        double fill = INFINITY;
-        for (double x : hs) if (x == x && x < fill) fill = x;
-        if (fill == INFINITY) fill = 0.0;
-        const int64_t chunks = M / SD_SPEAKERS;
-        if (nl <= LSAP_MAXC) {
-            hipLaunchKernelGGL(k_constrained_argmax, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, c->stream, d_soft, chunks, nl, fill, d_hard);
-            KCHECK(c);
-            HIPCHK(c, hipMemcpyAsync(hard.data(), d_hard, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        } else SD_FAIL(c, SD_ERR_ARG, "constrained assignment supports up to %d clusters (found %d)", LSAP_MAXC, nl);
-        if (soft_best)                                             // confidence follows the cluster actually assigned
-            for (int64_t i = 0; i < M; ++i) (*soft_best)[(size_t)i] = hard[(size_t)i] >= 0 ? hs[(size_t)i * nl + hard[(size_t)i]] : NAN;
-    }
-    if (Kout) *Kout = nl;
-    c->last_cen_counts.resize((size_t)nl);
-    for (int k = 0; k < nl; ++k) c->last_cen_counts[(size_t)k] = off[(size_t)k + 1] - off[(size_t)k];
-    c->last_cen_d = d;
-    c->last_cen_K = nl;
+    double* d_cen2 = nullptr; double* d_soft = nullptr;
+    if ((rc = final_means(c, X, d, lab, nl, 0, order, off, &d_cen2))) return rc;
+    std::vector<int64_t> counts((size_t)nl);
+    for (int k = 0; k < nl; ++k) counts[(size_t)k] = off[(size_t)k + 1] - off[(size_t)k];
+    if ((rc = assign_all(c, d_emb, M, d, d_cen2, nl, counts, hard, Kout, soft_best, &d_soft))) return rc;
     if (dumping) {
         StepStash& S = c->stash;
         S.clustered = true; S.N = N; S.K = nl; S.cluster_res = lab; S.hard_pre = hard;

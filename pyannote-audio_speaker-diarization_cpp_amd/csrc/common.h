@@ -215,6 +215,13 @@ struct sd_ctx {
     std::vector<double> last_cen;
     std::vector<int64_t> last_cen_counts;
     int last_cen_K = 0, last_cen_d = 0;
+    std::vector<int32_t> last_enrolled;          // gallery row of every one of those K labels, -1 for a speaker nobody enrolled (sd_last_enrolled)
+    // the enrolled gallery (sd_set_enrolled): the context's own device copy [enr_M][enr_d], the squared norms of its rows (k_row_sqnorms), and a host copy
+    // for the candidate loop and the centroid table of run_clustering; enr_M = 0: none, and nothing of the clustering stage changes
+    DevBuf enr_gal, enr_m2;
+    std::vector<double> enr_host;
+    int64_t enr_M = 0;
+    int enr_d = 0;
     double speaker_match_threshold = (double)0.7153814381597874f * (double)0.7153814381597874f / 2;      // sd_match_speakers: t * t / 2, the cosine distance at which the default clustering stops merging two unit vectors
     // the activity stage (activity.hip): pyannote's Binarize parameters for the speech / overlap timeline, and the timeline of the last whole-path call
     double activity_onset = 0.5, activity_offset = 0.5, activity_min_on = 0.0, activity_min_off = 0.0;
@@ -429,6 +436,11 @@ void spans_to_samples(const sd_turn* spans, int64_t n_spans, int32_t label, int6
 int run_span_masks(sd_ctx* c, const std::vector<int64_t>& spans, int64_t chunks, int64_t n, float* d_masks /*[chunks * 3][293]*/);
 int run_voiceprint_mean(sd_ctx* c, const float* d_emb /*[chunks * 3][192]*/, int64_t chunks, double* h_mean /*[192]*/, int64_t* n_live);      // synchronises
 int run_speaker_dist(sd_ctx* c, const double* d_cen, int64_t K, const double* d_gal, int64_t M, int d, double* d_dist, double* h_dist /*[K][M]*/);      // synchronises
+int run_gallery_norms(sd_ctx* c, const double* d_gal, int64_t M, int d, double* d_m2 /*[M]*/);      // asynchronous
+int run_nearest_gallery(sd_ctx* c, const double* d_E, const int* d_tidx /*[N] or null*/, int64_t N, const double* d_gal, const double* d_m2, int64_t M, int d,
+                        int* d_best /*[N]*/, double* d_dist /*[N]*/);      // synchronises
+// ---- cluster.hip: the three refusals of a call that clusters under an enrolled gallery (SD_ERR_ARG; nothing is touched); SD_OK without a gallery
+int enrolled_refusal(sd_ctx* c, int d, int num_clusters, int min_clusters, int max_clusters);
 // ---- reconstruct.hip
 int run_reconstruct(sd_ctx* c, const float* d_seg, const int* d_nact, const int* d_hard, const int32_t* d_count,
                     int64_t n_count, int64_t chunks, int64_t n_samples, int K, std::vector<sd_turn>& turns);

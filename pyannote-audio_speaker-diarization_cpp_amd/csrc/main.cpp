@@ -39,6 +39,10 @@
 //                   FILE (sd_read_voiceprints, sd_match_speakers): a matched cluster prints as [start -- end] --> NAME and goes into the RTTM under its name, an
 //                   unmatched one prints as without the flag.  X in [0, 2] = the largest cosine distance that still matches (option "speaker_match_threshold").
 //                   Works with --stream; refused with --activity and with --gpus N > 1
+//   --speakers FILE --enrolled [--speakers-threshold X]   enrol the voiceprints of FILE BEFORE the job (sd_set_enrolled): the clustering itself claims the
+//                   embeddings within X of a voiceprint for that person, clusters the rest and prints / writes the names sd_last_enrolled gives -- no
+//                   matching afterwards.  With --stream a label means the same person in every update (--stream-updates prints the names too).
+//                   Refused with --enroll, --activity, --dump-steps and --gpus N > 1
 //   --enroll NAME --speakers FILE [--enroll-span START END]...   no diarization: the voiceprint of the wav -- all of it, or the given spans in seconds --
 //                   (sd_voiceprint_wav) replaces or is appended as NAME in FILE (created when absent); prints "enrolled NAME from N windows".
 //                   A bad value of any of these is a usage error (exit 2) before anything touches the GPU
@@ -61,7 +65,7 @@ struct Args { const char* seg = nullptr; const char* emb = nullptr; const char* 
               int cl_method = -1; double cl_threshold = -1.0; long long cl_min_size = -1;         // -1: leave the library's default
               int activity = -1; double act[4] = {-1.0, -1.0, -1.0, -1.0}; bool act_hamming = false;      // --activity: SD_ACTIVITY_*; onset, offset, min on, min off (-1: default)
               long long stream_piece = 0; bool stream_updates = false;         // --stream: samples per piece (0: off)
-              const char* speakers = nullptr; double speakers_threshold = -1.0; const char* enroll = nullptr; std::vector<sd_turn> enroll_spans; };      // --speakers FILE, its threshold (-1: default), --enroll NAME and its spans
+              const char* speakers = nullptr; double speakers_threshold = -1.0; const char* enroll = nullptr; std::vector<sd_turn> enroll_spans; bool enrolled = false; };      // --speakers FILE, its threshold (-1: default), --enroll NAME and its spans
 
 // the clustering hyper-parameters the command line set; false (message printed) on a refusal
 static bool apply_clustering(sd_ctx* ctx, const Args& a)
@@ -101,6 +105,28 @@ static bool match_clusters(sd_ctx* ctx, const Args& a, const Gallery& g, std::ve
     const int rc = sd_match_speakers(ctx, nullptr, K, g.emb, g.M, SD_EMB_DIM, NAN, match.data(), nullptr);
     if (rc != SD_OK) { fprintf(stderr, "matching against %s failed (%d): %s\n", a.speakers, rc, sd_last_error(ctx)); return false; }
     for (int64_t k = 0; k < K; ++k) if (match[(size_t)k] >= 0) names[(size_t)k] = g.names[match[(size_t)k]];
+    return true;
+}
+
+// --speakers FILE --enrolled, before the job: the threshold, then the gallery; false (message printed) on a failure
+static bool enrol_gallery(sd_ctx* ctx, const Args& a, const Gallery& g)
+{
+    if (a.speakers_threshold >= 0.0 && sd_set_option_f64(ctx, "speaker_match_threshold", a.speakers_threshold) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
+    const int rc = sd_set_enrolled(ctx, g.emb, g.M, SD_EMB_DIM);
+    if (rc != SD_OK) { fprintf(stderr, "enrolling %s failed (%d): %s\n", a.speakers, rc, sd_last_error(ctx)); return false; }
+    return true;
+}
+
+// ... and after it: names[k] = the name of the voiceprint that raw label k stands for (sd_last_enrolled), or null
+static bool enrolled_names(sd_ctx* ctx, const Gallery& g, std::vector<const char*>& names)
+{
+    names.clear();
+    int64_t K = 0;
+    if (sd_last_enrolled(ctx, nullptr, 0, &K) != SD_OK) return false;
+    std::vector<int32_t> rows((size_t)K, -1);
+    if (K > 0 && sd_last_enrolled(ctx, rows.data(), K, &K) != SD_OK) return false;
+    names.assign((size_t)K, nullptr);
+    for (int64_t k = 0; k < K; ++k) if (rows[(size_t)k] >= 0 && rows[(size_t)k] < g.M) names[(size_t)k] = g.names[rows[(size_t)k]];
     return true;
 }
 
@@ -182,13 +208,14 @@ static int run_single(const Args& a)
     if (a.precision == 3 && sd_set_option(ctx, "seg_precision", 3) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return 1; }
     if (a.dump_dir && sd_set_dump_dir(ctx, a.dump_dir, a.dump_level) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return 1; }
     if (!apply_clustering(ctx, a) || !apply_activity(ctx, a)) return 1;
+    if (a.enrolled && !enrol_gallery(ctx, a, g)) return 1;
     sd_turn* turns = nullptr; int64_t nt = 0;
     const int rc = a.activity >= 0 ? sd_activity_wav(ctx, a.wav, a.wav_flags, a.activity, &turns, &nt)
                                    : sd_diarize_wav(ctx, a.wav, a.wav_flags, &turns, &nt);      // 8 / 16 / 32-bit PCM like wav.h:99-122; rate and channels checked
     if (rc != SD_OK) { fprintf(stderr, "%s failed (%d): %s\n", a.activity >= 0 ? "activity detection" : "diarization", rc, sd_last_error(ctx)); return 1; }
     TRACE("sd_diarize_wav done");
     std::vector<const char*> names;
-    if (a.speakers && !match_clusters(ctx, a, g, names)) return 1;
+    if (a.speakers && !(a.enrolled ? enrolled_names(ctx, g, names) : match_clusters(ctx, a, g, names))) return 1;
     print_block(ctx, turns, nt, a, nullptr, a.speakers ? &names : nullptr);
     sd_free_turns(turns);
     sd_destroy(ctx);
@@ -201,6 +228,7 @@ struct StreamRun {
     sd_ctx* ctx; sd_stream* st; const Args& a;
     double ms[4] = {0, 0, 0, 0};                    // stage times summed over every call of the run
     sd_turn* turns = nullptr; int64_t nt = 0;
+    const Gallery* gal = nullptr;                   // --enrolled: the update blocks print the names too
     void bill() { double m[4]; sd_stage_ms(ctx, m); for (int q = 0; q < 4; ++q) ms[q] += m[q]; }
     // turns of what has been pushed; too little audio for a chunk is no turns yet, not a failure
     bool ask()
@@ -227,9 +255,15 @@ struct StreamRun {
         int64_t n = 0, sealed = 0, total = 0;
         sd_stream_info(st, &n, &sealed, &total);
         printf("== %g s, %lld/%lld chunks\n", (double)n / SD_SAMPLE_RATE, (long long)sealed, (long long)total);
+        std::vector<const char*> names, turn_name((size_t)nt, nullptr);
+        if (gal && enrolled_names(ctx, *gal, names))
+            for (int64_t i = 0; i < nt; ++i) if (turns[i].label >= 0 && (size_t)turns[i].label < names.size()) turn_name[(size_t)i] = names[(size_t)turns[i].label];
         if (a.relabel) sd_relabel_turns(turns, nt);
         char line[160];
-        for (int64_t i = 0; i < nt; ++i) { sd_format_turn(&turns[i], line, sizeof(line)); printf("%s\n", line); }
+        for (int64_t i = 0; i < nt; ++i) {
+            if (turn_name[(size_t)i]) { printf("[%g -- %g] --> %s\n", turns[i].start, turns[i].end, turn_name[(size_t)i]); continue; }
+            sd_format_turn(&turns[i], line, sizeof(line)); printf("%s\n", line);
+        }
         fflush(stdout);
         return true;
     }
@@ -307,6 +341,7 @@ static int run_stream(const Args& a)
     if (a.precision && sd_set_option(ctx, "ecapa_precision", a.precision) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
     if (a.precision == 3 && sd_set_option(ctx, "seg_precision", 3) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
     if (!apply_clustering(ctx, a)) return leave(1);
+    if (a.enrolled) { if (!enrol_gallery(ctx, a, g)) return leave(1); r.gal = &g; }
     if (sd_stream_open(ctx, &r.st) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
     const bool fed = std::string(a.wav) == "-" ? stream_stdin(r) : stream_file(r);
     if (!fed || !r.ask()) return leave(1);
@@ -314,7 +349,7 @@ static int run_stream(const Args& a)
     sd_stream_info(r.st, &n, nullptr, &total);
     if (total <= 0) { fprintf(stderr, "diarization failed (%d): audio of %lld samples yields no chunk\n", SD_ERR_SHORT, (long long)n); return leave(1); }
     std::vector<const char*> names;
-    if (a.speakers && !match_clusters(ctx, a, g, names)) return leave(1);
+    if (a.speakers && !(a.enrolled ? enrolled_names(ctx, g, names) : match_clusters(ctx, a, g, names))) return leave(1);
     print_block(ctx, r.turns, r.nt, a, r.ms, a.speakers ? &names : nullptr);
     return leave(0);
 }
@@ -415,6 +450,7 @@ int main(int argc, char* argv[])
             }
         }
         else if (s == "--stream-updates") a.stream_updates = true;
+        else if (s == "--enrolled") a.enrolled = true;
         else if (s == "--stream") {
             if (i + 1 >= argc) { fprintf(stderr, "usage: --stream needs a value\n"); return 2; }
             const char* v = argv[++i];
@@ -478,6 +514,9 @@ int main(int argc, char* argv[])
     if (a.speakers_threshold >= 0.0 && (!a.speakers || a.enroll)) { fprintf(stderr, "usage: --speakers-threshold needs --speakers FILE (and no --enroll)\n"); return 2; }
     if (a.speakers && a.activity >= 0) { fprintf(stderr, "usage: --speakers names the clusters of a diarization; --activity is refused with it\n"); return 2; }
     if (a.speakers && a.gpus > 1) { fprintf(stderr, "usage: --speakers runs on one GPU; --gpus %d is refused\n", a.gpus); return 2; }
+    if (a.enrolled && !a.speakers) { fprintf(stderr, "usage: --enrolled needs --speakers FILE, the voiceprints to enrol\n"); return 2; }
+    if (a.enrolled && a.enroll) { fprintf(stderr, "usage: --enrolled enrols the voiceprints of FILE for a diarization; --enroll runs none and is refused with it\n"); return 2; }
+    if (a.enrolled && a.dump_dir) { fprintf(stderr, "usage: --dump-steps describes the reference's flow; --enrolled is refused with it\n"); return 2; }
     if (a.enroll && (a.stream_piece > 0 || a.dump_dir)) { fprintf(stderr, "usage: --enroll runs no diarization; --stream and --dump-steps are refused with it\n"); return 2; }
     if (pos.size() < 3) {
         printf("program [segment model file] [embeding model file] [wave file]\n");   // sd.cpp:3423

@@ -298,6 +298,7 @@ int shard_infer(sd_ctx* c, const DevWav& w, int64_t lo, int64_t hi, float* d_seg
 int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, std::vector<sd_turn>& v)
 {
     int rc;
+    if ((rc = enrolled_refusal(c, SD_EMB_DIM, c->num_clusters, c->min_clusters, c->max_clusters))) return rc;      // before anything is touched
     const double t0 = now_ms();
     const int64_t M = chunks * SD_SPEAKERS;
     const int64_t nf = count_frames_host(chunks);

@@ -1,7 +1,10 @@
-// speakers.hip -- known speakers (compiled with -ffp-contract=off): the three kernels behind sd_span_masks, sd_voiceprint* and sd_speaker_distances
+// speakers.hip -- known speakers (compiled with -ffp-contract=off): the kernels behind sd_span_masks, sd_voiceprint*, sd_speaker_distances and the
+// enrolled gallery (sd_set_enrolled, sd_nearest_speakers, the enrolled branch of run_clustering)
 //   k_span_masks       the mask rows of getEmbedding's items (sd.cpp:2436-2561) from time spans instead of from the segmentation scores
 //   k_voiceprint_mean  the mean of the embeddings of the live windows, summed as assign_embeddings sums a centroid         sd.cpp:2149-2167
 //   k_speaker_dist     cosine distance of every centroid to every row of a gallery, the reference's sequential sums        sd.cpp:476-498
+//   k_row_sqnorms      m2 of every gallery row, once per gallery                                                           sd.cpp:476-498
+//   k_nearest_gallery  nearest gallery row (first minimum) and its distance for every train row, no N x M table            sd.cpp:476-498, 293-316
 // A voiceprint is computed exactly as the diarizer computes its own embeddings -- same chunks (sd.cpp:1419, 1457), same item grid, same batches of 32
 // through run_embed -- with one difference: the mask of item 3c says "these samples of chunk c lie in a span" and items 3c + 1, 3c + 2 are empty, so the
 // existing compaction drops them before any arithmetic.  That makes a voiceprint commensurable with the centroids run_clustering keeps (cluster.hip).
@@ -123,6 +126,106 @@ __global__ __launch_bounds__(SPK_TM) void k_speaker_dist(const double* __restric
     }
 }
 
+
+// ---------------------------------------------------------------- k_row_sqnorms : one thread per row
+// m2[m] = sum over i ascending of V[m][i] * V[m][i]: the sequential sum every cosine distance of this file takes for its second operand (sd.cpp:476-498).
+// The bits do not depend on what the row is paired with, so a gallery computes them once.
+__global__ void k_row_sqnorms(const double* __restrict__ V, int64_t M, int d, double* __restrict__ m2)
+{
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= M) return;
+    const double* r = V + (size_t)m * d;
+    double s = 0.0;
+    for (int i = 0; i < d; ++i) s += r[i] * r[i];
+    m2[m] = s;
+}
+
+// ---------------------------------------------------------------- k_nearest_gallery : one workgroup per tile of NG_R train rows, one lane per row
+// best[n] = the smallest m that attains min over m of dist(n, m), dist[n] = that minimum; dist(n, m) = 1 - dot / (sqrt(m1) * sqrt(m2)) of train row
+// x = E[tidx[n]] (tidx == NULL: E[n]) and gallery row m: dot and m1 sequential f64 sums over i ascending, m2 from k_row_sqnorms -- the bits of
+// k_speaker_dist for the same pair, k_speaker_dist with the roles of the two operands exchanged.  Nothing of size N x M exists: every lane keeps a running
+// (min, arg-min).  The NG_R rows of the tile are staged once in LDS at an odd pitch (d | 1 doubles: the lanes of a ds_read_b64 group fall on different bank
+// pairs; NG_R x 193 doubles = 99 KB for d = 192, above the 64 KB a launch gets without asking: run_nearest_gallery sets the kernel's dynamic-LDS
+// attribute); rows longer than NG_DMAX stay in global memory and every lane walks its own.  The gallery streams through in tiles of NG_TK rows: wave w
+// of the NG_WAVES waves takes the tiles t with t % NG_WAVES == w, its gallery addresses are the same in every lane (scalar loads, one broadcast operand per
+// multiply), tiles and rows inside a tile in ascending m with a strict <.  The waves' results meet in LDS, combined in wave order by
+// "smaller distance, or the same distance and a smaller m": whatever the split, the first minimum of the whole gallery wins.
+// A zero-norm train row sets *err (the reference throws, sd.cpp:493-495); gallery rows are checked where the gallery is set (m2 > 0, finite).
+// Bounds: train rows n0 + r < N at the staging loads, at the row pointer of the global form and at the stores; gallery rows m0 + k < M at the loads (a row
+// past the end reads row M - 1 and its result is dropped) and at the compare.
+#define NG_R 64
+#define NG_TK 8
+#define NG_WAVES 4
+#define NG_DMAX 192
+template <bool IN_LDS>
+__device__ __forceinline__ void nearest_scan(const double* xr, double m1, const double* __restrict__ V, const double* __restrict__ gm2, int64_t M, int d,
+                                             int wave, double& bd, int& bm)
+{
+    const double s1 = sqrt(m1);
+    for (int64_t m0 = (int64_t)wave * NG_TK; m0 < M; m0 += (int64_t)NG_WAVES * NG_TK) {
+        const double* vp[NG_TK];
+        double dot[NG_TK];
+#pragma unroll
+        for (int k = 0; k < NG_TK; ++k) { const int64_t m = m0 + k < M ? m0 + k : M - 1; vp[k] = V + (size_t)m * d; dot[k] = 0.0; }
+#pragma unroll 4
+        for (int i = 0; i < d; ++i) {                                        // i ascending: the order of every dot sum is the reference's
+            const double x = xr[i];
+#pragma unroll
+            for (int k = 0; k < NG_TK; ++k) dot[k] += x * vp[k][i];
+        }
+#pragma unroll
+        for (int k = 0; k < NG_TK; ++k) {
+            if (m0 + k >= M) continue;
+            const double v = 1.0 - (dot[k] / (s1 * sqrt(gm2[m0 + k])));
+            if (v < bd) { bd = v; bm = (int)(m0 + k); }
+        }
+    }
+}
+__global__ __launch_bounds__(NG_R * NG_WAVES) void k_nearest_gallery(const double* __restrict__ E, const int* __restrict__ tidx, int64_t N,
+                                                                     const double* __restrict__ V, const double* __restrict__ gm2, int64_t M, int d,
+                                                                     int* __restrict__ best, double* __restrict__ dist, int* __restrict__ err)
+{
+    extern __shared__ __attribute__((aligned(16))) double ng_x[];            // [NG_R][d | 1] when d <= NG_DMAX, else nothing
+    __shared__ double wd[NG_WAVES][NG_R];
+    __shared__ int wm[NG_WAVES][NG_R];
+    const int tid = threadIdx.x, lane = tid & (NG_R - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid / NG_R);             // the same in all 64 lanes: gallery addresses stay scalar
+    const int64_t n0 = (int64_t)blockIdx.x * NG_R, n = n0 + lane;
+    const bool in_lds = d <= NG_DMAX;
+    const int pitch = d | 1;
+    if (in_lds) {
+        for (int e = tid; e < NG_R * d; e += NG_R * NG_WAVES) {
+            const int r = e / d, q = e - r * d;
+            double v = 0.0;
+            if (n0 + r < N) { const int64_t row = tidx ? (int64_t)tidx[n0 + r] : n0 + r; v = E[(size_t)row * d + q]; }
+            ng_x[r * pitch + q] = v;
+        }
+        __syncthreads();
+    }
+    const int64_t nr = n < N ? n : N - 1;                                    // a lane past the end walks the last row; nothing of it is stored
+    const double* xg = E + (size_t)(tidx ? (int64_t)tidx[nr] : nr) * d;
+    const double* xl = ng_x + lane * pitch;
+    double m1 = 0.0;
+    if (in_lds) for (int i = 0; i < d; ++i) m1 += xl[i] * xl[i];
+    else        for (int i = 0; i < d; ++i) m1 += xg[i] * xg[i];
+    double bd = INFINITY; int bm = -1;
+    if (in_lds) nearest_scan<true>(xl, m1, V, gm2, M, d, wave, bd, bm);
+    else        nearest_scan<false>(xg, m1, V, gm2, M, d, wave, bd, bm);
+    wd[wave][lane] = bd; wm[wave][lane] = bm;
+    __syncthreads();
+    if (wave == 0 && n < N) {
+#pragma unroll
+        for (int w = 1; w < NG_WAVES; ++w) {
+            const double v = wd[w][lane]; const int m = wm[w][lane];
+            if (m >= 0 && (bm < 0 || v < bd || (v == bd && m < bm))) { bd = v; bm = m; }
+        }
+        if (m1 == 0.0) *err = 1;
+        best[n] = bm < 0 ? 0 : bm;                                           // no distance compared smaller than +inf (NaN in the row): row 0, NaN
+        dist[n] = bm < 0 ? NAN : bd;
+    }
+}
+static std::atomic<unsigned> g_attr_ng{0};                                    // devices whose k_nearest_gallery has its dynamic-LDS attribute
+
 // ---------------------------------------------------------------- host
 // every span has 0 <= start <= end, both numbers (sd_voiceprint*'s SD_ERR_ARG rule); pure check, nothing of the context is touched before it passes
 int check_spans(sd_ctx* c, const sd_turn* spans, int64_t n_spans, const char* who)
@@ -210,5 +313,40 @@ int run_speaker_dist(sd_ctx* c, const double* d_cen, int64_t K, const double* d_
     HIPCHK(c, hipMemcpyAsync(&herr, d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (herr) SD_FAIL(c, SD_ERR_NUMERIC, "zero-magnitude centroid or gallery row (reference throws, sd.cpp:493-495)");
+    return SD_OK;
+}
+
+// d_m2 [M] = the squared norms of the gallery rows (k_row_sqnorms); asynchronous on the stream
+int run_gallery_norms(sd_ctx* c, const double* d_gal, int64_t M, int d, double* d_m2)
+{
+    if (M <= 0) return SD_OK;
+    ProfScope ps(c, "gallery_norms", 2.0 * (double)M * d, (double)M * d * 8.0);
+    hipLaunchKernelGGL(k_row_sqnorms, GRID1(M), 0, c->stream, d_gal, M, d, d_m2);
+    KCHECK(c);
+    return SD_OK;
+}
+
+// d_best [N], d_dist [N] = nearest gallery row (first minimum) and its distance of the rows d_E[d_tidx[n]] (d_tidx == NULL: d_E[n]); d_m2 from
+// run_gallery_norms.  Device memory beyond the operands: nothing but the error flag.  Synchronises the stream; SD_ERR_NUMERIC on a zero-norm train row
+int run_nearest_gallery(sd_ctx* c, const double* d_E, const int* d_tidx, int64_t N, const double* d_gal, const double* d_m2, int64_t M, int d,
+                        int* d_best, double* d_dist)
+{
+    if (N <= 0 || M <= 0) return SD_OK;
+    const int64_t tiles = (N + NG_R - 1) / NG_R;
+    if (tiles > 0x7fffffff || M > 0x7fffffff) SD_FAIL(c, SD_ERR_ARG, "nearest speakers: %lld x %lld is out of range", (long long)N, (long long)M);
+    const size_t lds = d <= NG_DMAX ? (size_t)NG_R * (size_t)(d | 1) * sizeof(double) : 0;
+    if (!conv_set_dyn_lds(c, g_attr_ng, {(const void*)k_nearest_gallery}, (size_t)NG_R * (NG_DMAX | 1) * sizeof(double)))
+        SD_FAIL(c, SD_ERR_HIP, "nearest speakers: the device refuses %zu bytes of LDS per workgroup", (size_t)NG_R * (NG_DMAX | 1) * sizeof(double));
+    WS(c, int, d_err, "spk_err", 4);
+    HIPCHK(c, hipMemsetAsync(d_err, 0, sizeof(int), c->stream));
+    {
+        ProfScope ps(c, "nearest_gallery", 2.0 * (double)N * (double)M * d, (double)tiles * (double)M * d * 8.0 + (double)N * d * 8.0);
+        hipLaunchKernelGGL(k_nearest_gallery, dim3((unsigned)tiles), dim3(NG_R * NG_WAVES), lds, c->stream, d_E, d_tidx, N, d_gal, d_m2, M, d, d_best, d_dist, d_err);
+        KCHECK(c);
+    }
+    int herr = 0;
+    HIPCHK(c, hipMemcpyAsync(&herr, d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (herr) SD_FAIL(c, SD_ERR_NUMERIC, "zero-magnitude embedding against the gallery (reference throws, sd.cpp:493-495)");
     return SD_OK;
 }

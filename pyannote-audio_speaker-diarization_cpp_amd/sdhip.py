@@ -57,6 +57,7 @@ EXPORTS = [
     "sd_stream_close", "sd_stream_sealed_chunks",
     "sd_last_speakers", "sd_span_masks", "sd_voiceprint", "sd_voiceprint_dev", "sd_voiceprint_f32", "sd_voiceprint_wav", "sd_speaker_distances",
     "sd_match_speakers", "sd_read_voiceprints", "sd_write_voiceprints", "sd_free_voiceprints", "sd_voiceprints_error", "sd_write_rttm_named",
+    "sd_set_enrolled", "sd_enrolled_info", "sd_nearest_speakers", "sd_last_enrolled",
 ]
 # SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
 LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
@@ -167,6 +168,10 @@ def lib():
     L.sd_free_voiceprints.restype = None
     L.sd_voiceprints_error.restype = C.c_char_p
     L.sd_write_rttm_named.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Turn), i64, C.POINTER(dbl), C.POINTER(C.c_char_p), i64]
+    L.sd_set_enrolled.argtypes = [vp, vp, i64, C.c_int]
+    L.sd_enrolled_info.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_int)]
+    L.sd_nearest_speakers.argtypes = [vp, vp, i64, vp, i64, C.c_int, vp, vp]
+    L.sd_last_enrolled.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.sd_format_turn.argtypes = [C.POINTER(Turn), C.c_char_p, C.c_int]
     L.sd_stage_ms.argtypes = [vp, C.POINTER(dbl)]
     L.sd_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
@@ -668,6 +673,45 @@ class Diarizer:
         self._chk(lib().sd_match_speakers(self._h, None if cen is None else _ptr(cen), K, _ptr(gal), M, d,
                                           float("nan") if threshold is None else float(threshold), _ptr(match), _ptr(best)))
         return match, best
+
+    # ---- enrolled speakers (sd_set_enrolled, sd_enrolled_info, sd_nearest_speakers, sd_last_enrolled)
+    def set_enrolled(self, gallery=None):
+        """sd_set_enrolled: enrol the voiceprints [M][d] for every following call of this context that clusters; None (or no row) clears the gallery"""
+        if gallery is None or len(gallery) == 0:
+            self._chk(lib().sd_set_enrolled(self._h, None, 0, 0))
+            return
+        gal = np.ascontiguousarray(gallery, np.float64)
+        M, d = gal.shape
+        self._chk(lib().sd_set_enrolled(self._h, _ptr(gal), M, d))
+
+    def enrolled_info(self):
+        """sd_enrolled_info: (rows, dimensions) of the enrolled gallery, (0, 0) when there is none"""
+        M, d = C.c_int64(0), C.c_int(0)
+        self._chk(lib().sd_enrolled_info(self._h, C.byref(M), C.byref(d)))
+        return int(M.value), int(d.value)
+
+    def nearest_speakers(self, X, gallery=None):
+        """sd_nearest_speakers: (best [N] int32, dist [N] float64) = the nearest gallery row (first minimum) of every row of X [N][d] and its cosine
+        distance; gallery None = the enrolled one"""
+        X = np.ascontiguousarray(X, np.float64)
+        N, d = X.shape
+        if gallery is None:
+            gal, (M, _) = None, self.enrolled_info()
+        else:
+            gal = np.ascontiguousarray(gallery, np.float64)
+            M = gal.shape[0]
+            assert gal.ndim == 2 and gal.shape[1] == d
+        best, dist = np.zeros(N, np.int32), np.zeros(N, np.float64)
+        self._chk(lib().sd_nearest_speakers(self._h, _ptr(X), N, None if gal is None else _ptr(gal), M, d, _ptr(best), _ptr(dist)))
+        return best, dist
+
+    def last_enrolled(self):
+        """sd_last_enrolled: [K] int32, the gallery row of every label of the last call that clustered, -1 for a speaker nobody enrolled"""
+        K = C.c_int64(0)
+        self._chk(lib().sd_last_enrolled(self._h, None, 0, C.byref(K)))
+        rows = np.full(K.value, -1, np.int32)
+        self._chk(lib().sd_last_enrolled(self._h, _ptr(rows) if K.value else None, K.value, C.byref(K)))
+        return rows
 
     # ---- a15-a17
     def reconstruct(self, seg, binarized, hard, count, n_samples):
