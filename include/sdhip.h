@@ -366,6 +366,34 @@ int sd_nearest_speakers(sd_ctx*, const double* h_X /*[N][d], no NaN rows*/, int6
 /* gallery row of every label of the last call that clustered, -1 for a speaker nobody enrolled; all -1 without a gallery */
 int sd_last_enrolled(const sd_ctx*, int32_t* h_rows /*[cap]*/, int64_t cap, int64_t* K);     /* sd.cpp:476-498 / 2149-2212 */
 
+/* ---- many recordings in one call: replaces a loop of speakerDiarization() calls (sd.cpp:2937-3234) over short files.  The two networks run once over
+ * all recordings -- their chunks share the segmentation batches ("seg_batch_chunks") and their live items the embedding batches -- and everything
+ * behind the networks runs per recording, one after the other, exactly as in sd_diarize: every clustering option, "constrained_assignment" and an
+ * enrolled gallery apply to every recording.  turns[r] / n_turns[r] (free each with sd_free_turns) are what sd_diarize returns for recording r alone
+ * on this context, bit for bit, in "ecapa_precision" 0, 1 and 2; mode 3 repeats ALL batches of an embedding call on the f32 kernels when any
+ * embedding overflows, so there a packed call equals the loop only while no recording of the pack triggers that fallback.
+ * status[r] = SD_OK, SD_ERR_SHORT (sd_num_chunks(n[r]) <= 0; turns[r] = NULL) or SD_ERR_NUMERIC from that recording's clustering (turns[r] = NULL);
+ * the other recordings go on and the call returns SD_OK.  Any other failure (SD_ERR_HIP, SD_ERR_MODEL) is returned at once and nothing stays
+ * allocated to the caller.  Refused with SD_ERR_ARG before anything is touched: R < 1, a null row, a dump directory set (the step files describe
+ * one recording), a planted workload set (its chunk range means one recording), the refusals of an enrolled gallery (above), and a pack of more
+ * than SD_MANY_MAX_CHUNKS chunks (sd_many_plan's total: 3 * 501 feature rows per chunk must stay within the int row counts of a launch, 2^31 / 4).
+ * Host float rows must hold finite samples: the first convolution reads 4 samples past a recording's last window with zero weights, and in a
+ * pack those can be the first samples of the next recording.
+ * sd_stage_ms: [0], [1] = the shared inference, [2] = the sum of the finalizes, [3] = the call.
+ * sd_many_plan (host-only): the packed layout.  Recording r has chunks_r = sd_num_chunks(n[r]) chunks and a slot of roundup32(chunks_r + 9) chunks
+ * (none when chunks_r <= 0) at chunk_base[r] = the sum of the earlier slots; *total_chunks = the sum of all slots.  Its samples sit at sample
+ * 8000 * chunk_base[r] of the packed waveform with zeros behind them up to the end of the slot, which lies at or behind the end of its last
+ * chunk's 80 000-sample window; every base is a multiple of 32 chunks = 3 reference embedding batches (sd.cpp:2429).
+ * sd_many_select: makes recording r of the last sd_diarize_many* call of this ctx "the last job" for sd_last_confidence, sd_last_speakers and
+ * sd_last_enrolled (after the call itself that is the last recording that was finalized); SD_ERR_ARG for an r outside the call or one whose
+ * status is not SD_OK. */
+#define SD_MANY_MAX_CHUNKS 357199
+int sd_many_plan(const int64_t* n, int64_t R, int64_t* chunk_base /*[R]*/, int64_t* total_chunks);     /* sd.cpp:1419, 1457, 2429 */
+int sd_diarize_many(sd_ctx*, const int16_t* const* h_pcm /*[R]*/, const int64_t* n /*[R]*/, int64_t R, sd_turn** turns /*[R]*/, int64_t* n_turns /*[R]*/, int32_t* status /*[R]*/);     /* sd.cpp:2937-3234 */
+int sd_diarize_many_dev(sd_ctx*, const int16_t* const* d_pcm /*[R]*/, const int64_t* n /*[R]*/, int64_t R, sd_turn** turns /*[R]*/, int64_t* n_turns /*[R]*/, int32_t* status /*[R]*/);     /* sd.cpp:2937-3234 */
+int sd_diarize_many_f32(sd_ctx*, const float* const* h_wav /*[R]*/, const int64_t* n /*[R]*/, int64_t R, sd_turn** turns /*[R]*/, int64_t* n_turns /*[R]*/, int32_t* status /*[R]*/);     /* sd.cpp:2937-3234, 2948-2951 */
+int sd_many_select(sd_ctx*, int64_t r);     /* sd.cpp:2149-2167, 2191-2207 */
+
 /* ---- a18: the reference's output line (sd.cpp:3439) */
 int sd_format_turn(const sd_turn* t, char* buf, int cap);
 

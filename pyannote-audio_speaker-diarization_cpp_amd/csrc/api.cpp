@@ -2,6 +2,7 @@
 // around the embedding stage, wav reader (wav.h:62-126), output formats and the measurement hooks.
 // (The other stage wrappers and the whole-path driver are in pipeline.cpp.)
 #include "common.h"
+#include "many_plan.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -179,15 +180,7 @@ extern "C" int sd_linkage_method_from_name(const char* name)
 }
 
 // ------------------------------------------------------------------ helpers
-extern "C" int64_t sd_num_chunks(int64_t n, int64_t* last_len)
-{
-    int64_t i = 0, cnt = 0;
-    if (n > SD_CHUNK) { cnt = (n - SD_CHUNK + SD_HOP - 1) / SD_HOP; i = cnt * SD_HOP; }   // while (i + window < n), sd.cpp:1419
-    int64_t ll = 0;
-    if (i + 1 < n) { ll = n - i; cnt++; }                                                  // sd.cpp:1457
-    if (last_len) *last_len = ll;
-    return cnt;
-}
+extern "C" int64_t sd_num_chunks(int64_t n, int64_t* last_len) { return sd_chunk_rule(n, last_len); }      // many_plan.h: the one statement of the rule
 
 // ------------------------------------------------------------------ embedding path
 extern "C" int sd_embed_dev(sd_ctx* c, const float* d_wav, int64_t n, const float* d_masks, int64_t items, int64_t first_item, float* d_emb)

@@ -154,6 +154,15 @@ struct StepStash {
     int64_t infer_items = 0;                   // items of the last shard_infer call (masks / counts workspaces describe them)
 };
 
+// what finalize leaves in the context for one recording of a sd_diarize_many* call (many.hip): sd_many_select puts it back
+struct ManyJob {
+    int status = SD_OK;
+    std::vector<double> conf, cen;
+    std::vector<int64_t> cen_counts;
+    int cen_K = 0, cen_d = 0;
+    std::vector<int32_t> enrolled;
+};
+
 struct sd_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -243,6 +252,7 @@ struct sd_ctx {
     const float* planted_scores = nullptr;      // sd_set_planted: measurement / test hook
     const float* planted_emb = nullptr;
     int64_t planted_lo = 0, planted_n = 0;
+    std::vector<ManyJob> many_jobs;             // per recording of the last sd_diarize_many* call (sd_many_select)
     std::vector<sd_stream*> streams;            // open sd_stream objects of this context (stream.hip); sd_destroy closes what is left
 };
 

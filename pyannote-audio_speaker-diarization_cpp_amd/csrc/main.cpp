@@ -46,6 +46,12 @@
 //   --enroll NAME --speakers FILE [--enroll-span START END]...   no diarization: the voiceprint of the wav -- all of it, or the given spans in seconds --
 //                   (sd_voiceprint_wav) replaces or is appended as NAME in FILE (created when absent); prints "enrolled NAME from N windows".
 //                   A bad value of any of these is a usage error (exit 2) before anything touches the GPU
+//   --many LIST     instead of the wav argument: LIST names one wav file per line (empty lines and lines that start with # are skipped); all of them go
+//                   through the two networks together (sd_diarize_many_f32) and each gets the turns of a run of its own, bit for bit.  Every file is read
+//                   with the --resample / --downmix / --assume-16k rules of the single-file path.  Output: a line "== <path>" and that file's turns, in
+//                   list order; a file that cannot be read, is refused or is too short gets "== <path>: <message>" and the exit status is 1.
+//                   --rttm DIR writes DIR/<file name without .wav>.rttm per recording; --speakers (with or without --enrolled) and --relabel work per
+//                   recording.  Refused with --gpus N > 1, --stream, --activity, --dump-steps and --enroll
 //   --relabel       stdout / RTTM labels renumbered the way pyannote.audio names its output (the clusters that occur,
 //                   sorted by their string, become 0, 1, ... = SPEAKER_00, SPEAKER_01, ...); default = raw cluster ids (sd.cpp:3439)
 #include <cerrno>
@@ -60,12 +66,14 @@
 #include <sys/wait.h>
 #include <unistd.h>
 #include "sdhip.h"
+#include "many_plan.h"
 
 struct Args { const char* seg = nullptr; const char* emb = nullptr; const char* wav = nullptr; const char* rttm = nullptr; int gpus = 1; bool relabel = false; int precision = 0; int wav_flags = 0; const char* dump_dir = nullptr; int dump_level = 1;
               int cl_method = -1; double cl_threshold = -1.0; long long cl_min_size = -1;         // -1: leave the library's default
               int activity = -1; double act[4] = {-1.0, -1.0, -1.0, -1.0}; bool act_hamming = false;      // --activity: SD_ACTIVITY_*; onset, offset, min on, min off (-1: default)
               long long stream_piece = 0; bool stream_updates = false;         // --stream: samples per piece (0: off)
-              const char* speakers = nullptr; double speakers_threshold = -1.0; const char* enroll = nullptr; std::vector<sd_turn> enroll_spans; bool enrolled = false; };      // --speakers FILE, its threshold (-1: default), --enroll NAME and its spans
+              const char* speakers = nullptr; double speakers_threshold = -1.0; const char* enroll = nullptr; std::vector<sd_turn> enroll_spans; bool enrolled = false;
+              const char* many = nullptr; };      // --speakers FILE, its threshold (-1: default), --enroll NAME and its spans
 
 // the clustering hyper-parameters the command line set; false (message printed) on a refusal
 static bool apply_clustering(sd_ctx* ctx, const Args& a)
@@ -221,6 +229,109 @@ static int run_single(const Args& a)
     sd_destroy(ctx);
     TRACE("sd_destroy done");
     return 0;
+}
+
+// ---- --many: the samples sd_diarize_wav would diarize (same readers, same --resample / --downmix / --assume-16k rules) as host floats; 16-bit samples
+// divided by 32768 here are the floats k_pcm_to_f32 makes of them (the division is exact)
+static bool many_load(sd_ctx* ctx, const char* path, int flags, std::vector<float>& out, std::string& msg)
+{
+    {
+        int16_t* pcm = nullptr; int64_t np = 0; int32_t sr16 = 0, ch16 = 0;
+        if (sd_read_wav(path, &pcm, &np, &sr16, &ch16) == SD_OK) {
+            const bool take = (sr16 == 16000 || (flags & SD_WAV_ASSUME_16K)) && !(ch16 > 1 && (flags & SD_WAV_DOWNMIX));
+            if (take) { out.resize((size_t)np); for (int64_t i = 0; i < np; ++i) out[(size_t)i] = (float)pcm[i] * (1.0f / 32768.0f); }
+            sd_free_pcm(pcm);
+            if (take) return true;
+        }
+    }
+    float* wav = nullptr; int64_t n = 0; int32_t sr = 0, ch = 0, bits = 0;
+    if (sd_read_wav_f32(path, &wav, &n, &sr, &ch, &bits) != SD_OK) { msg = "cannot read PCM wav"; return false; }
+    if (ch > 1 && (flags & SD_WAV_DOWNMIX))
+        for (int64_t i = 0; i < n; ++i) {
+            float s = 0.0f;
+            for (int q = 0; q < ch; ++q) s += wav[i * ch + q];
+            wav[i] = s / (float)ch;
+        }
+    bool ok = true;
+    if (sr == 16000 || (flags & SD_WAV_ASSUME_16K)) out.assign(wav, wav + n);
+    else if (!(flags & SD_WAV_RESAMPLE)) { msg = "sample rate " + std::to_string(sr) + " Hz; the pipeline needs 16000 -- pass --resample (or --assume-16k for the reference's behaviour)"; ok = false; }
+    else {
+        int64_t no = 0;
+        const int64_t cap = sd_resample_len(n, sr, 16000);
+        out.assign((size_t)(cap > 0 ? cap : 1), 0.0f);
+        const int rc = n > 0 ? sd_resample(ctx, wav, n, sr, 16000, out.data(), (int64_t)out.size(), &no) : SD_OK;
+        if (rc != SD_OK) { msg = std::string("resampling failed: ") + sd_last_error(ctx); ok = false; }
+        out.resize((size_t)no);
+    }
+    sd_free_wav(wav);
+    return ok;
+}
+
+static int run_many(const Args& a)
+{
+    std::vector<std::string> paths; std::string err;
+    if (!many_read_list(a.many, paths, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
+    Gallery g;
+    if (a.speakers && !g.read(a.speakers)) return 1;
+    sd_ctx* ctx = sd_create(a.seg, a.emb, 0);
+    if (!ctx) { fprintf(stderr, "sd_create failed: %s\n", sd_create_error()); return 1; }
+    auto leave = [&](int rc) { sd_destroy(ctx); return rc; };
+    if (a.precision && sd_set_option(ctx, "ecapa_precision", a.precision) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
+    if (a.precision == 3 && sd_set_option(ctx, "seg_precision", 3) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
+    if (!apply_clustering(ctx, a)) return leave(1);
+    if (a.enrolled && !enrol_gallery(ctx, a, g)) return leave(1);
+    const size_t P = paths.size();
+    std::vector<std::vector<float>> wav(P);
+    std::vector<std::string> msg(P);
+    std::vector<const float*> rows; std::vector<int64_t> lens; std::vector<size_t> who;      // the files that were read
+    for (size_t i = 0; i < P; ++i)
+        if (many_load(ctx, paths[i].c_str(), a.wav_flags, wav[i], msg[i])) {
+            if (wav[i].empty()) { msg[i] = "holds no samples"; continue; }
+            rows.push_back(wav[i].data()); lens.push_back((int64_t)wav[i].size()); who.push_back(i);
+        }
+    const size_t R = rows.size();
+    std::vector<sd_turn*> turns(R ? R : 1, nullptr); std::vector<int64_t> nt(R ? R : 1, 0); std::vector<int32_t> status(R ? R : 1, SD_OK);
+    if (R > 0) {
+        const int rc = sd_diarize_many_f32(ctx, rows.data(), lens.data(), (int64_t)R, turns.data(), nt.data(), status.data());
+        if (rc != SD_OK) { fprintf(stderr, "diarization failed (%d): %s\n", rc, sd_last_error(ctx)); return leave(1); }
+        double ms[4]; sd_stage_ms(ctx, ms);
+        fprintf(stderr, "%zu recordings: segmentation %.1f ms, embedding %.1f ms, clustering %.1f ms, call %.1f ms\n", R, ms[0], ms[1], ms[2], ms[3]);
+    }
+    std::vector<size_t> slot(P, (size_t)-1);
+    for (size_t r = 0; r < R; ++r) slot[who[r]] = r;
+    int worst = 0;
+    std::vector<std::string> stems;
+    for (size_t i = 0; i < P; ++i) {
+        const size_t r = slot[i];
+        if (r != (size_t)-1 && status[r] == SD_ERR_SHORT) msg[i] = "audio of " + std::to_string(lens[r]) + " samples yields no chunk";
+        else if (r != (size_t)-1 && status[r] != SD_OK) msg[i] = "diarization failed (" + std::to_string(status[r]) + ")";
+        if (r == (size_t)-1 || status[r] != SD_OK) { printf("== %s: %s\n", paths[i].c_str(), msg[i].c_str()); worst = 1; continue; }
+        printf("== %s\n", paths[i].c_str());
+        std::vector<const char*> names, turn_name((size_t)nt[r], nullptr);
+        if (a.speakers && sd_many_select(ctx, (int64_t)r) == SD_OK && (a.enrolled ? enrolled_names(ctx, g, names) : match_clusters(ctx, a, g, names)))
+            for (int64_t t = 0; t < nt[r]; ++t) if (turns[r][t].label >= 0 && (size_t)turns[r][t].label < names.size()) turn_name[(size_t)t] = names[(size_t)turns[r][t].label];
+        if (a.relabel) sd_relabel_turns(turns[r], nt[r]);
+        char line[160];
+        for (int64_t t = 0; t < nt[r]; ++t) {
+            if (turn_name[(size_t)t]) { printf("[%g -- %g] --> %s\n", turns[r][t].start, turns[r][t].end, turn_name[(size_t)t]); continue; }
+            sd_format_turn(&turns[r][t], line, sizeof(line)); printf("%s\n", line);
+        }
+        if (a.rttm) {
+            std::string stem = paths[i].substr(paths[i].find_last_of('/') == std::string::npos ? 0 : paths[i].find_last_of('/') + 1);
+            if (stem.size() > 4 && stem.compare(stem.size() - 4, 4, ".wav") == 0) stem.resize(stem.size() - 4);
+            for (const std::string& s : stems) if (s == stem) { stem += "_" + std::to_string(i); break; }      // the same file name twice in the list
+            stems.push_back(stem);
+            const std::string out = std::string(a.rttm) + "/" + stem + ".rttm";
+            std::vector<const char*> by_label;
+            for (int64_t t = 0; t < nt[r]; ++t) if (turns[r][t].label >= 0) { if ((size_t)turns[r][t].label >= by_label.size()) by_label.resize((size_t)turns[r][t].label + 1, nullptr); by_label[(size_t)turns[r][t].label] = turn_name[(size_t)t]; }
+            const int rc = a.speakers ? sd_write_rttm_named(out.c_str(), paths[i].c_str(), turns[r], nt[r], nullptr, by_label.data(), (int64_t)by_label.size())
+                                      : sd_write_rttm(out.c_str(), paths[i].c_str(), turns[r], nt[r]);
+            if (rc != SD_OK) { fprintf(stderr, "cannot write %s\n", out.c_str()); worst = 1; }
+        }
+    }
+    fflush(stdout);
+    for (size_t r = 0; r < R; ++r) sd_free_turns(turns[r]);
+    return leave(worst);
 }
 
 // ---- --stream: the recording goes through an sd_stream piece by piece
@@ -449,6 +560,10 @@ int main(int argc, char* argv[])
                 if (end == v || *end || a.cl_min_size < 1 || a.cl_min_size > 0x7fffffff) { fprintf(stderr, "usage: --min-cluster-size takes an integer >= 1 (got '%s')\n", v); return 2; }
             }
         }
+        else if (s == "--many") {
+            if (i + 1 >= argc || !argv[i + 1][0]) { fprintf(stderr, "usage: --many needs a list file\n"); return 2; }
+            a.many = argv[++i];
+        }
         else if (s == "--stream-updates") a.stream_updates = true;
         else if (s == "--enrolled") a.enrolled = true;
         else if (s == "--stream") {
@@ -518,6 +633,9 @@ int main(int argc, char* argv[])
     if (a.enrolled && a.enroll) { fprintf(stderr, "usage: --enrolled enrols the voiceprints of FILE for a diarization; --enroll runs none and is refused with it\n"); return 2; }
     if (a.enrolled && a.dump_dir) { fprintf(stderr, "usage: --dump-steps describes the reference's flow; --enrolled is refused with it\n"); return 2; }
     if (a.enroll && (a.stream_piece > 0 || a.dump_dir)) { fprintf(stderr, "usage: --enroll runs no diarization; --stream and --dump-steps are refused with it\n"); return 2; }
+    if (a.many && (a.gpus > 1 || a.stream_piece > 0 || a.activity >= 0 || a.dump_dir || a.enroll)) { fprintf(stderr, "usage: --many diarizes a list of recordings on one GPU; --gpus N, --stream, --activity, --dump-steps and --enroll are refused with it\n"); return 2; }
+    if (a.many && pos.size() != 2) { fprintf(stderr, "usage: --many LIST takes the place of the wav argument\n"); return 2; }
+    if (a.many) { a.seg = pos[0]; a.emb = pos[1]; return run_many(a); }
     if (pos.size() < 3) {
         printf("program [segment model file] [embeding model file] [wave file]\n");   // sd.cpp:3423
         return 0;

@@ -1,0 +1,229 @@
+// many.hip -- sd_diarize_many*: many recordings in one call, both networks over one packed waveform, finalize per recording.
+//
+// Layout (many_plan.h): recording r gets a slot of roundup32(chunks_r + 9) chunks at chunk base B_r, sample base 8000 B_r, zeros behind its n_r
+// samples.  Packed chunk B_r + k starts at the sample where chunk k of the recording alone starts, B_r * 3 is a multiple of 96 items, so the
+// reference's embedding batches of 32 items (sd.cpp:2429) fall where they fall in the recording alone, and the 9+ chunks behind chunks_r are
+// nobody's: their masks are zeroed, frontend_prepare drops their items as dead, finalize never sees their rows.
+//   k_many_pack       one launch: the samples of every recording into its slot (16-bit: x 1/32768 as k_pcm_to_f32; f32: copied), zeros behind them
+//   k_many_gap_masks  one launch: zero mask rows for the gap chunks of every slot
+// Both walk a table indexed by recording; every store is guarded by the row's own slot length and by the length of the destination.
+#include "common.h"
+#include "many_plan.h"
+#include <algorithm>
+
+struct ManyRow { const void* src; int64_t n, base, len; };      // src[0, n) -> dst[base, base + n), zeros in dst[base + n, base + len)
+struct ManyGap { int64_t first, count; };                         // chunks [first, first + count) belong to nobody
+
+// grid (x: a stride over the samples of a slot, y: a stride over the table), 256 threads
+__global__ void k_many_pack(const ManyRow* __restrict__ rows, int R, int is_f32, float* __restrict__ dst, int64_t dst_len)
+{
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    for (int r = blockIdx.y; r < R; r += gridDim.y) {
+        const ManyRow row = rows[r];
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < row.len && row.base + i < dst_len; i += step) {
+            float v = 0.0f;
+            if (i < row.n) v = is_f32 ? ((const float*)row.src)[i] : (float)((const int16_t*)row.src)[i] * (1.0f / 32768.0f);      // sd.cpp:2948-2951
+            dst[row.base + i] = v;
+        }
+    }
+}
+
+// masks [total_chunks * 3][293]; same grid shape
+__global__ void k_many_gap_masks(const ManyGap* __restrict__ gaps, int G, float* __restrict__ masks, int64_t total_chunks)
+{
+    const int64_t step = (int64_t)gridDim.x * blockDim.x, per = (int64_t)SD_SPEAKERS * SD_FRAMES, all = total_chunks * per;
+    for (int g = blockIdx.y; g < G; g += gridDim.y) {
+        const ManyGap gap = gaps[g];
+        const int64_t first = gap.first * per, cnt = gap.count * per;
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt && first + i < all; i += step) masks[first + i] = 0.0f;
+    }
+}
+
+static dim3 many_grid(int64_t longest, int64_t table)
+{
+    const int64_t gx = std::min<int64_t>(std::max<int64_t>((longest + 255) / 256, 1), 2048), gy = std::min<int64_t>(std::max<int64_t>(table, 1), 1024);
+    return dim3((unsigned)gx, (unsigned)gy);
+}
+
+extern "C" int sd_many_plan(const int64_t* n, int64_t R, int64_t* chunk_base, int64_t* total_chunks)
+{
+    return many_plan(n, R, chunk_base, total_chunks) ? SD_ERR_ARG : SD_OK;
+}
+
+// ------------------------------------------------------------------ segmentation over the pack
+// A full chunk of a recording reads samples of that recording only, and packed chunk B_r + k starts where chunk k starts: run_segment on the pack
+// "as one recording" computes it from the same samples with the same kernels -- provided its batch is on the same side of the one threshold at
+// which PyanNet's kernels change with the batch size: up to SD_SKINNY_MAX_ROWS / 293 = 13 chunks the dense layers take k_skinny_gemm, above that
+// the 128 x 128 tile, and the two differ in the last bits (common.h; stream.hip minds the same thing).  So the plan keeps, for every chunk, the
+// side its batch has in the loop of single calls (batches of seg_batch_chunks from chunk 0 of the recording):
+//   tile side    chunks [0, T_r): ranges of neighbouring recordings are joined across the gap chunks between them (rows that nobody reads) and
+//                run in shared batches of seg_batch_chunks, each of 14 chunks or more;
+//   skinny side  chunks [T_r, full_r): the batches of the single path, one recording at a time (a batch of at most 13 chunks has no room for more);
+//   short last chunk (sd.cpp:1457-1480): the single path's own call on a view of the slot -- its frame count depends on its length, and the shared
+//                first convolution the single path takes for it is not the per-row form of run_segment_rows bit for bit (tests/test_next_rows.py)
+struct ManyRec { int64_t n, chunks, base, full, last_len; };
+#define MANY_SKINNY_CHUNKS (SD_SKINNY_MAX_ROWS / SD_FRAMES)
+#define MANY_JOIN_CHUNKS 256      /* tile ranges at most this far apart are one range: up to 4096 chunks are one wave of LSTM workgroups, a launch sequence more costs more */
+
+static int many_segment(sd_ctx* c, const float* d_pack, int64_t total, const std::vector<ManyRec>& rec, float* d_seg)
+{
+    const size_t row = (size_t)SD_FRAMES * 3;
+    const int64_t cb = c->seg_batch_chunks < 1 ? 1 : c->seg_batch_chunks;
+    const DevWav pack{d_pack, total * (int64_t)SD_HOP, 0, true};      // sd_num_chunks of it = total - 9 full chunks and no short one: every real chunk is among them
+    std::vector<std::pair<int64_t, int64_t>> tile, skinny;
+    for (const ManyRec& q : rec) {
+        if (q.chunks <= 0) continue;
+        const int64_t rem = q.full % cb;
+        const int64_t T = cb <= MANY_SKINNY_CHUNKS ? 0 : ((rem == 0 || rem > MANY_SKINNY_CHUNKS) ? q.full : q.full - rem);
+        if (T > 0) {
+            if (!tile.empty() && q.base - tile.back().second <= MANY_JOIN_CHUNKS) tile.back().second = q.base + T;
+            else tile.emplace_back(q.base, q.base + T);
+        }
+        for (int64_t k = T; k < q.full; k += cb) skinny.emplace_back(q.base + k, q.base + std::min(q.full, k + cb));
+    }
+    int rc;
+    for (const auto& t : tile)
+        for (int64_t k = t.first; k < t.second; k += cb) {
+            int64_t lo = k, hi = std::min(t.second, k + cb);
+            if (hi - lo <= MANY_SKINNY_CHUNKS) lo = hi - (MANY_SKINNY_CHUNKS + 1);      // the rest of a range: reaches back into chunks already computed (same bits) to stay on the tile side
+            if ((rc = run_segment(c, pack, lo, hi, d_seg + (size_t)lo * row))) return rc;
+        }
+    for (const auto& s : skinny)
+        if ((rc = run_segment(c, pack, s.first, s.second, d_seg + (size_t)s.first * row))) return rc;
+    for (const ManyRec& q : rec) {
+        if (q.chunks <= 0 || q.full == q.chunks) continue;
+        const DevWav view{d_pack + q.base * (int64_t)SD_HOP, q.n, 0, true};      // zeros up to the end of the slot, at least 8000 of them behind a short last chunk
+        if ((rc = run_segment(c, view, q.chunks - 1, q.chunks, d_seg + (size_t)(q.base + q.chunks - 1) * row))) return rc;
+    }
+    return SD_OK;
+}
+
+// ------------------------------------------------------------------ the call
+enum { MANY_PCM_HOST, MANY_PCM_DEV, MANY_F32_HOST };
+
+static int many_run(sd_ctx* c, const void* const* src, int form, const int64_t* n, int64_t R, sd_turn** turns, int64_t* n_turns, int32_t* status, const char* who)
+{
+    // refusals: nothing is touched
+    if (!src || !n || !turns || !n_turns || !status || R < 1) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument (R >= 1)", who);
+    for (int64_t r = 0; r < R; ++r) if (!src[r]) SD_FAIL(c, SD_ERR_ARG, "%s: recording %lld is a null pointer", who, (long long)r);
+    if (!c->dump_dir.empty()) SD_FAIL(c, SD_ERR_ARG, "%s: a dump directory is set (the step files describe one recording)", who);
+    if (c->planted_n > 0) SD_FAIL(c, SD_ERR_ARG, "%s: a planted workload is set (its chunk range means one recording)", who);
+    std::vector<int64_t> base((size_t)R);
+    int64_t total = 0;
+    if (many_plan(n, R, base.data(), &total)) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument (at most 2^20 recordings of at most 2^40 samples)", who);
+    if (total > SD_MANY_MAX_CHUNKS) SD_FAIL(c, SD_ERR_ARG, "%s: %lld packed chunks (limit %d: the rows of one call are counted in int)", who, (long long)total, SD_MANY_MAX_CHUNKS);
+    int rc;
+    if ((rc = enrolled_refusal(c, SD_EMB_DIM, c->num_clusters, c->min_clusters, c->max_clusters))) return rc;
+
+    const double t0 = now_ms();
+    clear_stage_ms(c);
+    std::vector<ManyRec> rec((size_t)R);
+    std::vector<ManyRow> rows;
+    std::vector<ManyGap> gaps;
+    int64_t src_samples = 0, longest = SD_WAV_PAD, longest_gap = 0;
+    for (int64_t r = 0; r < R; ++r) {
+        ManyRec& q = rec[(size_t)r];
+        q.n = n[r]; q.base = base[(size_t)r];
+        q.chunks = sd_chunk_rule(q.n, &q.last_len);
+        q.full = (q.last_len > 0 && q.last_len < SD_CHUNK) ? q.chunks - 1 : q.chunks;
+        if (q.chunks <= 0) continue;
+        const int64_t slot = many_slot_chunks(q.n);
+        rows.push_back(ManyRow{src[r], q.n, q.base * (int64_t)SD_HOP, slot * (int64_t)SD_HOP});
+        gaps.push_back(ManyGap{q.base + q.chunks, slot - q.chunks});
+        src_samples += q.n;
+        longest = std::max(longest, slot * (int64_t)SD_HOP);
+        longest_gap = std::max(longest_gap, slot - q.chunks);
+    }
+    c->many_jobs.assign((size_t)R, ManyJob());
+    for (int64_t r = 0; r < R; ++r) { turns[r] = nullptr; n_turns[r] = 0; status[r] = SD_ERR_SHORT; c->many_jobs[(size_t)r].status = SD_ERR_SHORT; }
+    if (total <= 0) { c->stage_ms[3] = now_ms() - t0; return SD_OK; }
+    rows.push_back(ManyRow{nullptr, 0, total * (int64_t)SD_HOP, SD_WAV_PAD});      // the zeroed floats behind the last slot (DevWav::padded)
+
+    const int64_t pack_len = total * (int64_t)SD_HOP + SD_WAV_PAD;
+    const size_t row_bytes = rows.size() * sizeof(ManyRow), gap_bytes = gaps.size() * sizeof(ManyGap);
+    WS(c, float, d_pack, "many_wav", pack_len);
+    WS(c, char, d_tab, "many_tab", row_bytes + gap_bytes);
+    WS(c, float, d_seg, "many_seg", total * SD_FRAMES * 3);
+    WS(c, float, d_masks, "many_masks", total * 3 * SD_FRAMES);
+    WS(c, float, d_emb, "many_emb", total * 3 * SD_EMB_DIM);
+    if (form != MANY_PCM_DEV) {      // host rows: uploaded back to back, then packed like device rows
+        const size_t es = form == MANY_F32_HOST ? sizeof(float) : sizeof(int16_t);
+        WS(c, char, d_src, "many_src", (size_t)src_samples * es);
+        size_t off = 0;
+        for (ManyRow& w : rows) {
+            if (!w.src) continue;
+            HIPCHK(c, hipMemcpyAsync(d_src + off, w.src, (size_t)w.n * es, hipMemcpyHostToDevice, c->stream));
+            w.src = d_src + off;
+            off += (size_t)w.n * es;
+        }
+    }
+    HIPCHK(c, hipMemcpy(d_tab, rows.data(), row_bytes, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_tab + row_bytes, gaps.data(), gap_bytes, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_many_pack, many_grid(longest, (int64_t)rows.size()), dim3(256), 0, c->stream, (const ManyRow*)d_tab, (int)rows.size(),
+                       form == MANY_F32_HOST ? 1 : 0, d_pack, pack_len);
+    KCHECK(c);
+
+    // both networks once over the pack (shard_infer's steps; the segmentation step is many_segment)
+    HIPCHK(c, hipMemsetAsync(d_seg, 0, (size_t)total * SD_FRAMES * 3 * sizeof(float), c->stream));      // gap rows: defined values for run_postseg
+    if ((rc = many_segment(c, d_pack, total, rec, d_seg))) return rc;
+    if ((rc = run_postseg(c, d_seg, total, nullptr, d_masks, nullptr))) return rc;
+    hipLaunchKernelGGL(k_many_gap_masks, many_grid(longest_gap * SD_SPEAKERS * SD_FRAMES, (int64_t)gaps.size()), dim3(256), 0, c->stream,
+                       (const ManyGap*)(d_tab + row_bytes), (int)gaps.size(), d_masks, total);
+    KCHECK(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const double t1 = now_ms();
+    c->stage_ms[0] = t1 - t0;
+    // w.n is the packed length here.  The one place below run_embed that reads it, k_stft_fbank, clips a VALUE with it (a sample at or behind n reads
+    // as 0.0f): behind n_r the pack holds the same +0.0f.  The sample COUNTS of an item come from its mask row alone (k_mask_prefix) in both paths
+    if ((rc = run_embed(c, DevWav{d_pack, total * (int64_t)SD_HOP, 0, true}, d_masks, total * 3, 0, d_emb))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->stage_ms[1] = now_ms() - t1;
+
+    // finalize, one recording after the other; what it leaves in the context is kept per recording
+    auto give_back = [&]() { for (int64_t r = 0; r < R; ++r) { sd_free_turns(turns[r]); turns[r] = nullptr; n_turns[r] = 0; } };
+    for (int64_t r = 0; r < R; ++r) {
+        const ManyRec& q = rec[(size_t)r];
+        if (q.chunks <= 0) continue;
+        std::vector<sd_turn> v;
+        rc = finalize(c, d_seg + (size_t)q.base * SD_FRAMES * 3, d_emb + (size_t)q.base * 3 * SD_EMB_DIM, q.chunks, q.n, v);
+        ManyJob& job = c->many_jobs[(size_t)r];
+        status[r] = job.status = rc;
+        if (rc == SD_ERR_NUMERIC) continue;                    // this recording's clustering; the others go on
+        if (rc == SD_OK) rc = turns_out(c, v, &turns[r], &n_turns[r]);
+        if (rc) { give_back(); return rc; }
+        job.conf = c->last_conf; job.cen = c->last_cen; job.cen_counts = c->last_cen_counts;
+        job.cen_K = c->last_cen_K; job.cen_d = c->last_cen_d; job.enrolled = c->last_enrolled;
+    }
+    c->stage_ms[3] = now_ms() - t0;
+    return SD_OK;
+}
+
+extern "C" int sd_diarize_many(sd_ctx* c, const int16_t* const* h_pcm, const int64_t* n, int64_t R, sd_turn** turns, int64_t* n_turns, int32_t* status)
+{
+    ENTER(c);
+    return many_run(c, (const void* const*)h_pcm, MANY_PCM_HOST, n, R, turns, n_turns, status, "sd_diarize_many");
+}
+
+extern "C" int sd_diarize_many_dev(sd_ctx* c, const int16_t* const* d_pcm, const int64_t* n, int64_t R, sd_turn** turns, int64_t* n_turns, int32_t* status)
+{
+    ENTER(c);
+    return many_run(c, (const void* const*)d_pcm, MANY_PCM_DEV, n, R, turns, n_turns, status, "sd_diarize_many_dev");
+}
+
+extern "C" int sd_diarize_many_f32(sd_ctx* c, const float* const* h_wav, const int64_t* n, int64_t R, sd_turn** turns, int64_t* n_turns, int32_t* status)
+{
+    ENTER(c);
+    return many_run(c, (const void* const*)h_wav, MANY_F32_HOST, n, R, turns, n_turns, status, "sd_diarize_many_f32");
+}
+
+extern "C" int sd_many_select(sd_ctx* c, int64_t r)
+{
+    if (!c) return SD_ERR_ARG;
+    c->err.clear();
+    if (r < 0 || r >= (int64_t)c->many_jobs.size()) SD_FAIL(c, SD_ERR_ARG, "sd_many_select: the last sd_diarize_many* call of this context had %zu recordings", c->many_jobs.size());
+    const ManyJob& job = c->many_jobs[(size_t)r];
+    if (job.status != SD_OK) SD_FAIL(c, SD_ERR_ARG, "sd_many_select: recording %lld ended with status %d and left no job", (long long)r, job.status);
+    c->last_conf = job.conf; c->last_cen = job.cen; c->last_cen_counts = job.cen_counts;
+    c->last_cen_K = job.cen_K; c->last_cen_d = job.cen_d; c->last_enrolled = job.enrolled;
+    return SD_OK;
+}

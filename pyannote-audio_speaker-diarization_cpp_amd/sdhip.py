@@ -58,6 +58,7 @@ EXPORTS = [
     "sd_last_speakers", "sd_span_masks", "sd_voiceprint", "sd_voiceprint_dev", "sd_voiceprint_f32", "sd_voiceprint_wav", "sd_speaker_distances",
     "sd_match_speakers", "sd_read_voiceprints", "sd_write_voiceprints", "sd_free_voiceprints", "sd_voiceprints_error", "sd_write_rttm_named",
     "sd_set_enrolled", "sd_enrolled_info", "sd_nearest_speakers", "sd_last_enrolled",
+    "sd_many_plan", "sd_diarize_many", "sd_diarize_many_dev", "sd_diarize_many_f32", "sd_many_select",
 ]
 # SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
 LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
@@ -172,6 +173,11 @@ def lib():
     L.sd_enrolled_info.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_int)]
     L.sd_nearest_speakers.argtypes = [vp, vp, i64, vp, i64, C.c_int, vp, vp]
     L.sd_last_enrolled.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    if hasattr(L, "sd_many_plan"):      # (an older build loaded through SDHIP_LIB by the A/B tools has none of these)
+        L.sd_many_plan.argtypes = [vp, i64, vp, vp]
+        for f in (L.sd_diarize_many, L.sd_diarize_many_dev, L.sd_diarize_many_f32):
+            f.argtypes = [vp, vp, vp, i64, vp, vp, vp]
+        L.sd_many_select.argtypes = [vp, i64]
     L.sd_format_turn.argtypes = [C.POINTER(Turn), C.c_char_p, C.c_int]
     L.sd_stage_ms.argtypes = [vp, C.POINTER(dbl)]
     L.sd_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
@@ -281,6 +287,17 @@ def shard_sample_range(lo, hi, n_total):
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def many_plan(lengths):
+    """sd_many_plan (host-only): (chunk_base [R] int64, total_chunks) of the packed layout of sd_diarize_many* for recordings of these lengths"""
+    n = np.ascontiguousarray(lengths, np.int64)
+    base = np.zeros(len(n), np.int64)
+    total = C.c_int64(0)
+    rc = lib().sd_many_plan(_ptr(n) if len(n) else None, len(n), _ptr(base) if len(n) else None, C.addressof(total))
+    if rc:
+        raise SdError(rc, "sd_many_plan: bad argument")
+    return base, total.value
 
 
 def convert_onnx(onnx_path, kind, out_path):
@@ -775,6 +792,40 @@ class Diarizer:
         n = C.c_int64(0)
         self._chk(lib().sd_diarize_dev(self._h, C.c_void_p(d_pcm_ptr), n_samples, C.byref(p), C.byref(n)))
         return self._clustered(p, n)
+
+    def _many(self, fn, ptrs, lengths):
+        """one sd_diarize_many* call -> per recording the turns, or the error code (SD_ERR_SHORT = 4, SD_ERR_NUMERIC = 5) it ended with"""
+        R = len(ptrs)
+        rows = (C.c_void_p * max(R, 1))(*ptrs)
+        n = (C.c_int64 * max(R, 1))(*[int(v) for v in lengths])
+        turns = (C.POINTER(Turn) * max(R, 1))()
+        nt = (C.c_int64 * max(R, 1))()
+        status = (C.c_int32 * max(R, 1))()
+        self._chk(fn(self._h, rows, n, R, turns, nt, status))
+        self._last_d = EMB_DIM
+        out = []
+        for r in range(R):
+            t = self._turns(turns[r], C.c_int64(nt[r]))
+            out.append(t if status[r] == 0 else int(status[r]))
+        return out
+
+    def diarize_many(self, recordings):
+        """sd_diarize_many: int16 recordings -> list of (turns | error code), each what diarize() gives for that recording alone"""
+        recs = [np.ascontiguousarray(p, np.int16) for p in recordings]
+        return self._many(lib().sd_diarize_many, [p.ctypes.data for p in recs], [len(p) for p in recs])
+
+    def diarize_many_f32(self, recordings):
+        recs = [np.ascontiguousarray(p, np.float32) for p in recordings]
+        return self._many(lib().sd_diarize_many_f32, [p.ctypes.data for p in recs], [len(p) for p in recs])
+
+    def diarize_many_dev(self, d_pcm_ptrs, lengths):
+        """sd_diarize_many_dev: device pointers of int16 recordings and their lengths"""
+        return self._many(lib().sd_diarize_many_dev, [int(p) for p in d_pcm_ptrs], lengths)
+
+    def many_select(self, r):
+        """sd_many_select: recording r of the last diarize_many* call becomes the last job of last_confidence / last_speakers / last_enrolled"""
+        self._chk(lib().sd_many_select(self._h, int(r)))
+        self._last_d = EMB_DIM
 
     def shard_infer_dev(self, d_pcm_shard_ptr, first_sample, shard_samples, n_total, chunk_lo, chunk_hi, d_seg_ptr, d_emb_ptr):
         self._chk(lib().sd_shard_infer_dev(self._h, C.c_void_p(d_pcm_shard_ptr), first_sample, shard_samples, n_total,
