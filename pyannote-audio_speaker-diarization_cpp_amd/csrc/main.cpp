@@ -67,6 +67,7 @@
 #include <unistd.h>
 #include "sdhip.h"
 #include "many_plan.h"
+#include "wav_file.h"
 
 struct Args { const char* seg = nullptr; const char* emb = nullptr; const char* wav = nullptr; const char* rttm = nullptr; int gpus = 1; bool relabel = false; int precision = 0; int wav_flags = 0; const char* dump_dir = nullptr; int dump_level = 1;
               int cl_method = -1; double cl_threshold = -1.0; long long cl_min_size = -1;         // -1: leave the library's default
@@ -82,6 +83,19 @@ static bool apply_clustering(sd_ctx* ctx, const Args& a)
     if (a.cl_threshold >= 0.0 && sd_set_option_f64(ctx, "clustering_threshold", a.cl_threshold) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
     if (a.cl_min_size >= 0 && sd_set_option(ctx, "min_cluster_size", a.cl_min_size) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
     return true;
+}
+
+// the context of a run: created on `device`, --precision and the clustering hyper-parameters set.  Null on a failure: the message is printed (behind
+// `prefix`: run_rank's "rank N: ") and what was created is destroyed
+static sd_ctx* open_context(const Args& a, int device = 0, const char* prefix = "")
+{
+    sd_ctx* ctx = sd_create(a.seg, a.emb, device);
+    if (!ctx) { fprintf(stderr, "%ssd_create failed: %s\n", prefix, sd_create_error()); return nullptr; }
+    if ((a.precision && sd_set_option(ctx, "ecapa_precision", a.precision) != SD_OK) || (a.precision == 3 && sd_set_option(ctx, "seg_precision", 3) != SD_OK))
+        fprintf(stderr, "%s%s\n", prefix, sd_last_error(ctx));
+    else if (apply_clustering(ctx, a)) return ctx;
+    sd_destroy(ctx);
+    return nullptr;
 }
 
 static const char* const kActivityKeys[4] = {"activity_onset", "activity_offset", "activity_min_duration_on", "activity_min_duration_off"};
@@ -138,17 +152,17 @@ static bool enrolled_names(sd_ctx* ctx, const Gallery& g, std::vector<const char
     return true;
 }
 
-static void print_block(sd_ctx* ctx, sd_turn* turns, int64_t nt, const Args& a, const double* ms_sum = nullptr, const std::vector<const char*>* names = nullptr)
+// --speakers, after a job: names[k] = the name raw label k of the last job goes by, or null; false (message printed) on a failure
+static bool cluster_names(sd_ctx* ctx, const Args& a, const Gallery& g, std::vector<const char*>& names)
 {
-    double ms[4];
-    if (ms_sum) memcpy(ms, ms_sum, sizeof(ms)); else sd_stage_ms(ctx, ms);
-    printf("-----------\nSegmenations time: %lldms\n", (long long)ms[0]);      // labels of sd.cpp:3028, 3110, 3231
-    printf("-----------\nEmbedding time: %lldms\n", (long long)ms[1]);
-    printf("-----------\nClustering time: %lldms\n", (long long)ms[2]);
-    printf("\n----Summary----\n-----------\nTime cost: %lldms\n", (long long)ms[3]);
-    printf("----------------------------------------------------\n");
-    // the name of every turn by its raw label, before --relabel renumbers the labels
-    std::vector<const char*> turn_name((size_t)nt, nullptr);
+    return a.enrolled ? enrolled_names(ctx, g, names) : match_clusters(ctx, a, g, names);
+}
+
+// The turn lines of a block.  First the name of every turn by its raw label (names: null = none), then --relabel renumbers the labels, then the lines.
+// turn_name: the name each turn was printed under, or null
+static void print_turns(sd_turn* turns, int64_t nt, const Args& a, const std::vector<const char*>* names, std::vector<const char*>& turn_name)
+{
+    turn_name.assign((size_t)nt, nullptr);
     if (names) for (int64_t i = 0; i < nt; ++i) if (turns[i].label >= 0 && (size_t)turns[i].label < names->size()) turn_name[(size_t)i] = (*names)[(size_t)turns[i].label];
     if (a.relabel && a.activity < 0) sd_relabel_turns(turns, nt);
     char line[160];
@@ -158,10 +172,30 @@ static void print_block(sd_ctx* ctx, sd_turn* turns, int64_t nt, const Args& a, 
         else sd_format_turn(&turns[i], line, sizeof(line));
         printf("%s\n", line);
     }
+}
+
+// the name table of sd_write_rttm_named: names by the labels as they are behind print_turns
+static std::vector<const char*> names_by_label(const sd_turn* turns, int64_t nt, const std::vector<const char*>& turn_name)
+{
+    std::vector<const char*> by_label;
+    for (int64_t i = 0; i < nt; ++i) if (turns[i].label >= 0) { if ((size_t)turns[i].label >= by_label.size()) by_label.resize((size_t)turns[i].label + 1, nullptr); by_label[(size_t)turns[i].label] = turn_name[(size_t)i]; }
+    return by_label;
+}
+
+static void print_block(sd_ctx* ctx, sd_turn* turns, int64_t nt, const Args& a, const double* ms_sum = nullptr, const std::vector<const char*>* names = nullptr)
+{
+    double ms[4];
+    if (ms_sum) memcpy(ms, ms_sum, sizeof(ms)); else sd_stage_ms(ctx, ms);
+    printf("-----------\nSegmenations time: %lldms\n", (long long)ms[0]);      // labels of sd.cpp:3028, 3110, 3231
+    printf("-----------\nEmbedding time: %lldms\n", (long long)ms[1]);
+    printf("-----------\nClustering time: %lldms\n", (long long)ms[2]);
+    printf("\n----Summary----\n-----------\nTime cost: %lldms\n", (long long)ms[3]);
+    printf("----------------------------------------------------\n");
+    std::vector<const char*> turn_name;
+    print_turns(turns, nt, a, names, turn_name);
     printf("----------------------------------------------------\n");
     if (a.rttm && names) {
-        std::vector<const char*> by_label;                      // names by the labels as they are now
-        for (int64_t i = 0; i < nt; ++i) if (turns[i].label >= 0) { if ((size_t)turns[i].label >= by_label.size()) by_label.resize((size_t)turns[i].label + 1, nullptr); by_label[(size_t)turns[i].label] = turn_name[(size_t)i]; }
+        const std::vector<const char*> by_label = names_by_label(turns, nt, turn_name);
         sd_write_rttm_named(a.rttm, a.wav, turns, nt, nullptr, by_label.data(), (int64_t)by_label.size());
     }
     else if (a.rttm) sd_write_rttm(a.rttm, a.wav, turns, nt);
@@ -209,62 +243,48 @@ static int run_single(const Args& a)
     TRACE("run_single");
     Gallery g;
     if (a.speakers && !g.read(a.speakers)) return 1;
-    sd_ctx* ctx = sd_create(a.seg, a.emb, 0);
-    if (!ctx) { fprintf(stderr, "sd_create failed: %s\n", sd_create_error()); return 1; }
+    sd_ctx* ctx = open_context(a);
+    if (!ctx) return 1;
     TRACE("sd_create done");
-    if (a.precision && sd_set_option(ctx, "ecapa_precision", a.precision) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return 1; }
-    if (a.precision == 3 && sd_set_option(ctx, "seg_precision", 3) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return 1; }
-    if (a.dump_dir && sd_set_dump_dir(ctx, a.dump_dir, a.dump_level) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return 1; }
-    if (!apply_clustering(ctx, a) || !apply_activity(ctx, a)) return 1;
-    if (a.enrolled && !enrol_gallery(ctx, a, g)) return 1;
     sd_turn* turns = nullptr; int64_t nt = 0;
+    auto leave = [&](int rc) { sd_free_turns(turns); sd_destroy(ctx); return rc; };      // every way out gives back what it holds
+    if (a.dump_dir && sd_set_dump_dir(ctx, a.dump_dir, a.dump_level) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
+    if (!apply_activity(ctx, a)) return leave(1);
+    if (a.enrolled && !enrol_gallery(ctx, a, g)) return leave(1);
     const int rc = a.activity >= 0 ? sd_activity_wav(ctx, a.wav, a.wav_flags, a.activity, &turns, &nt)
                                    : sd_diarize_wav(ctx, a.wav, a.wav_flags, &turns, &nt);      // 8 / 16 / 32-bit PCM like wav.h:99-122; rate and channels checked
-    if (rc != SD_OK) { fprintf(stderr, "%s failed (%d): %s\n", a.activity >= 0 ? "activity detection" : "diarization", rc, sd_last_error(ctx)); return 1; }
+    if (rc != SD_OK) { fprintf(stderr, "%s failed (%d): %s\n", a.activity >= 0 ? "activity detection" : "diarization", rc, sd_last_error(ctx)); return leave(1); }
     TRACE("sd_diarize_wav done");
     std::vector<const char*> names;
-    if (a.speakers && !(a.enrolled ? enrolled_names(ctx, g, names) : match_clusters(ctx, a, g, names))) return 1;
+    if (a.speakers && !cluster_names(ctx, a, g, names)) return leave(1);
     print_block(ctx, turns, nt, a, nullptr, a.speakers ? &names : nullptr);
-    sd_free_turns(turns);
-    sd_destroy(ctx);
+    const int done = leave(0);
     TRACE("sd_destroy done");
-    return 0;
+    return done;
 }
 
-// ---- --many: the samples sd_diarize_wav would diarize (same readers, same --resample / --downmix / --assume-16k rules) as host floats; 16-bit samples
-// divided by 32768 here are the floats k_pcm_to_f32 makes of them (the division is exact)
+// ---- the off-rate samples of a file (WavLoad::F32_OFF_RATE) at 16 kHz: sd_resample, the kernel the wav entries of the library resample with
+static int resample_16k(sd_ctx* ctx, const WavLoad& f, std::vector<float>& out)
+{
+    const int64_t cap = sd_resample_len(f.n, f.sr, 16000);
+    out.assign((size_t)(cap > 0 ? cap : 1), 0.0f);
+    int64_t no = 0;
+    const int rc = sd_resample(ctx, f.f32, f.n, f.sr, 16000, out.data(), (int64_t)out.size(), &no);
+    out.resize((size_t)(rc == SD_OK ? no : 0));
+    return rc;
+}
+
+// ---- --many: the samples sd_diarize_wav would diarize (wav_load: same readers, same --resample / --downmix / --assume-16k rules) as host floats; 16-bit
+// samples divided by 32768 here are the floats k_pcm_to_f32 makes of them (the division is exact)
 static bool many_load(sd_ctx* ctx, const char* path, int flags, std::vector<float>& out, std::string& msg)
 {
-    {
-        int16_t* pcm = nullptr; int64_t np = 0; int32_t sr16 = 0, ch16 = 0;
-        if (sd_read_wav(path, &pcm, &np, &sr16, &ch16) == SD_OK) {
-            const bool take = (sr16 == 16000 || (flags & SD_WAV_ASSUME_16K)) && !(ch16 > 1 && (flags & SD_WAV_DOWNMIX));
-            if (take) { out.resize((size_t)np); for (int64_t i = 0; i < np; ++i) out[(size_t)i] = (float)pcm[i] * (1.0f / 32768.0f); }
-            sd_free_pcm(pcm);
-            if (take) return true;
-        }
-    }
-    float* wav = nullptr; int64_t n = 0; int32_t sr = 0, ch = 0, bits = 0;
-    if (sd_read_wav_f32(path, &wav, &n, &sr, &ch, &bits) != SD_OK) { msg = "cannot read PCM wav"; return false; }
-    if (ch > 1 && (flags & SD_WAV_DOWNMIX))
-        for (int64_t i = 0; i < n; ++i) {
-            float s = 0.0f;
-            for (int q = 0; q < ch; ++q) s += wav[i * ch + q];
-            wav[i] = s / (float)ch;
-        }
-    bool ok = true;
-    if (sr == 16000 || (flags & SD_WAV_ASSUME_16K)) out.assign(wav, wav + n);
-    else if (!(flags & SD_WAV_RESAMPLE)) { msg = "sample rate " + std::to_string(sr) + " Hz; the pipeline needs 16000 -- pass --resample (or --assume-16k for the reference's behaviour)"; ok = false; }
-    else {
-        int64_t no = 0;
-        const int64_t cap = sd_resample_len(n, sr, 16000);
-        out.assign((size_t)(cap > 0 ? cap : 1), 0.0f);
-        const int rc = n > 0 ? sd_resample(ctx, wav, n, sr, 16000, out.data(), (int64_t)out.size(), &no) : SD_OK;
-        if (rc != SD_OK) { msg = std::string("resampling failed: ") + sd_last_error(ctx); ok = false; }
-        out.resize((size_t)no);
-    }
-    sd_free_wav(wav);
-    return ok;
+    WavLoad f;
+    wav_load(path, flags, f);
+    if (f.refused()) { msg = f.msg; return false; }
+    if (f.kind == WavLoad::PCM16) { out.resize((size_t)f.n); for (int64_t i = 0; i < f.n; ++i) out[(size_t)i] = (float)f.pcm[i] * (1.0f / 32768.0f); }
+    else if (f.kind == WavLoad::F32) out.assign(f.f32, f.f32 + f.n);
+    else if (resample_16k(ctx, f, out) != SD_OK) { msg = std::string("resampling failed: ") + sd_last_error(ctx); return false; }
+    return true;
 }
 
 static int run_many(const Args& a)
@@ -273,12 +293,9 @@ static int run_many(const Args& a)
     if (!many_read_list(a.many, paths, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
     Gallery g;
     if (a.speakers && !g.read(a.speakers)) return 1;
-    sd_ctx* ctx = sd_create(a.seg, a.emb, 0);
-    if (!ctx) { fprintf(stderr, "sd_create failed: %s\n", sd_create_error()); return 1; }
+    sd_ctx* ctx = open_context(a);
+    if (!ctx) return 1;
     auto leave = [&](int rc) { sd_destroy(ctx); return rc; };
-    if (a.precision && sd_set_option(ctx, "ecapa_precision", a.precision) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
-    if (a.precision == 3 && sd_set_option(ctx, "seg_precision", 3) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
-    if (!apply_clustering(ctx, a)) return leave(1);
     if (a.enrolled && !enrol_gallery(ctx, a, g)) return leave(1);
     const size_t P = paths.size();
     std::vector<std::vector<float>> wav(P);
@@ -307,23 +324,16 @@ static int run_many(const Args& a)
         else if (r != (size_t)-1 && status[r] != SD_OK) msg[i] = "diarization failed (" + std::to_string(status[r]) + ")";
         if (r == (size_t)-1 || status[r] != SD_OK) { printf("== %s: %s\n", paths[i].c_str(), msg[i].c_str()); worst = 1; continue; }
         printf("== %s\n", paths[i].c_str());
-        std::vector<const char*> names, turn_name((size_t)nt[r], nullptr);
-        if (a.speakers && sd_many_select(ctx, (int64_t)r) == SD_OK && (a.enrolled ? enrolled_names(ctx, g, names) : match_clusters(ctx, a, g, names)))
-            for (int64_t t = 0; t < nt[r]; ++t) if (turns[r][t].label >= 0 && (size_t)turns[r][t].label < names.size()) turn_name[(size_t)t] = names[(size_t)turns[r][t].label];
-        if (a.relabel) sd_relabel_turns(turns[r], nt[r]);
-        char line[160];
-        for (int64_t t = 0; t < nt[r]; ++t) {
-            if (turn_name[(size_t)t]) { printf("[%g -- %g] --> %s\n", turns[r][t].start, turns[r][t].end, turn_name[(size_t)t]); continue; }
-            sd_format_turn(&turns[r][t], line, sizeof(line)); printf("%s\n", line);
-        }
+        std::vector<const char*> names, turn_name;
+        const bool named = a.speakers && sd_many_select(ctx, (int64_t)r) == SD_OK && cluster_names(ctx, a, g, names);
+        print_turns(turns[r], nt[r], a, named ? &names : nullptr, turn_name);
         if (a.rttm) {
             std::string stem = paths[i].substr(paths[i].find_last_of('/') == std::string::npos ? 0 : paths[i].find_last_of('/') + 1);
             if (stem.size() > 4 && stem.compare(stem.size() - 4, 4, ".wav") == 0) stem.resize(stem.size() - 4);
             for (const std::string& s : stems) if (s == stem) { stem += "_" + std::to_string(i); break; }      // the same file name twice in the list
             stems.push_back(stem);
             const std::string out = std::string(a.rttm) + "/" + stem + ".rttm";
-            std::vector<const char*> by_label;
-            for (int64_t t = 0; t < nt[r]; ++t) if (turns[r][t].label >= 0) { if ((size_t)turns[r][t].label >= by_label.size()) by_label.resize((size_t)turns[r][t].label + 1, nullptr); by_label[(size_t)turns[r][t].label] = turn_name[(size_t)t]; }
+            const std::vector<const char*> by_label = names_by_label(turns[r], nt[r], turn_name);
             const int rc = a.speakers ? sd_write_rttm_named(out.c_str(), paths[i].c_str(), turns[r], nt[r], nullptr, by_label.data(), (int64_t)by_label.size())
                                       : sd_write_rttm(out.c_str(), paths[i].c_str(), turns[r], nt[r]);
             if (rc != SD_OK) { fprintf(stderr, "cannot write %s\n", out.c_str()); worst = 1; }
@@ -366,15 +376,8 @@ struct StreamRun {
         int64_t n = 0, sealed = 0, total = 0;
         sd_stream_info(st, &n, &sealed, &total);
         printf("== %g s, %lld/%lld chunks\n", (double)n / SD_SAMPLE_RATE, (long long)sealed, (long long)total);
-        std::vector<const char*> names, turn_name((size_t)nt, nullptr);
-        if (gal && enrolled_names(ctx, *gal, names))
-            for (int64_t i = 0; i < nt; ++i) if (turns[i].label >= 0 && (size_t)turns[i].label < names.size()) turn_name[(size_t)i] = names[(size_t)turns[i].label];
-        if (a.relabel) sd_relabel_turns(turns, nt);
-        char line[160];
-        for (int64_t i = 0; i < nt; ++i) {
-            if (turn_name[(size_t)i]) { printf("[%g -- %g] --> %s\n", turns[i].start, turns[i].end, turn_name[(size_t)i]); continue; }
-            sd_format_turn(&turns[i], line, sizeof(line)); printf("%s\n", line);
-        }
+        std::vector<const char*> names, turn_name;
+        print_turns(turns, nt, a, gal && enrolled_names(ctx, *gal, names) ? &names : nullptr, turn_name);
         fflush(stdout);
         return true;
     }
@@ -382,39 +385,18 @@ struct StreamRun {
     bool feed_f32(const float* p, int64_t n) { for (int64_t i = 0; i < n; i += a.stream_piece) if (!part(sd_stream_push_f32(st, p + i, n - i < a.stream_piece ? n - i : a.stream_piece)) || !piece_done()) return false; return true; }
 };
 
-// the samples sd_diarize_wav would diarize (same reader, same --resample / --downmix / --assume-16k rules), pushed in pieces
+// the samples sd_diarize_wav would diarize (wav_load: same readers, same --resample / --downmix / --assume-16k rules), pushed in pieces
 static bool stream_file(StreamRun& r)
 {
-    const Args& a = r.a;
-    {
-        int16_t* pcm = nullptr; int64_t np = 0; int32_t sr16 = 0, ch16 = 0;
-        if (sd_read_wav(a.wav, &pcm, &np, &sr16, &ch16) == SD_OK) {
-            const bool take = (sr16 == 16000 || (a.wav_flags & SD_WAV_ASSUME_16K)) && !(ch16 > 1 && (a.wav_flags & SD_WAV_DOWNMIX));
-            const bool ok = take ? r.feed_pcm(pcm, np) : true;
-            sd_free_pcm(pcm);
-            if (take) return ok;
-        }
-    }
-    float* wav = nullptr; int64_t n = 0; int32_t sr = 0, ch = 0, bits = 0;
-    if (sd_read_wav_f32(a.wav, &wav, &n, &sr, &ch, &bits) != SD_OK) { fprintf(stderr, "cannot read PCM wav: %s\n", a.wav); return false; }
-    if (ch > 1 && (a.wav_flags & SD_WAV_DOWNMIX))
-        for (int64_t i = 0; i < n; ++i) {
-            float s = 0.0f;
-            for (int q = 0; q < ch; ++q) s += wav[i * ch + q];
-            wav[i] = s / (float)ch;
-        }
-    bool ok;
-    if (sr == 16000 || (a.wav_flags & SD_WAV_ASSUME_16K)) ok = r.feed_f32(wav, n);
-    else if (!(a.wav_flags & SD_WAV_RESAMPLE)) { fprintf(stderr, "%s: sample rate %d Hz; the pipeline needs 16000 -- pass --resample (or --assume-16k for the reference's behaviour)\n", a.wav, sr); ok = false; }
-    else {
-        int64_t no = 0;
-        std::vector<float> out((size_t)(sd_resample_len(n, sr, 16000) > 0 ? sd_resample_len(n, sr, 16000) : 1));
-        const int rc = sd_resample(r.ctx, wav, n, sr, 16000, out.data(), (int64_t)out.size(), &no);
-        if (rc != SD_OK) { fprintf(stderr, "resampling failed (%d): %s\n", rc, sd_last_error(r.ctx)); ok = false; }
-        else ok = r.feed_f32(out.data(), no);
-    }
-    sd_free_wav(wav);
-    return ok;
+    WavLoad f;
+    wav_load(r.a.wav, r.a.wav_flags, f);
+    if (f.refused()) { fprintf(stderr, "%s\n", f.refusal(r.a.wav).c_str()); return false; }
+    if (f.kind == WavLoad::PCM16) return r.feed_pcm(f.pcm, f.n);
+    if (f.kind == WavLoad::F32) return r.feed_f32(f.f32, f.n);
+    std::vector<float> out;
+    const int rc = resample_16k(r.ctx, f, out);
+    if (rc != SD_OK) { fprintf(stderr, "resampling failed (%d): %s\n", rc, sd_last_error(r.ctx)); return false; }
+    return r.feed_f32(out.data(), (int64_t)out.size());
 }
 
 // headerless s16le 16 kHz mono samples from stdin, pushed as they arrive: reads of at most 2 MiB, an update block whenever a piece is complete
@@ -444,14 +426,11 @@ static int run_stream(const Args& a)
 {
     Gallery g;
     if (a.speakers && !g.read(a.speakers)) return 1;
-    sd_ctx* ctx = sd_create(a.seg, a.emb, 0);
-    if (!ctx) { fprintf(stderr, "sd_create failed: %s\n", sd_create_error()); return 1; }
+    sd_ctx* ctx = open_context(a);
+    if (!ctx) return 1;
     sd_stream* st = nullptr;
     StreamRun r{ctx, st, a};
     auto leave = [&](int rc) { sd_free_turns(r.turns); sd_stream_close(r.st); sd_destroy(ctx); return rc; };      // every way out gives back what it holds
-    if (a.precision && sd_set_option(ctx, "ecapa_precision", a.precision) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
-    if (a.precision == 3 && sd_set_option(ctx, "seg_precision", 3) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
-    if (!apply_clustering(ctx, a)) return leave(1);
     if (a.enrolled) { if (!enrol_gallery(ctx, a, g)) return leave(1); r.gal = &g; }
     if (sd_stream_open(ctx, &r.st) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
     const bool fed = std::string(a.wav) == "-" ? stream_stdin(r) : stream_file(r);
@@ -460,7 +439,7 @@ static int run_stream(const Args& a)
     sd_stream_info(r.st, &n, nullptr, &total);
     if (total <= 0) { fprintf(stderr, "diarization failed (%d): audio of %lld samples yields no chunk\n", SD_ERR_SHORT, (long long)n); return leave(1); }
     std::vector<const char*> names;
-    if (a.speakers && !(a.enrolled ? enrolled_names(ctx, g, names) : match_clusters(ctx, a, g, names))) return leave(1);
+    if (a.speakers && !cluster_names(ctx, a, g, names)) return leave(1);
     print_block(ctx, r.turns, r.nt, a, r.ms, a.speakers ? &names : nullptr);
     return leave(0);
 }
@@ -488,11 +467,8 @@ static int run_rank(const Args& a, int rank, int world, int id_rd, const std::ve
                         "are single-GPU options)\n", rank, a.wav, sr, a.wav_flags ? ", --resample / --downmix given" : "");
         return 1;
     }
-    sd_ctx* ctx = sd_create(a.seg, a.emb, rank);
-    if (!ctx) { fprintf(stderr, "rank %d: sd_create failed: %s\n", rank, sd_create_error()); return 1; }
-    if (a.precision && sd_set_option(ctx, "ecapa_precision", a.precision) != SD_OK) { fprintf(stderr, "rank %d: %s\n", rank, sd_last_error(ctx)); return 1; }
-    if (a.precision == 3 && sd_set_option(ctx, "seg_precision", 3) != SD_OK) { fprintf(stderr, "rank %d: %s\n", rank, sd_last_error(ctx)); return 1; }
-    if (!apply_clustering(ctx, a)) return 1;
+    sd_ctx* ctx = open_context(a, rank, ("rank " + std::to_string(rank) + ": ").c_str());
+    if (!ctx) return 1;
     unsigned char id[SD_COMM_ID_BYTES];
     if (rank == 0) {
         for (size_t q = 0; q < ready_rd.size(); ++q) {

@@ -1,7 +1,8 @@
-// pipeline.cpp -- stage wrappers and the whole-path driver behind the C ABI.
+// pipeline.cpp -- stage wrappers and the whole-path entries behind the C ABI: a source is brought to a DevWav (bring), then the family's tail runs.
 // speakerDiarization() (sd.cpp:2937-3234) re-stated as: scale pcm -> segmentation -> post-seg ->
 // embeddings -> [multi-GPU: all-gather here] -> count, clustering, reconstruction, annotation.
 #include "common.h"
+#include "wav_file.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -388,11 +389,73 @@ extern "C" int sd_set_planted(sd_ctx* c, const float* d_scores, const float* d_e
     return SD_OK;
 }
 
-// ------------------------------------------------------------------ the whole-path entries: sd_diarize* and sd_activity*
-// Each entry is its own argument checks around the driver of its source form (device pcm, host pcm, host f32, wav file); a driver brings the
-// samples into a padded DevWav and hands it to the family's tail -- diarize_wav_dev, or activity_wav_dev (below) of a kind -- with t0, the
-// entry's own start: the tail sets stage_ms[3] = the time since then
-typedef std::function<int(sd_ctx*, const DevWav&, double, std::vector<sd_turn>&)> WavTail;
+// ------------------------------------------------------------------ the whole-path entries: sd_diarize*, sd_activity* and sd_voiceprint*
+// Each family has one body for its four entries (device pcm, host pcm, host f32, wav file): ENTER, the argument checks, bring() -- the source becomes a
+// padded DevWav and t0, the start of what stage_ms[3] covers -- and the family's tail, called directly: diarize_wav_dev and activity_wav_dev fill a turn
+// vector that turns_out hands over, voiceprint_wav_dev has no turns.  No entry calls another entry.
+struct Source {
+    enum Form { DevPcm, HostPcm, HostF32, WavFile } form;
+    const void* in;                  // d_pcm, h_pcm, h_wav or the path
+    int64_t n; int flags;            // samples of the first three forms; SD_WAV_* of a file
+};
+
+// What bring() leaves: the device samples and t0, and the scratch that must live until the entry returns -- the upload of host pcm (a per-call hipMalloc
+// and a synchronous hipMemcpy inside the call, freed behind the networks: no implicit synchronisation in front of them) and the samples of a wav file
+// (f32_to_wav and the resampler's upload copy from them asynchronously)
+struct Brought { DevWav w; double t0 = 0; DevTmp pcm; WavLoad file; };
+
+// t0 and clear_stage_ms: device pcm and host pcm once the device samples exist (the upload of host pcm is outside stage_ms[3]), host f32 before the upload,
+// a wav file as the form it resolves to -- the resampled one after the file is read, before the upload of the off-rate samples
+static int bring(sd_ctx* c, const Source& s, const char* who, Brought& b)
+{
+    switch (s.form) {
+    case Source::DevPcm:             // n <= 0 is this form's only guard on n: nothing is uploaded from a count that is not one
+        if (s.n <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)s.n);
+        b.t0 = now_ms();
+        clear_stage_ms(c);
+        return pcm_to_wav(c, (const int16_t*)s.in, s.n, &b.w);
+    case Source::HostPcm:
+        if (s.n <= 0) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument", who);
+        if (b.pcm.alloc(s.n * sizeof(int16_t))) SD_FAIL(c, SD_ERR_HIP, "hipMalloc(%zu) failed", (size_t)s.n * sizeof(int16_t));
+        HIPCHK(c, hipMemcpy(b.pcm.p, s.in, s.n * sizeof(int16_t), hipMemcpyHostToDevice));
+        return bring(c, Source{Source::DevPcm, b.pcm.p, s.n, 0}, who, b);
+    case Source::HostF32:            // 8 / 32-bit wavs: samples already divided by 32768 exactly as the reference's loop does for every bit depth (sd.cpp:2948-2951)
+        if (s.n <= 0) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument", who);
+        b.t0 = now_ms();
+        clear_stage_ms(c);
+        return f32_to_wav(c, (const float*)s.in, s.n, &b.w);
+    case Source::WavFile: break;
+    }
+    // a wav file: wav_file.h reads it and applies the rate / channel rule; the resampling is done here, on the device
+    const char* path = (const char*)s.in;
+    WavLoad& f = b.file;
+    wav_load(path, s.flags, f);
+    if (f.refused()) SD_FAIL(c, f.kind == WavLoad::NO_SAMPLES ? SD_ERR_SHORT : SD_ERR_ARG, "%s", f.refusal(path).c_str());
+    if (f.kind == WavLoad::PCM16) return bring(c, Source{Source::HostPcm, f.pcm, f.n, 0}, who, b);
+    if (f.kind == WavLoad::F32) return bring(c, Source{Source::HostF32, f.f32, f.n, 0}, who, b);
+    b.t0 = now_ms();
+    const int64_t no = sd_resample_len(f.n, f.sr, 16000);
+    if (no <= 0) SD_FAIL(c, SD_ERR_SHORT, "%s: %lld samples at %d Hz give no 16 kHz sample", path, (long long)f.n, f.sr);
+    clear_stage_ms(c);
+    WS(c, float, d_in, "rs_in", f.n);
+    WS(c, float, d_wav, "wav_f32", no + SD_WAV_PAD);
+    HIPCHK(c, hipMemcpyAsync(d_in, f.f32, (size_t)f.n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_wav + no, 0, SD_WAV_PAD * sizeof(float), c->stream));
+    b.w = DevWav{d_wav, no, 0, true};
+    return resample_dev(c, d_in, f.n, f.sr, 16000, d_wav, no);
+}
+
+// What every family refuses on the source, its other arguments and the flags of a file alone (SD_ERR_ARG), in the order and the words the forms have:
+// rest_ok = the family's own arguments are fine, hint = its remark on them
+static int check_args(sd_ctx* c, const Source& s, bool rest_ok, const char* who, const char* hint = "")
+{
+    if (s.form == Source::HostPcm && (!s.in || s.n <= 0)) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument", who);
+    if (!s.in || !rest_ok) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument%s", who, hint);
+    if (s.form == Source::WavFile && (s.flags & ~(SD_WAV_RESAMPLE | SD_WAV_DOWNMIX | SD_WAV_ASSUME_16K))) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument", who);
+    return SD_OK;
+}
+// a wav entry that fails behind its argument checks leaves an empty list
+static void no_turns_yet(const Source& s, sd_turn** turns, int64_t* n_turns) { if (s.form == Source::WavFile) { *turns = nullptr; *n_turns = 0; } }
 
 // chunks, both networks, finalize -> turns
 static int diarize_wav_dev(sd_ctx* c, const DevWav& w, double t0, std::vector<sd_turn>& v)
@@ -413,110 +476,33 @@ static int diarize_wav_dev(sd_ctx* c, const DevWav& w, double t0, std::vector<sd
     return SD_OK;
 }
 
-static int run_tail(sd_ctx* c, const DevWav& w, double t0, const WavTail& tail, sd_turn** turns, int64_t* n_turns)
+static int diarize_from(sd_ctx* c, const Source& s, const char* who, sd_turn** turns, int64_t* n_turns)
 {
+    ENTER(c);
+    int rc;
+    if ((rc = check_args(c, s, turns && n_turns, who))) return rc;
+    no_turns_yet(s, turns, n_turns);
+    Brought b;
     std::vector<sd_turn> v;
-    if (int rc = tail(c, w, t0, v)) return rc;
+    if ((rc = bring(c, s, who, b)) || (rc = diarize_wav_dev(c, b.w, b.t0, v))) return rc;
     return turns_out(c, v, turns, n_turns);
-}
-
-// device pcm.  n <= 0 is this form's only guard on n: nothing is uploaded from a count that is not one
-static int whole_dev(sd_ctx* c, const int16_t* d_pcm, int64_t n, const WavTail& tail, sd_turn** turns, int64_t* n_turns)
-{
-    if (n <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)n);
-    const double t0 = now_ms();
-    clear_stage_ms(c);
-    DevWav w;
-    if (int rc = pcm_to_wav(c, d_pcm, n, &w)) return rc;
-    return run_tail(c, w, t0, tail, turns, n_turns);
-}
-
-// host pcm: uploaded, then the family's device-pcm entry with its own checks
-static int whole_pcm(sd_ctx* c, const int16_t* h_pcm, int64_t n, const char* who, const std::function<int(const int16_t*)>& dev_entry)
-{
-    if (!h_pcm || n <= 0) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument", who);
-    DTMP(c, dp, n * sizeof(int16_t));
-    HIPCHK(c, hipMemcpy(dp.p, h_pcm, n * sizeof(int16_t), hipMemcpyHostToDevice));
-    return dev_entry((const int16_t*)dp.p);
-}
-
-// host floats (8 / 32-bit wavs): samples already divided by 32768 exactly as the reference's loop does for every bit depth (sd.cpp:2948-2951)
-static int whole_f32(sd_ctx* c, const float* h_wav, int64_t n, const WavTail& tail, sd_turn** turns, int64_t* n_turns)
-{
-    const double t0 = now_ms();
-    clear_stage_ms(c);
-    DevWav w;
-    if (int rc = f32_to_wav(c, h_wav, n, &w)) return rc;
-    return run_tail(c, w, t0, tail, turns, n_turns);
-}
-
-// wav file: reader + rate / channel handling, then the family's host-pcm entry, its host-f32 entry or -- behind the resampler -- its tail
-typedef std::function<int(const int16_t*, int64_t)> PcmEntry;
-typedef std::function<int(const float*, int64_t)> F32Entry;
-static int whole_wav(sd_ctx* c, const char* path, int flags, const PcmEntry& pcm_entry, const F32Entry& f32_entry, const WavTail& tail, sd_turn** turns, int64_t* n_turns)
-{
-    *turns = nullptr; *n_turns = 0;
-    {   // the common case -- 16-bit, 16 kHz, nothing to mix -- stays int16 up to the GPU (k_pcm_to_f32 does the reference's / 32768 there)
-        int16_t* pcm = nullptr; int64_t np = 0; int32_t sr16 = 0, ch16 = 0;
-        if (sd_read_wav(path, &pcm, &np, &sr16, &ch16) == SD_OK) {
-            struct FreePcm { int16_t* p; ~FreePcm() { sd_free_pcm(p); } } g{pcm};
-            if ((sr16 == 16000 || (flags & SD_WAV_ASSUME_16K)) && !(ch16 > 1 && (flags & SD_WAV_DOWNMIX))) return pcm_entry(pcm, np);
-        }
-    }
-    float* wav = nullptr; int64_t n = 0; int32_t sr = 0, ch = 0, bits = 0;
-    if (sd_read_wav_f32(path, &wav, &n, &sr, &ch, &bits) != SD_OK) SD_FAIL(c, SD_ERR_ARG, "cannot read PCM wav: %s", path);
-    struct Free { float* p; ~Free() { sd_free_wav(p); } } guard{wav};
-    if (ch > 1 && (flags & SD_WAV_DOWNMIX)) {
-        // the buffer holds all n * ch interleaved samples (the reference keeps the first n of them as "mono", wav.h:95-97)
-        for (int64_t i = 0; i < n; ++i) {
-            float s = 0.0f;
-            for (int q = 0; q < ch; ++q) s += wav[i * ch + q];
-            wav[i] = s / (float)ch;
-        }
-    }
-    if (sr == 16000 || (flags & SD_WAV_ASSUME_16K)) return f32_entry(wav, n);      // ASSUME_16K: the reference's behaviour (sd.cpp:2940-2942)
-    if (!(flags & SD_WAV_RESAMPLE))
-        SD_FAIL(c, SD_ERR_ARG, "%s: sample rate %d Hz; the pipeline needs 16000 (README.md:37 of the reference, which would process the file as if it "
-                               "were 16 kHz: SD_WAV_ASSUME_16K / --assume-16k does the same) -- pass SD_WAV_RESAMPLE / --resample", path, sr);
-    if (n <= 0) SD_FAIL(c, SD_ERR_SHORT, "%s holds no samples", path);
-    const double t0 = now_ms();
-    const int64_t no = sd_resample_len(n, sr, 16000);
-    if (no <= 0) SD_FAIL(c, SD_ERR_SHORT, "%s: %lld samples at %d Hz give no 16 kHz sample", path, (long long)n, sr);
-    clear_stage_ms(c);
-    WS(c, float, d_in, "rs_in", n);
-    WS(c, float, d_wav, "wav_f32", no + SD_WAV_PAD);
-    HIPCHK(c, hipMemcpyAsync(d_in, wav, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_wav + no, 0, SD_WAV_PAD * sizeof(float), c->stream));
-    if (int rc = resample_dev(c, d_in, n, sr, 16000, d_wav, no)) return rc;
-    return run_tail(c, DevWav{d_wav, no, 0, true}, t0, tail, turns, n_turns);
 }
 
 extern "C" int sd_diarize_dev(sd_ctx* c, const int16_t* d_pcm, int64_t n, sd_turn** turns, int64_t* n_turns)
 {
-    ENTER(c);
-    if (!d_pcm || !turns || !n_turns) SD_FAIL(c, SD_ERR_ARG, "sd_diarize_dev: bad argument");
-    return whole_dev(c, d_pcm, n, diarize_wav_dev, turns, n_turns);
+    return diarize_from(c, Source{Source::DevPcm, d_pcm, n, 0}, "sd_diarize_dev", turns, n_turns);
 }
-
 extern "C" int sd_diarize(sd_ctx* c, const int16_t* h_pcm, int64_t n, sd_turn** turns, int64_t* n_turns)
 {
-    ENTER(c);
-    return whole_pcm(c, h_pcm, n, "sd_diarize", [&](const int16_t* d_pcm) { return sd_diarize_dev(c, d_pcm, n, turns, n_turns); });
+    return diarize_from(c, Source{Source::HostPcm, h_pcm, n, 0}, "sd_diarize", turns, n_turns);
 }
-
 extern "C" int sd_diarize_f32(sd_ctx* c, const float* h_wav, int64_t n, sd_turn** turns, int64_t* n_turns)
 {
-    ENTER(c);
-    if (!h_wav || n <= 0 || !turns || !n_turns) SD_FAIL(c, SD_ERR_ARG, "sd_diarize_f32: bad argument");
-    return whole_f32(c, h_wav, n, diarize_wav_dev, turns, n_turns);
+    return diarize_from(c, Source{Source::HostF32, h_wav, n, 0}, "sd_diarize_f32", turns, n_turns);
 }
-
 extern "C" int sd_diarize_wav(sd_ctx* c, const char* path, int flags, sd_turn** turns, int64_t* n_turns)
 {
-    ENTER(c);
-    if (!path || !turns || !n_turns || (flags & ~(SD_WAV_RESAMPLE | SD_WAV_DOWNMIX | SD_WAV_ASSUME_16K))) SD_FAIL(c, SD_ERR_ARG, "sd_diarize_wav: bad argument");
-    return whole_wav(c, path, flags, [&](const int16_t* pcm, int64_t n) { return sd_diarize(c, pcm, n, turns, n_turns); },
-                     [&](const float* wav, int64_t n) { return sd_diarize_f32(c, wav, n, turns, n_turns); }, diarize_wav_dev, turns, n_turns);
+    return diarize_from(c, Source{Source::WavFile, path, 0, flags}, "sd_diarize_wav", turns, n_turns);
 }
 
 // ------------------------------------------------------------------ speech / overlapped-speech regions (activity.hip)
@@ -575,46 +561,34 @@ static int activity_wav_dev(sd_ctx* c, const DevWav& w, int kind, double t0, std
     c->stage_ms[3] = now_ms() - t0;
     return SD_OK;
 }
-static WavTail activity_tail(int kind)
-{
-    return [kind](sd_ctx* c, const DevWav& w, double t0, std::vector<sd_turn>& v) { return activity_wav_dev(c, w, kind, t0, v); };
-}
 
-static int check_activity_args(sd_ctx* c, const void* in, int kind, sd_turn** turns, int64_t* n_turns, const char* who)
+static int activity_from(sd_ctx* c, const Source& s, int kind, const char* who, sd_turn** turns, int64_t* n_turns)
 {
-    if (!in || !turns || !n_turns || (kind != SD_ACTIVITY_SPEECH && kind != SD_ACTIVITY_OVERLAP))
-        SD_FAIL(c, SD_ERR_ARG, "%s: bad argument (kind = SD_ACTIVITY_SPEECH or SD_ACTIVITY_OVERLAP)", who);
-    return SD_OK;
+    ENTER(c);
+    int rc;
+    if ((rc = check_args(c, s, turns && n_turns && (kind == SD_ACTIVITY_SPEECH || kind == SD_ACTIVITY_OVERLAP), who, " (kind = SD_ACTIVITY_SPEECH or SD_ACTIVITY_OVERLAP)"))) return rc;
+    no_turns_yet(s, turns, n_turns);
+    Brought b;
+    std::vector<sd_turn> v;
+    if ((rc = bring(c, s, who, b)) || (rc = activity_wav_dev(c, b.w, kind, b.t0, v))) return rc;
+    return turns_out(c, v, turns, n_turns);
 }
 
 extern "C" int sd_activity_dev(sd_ctx* c, const int16_t* d_pcm, int64_t n, int kind, sd_turn** turns, int64_t* n_turns)
 {
-    ENTER(c);
-    if (int rc = check_activity_args(c, d_pcm, kind, turns, n_turns, "sd_activity_dev")) return rc;
-    return whole_dev(c, d_pcm, n, activity_tail(kind), turns, n_turns);
+    return activity_from(c, Source{Source::DevPcm, d_pcm, n, 0}, kind, "sd_activity_dev", turns, n_turns);
 }
-
 extern "C" int sd_activity(sd_ctx* c, const int16_t* h_pcm, int64_t n, int kind, sd_turn** turns, int64_t* n_turns)
 {
-    ENTER(c);
-    return whole_pcm(c, h_pcm, n, "sd_activity", [&](const int16_t* d_pcm) { return sd_activity_dev(c, d_pcm, n, kind, turns, n_turns); });
+    return activity_from(c, Source{Source::HostPcm, h_pcm, n, 0}, kind, "sd_activity", turns, n_turns);
 }
-
 extern "C" int sd_activity_f32(sd_ctx* c, const float* h_wav, int64_t n, int kind, sd_turn** turns, int64_t* n_turns)
 {
-    ENTER(c);
-    if (int rc = check_activity_args(c, h_wav, kind, turns, n_turns, "sd_activity_f32")) return rc;
-    if (n <= 0) SD_FAIL(c, SD_ERR_ARG, "sd_activity_f32: bad argument");
-    return whole_f32(c, h_wav, n, activity_tail(kind), turns, n_turns);
+    return activity_from(c, Source{Source::HostF32, h_wav, n, 0}, kind, "sd_activity_f32", turns, n_turns);
 }
-
 extern "C" int sd_activity_wav(sd_ctx* c, const char* path, int flags, int kind, sd_turn** turns, int64_t* n_turns)
 {
-    ENTER(c);
-    if (int rc = check_activity_args(c, path, kind, turns, n_turns, "sd_activity_wav")) return rc;
-    if (flags & ~(SD_WAV_RESAMPLE | SD_WAV_DOWNMIX | SD_WAV_ASSUME_16K)) SD_FAIL(c, SD_ERR_ARG, "sd_activity_wav: bad argument");
-    return whole_wav(c, path, flags, [&](const int16_t* pcm, int64_t n) { return sd_activity(c, pcm, n, kind, turns, n_turns); },
-                     [&](const float* wav, int64_t n) { return sd_activity_f32(c, wav, n, kind, turns, n_turns); }, activity_tail(kind), turns, n_turns);
+    return activity_from(c, Source{Source::WavFile, path, 0, flags}, kind, "sd_activity_wav", turns, n_turns);
 }
 
 // ------------------------------------------------------------------ voiceprint of a speaker from regions of a recording (speakers.hip)
@@ -663,53 +637,30 @@ static int voiceprint_wav_dev(sd_ctx* c, const DevWav& w, const VoiceprintArgs& 
     memcpy(a.h_emb, mean, sizeof(mean));
     return SD_OK;
 }
-static WavTail voiceprint_tail(const VoiceprintArgs& a)
-{
-    return [a](sd_ctx* c, const DevWav& w, double t0, std::vector<sd_turn>&) { return voiceprint_wav_dev(c, w, a, t0); };
-}
-// the whole_* drivers end in turns_out: a voiceprint has none, the empty list is given back at once
-static int no_turns(int rc, sd_turn* t) { sd_free_turns(t); return rc; }
 
-static int check_voiceprint_args(sd_ctx* c, const void* in, const VoiceprintArgs& a, const char* who)
+static int voiceprint_from(sd_ctx* c, const Source& s, const VoiceprintArgs& a, const char* who)
 {
-    if (!in || !a.h_emb) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument", who);
-    return check_spans(c, a.spans, a.n_spans, who);
+    ENTER(c);
+    int rc;
+    if ((rc = check_args(c, s, a.h_emb != nullptr, who)) || (rc = check_spans(c, a.spans, a.n_spans, who))) return rc;
+    Brought b;
+    if ((rc = bring(c, s, who, b))) return rc;
+    return voiceprint_wav_dev(c, b.w, a, b.t0);
 }
 
 extern "C" int sd_voiceprint_dev(sd_ctx* c, const int16_t* d_pcm, int64_t n, const sd_turn* spans, int64_t n_spans, int32_t label, double* h_emb, int64_t* n_windows)
 {
-    ENTER(c);
-    const VoiceprintArgs a{spans, n_spans, label, h_emb, n_windows};
-    if (int rc = check_voiceprint_args(c, d_pcm, a, "sd_voiceprint_dev")) return rc;
-    sd_turn* t = nullptr; int64_t nt = 0;
-    return no_turns(whole_dev(c, d_pcm, n, voiceprint_tail(a), &t, &nt), t);
+    return voiceprint_from(c, Source{Source::DevPcm, d_pcm, n, 0}, VoiceprintArgs{spans, n_spans, label, h_emb, n_windows}, "sd_voiceprint_dev");
 }
-
 extern "C" int sd_voiceprint(sd_ctx* c, const int16_t* h_pcm, int64_t n, const sd_turn* spans, int64_t n_spans, int32_t label, double* h_emb, int64_t* n_windows)
 {
-    ENTER(c);
-    const VoiceprintArgs a{spans, n_spans, label, h_emb, n_windows};
-    if (int rc = check_voiceprint_args(c, h_pcm, a, "sd_voiceprint")) return rc;
-    return whole_pcm(c, h_pcm, n, "sd_voiceprint", [&](const int16_t* d_pcm) { return sd_voiceprint_dev(c, d_pcm, n, spans, n_spans, label, h_emb, n_windows); });
+    return voiceprint_from(c, Source{Source::HostPcm, h_pcm, n, 0}, VoiceprintArgs{spans, n_spans, label, h_emb, n_windows}, "sd_voiceprint");
 }
-
 extern "C" int sd_voiceprint_f32(sd_ctx* c, const float* h_wav, int64_t n, const sd_turn* spans, int64_t n_spans, int32_t label, double* h_emb, int64_t* n_windows)
 {
-    ENTER(c);
-    const VoiceprintArgs a{spans, n_spans, label, h_emb, n_windows};
-    if (int rc = check_voiceprint_args(c, h_wav, a, "sd_voiceprint_f32")) return rc;
-    if (n <= 0) SD_FAIL(c, SD_ERR_ARG, "sd_voiceprint_f32: bad argument");
-    sd_turn* t = nullptr; int64_t nt = 0;
-    return no_turns(whole_f32(c, h_wav, n, voiceprint_tail(a), &t, &nt), t);
+    return voiceprint_from(c, Source{Source::HostF32, h_wav, n, 0}, VoiceprintArgs{spans, n_spans, label, h_emb, n_windows}, "sd_voiceprint_f32");
 }
-
 extern "C" int sd_voiceprint_wav(sd_ctx* c, const char* path, int flags, const sd_turn* spans, int64_t n_spans, int32_t label, double* h_emb, int64_t* n_windows)
 {
-    ENTER(c);
-    const VoiceprintArgs a{spans, n_spans, label, h_emb, n_windows};
-    if (int rc = check_voiceprint_args(c, path, a, "sd_voiceprint_wav")) return rc;
-    if (flags & ~(SD_WAV_RESAMPLE | SD_WAV_DOWNMIX | SD_WAV_ASSUME_16K)) SD_FAIL(c, SD_ERR_ARG, "sd_voiceprint_wav: bad argument");
-    sd_turn* t = nullptr; int64_t nt = 0;
-    return no_turns(whole_wav(c, path, flags, [&](const int16_t* pcm, int64_t n) { return sd_voiceprint(c, pcm, n, spans, n_spans, label, h_emb, n_windows); },
-                              [&](const float* wav, int64_t n) { return sd_voiceprint_f32(c, wav, n, spans, n_spans, label, h_emb, n_windows); }, voiceprint_tail(a), &t, &nt), t);
+    return voiceprint_from(c, Source{Source::WavFile, path, 0, flags}, VoiceprintArgs{spans, n_spans, label, h_emb, n_windows}, "sd_voiceprint_wav");
 }

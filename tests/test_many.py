@@ -228,3 +228,58 @@ def test_cli_many_prints_what_the_single_file_runs_print(weights, tmp_path):
         assert len(lines) == len(s) and all(l.startswith("SPEAKER " + p + " 1 ") for l in lines)
     out = subprocess.run([exe, weights[0], weights[1], "--many", str(lst), "--stream", "1"], capture_output=True, text=True, timeout=60)
     assert out.returncode == 2 and "--many" in out.stderr
+
+
+def test_cli_many_reads_off_rate_and_stereo_files_as_the_single_file_run_does(weights, tmp_path):
+    """--many under --resample, --downmix and --assume-16k: each file's block holds the turn lines of the single-file run with the flags that affect that
+    file; without a flag the 44.1 kHz file is refused in its block, with the reason, and the others are diarized"""
+    import struct
+    exe = os.path.join(PKG, "speakerDiarizer")
+    rule = "-" * 52
+
+    def wav(path, samples, sr, channels=1):
+        data = np.asarray(samples, np.int16).tobytes()
+        fmt = struct.pack("<HHIIHH", 1, channels, sr, sr * channels * 2, channels * 2, 16)
+        path.write_bytes(b"RIFF" + struct.pack("<I", 36 + len(data)) + b"WAVE" + b"fmt " + struct.pack("<I", 16) + fmt + b"data" + struct.pack("<I", len(data)) + data)
+
+    def single(args):
+        out = subprocess.run([exe, weights[0], weights[1]] + args, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr
+        lines = out.stdout.splitlines()
+        i0 = lines.index(rule)
+        return lines[i0 + 1:lines.index(rule, i0 + 1)]
+
+    def many(flags):
+        out = subprocess.run([exe, weights[0], weights[1], "--many", str(lst)] + flags, capture_output=True, text=True, timeout=300)
+        blocks, cur = {}, None
+        for l in out.stdout.splitlines():
+            if l.startswith("== "):
+                cur = l[3:]
+                blocks[cur] = []
+            else:
+                blocks[cur].append(l)
+        return out, blocks
+
+    pcm = synth.make_pcm(21.0, seed=3)
+    t44 = np.arange(int(len(pcm) * 44100 / 16000)) * (16000.0 / 44100.0)
+    pcm44 = np.rint(np.interp(t44, np.arange(len(pcm)), pcm.astype(np.float64))).astype(np.int16)
+    left = pcm.astype(np.int32)
+    right = np.roll(left, 4000) // 2
+    m44, st = str(tmp_path / "m44.wav"), str(tmp_path / "st.wav")
+    wav(tmp_path / "m44.wav", pcm44, 44100)
+    wav(tmp_path / "st.wav", np.stack([left, right], 1).reshape(-1), 16000, channels=2)
+    lst = tmp_path / "list.txt"
+    lst.write_text(m44 + "\n" + st + "\n")
+    st_plain = single([st])
+    assert len(st_plain) >= 1
+    for flags, want44, want_st in ((["--resample"], single([m44, "--resample"]), st_plain),
+                                   (["--assume-16k", "--downmix"], single([m44, "--assume-16k"]), single([st, "--downmix"]))):
+        assert len(want44) >= 1 and len(want_st) >= 1
+        out, blocks = many(flags)
+        assert out.returncode == 0, out.stderr
+        assert list(blocks) == [m44, st] and blocks[m44] == want44 and blocks[st] == want_st, flags
+    out, blocks = many([])
+    assert out.returncode == 1
+    head = [b for b in blocks if b.startswith(m44 + ": ")]
+    assert list(blocks) == head + [st] and len(head) == 1 and "44100" in head[0] and "--resample" in head[0]
+    assert blocks[head[0]] == [] and blocks[st] == st_plain
