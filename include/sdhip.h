@@ -394,6 +394,70 @@ int sd_diarize_many_dev(sd_ctx*, const int16_t* const* d_pcm /*[R]*/, const int6
 int sd_diarize_many_f32(sd_ctx*, const float* const* h_wav /*[R]*/, const int64_t* n /*[R]*/, int64_t R, sd_turn** turns /*[R]*/, int64_t* n_turns /*[R]*/, int32_t* status /*[R]*/);     /* sd.cpp:2937-3234, 2948-2951 */
 int sd_many_select(sd_ctx*, int64_t r);     /* sd.cpp:2149-2167, 2191-2207 */
 
+/* ---- scoring against a ground truth (host-only, no context, no GPU).  The reference has no counterpart: it prints turns and measures nothing.
+ * sd_der is the diarization error rate of pyannote.metrics' DiarizationErrorRate, restated:
+ *  - the time line is cut at every start and end of a turn of ref and of hyp (and of a uem span and a collar zone, below).  In an elementary interval of
+ *    length D, A = the distinct labels of the reference turns that cover it, B = those of the hypothesis turns;
+ *      total += |A| D,  missed += max(0, |A| - |B|) D,  false_alarm += max(0, |B| - |A|) D,
+ *      correct += |{a in A : map(a) in B}| D,  confusion += (min(|A|, |B|) - that count) D;
+ *    der = (missed + false_alarm + confusion) / total, NaN when total == 0.
+ *  - map is the one-to-one pairing of reference and hypothesis labels that maximises the summed co-occurrence duration (sum of D over the scored
+ *    intervals with a in A and b in B), found by a rectangular assignment solver for any number of labels.  Every optimal pairing gives the same
+ *    correct, so the components are defined where the pairing is not unique; a pair that never co-occurs is no pair.
+ *  - uem (may be NULL): only time inside these spans is scored; their labels are not read.
+ *  - collar (seconds, >= 0): around every start and end t of a reference turn the zone from the f64 value t - collar / 2 to the f64 value
+ *    t + collar / 2 is not scored (pyannote's convention: half on each side).
+ *  - skip_overlap != 0: intervals with |A| >= 2 are not scored.
+ * Arithmetic is f64: intervals in ascending time, each length one subtraction of two boundaries, each component a sum that carries its rounding
+ * errors (the result is the exact sum of those lengths rounded once).  Labels are any integers >= 0.  map[h] (h < cap; map may be NULL with
+ * cap = 0) = the reference label paired with hypothesis label h, or -1; *n_map = the largest hypothesis label + 1.
+ * SD_ERR_ARG: a negative or NaN time, end < start, a negative label, a negative or NaN collar.
+ * sd_read_rttm: the SPEAKER lines of an RTTM file as sd_write_rttm* and pyannote write them: fields separated by white space, field 2 the uri
+ * (uri != NULL keeps the lines of that uri only), 4 the start, 5 the duration (end = start + duration), 8 the speaker name.  Labels number the
+ * names in order of first appearance; names [K] (may be NULL) returns them.  Lines of other record types and ;; comments are passed over; a
+ * SPEAKER line with fewer than 8 fields or a start or duration that is not a number >= 0 returns SD_ERR_ARG.  Free the turns with sd_free_turns,
+ * the names with sd_free_rttm_names.  sd_score_error = the reason for the last non-OK return of sd_der / sd_read_rttm, with the line number. */
+typedef struct sd_der_result { double der, total, missed, false_alarm, confusion, correct; } sd_der_result;
+int sd_der(const sd_turn* ref, int64_t n_ref, const sd_turn* hyp, int64_t n_hyp, const sd_turn* uem /* or NULL */, int64_t n_uem, double collar,
+           int skip_overlap, sd_der_result* result, int32_t* map /*[cap] or NULL*/, int64_t cap, int64_t* n_map /* or NULL */);
+int sd_read_rttm(const char* path, const char* uri /* or NULL */, sd_turn** turns, int64_t* n, char*** names /* or NULL */, int64_t* K /* or NULL */);
+void sd_free_rttm_names(char** names, int64_t K);
+const char* sd_score_error(void);
+
+/* ---- many cuts of one dendrogram: for a caller who tries several clustering thresholds on one recording.  The linkage is most of a finalize and
+ * depends on none of "clustering_threshold", "min_cluster_size" and "num_clusters"; a cut object runs it once.
+ * sd_cut_open_dev (d_seg, d_emb as for sd_finalize_dev) and the whole-path forms sd_cut_open / _pcm_dev / _f32 / _wav (samples as for sd_diarize /
+ * _dev / _f32 / _wav: same flags, same refusals; both networks run inside) do everything of a finalize that does not depend on the cut: binarisation,
+ * speaker count, the f64 embeddings, the train rows (sd.cpp:2224), their gathered and normalised copies, and ONE linkage with the context's
+ * "clustering_method" at that moment.  The cut owns copies of all of it, on the device and -- the dendrogram -- on the host: other calls on the
+ * context may come between two calls on a cut.
+ * sd_cut_turns_many evaluates T cuts: turns[t] / n_turns[t] (free each with sd_free_turns) and K[t] (may be NULL; the number of label columns, largest
+ * label + 1) are what sd_finalize_dev returns on the same inputs with the three options of specs[t] set -- turns, order and labels, bit for bit.
+ * In a spec a NaN threshold, min_cluster_size 0 and num_clusters 0 mean the context's current option; num_clusters -1 means unset.  "min_clusters",
+ * "max_clusters" and "constrained_assignment" are read from the context at the call.  The context's options are never changed.  After the call
+ * sd_last_confidence and sd_last_speakers describe cut T - 1 as after that sd_finalize_dev.  sd_cut_turns is the T = 1 case of the same code.
+ * All cuts of a group share their device launches: one assignment of every embedding to the centroids of all cuts, one pass over the frames for
+ * the activations of all cuts, one selection of the most active clusters, one copy back.  A group is the longest run of consecutive specs whose
+ * activation tables fit a byte budget (1 GiB; test key "cut_group_bytes"); results do not depend on the grouping.  Under "constrained_assignment"
+ * the assignment runs cut by cut.
+ * sd_cut_dendrogram: the linkage matrix Z [N - 1][4] of the N train rows (*N; at most cap rows are written, Z may be NULL); its heights are the
+ * only thresholds at which a cut can change.  N < 2: no row.
+ * SD_ERR_ARG before anything is touched, at open and at every evaluation: an enrolled gallery (its flow clusters other rows), a dump directory
+ * (the step files describe one finalize); at an evaluation also a threshold outside [0, 2], min_cluster_size < 0, num_clusters < -1.
+ * sd_destroy closes the cuts still open.  Not for streams, sd_diarize_many or the sharded path; another linkage method needs another cut. */
+typedef struct sd_cut sd_cut;
+typedef struct sd_cut_spec { double threshold; int32_t min_cluster_size; int32_t num_clusters; } sd_cut_spec;
+int sd_cut_open_dev(sd_ctx*, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, sd_cut** cut);
+int sd_cut_open(sd_ctx*, const int16_t* h_pcm, int64_t n, sd_cut** cut);
+int sd_cut_open_pcm_dev(sd_ctx*, const int16_t* d_pcm, int64_t n, sd_cut** cut);
+int sd_cut_open_f32(sd_ctx*, const float* h_wav, int64_t n, sd_cut** cut);
+int sd_cut_open_wav(sd_ctx*, const char* path, int flags, sd_cut** cut);
+int sd_cut_turns(sd_cut*, const sd_cut_spec* spec, sd_turn** turns, int64_t* n_turns, int32_t* K /* or NULL */);
+int sd_cut_turns_many(sd_cut*, const sd_cut_spec* specs /*[T]*/, int64_t T, sd_turn** turns /*[T]*/, int64_t* n_turns /*[T]*/, int32_t* K /*[T] or NULL*/);
+int sd_cut_dendrogram(const sd_cut*, double* h_Z /*[cap][4] or NULL*/, int64_t cap, int64_t* N);
+int sd_cut_info(const sd_cut*, int64_t* chunks, int64_t* n_samples, int64_t* train_rows);      /* any pointer may be NULL */
+void sd_cut_close(sd_cut*);
+
 /* ---- a18: the reference's output line (sd.cpp:3439) */
 int sd_format_turn(const sd_turn* t, char* buf, int cap);
 

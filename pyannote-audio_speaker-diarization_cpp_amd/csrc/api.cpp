@@ -59,6 +59,7 @@ extern "C" void sd_destroy(sd_ctx* c)
     sd_flush_profile(c);
     (void)sd_comm_destroy(c);
     while (!c->streams.empty()) sd_stream_close(c->streams.back());      // streams still open own device memory of their own
+    while (!c->cuts.empty()) sd_cut_close(c->cuts.back());               // ... and so do cuts
     for (void* p : c->owned) (void)hipFree(p);
     for (auto& kv : c->ws) kv.second.release();
     c->enr_gal.release(); c->enr_m2.release();
@@ -154,6 +155,7 @@ extern "C" int sd_set_option(sd_ctx* c, const char* key, int64_t v)
     else if (k == "min_clusters") c->min_clusters = (int)v;
     else if (k == "max_clusters") c->max_clusters = (int)v;
     else if (k == "activity_hamming") { if (v != 0 && v != 1) SD_FAIL(c, SD_ERR_ARG, "activity_hamming must be 0 or 1"); c->activity_hamming = v != 0; }
+    else if (k == "cut_group_bytes") { if (v < 1) SD_FAIL(c, SD_ERR_ARG, "cut_group_bytes must be at least 1"); c->cut_group_bytes = v; }      // test key (sdhip_test.h)
     else if (k == "profile") { c->profile = v != 0; c->profile_detail = v >= 2; }
     else SD_FAIL(c, SD_ERR_ARG, "unknown option %s", key);
     return SD_OK;

@@ -227,7 +227,7 @@ static double cos_dist_host(const double* a, const double* b, int d, bool* err) 
 }
 
 // group rows by label (ascending row order inside each group); a row with a negative label belongs to no group
-static void group_by_label(const std::vector<int>& lab, int nl, std::vector<int>& order, std::vector<int>& off)
+void group_by_label(const std::vector<int>& lab, int nl, std::vector<int>& order, std::vector<int>& off)
 {
     off.assign((size_t)nl + 1, 0);
     for (int v : lab) if (v >= 0) off[(size_t)v + 1]++;
@@ -240,7 +240,7 @@ static void group_by_label(const std::vector<int>& lab, int nl, std::vector<int>
 // Constrained number of clusters -- the branch the reference leaves unimplemented (assert(false), sd.cpp:2368-2369);
 // specification = the Python it was ported from, clustering/Clustering.py:352-399: re-cut the dendrogram by merge
 // index, walking away from the tuned threshold, until the number of large clusters is (closest to) num_clusters.
-static void constrained_recut(const std::vector<double>& Z, int64_t N, double threshold, size_t mcs, int num_clusters, std::vector<int>& lab)
+void constrained_recut(const std::vector<double>& Z, int64_t N, double threshold, size_t mcs, int num_clusters, std::vector<int>& lab)
 {
     std::vector<double> Zi(Z);
     for (int64_t k = 0; k < N - 1; ++k) Zi[(size_t)k * 4 + 2] = (double)k;          // Clustering.py:353-354
@@ -275,8 +275,8 @@ static void constrained_recut(const std::vector<double>& Z, int64_t N, double th
 // Method, threshold and minimum cluster size are the three hyper-parameters of Clustering.py:251-276; their defaults are the constants the
 // reference hard-codes (sd.cpp:2049-2056: centroid, the float-typed threshold promoted to double, 15).  Clustering.py:317-333: centroid, median and ward
 // are euclidean-only and run on the unit-normalised rows (Xn, with the port's f32 norm); the other four run on the rows as they are with the cosine metric.
-static int cluster_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, int d, double** Xout, double** Xnout, std::vector<int>& lab, int* nlout,
-                        std::vector<double>* Zh)
+int cluster_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, int d, double** Xout, double** Xnout, std::vector<int>& lab, int* nlout,
+                 std::vector<double>* Zh)
 {
     const int64_t N = (int64_t)idx.size();
     WS(c, int, d_tidx, "cl_tidx", N);
@@ -296,7 +296,7 @@ static int cluster_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& 
 }
 
 // a11: which clusters reach mcs rows (clusters without a row are neither)
-static void split_by_size(const std::vector<int>& off, int nl, size_t mcs, std::vector<int>& large, std::vector<int>& small)
+void split_by_size(const std::vector<int>& off, int nl, size_t mcs, std::vector<int>& large, std::vector<int>& small)
 {
     large.clear(); small.clear();
     for (int k = 0; k < nl; ++k) {
@@ -310,7 +310,7 @@ static void split_by_size(const std::vector<int>& off, int nl, size_t mcs, std::
 // ascending id -- by the cosine distance of the means of the UN-normalised rows (sd.cpp:2386), the reference's float minVal loop (sd.cpp:2396).  The rows of a
 // cluster that goes to an enrolled candidate get label -1; the labels that survive are renumbered 0 .. nl - 1 in sorted-id order (findUniqueClusters,
 // sd.cpp:519-548).
-static int reassign_small(sd_ctx* c, const double* X, int d, const std::vector<int>& order, const std::vector<int>& off, const std::vector<int>& large,
+int reassign_small(sd_ctx* c, const double* X, int d, const std::vector<int>& order, const std::vector<int>& off, const std::vector<int>& large,
                           const std::vector<int>& small, const double* enrolled, int G, std::vector<int>& lab, int& nl)
 {
     const size_t N = order.size();
@@ -350,7 +350,7 @@ static int reassign_small(sd_ctx* c, const double* X, int d, const std::vector<i
 
 // a14, first half: the means of the nl final clusters (un-normalised rows of X, members in ascending row order) into rows [G, G + nl) of the centroid table
 // "cl_cen"; rows [0, G) are left to the caller (the enrolled flow's voiceprints).  order / off describe the membership afterwards.
-static int final_means(sd_ctx* c, const double* X, int d, const std::vector<int>& lab, int nl, int G, std::vector<int>& order, std::vector<int>& off, double** cen_out)
+int final_means(sd_ctx* c, const double* X, int d, const std::vector<int>& lab, int nl, int G, std::vector<int>& order, std::vector<int>& off, double** cen_out)
 {
     group_by_label(lab, nl, order, off);
     WS(c, int, d_order2, "cl_order", std::max<size_t>(order.size(), 1));      // (no new cluster at all: the enrolled flow with every row claimed)
@@ -368,7 +368,7 @@ static int final_means(sd_ctx* c, const double* X, int d, const std::vector<int>
 
 // a14, second half: cosine cdist of ALL M rows to the K centroids, arg-max (or the constrained arg-max); the centroids and their counts become what
 // sd_last_speakers describes.  *soft_out (may be NULL) = the [M][K] score table where one was written, else null.
-static int assign_all(sd_ctx* c, const double* d_emb, int64_t M, int d, const double* d_cen2, int K, const std::vector<int64_t>& counts,
+int assign_all(sd_ctx* c, const double* d_emb, int64_t M, int d, const double* d_cen2, int K, const std::vector<int64_t>& counts,
                       std::vector<int>& hard, int* Kout, std::vector<double>* soft_best, double** soft_out)
 {
     const bool dumping = !c->dump_dir.empty();

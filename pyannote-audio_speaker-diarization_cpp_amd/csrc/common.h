@@ -254,6 +254,8 @@ struct sd_ctx {
     int64_t planted_lo = 0, planted_n = 0;
     std::vector<ManyJob> many_jobs;             // per recording of the last sd_diarize_many* call (sd_many_select)
     std::vector<sd_stream*> streams;            // open sd_stream objects of this context (stream.hip); sd_destroy closes what is left
+    std::vector<sd_cut*> cuts;                  // open sd_cut objects of this context (cut.hip); sd_destroy closes what is left
+    int64_t cut_group_bytes = (int64_t)1 << 30; // sd_cut_turns_many: bytes the activation tables of one group of cuts may take (test key)
 };
 
 #define SD_FAIL(ctx, code, ...) do { char _b[512]; snprintf(_b, sizeof(_b), __VA_ARGS__); (ctx)->err = _b; return (code); } while (0)
@@ -417,7 +419,13 @@ inline void clear_stage_ms(sd_ctx* c) { for (double& ms : c->stage_ms) ms = 0; }
 // both networks on chunks [lo, hi) -> d_seg [hi-lo][293][3], d_emb [(hi-lo)*3][192]; seg_done: d_seg already holds the scores (stream.hip)
 int shard_infer(sd_ctx* c, const DevWav& w, int64_t lo, int64_t hi, float* d_seg, float* d_emb, bool seg_done = false);
 int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, std::vector<sd_turn>& v);
+__global__ void k_f32_to_f64(const float* __restrict__ a, double* __restrict__ b, int64_t n);      // embeddings widened before clustering (sd.cpp:2555); grid GRID1(n)
+// the per-turn confidence of finalize (sdhip.h: sd_last_confidence) from the [chunks * 3] assignment behind the inactive rule and the best scores
+void turn_confidence(const std::vector<sd_turn>& v, const std::vector<int>& hard, const std::vector<double>& soft_best, int64_t chunks, std::vector<double>& conf);
 int turns_out(sd_ctx* c, const std::vector<sd_turn>& v, sd_turn** turns, int64_t* n_turns);
+// ---- cut.hip: the tail of the sd_cut_open* entries (sdhip.h, "many cuts of one dendrogram"); refuses a gallery and a dump directory itself
+int cut_refusal(sd_ctx* c, const char* who);
+int cut_open_dev(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, sd_cut** out);
 // ---- resample.hip
 int resample_dev(sd_ctx* c, const float* d_in, int64_t n, int32_t in_sr, int32_t out_sr, float* d_out, int64_t n_out);
 // ---- postseg.hip
@@ -449,8 +457,24 @@ int run_speaker_dist(sd_ctx* c, const double* d_cen, int64_t K, const double* d_
 int run_gallery_norms(sd_ctx* c, const double* d_gal, int64_t M, int d, double* d_m2 /*[M]*/);      // asynchronous
 int run_nearest_gallery(sd_ctx* c, const double* d_E, const int* d_tidx /*[N] or null*/, int64_t N, const double* d_gal, const double* d_m2, int64_t M, int d,
                         int* d_best /*[N]*/, double* d_dist /*[N]*/);      // synchronises
+// ---- cluster.hip: the steps of run_clustering, for cut.hip, which walks the same flow once per cut of one dendrogram
+__global__ void k_cluster_means(const double* __restrict__ X, int d, const int* __restrict__ order, const int* __restrict__ off, double* __restrict__ cen);
+int cluster_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, int d, double** Xout, double** Xnout, std::vector<int>& lab, int* nlout, std::vector<double>* Zh);
+void group_by_label(const std::vector<int>& lab, int nl, std::vector<int>& order, std::vector<int>& off);
+void constrained_recut(const std::vector<double>& Z, int64_t N, double threshold, size_t mcs, int num_clusters, std::vector<int>& lab);
+void split_by_size(const std::vector<int>& off, int nl, size_t mcs, std::vector<int>& large, std::vector<int>& small);
+int reassign_small(sd_ctx* c, const double* X, int d, const std::vector<int>& order, const std::vector<int>& off, const std::vector<int>& large,
+                   const std::vector<int>& small, const double* enrolled, int G, std::vector<int>& lab, int& nl);
+int final_means(sd_ctx* c, const double* X, int d, const std::vector<int>& lab, int nl, int G, std::vector<int>& order, std::vector<int>& off, double** cen_out);
+int assign_all(sd_ctx* c, const double* d_emb, int64_t M, int d, const double* d_cen2, int K, const std::vector<int64_t>& counts,
+               std::vector<int>& hard, int* Kout, std::vector<double>* soft_best, double** soft_out);
 // ---- cluster.hip: the three refusals of a call that clusters under an enrolled gallery (SD_ERR_ARG; nothing is touched); SD_OK without a gallery
 int enrolled_refusal(sd_ctx* c, int d, int num_clusters, int min_clusters, int max_clusters);
 // ---- reconstruct.hip
+// what run_reconstruct derives from the sizes of a job alone: the activation frames, the first frame of every chunk, the crop of activations and
+// counts to their common extent (sd.cpp:2691-2706) and the start of the cropped window
+struct ReconFrames { int64_t nact = 0, ar0 = 0, cr0 = 0, rows = 0, crow_all = 0; float astart = 0; std::vector<int> sfr; };
+void reconstruct_frames(int64_t chunks, int64_t n_count, int64_t n_samples, ReconFrames& g);
+void to_annotation_host(const std::vector<uint8_t>& binary, int64_t rows, int K, double w_start, std::vector<sd_turn>& out);
 int run_reconstruct(sd_ctx* c, const float* d_seg, const int* d_nact, const int* d_hard, const int32_t* d_count,
                     int64_t n_count, int64_t chunks, int64_t n_samples, int K, std::vector<sd_turn>& turns);

@@ -52,6 +52,16 @@
 //                   list order; a file that cannot be read, is refused or is too short gets "== <path>: <message>" and the exit status is 1.
 //                   --rttm DIR writes DIR/<file name without .wav>.rttm per recording; --speakers (with or without --enrolled) and --relabel work per
 //                   recording.  Refused with --gpus N > 1, --stream, --activity, --dump-steps and --enroll
+//   --score REF.rttm [--collar X] [--skip-overlap] [--uem-from-ref]   after the diarization, one more line on stderr: the diarization error rate of the turns
+//                   against the SPEAKER lines of REF.rttm (sd_read_rttm, sd_der: the rule of pyannote.metrics' DiarizationErrorRate),
+//                   "DER d (missed m, false alarm f, confusion c, total t s)".  X = the collar in seconds (half on each side of every reference boundary),
+//                   --skip-overlap leaves reference overlap unscored, --uem-from-ref scores the time from the first reference start to the last reference end only
+//   --tune REF.rttm --thresholds LO:HI:N [--min-cluster-sizes a,b,...]   no single diarization: one cut object (sd_cut_open_wav: both networks and the linkage
+//                   once) and the grid of N thresholds from LO to HI (N = 1: LO) times the sizes, thresholds outermost, in one sd_cut_turns_many; one line
+//                   "threshold T min_cluster_size M speakers K DER d (...)" per point and "best threshold T min_cluster_size M DER d", the first minimum in
+//                   grid order.  The scoring flags of --score apply.  A bad grid or an unreadable REF.rttm is a usage error (exit 2) before anything touches
+//                   the GPU.  Both are single-GPU, whole-file options: refused with --gpus N > 1, --stream, --activity, --many, --enroll and each other;
+//                   --tune also with --enrolled and --dump-steps
 //   --relabel       stdout / RTTM labels renumbered the way pyannote.audio names its output (the clusters that occur,
 //                   sorted by their string, become 0, 1, ... = SPEAKER_00, SPEAKER_01, ...); default = raw cluster ids (sd.cpp:3439)
 #include <cerrno>
@@ -74,7 +84,26 @@ struct Args { const char* seg = nullptr; const char* emb = nullptr; const char* 
               int activity = -1; double act[4] = {-1.0, -1.0, -1.0, -1.0}; bool act_hamming = false;      // --activity: SD_ACTIVITY_*; onset, offset, min on, min off (-1: default)
               long long stream_piece = 0; bool stream_updates = false;         // --stream: samples per piece (0: off)
               const char* speakers = nullptr; double speakers_threshold = -1.0; const char* enroll = nullptr; std::vector<sd_turn> enroll_spans; bool enrolled = false;
-              const char* many = nullptr; };      // --speakers FILE, its threshold (-1: default), --enroll NAME and its spans
+              const char* many = nullptr;         // --speakers FILE, its threshold (-1: default), --enroll NAME and its spans
+              const char* score = nullptr; const char* tune = nullptr; double collar = 0.0; bool skip_overlap = false, uem_from_ref = false;      // --score / --tune REF.rttm and how to score
+              std::vector<double> thresholds; std::vector<long long> min_sizes;      // --tune: the grid
+              std::vector<sd_turn> ref; };        // the turns of REF.rttm, read before anything touches the GPU
+
+// --score / --tune: the error rate of `turns` against a.ref by the command line's scoring flags, as the text behind "DER "; false (message printed) on a failure
+static bool score_turns(const Args& a, const sd_turn* turns, int64_t nt, sd_der_result& r, char* text, size_t cap)
+{
+    sd_turn uem{0.0, 0.0, 0, 0};
+    if (a.uem_from_ref && !a.ref.empty()) {
+        uem.start = a.ref[0].start; uem.end = a.ref[0].end;
+        for (const sd_turn& t : a.ref) { if (t.start < uem.start) uem.start = t.start; if (t.end > uem.end) uem.end = t.end; }
+    }
+    if (sd_der(a.ref.data(), (int64_t)a.ref.size(), turns, nt, a.uem_from_ref ? &uem : nullptr, a.uem_from_ref ? 1 : 0, a.collar, a.skip_overlap ? 1 : 0, &r, nullptr, 0, nullptr) != SD_OK) {
+        fprintf(stderr, "scoring failed: %s\n", sd_score_error());
+        return false;
+    }
+    snprintf(text, cap, "%.17g (missed %.17g, false alarm %.17g, confusion %.17g, total %.17g s)", r.der, r.missed, r.false_alarm, r.confusion, r.total);
+    return true;
+}
 
 // the clustering hyper-parameters the command line set; false (message printed) on a refusal
 static bool apply_clustering(sd_ctx* ctx, const Args& a)
@@ -255,12 +284,43 @@ static int run_single(const Args& a)
                                    : sd_diarize_wav(ctx, a.wav, a.wav_flags, &turns, &nt);      // 8 / 16 / 32-bit PCM like wav.h:99-122; rate and channels checked
     if (rc != SD_OK) { fprintf(stderr, "%s failed (%d): %s\n", a.activity >= 0 ? "activity detection" : "diarization", rc, sd_last_error(ctx)); return leave(1); }
     TRACE("sd_diarize_wav done");
+    char der_text[256]; sd_der_result der;
+    if (a.score && !score_turns(a, turns, nt, der, der_text, sizeof(der_text))) return leave(1);      // on the raw labels, before --relabel
     std::vector<const char*> names;
     if (a.speakers && !cluster_names(ctx, a, g, names)) return leave(1);
     print_block(ctx, turns, nt, a, nullptr, a.speakers ? &names : nullptr);
+    if (a.score) fprintf(stderr, "DER %s\n", der_text);
     const int done = leave(0);
     TRACE("sd_destroy done");
     return done;
+}
+
+// --tune: one cut object, the grid in one sd_cut_turns_many, every point scored against a.ref
+static int run_tune(const Args& a)
+{
+    sd_ctx* ctx = open_context(a);
+    if (!ctx) return 1;
+    sd_cut* cut = nullptr;
+    std::vector<sd_cut_spec> specs;
+    for (double t : a.thresholds) for (long long m : a.min_sizes) specs.push_back(sd_cut_spec{t, (int32_t)m, 0});
+    const int64_t T = (int64_t)specs.size();
+    std::vector<sd_turn*> turns((size_t)T, nullptr);
+    std::vector<int64_t> nt((size_t)T, 0);
+    std::vector<int32_t> K((size_t)T, 0);
+    auto leave = [&](int rc) { for (sd_turn* t : turns) sd_free_turns(t); sd_cut_close(cut); sd_destroy(ctx); return rc; };
+    int rc = sd_cut_open_wav(ctx, a.wav, a.wav_flags, &cut);
+    if (rc == SD_OK) rc = sd_cut_turns_many(cut, specs.data(), T, turns.data(), nt.data(), K.data());
+    if (rc != SD_OK) { fprintf(stderr, "tuning failed (%d): %s\n", rc, sd_last_error(ctx)); return leave(1); }
+    int64_t best = -1; double best_der = NAN;
+    char text[256];
+    for (int64_t i = 0; i < T; ++i) {
+        sd_der_result r;
+        if (!score_turns(a, turns[(size_t)i], nt[(size_t)i], r, text, sizeof(text))) return leave(1);
+        printf("threshold %.17g min_cluster_size %d speakers %d DER %s\n", specs[(size_t)i].threshold, specs[(size_t)i].min_cluster_size ? specs[(size_t)i].min_cluster_size : 15, K[(size_t)i], text);
+        if (best < 0 || (r.der == r.der && !(best_der <= r.der))) { best = i; best_der = r.der; }      // the first minimum in grid order
+    }
+    printf("best threshold %.17g min_cluster_size %d DER %.17g\n", specs[(size_t)best].threshold, specs[(size_t)best].min_cluster_size ? specs[(size_t)best].min_cluster_size : 15, best_der);
+    return leave(0);
 }
 
 // ---- the off-rate samples of a file (WavLoad::F32_OFF_RATE) at 16 kHz: sd_resample, the kernel the wav entries of the library resample with
@@ -540,6 +600,41 @@ int main(int argc, char* argv[])
             if (i + 1 >= argc || !argv[i + 1][0]) { fprintf(stderr, "usage: --many needs a list file\n"); return 2; }
             a.many = argv[++i];
         }
+        else if (s == "--skip-overlap") a.skip_overlap = true;
+        else if (s == "--uem-from-ref") a.uem_from_ref = true;
+        else if (s == "--score" || s == "--tune" || s == "--collar" || s == "--thresholds" || s == "--min-cluster-sizes") {
+            // checked here: a bad grid is a usage error before any context is created
+            if (i + 1 >= argc || !argv[i + 1][0]) { fprintf(stderr, "usage: %s needs a value\n", s.c_str()); return 2; }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            if (s == "--score") a.score = v;
+            else if (s == "--tune") a.tune = v;
+            else if (s == "--collar") {
+                a.collar = strtod(v, &end);
+                if (end == v || *end || !(a.collar >= 0.0) || a.collar > 1e300) { fprintf(stderr, "usage: --collar takes a number of seconds >= 0 (got '%s')\n", v); return 2; }
+            } else if (s == "--thresholds") {
+                const double lo = strtod(v, &end);
+                bool ok = end != v && *end == ':';
+                const char* p2 = ok ? end + 1 : v;
+                const double hi = ok ? strtod(p2, &end) : 0.0;
+                ok = ok && end != p2 && *end == ':';
+                const char* p3 = ok ? end + 1 : v;
+                const long long cnt = ok ? strtoll(p3, &end, 10) : 0;
+                ok = ok && end != p3 && !*end && lo >= 0.0 && hi >= lo && hi <= 2.0 && cnt >= 1 && cnt <= 100000;
+                if (!ok) { fprintf(stderr, "usage: --thresholds takes LO:HI:N with 0 <= LO <= HI <= 2 and 1 <= N <= 100000 (got '%s')\n", v); return 2; }
+                a.thresholds.clear();
+                for (long long q = 0; q < cnt; ++q) a.thresholds.push_back(cnt == 1 ? lo : lo + (hi - lo) * (double)q / (double)(cnt - 1));
+            } else {
+                a.min_sizes.clear();
+                for (const char* q = v;;) {
+                    const long long m = strtoll(q, &end, 10);
+                    if (end == q || (*end && *end != ',') || m < 1 || m > 0x7fffffff) { fprintf(stderr, "usage: --min-cluster-sizes takes integers >= 1 separated by commas (got '%s')\n", v); return 2; }
+                    a.min_sizes.push_back(m);
+                    if (!*end) break;
+                    q = end + 1;
+                }
+            }
+        }
         else if (s == "--stream-updates") a.stream_updates = true;
         else if (s == "--enrolled") a.enrolled = true;
         else if (s == "--stream") {
@@ -611,6 +706,19 @@ int main(int argc, char* argv[])
     if (a.enroll && (a.stream_piece > 0 || a.dump_dir)) { fprintf(stderr, "usage: --enroll runs no diarization; --stream and --dump-steps are refused with it\n"); return 2; }
     if (a.many && (a.gpus > 1 || a.stream_piece > 0 || a.activity >= 0 || a.dump_dir || a.enroll)) { fprintf(stderr, "usage: --many diarizes a list of recordings on one GPU; --gpus N, --stream, --activity, --dump-steps and --enroll are refused with it\n"); return 2; }
     if (a.many && pos.size() != 2) { fprintf(stderr, "usage: --many LIST takes the place of the wav argument\n"); return 2; }
+    if (a.score && a.tune) { fprintf(stderr, "usage: --score scores one diarization, --tune a grid of them; give one of the two\n"); return 2; }
+    if ((a.score || a.tune) && (a.gpus > 1 || a.stream_piece > 0 || a.activity >= 0 || a.many || a.enroll)) { fprintf(stderr, "usage: %s scores the speaker turns of one file on one GPU; --gpus N, --stream, --activity, --many and --enroll are refused with it\n", a.score ? "--score" : "--tune"); return 2; }
+    if (a.tune && (a.enrolled || a.dump_dir)) { fprintf(stderr, "usage: --tune cuts one dendrogram many times; --enrolled and --dump-steps are refused with it\n"); return 2; }
+    if (a.tune && a.thresholds.empty()) { fprintf(stderr, "usage: --tune REF.rttm needs --thresholds LO:HI:N\n"); return 2; }
+    if (!a.tune && (!a.thresholds.empty() || !a.min_sizes.empty())) { fprintf(stderr, "usage: --thresholds and --min-cluster-sizes need --tune REF.rttm\n"); return 2; }
+    if (!a.tune && !a.score && (a.collar > 0.0 || a.skip_overlap || a.uem_from_ref)) { fprintf(stderr, "usage: --collar, --skip-overlap and --uem-from-ref need --score or --tune REF.rttm\n"); return 2; }
+    if (a.tune && a.min_sizes.empty()) a.min_sizes.push_back(a.cl_min_size >= 1 ? a.cl_min_size : 0);      // (0 = the context's option)
+    if (a.score || a.tune) {
+        sd_turn* rt = nullptr; int64_t rn = 0;
+        if (sd_read_rttm(a.score ? a.score : a.tune, nullptr, &rt, &rn, nullptr, nullptr) != SD_OK) { fprintf(stderr, "usage: %s REF.rttm: %s\n", a.score ? "--score" : "--tune", sd_score_error()); return 2; }
+        a.ref.assign(rt, rt + rn);
+        sd_free_turns(rt);
+    }
     if (a.many) { a.seg = pos[0]; a.emb = pos[1]; return run_many(a); }
     if (pos.size() < 3) {
         printf("program [segment model file] [embeding model file] [wave file]\n");   // sd.cpp:3423
@@ -618,6 +726,7 @@ int main(int argc, char* argv[])
     }
     a.seg = pos[0]; a.emb = pos[1]; a.wav = pos[2];
     if (a.enroll) return run_enroll(a);
+    if (a.tune) return run_tune(a);
     if (a.stream_piece > 0) return run_stream(a);
     if (a.gpus <= 1) return run_single(a);
 

@@ -296,6 +296,27 @@ int shard_infer(sd_ctx* c, const DevWav& w, int64_t lo, int64_t hi, float* d_seg
     return SD_OK;
 }
 
+// per-turn confidence: mean soft score (2 - cosine distance to the centroid, sd.cpp:2191-2207) of the
+// (chunk, local speaker) items assigned to the turn's cluster whose 5 s chunk [0.5 c, 0.5 c + 5) overlaps the turn
+void turn_confidence(const std::vector<sd_turn>& v, const std::vector<int>& hard, const std::vector<double>& soft_best, int64_t chunks, std::vector<double>& conf)
+{
+    conf.assign(v.size(), NAN);
+    for (size_t t = 0; t < v.size(); ++t) {
+        int64_t c0 = (int64_t)std::floor((v[t].start - 5.0) / 0.5), c1 = (int64_t)std::ceil(v[t].end / 0.5);
+        if (c0 < 0) c0 = 0;
+        if (c1 > chunks - 1) c1 = chunks - 1;
+        double sum = 0.0; int64_t cnt = 0;
+        for (int64_t ck = c0; ck <= c1; ++ck) {
+            if (!(0.5 * (double)ck < v[t].end && 0.5 * (double)ck + 5.0 > v[t].start)) continue;
+            for (int s = 0; s < SD_SPEAKERS; ++s) {
+                const size_t i = (size_t)(ck * SD_SPEAKERS + s);
+                if (hard[i] == v[t].label && soft_best[i] == soft_best[i]) { sum += soft_best[i]; cnt++; }
+            }
+        }
+        if (cnt > 0) conf[t] = sum / (double)cnt;
+    }
+}
+
 int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, std::vector<sd_turn>& v)
 {
     int rc;
@@ -331,24 +352,8 @@ int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, 
         c->stash.infer_items = 0;            // the per-batch files describe the inference that led to THIS finalize only
         if (rc) return rc;
     }
-    // per-turn confidence: mean soft score (2 - cosine distance to the centroid, sd.cpp:2191-2207) of the
-    // (chunk, local speaker) items assigned to the turn's cluster whose 5 s chunk [0.5 c, 0.5 c + 5) overlaps the turn
     { KernelStat& ks = c->stats["clusters_K"]; ks.launches++; ks.flops += (double)Kr; ks.bytes += (double)v.size(); }       // bench: K and turns per job
-    c->last_conf.assign(v.size(), NAN);
-    for (size_t t = 0; t < v.size(); ++t) {
-        int64_t c0 = (int64_t)std::floor((v[t].start - 5.0) / 0.5), c1 = (int64_t)std::ceil(v[t].end / 0.5);
-        if (c0 < 0) c0 = 0;
-        if (c1 > chunks - 1) c1 = chunks - 1;
-        double sum = 0.0; int64_t cnt = 0;
-        for (int64_t ck = c0; ck <= c1; ++ck) {
-            if (!(0.5 * (double)ck < v[t].end && 0.5 * (double)ck + 5.0 > v[t].start)) continue;
-            for (int s = 0; s < SD_SPEAKERS; ++s) {
-                const size_t i = (size_t)(ck * SD_SPEAKERS + s);
-                if (hard[i] == v[t].label && soft_best[i] == soft_best[i]) { sum += soft_best[i]; cnt++; }
-            }
-        }
-        if (cnt > 0) c->last_conf[t] = sum / (double)cnt;
-    }
+    turn_confidence(v, hard, soft_best, chunks, c->last_conf);
     c->stage_ms[2] += now_ms() - t0;
     return SD_OK;
 }
@@ -503,6 +508,50 @@ extern "C" int sd_diarize_f32(sd_ctx* c, const float* h_wav, int64_t n, sd_turn*
 extern "C" int sd_diarize_wav(sd_ctx* c, const char* path, int flags, sd_turn** turns, int64_t* n_turns)
 {
     return diarize_from(c, Source{Source::WavFile, path, 0, flags}, "sd_diarize_wav", turns, n_turns);
+}
+
+// ------------------------------------------------------------------ a cut object from samples (cut.hip): chunks, both networks, then everything of a
+// finalize in front of the cut of the dendrogram.  stage_ms[0], [1] = the inference, [3] = the time since t0
+static int cut_wav_dev(sd_ctx* c, const DevWav& w, double t0, sd_cut** cut)
+{
+    const int64_t chunks = sd_num_chunks(w.n, nullptr);
+    if (chunks <= 0) SD_FAIL(c, SD_ERR_SHORT, "audio of %lld samples yields no chunk", (long long)w.n);
+    WS(c, float, d_seg, "dz_seg", chunks * SD_FRAMES * 3);
+    WS(c, float, d_emb, "dz_emb", chunks * 3 * SD_EMB_DIM);
+    int rc;
+    if ((rc = shard_infer(c, w, 0, chunks, d_seg, d_emb))) return rc;
+    if ((rc = cut_open_dev(c, d_seg, d_emb, chunks, w.n, cut))) return rc;
+    c->stage_ms[3] = now_ms() - t0;
+    return SD_OK;
+}
+
+static int cut_from(sd_ctx* c, const Source& s, const char* who, sd_cut** cut)
+{
+    ENTER(c);
+    int rc;
+    if ((rc = check_args(c, s, cut != nullptr, who))) return rc;
+    *cut = nullptr;
+    if ((rc = cut_refusal(c, who))) return rc;                   // before anything is touched
+    Brought b;
+    if ((rc = bring(c, s, who, b))) return rc;
+    return cut_wav_dev(c, b.w, b.t0, cut);
+}
+
+extern "C" int sd_cut_open_pcm_dev(sd_ctx* c, const int16_t* d_pcm, int64_t n, sd_cut** cut)
+{
+    return cut_from(c, Source{Source::DevPcm, d_pcm, n, 0}, "sd_cut_open_pcm_dev", cut);
+}
+extern "C" int sd_cut_open(sd_ctx* c, const int16_t* h_pcm, int64_t n, sd_cut** cut)
+{
+    return cut_from(c, Source{Source::HostPcm, h_pcm, n, 0}, "sd_cut_open", cut);
+}
+extern "C" int sd_cut_open_f32(sd_ctx* c, const float* h_wav, int64_t n, sd_cut** cut)
+{
+    return cut_from(c, Source{Source::HostF32, h_wav, n, 0}, "sd_cut_open_f32", cut);
+}
+extern "C" int sd_cut_open_wav(sd_ctx* c, const char* path, int flags, sd_cut** cut)
+{
+    return cut_from(c, Source{Source::WavFile, path, 0, flags}, "sd_cut_open_wav", cut);
 }
 
 // ------------------------------------------------------------------ speech / overlapped-speech regions (activity.hip)

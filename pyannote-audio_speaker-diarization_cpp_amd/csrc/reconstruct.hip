@@ -94,7 +94,7 @@ static void crop_range(double w_start, double w_step, double w_dur, int64_t w_ns
 }
 
 // a17 on the host: binary [rows][K] -> turns
-static void to_annotation_host(const std::vector<uint8_t>& binary, int64_t rows, int K, double w_start, std::vector<sd_turn>& out)
+void to_annotation_host(const std::vector<uint8_t>& binary, int64_t rows, int K, double w_start, std::vector<sd_turn>& out)
 {
     const double onset = 0.5, offset = 0.5;                                   // sd.cpp:3228-3230
     const float min_off_f = 0.5817029604921046;                               // float at the call site, sd.cpp:3210
@@ -141,6 +141,28 @@ static void to_annotation_host(const std::vector<uint8_t>& binary, int64_t rows,
     std::sort(out.begin(), out.end(), [](const sd_turn& a, const sd_turn& b) { return a.start < b.start; });
 }
 
+// the part of a reconstruction that the sizes of the job decide: frames, first frame per chunk, the two crops
+void reconstruct_frames(int64_t chunks, int64_t n_count, int64_t n_samples, ReconFrames& g)
+{
+    // activations grid: frames window (0.0, step, dur) (sd.cpp:1233), chunk windows (0.0, 0.5, 5.0)
+    const double target = 0.0 + 5.0 + (double)(chunks - 1) * 0.5;
+    g.nact = closest_frame_host(0.0, kFrameStep, kFrameDur, target) + 1;
+    g.sfr.resize((size_t)chunks);
+    double start = 0.0;
+    for (int64_t i = 0; i < chunks; ++i) { g.sfr[(size_t)i] = (int)closest_frame_host(0.0, kFrameStep, kFrameDur, start); start += 0.5; }
+    // extents and their intersection, sd.cpp:2691-2706.  count window = (0.5, step, dur, num_samples 235)
+    const double c_start_w = 0.0 + 0.1 * 5.0;
+    const double a_end = 0.0 + (0 - .5) * kFrameStep + .5 * kFrameDur + (double)g.nact * kFrameStep;
+    const double c_end = c_start_w + (0 - .5) * kFrameStep + .5 * kFrameDur + (double)n_count * kFrameStep;
+    const double f0 = std::max(0.0, c_start_w), f1 = std::min(a_end, c_end);
+    int64_t ar1, cr1; float cstart;
+    const int Ft = SD_FRAMES - 2 * (int)std::floor((double)SD_FRAMES * 0.1);
+    crop_range(0.0, kFrameStep, kFrameDur, n_samples, f0, f1, g.nact, &g.ar0, &ar1, &g.astart);
+    crop_range(c_start_w, kFrameStep, kFrameDur, Ft, f0, f1, n_count, &g.cr0, &cr1, &cstart);
+    g.rows = ar1 - g.ar0;
+    g.crow_all = cr1 - g.cr0;
+}
+
 // hard: host [chunks][3] with -2 for inactive local speakers (sd.cpp:3172-3191 applied by the caller)
 int run_reconstruct(sd_ctx* c, const float* d_seg, const int* /*d_nact*/, const int* d_hard, const int32_t* d_count,
                     int64_t n_count, int64_t chunks, int64_t n_samples, int K, std::vector<sd_turn>& turns)
@@ -148,32 +170,19 @@ int run_reconstruct(sd_ctx* c, const float* d_seg, const int* /*d_nact*/, const 
     turns.clear();
     c->stash.rows = 0;
     if (chunks <= 0 || K <= 0) return SD_OK;
-    // activations grid: frames window (0.0, step, dur) (sd.cpp:1233), chunk windows (0.0, 0.5, 5.0)
-    const double target = 0.0 + 5.0 + (double)(chunks - 1) * 0.5;
-    const int64_t nact = closest_frame_host(0.0, kFrameStep, kFrameDur, target) + 1;
-    std::vector<int> sfr((size_t)chunks);
-    double start = 0.0;
-    for (int64_t i = 0; i < chunks; ++i) { sfr[(size_t)i] = (int)closest_frame_host(0.0, kFrameStep, kFrameDur, start); start += 0.5; }
+    ReconFrames g;
+    reconstruct_frames(chunks, n_count, n_samples, g);
+    const int64_t nact = g.nact, ar0 = g.ar0, cr0 = g.cr0, rows = g.rows;
     WS(c, int, d_sfr, "rc_sfr", chunks);
     WS(c, double, d_act, "rc_act", nact * K);
-    HIPCHK(c, hipMemcpyAsync(d_sfr, sfr.data(), (size_t)chunks * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_sfr, g.sfr.data(), (size_t)chunks * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     {
         ProfScope ps(c, "activations", 0, (double)chunks * SD_FRAMES * 3 * 4.0 + (double)nact * K * 8.0);
         hipLaunchKernelGGL(k_activations, dim3((unsigned)((nact * K + 255) / 256)), dim3(256), 0, c->stream, d_seg, d_hard, d_sfr, chunks, K, d_act, nact);
         KCHECK(c);
     }
-    // extents and their intersection, sd.cpp:2691-2706.  count window = (0.5, step, dur, num_samples 235)
-    const double c_start_w = 0.0 + 0.1 * 5.0;
-    const double a_end = 0.0 + (0 - .5) * kFrameStep + .5 * kFrameDur + (double)nact * kFrameStep;
-    const double c_end = c_start_w + (0 - .5) * kFrameStep + .5 * kFrameDur + (double)n_count * kFrameStep;
-    const double f0 = std::max(0.0, c_start_w), f1 = std::min(a_end, c_end);
-    int64_t ar0, ar1, cr0, cr1; float astart, cstart;
-    const int Ft = SD_FRAMES - 2 * (int)std::floor((double)SD_FRAMES * 0.1);
-    crop_range(0.0, kFrameStep, kFrameDur, n_samples, f0, f1, nact, &ar0, &ar1, &astart);
-    crop_range(c_start_w, kFrameStep, kFrameDur, Ft, f0, f1, n_count, &cr0, &cr1, &cstart);
-    const int64_t rows = ar1 - ar0;
-    int64_t crow = cr1 - cr0;
+    int64_t crow = g.crow_all;
     if (rows <= 0) return SD_OK;                      // reference would index an empty vector here (sd.cpp:2735)
     { StepStash& S = c->stash; S.ar0 = ar0; S.cr0 = cr0; S.rows = rows; S.crow_all = crow; S.nact = nact; }      // step dumps
     if (crow > rows) crow = rows;                     // reference asserts cropped_count.size() <= rows (sd.cpp:2745)
@@ -186,6 +195,6 @@ int run_reconstruct(sd_ctx* c, const float* d_seg, const int* /*d_nact*/, const 
     std::vector<uint8_t> binary((size_t)rows * K);
     HIPCHK(c, hipMemcpyAsync(binary.data(), d_binary, binary.size(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    to_annotation_host(binary, rows, K, (double)astart, turns);
+    to_annotation_host(binary, rows, K, (double)g.astart, turns);
     return SD_OK;
 }

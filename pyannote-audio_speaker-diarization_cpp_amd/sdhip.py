@@ -20,6 +20,16 @@ class Turn(C.Structure):
     _fields_ = [("start", C.c_double), ("end", C.c_double), ("label", C.c_int32), ("_pad", C.c_int32)]
 
 
+class DerResult(C.Structure):
+    """sd_der_result of include/sdhip.h"""
+    _fields_ = [(n, C.c_double) for n in ("der", "total", "missed", "false_alarm", "confusion", "correct")]
+
+
+class CutSpec(C.Structure):
+    """sd_cut_spec of include/sdhip.h"""
+    _fields_ = [("threshold", C.c_double), ("min_cluster_size", C.c_int32), ("num_clusters", C.c_int32)]
+
+
 class ConvCase(C.Structure):
     """sd_conv_case of include/sdhip_test.h"""
     _fields_ = [(n, C.c_int32) for n in (
@@ -59,6 +69,9 @@ EXPORTS = [
     "sd_match_speakers", "sd_read_voiceprints", "sd_write_voiceprints", "sd_free_voiceprints", "sd_voiceprints_error", "sd_write_rttm_named",
     "sd_set_enrolled", "sd_enrolled_info", "sd_nearest_speakers", "sd_last_enrolled",
     "sd_many_plan", "sd_diarize_many", "sd_diarize_many_dev", "sd_diarize_many_f32", "sd_many_select",
+    "sd_der", "sd_read_rttm", "sd_free_rttm_names", "sd_score_error",
+    "sd_cut_open_dev", "sd_cut_open", "sd_cut_open_pcm_dev", "sd_cut_open_f32", "sd_cut_open_wav", "sd_cut_turns", "sd_cut_turns_many",
+    "sd_cut_dendrogram", "sd_cut_info", "sd_cut_close",
 ]
 # SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
 LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
@@ -178,6 +191,22 @@ def lib():
         for f in (L.sd_diarize_many, L.sd_diarize_many_dev, L.sd_diarize_many_f32):
             f.argtypes = [vp, vp, vp, i64, vp, vp, vp]
         L.sd_many_select.argtypes = [vp, i64]
+    if hasattr(L, "sd_der"):            # (an older build loaded through SDHIP_LIB by the A/B tools has none of these)
+        L.sd_der.argtypes = [C.POINTER(Turn), i64, C.POINTER(Turn), i64, C.POINTER(Turn), i64, dbl, C.c_int, C.POINTER(DerResult), vp, i64, C.POINTER(i64)]
+        L.sd_read_rttm.argtypes = [C.c_char_p, C.c_char_p, tpp, C.POINTER(i64), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(i64)]
+        L.sd_free_rttm_names.argtypes = [C.POINTER(C.c_char_p), i64]
+        L.sd_free_rttm_names.restype = None
+        L.sd_score_error.restype = C.c_char_p
+        L.sd_cut_open_dev.argtypes = [vp, vp, vp, i64, i64, C.POINTER(vp)]
+        for f in (L.sd_cut_open, L.sd_cut_open_pcm_dev, L.sd_cut_open_f32):
+            f.argtypes = [vp, vp, i64, C.POINTER(vp)]
+        L.sd_cut_open_wav.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(vp)]
+        L.sd_cut_turns.argtypes = [vp, C.POINTER(CutSpec), tpp, C.POINTER(i64), C.POINTER(i32)]
+        L.sd_cut_turns_many.argtypes = [vp, C.POINTER(CutSpec), i64, tpp, C.POINTER(i64), C.POINTER(i32)]
+        L.sd_cut_dendrogram.argtypes = [vp, vp, i64, C.POINTER(i64)]
+        L.sd_cut_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+        L.sd_cut_close.argtypes = [vp]
+        L.sd_cut_close.restype = None
     L.sd_format_turn.argtypes = [C.POINTER(Turn), C.c_char_p, C.c_int]
     L.sd_stage_ms.argtypes = [vp, C.POINTER(dbl)]
     L.sd_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
@@ -357,6 +386,40 @@ def write_rttm(path, uri, turns, conf=None):
         raise SdError(rc, "cannot write " + path)
 
 
+DER_COMPONENTS = ("total", "missed", "false_alarm", "confusion", "correct")
+
+
+def der(ref, hyp, uem=None, collar=0.0, skip_overlap=False):
+    """sd_der: the diarization error rate of hypothesis turns against reference turns ([(start, end, label)], labels >= 0) by the rule of
+    pyannote.metrics' DiarizationErrorRate (include/sdhip.h).  uem: [(start, end)] spans that are scored, None = everything.  Returns a dict: der,
+    total, missed, false_alarm, confusion, correct (seconds) and map = {hypothesis label: reference label} of the optimal pairing.  Host-only."""
+    r, h = _turn_array(ref), _turn_array(hyp)
+    u, nu = _span_array(uem)
+    cap = max([int(t[2]) for t in hyp if int(t[2]) >= 0] + [-1]) + 1
+    m = (C.c_int32 * max(cap, 1))()
+    out, nm = DerResult(), C.c_int64(0)
+    rc = lib().sd_der(r, len(ref), h, len(hyp), u, nu, float(collar), 1 if skip_overlap else 0, C.byref(out), m, cap, C.byref(nm))
+    if rc:
+        raise SdError(rc, lib().sd_score_error().decode())
+    res = {k: getattr(out, k) for k in ("der",) + DER_COMPONENTS}
+    res["map"] = {k: int(m[k]) for k in range(min(cap, nm.value)) if m[k] >= 0}
+    return res
+
+
+def read_rttm(path, uri=None):
+    """sd_read_rttm: the SPEAKER lines of an RTTM file (of one uri, or of all) -> (turns [(start, end, label)], names): label k is names[k], numbered in
+    order of first appearance.  Host-only; a malformed line raises with its line number."""
+    p, n, names, K = C.POINTER(Turn)(), C.c_int64(0), C.POINTER(C.c_char_p)(), C.c_int64(0)
+    rc = lib().sd_read_rttm(str(path).encode(), None if uri is None else str(uri).encode(), C.byref(p), C.byref(n), C.byref(names), C.byref(K))
+    if rc:
+        raise SdError(rc, lib().sd_score_error().decode())
+    turns = [(p[i].start, p[i].end, int(p[i].label)) for i in range(n.value)]
+    out_names = [names[i].decode() for i in range(K.value)]
+    lib().sd_free_turns(p)
+    lib().sd_free_rttm_names(names, K)
+    return turns, out_names
+
+
 def read_voiceprints(path):
     """sd_read_voiceprints: a voiceprint file -> (names, emb [M][192] float64).  Host-only; a malformed line raises with its line number."""
     names, emb, M = C.POINTER(C.c_char_p)(), C.POINTER(C.c_double)(), C.c_int64(0)
@@ -480,6 +543,86 @@ class Stream:
         e = np.zeros((rows * SPEAKERS, EMB_DIM), np.float32) if emb else None
         self._d._chk(lib().sd_stream_read(self._handle(), int(lo), int(hi), _ptr(s) if seg else None, _ptr(e) if emb else None))
         return s, e
+
+
+class Cut:
+    """sd_cut_*: one dendrogram, many cuts.  Opening runs everything of a finalize that does not depend on clustering_threshold, min_cluster_size and
+    num_clusters -- the linkage above all -- once; turns_many evaluates any number of cuts on it, each equal to Diarizer.finalize_dev under those options.
+    Made by Diarizer.cut_open*; also a context manager."""
+
+    def __init__(self, diarizer, handle):
+        self._d = diarizer
+        self._k = handle
+
+    def close(self):
+        if self._k and self._d._h:              # a closed Diarizer has closed its cuts (sd_destroy)
+            lib().sd_cut_close(self._k)
+        self._k = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._k or not self._d._h:
+            raise SdError(1, "the cut is closed")
+        return self._k
+
+    @staticmethod
+    def _spec(s):
+        """(threshold, min_cluster_size, num_clusters), a dict of them or None; None / missing = the context's current option"""
+        if s is None:
+            s = {}
+        if isinstance(s, dict):
+            s = (s.get("threshold"), s.get("min_cluster_size"), s.get("num_clusters"))
+        s = tuple(s) + (None,) * (3 - len(s))
+        return CutSpec(float("nan") if s[0] is None else float(s[0]), 0 if s[1] is None else int(s[1]), 0 if s[2] is None else int(s[2]))
+
+    def turns_many(self, specs, with_k=False):
+        """sd_cut_turns_many: the turns of every spec (see _spec) in one call; with_k: (turns, K) pairs"""
+        T = len(specs)
+        arr = (CutSpec * max(T, 1))(*[self._spec(s) for s in specs])
+        tp, nt, K = (C.POINTER(Turn) * max(T, 1))(), (C.c_int64 * max(T, 1))(), (C.c_int32 * max(T, 1))()
+        self._d._chk(lib().sd_cut_turns_many(self._handle(), arr, T, tp, nt, K))
+        self._d._last_d = EMB_DIM
+        out = []
+        for t in range(T):
+            turns = [(tp[t][i].start, tp[t][i].end, int(tp[t][i].label)) for i in range(nt[t])]
+            lib().sd_free_turns(tp[t])
+            out.append((turns, int(K[t])) if with_k else turns)
+        return out
+
+    def turns(self, threshold=None, min_cluster_size=None, num_clusters=None):
+        """sd_cut_turns: one cut"""
+        p, n = C.POINTER(Turn)(), C.c_int64(0)
+        spec = self._spec((threshold, min_cluster_size, num_clusters))
+        self._d._chk(lib().sd_cut_turns(self._handle(), C.byref(spec), C.byref(p), C.byref(n), None))
+        return self._d._clustered(p, n)
+
+    def dendrogram(self):
+        """sd_cut_dendrogram: the linkage matrix [N - 1][4] of the N train rows (N < 2: no row)"""
+        N = C.c_int64(0)
+        rc = lib().sd_cut_dendrogram(self._handle(), None, 0, C.byref(N))
+        Z = np.zeros((max(N.value - 1, 0), 4), np.float64)
+        rc = rc or lib().sd_cut_dendrogram(self._handle(), _ptr(Z) if len(Z) else None, len(Z), C.byref(N))
+        if rc:
+            raise SdError(rc, "sd_cut_dendrogram: bad argument")
+        return Z
+
+    def info(self):
+        """(chunks, samples, train rows)"""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        if lib().sd_cut_info(self._handle(), C.byref(a), C.byref(b), C.byref(c)):
+            raise SdError(1, "sd_cut_info: bad argument")
+        return int(a.value), int(b.value), int(c.value)
 
 
 class Diarizer:
@@ -860,6 +1003,49 @@ class Diarizer:
     def stream(self):
         """sd_stream_open: incremental diarization of a growing recording on this context"""
         return Stream(self)
+
+    # ---- many cuts of one dendrogram
+    def _cut(self, rc, h):
+        self._chk(rc)
+        return Cut(self, h)
+
+    def cut_open_dev(self, d_seg_ptr, d_emb_ptr, chunks, n_samples):
+        h = C.c_void_p(None)
+        return self._cut(lib().sd_cut_open_dev(self._h, C.c_void_p(d_seg_ptr), C.c_void_p(d_emb_ptr), chunks, n_samples, C.byref(h)), h)
+
+    def cut_open(self, pcm):
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        h = C.c_void_p(None)
+        return self._cut(lib().sd_cut_open(self._h, _ptr(pcm), len(pcm), C.byref(h)), h)
+
+    def cut_open_pcm_dev(self, d_pcm_ptr, n_samples):
+        h = C.c_void_p(None)
+        return self._cut(lib().sd_cut_open_pcm_dev(self._h, C.c_void_p(d_pcm_ptr), n_samples, C.byref(h)), h)
+
+    def cut_open_f32(self, wav):
+        wav = np.ascontiguousarray(wav, np.float32)
+        h = C.c_void_p(None)
+        return self._cut(lib().sd_cut_open_f32(self._h, _ptr(wav), len(wav), C.byref(h)), h)
+
+    def cut_open_wav(self, path, resample=False, downmix=False, assume_16k=False):
+        h = C.c_void_p(None)
+        return self._cut(lib().sd_cut_open_wav(self._h, str(path).encode(), (1 if resample else 0) | (2 if downmix else 0) | (4 if assume_16k else 0), C.byref(h)), h)
+
+    def tune(self, cut, ref_turns, thresholds, min_cluster_sizes=(None,), **der_options):
+        """every (threshold, min_cluster_size) of the grid -- thresholds outermost -- as one Cut.turns_many, each scored against ref_turns with der(**der_options).
+        Returns (table, best): table = a list of dicts with threshold, min_cluster_size, speakers (label columns) and der's fields -- the components too, so
+        that several recordings pool as the sum of errors over the sum of totals --; best = the first row with the smallest der (NaN counts as largest)."""
+        grid = [(float(t), m) for t in thresholds for m in min_cluster_sizes]
+        table = []
+        for (t, m), (turns, K) in zip(grid, cut.turns_many([(t, m, None) for t, m in grid], with_k=True)):
+            row = dict(threshold=t, min_cluster_size=m, speakers=K)
+            row.update(der(ref_turns, turns, **der_options))
+            table.append(row)
+        best = None
+        for row in table:
+            if best is None or (row["der"] == row["der"] and not best["der"] <= row["der"]):
+                best = row
+        return table, best
 
     def last_confidence(self):
         n = C.c_int64(0)
