@@ -343,8 +343,8 @@ extern "C" int sd_relabel_turns(sd_turn* turns, int64_t n) { return sd_relabel_t
 extern "C" int sd_last_confidence(const sd_ctx* c, double* conf, int64_t cap, int64_t* n)
 {
     if (!c) return SD_ERR_ARG;
-    if (n) *n = (int64_t)c->last_conf.size();
-    if (conf) for (int64_t i = 0; i < cap && i < (int64_t)c->last_conf.size(); ++i) conf[i] = c->last_conf[(size_t)i];
+    if (n) *n = (int64_t)c->last.conf.size();
+    if (conf) for (int64_t i = 0; i < cap && i < (int64_t)c->last.conf.size(); ++i) conf[i] = c->last.conf[(size_t)i];
     return SD_OK;
 }
 
@@ -381,11 +381,11 @@ extern "C" int sd_write_rttm(const char* path, const char* uri, const sd_turn* t
 extern "C" int sd_last_speakers(const sd_ctx* c, double* h_centroids, int64_t cap, int64_t* K, int64_t* h_counts)
 {
     if (!c || cap < 0) return SD_ERR_ARG;
-    const int64_t k = c->last_cen_K, d = c->last_cen_d;
+    const int64_t k = c->last.cen_K, d = c->last.cen_d;
     if (K) *K = k;
     for (int64_t i = 0; i < k && i < cap; ++i) {
-        if (h_centroids) memcpy(h_centroids + i * d, &c->last_cen[(size_t)(i * d)], (size_t)d * sizeof(double));
-        if (h_counts) h_counts[i] = c->last_cen_counts[(size_t)i];
+        if (h_centroids) memcpy(h_centroids + i * d, &c->last.cen[(size_t)(i * d)], (size_t)d * sizeof(double));
+        if (h_counts) h_counts[i] = c->last.cen_counts[(size_t)i];
     }
     return SD_OK;
 }
@@ -395,9 +395,9 @@ static int speaker_dist_host(sd_ctx* c, const double* h_cen, int64_t K, const do
 {
     if (!h_gallery || K < 1 || M < 1 || d < 1) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument (K, M, d >= 1)", who);
     if (!h_cen) {
-        if (c->last_cen_K < 1) SD_FAIL(c, SD_ERR_ARG, "%s: no clustering call on this context yet", who);
-        if (K != c->last_cen_K || d != c->last_cen_d) SD_FAIL(c, SD_ERR_ARG, "%s: the last job has %d centroids of %d dimensions, not %lld of %d", who, c->last_cen_K, c->last_cen_d, (long long)K, d);
-        h_cen = c->last_cen.data();
+        if (c->last.cen_K < 1) SD_FAIL(c, SD_ERR_ARG, "%s: no clustering call on this context yet", who);
+        if (K != c->last.cen_K || d != c->last.cen_d) SD_FAIL(c, SD_ERR_ARG, "%s: the last job has %d centroids of %d dimensions, not %lld of %d", who, c->last.cen_K, c->last.cen_d, (long long)K, d);
+        h_cen = c->last.cen.data();
     }
     if ((double)K * (double)M > 4e9) SD_FAIL(c, SD_ERR_ARG, "%s: a %lld x %lld table is out of range", who, (long long)K, (long long)M);
     dist.resize((size_t)K * (size_t)M);
@@ -518,9 +518,9 @@ extern "C" int sd_nearest_speakers(sd_ctx* c, const double* h_X, int64_t N, cons
 extern "C" int sd_last_enrolled(const sd_ctx* c, int32_t* h_rows, int64_t cap, int64_t* K)
 {
     if (!c || cap < 0) return SD_ERR_ARG;
-    const int64_t k = c->last_cen_K;
+    const int64_t k = c->last.cen_K;
     if (K) *K = k;
-    for (int64_t i = 0; i < k && i < cap; ++i) if (h_rows) h_rows[i] = i < (int64_t)c->last_enrolled.size() ? c->last_enrolled[(size_t)i] : -1;
+    for (int64_t i = 0; i < k && i < cap; ++i) if (h_rows) h_rows[i] = i < (int64_t)c->last.enrolled.size() ? c->last.enrolled[(size_t)i] : -1;
     return SD_OK;
 }
 

@@ -5,7 +5,8 @@
 //   a13 Clustering::fcluster(criterion=distance)                                   cl.cpp:121-232, 442-457
 //   a14 assign_embeddings (centroids, cosine cdist, argmax)                        sd.cpp:2119-2212
 //   constrained arg-max and the hyper-parameter recut                              clustering/Clustering.py
-// a12, Clustering::linkage, is run_linkage in linkage.hip.  fcluster is O(N) pointer chasing and runs on the host.
+// a12, Clustering::linkage, is run_linkage in linkage.hip.  fcluster is O(N) pointer chasing and runs on the host: it and the rest of the host arithmetic
+// of a cut (number-of-clusters rules, re-cut, size split) are cluster_host.h; cluster_cut below is the one finish of a cut, for run_clustering and cut.hip.
 #include "common.h"
 #include "exact_fp.h"
 #include <algorithm>
@@ -31,58 +32,17 @@ __global__ void k_gather_normalize(const double* __restrict__ X, const int* __re
     }
 }
 
-// fcluster(criterion="distance"), cl.cpp:121-232 + 442-457.  Node ids grow with merge order, so the
-// per-node max merge height is a forward pass; labels follow the reference's visiting order: internal
-// left subtree, internal right subtree, then the leaf children of the node.
-void fcluster_host(const std::vector<double>& Z, int64_t n, double cutoff, std::vector<int>& T)
+// a12 with its copy back: the linkage matrix of the N >= 2 rows of d_Xn on the host ([N - 1][4]); fewer rows: no linkage runs and Z is empty
+int run_linkage_host(sd_ctx* c, const double* d_Xn, int64_t N, int d, int method, int metric, std::vector<double>& Z)
 {
-    T.assign((size_t)n, 0);
-    if (n == 1) { T[0] = 1; return; }
-    if (n < 2) return;
-    std::vector<double> MD((size_t)n - 1);
-    for (int64_t k = 0; k < n - 1; ++k) {
-        double mx = Z[k * 4 + 2];
-        const int64_t lc = (int64_t)Z[k * 4 + 0], rc = (int64_t)Z[k * 4 + 1];
-        if (lc >= n && MD[lc - n] > mx) mx = MD[lc - n];
-        if (rc >= n && MD[rc - n] > mx) mx = MD[rc - n];
-        MD[k] = mx;
-    }
-    struct Fr { int64_t node; int label; int state; };
-    std::vector<Fr> st;
-    st.push_back({2 * n - 2, 0, 0});
-    int ncl = 0;
-    while (!st.empty()) {
-        Fr& f = st.back();
-        const int64_t k = f.node - n;
-        const int64_t lc = (int64_t)Z[k * 4 + 0], rc = (int64_t)Z[k * 4 + 1];
-        if (f.state == 0) {
-            if (f.label == 0 && MD[k] <= cutoff) f.label = ++ncl;
-            f.state = 1;
-            if (lc >= n) { const int lab = f.label; st.push_back({lc, lab, 0}); continue; }
-        }
-        if (f.state == 1) {
-            f.state = 2;
-            if (rc >= n) { const int lab = f.label; st.push_back({rc, lab, 0}); continue; }
-        }
-        if (lc < n) T[lc] = f.label ? f.label : ++ncl;
-        if (rc < n) T[rc] = f.label ? f.label : ++ncl;
-        st.pop_back();
-    }
-}
-
-int run_cluster_labels(sd_ctx* c, const double* d_Xn, int64_t N, int d, double cutoff, std::vector<int>& labels1, std::vector<double>* Zout, int method, int metric)
-{
-    labels1.assign((size_t)N, 0);
-    if (N == 1) { labels1[0] = 1; return SD_OK; }
+    Z.clear();
     if (N < 2) return SD_OK;
     WS(c, double, dZ, "cl_Z", (N - 1) * 4);
     int rc = run_linkage(c, d_Xn, N, d, dZ, method, metric);
     if (rc) return rc;
-    std::vector<double> Z((size_t)(N - 1) * 4);
+    Z.resize((size_t)(N - 1) * 4);
     HIPCHK(c, hipMemcpyAsync(Z.data(), dZ, Z.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    fcluster_host(Z, N, cutoff, labels1);
-    if (Zout) Zout->swap(Z);
     return SD_OK;
 }
 
@@ -226,57 +186,12 @@ static double cos_dist_host(const double* a, const double* b, int d, bool* err) 
     return 1.0 - (dot / (sqrt(m1) * sqrt(m2)));
 }
 
-// group rows by label (ascending row order inside each group); a row with a negative label belongs to no group
-void group_by_label(const std::vector<int>& lab, int nl, std::vector<int>& order, std::vector<int>& off)
-{
-    off.assign((size_t)nl + 1, 0);
-    for (int v : lab) if (v >= 0) off[(size_t)v + 1]++;
-    for (int k = 0; k < nl; ++k) off[(size_t)k + 1] += off[(size_t)k];
-    order.resize((size_t)off[(size_t)nl]);
-    std::vector<int> pos(off.begin(), off.end() - 1);
-    for (size_t i = 0; i < lab.size(); ++i) if (lab[i] >= 0) order[(size_t)pos[(size_t)lab[i]]++] = (int)i;
-}
-
-// Constrained number of clusters -- the branch the reference leaves unimplemented (assert(false), sd.cpp:2368-2369);
-// specification = the Python it was ported from, clustering/Clustering.py:352-399: re-cut the dendrogram by merge
-// index, walking away from the tuned threshold, until the number of large clusters is (closest to) num_clusters.
-void constrained_recut(const std::vector<double>& Z, int64_t N, double threshold, size_t mcs, int num_clusters, std::vector<int>& lab)
-{
-    std::vector<double> Zi(Z);
-    for (int64_t k = 0; k < N - 1; ++k) Zi[(size_t)k * 4 + 2] = (double)k;          // Clustering.py:353-354
-    std::vector<int64_t> order((size_t)N - 1);
-    for (int64_t k = 0; k < N - 1; ++k) order[(size_t)k] = k;
-    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
-        return fabs(Z[(size_t)a * 4 + 2] - threshold) < fabs(Z[(size_t)b * 4 + 2] - threshold); });   // :362
-    auto count_large = [&](const std::vector<int>& t1) {
-        int mx = 0; for (int v : t1) if (v > mx) mx = v;
-        std::vector<size_t> cnt((size_t)mx + 1, 0);
-        for (int v : t1) cnt[(size_t)v]++;
-        int nlarge = 0; for (size_t v = 1; v < cnt.size(); ++v) if (cnt[v] >= mcs) nlarge++;
-        return nlarge;
-    };
-    int64_t best_iteration = N - 1; int best_large = 1;                               // :356-357
-    std::vector<int> t1;
-    bool exact = false;
-    for (int64_t it : order) {
-        if (Zi[(size_t)it * 4 + 3] < (double)mcs) continue;                           // :366-368
-        fcluster_host(Zi, N, (double)it, t1);                                         // :371
-        const int nlarge = count_large(t1);
-        if (std::abs(nlarge - num_clusters) < std::abs(best_large - num_clusters)) { best_iteration = it; best_large = nlarge; }   // :377-381
-        if (nlarge == num_clusters) { exact = true; break; }                          // :384-385
-    }
-    if (!exact) fcluster_host(Zi, N, (double)best_iteration, t1);                     // :388-391
-    lab.resize((size_t)N);
-    for (int64_t i = 0; i < N; ++i) lab[(size_t)i] = t1[(size_t)i] - 1;
-}
-
 // ---------------------------------------------------------------- the steps of run_clustering: the plain flow and the enrolled flow call the same ones
-// a10 / a11 / a12 / a13: rows idx[0 .. N) of d_emb gathered (X) and normalised with the f32 norm (Xn), then the labels of the dendrogram cut, 0-based, nl of them.
-// Method, threshold and minimum cluster size are the three hyper-parameters of Clustering.py:251-276; their defaults are the constants the
-// reference hard-codes (sd.cpp:2049-2056: centroid, the float-typed threshold promoted to double, 15).  Clustering.py:317-333: centroid, median and ward
-// are euclidean-only and run on the unit-normalised rows (Xn, with the port's f32 norm); the other four run on the rows as they are with the cosine metric.
-int cluster_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, int d, double** Xout, double** Xnout, std::vector<int>& lab, int* nlout,
-                 std::vector<double>* Zh)
+// a10 / a11 / a12: rows idx[0 .. N) of d_emb gathered (X) and normalised with the f32 norm (Xn), then the dendrogram of them (Z on the host; empty for N < 2).
+// The method is one of the three hyper-parameters of Clustering.py:251-276; its default is the constant the reference hard-codes (sd.cpp:2049-2056: centroid).
+// Clustering.py:317-333: centroid, median and ward are euclidean-only and run on the unit-normalised rows (Xn, with the port's f32 norm); the other four run
+// on the rows as they are with the cosine metric.  Threshold and minimum cluster size act behind this step: cluster_cut, or the enrolled flow's own steps.
+int cluster_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, int d, double** Xout, double** Xnout, std::vector<double>& Z)
 {
     const int64_t N = (int64_t)idx.size();
     WS(c, int, d_tidx, "cl_tidx", N);
@@ -287,30 +202,15 @@ int cluster_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, in
     KCHECK(c);
     const int method = c->clustering_method;
     const bool euclid = method == SD_LINKAGE_CENTROID || method == SD_LINKAGE_MEDIAN || method == SD_LINKAGE_WARD;
-    int rc = run_cluster_labels(c, euclid ? Xn : X, N, d, c->clustering_threshold, lab, Zh, method, euclid ? SD_METRIC_EUCLIDEAN : SD_METRIC_COSINE);
-    if (rc) return rc;
-    int nl = 0;
-    for (auto& v : lab) { v -= 1; if (v + 1 > nl) nl = v + 1; }
-    *Xout = X; *Xnout = Xn; *nlout = nl;
-    return SD_OK;
-}
-
-// a11: which clusters reach mcs rows (clusters without a row are neither)
-void split_by_size(const std::vector<int>& off, int nl, size_t mcs, std::vector<int>& large, std::vector<int>& small)
-{
-    large.clear(); small.clear();
-    for (int k = 0; k < nl; ++k) {
-        const size_t cnt = (size_t)(off[(size_t)k + 1] - off[(size_t)k]);
-        if (cnt == 0) continue;
-        if (cnt >= mcs) large.push_back(k); else small.push_back(k);
-    }
+    *Xout = X; *Xnout = Xn;
+    return run_linkage_host(c, euclid ? Xn : X, N, d, method, euclid ? SD_METRIC_EUCLIDEAN : SD_METRIC_COSINE, Z);
 }
 
 // a11: every small cluster goes to the nearest candidate -- first the G rows of `enrolled` (host, [G][d]; the enrolled flow), then the large clusters in
 // ascending id -- by the cosine distance of the means of the UN-normalised rows (sd.cpp:2386), the reference's float minVal loop (sd.cpp:2396).  The rows of a
 // cluster that goes to an enrolled candidate get label -1; the labels that survive are renumbered 0 .. nl - 1 in sorted-id order (findUniqueClusters,
 // sd.cpp:519-548).
-int reassign_small(sd_ctx* c, const double* X, int d, const std::vector<int>& order, const std::vector<int>& off, const std::vector<int>& large,
+static int reassign_small(sd_ctx* c, const double* X, int d, const std::vector<int>& order, const std::vector<int>& off, const std::vector<int>& large,
                           const std::vector<int>& small, const double* enrolled, int G, std::vector<int>& lab, int& nl)
 {
     const size_t N = order.size();
@@ -348,6 +248,20 @@ int reassign_small(sd_ctx* c, const double* X, int d, const std::vector<int>& or
     return SD_OK;
 }
 
+// One cut of the dendrogram Z of the N train rows X (cluster_rows): cluster_plan (cluster_host.h), then the all-small rule or the small -> large pass.  p.lab /
+// p.nl are final afterwards (p.order / p.off: the membership before the pass); p.trivial: one cluster, nothing was read.  first_cut: see cluster_plan.
+int cluster_cut(sd_ctx* c, const std::vector<double>& Z, int64_t N, const double* X, int d, const ClusterSpec& spec, ClusterPlan& p, std::vector<int>* first_cut)
+{
+    cluster_plan(Z, N, spec, p, first_cut);
+    if (p.trivial) return SD_OK;
+    if (p.large.empty()) {
+        // reference: assert(false) in assert-enabled builds (sd.cpp:2368), all-zero labels otherwise (sd.cpp:2371-2375)
+        std::fill(p.lab.begin(), p.lab.end(), 0);
+        p.nl = 1;
+    } else if (!p.small.empty()) return reassign_small(c, X, d, p.order, p.off, p.large, p.small, nullptr, 0, p.lab, p.nl);
+    return SD_OK;
+}
+
 // a14, first half: the means of the nl final clusters (un-normalised rows of X, members in ascending row order) into rows [G, G + nl) of the centroid table
 // "cl_cen"; rows [0, G) are left to the caller (the enrolled flow's voiceprints).  order / off describe the membership afterwards.
 int final_means(sd_ctx* c, const double* X, int d, const std::vector<int>& lab, int nl, int G, std::vector<int>& order, std::vector<int>& off, double** cen_out)
@@ -366,10 +280,11 @@ int final_means(sd_ctx* c, const double* X, int d, const std::vector<int>& lab, 
     return SD_OK;
 }
 
-// a14, second half: cosine cdist of ALL M rows to the K centroids, arg-max (or the constrained arg-max); the centroids and their counts become what
-// sd_last_speakers describes.  *soft_out (may be NULL) = the [M][K] score table where one was written, else null.
+// a14, second half: cosine cdist of ALL M rows to the K centroids, arg-max (or the constrained arg-max); the centroids and their counts become the centroid
+// part of `res` (what sd_last_speakers describes once the caller commits it), cen_K last: 0 stays 0 where this fails.  *soft_out (may be NULL) = the [M][K]
+// score table where one was written, else null.
 int assign_all(sd_ctx* c, const double* d_emb, int64_t M, int d, const double* d_cen2, int K, const std::vector<int64_t>& counts,
-                      std::vector<int>& hard, int* Kout, std::vector<double>* soft_best, double** soft_out)
+                      std::vector<int>& hard, int* Kout, std::vector<double>* soft_best, double** soft_out, JobResult& res)
 {
     const bool dumping = !c->dump_dir.empty();
     WS(c, int, d_hard, "cl_hard", M);
@@ -386,8 +301,8 @@ int assign_all(sd_ctx* c, const double* d_emb, int64_t M, int d, const double* d
     HIPCHK(c, hipMemcpyAsync(hard.data(), d_hard, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&herr, d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (soft_best) HIPCHK(c, hipMemcpyAsync(soft_best->data(), d_best, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    c->last_cen.resize((size_t)K * d);                              // the centroids ride this synchronisation (sd_last_speakers)
-    HIPCHK(c, hipMemcpyAsync(c->last_cen.data(), d_cen2, c->last_cen.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    res.cen.resize((size_t)K * d);                                  // the centroids ride this synchronisation (sd_last_speakers)
+    HIPCHK(c, hipMemcpyAsync(res.cen.data(), d_cen2, res.cen.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (herr) SD_FAIL(c, SD_ERR_NUMERIC, "zero-magnitude embedding or centroid in assignment (reference throws, sd.cpp:493-495)");
     if (constrained_assign) {
@@ -408,9 +323,9 @@ int assign_all(sd_ctx* c, const double* d_emb, int64_t M, int d, const double* d
             for (int64_t i = 0; i < M; ++i) (*soft_best)[(size_t)i] = hard[(size_t)i] >= 0 ? hs[(size_t)i * K + hard[(size_t)i]] : NAN;
     }
     if (Kout) *Kout = K;
-    c->last_cen_counts = counts;
-    c->last_cen_d = d;
-    c->last_cen_K = K;
+    res.cen_counts = counts;
+    res.cen_d = d;
+    res.cen_K = K;
     if (soft_out) *soft_out = d_soft;
     return SD_OK;
 }
@@ -428,6 +343,9 @@ int enrolled_refusal(sd_ctx* c, int d, int num_clusters, int min_clusters, int m
 
 // The enrolled flow (sdhip.h, "enrolled speakers", steps 1 - 9).  tidx = the N >= 1 train rows.  *taken = false: no row was claimed (G = 0), nothing of the
 // context's results has been written and the caller goes on with the plain flow.
+// Steps 5 - 7 call the steps of a cut themselves instead of cluster_cut, because three rules differ from the plain flow: there is no trivial exit (one
+// unclaimed row is a cluster of its own next to the candidates), there is no all-small rule while a candidate is enrolled (small clusters can always go to
+// a candidate), and the minimum cluster size comes from N, all train rows, not from N', the unclaimed ones.
 static int clustering_enrolled(sd_ctx* c, const double* d_emb, int64_t M, int d, const std::vector<int>& tidx, std::vector<int>& hard, int* Kout,
                                std::vector<double>* soft_best, bool* taken)
 {
@@ -459,7 +377,7 @@ static int clustering_enrolled(sd_ctx* c, const double* d_emb, int64_t M, int d,
         if (gd[(size_t)i] <= t) counts[(size_t)(std::lower_bound(U.begin(), U.end(), g[(size_t)i]) - U.begin())]++;
         else ridx.push_back(tidx[(size_t)i]);
     }
-    const size_t mcs = std::min<size_t>((size_t)c->min_cluster_size, std::max<size_t>(1, (size_t)std::round(0.1 * (double)N)));     // from N, not N'
+    const size_t mcs = resolve_min_cluster_size(c->min_cluster_size, N);     // from N, not N'
     std::vector<double> cand((size_t)G * d);
     for (int a = 0; a < G; ++a) memcpy(&cand[(size_t)a * d], &c->enr_host[(size_t)U[(size_t)a] * d], (size_t)d * sizeof(double));
     // 5 - 7: the new clusters of R
@@ -467,7 +385,10 @@ static int clustering_enrolled(sd_ctx* c, const double* d_emb, int64_t M, int d,
     int L = 0;
     double* X = nullptr; double* Xn = nullptr;
     if (!ridx.empty()) {
-        if ((rc = cluster_rows(c, d_emb, ridx, d, &X, &Xn, lab, &L, nullptr))) return rc;
+        std::vector<double> Z;
+        if ((rc = cluster_rows(c, d_emb, ridx, d, &X, &Xn, Z))) return rc;
+        fcluster_host(Z, (int64_t)ridx.size(), c->clustering_threshold, lab);
+        for (auto& v : lab) { v -= 1; if (v + 1 > L) L = v + 1; }
         group_by_label(lab, L, order, off);
         std::vector<int> large, small;
         split_by_size(off, L, mcs, large, small);
@@ -478,13 +399,43 @@ static int clustering_enrolled(sd_ctx* c, const double* d_emb, int64_t M, int d,
     // 8: the table [V[U[0]] .. V[U[G-1]], mean_0 .. mean_{L-1}]
     HIPCHK(c, hipMemcpyAsync(d_cen2, cand.data(), cand.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     for (int k = 0; k < L; ++k) counts.push_back(off[(size_t)k + 1] - off[(size_t)k]);
-    if ((rc = assign_all(c, d_emb, M, d, d_cen2, G + L, counts, hard, Kout, soft_best, nullptr))) return rc;
-    c->last_enrolled.assign((size_t)(G + L), -1);                           // 9
-    for (int a = 0; a < G; ++a) c->last_enrolled[(size_t)a] = U[(size_t)a];
+    if ((rc = assign_all(c, d_emb, M, d, d_cen2, G + L, counts, hard, Kout, soft_best, nullptr, c->last))) return rc;
+    c->last.enrolled.assign((size_t)(G + L), -1);                           // 9
+    for (int a = 0; a < G; ++a) c->last.enrolled[(size_t)a] = U[(size_t)a];
     return SD_OK;
 }
 
-// d_emb: [M][d] f64 (NaN rows = no embedding), M = chunks*3.  hard: [M]
+// a10: the rows of d_emb [M][d] whose first element is not NaN (sd.cpp:2224), ascending; synchronises the stream
+int train_rows(sd_ctx* c, const double* d_e64, int64_t M, int d, std::vector<int>& tidx)
+{
+    std::vector<double> first((size_t)M);
+    HIPCHK(c, hipMemcpy2DAsync(first.data(), sizeof(double), d_e64, (size_t)d * sizeof(double), sizeof(double), (size_t)M, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    tidx.clear();
+    for (int64_t i = 0; i < M; ++i) if (!std::isnan(first[(size_t)i])) tidx.push_back((int)i);
+    return SD_OK;
+}
+
+// The centroid of the one-cluster exit: the mean of the train rows by the rule of a14 (the single row itself), a NaN row when there is none; synchronises
+int mean_of_rows(sd_ctx* c, const double* d_emb, int d, const std::vector<int>& tidx, std::vector<double>& h_cen)
+{
+    const size_t N = tidx.size();
+    h_cen.assign((size_t)d, NAN);
+    if (N == 0) return SD_OK;
+    const int off1[2] = {0, (int)N};
+    WS(c, int, d_order1, "cl_order", N);
+    WS(c, int, d_off1, "cl_off", 2);
+    WS(c, double, d_cen1, "cl_cen", (size_t)d);
+    HIPCHK(c, hipMemcpyAsync(d_order1, tidx.data(), N * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_off1, off1, sizeof(off1), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_cluster_means, dim3(1), dim3(((d + 63) / 64) * 64), 0, c->stream, d_emb, d, d_order1, d_off1, d_cen1);
+    KCHECK(c);
+    HIPCHK(c, hipMemcpyAsync(h_cen.data(), d_cen1, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SD_OK;
+}
+
+// d_emb: [M][d] f64 (NaN rows = no embedding), M = chunks*3.  hard: [M].  c->last: centroids and `enrolled` are this call's; `conf` is the caller's (finalize)
 int run_clustering(sd_ctx* c, const double* d_emb, int64_t M, int d, std::vector<int>& hard, int* Kout,
                    int num_clusters, int min_clusters, int max_clusters, std::vector<double>* soft_best)
 {
@@ -494,95 +445,44 @@ int run_clustering(sd_ctx* c, const double* d_emb, int64_t M, int d, std::vector
     if (Kout) *Kout = 1;
     const bool dumping = !c->dump_dir.empty();
     c->stash.clustered = false;
-    c->last_cen_K = 0;                                              // sd_last_speakers describes this call from its successful end on
-    c->last_enrolled.clear();                                       // ... and sd_last_enrolled: -1 for every label unless the enrolled flow says otherwise
+    JobResult& res = c->last;
+    res.cen_K = 0;                                                  // sd_last_speakers describes this call from its successful end on
+    res.enrolled.clear();                                           // ... and sd_last_enrolled: -1 for every label unless the enrolled flow says otherwise
     if (M <= 0) return SD_OK;
-    // a10: rows whose first element is not NaN (sd.cpp:2224)
-    std::vector<double> first((size_t)M);
-    HIPCHK(c, hipMemcpy2DAsync(first.data(), sizeof(double), d_emb, (size_t)d * sizeof(double), sizeof(double), (size_t)M, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int rc;
     std::vector<int> tidx;
-    for (int64_t i = 0; i < M; ++i) if (!std::isnan(first[(size_t)i])) tidx.push_back((int)i);
+    if ((rc = train_rows(c, d_emb, M, d, tidx))) return rc;
     const int64_t N = (int64_t)tidx.size();
     if (c->enr_M > 0 && N > 0) {                                    // enrolled speakers claim their rows first; no row claimed: the plain flow, untouched
         bool taken = false;
         int rce = clustering_enrolled(c, d_emb, M, d, tidx, hard, Kout, soft_best, &taken);
         if (rce || taken) return rce;
     }
-    // set_num_clusters (sd.cpp:2261-2296; with num_clusters given, max = num_clusters as in Clustering.py:27-41 --
-    // the port's `max_clusters == num_clusters;` is a no-op typo, sd.cpp:2278)
-    const bool constrained = (num_clusters != -1) || (min_clusters != -1) || (max_clusters != -1);
-    if (num_clusters != -1) { min_clusters = num_clusters; max_clusters = num_clusters; }
-    if (min_clusters == -1) min_clusters = 1;
-    if (max_clusters == -1) max_clusters = (int)N;
-    min_clusters = std::max(1, std::min((int)N, min_clusters));
-    max_clusters = std::max(1, std::min((int)N, max_clusters));
-    if (min_clusters > max_clusters) min_clusters = max_clusters;
-    if (min_clusters == max_clusters) num_clusters = min_clusters;
-    if (N < 2 || max_clusters < 2) {                                // all zeros (sd.cpp:2081-2088)
-        // one cluster, label 0: its centroid is the mean of the train rows by the rule of a14 below (the single row itself; a NaN row with count 0 when there is none)
-        c->last_cen.assign((size_t)d, NAN);
-        c->last_cen_counts.assign(1, N);
-        c->last_cen_d = d;
-        if (N > 0) {
-            const int off1[2] = {0, (int)N};
-            WS(c, int, d_order1, "cl_order", N);
-            WS(c, int, d_off1, "cl_off", 2);
-            WS(c, double, d_cen1, "cl_cen", (size_t)d);
-            HIPCHK(c, hipMemcpyAsync(d_order1, tidx.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(d_off1, off1, sizeof(off1), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_cluster_means, dim3(1), dim3(((d + 63) / 64) * 64), 0, c->stream, d_emb, d, d_order1, d_off1, d_cen1);
-            KCHECK(c);
-            HIPCHK(c, hipMemcpyAsync(c->last_cen.data(), d_cen1, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
-        c->last_cen_K = 1;
+    const ClusterSpec spec = {c->clustering_threshold, c->min_cluster_size, num_clusters, min_clusters, max_clusters};
+    if (resolve_num_clusters(spec, N).trivial) {                    // all zeros (sd.cpp:2081-2088), before any linkage runs
+        // one cluster, label 0: its centroid is the mean of the train rows (a NaN row with count 0 when there is none)
+        res.cen_counts.assign(1, N);
+        res.cen_d = d;
+        if ((rc = mean_of_rows(c, d_emb, d, tidx, res.cen))) return rc;
+        res.cen_K = 1;
         return SD_OK;
     }
-    // a12+a13
-    const double thr = c->clustering_threshold;
-    std::vector<int> lab;
+    // a12, then a13 + a11: the dendrogram and its cut
     std::vector<double> Zh;
     double* X = nullptr; double* Xn = nullptr;
-    int nl = 0;
-    int rc = cluster_rows(c, d_emb, tidx, d, &X, &Xn, lab, &nl, &Zh);
-    if (rc) return rc;
-    if (dumping) c->stash.clusters = lab;
-    // a11: size split
-    size_t mcs = std::min<size_t>((size_t)c->min_cluster_size, std::max<size_t>(1, (size_t)std::round(0.1 * (double)N)));     // sd.cpp:2308, Clustering.py:309-311
-    std::vector<int> order, off;
-    group_by_label(lab, nl, order, off);
-    if (constrained) {
-        int nlarge0 = 0;
-        for (int k = 0; k < nl; ++k) if ((size_t)(off[(size_t)k + 1] - off[(size_t)k]) >= mcs) nlarge0++;
-        int target = (min_clusters == max_clusters) ? min_clusters : -1;
-        if (nlarge0 < min_clusters) target = min_clusters;                                            // sd.cpp:2361-2366
-        if (nlarge0 > max_clusters) target = max_clusters;
-        if (target != -1) {
-            constrained_recut(Zh, N, thr, mcs, target, lab);
-            nl = 0;
-            for (int v : lab) if (v + 1 > nl) nl = v + 1;
-            group_by_label(lab, nl, order, off);
-        }
-    }
-    std::vector<int> large, small;
-    split_by_size(off, nl, mcs, large, small);
-    if (large.empty()) {
-        // reference: assert(false) in assert-enabled builds (sd.cpp:2368), all-zero labels otherwise (sd.cpp:2371-2375)
-        std::fill(lab.begin(), lab.end(), 0);
-        nl = 1;
-    } else if (!small.empty()) {
-        if ((rc = reassign_small(c, X, d, order, off, large, small, nullptr, 0, lab, nl))) return rc;
-    }
+    if ((rc = cluster_rows(c, d_emb, tidx, d, &X, &Xn, Zh))) return rc;
+    ClusterPlan p;
+    if ((rc = cluster_cut(c, Zh, N, X, d, spec, p, dumping ? &c->stash.clusters : nullptr))) return rc;
+    const int nl = p.nl;
     // a14: centroids of the final clusters (un-normalised train rows), cosine cdist of ALL rows, argmax
     double* d_cen2 = nullptr; double* d_soft = nullptr;
-    if ((rc = final_means(c, X, d, lab, nl, 0, order, off, &d_cen2))) return rc;
+    if ((rc = final_means(c, X, d, p.lab, nl, 0, p.order, p.off, &d_cen2))) return rc;
     std::vector<int64_t> counts((size_t)nl);
-    for (int k = 0; k < nl; ++k) counts[(size_t)k] = off[(size_t)k + 1] - off[(size_t)k];
-    if ((rc = assign_all(c, d_emb, M, d, d_cen2, nl, counts, hard, Kout, soft_best, &d_soft))) return rc;
+    for (int k = 0; k < nl; ++k) counts[(size_t)k] = p.off[(size_t)k + 1] - p.off[(size_t)k];
+    if ((rc = assign_all(c, d_emb, M, d, d_cen2, nl, counts, hard, Kout, soft_best, &d_soft, res))) return rc;
     if (dumping) {
         StepStash& S = c->stash;
-        S.clustered = true; S.N = N; S.K = nl; S.cluster_res = lab; S.hard_pre = hard;
+        S.clustered = true; S.N = N; S.K = nl; S.cluster_res = p.lab; S.hard_pre = hard;
         S.X.resize((size_t)N * d); S.Xn.resize((size_t)N * d); S.soft.resize((size_t)M * nl);
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipMemcpy(S.X.data(), X, S.X.size() * sizeof(double), hipMemcpyDeviceToHost));

@@ -13,6 +13,7 @@
 #include <initializer_list>
 #include <vector>
 #include "../../include/sdhip_test.h"
+#include "cluster_host.h"
 
 #define SD_T 501          // STFT frames per item (1 + 80000/160), sd.cpp:1980-2008
 #define SD_TP 501         // rows per item in activation buffers (= T: no padding rows; a 128-row tile may span two items)
@@ -154,14 +155,13 @@ struct StepStash {
     int64_t infer_items = 0;                   // items of the last shard_infer call (masks / counts workspaces describe them)
 };
 
-// what finalize leaves in the context for one recording of a sd_diarize_many* call (many.hip): sd_many_select puts it back
-struct ManyJob {
-    int status = SD_OK;
-    std::vector<double> conf, cen;
-    std::vector<int64_t> cen_counts;
-    int cen_K = 0, cen_d = 0;
-    std::vector<int32_t> enrolled;
-};
+// What the last job leaves for sd_last_confidence / sd_last_speakers / sd_last_enrolled, as one value (sd_ctx::last).  conf: per-turn confidence, written at
+// the end of finalize / sd_cut_turns_many.  The last clustering call (run_clustering, or the last cut): its cen_K final centroids [cen_K][cen_d] -- row k = raw
+// label k -- and the train rows of each; cen_K = 0 before any and after one that failed.  enrolled: their gallery rows, -1 (or absent) where nobody enrolled.
+struct JobResult { std::vector<double> conf, cen; std::vector<int64_t> cen_counts; int cen_K = 0, cen_d = 0; std::vector<int32_t> enrolled; };
+
+// one recording of a sd_diarize_many* call (many.hip): what finalize left in the context for it; sd_many_select puts it back
+struct ManyJob { int status = SD_OK; JobResult res; };
 
 struct sd_ctx {
     int device = 0;
@@ -219,12 +219,7 @@ struct sd_ctx {
     int clustering_method = SD_LINKAGE_CENTROID;
     double clustering_threshold = (double)0.7153814381597874f;      // the reference's float constant, widened
     int min_cluster_size = 15;
-    std::vector<double> last_conf;               // per-turn confidence of the last finalize (sd_last_confidence)
-    // the last clustering call (run_clustering): its K final centroids [K][last_cen_d] -- row k = raw label k -- and the train rows of each (sd_last_speakers); last_cen_K = 0 before any
-    std::vector<double> last_cen;
-    std::vector<int64_t> last_cen_counts;
-    int last_cen_K = 0, last_cen_d = 0;
-    std::vector<int32_t> last_enrolled;          // gallery row of every one of those K labels, -1 for a speaker nobody enrolled (sd_last_enrolled)
+    JobResult last;                             // the last job (sd_last_confidence, sd_last_speakers, sd_last_enrolled)
     // the enrolled gallery (sd_set_enrolled): the context's own device copy [enr_M][enr_d], the squared norms of its rows (k_row_sqnorms), and a host copy
     // for the candidate loop and the centroid table of run_clustering; enr_M = 0: none, and nothing of the clustering stage changes
     DevBuf enr_gal, enr_m2;
@@ -418,8 +413,10 @@ int f32_to_wav(sd_ctx* c, const float* h_wav, int64_t n, DevWav* out);
 inline void clear_stage_ms(sd_ctx* c) { for (double& ms : c->stage_ms) ms = 0; }
 // both networks on chunks [lo, hi) -> d_seg [hi-lo][293][3], d_emb [(hi-lo)*3][192]; seg_done: d_seg already holds the scores (stream.hip)
 int shard_infer(sd_ctx* c, const DevWav& w, int64_t lo, int64_t hi, float* d_seg, float* d_emb, bool seg_done = false);
+// the front of finalize, into buffers the caller names: binarised scores, active frames per row, the speaker count (d_count_avg may be null) and the
+// embeddings widened to f64 (sd.cpp:2555)
+int finalize_front(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, uint8_t* d_bin, int* d_nact, int32_t* d_count, double* d_count_avg, double* d_e64);
 int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, std::vector<sd_turn>& v);
-__global__ void k_f32_to_f64(const float* __restrict__ a, double* __restrict__ b, int64_t n);      // embeddings widened before clustering (sd.cpp:2555); grid GRID1(n)
 // the per-turn confidence of finalize (sdhip.h: sd_last_confidence) from the [chunks * 3] assignment behind the inactive rule and the best scores
 void turn_confidence(const std::vector<sd_turn>& v, const std::vector<int>& hard, const std::vector<double>& soft_best, int64_t chunks, std::vector<double>& conf);
 int turns_out(sd_ctx* c, const std::vector<sd_turn>& v, sd_turn** turns, int64_t* n_turns);
@@ -438,11 +435,9 @@ int sd_np_rint_host(double v);
 int64_t closest_frame_host(double w_start, double w_step, double w_dur, double t);
 // ---- linkage.hip
 int run_linkage(sd_ctx* c, const double* d_X, int64_t N, int d, double* d_Z, int method = SD_LINKAGE_CENTROID, int metric = SD_METRIC_EUCLIDEAN);
-int run_cluster_labels(sd_ctx* c, const double* d_X, int64_t N, int d, double cutoff, std::vector<int>& labels1, std::vector<double>* Zout = nullptr,
-                       int method = SD_LINKAGE_CENTROID, int metric = SD_METRIC_EUCLIDEAN);
+int run_linkage_host(sd_ctx* c, const double* d_X, int64_t N, int d, int method, int metric, std::vector<double>& Z);      // cluster.hip: run_linkage, Z on the host
 int run_clustering(sd_ctx* c, const double* d_emb /*[M][d] f64*/, int64_t M, int d, std::vector<int>& hard, int* K,
                    int num_clusters = -1, int min_clusters = -1, int max_clusters = -1, std::vector<double>* soft_best = nullptr);
-void fcluster_host(const std::vector<double>& Z, int64_t n, double cutoff, std::vector<int>& T);
 // ---- activity.hip
 int64_t activity_frames_host(int64_t chunks);                     // frames aggregate() yields for `chunks` chunks (sd.cpp:1232-1234)
 int64_t activity_rows_host(int64_t nf, int64_t n_samples);        // ... without those that lie wholly in the last chunk's zero padding
@@ -457,17 +452,14 @@ int run_speaker_dist(sd_ctx* c, const double* d_cen, int64_t K, const double* d_
 int run_gallery_norms(sd_ctx* c, const double* d_gal, int64_t M, int d, double* d_m2 /*[M]*/);      // asynchronous
 int run_nearest_gallery(sd_ctx* c, const double* d_E, const int* d_tidx /*[N] or null*/, int64_t N, const double* d_gal, const double* d_m2, int64_t M, int d,
                         int* d_best /*[N]*/, double* d_dist /*[N]*/);      // synchronises
-// ---- cluster.hip: the steps of run_clustering, for cut.hip, which walks the same flow once per cut of one dendrogram
-__global__ void k_cluster_means(const double* __restrict__ X, int d, const int* __restrict__ order, const int* __restrict__ off, double* __restrict__ cen);
-int cluster_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, int d, double** Xout, double** Xnout, std::vector<int>& lab, int* nlout, std::vector<double>* Zh);
-void group_by_label(const std::vector<int>& lab, int nl, std::vector<int>& order, std::vector<int>& off);
-void constrained_recut(const std::vector<double>& Z, int64_t N, double threshold, size_t mcs, int num_clusters, std::vector<int>& lab);
-void split_by_size(const std::vector<int>& off, int nl, size_t mcs, std::vector<int>& large, std::vector<int>& small);
-int reassign_small(sd_ctx* c, const double* X, int d, const std::vector<int>& order, const std::vector<int>& off, const std::vector<int>& large,
-                   const std::vector<int>& small, const double* enrolled, int G, std::vector<int>& lab, int& nl);
+// ---- cluster.hip: the steps of run_clustering that cut.hip shares: the front (train rows, X / Xn / dendrogram), the one finish of a cut, the centroids
+int train_rows(sd_ctx* c, const double* d_e64, int64_t M, int d, std::vector<int>& tidx);
+int cluster_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, int d, double** Xout, double** Xnout, std::vector<double>& Z);
+int cluster_cut(sd_ctx* c, const std::vector<double>& Z, int64_t N, const double* X, int d, const ClusterSpec& spec, ClusterPlan& p, std::vector<int>* first_cut);
+int mean_of_rows(sd_ctx* c, const double* d_emb, int d, const std::vector<int>& tidx, std::vector<double>& h_cen);
 int final_means(sd_ctx* c, const double* X, int d, const std::vector<int>& lab, int nl, int G, std::vector<int>& order, std::vector<int>& off, double** cen_out);
 int assign_all(sd_ctx* c, const double* d_emb, int64_t M, int d, const double* d_cen2, int K, const std::vector<int64_t>& counts,
-               std::vector<int>& hard, int* Kout, std::vector<double>* soft_best, double** soft_out);
+               std::vector<int>& hard, int* Kout, std::vector<double>* soft_best, double** soft_out, JobResult& res);
 // ---- cluster.hip: the three refusals of a call that clusters under an enrolled gallery (SD_ERR_ARG; nothing is touched); SD_OK without a gallery
 int enrolled_refusal(sd_ctx* c, int d, int num_clusters, int min_clusters, int max_clusters);
 // ---- reconstruct.hip

@@ -1,8 +1,7 @@
 // cut.hip -- many cuts of one dendrogram (sdhip.h: sd_cut_*; compiled with -ffp-contract=off like cluster.hip and reconstruct.hip, whose bits it must give).
 // A cut object holds everything of a finalize (pipeline.cpp) that does not depend on "clustering_threshold", "min_cluster_size" and "num_clusters":
-// scores, count, f64 embeddings, the gathered train rows and the dendrogram.  sd_cut_turns_many then walks run_clustering's flow (cluster.hip) once per
-// cut on the host -- with cluster.hip's own functions -- and runs the three stages that touch every embedding row or every frame ONCE for all cuts of
-// a group:
+// scores, count, f64 embeddings, the gathered train rows and the dendrogram.  sd_cut_turns_many then calls run_clustering's own finish of a cut
+// (cluster_cut, cluster.hip) once per cut and runs the three stages that touch every embedding row or every frame ONCE for all cuts of a group:
 //   k_assign_cuts        k_assign + k_mark_inactive: every row against the centroids of all cuts (one concatenated table), arg-max inside each cut's segment
 //   k_activations_cuts   k_activations for all cuts: act[t][f][k], K_t columns for cut t
 //   k_topk_cuts          k_topk for all cuts
@@ -172,25 +171,17 @@ static int cut_fill(sd_ctx* c, sd_cut* k, const float* d_seg, const float* d_emb
     HIPCHK(c, hipMemcpyAsync(k->seg.p, d_seg, seg_bytes, hipMemcpyDeviceToDevice, c->stream));
     WS(c, uint8_t, d_bin, "fin_bin", chunks * SD_FRAMES * 3);
     int rc;
-    if ((rc = run_postseg(c, k->seg.as<float>(), chunks, d_bin, nullptr, k->nact.as<int>()))) return rc;
-    if ((rc = run_count(c, d_bin, chunks, k->count.as<int32_t>(), nf))) return rc;
-    hipLaunchKernelGGL(k_f32_to_f64, GRID1(M * d), 0, c->stream, d_emb, k->e64.as<double>(), M * d);
-    KCHECK(c);
+    if ((rc = finalize_front(c, k->seg.as<float>(), d_emb, chunks, d_bin, k->nact.as<int>(), k->count.as<int32_t>(), nullptr, k->e64.as<double>()))) return rc;
     reconstruct_frames(chunks, nf, k->n, k->g);
     HIPCHK(c, hipMemcpyAsync(k->sfr.p, k->g.sfr.data(), (size_t)chunks * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    // a10: rows whose first element is not NaN (sd.cpp:2224)
-    std::vector<double> first((size_t)M);
     k->h_nact.resize((size_t)M);
-    HIPCHK(c, hipMemcpy2DAsync(first.data(), sizeof(double), k->e64.p, (size_t)d * sizeof(double), sizeof(double), (size_t)M, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(k->h_nact.data(), k->nact.p, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int64_t i = 0; i < M; ++i) if (!std::isnan(first[(size_t)i])) k->tidx.push_back((int)i);
+    if ((rc = train_rows(c, k->e64.as<double>(), M, d, k->tidx))) return rc;      // a10; its synchronisation carries h_nact too
     k->N = (int64_t)k->tidx.size();
     if (k->N < 1) return SD_OK;
-    // a10 - a12 through cluster.hip's own step: X, Xn and the dendrogram (its cut at the context's threshold is not kept)
+    // a10 - a12 through cluster.hip's own step: X, Xn and the dendrogram
     double* X = nullptr; double* Xn = nullptr;
-    std::vector<int> lab; int nl = 0;
-    if ((rc = cluster_rows(c, k->e64.as<double>(), k->tidx, d, &X, &Xn, lab, &nl, &k->Z))) return rc;
+    if ((rc = cluster_rows(c, k->e64.as<double>(), k->tidx, d, &X, &Xn, k->Z))) return rc;
     const size_t xb = (size_t)k->N * d * sizeof(double);
     if (k->X.reserve(xb) || k->Xn.reserve(xb)) SD_FAIL(c, SD_ERR_HIP, "sd_cut_open: hipMalloc of the cut's buffers failed");
     HIPCHK(c, hipMemcpyAsync(k->X.p, X, xb, hipMemcpyDeviceToDevice, c->stream));
@@ -250,62 +241,16 @@ extern "C" int sd_cut_info(const sd_cut* k, int64_t* chunks, int64_t* n_samples,
 // ---------------------------------------------------------------- evaluate
 namespace {
 struct CutJob {
-    double thr = 0; int mcs_opt = 0, num_clusters = -1;       // the three options, resolved
-    bool trivial = false;                                     // run_clustering's "all zeros" exit (sd.cpp:2081-2088): one cluster, no centroid table
-    std::vector<int> lab, order, off;                         // labels of the train rows behind the small -> large pass, nl of them; membership
-    int nl = 1;
+    ClusterSpec spec;                                         // the three options, resolved, and the context's min_clusters / max_clusters
+    ClusterPlan p;                                            // cluster_cut's: trivial (one cluster, no centroid table), else the nl final labels of the train rows
     std::vector<int> hard;                                    // [M] behind the inactive rule
     std::vector<double> best;                                 // [M]
     int Kr = 1;                                               // label columns of the reconstruction (sd.cpp:2803-2812)
     std::vector<sd_turn> turns;
 };
 
-// run_clustering's flow from set_num_clusters to the small -> large pass, on the cut's dendrogram
-int cut_labels(sd_cut* k, CutJob& j)
-{
-    sd_ctx* c = k->c;
-    const int64_t N = k->N;
-    int num_clusters = j.num_clusters, min_clusters = c->min_clusters, max_clusters = c->max_clusters;
-    // set_num_clusters (sd.cpp:2261-2296; Clustering.py:27-41)
-    const bool constrained = (num_clusters != -1) || (min_clusters != -1) || (max_clusters != -1);
-    if (num_clusters != -1) { min_clusters = num_clusters; max_clusters = num_clusters; }
-    if (min_clusters == -1) min_clusters = 1;
-    if (max_clusters == -1) max_clusters = (int)N;
-    min_clusters = std::max(1, std::min((int)N, min_clusters));
-    max_clusters = std::max(1, std::min((int)N, max_clusters));
-    if (min_clusters > max_clusters) min_clusters = max_clusters;
-    if (N < 2 || max_clusters < 2) { j.trivial = true; j.nl = 1; return SD_OK; }
-    fcluster_host(k->Z, N, j.thr, j.lab);                                            // a13
-    int nl = 0;
-    for (auto& v : j.lab) { v -= 1; if (v + 1 > nl) nl = v + 1; }
-    const size_t mcs = std::min<size_t>((size_t)j.mcs_opt, std::max<size_t>(1, (size_t)std::round(0.1 * (double)N)));     // sd.cpp:2308, Clustering.py:309-311
-    group_by_label(j.lab, nl, j.order, j.off);
-    if (constrained) {
-        int nlarge0 = 0;
-        for (int q = 0; q < nl; ++q) if ((size_t)(j.off[(size_t)q + 1] - j.off[(size_t)q]) >= mcs) nlarge0++;
-        int target = (min_clusters == max_clusters) ? min_clusters : -1;
-        if (nlarge0 < min_clusters) target = min_clusters;                           // sd.cpp:2361-2366
-        if (nlarge0 > max_clusters) target = max_clusters;
-        if (target != -1) {
-            constrained_recut(k->Z, N, j.thr, mcs, target, j.lab);
-            nl = 0;
-            for (int v : j.lab) if (v + 1 > nl) nl = v + 1;
-            group_by_label(j.lab, nl, j.order, j.off);
-        }
-    }
-    std::vector<int> large, small;
-    split_by_size(j.off, nl, mcs, large, small);
-    if (large.empty()) { std::fill(j.lab.begin(), j.lab.end(), 0); nl = 1; }         // sd.cpp:2371-2375
-    else if (!small.empty()) { if (int rc = reassign_small(c, k->X.as<double>(), SD_EMB_DIM, j.order, j.off, large, small, nullptr, 0, j.lab, nl)) return rc; }
-    j.nl = nl;
-    return SD_OK;
-}
-
-// what sd_last_speakers describes behind a cut
-struct LastSpeakers { std::vector<double> cen; std::vector<int64_t> counts; };
-
 // the cuts [g0, g1) of one group: assignment, activations, top-k and the copy back once for all of them, then the turns of each
-int cut_group(sd_cut* k, std::vector<CutJob>& jobs, size_t g0, size_t g1, LastSpeakers* last /* non-null: jobs[g1 - 1] is the last cut of the call */)
+int cut_group(sd_cut* k, std::vector<CutJob>& jobs, size_t g0, size_t g1, JobResult* last /* non-null: jobs[g1 - 1] is the last cut of the call; its centroid part is filled */)
 {
     sd_ctx* c = k->c;
     const int d = SD_EMB_DIM;
@@ -317,7 +262,7 @@ int cut_group(sd_cut* k, std::vector<CutJob>& jobs, size_t g0, size_t g1, LastSp
     for (int t = 0; t < Tg; ++t) {
         CutJob& j = jobs[g0 + (size_t)t];
         j.hard.assign((size_t)M, 0); j.best.assign((size_t)M, NAN);
-        if (!j.trivial) nontriv.push_back(t);
+        if (!j.p.trivial) nontriv.push_back(t);
     }
     const bool constrained_assign = c->constrained_assignment && (M % SD_SPEAKERS) == 0;
     const double* X = k->X.as<double>();
@@ -325,13 +270,13 @@ int cut_group(sd_cut* k, std::vector<CutJob>& jobs, size_t g0, size_t g1, LastSp
     if (!nontriv.empty() && !constrained_assign) {
         const int Tn = (int)nontriv.size();
         std::vector<int> coff((size_t)Tn + 1, 0);
-        for (int q = 0; q < Tn; ++q) coff[(size_t)q + 1] = coff[(size_t)q] + jobs[g0 + (size_t)nontriv[(size_t)q]].nl;
+        for (int q = 0; q < Tn; ++q) coff[(size_t)q + 1] = coff[(size_t)q] + jobs[g0 + (size_t)nontriv[(size_t)q]].p.nl;
         const int total = coff[(size_t)Tn];
         WS(c, double, d_cen, "cl_cen", (size_t)total * d);                           // the whole table first: final_means then fills it cut by cut without moving it
         for (int q = 0; q < Tn; ++q) {
             CutJob& j = jobs[g0 + (size_t)nontriv[(size_t)q]];
             double* cen = nullptr;
-            if ((rc = final_means(c, X, d, j.lab, j.nl, coff[(size_t)q], j.order, j.off, &cen))) return rc;
+            if ((rc = final_means(c, X, d, j.p.lab, j.p.nl, coff[(size_t)q], j.p.order, j.p.off, &cen))) return rc;
             if (cen != d_cen) SD_FAIL(c, SD_ERR_HIP, "sd_cut_turns_many: the centroid table moved");
         }
         WS(c, double, d_m2, "cut_m2", total);
@@ -356,8 +301,8 @@ int cut_group(sd_cut* k, std::vector<CutJob>& jobs, size_t g0, size_t g1, LastSp
             HIPCHK(c, hipMemcpyAsync(j.best.data(), d_best + (size_t)q * M, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         }
         HIPCHK(c, hipMemcpyAsync(&herr, d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        if (last && !jobs[g1 - 1].trivial) {
-            last->cen.resize((size_t)jobs[g1 - 1].nl * d);
+        if (last && !jobs[g1 - 1].p.trivial) {
+            last->cen.resize((size_t)jobs[g1 - 1].p.nl * d);
             HIPCHK(c, hipMemcpyAsync(last->cen.data(), d_cen + (size_t)coff[(size_t)Tn - 1] * d, last->cen.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         }
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -365,40 +310,30 @@ int cut_group(sd_cut* k, std::vector<CutJob>& jobs, size_t g0, size_t g1, LastSp
     }
     for (int t = 0; t < Tg; ++t) {
         CutJob& j = jobs[g0 + (size_t)t];
-        if (!j.trivial && !constrained_assign) continue;
-        if (!j.trivial) {                                                            // the constrained arg-max needs the whole score table: cut by cut through assign_all
+        if (!j.p.trivial && !constrained_assign) continue;
+        if (!j.p.trivial) {                                                          // the constrained arg-max needs the whole score table: cut by cut through assign_all
             double* cen = nullptr;
-            if ((rc = final_means(c, X, d, j.lab, j.nl, 0, j.order, j.off, &cen))) return rc;
-            std::vector<int64_t> counts((size_t)j.nl);
-            for (int q = 0; q < j.nl; ++q) counts[(size_t)q] = j.off[(size_t)q + 1] - j.off[(size_t)q];
-            if ((rc = assign_all(c, e64, M, d, cen, j.nl, counts, j.hard, nullptr, &j.best, nullptr))) return rc;
-            if (last && t == Tg - 1) last->cen = c->last_cen;
+            if ((rc = final_means(c, X, d, j.p.lab, j.p.nl, 0, j.p.order, j.p.off, &cen))) return rc;
+            std::vector<int64_t> counts((size_t)j.p.nl);
+            for (int q = 0; q < j.p.nl; ++q) counts[(size_t)q] = j.p.off[(size_t)q + 1] - j.p.off[(size_t)q];
+            JobResult one;                                                           // the centroids of a cut that is not the call's last are not kept
+            if ((rc = assign_all(c, e64, M, d, cen, j.p.nl, counts, j.hard, nullptr, &j.best, nullptr, (last && t == Tg - 1) ? *last : one))) return rc;
         }
         for (int64_t i = 0; i < M; ++i) if (k->h_nact[(size_t)i] == 0) j.hard[(size_t)i] = -2;      // sd.cpp:3172-3191
         HIPCHK(c, hipMemcpyAsync(d_hard + (size_t)t * M, j.hard.data(), (size_t)M * sizeof(int), hipMemcpyHostToDevice, c->stream));
     }
     if (last) {
         CutJob& j = jobs[g1 - 1];
-        if (j.trivial) {
-            // one cluster, label 0: the mean of the train rows by the rule of a14 (a NaN row with count 0 when there is none), as run_clustering leaves it
-            last->cen.assign((size_t)d, NAN);
-            last->counts.assign(1, k->N);
-            if (k->N > 0) {
-                const int off1[2] = {0, (int)k->N};
-                WS(c, int, d_order1, "cl_order", k->N);
-                WS(c, int, d_off1, "cl_off", 2);
-                WS(c, double, d_cen1, "cut_cen1", (size_t)d);
-                HIPCHK(c, hipMemcpyAsync(d_order1, k->tidx.data(), (size_t)k->N * sizeof(int), hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipMemcpyAsync(d_off1, off1, sizeof(off1), hipMemcpyHostToDevice, c->stream));
-                hipLaunchKernelGGL(k_cluster_means, dim3(1), dim3(((d + 63) / 64) * 64), 0, c->stream, e64, d, d_order1, d_off1, d_cen1);
-                KCHECK(c);
-                HIPCHK(c, hipMemcpyAsync(last->cen.data(), d_cen1, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-            }
+        if (j.p.trivial) {
+            // one cluster, label 0: the mean of the train rows (a NaN row with count 0 when there is none), as run_clustering leaves it
+            last->cen_counts.assign(1, k->N);
+            if ((rc = mean_of_rows(c, e64, d, k->tidx, last->cen))) return rc;
         } else {
-            last->counts.resize((size_t)j.nl);
-            for (int q = 0; q < j.nl; ++q) last->counts[(size_t)q] = j.off[(size_t)q + 1] - j.off[(size_t)q];
+            last->cen_counts.resize((size_t)j.p.nl);
+            for (int q = 0; q < j.p.nl; ++q) last->cen_counts[(size_t)q] = j.p.off[(size_t)q + 1] - j.p.off[(size_t)q];
         }
+        last->cen_d = d;
+        last->cen_K = (int)last->cen_counts.size();
     }
     // a15 - a17 for all cuts: column counts, activations, top-k, one copy back
     std::vector<int> koff((size_t)Tg + 1, 0);
@@ -453,24 +388,25 @@ int cut_turns_many(sd_cut* k, const sd_cut_spec* specs, int64_t T, sd_turn** tur
     for (int64_t t = 0; t < T; ++t) {
         const sd_cut_spec& s = specs[t];
         CutJob& j = jobs[(size_t)t];
-        if (s.threshold != s.threshold) j.thr = c->clustering_threshold;
-        else if (s.threshold >= 0.0 && s.threshold <= 2.0) j.thr = s.threshold;
+        if (s.threshold != s.threshold) j.spec.threshold = c->clustering_threshold;
+        else if (s.threshold >= 0.0 && s.threshold <= 2.0) j.spec.threshold = s.threshold;
         else SD_FAIL(c, SD_ERR_ARG, "sd_cut_turns_many: spec %lld: the threshold must lie in [0, 2] (NaN = the context's)", (long long)t);
         if (s.min_cluster_size < 0) SD_FAIL(c, SD_ERR_ARG, "sd_cut_turns_many: spec %lld: min_cluster_size must be at least 1 (0 = the context's)", (long long)t);
-        j.mcs_opt = s.min_cluster_size == 0 ? c->min_cluster_size : s.min_cluster_size;
+        j.spec.min_cluster_size = s.min_cluster_size == 0 ? c->min_cluster_size : s.min_cluster_size;
         if (s.num_clusters < -1) SD_FAIL(c, SD_ERR_ARG, "sd_cut_turns_many: spec %lld: num_clusters must be -1 (unset), 0 (the context's) or a count", (long long)t);
-        j.num_clusters = s.num_clusters == 0 ? c->num_clusters : s.num_clusters;
+        j.spec.num_clusters = s.num_clusters == 0 ? c->num_clusters : s.num_clusters;
+        j.spec.min_clusters = c->min_clusters; j.spec.max_clusters = c->max_clusters;
     }
     for (int64_t t = 0; t < T; ++t) { turns[t] = nullptr; n_turns[t] = 0; if (K) K[t] = 0; }
     int rc;
-    for (CutJob& j : jobs) if ((rc = cut_labels(k, j))) return rc;
+    for (CutJob& j : jobs) if ((rc = cluster_cut(c, k->Z, k->N, k->X.as<double>(), SD_EMB_DIM, j.spec, j.p, nullptr))) return rc;
     // groups: the longest runs of consecutive cuts whose activation tables [nact][nl] (nl bounds the label columns) fit the budget
-    LastSpeakers last;
+    JobResult last;                                                                  // committed once, at the end: a call that fails leaves the context's record alone
     const double budget = (double)(c->cut_group_bytes > 0 ? c->cut_group_bytes : 1);
     for (size_t g0 = 0; g0 < jobs.size();) {
         size_t g1 = g0; double bytes = 0;
         while (g1 < jobs.size()) {
-            const double b = (double)k->g.nact * jobs[g1].nl * sizeof(double);
+            const double b = (double)k->g.nact * jobs[g1].p.nl * sizeof(double);
             if (g1 > g0 && bytes + b > budget) break;
             bytes += b; ++g1;
         }
@@ -480,9 +416,8 @@ int cut_turns_many(sd_cut* k, const sd_cut_spec* specs, int64_t T, sd_turn** tur
     // the context describes cut T - 1 as after that finalize (sd_last_speakers, sd_last_enrolled, sd_last_confidence)
     const CutJob& jl = jobs.back();
     c->stash.clustered = false;
-    c->last_enrolled.clear();
-    c->last_cen = last.cen; c->last_cen_counts = last.counts; c->last_cen_d = SD_EMB_DIM; c->last_cen_K = (int)last.counts.size();
-    turn_confidence(jl.turns, jl.hard, jl.best, k->chunks, c->last_conf);
+    turn_confidence(jl.turns, jl.hard, jl.best, k->chunks, last.conf);
+    c->last = std::move(last);                                                       // (enrolled stays empty: a cut refuses a gallery)
     for (int64_t t = 0; t < T; ++t) {
         if ((rc = turns_out(c, jobs[(size_t)t].turns, &turns[t], &n_turns[t]))) { for (int64_t q = 0; q < t; ++q) { free(turns[q]); turns[q] = nullptr; n_turns[q] = 0; } return rc; }
         if (K) K[t] = jobs[(size_t)t].Kr;

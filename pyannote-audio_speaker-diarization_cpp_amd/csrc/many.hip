@@ -191,8 +191,7 @@ static int many_run(sd_ctx* c, const void* const* src, int form, const int64_t* 
         if (rc == SD_ERR_NUMERIC) continue;                    // this recording's clustering; the others go on
         if (rc == SD_OK) rc = turns_out(c, v, &turns[r], &n_turns[r]);
         if (rc) { give_back(); return rc; }
-        job.conf = c->last_conf; job.cen = c->last_cen; job.cen_counts = c->last_cen_counts;
-        job.cen_K = c->last_cen_K; job.cen_d = c->last_cen_d; job.enrolled = c->last_enrolled;
+        job.res = c->last;
     }
     c->stage_ms[3] = now_ms() - t0;
     return SD_OK;
@@ -223,7 +222,6 @@ extern "C" int sd_many_select(sd_ctx* c, int64_t r)
     if (r < 0 || r >= (int64_t)c->many_jobs.size()) SD_FAIL(c, SD_ERR_ARG, "sd_many_select: the last sd_diarize_many* call of this context had %zu recordings", c->many_jobs.size());
     const ManyJob& job = c->many_jobs[(size_t)r];
     if (job.status != SD_OK) SD_FAIL(c, SD_ERR_ARG, "sd_many_select: recording %lld ended with status %d and left no job", (long long)r, job.status);
-    c->last_conf = job.conf; c->last_cen = job.cen; c->last_cen_counts = job.cen_counts;
-    c->last_cen_K = job.cen_K; c->last_cen_d = job.cen_d; c->last_enrolled = job.enrolled;
+    c->last = job.res;
     return SD_OK;
 }

@@ -148,9 +148,9 @@ extern "C" int sd_cluster_ex(sd_ctx* c, const double* h_X, int64_t N, int d, int
     if (int rc = check_method_metric(c, method, metric)) return rc;
     DTMP(c, dx, N * d * sizeof(double));
     HIPCHK(c, hipMemcpy(dx.p, h_X, N * d * sizeof(double), hipMemcpyHostToDevice));
-    std::vector<int> lab;
-    int rc = run_cluster_labels(c, (const double*)dx.p, N, d, cutoff, lab, nullptr, method, metric);
-    if (rc) return rc;
+    std::vector<double> Z; std::vector<int> lab;
+    if (int rc = run_linkage_host(c, (const double*)dx.p, N, d, method, metric, Z)) return rc;
+    fcluster_host(Z, N, cutoff, lab);
     for (int64_t i = 0; i < N; ++i) h_labels1[i] = lab[(size_t)i];
     return SD_OK;
 }
@@ -317,6 +317,17 @@ void turn_confidence(const std::vector<sd_turn>& v, const std::vector<int>& hard
     }
 }
 
+int finalize_front(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, uint8_t* d_bin, int* d_nact, int32_t* d_count, double* d_count_avg, double* d_e64)
+{
+    const int64_t M = chunks * SD_SPEAKERS;
+    int rc;
+    if ((rc = run_postseg(c, d_seg, chunks, d_bin, nullptr, d_nact))) return rc;
+    if ((rc = run_count(c, d_bin, chunks, d_count, count_frames_host(chunks), d_count_avg))) return rc;
+    hipLaunchKernelGGL(k_f32_to_f64, GRID1(M * SD_EMB_DIM), 0, c->stream, d_emb, d_e64, M * SD_EMB_DIM);
+    KCHECK(c);
+    return SD_OK;
+}
+
 int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, std::vector<sd_turn>& v)
 {
     int rc;
@@ -329,12 +340,9 @@ int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, 
     WS(c, int32_t, d_count, "fin_count", nf);
     WS(c, double, d_e64, "fin_e64", M * SD_EMB_DIM);
     WS(c, int, d_hard, "fin_hard", M);
-    if ((rc = run_postseg(c, d_seg, chunks, d_bin, nullptr, d_nact))) return rc;
     double* d_count_avg = nullptr;
     if (!c->dump_dir.empty()) { WS(c, double, t_avg, "fin_count_avg", nf); d_count_avg = t_avg; }
-    if ((rc = run_count(c, d_bin, chunks, d_count, nf, d_count_avg))) return rc;
-    hipLaunchKernelGGL(k_f32_to_f64, GRID1(M * SD_EMB_DIM), 0, c->stream, d_emb, d_e64, M * SD_EMB_DIM);
-    KCHECK(c);
+    if ((rc = finalize_front(c, d_seg, d_emb, chunks, d_bin, d_nact, d_count, d_count_avg, d_e64))) return rc;
     std::vector<int> hard; int K = 1;
     std::vector<double> soft_best;
     if ((rc = run_clustering(c, d_e64, M, SD_EMB_DIM, hard, &K, c->num_clusters, c->min_clusters, c->max_clusters, &soft_best))) return rc;
@@ -353,7 +361,7 @@ int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, 
         if (rc) return rc;
     }
     { KernelStat& ks = c->stats["clusters_K"]; ks.launches++; ks.flops += (double)Kr; ks.bytes += (double)v.size(); }       // bench: K and turns per job
-    turn_confidence(v, hard, soft_best, chunks, c->last_conf);
+    turn_confidence(v, hard, soft_best, chunks, c->last.conf);
     c->stage_ms[2] += now_ms() - t0;
     return SD_OK;
 }
