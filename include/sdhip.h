@@ -288,6 +288,28 @@ int sd_stream_read(sd_stream*, int64_t chunk_lo, int64_t chunk_hi, float* h_seg,
 void sd_stream_close(sd_stream*);
 /* host-only: the sealed chunks of an n_samples-sample recording, 32 * (full / 32) as above (slide()'s chunk rule, sd.cpp:1419, 1457) */
 int64_t sd_stream_sealed_chunks(int64_t n_samples);
+/* ---- many live recordings at once: S streams of ONE context in one call, for a caller with dozens of calls in progress on one card.  Every stream
+ * keeps its contract: after any sequence of single and group calls its turns, labels, confidences, centroids and cached rows are the bytes it gives
+ * when it is driven alone, which are those of sd_diarize of everything pushed to it.  The networks run once per call over a pack of the streams'
+ * ranges -- a block that became sealed, or the pending chunks [sealed, total) -- laid out by sd_many_plan's rule (a range of c chunks gets a slot of
+ * roundup32(c + 9) chunks), so the ranges share the segmentation batches and the embedding batches.
+ * sd_stream_push_many*: n[i] samples for stream s[i], as for sd_stream_push / _dev / _f32; n[i] == 0 with any pointer is legal and gives that stream
+ * nothing.  One upload, one conversion launch and one synchronisation for all of them; every block that became sealed in any stream (two or more
+ * in one stream included) is inferred in one packed inference, and sd_stream_info of every stream says what it says after the single push.
+ * sd_stream_turns_many: the pending range of every stream with samples pushed since its last turns is inferred in one packed inference, then
+ * every stream is finalized in the order of the list under the context's current options, an enrolled gallery included.  status[i] = SD_OK,
+ * SD_ERR_SHORT (no chunk yet; turns[i] = NULL) or SD_ERR_NUMERIC from that stream's clustering (turns[i] = NULL); the other streams go on and the
+ * call returns SD_OK.  Any other failure ends the call and nothing stays allocated to the caller.  Afterwards sd_many_select(ctx, i) makes stream i
+ * the job that sd_last_confidence, sd_last_speakers and sd_last_enrolled describe.
+ * Refused with SD_ERR_ARG before anything is touched: a null array, S < 1, a null stream, a null sample pointer with n[i] > 0, a negative n[i], the
+ * same stream twice, streams of different contexts, a stream that is unusable after SD_ERR_HIP, a stream opened under another precision than the
+ * context has now, a planted workload (its chunk range means one recording), a pack of more than SD_MANY_MAX_CHUNKS chunks, and for
+ * sd_stream_turns_many a dump directory and the refusals of an enrolled gallery.  SD_ERR_HIP in the middle of a call makes every stream of the
+ * call unusable.  sd_stage_ms: as for sd_stream_push and sd_stream_turns, [2] = the sum of the finalizes. */
+int sd_stream_push_many(sd_stream* const* s /*[S]*/, const int16_t* const* h_pcm /*[S]*/, const int64_t* n /*[S]*/, int64_t S);     /* sd.cpp:2937-3234, 2950 */
+int sd_stream_push_many_dev(sd_stream* const* s /*[S]*/, const int16_t* const* d_pcm /*[S]*/, const int64_t* n /*[S]*/, int64_t S);     /* sd.cpp:2937-3234, 2950 */
+int sd_stream_push_many_f32(sd_stream* const* s /*[S]*/, const float* const* h_wav /*[S]*/, const int64_t* n /*[S]*/, int64_t S);     /* sd.cpp:2937-3234, 2948-2951 */
+int sd_stream_turns_many(sd_stream* const* s /*[S]*/, int64_t S, sd_turn** turns /*[S]*/, int64_t* n_turns /*[S]*/, int32_t* status /*[S]*/);     /* sd.cpp:2937-3234 */
 
 /* ---- known speakers: cluster numbers mean nothing outside one call; these entries give the clusters an identity that lasts.  The centroids that
  * assign_embeddings builds (sd.cpp:2149-2167; what pyannote hands out with return_embeddings=True, Clustering.py:97-164) come out of the last job, a
@@ -384,9 +406,9 @@ int sd_last_enrolled(const sd_ctx*, int32_t* h_rows /*[cap]*/, int64_t cap, int6
  * (none when chunks_r <= 0) at chunk_base[r] = the sum of the earlier slots; *total_chunks = the sum of all slots.  Its samples sit at sample
  * 8000 * chunk_base[r] of the packed waveform with zeros behind them up to the end of the slot, which lies at or behind the end of its last
  * chunk's 80 000-sample window; every base is a multiple of 32 chunks = 3 reference embedding batches (sd.cpp:2429).
- * sd_many_select: makes recording r of the last sd_diarize_many* call of this ctx "the last job" for sd_last_confidence, sd_last_speakers and
- * sd_last_enrolled (after the call itself that is the last recording that was finalized); SD_ERR_ARG for an r outside the call or one whose
- * status is not SD_OK. */
+ * sd_many_select: makes recording r of the last sd_diarize_many* call of this ctx -- or stream r of its last sd_stream_turns_many call, whichever
+ * of the two came later -- "the last job" for sd_last_confidence, sd_last_speakers and sd_last_enrolled (after the call itself that is the last
+ * recording that was finalized); SD_ERR_ARG for an r outside the call or one whose status is not SD_OK. */
 #define SD_MANY_MAX_CHUNKS 357199
 int sd_many_plan(const int64_t* n, int64_t R, int64_t* chunk_base /*[R]*/, int64_t* total_chunks);     /* sd.cpp:1419, 1457, 2429 */
 int sd_diarize_many(sd_ctx*, const int16_t* const* h_pcm /*[R]*/, const int64_t* n /*[R]*/, int64_t R, sd_turn** turns /*[R]*/, int64_t* n_turns /*[R]*/, int32_t* status /*[R]*/);     /* sd.cpp:2937-3234 */

@@ -247,7 +247,7 @@ struct sd_ctx {
     const float* planted_scores = nullptr;      // sd_set_planted: measurement / test hook
     const float* planted_emb = nullptr;
     int64_t planted_lo = 0, planted_n = 0;
-    std::vector<ManyJob> many_jobs;             // per recording of the last sd_diarize_many* call (sd_many_select)
+    std::vector<ManyJob> many_jobs;             // per recording of the last sd_diarize_many* call, or per stream of the last sd_stream_turns_many (sd_many_select)
     std::vector<sd_stream*> streams;            // open sd_stream objects of this context (stream.hip); sd_destroy closes what is left
     std::vector<sd_cut*> cuts;                  // open sd_cut objects of this context (cut.hip); sd_destroy closes what is left
     int64_t cut_group_bytes = (int64_t)1 << 30; // sd_cut_turns_many: bytes the activation tables of one group of cuts may take (test key)
@@ -420,6 +420,17 @@ int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, 
 // the per-turn confidence of finalize (sdhip.h: sd_last_confidence) from the [chunks * 3] assignment behind the inactive rule and the best scores
 void turn_confidence(const std::vector<sd_turn>& v, const std::vector<int>& hard, const std::vector<double>& soft_best, int64_t chunks, std::vector<double>& conf);
 int turns_out(sd_ctx* c, const std::vector<sd_turn>& v, sd_turn** turns, int64_t* n_turns);
+// ---- many.hip: both networks once over a pack of slots (many_plan.h).  sd_diarize_many* packs recordings, stream.hip the ranges of a group of streams
+struct ManyRow { const void* src; int64_t n, base, len; };      // src[0, n) -> dst[base, base + n), zeros in dst[base + n, base + len)
+struct ManyGap { int64_t first, count; };                         // chunks [first, first + count) belong to nobody
+// one slot: a recording, or chunks [lo, lo + chunks) of a stream whose audio from sample lo * 8000 on is what the slot holds.  n, chunks, full and
+// last_len describe the slot's n samples as a recording of its own (sd_chunk_rule); its first `tile` full chunks are on the tile side of PyanNet's
+// dense layers in the path the slot has to equal, the other full ones on the skinny side in batches of seg_batch_chunks (many.hip: many_segment)
+struct PackRange { int64_t n, chunks, base, full, last_len, tile, lo; };
+dim3 many_grid(int64_t longest, int64_t table);      // x: a stride over the longest row of a table, y: a stride over the table; 256 threads
+// rows: one per slot that has a chunk, src on the device (is_f32: float samples, else 16-bit); total = many_plan's.  Leaves the scores [total][293][3]
+// and embeddings [total * 3][192] of the pack in workspaces; stage_ms[0] and [1] are counted from t0
+int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vector<PackRange>& rec, int64_t total, double t0, float** seg_out, float** emb_out);
 // ---- cut.hip: the tail of the sd_cut_open* entries (sdhip.h, "many cuts of one dendrogram"); refuses a gallery and a dump directory itself
 int cut_refusal(sd_ctx* c, const char* who);
 int cut_open_dev(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, sd_cut** out);

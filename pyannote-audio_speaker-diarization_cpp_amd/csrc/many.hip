@@ -7,12 +7,11 @@
 //   k_many_pack       one launch: the samples of every recording into its slot (16-bit: x 1/32768 as k_pcm_to_f32; f32: copied), zeros behind them
 //   k_many_gap_masks  one launch: zero mask rows for the gap chunks of every slot
 // Both walk a table indexed by recording; every store is guarded by the row's own slot length and by the length of the destination.
+// pack_infer, the inference over a filled table, is shared with the group calls of stream.hip, whose slots hold ranges of streams.
 #include "common.h"
 #include "many_plan.h"
 #include <algorithm>
-
-struct ManyRow { const void* src; int64_t n, base, len; };      // src[0, n) -> dst[base, base + n), zeros in dst[base + n, base + len)
-struct ManyGap { int64_t first, count; };                         // chunks [first, first + count) belong to nobody
+#include <utility>
 
 // grid (x: a stride over the samples of a slot, y: a stride over the table), 256 threads
 __global__ void k_many_pack(const ManyRow* __restrict__ rows, int R, int is_f32, float* __restrict__ dst, int64_t dst_len)
@@ -39,7 +38,7 @@ __global__ void k_many_gap_masks(const ManyGap* __restrict__ gaps, int G, float*
     }
 }
 
-static dim3 many_grid(int64_t longest, int64_t table)
+dim3 many_grid(int64_t longest, int64_t table)
 {
     const int64_t gx = std::min<int64_t>(std::max<int64_t>((longest + 255) / 256, 1), 2048), gy = std::min<int64_t>(std::max<int64_t>(table, 1), 1024);
     return dim3((unsigned)gx, (unsigned)gy);
@@ -61,20 +60,30 @@ extern "C" int sd_many_plan(const int64_t* n, int64_t R, int64_t* chunk_base, in
 //   skinny side  chunks [T_r, full_r): the batches of the single path, one recording at a time (a batch of at most 13 chunks has no room for more);
 //   short last chunk (sd.cpp:1457-1480): the single path's own call on a view of the slot -- its frame count depends on its length, and the shared
 //                first convolution the single path takes for it is not the per-row form of run_segment_rows bit for bit (tests/test_next_rows.py)
-struct ManyRec { int64_t n, chunks, base, full, last_len; };
 #define MANY_SKINNY_CHUNKS (SD_SKINNY_MAX_ROWS / SD_FRAMES)
 #define MANY_JOIN_CHUNKS 256      /* tile ranges at most this far apart are one range: up to 4096 chunks are one wave of LSTM workgroups, a launch sequence more costs more */
 
-static int many_segment(sd_ctx* c, const float* d_pack, int64_t total, const std::vector<ManyRec>& rec, float* d_seg)
+// the side of the full chunks of a recording in the loop of single calls: the batches of seg_batch_chunks from chunk 0 on, the last one on the skinny
+// side when it has 13 chunks or fewer (stream_book.h: group_tile_chunks states the same rule, and a stream's exception to it)
+static int64_t many_tile_chunks(int64_t full, int64_t cb)
+{
+    const int64_t rem = full % cb;
+    return cb <= MANY_SKINNY_CHUNKS ? 0 : ((rem == 0 || rem > MANY_SKINNY_CHUNKS) ? full : full - rem);
+}
+
+// A slot of a stream's range (q.lo > 0, stream.hip) differs in two things.  Its tile side is what the caller says, and can be shorter than 14 chunks
+// (1 .. 13 pending chunks behind sealed ones): such a range reaches FORWARD into the zero chunks of its own slot -- at least 19 of them -- and the
+// rows it computes there are the slot's gap rows, or the row the short last chunk's own call writes afterwards.  And its short last chunk is chunk
+// lo + chunks - 1 of a recording that holds samples from lo * 8000 on: the view says so, as the stream's own tail does.
+static int many_segment(sd_ctx* c, const float* d_pack, int64_t total, const std::vector<PackRange>& rec, float* d_seg)
 {
     const size_t row = (size_t)SD_FRAMES * 3;
     const int64_t cb = c->seg_batch_chunks < 1 ? 1 : c->seg_batch_chunks;
     const DevWav pack{d_pack, total * (int64_t)SD_HOP, 0, true};      // sd_num_chunks of it = total - 9 full chunks and no short one: every real chunk is among them
     std::vector<std::pair<int64_t, int64_t>> tile, skinny;
-    for (const ManyRec& q : rec) {
+    for (const PackRange& q : rec) {
         if (q.chunks <= 0) continue;
-        const int64_t rem = q.full % cb;
-        const int64_t T = cb <= MANY_SKINNY_CHUNKS ? 0 : ((rem == 0 || rem > MANY_SKINNY_CHUNKS) ? q.full : q.full - rem);
+        const int64_t T = q.tile;
         if (T > 0) {
             if (!tile.empty() && q.base - tile.back().second <= MANY_JOIN_CHUNKS) tile.back().second = q.base + T;
             else tile.emplace_back(q.base, q.base + T);
@@ -85,16 +94,65 @@ static int many_segment(sd_ctx* c, const float* d_pack, int64_t total, const std
     for (const auto& t : tile)
         for (int64_t k = t.first; k < t.second; k += cb) {
             int64_t lo = k, hi = std::min(t.second, k + cb);
-            if (hi - lo <= MANY_SKINNY_CHUNKS) lo = hi - (MANY_SKINNY_CHUNKS + 1);      // the rest of a range: reaches back into chunks already computed (same bits) to stay on the tile side
+            if (hi - lo <= MANY_SKINNY_CHUNKS) {
+                if (hi - (MANY_SKINNY_CHUNKS + 1) >= t.first) lo = hi - (MANY_SKINNY_CHUNKS + 1);      // the rest of a range: reaches back into chunks already computed (same bits) to stay on the tile side
+                else hi = lo + MANY_SKINNY_CHUNKS + 1;                                                   // a range shorter than that: forward, into its slot's zero chunks
+            }
+            if (lo < 0 || hi > total - SD_MANY_GAP) SD_FAIL(c, SD_ERR_ARG, "packed segmentation batch [%lld,%lld) leaves the pack's %lld full chunks", (long long)lo, (long long)hi, (long long)(total - SD_MANY_GAP));
             if ((rc = run_segment(c, pack, lo, hi, d_seg + (size_t)lo * row))) return rc;
         }
     for (const auto& s : skinny)
         if ((rc = run_segment(c, pack, s.first, s.second, d_seg + (size_t)s.first * row))) return rc;
-    for (const ManyRec& q : rec) {
+    for (const PackRange& q : rec) {
         if (q.chunks <= 0 || q.full == q.chunks) continue;
-        const DevWav view{d_pack + q.base * (int64_t)SD_HOP, q.n, 0, true};      // zeros up to the end of the slot, at least 8000 of them behind a short last chunk
-        if ((rc = run_segment(c, view, q.chunks - 1, q.chunks, d_seg + (size_t)(q.base + q.chunks - 1) * row))) return rc;
+        const DevWav view{d_pack + q.base * (int64_t)SD_HOP, q.n + q.lo * (int64_t)SD_HOP, q.lo * (int64_t)SD_HOP, true};      // zeros up to the end of the slot, at least 8000 of them behind a short last chunk
+        if ((rc = run_segment(c, view, q.lo + q.chunks - 1, q.lo + q.chunks, d_seg + (size_t)(q.base + q.chunks - 1) * row))) return rc;
     }
+    return SD_OK;
+}
+
+// ------------------------------------------------------------------ both networks once over the pack (shard_infer's steps; the segmentation step is many_segment)
+int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vector<PackRange>& rec, int64_t total, double t0, float** seg_out, float** emb_out)
+{
+    std::vector<ManyGap> gaps;
+    int64_t longest = SD_WAV_PAD, longest_gap = 0;
+    for (const PackRange& q : rec) {
+        if (q.chunks <= 0) continue;
+        const int64_t slot = many_slot_chunks(q.n);
+        gaps.push_back(ManyGap{q.base + q.chunks, slot - q.chunks});
+        longest = std::max(longest, slot * (int64_t)SD_HOP);
+        longest_gap = std::max(longest_gap, slot - q.chunks);
+    }
+    rows.push_back(ManyRow{nullptr, 0, total * (int64_t)SD_HOP, SD_WAV_PAD});      // the zeroed floats behind the last slot (DevWav::padded)
+
+    const int64_t pack_len = total * (int64_t)SD_HOP + SD_WAV_PAD;
+    const size_t row_bytes = rows.size() * sizeof(ManyRow), gap_bytes = gaps.size() * sizeof(ManyGap);
+    WS(c, float, d_pack, "many_wav", pack_len);
+    WS(c, char, d_tab, "many_tab", row_bytes + gap_bytes);
+    WS(c, float, d_seg, "many_seg", total * SD_FRAMES * 3);
+    WS(c, float, d_masks, "many_masks", total * 3 * SD_FRAMES);
+    WS(c, float, d_emb, "many_emb", total * 3 * SD_EMB_DIM);
+    HIPCHK(c, hipMemcpy(d_tab, rows.data(), row_bytes, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_tab + row_bytes, gaps.data(), gap_bytes, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_many_pack, many_grid(longest, (int64_t)rows.size()), dim3(256), 0, c->stream, (const ManyRow*)d_tab, (int)rows.size(), is_f32, d_pack, pack_len);
+    KCHECK(c);
+
+    int rc;
+    HIPCHK(c, hipMemsetAsync(d_seg, 0, (size_t)total * SD_FRAMES * 3 * sizeof(float), c->stream));      // gap rows: defined values for run_postseg
+    if ((rc = many_segment(c, d_pack, total, rec, d_seg))) return rc;
+    if ((rc = run_postseg(c, d_seg, total, nullptr, d_masks, nullptr))) return rc;
+    hipLaunchKernelGGL(k_many_gap_masks, many_grid(longest_gap * SD_SPEAKERS * SD_FRAMES, (int64_t)gaps.size()), dim3(256), 0, c->stream,
+                       (const ManyGap*)(d_tab + row_bytes), (int)gaps.size(), d_masks, total);
+    KCHECK(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const double t1 = now_ms();
+    c->stage_ms[0] = t1 - t0;
+    // w.n is the packed length here.  The one place below run_embed that reads it, k_stft_fbank, clips a VALUE with it (a sample at or behind n reads
+    // as 0.0f): behind n_r the pack holds the same +0.0f.  The sample COUNTS of an item come from its mask row alone (k_mask_prefix) in both paths
+    if ((rc = run_embed(c, DevWav{d_pack, total * (int64_t)SD_HOP, 0, true}, d_masks, total * 3, 0, d_emb))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->stage_ms[1] = now_ms() - t1;
+    *seg_out = d_seg; *emb_out = d_emb;
     return SD_OK;
 }
 
@@ -117,72 +175,41 @@ static int many_run(sd_ctx* c, const void* const* src, int form, const int64_t* 
 
     const double t0 = now_ms();
     clear_stage_ms(c);
-    std::vector<ManyRec> rec((size_t)R);
+    const int64_t cb = c->seg_batch_chunks < 1 ? 1 : c->seg_batch_chunks;
+    std::vector<PackRange> rec((size_t)R);
     std::vector<ManyRow> rows;
-    std::vector<ManyGap> gaps;
-    int64_t src_samples = 0, longest = SD_WAV_PAD, longest_gap = 0;
+    int64_t src_samples = 0;
     for (int64_t r = 0; r < R; ++r) {
-        ManyRec& q = rec[(size_t)r];
-        q.n = n[r]; q.base = base[(size_t)r];
+        PackRange& q = rec[(size_t)r];
+        q.n = n[r]; q.base = base[(size_t)r]; q.lo = 0;
         q.chunks = sd_chunk_rule(q.n, &q.last_len);
         q.full = (q.last_len > 0 && q.last_len < SD_CHUNK) ? q.chunks - 1 : q.chunks;
+        q.tile = q.chunks > 0 ? many_tile_chunks(q.full, cb) : 0;
         if (q.chunks <= 0) continue;
-        const int64_t slot = many_slot_chunks(q.n);
-        rows.push_back(ManyRow{src[r], q.n, q.base * (int64_t)SD_HOP, slot * (int64_t)SD_HOP});
-        gaps.push_back(ManyGap{q.base + q.chunks, slot - q.chunks});
+        rows.push_back(ManyRow{src[r], q.n, q.base * (int64_t)SD_HOP, many_slot_chunks(q.n) * (int64_t)SD_HOP});
         src_samples += q.n;
-        longest = std::max(longest, slot * (int64_t)SD_HOP);
-        longest_gap = std::max(longest_gap, slot - q.chunks);
     }
     c->many_jobs.assign((size_t)R, ManyJob());
     for (int64_t r = 0; r < R; ++r) { turns[r] = nullptr; n_turns[r] = 0; status[r] = SD_ERR_SHORT; c->many_jobs[(size_t)r].status = SD_ERR_SHORT; }
     if (total <= 0) { c->stage_ms[3] = now_ms() - t0; return SD_OK; }
-    rows.push_back(ManyRow{nullptr, 0, total * (int64_t)SD_HOP, SD_WAV_PAD});      // the zeroed floats behind the last slot (DevWav::padded)
 
-    const int64_t pack_len = total * (int64_t)SD_HOP + SD_WAV_PAD;
-    const size_t row_bytes = rows.size() * sizeof(ManyRow), gap_bytes = gaps.size() * sizeof(ManyGap);
-    WS(c, float, d_pack, "many_wav", pack_len);
-    WS(c, char, d_tab, "many_tab", row_bytes + gap_bytes);
-    WS(c, float, d_seg, "many_seg", total * SD_FRAMES * 3);
-    WS(c, float, d_masks, "many_masks", total * 3 * SD_FRAMES);
-    WS(c, float, d_emb, "many_emb", total * 3 * SD_EMB_DIM);
     if (form != MANY_PCM_DEV) {      // host rows: uploaded back to back, then packed like device rows
         const size_t es = form == MANY_F32_HOST ? sizeof(float) : sizeof(int16_t);
         WS(c, char, d_src, "many_src", (size_t)src_samples * es);
         size_t off = 0;
         for (ManyRow& w : rows) {
-            if (!w.src) continue;
             HIPCHK(c, hipMemcpyAsync(d_src + off, w.src, (size_t)w.n * es, hipMemcpyHostToDevice, c->stream));
             w.src = d_src + off;
             off += (size_t)w.n * es;
         }
     }
-    HIPCHK(c, hipMemcpy(d_tab, rows.data(), row_bytes, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_tab + row_bytes, gaps.data(), gap_bytes, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_many_pack, many_grid(longest, (int64_t)rows.size()), dim3(256), 0, c->stream, (const ManyRow*)d_tab, (int)rows.size(),
-                       form == MANY_F32_HOST ? 1 : 0, d_pack, pack_len);
-    KCHECK(c);
-
-    // both networks once over the pack (shard_infer's steps; the segmentation step is many_segment)
-    HIPCHK(c, hipMemsetAsync(d_seg, 0, (size_t)total * SD_FRAMES * 3 * sizeof(float), c->stream));      // gap rows: defined values for run_postseg
-    if ((rc = many_segment(c, d_pack, total, rec, d_seg))) return rc;
-    if ((rc = run_postseg(c, d_seg, total, nullptr, d_masks, nullptr))) return rc;
-    hipLaunchKernelGGL(k_many_gap_masks, many_grid(longest_gap * SD_SPEAKERS * SD_FRAMES, (int64_t)gaps.size()), dim3(256), 0, c->stream,
-                       (const ManyGap*)(d_tab + row_bytes), (int)gaps.size(), d_masks, total);
-    KCHECK(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const double t1 = now_ms();
-    c->stage_ms[0] = t1 - t0;
-    // w.n is the packed length here.  The one place below run_embed that reads it, k_stft_fbank, clips a VALUE with it (a sample at or behind n reads
-    // as 0.0f): behind n_r the pack holds the same +0.0f.  The sample COUNTS of an item come from its mask row alone (k_mask_prefix) in both paths
-    if ((rc = run_embed(c, DevWav{d_pack, total * (int64_t)SD_HOP, 0, true}, d_masks, total * 3, 0, d_emb))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->stage_ms[1] = now_ms() - t1;
+    float *d_seg = nullptr, *d_emb = nullptr;
+    if ((rc = pack_infer(c, rows, form == MANY_F32_HOST ? 1 : 0, rec, total, t0, &d_seg, &d_emb))) return rc;
 
     // finalize, one recording after the other; what it leaves in the context is kept per recording
     auto give_back = [&]() { for (int64_t r = 0; r < R; ++r) { sd_free_turns(turns[r]); turns[r] = nullptr; n_turns[r] = 0; } };
     for (int64_t r = 0; r < R; ++r) {
-        const ManyRec& q = rec[(size_t)r];
+        const PackRange& q = rec[(size_t)r];
         if (q.chunks <= 0) continue;
         std::vector<sd_turn> v;
         rc = finalize(c, d_seg + (size_t)q.base * SD_FRAMES * 3, d_emb + (size_t)q.base * 3 * SD_EMB_DIM, q.chunks, q.n, v);
@@ -219,7 +246,7 @@ extern "C" int sd_many_select(sd_ctx* c, int64_t r)
 {
     if (!c) return SD_ERR_ARG;
     c->err.clear();
-    if (r < 0 || r >= (int64_t)c->many_jobs.size()) SD_FAIL(c, SD_ERR_ARG, "sd_many_select: the last sd_diarize_many* call of this context had %zu recordings", c->many_jobs.size());
+    if (r < 0 || r >= (int64_t)c->many_jobs.size()) SD_FAIL(c, SD_ERR_ARG, "sd_many_select: the last sd_diarize_many* / sd_stream_turns_many call of this context had %zu recordings", c->many_jobs.size());
     const ManyJob& job = c->many_jobs[(size_t)r];
     if (job.status != SD_OK) SD_FAIL(c, SD_ERR_ARG, "sd_many_select: recording %lld ended with status %d and left no job", (long long)r, job.status);
     c->last = job.res;

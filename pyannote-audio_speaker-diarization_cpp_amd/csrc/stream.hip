@@ -3,6 +3,8 @@
 // again (stream_book.h: blocks of 32 chunks whose every chunk ends in front of the last sample), the audio behind them as f32 on the
 // device, and at sd_stream_turns infers only the chunks behind the sealed part before the usual finalize.  The networks run through
 // shard_infer on sub-ranges (pipeline.cpp); the device code here is the tail's compaction (16-bit pushes are appended by k_pcm_to_f32).
+// sd_stream_push_many* / sd_stream_turns_many serve many streams of one context in one call: the networks run over a pack of the streams' blocks and
+// pending ranges (many.hip: pack_infer), three table-driven copy kernels replace the per-stream launches; the single-stream entries keep their paths.
 #include "common.h"
 #include "stream_book.h"
 #include <algorithm>
@@ -21,6 +23,68 @@ __global__ void k_tail_move(const float* __restrict__ src, float* __restrict__ d
         else if (j < len + SD_TAIL_PAD) dst[j] = 0.0f;
     }
 }
+
+// ------------------------------------------------------------------ device code of the group calls (sd_stream_push_many*, sd_stream_turns_many)
+// Three copy kernels, each ONE launch per call for all streams, walking a table of rows: dst[0, len) = src[0, len) and `pad` zeros behind, nothing at
+// or behind dst[room].  A row is cut into groups of four floats at the 16-byte boundaries of its DESTINATION (a tail ends anywhere): group 0 is the
+// 0 .. 3 floats in front of the first boundary, group g the four from head + 4 (g - 1) on, stored as one float4; the source is read 16 bytes (8 for
+// 16-bit samples) at a time where it is aligned at `head` too -- the host pushes are staged so that it is -- and element by element where not.
+//   k_group_append     the pushes of all streams to the ends of their tails, SD_TAIL_PAD zeros behind each (16-bit: x 1/32768 as k_pcm_to_f32; f32: copied)
+//   k_group_scatter    rows of the pack's scores / embeddings into the caches of the streams that own them
+//   k_group_tail_move  the compactions of all streams that sealed: k_tail_move per row
+// grid (x: a stride over the groups of a row, y: a stride over the table), 256 threads; 64-bit indices throughout
+struct GroupRow { const void* src; float* dst; int64_t len, room; };
+
+template <bool PCM> __device__ __forceinline__ float group_load(const void* src, int64_t j)
+{
+    return PCM ? (float)((const int16_t*)src)[j] * (1.0f / 32768.0f) : ((const float*)src)[j];      // sd.cpp:2948-2951
+}
+
+template <bool PCM> __device__ __forceinline__ void group_copy(const GroupRow* __restrict__ rows, int R, int64_t pad)
+{
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    for (int r = blockIdx.y; r < R; r += gridDim.y) {
+        const GroupRow row = rows[r];
+        const int64_t end = row.len + pad < row.room ? row.len + pad : row.room;      // floats of dst this row may write
+        const int64_t n = row.len < end ? row.len : end;                               // ... that come from src
+        int64_t head = (int64_t)((16 - ((uintptr_t)row.dst & 15)) & 15) / 4;
+        if (head > end) head = end;
+        const uintptr_t src_at_head = (uintptr_t)row.src + (uintptr_t)head * (PCM ? sizeof(int16_t) : sizeof(float));
+        const bool wide = (src_at_head & (PCM ? 7 : 15)) == 0;
+        for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; ; g += step) {
+            const int64_t i = g == 0 ? 0 : head + 4 * (g - 1);
+            const int64_t cnt = g == 0 ? head : 4;
+            if (i >= end) break;
+            if (g > 0 && i + 4 <= end) {      // a whole aligned group: one 16-byte store
+                float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (i + 4 <= n && wide) {
+                    if (PCM) {
+                        const short4 p = *reinterpret_cast<const short4*>((const int16_t*)row.src + i);
+                        v = make_float4((float)p.x * (1.0f / 32768.0f), (float)p.y * (1.0f / 32768.0f), (float)p.z * (1.0f / 32768.0f), (float)p.w * (1.0f / 32768.0f));
+                    } else v = *reinterpret_cast<const float4*>((const float*)row.src + i);
+                } else {
+                    if (i < n) v.x = group_load<PCM>(row.src, i);
+                    if (i + 1 < n) v.y = group_load<PCM>(row.src, i + 1);
+                    if (i + 2 < n) v.z = group_load<PCM>(row.src, i + 2);
+                    if (i + 3 < n) v.w = group_load<PCM>(row.src, i + 3);
+                }
+                *reinterpret_cast<float4*>(row.dst + i) = v;
+                continue;
+            }
+            for (int64_t j = i; j < i + cnt && j < end; ++j) row.dst[j] = j < n ? group_load<PCM>(row.src, j) : 0.0f;
+        }
+    }
+}
+
+__global__ void k_group_append(const GroupRow* __restrict__ rows, int R, int is_f32)
+{
+    if (is_f32) group_copy<false>(rows, R, SD_TAIL_PAD);
+    else group_copy<true>(rows, R, SD_TAIL_PAD);
+}
+__global__ void k_group_scatter(const GroupRow* __restrict__ rows, int R) { group_copy<false>(rows, R, 0); }
+__global__ void k_group_tail_move(const GroupRow* __restrict__ rows, int R) { group_copy<false>(rows, R, SD_TAIL_PAD); }
+
+static_assert(SD_GROUP_SKINNY_CHUNKS == SD_SKINNY_MAX_ROWS / SD_FRAMES, "stream_book.h states the skinny limit of common.h without including it");
 
 struct sd_stream {
     sd_ctx* c = nullptr;
@@ -203,6 +267,235 @@ int read_impl(sd_stream* s, int64_t lo, int64_t hi, float* h_seg, float* h_emb)
 
 // a HIP failure in the middle of a call leaves a tail or a cache nobody can vouch for
 int guard(sd_stream* s, int rc) { if (rc == SD_ERR_HIP) s->dead = true; return rc; }
+
+// ------------------------------------------------------------------ groups of streams
+// the refusals both group calls share; the caller has checked the list itself and every entry against null
+int group_check(sd_ctx* c, sd_stream* const* s, int64_t S, const char* who)
+{
+    std::vector<const sd_stream*> seen(s, s + S);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) SD_FAIL(c, SD_ERR_ARG, "%s: the same stream twice in the list", who);
+    for (int64_t i = 0; i < S; ++i) if (s[i]->c != c) SD_FAIL(c, SD_ERR_ARG, "%s: stream %lld belongs to another context", who, (long long)i);
+    for (int64_t i = 0; i < S; ++i) if (int rc = check_call(s[i], who)) return rc;
+    if (c->planted_n > 0) SD_FAIL(c, SD_ERR_ARG, "%s: a planted workload is set (its chunk range means one recording)", who);
+    return SD_OK;
+}
+
+// the ranges the streams contribute once stream i holds n_after[i] samples and `sealed[i]` sealed chunks, with their slots
+int group_ranges(sd_ctx* c, int64_t S, const int64_t* n_after, const int64_t* sealed, const char* wanted, bool pending, std::vector<GroupRange>& out, int64_t* total, const char* who)
+{
+    out.clear();
+    for (int64_t i = 0; i < S; ++i) {
+        GroupRange r;
+        if (!wanted[i] || !group_range(n_after[i], sealed[i], c->seg_batch_chunks, pending, r)) continue;
+        r.stream = i;
+        out.push_back(r);
+    }
+    if (group_plan(out.data(), (int64_t)out.size(), total)) SD_FAIL(c, SD_ERR_ARG, "%s: a range of more than 2^40 samples", who);
+    if (*total > SD_MANY_MAX_CHUNKS) SD_FAIL(c, SD_ERR_ARG, "%s: %lld packed chunks (limit %d: the rows of one call are counted in int)", who, (long long)*total, SD_MANY_MAX_CHUNKS);
+    return SD_OK;
+}
+
+int group_launch(sd_ctx* c, int which, const GroupRow* d_rows, const std::vector<GroupRow>& rows, int is_f32)
+{
+    if (rows.empty()) return SD_OK;
+    int64_t longest = 1;
+    for (const GroupRow& r : rows) longest = std::max(longest, r.len + SD_TAIL_PAD);
+    const dim3 grid = many_grid(longest / 4 + 2, (int64_t)rows.size());
+    if (which == 0) hipLaunchKernelGGL(k_group_append, grid, dim3(256), 0, c->stream, d_rows, (int)rows.size(), is_f32);
+    else if (which == 1) hipLaunchKernelGGL(k_group_scatter, grid, dim3(256), 0, c->stream, d_rows, (int)rows.size());
+    else hipLaunchKernelGGL(k_group_tail_move, grid, dim3(256), 0, c->stream, d_rows, (int)rows.size());
+    KCHECK(c);
+    return SD_OK;
+}
+
+// Both networks over the pack of these ranges, read from the tails; their rows into the owners' caches; and, for blocks that became sealed, the
+// compactions.  Tails, caches and compaction targets have their room (book_reserve_group).
+int group_infer(sd_ctx* c, sd_stream* const* s, const std::vector<GroupRange>& ranges, int64_t total, bool pending)
+{
+    if (ranges.empty()) return SD_OK;
+    const double t0 = now_ms();
+    std::vector<ManyRow> rows;
+    std::vector<PackRange> rec;
+    for (const GroupRange& r : ranges) {
+        const StreamBook& b = s[r.stream]->b;
+        rows.push_back(ManyRow{b.tail_now(), r.n_eq, r.base * (int64_t)SD_HOP, r.slot * (int64_t)SD_HOP});
+        rec.push_back(PackRange{r.n_eq, r.hi - r.lo, r.base, r.full, r.last_len, r.tile, r.lo});
+    }
+    float *d_seg = nullptr, *d_emb = nullptr;
+    int rc;
+    if ((rc = pack_infer(c, rows, 1, rec, total, t0, &d_seg, &d_emb))) return rc;
+    std::vector<GroupRow> seg, emb, mov;
+    for (const GroupRange& r : ranges) {
+        StreamBook& b = s[r.stream]->b;
+        const int64_t cnt = r.hi - r.lo;
+        seg.push_back(GroupRow{d_seg + r.base * SD_SEG_ROW, b.seg + r.lo * SD_SEG_ROW, cnt * SD_SEG_ROW, (b.cache_cap - r.lo) * SD_SEG_ROW});
+        emb.push_back(GroupRow{d_emb + r.base * SD_EMB_ROW, b.emb + r.lo * SD_EMB_ROW, cnt * SD_EMB_ROW, (b.cache_cap - r.lo) * SD_EMB_ROW});
+        GroupMove mv;
+        if (pending) b.pending_n = b.n;
+        else if (book_seal_planned(b, r.hi, mv)) mov.push_back(GroupRow{mv.src, mv.dst, mv.len, mv.room});
+    }
+    const size_t R = ranges.size();
+    WS(c, GroupRow, d_tab, "stg_tab", 3 * R);
+    HIPCHK(c, hipMemcpy(d_tab, seg.data(), R * sizeof(GroupRow), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_tab + R, emb.data(), R * sizeof(GroupRow), hipMemcpyHostToDevice));
+    if (!mov.empty()) HIPCHK(c, hipMemcpy(d_tab + 2 * R, mov.data(), mov.size() * sizeof(GroupRow), hipMemcpyHostToDevice));
+    if ((rc = group_launch(c, 1, d_tab, seg, 0))) return rc;
+    if ((rc = group_launch(c, 1, d_tab + R, emb, 0))) return rc;
+    if ((rc = group_launch(c, 2, d_tab + 2 * R, mov, 0))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!pending) {
+        HipDev dev{c};
+        for (const GroupRange& r : ranges) book_seal_trim(dev, s[r.stream]->b);
+    }
+    return SD_OK;
+}
+
+int push_many_impl(sd_ctx* c, sd_stream* const* s, const void* const* src, const int64_t* n, int64_t S, int kind, const char* who)
+{
+    // refusals: nothing is touched
+    if (!src || !n) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument", who);
+    int64_t pushed = 0;
+    for (int64_t i = 0; i < S; ++i) {
+        if (n[i] < 0 || n[i] > SD_MANY_MAX_SAMPLES || (n[i] > 0 && !src[i])) SD_FAIL(c, SD_ERR_ARG, "%s: bad samples for stream %lld", who, (long long)i);
+        pushed += n[i];
+    }
+    int rc;
+    if ((rc = group_check(c, s, S, who))) return rc;
+    std::vector<int64_t> n_after((size_t)S), sealed((size_t)S);
+    std::vector<char> wanted((size_t)S, 1);
+    for (int64_t i = 0; i < S; ++i) { n_after[(size_t)i] = s[i]->b.n + n[i]; sealed[(size_t)i] = s[i]->b.sealed; }
+    std::vector<GroupRange> ranges;
+    int64_t total = 0;
+    if ((rc = group_ranges(c, S, n_after.data(), sealed.data(), wanted.data(), false, ranges, &total, who))) return rc;
+    if (pushed == 0) return SD_OK;
+
+    const double t0 = now_ms();
+    clear_stage_ms(c);
+    // growth before the first kernel: a failed allocation leaves every stream what it was
+    HipDev dev{c};
+    std::vector<char> busy((size_t)S, 0);
+    for (const GroupRange& r : ranges) busy[(size_t)r.stream] = 1;
+    for (int64_t i = 0; i < S; ++i)
+        if ((n[i] > 0 || busy[(size_t)i]) && (rc = book_reserve_group(dev, s[i]->b, n[i]))) return rc;
+
+    // the samples of all streams: host ones uploaded back to back (each placed so that it is as aligned as its place in the tail), one conversion launch
+    const size_t es = kind == PUSH_F32_HOST ? sizeof(float) : sizeof(int16_t);
+    std::vector<GroupRow> rows;
+    std::vector<size_t> off;
+    size_t stage_len = 0;
+    for (int64_t i = 0; i < S; ++i) {
+        if (n[i] <= 0) continue;
+        StreamBook& b = s[i]->b;
+        float* dst = b.tail_now() + b.tail_len();
+        rows.push_back(GroupRow{src[i], dst, n[i], b.tail_cap[b.cur] - b.tail_len()});
+        const size_t head = (size_t)((16 - ((uintptr_t)dst & 15)) & 15) / 4;
+        while ((stage_len + head) % 4 != 0) ++stage_len;
+        off.push_back(stage_len);
+        stage_len += (size_t)n[i];
+    }
+    WS(c, GroupRow, d_tab, "stg_tab", rows.size());
+    if (kind != PUSH_PCM_DEV) {
+        WS(c, char, stage, "stg_src", stage_len * es);
+        for (size_t q = 0; q < rows.size(); ++q) {
+            HIPCHK(c, hipMemcpyAsync(stage + off[q] * es, rows[q].src, (size_t)rows[q].len * es, hipMemcpyHostToDevice, c->stream));
+            rows[q].src = stage + off[q] * es;
+        }
+    }
+    HIPCHK(c, hipMemcpy(d_tab, rows.data(), rows.size() * sizeof(GroupRow), hipMemcpyHostToDevice));
+    if ((rc = group_launch(c, 0, d_tab, rows, kind == PUSH_F32_HOST ? 1 : 0))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // the callers' buffers may go: once for all streams
+    for (int64_t i = 0; i < S; ++i) s[i]->b.n += n[i];
+
+    if ((rc = group_infer(c, s, ranges, total, false))) return rc;
+    c->stage_ms[3] = now_ms() - t0;
+    return SD_OK;
+}
+
+int turns_many_impl(sd_ctx* c, sd_stream* const* s, int64_t S, sd_turn** turns, int64_t* n_turns, int32_t* status)
+{
+    const char* who = "sd_stream_turns_many";
+    // refusals: nothing is touched
+    if (!turns || !n_turns || !status) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument", who);
+    int rc;
+    if ((rc = group_check(c, s, S, who))) return rc;
+    if (!c->dump_dir.empty()) SD_FAIL(c, SD_ERR_ARG, "%s: the step files describe one whole-path inference; clear the dump directory", who);
+    if ((rc = enrolled_refusal(c, SD_EMB_DIM, c->num_clusters, c->min_clusters, c->max_clusters))) return rc;
+    std::vector<int64_t> n_now((size_t)S), sealed((size_t)S);
+    std::vector<char> all((size_t)S, 1), stale((size_t)S, 0);
+    for (int64_t i = 0; i < S; ++i) { n_now[(size_t)i] = s[i]->b.n; sealed[(size_t)i] = s[i]->b.sealed; }
+    std::vector<GroupRange> to_seal, to_infer;      // (to_seal: nothing unless an earlier push failed half way)
+    int64_t seal_total = 0, total = 0;
+    if ((rc = group_ranges(c, S, n_now.data(), sealed.data(), all.data(), false, to_seal, &seal_total, who))) return rc;
+    for (int64_t i = 0; i < S; ++i) {
+        const int64_t to = stream_sealed_chunks(s[i]->b.n);
+        stale[(size_t)i] = (s[i]->b.pending_n != s[i]->b.n || to > s[i]->b.sealed) ? 1 : 0;
+        sealed[(size_t)i] = std::max(to, s[i]->b.sealed);
+    }
+    if ((rc = group_ranges(c, S, n_now.data(), sealed.data(), stale.data(), true, to_infer, &total, who))) return rc;
+
+    const double t0 = now_ms();
+    clear_stage_ms(c);
+    c->many_jobs.assign((size_t)S, ManyJob());
+    for (int64_t i = 0; i < S; ++i) { turns[i] = nullptr; n_turns[i] = 0; status[i] = SD_ERR_SHORT; c->many_jobs[(size_t)i].status = SD_ERR_SHORT; }
+    HipDev dev{c};
+    for (const GroupRange& r : to_seal) if ((rc = book_reserve_group(dev, s[r.stream]->b, 0))) return rc;
+    for (const GroupRange& r : to_infer) if ((rc = book_reserve_group(dev, s[r.stream]->b, 0))) return rc;
+    if ((rc = group_infer(c, s, to_seal, seal_total, false))) return rc;
+    if ((rc = group_infer(c, s, to_infer, total, true))) return rc;
+
+    // the unchanged finalize, one stream after the other; what it leaves in the context is kept per stream (sd_many_select)
+    auto give_back = [&]() { for (int64_t i = 0; i < S; ++i) { sd_free_turns(turns[i]); turns[i] = nullptr; n_turns[i] = 0; } };
+    for (int64_t i = 0; i < S; ++i) {
+        const StreamBook& b = s[i]->b;
+        const int64_t chunks = sd_num_chunks(b.n, nullptr);
+        if (chunks <= 0) continue;
+        std::vector<sd_turn> v;
+        rc = finalize(c, b.seg, b.emb, chunks, b.n, v);
+        ManyJob& job = c->many_jobs[(size_t)i];
+        status[i] = job.status = rc;
+        if (rc == SD_ERR_NUMERIC) continue;                    // this stream's clustering; the others go on
+        if (rc == SD_OK) rc = turns_out(c, v, &turns[i], &n_turns[i]);
+        if (rc) { give_back(); return rc; }
+        job.res = c->last;
+    }
+    c->stage_ms[3] = now_ms() - t0;
+    return SD_OK;
+}
+
+// SD_ERR_HIP in the middle of a group call: nobody can vouch for any tail or cache of the call
+int group_guard(sd_stream* const* s, int64_t S, int rc) { if (rc == SD_ERR_HIP) for (int64_t i = 0; i < S; ++i) s[i]->dead = true; return rc; }
+bool group_list_ok(sd_stream* const* s, int64_t S)
+{
+    if (!s || S < 1) return false;
+    for (int64_t i = 0; i < S; ++i) if (!s[i]) return false;
+    return true;
+}
+}
+
+extern "C" int sd_stream_push_many(sd_stream* const* s, const int16_t* const* h_pcm, const int64_t* n, int64_t S)
+{
+    if (!group_list_ok(s, S)) return SD_ERR_ARG;
+    ENTER(s[0]->c);
+    return group_guard(s, S, push_many_impl(s[0]->c, s, (const void* const*)h_pcm, n, S, PUSH_PCM_HOST, "sd_stream_push_many"));
+}
+extern "C" int sd_stream_push_many_dev(sd_stream* const* s, const int16_t* const* d_pcm, const int64_t* n, int64_t S)
+{
+    if (!group_list_ok(s, S)) return SD_ERR_ARG;
+    ENTER(s[0]->c);
+    return group_guard(s, S, push_many_impl(s[0]->c, s, (const void* const*)d_pcm, n, S, PUSH_PCM_DEV, "sd_stream_push_many_dev"));
+}
+extern "C" int sd_stream_push_many_f32(sd_stream* const* s, const float* const* h_wav, const int64_t* n, int64_t S)
+{
+    if (!group_list_ok(s, S)) return SD_ERR_ARG;
+    ENTER(s[0]->c);
+    return group_guard(s, S, push_many_impl(s[0]->c, s, (const void* const*)h_wav, n, S, PUSH_F32_HOST, "sd_stream_push_many_f32"));
+}
+extern "C" int sd_stream_turns_many(sd_stream* const* s, int64_t S, sd_turn** turns, int64_t* n_turns, int32_t* status)
+{
+    if (!group_list_ok(s, S)) return SD_ERR_ARG;
+    ENTER(s[0]->c);
+    return group_guard(s, S, turns_many_impl(s[0]->c, s, S, turns, n_turns, status));
 }
 
 extern "C" int64_t sd_stream_sealed_chunks(int64_t n_samples) { return stream_sealed_chunks(n_samples); }

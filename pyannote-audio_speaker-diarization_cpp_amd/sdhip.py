@@ -65,6 +65,7 @@ EXPORTS = [
     "sd_activity_scores", "sd_activity_regions", "sd_activity", "sd_activity_dev", "sd_activity_f32", "sd_activity_wav", "sd_last_activity_scores",
     "sd_stream_open", "sd_stream_push", "sd_stream_push_dev", "sd_stream_push_f32", "sd_stream_turns", "sd_stream_info", "sd_stream_read",
     "sd_stream_close", "sd_stream_sealed_chunks",
+    "sd_stream_push_many", "sd_stream_push_many_dev", "sd_stream_push_many_f32", "sd_stream_turns_many",
     "sd_last_speakers", "sd_span_masks", "sd_voiceprint", "sd_voiceprint_dev", "sd_voiceprint_f32", "sd_voiceprint_wav", "sd_speaker_distances",
     "sd_match_speakers", "sd_read_voiceprints", "sd_write_voiceprints", "sd_free_voiceprints", "sd_voiceprints_error", "sd_write_rttm_named",
     "sd_set_enrolled", "sd_enrolled_info", "sd_nearest_speakers", "sd_last_enrolled",
@@ -191,7 +192,11 @@ def lib():
         for f in (L.sd_diarize_many, L.sd_diarize_many_dev, L.sd_diarize_many_f32):
             f.argtypes = [vp, vp, vp, i64, vp, vp, vp]
         L.sd_many_select.argtypes = [vp, i64]
-    if hasattr(L, "sd_der"):            # (an older build loaded through SDHIP_LIB by the A/B tools has none of these)
+    if hasattr(L, "sd_stream_push_many"):      # (likewise)
+        for f in (L.sd_stream_push_many, L.sd_stream_push_many_dev, L.sd_stream_push_many_f32):
+            f.argtypes = [vp, vp, vp, i64]
+        L.sd_stream_turns_many.argtypes = [vp, i64, vp, vp, vp]
+    if hasattr(L, "sd_der"):           # (an older build loaded through SDHIP_LIB by the A/B tools has none of these)
         L.sd_der.argtypes = [C.POINTER(Turn), i64, C.POINTER(Turn), i64, C.POINTER(Turn), i64, dbl, C.c_int, C.POINTER(DerResult), vp, i64, C.POINTER(i64)]
         L.sd_read_rttm.argtypes = [C.c_char_p, C.c_char_p, tpp, C.POINTER(i64), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(i64)]
         L.sd_free_rttm_names.argtypes = [C.POINTER(C.c_char_p), i64]
@@ -1003,6 +1008,52 @@ class Diarizer:
     def stream(self):
         """sd_stream_open: incremental diarization of a growing recording on this context"""
         return Stream(self)
+
+    # ---- many streams of this context in one call
+    def _push_many(self, fn, streams, ptrs, lengths):
+        S = len(streams)
+        if not (S == len(ptrs) == len(lengths)):
+            raise SdError(1, "one pointer and one length per stream")
+        hs = (C.c_void_p * max(S, 1))(*[s._handle().value for s in streams])
+        rows = (C.c_void_p * max(S, 1))(*[int(p) or None for p in ptrs])
+        n = (C.c_int64 * max(S, 1))(*[int(v) for v in lengths])
+        rc = fn(hs, rows, n, S)
+        if rc and not S:
+            raise SdError(rc, "an empty list of streams")
+        self._chk(rc)
+
+    def stream_push_many(self, streams, pcms):
+        """sd_stream_push_many: int16 samples for every stream of the list (an empty array: nothing for that stream), one upload and one packed inference
+        of the blocks that became sealed; every stream is then what Stream.push of its own samples leaves"""
+        pcms = [np.ascontiguousarray(p, np.int16) for p in pcms]
+        self._push_many(lib().sd_stream_push_many, streams, [p.ctypes.data if len(p) else 0 for p in pcms], [len(p) for p in pcms])
+
+    def stream_push_many_f32(self, streams, wavs):
+        wavs = [np.ascontiguousarray(w, np.float32) for w in wavs]
+        self._push_many(lib().sd_stream_push_many_f32, streams, [w.ctypes.data if len(w) else 0 for w in wavs], [len(w) for w in wavs])
+
+    def stream_push_many_dev(self, streams, d_pcm_ptrs, lengths):
+        """sd_stream_push_many_dev: device pointers of int16 samples and their lengths"""
+        self._push_many(lib().sd_stream_push_many_dev, streams, d_pcm_ptrs, lengths)
+
+    def stream_turns_many(self, streams):
+        """sd_stream_turns_many: per stream the turns Stream.turns gives, or the error code (SD_ERR_SHORT = 4, SD_ERR_NUMERIC = 5) it ended with;
+        many_select(i) then makes stream i the last job"""
+        S = len(streams)
+        hs = (C.c_void_p * max(S, 1))(*[s._handle().value for s in streams])
+        turns = (C.POINTER(Turn) * max(S, 1))()
+        nt = (C.c_int64 * max(S, 1))()
+        status = (C.c_int32 * max(S, 1))()
+        rc = lib().sd_stream_turns_many(hs, S, turns, nt, status)
+        if rc and not S:
+            raise SdError(rc, "an empty list of streams")
+        self._chk(rc)
+        self._last_d = EMB_DIM
+        out = []
+        for i in range(S):
+            t = self._turns(turns[i], C.c_int64(nt[i]))
+            out.append(t if status[i] == 0 else int(status[i]))
+        return out
 
     # ---- many cuts of one dendrogram
     def _cut(self, rc, h):
