@@ -288,6 +288,26 @@ int sd_stream_read(sd_stream*, int64_t chunk_lo, int64_t chunk_hi, float* h_seg,
 void sd_stream_close(sd_stream*);
 /* host-only: the sealed chunks of an n_samples-sample recording, 32 * (full / 32) as above (slide()'s chunk rule, sd.cpp:1419, 1457) */
 int64_t sd_stream_sealed_chunks(int64_t n_samples);
+/* ---- a stream that runs all day: a sliding window.  After sd_stream_forget the stream is a new stream to which the kept samples were pushed, except
+ * that it remembers how many samples it has forgotten.  sd_stream_forget drops D = sealed - 32 * keep_blocks chunks (nothing where D <= 0): the front
+ * D rows of the score and the embedding cache go -- the kept sealed rows are copied into fresh, smaller allocations and the old ones are given back,
+ * so device memory really shrinks --, n_samples drops by D * 8000, sealed by D, and the origin rises by D * 8000.  The tail already starts at
+ * sample sealed * 8000 and is not touched.  D is a multiple of 32 chunks = 256 000 samples, so block boundaries and the 96-item embedding batches
+ * stay where a new stream puts them, and a cached sealed row depends on its own chunk and on the kernel alone: sd_stream_turns, _read, _info and
+ * every sd_last_* result are, bit for bit, those of sd_diarize of samples [origin, origin + n_samples) of what was pushed, with times counted from
+ * the origin.  The pending rows are inferred again by the next sd_stream_turns, as after a push (which kernel a pending chunk's scores take depends
+ * on the chunks in front of it in its batch).  A failed allocation inside a forget -- by hand, or by the window behind a push -- returns SD_ERR_HIP,
+ * leaves the stream exactly what it was before that forget and leaves it usable; behind a push the samples are in and the blocks sealed
+ * (sd_stream_info says so: do not push them again), in a group call the streams later in the list keep their blocks until their next push that seals.
+ * Every other SD_ERR_HIP, a failed copy inside a forget included, makes the stream unusable as for the other calls.
+ * sd_stream_set_window(W >= 0) is the policy: every push, single or through sd_stream_push_many*, that seals a block then forgets down to W blocks
+ * (in a group call per stream, after the group's launches); -1 = off, the default.  sd_stream_origin: the samples forgotten so far.
+ * SD_ERR_ARG: keep_blocks < 0 (set_window: < -1), a stream that is unusable or whose precision options changed, as for the other calls.
+ * What the window does NOT do: it carries no speakers over.  The labels of a windowed stream mean the same person from one update to the next only
+ * under an enrolled gallery -- as for streams in general, whose every update clusters anew. */
+int sd_stream_forget(sd_stream*, int64_t keep_blocks);                         /* sd.cpp:2937-3234, repeated */
+int sd_stream_set_window(sd_stream*, int64_t keep_blocks /* -1 = off, the default */);
+int sd_stream_origin(const sd_stream*, int64_t* first_sample);
 /* ---- many live recordings at once: S streams of ONE context in one call, for a caller with dozens of calls in progress on one card.  Every stream
  * keeps its contract: after any sequence of single and group calls its turns, labels, confidences, centroids and cached rows are the bytes it gives
  * when it is driven alone, which are those of sd_diarize of everything pushed to it.  The networks run once per call over a pack of the streams'
@@ -493,6 +513,24 @@ int sd_stage_ms(const sd_ctx*, double* ms4);
  *   "clustering_threshold" (0 .. 2, default (double)0.7153814381597874f): the three hyper-parameters of Clustering.py:251-276 / 317-333, which the
  *   reference hard-codes (sd.cpp:2049-2056).  Centroid, median and ward run on the unit-normalised rows with euclidean distances, the other four on
  *   the rows as they are with the cosine metric.  They apply to sd_clustering*, the whole path, sd_finalize_dev and the sharded path,
+ * "max_num_embeddings" (-1 = unset (default), or >= 1; anything else SD_ERR_ARG) and "clustering_seed" (any int64, default 0):
+ *   BaseClustering.max_num_embeddings of Clustering.py:12, 69-76, which the port carries commented out (sd.cpp:2218, 2231-2249: "IS INF").  Let T be
+ *   the train rows of a clustering call: the row indices i of emb [M][d] whose first element is not NaN (sd.cpp:2224), ascending.  With the option
+ *   unset or |T| <= max_num_embeddings nothing changes.  Otherwise the max_num_embeddings rows of T with the smallest key(seed, i) stay, ascending
+ *   by i, where in 64-bit wrap-around arithmetic
+ *       G = 0x9E3779B97F4A7C15,  fin(x): x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31
+ *       key(seed, i) = fin(fin((uint64)seed + G) + (uint64)i * G).
+ *   fin is a bijection and G is odd: distinct i have distinct keys and there is no tie rule.  i is the row's index in the table the call was
+ *   given (chunk * 3 + speaker), not its position among the train rows; the sample for m is a subset of the sample for m + 1; a row appended
+ *   to a growing recording removes at most one row from the sample.  From there on the sample IS "the train rows", as in Clustering.py: N of the
+ *   minimum-cluster-size rule and of the number-of-clusters rules is the sample size, the linkage, the cut and the small-cluster pass see the sample
+ *   only, centroids are means of sampled rows, sd_last_speakers counts sampled rows, voiceprints of an enrolled gallery claim among the sampled
+ *   rows -- and the final assignment labels ALL M rows as ever.  A deliberate deviation: the reference draws the sample with random.shuffle; the
+ *   keyed choice is the deterministic form of the same uniform sample.  Read wherever train rows are taken: sd_clustering*, the whole path,
+ *   sd_finalize_dev, rank 0 of a sharded job, streams, every recording of sd_diarize_many (i is local to the recording's own table) and, at
+ *   open, cut objects (sd_cut_info's train_rows and sd_cut_dendrogram describe the sample).  sd_sample_rows below shows the rule.  While the
+ *   option is set a call that clusters under a dump directory returns SD_ERR_ARG: the step files describe the reference's flow, which clusters
+ *   every train row (the same refusal as for an enrolled gallery),
  * "ecapa_precision" (0 = f32 MFMA = the reference's ORT precision (default); 1 = fp16 weights and activations on the fp16 MFMA with f32
  *   accumulation; 2 = the same with hi + lo fp16 weight planes; 3 = f32 tensors, both MFMA operands split into hi + lo fp16 halves, three
  *   products per multiply-add: f32-grade embeddings (<= 1e-7 cosine distance to mode 0) at about half of mode 0's time; a batch whose activations
@@ -513,6 +551,10 @@ int sd_set_option(sd_ctx*, const char* key, int64_t value);
  * sd_activity* above (NaN or out of range: SD_ERR_ARG), and "speaker_match_threshold" of sd_match_speakers above (outside [0, 2] or NaN: SD_ERR_ARG).
  * An unknown key returns SD_ERR_ARG. */
 int sd_set_option_f64(sd_ctx*, const char* key, double value);
+/* host-only: the rule of "max_num_embeddings" on a list of n distinct rows >= 0 in ascending order, through the function the clustering stage
+ * applies.  max_num = -1 or >= 1.  Returns the number of rows written to out -- min(n, max_num), n under -1 -- or -SD_ERR_ARG. */
+int64_t sd_sample_rows(const int32_t* rows /*[n] ascending*/, int64_t n, int64_t max_num, int64_t seed,
+                       int32_t* out /*[min(n, max_num)]*/);     /* Clustering.py:69-76; sd.cpp:2231-2249 */
 
 #ifdef __cplusplus
 }

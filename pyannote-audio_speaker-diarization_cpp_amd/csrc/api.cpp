@@ -151,6 +151,8 @@ extern "C" int sd_set_option(sd_ctx* c, const char* key, int64_t v)
     else if (k == "constrained_assignment") c->constrained_assignment = v != 0;
     else if (k == "clustering_method") { if (v < SD_LINKAGE_SINGLE || v > SD_LINKAGE_WEIGHTED) SD_FAIL(c, SD_ERR_ARG, "clustering_method must be one of SD_LINKAGE_SINGLE (0) .. SD_LINKAGE_WEIGHTED (6)"); c->clustering_method = (int)v; }
     else if (k == "min_cluster_size") { if (v < 1 || v > 0x7fffffff) SD_FAIL(c, SD_ERR_ARG, "min_cluster_size must be at least 1"); c->min_cluster_size = (int)v; }
+    else if (k == "max_num_embeddings") { if (v != -1 && v < 1) SD_FAIL(c, SD_ERR_ARG, "max_num_embeddings must be -1 (every train row) or at least 1"); c->max_num_embeddings = v; }
+    else if (k == "clustering_seed") c->clustering_seed = v;
     else if (k == "num_clusters") c->num_clusters = (int)v;
     else if (k == "min_clusters") c->min_clusters = (int)v;
     else if (k == "max_clusters") c->max_clusters = (int)v;
@@ -184,6 +186,17 @@ extern "C" int sd_linkage_method_from_name(const char* name)
 
 // ------------------------------------------------------------------ helpers
 extern "C" int64_t sd_num_chunks(int64_t n, int64_t* last_len) { return sd_chunk_rule(n, last_len); }      // many_plan.h: the one statement of the rule
+
+// host-only: the rule of "max_num_embeddings" on a list of rows, through the function train_rows (cluster.hip) applies
+extern "C" int64_t sd_sample_rows(const int32_t* rows, int64_t n, int64_t max_num, int64_t seed, int32_t* out)
+{
+    if (n < 0 || (n > 0 && (!rows || !out)) || (max_num != -1 && max_num < 1)) return -SD_ERR_ARG;
+    for (int64_t q = 0; q < n; ++q) if (rows[q] < 0 || (q > 0 && rows[q] <= rows[q - 1])) return -SD_ERR_ARG;      // ascending and distinct: distinct keys
+    std::vector<int32_t> kept;
+    const int64_t m = sample_rows(rows, n, max_num, seed, kept);
+    for (int64_t q = 0; q < m; ++q) out[q] = kept[(size_t)q];
+    return m;
+}
 
 // ------------------------------------------------------------------ embedding path
 extern "C" int sd_embed_dev(sd_ctx* c, const float* d_wav, int64_t n, const float* d_masks, int64_t items, int64_t first_item, float* d_emb)

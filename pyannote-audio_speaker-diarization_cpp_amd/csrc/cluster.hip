@@ -405,7 +405,8 @@ static int clustering_enrolled(sd_ctx* c, const double* d_emb, int64_t M, int d,
     return SD_OK;
 }
 
-// a10: the rows of d_emb [M][d] whose first element is not NaN (sd.cpp:2224), ascending; synchronises the stream
+// a10: the rows of d_emb [M][d] whose first element is not NaN (sd.cpp:2224), ascending; synchronises the stream.  Under "max_num_embeddings" the
+// sample of them (cluster_host.h: sample_rows) -- from here on the sample IS the train rows, as in Clustering.py:69-76
 int train_rows(sd_ctx* c, const double* d_e64, int64_t M, int d, std::vector<int>& tidx)
 {
     std::vector<double> first((size_t)M);
@@ -413,6 +414,12 @@ int train_rows(sd_ctx* c, const double* d_e64, int64_t M, int d, std::vector<int
     HIPCHK(c, hipStreamSynchronize(c->stream));
     tidx.clear();
     for (int64_t i = 0; i < M; ++i) if (!std::isnan(first[(size_t)i])) tidx.push_back((int)i);
+    if (c->max_num_embeddings >= 0 && (int64_t)tidx.size() > c->max_num_embeddings) {
+        static_assert(sizeof(int) == sizeof(int32_t), "row indices are 32-bit");
+        std::vector<int32_t> kept;
+        sample_rows(tidx.data(), (int64_t)tidx.size(), c->max_num_embeddings, c->clustering_seed, kept);
+        tidx.swap(kept);
+    }
     return SD_OK;
 }
 
@@ -440,6 +447,8 @@ int run_clustering(sd_ctx* c, const double* d_emb, int64_t M, int d, std::vector
                    int num_clusters, int min_clusters, int max_clusters, std::vector<double>* soft_best)
 {
     if (int rf = enrolled_refusal(c, d, num_clusters, min_clusters, max_clusters)) return rf;
+    if (c->max_num_embeddings >= 0 && !c->dump_dir.empty())
+        SD_FAIL(c, SD_ERR_ARG, "max_num_embeddings is set: the step files describe the reference's flow, which clusters every train row (unset it or clear the dump directory)");
     hard.assign((size_t)M, 0);
     if (soft_best) soft_best->assign((size_t)M, NAN);
     if (Kout) *Kout = 1;

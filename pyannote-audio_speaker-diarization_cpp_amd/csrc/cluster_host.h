@@ -127,6 +127,34 @@ inline ClusterCounts resolve_num_clusters(const ClusterSpec& s, int64_t N)
 // the minimum cluster size as it is used: the option, lowered for few rows (sd.cpp:2308, Clustering.py:309-311)
 inline size_t resolve_min_cluster_size(int option, int64_t N) { return std::min<size_t>((size_t)option, std::max<size_t>(1, (size_t)std::round(0.1 * (double)N))); }
 
+// max_num_embeddings (Clustering.py:12, 69-76; commented out in the port, sd.cpp:2231-2249): which train rows are clustered when there are more than
+// max_num of them.  The reference shuffles and keeps the first max_num; here the rows with the max_num smallest keys stay, ascending by row: the same
+// uniform sample, but a function of (seed, row index) alone.  fin is a bijection of 64-bit words and G is odd, so distinct rows have distinct keys
+// (no tie rule); the sample for m is a subset of the one for m + 1; a row appended to the list pushes at most one row out.
+inline uint64_t sample_fin(uint64_t x)
+{
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
+    return x;
+}
+inline uint64_t sample_key(int64_t seed, int64_t i)
+{
+    const uint64_t G = 0x9E3779B97F4A7C15ull;
+    return sample_fin(sample_fin((uint64_t)seed + G) + (uint64_t)i * G);
+}
+// rows [n] ascending -> out: all of them where max_num is -1 or n <= max_num, else the max_num rows with the smallest keys, ascending.  Returns the count
+inline int64_t sample_rows(const int32_t* rows, int64_t n, int64_t max_num, int64_t seed, std::vector<int32_t>& out)
+{
+    if (max_num < 0 || n <= max_num) { out.assign(rows, rows + (n > 0 ? n : 0)); return n > 0 ? n : 0; }
+    std::vector<uint64_t> key((size_t)n);
+    for (int64_t q = 0; q < n; ++q) key[(size_t)q] = sample_key(seed, rows[q]);
+    std::vector<uint64_t> sorted(key);
+    std::nth_element(sorted.begin(), sorted.begin() + (max_num - 1), sorted.end());
+    const uint64_t limit = sorted[(size_t)max_num - 1];                              // the largest key that stays
+    out.clear();
+    for (int64_t q = 0; q < n; ++q) if (key[(size_t)q] <= limit) out.push_back(rows[q]);
+    return (int64_t)out.size();
+}
+
 // Everything of a cut up to the point where centroids are needed: the 0-based labels of the N rows after the cut at spec.threshold and, where the
 // constraints ask for it (sd.cpp:2361-2366), after the re-cut; nl labels; the membership (order / off of group_by_label); the clusters that reach mcs
 // rows and those that do not.  trivial: one cluster, label 0 for every row, nothing else filled.

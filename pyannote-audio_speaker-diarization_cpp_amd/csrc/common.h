@@ -219,7 +219,10 @@ struct sd_ctx {
     int clustering_method = SD_LINKAGE_CENTROID;
     double clustering_threshold = (double)0.7153814381597874f;      // the reference's float constant, widened
     int min_cluster_size = 15;
-    JobResult last;                             // the last job (sd_last_confidence, sd_last_speakers, sd_last_enrolled)
+    int64_t max_num_embeddings = -1;            // Clustering.py:12, 69-76: cluster a sample of this many train rows, assign all (-1 = all of them, the port's "IS INF")
+    bool stream_intact = false;                 // a stream call failed only in an allocation of a forget: its streams stay usable (stream.hip: forget_to, guard)
+    int64_t clustering_seed = 0;                // ... chosen by sample_rows (cluster_host.h) under this seed
+    JobResult last;                            // the last job (sd_last_confidence, sd_last_speakers, sd_last_enrolled)
     // the enrolled gallery (sd_set_enrolled): the context's own device copy [enr_M][enr_d], the squared norms of its rows (k_row_sqnorms), and a host copy
     // for the candidate loop and the centroid table of run_clustering; enr_M = 0: none, and nothing of the clustering stage changes
     DevBuf enr_gal, enr_m2;

@@ -25,6 +25,9 @@
 //                   (NAME: single | complete | average | centroid | median | ward | weighted; X in 0..2; N >= 1) = sd_set_option "clustering_method" /
 //                   "min_cluster_size" and sd_set_option_f64 "clustering_threshold"; defaults are the reference's constants (centroid, 0.7153814, 15).
 //                   A bad value is a usage error (exit 2) before anything touches the GPU
+//   --max-num-embeddings N, --clustering-seed S   cluster a sample of at most N train rows and assign every row (BaseClustering.max_num_embeddings,
+//                   Clustering.py:12, 69-76; N >= 1, or -1 = every row) = sd_set_option "max_num_embeddings"; S (any 64-bit integer, default 0) picks the
+//                   sample = "clustering_seed".  A bad value is a usage error (exit 2) before anything touches the GPU
 //   --activity speech|overlap   regions of speech / of overlapped speech from the segmentation network alone (sd_activity_wav: pyannote's
 //                   VoiceActivityDetection / OverlappedSpeechDetection on the reference's aggregate + to_annotation, sd.cpp:1167-1311 / 2852-2935) instead of
 //                   speaker turns: lines [start -- end] --> SPEECH or OVERLAP; --rttm writes them as SPEAKER_00 / SPEAKER_01.  With it
@@ -35,6 +38,10 @@
 //                   per chunk as the audio comes in, the final turns are those of the run without the flag, bit for bit.  --stream-updates also prints,
 //                   after each piece, "== <seconds pushed> s, <sealed>/<total> chunks" and the turns so far.  With - as the wav path, headerless s16le
 //                   16 kHz mono samples are read from stdin until end of file (needs --stream).  Single GPU; not with --activity or --dump-steps
+//   --stream-window SECONDS   with --stream: a sliding window (sd_stream_set_window with ceil(SECONDS / 16) blocks of 32 chunks): after every piece that
+//                   seals a block the stream forgets all but that many; the turns are those of the audio still held, printed with absolute times
+//                   (t + sd_stream_origin / 16000); the header of a --stream-updates block still gives the seconds pushed, its chunk counts are those of the
+//                   audio held.  Without --stream, or with a value that is not a number of seconds > 0: usage error (exit 2)
 //   --speakers FILE [--speakers-threshold X]   after the diarization, match the centroids of the job's clusters (sd_last_speakers) against the voiceprints of
 //                   FILE (sd_read_voiceprints, sd_match_speakers): a matched cluster prints as [start -- end] --> NAME and goes into the RTTM under its name, an
 //                   unmatched one prints as without the flag.  X in [0, 2] = the largest cosine distance that still matches (option "speaker_match_threshold").
@@ -81,6 +88,8 @@
 
 struct Args { const char* seg = nullptr; const char* emb = nullptr; const char* wav = nullptr; const char* rttm = nullptr; int gpus = 1; bool relabel = false; int precision = 0; int wav_flags = 0; const char* dump_dir = nullptr; int dump_level = 1;
               int cl_method = -1; double cl_threshold = -1.0; long long cl_min_size = -1;         // -1: leave the library's default
+              long long cl_max_num = 0, cl_seed = 0; bool cl_seed_set = false;                    // --max-num-embeddings (0: not given), --clustering-seed
+              long long stream_window = -1;                                                       // --stream-window: blocks kept (-1: no window)
               int activity = -1; double act[4] = {-1.0, -1.0, -1.0, -1.0}; bool act_hamming = false;      // --activity: SD_ACTIVITY_*; onset, offset, min on, min off (-1: default)
               long long stream_piece = 0; bool stream_updates = false;         // --stream: samples per piece (0: off)
               const char* speakers = nullptr; double speakers_threshold = -1.0; const char* enroll = nullptr; std::vector<sd_turn> enroll_spans; bool enrolled = false;
@@ -111,6 +120,8 @@ static bool apply_clustering(sd_ctx* ctx, const Args& a)
     if (a.cl_method >= 0 && sd_set_option(ctx, "clustering_method", a.cl_method) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
     if (a.cl_threshold >= 0.0 && sd_set_option_f64(ctx, "clustering_threshold", a.cl_threshold) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
     if (a.cl_min_size >= 0 && sd_set_option(ctx, "min_cluster_size", a.cl_min_size) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
+    if (a.cl_max_num != 0 && sd_set_option(ctx, "max_num_embeddings", a.cl_max_num) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
+    if (a.cl_seed_set && sd_set_option(ctx, "clustering_seed", a.cl_seed) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return false; }
     return true;
 }
 
@@ -419,6 +430,9 @@ struct StreamRun {
         if (rc == SD_ERR_SHORT) return true;
         if (rc != SD_OK) { fprintf(stderr, "diarization failed (%d): %s\n", rc, sd_last_error(ctx)); return false; }
         bill();
+        int64_t origin = 0;                         // --stream-window: the stream's times count from the first sample it still holds
+        sd_stream_origin(st, &origin);
+        if (origin > 0) for (int64_t i = 0; i < nt; ++i) { turns[i].start += (double)origin / 16000.0; turns[i].end += (double)origin / 16000.0; }
         return true;
     }
     // one push call; a piece may take several (stdin arrives in smaller reads)
@@ -435,7 +449,9 @@ struct StreamRun {
         if (!ask()) return false;
         int64_t n = 0, sealed = 0, total = 0;
         sd_stream_info(st, &n, &sealed, &total);
-        printf("== %g s, %lld/%lld chunks\n", (double)n / SD_SAMPLE_RATE, (long long)sealed, (long long)total);
+        int64_t origin = 0;                         // --stream-window: seconds pushed, not seconds held; the chunks are those the stream still holds
+        sd_stream_origin(st, &origin);
+        printf("== %g s, %lld/%lld chunks\n", (double)(origin + n) / SD_SAMPLE_RATE, (long long)sealed, (long long)total);
         std::vector<const char*> names, turn_name;
         print_turns(turns, nt, a, gal && enrolled_names(ctx, *gal, names) ? &names : nullptr, turn_name);
         fflush(stdout);
@@ -493,6 +509,7 @@ static int run_stream(const Args& a)
     auto leave = [&](int rc) { sd_free_turns(r.turns); sd_stream_close(r.st); sd_destroy(ctx); return rc; };      // every way out gives back what it holds
     if (a.enrolled) { if (!enrol_gallery(ctx, a, g)) return leave(1); r.gal = &g; }
     if (sd_stream_open(ctx, &r.st) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
+    if (a.stream_window >= 0 && sd_stream_set_window(r.st, a.stream_window) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
     const bool fed = std::string(a.wav) == "-" ? stream_stdin(r) : stream_file(r);
     if (!fed || !r.ask()) return leave(1);
     int64_t n = 0, total = 0;
@@ -596,6 +613,29 @@ int main(int argc, char* argv[])
                 if (end == v || *end || a.cl_min_size < 1 || a.cl_min_size > 0x7fffffff) { fprintf(stderr, "usage: --min-cluster-size takes an integer >= 1 (got '%s')\n", v); return 2; }
             }
         }
+        else if (s == "--max-num-embeddings" || s == "--clustering-seed") {
+            if (i + 1 >= argc) { fprintf(stderr, "usage: %s needs a value\n", s.c_str()); return 2; }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            errno = 0;
+            const long long x = strtoll(v, &end, 10);
+            const bool number = end != v && !*end && errno != ERANGE;
+            if (s == "--max-num-embeddings") {
+                if (!number || (x != -1 && x < 1)) { fprintf(stderr, "usage: --max-num-embeddings takes an integer >= 1, or -1 for every row (got '%s')\n", v); return 2; }
+                a.cl_max_num = x;
+            } else {
+                if (!number) { fprintf(stderr, "usage: --clustering-seed takes a 64-bit integer (got '%s')\n", v); return 2; }
+                a.cl_seed = x; a.cl_seed_set = true;
+            }
+        }
+        else if (s == "--stream-window") {
+            if (i + 1 >= argc) { fprintf(stderr, "usage: --stream-window needs a value\n"); return 2; }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            const double sec = strtod(v, &end);
+            if (end == v || *end || !(sec > 0.0) || sec > 1e9) { fprintf(stderr, "usage: --stream-window takes a number of seconds > 0 (got '%s')\n", v); return 2; }
+            a.stream_window = (long long)ceil(sec / 16.0);      // blocks of 32 chunks = 256 000 samples
+        }
         else if (s == "--many") {
             if (i + 1 >= argc || !argv[i + 1][0]) { fprintf(stderr, "usage: --many needs a list file\n"); return 2; }
             a.many = argv[++i];
@@ -693,6 +733,8 @@ int main(int argc, char* argv[])
     if (a.stream_piece > 0 && a.gpus > 1) { fprintf(stderr, "usage: --stream runs on one GPU; --gpus %d is refused\n", a.gpus); return 2; }
     if (a.stream_piece > 0 && a.activity >= 0) { fprintf(stderr, "usage: --stream gives speaker turns; --activity is refused with it\n"); return 2; }
     if (a.stream_piece > 0 && a.dump_dir) { fprintf(stderr, "usage: --dump-steps describes one whole-path inference; --stream is refused with it\n"); return 2; }
+    if (a.stream_window >= 0 && a.stream_piece <= 0) { fprintf(stderr, "usage: --stream-window needs --stream SECONDS\n"); return 2; }
+    if (a.cl_max_num >= 1 && a.dump_dir) { fprintf(stderr, "usage: --dump-steps describes the reference's flow, which clusters every train row; --max-num-embeddings is refused with it\n"); return 2; }
     if (a.stream_updates && a.stream_piece <= 0) { fprintf(stderr, "usage: --stream-updates needs --stream SECONDS\n"); return 2; }
     if (pos.size() >= 3 && std::string(pos[2]) == "-" && a.stream_piece <= 0) { fprintf(stderr, "usage: samples from stdin (-) need --stream SECONDS\n"); return 2; }
     if (a.enroll && !a.speakers) { fprintf(stderr, "usage: --enroll NAME needs --speakers FILE, the voiceprint file to write\n"); return 2; }

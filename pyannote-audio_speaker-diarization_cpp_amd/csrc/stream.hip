@@ -91,14 +91,16 @@ struct sd_stream {
     StreamBook b;
     int ecapa_precision = 0, seg_precision = 0;      // fixed at sd_stream_open: a cache of mixed precision is nobody's answer
     bool dead = false;                               // after SD_ERR_HIP: every call but sd_stream_close is refused
+    int64_t window = -1;                             // sd_stream_set_window: sealed blocks kept after a push that seals one (-1: all of them)
 };
 
 namespace {
 // the device operations of stream_book.h on the stream's context; copies are ordered on the context's stream
 struct HipDev {
     sd_ctx* c;
+    bool alloc_failed = false;      // the failure this Dev reported was an allocation's: nothing has been launched or moved for it
     int alloc(void** p, size_t bytes) {
-        if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; SD_FAIL(c, SD_ERR_HIP, "hipMalloc of %zu bytes for a stream failed", bytes); }
+        if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; alloc_failed = true; SD_FAIL(c, SD_ERR_HIP, "hipMalloc of %zu bytes for a stream failed", bytes); }
         return SD_OK;
     }
     void release(void* p) { (void)hipStreamSynchronize(c->stream); (void)hipFree(p); }
@@ -151,6 +153,16 @@ int segment_pending(sd_stream* s, const DevWav& tail, int64_t lo, int64_t hi)
     return SD_OK;
 }
 
+// book_forget on the stream's context, by hand or as the window's policy behind a push.  A failed allocation leaves the book what it was before the
+// forget (stream_book.h) with nothing launched: the call returns SD_ERR_HIP, but guard / group_guard leave the streams usable (c->stream_intact)
+int forget_to(sd_stream* s, int64_t keep_blocks)
+{
+    HipDev dev{s->c};
+    const int rc = book_forget(dev, s->b, keep_blocks);
+    if (rc && dev.alloc_failed) s->c->stream_intact = true;
+    return rc;
+}
+
 // both networks on chunks [lo, hi) of the recording, read from the tail, into the cache rows of those chunks
 int infer_rows(sd_stream* s, int64_t lo, int64_t hi, bool pending)
 {
@@ -168,7 +180,7 @@ int infer_rows(sd_stream* s, int64_t lo, int64_t hi, bool pending)
 }
 
 // the blocks that have become sealed: inferred once, then their audio is dropped
-int seal_blocks(sd_stream* s)
+int seal_blocks(sd_stream* s, bool window)
 {
     StreamBook& b = s->b;
     const int64_t to = stream_sealed_chunks(b.n);
@@ -177,7 +189,8 @@ int seal_blocks(sd_stream* s)
     int rc;
     if ((rc = book_reserve_cache(dev, b, sd_num_chunks(b.n, nullptr)))) return rc;
     if ((rc = infer_rows(s, b.sealed, to, false))) return rc;
-    return book_seal(dev, b, to);
+    if ((rc = book_seal(dev, b, to))) return rc;
+    return window && s->window >= 0 ? forget_to(s, s->window) : SD_OK;      // the window's policy: a push that sealed a block forgets down to it
 }
 
 int check_call(sd_stream* s, const char* who)
@@ -218,7 +231,7 @@ int push_impl(sd_stream* s, const void* src, int64_t m, int kind, const char* wh
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));      // the caller's buffer may go
     b.n += m;
-    if ((rc = seal_blocks(s))) return rc;
+    if ((rc = seal_blocks(s, true))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->stage_ms[3] = now_ms() - t0;
     return SD_OK;
@@ -236,7 +249,7 @@ int turns_impl(sd_stream* s, sd_turn** turns, int64_t* n_turns)
     const double t0 = now_ms();
     clear_stage_ms(c);
     int rc;
-    if ((rc = seal_blocks(s))) return rc;            // (nothing to do unless an earlier push failed half way)
+    if ((rc = seal_blocks(s, false))) return rc;     // (nothing to do unless an earlier push failed half way; the window waits for the next push that seals)
     if (b.pending_n != b.n) {
         HipDev dev{c};
         if ((rc = book_reserve_cache(dev, b, total))) return rc;
@@ -265,8 +278,20 @@ int read_impl(sd_stream* s, int64_t lo, int64_t hi, float* h_seg, float* h_emb)
     return SD_OK;
 }
 
+// sd_stream_forget: all but the last keep_blocks sealed blocks go (stream_book.h: book_forget)
+int forget_impl(sd_stream* s, int64_t keep_blocks, const char* who)
+{
+    sd_ctx* c = s->c;
+    if (keep_blocks < 0) SD_FAIL(c, SD_ERR_ARG, "%s: keep_blocks must be >= 0", who);
+    if (int rc = check_call(s, who)) return rc;
+    if (int rc = forget_to(s, keep_blocks)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SD_OK;
+}
+
 // a HIP failure in the middle of a call leaves a tail or a cache nobody can vouch for
-int guard(sd_stream* s, int rc) { if (rc == SD_ERR_HIP) s->dead = true; return rc; }
+// (unless the only failure was an allocation of a forget: forget_to)
+int guard(sd_stream* s, int rc) { if (rc == SD_ERR_HIP && !s->c->stream_intact) s->dead = true; s->c->stream_intact = false; return rc; }
 
 // ------------------------------------------------------------------ groups of streams
 // the refusals both group calls share; the caller has checked the list itself and every entry against null
@@ -311,7 +336,7 @@ int group_launch(sd_ctx* c, int which, const GroupRow* d_rows, const std::vector
 
 // Both networks over the pack of these ranges, read from the tails; their rows into the owners' caches; and, for blocks that became sealed, the
 // compactions.  Tails, caches and compaction targets have their room (book_reserve_group).
-int group_infer(sd_ctx* c, sd_stream* const* s, const std::vector<GroupRange>& ranges, int64_t total, bool pending)
+int group_infer(sd_ctx* c, sd_stream* const* s, const std::vector<GroupRange>& ranges, int64_t total, bool pending, bool window = false)
 {
     if (ranges.empty()) return SD_OK;
     const double t0 = now_ms();
@@ -347,6 +372,8 @@ int group_infer(sd_ctx* c, sd_stream* const* s, const std::vector<GroupRange>& r
     if (!pending) {
         HipDev dev{c};
         for (const GroupRange& r : ranges) book_seal_trim(dev, s[r.stream]->b);
+        for (const GroupRange& r : ranges)      // the window's policy, per stream, behind the group's launches
+            if (window && s[r.stream]->window >= 0 && (rc = forget_to(s[r.stream], s[r.stream]->window))) return rc;
     }
     return SD_OK;
 }
@@ -407,7 +434,7 @@ int push_many_impl(sd_ctx* c, sd_stream* const* s, const void* const* src, const
     HIPCHK(c, hipStreamSynchronize(c->stream));      // the callers' buffers may go: once for all streams
     for (int64_t i = 0; i < S; ++i) s[i]->b.n += n[i];
 
-    if ((rc = group_infer(c, s, ranges, total, false))) return rc;
+    if ((rc = group_infer(c, s, ranges, total, false, true))) return rc;
     c->stage_ms[3] = now_ms() - t0;
     return SD_OK;
 }
@@ -464,7 +491,12 @@ int turns_many_impl(sd_ctx* c, sd_stream* const* s, int64_t S, sd_turn** turns, 
 }
 
 // SD_ERR_HIP in the middle of a group call: nobody can vouch for any tail or cache of the call
-int group_guard(sd_stream* const* s, int64_t S, int rc) { if (rc == SD_ERR_HIP) for (int64_t i = 0; i < S; ++i) s[i]->dead = true; return rc; }
+int group_guard(sd_stream* const* s, int64_t S, int rc)
+{
+    if (rc == SD_ERR_HIP && !s[0]->c->stream_intact) for (int64_t i = 0; i < S; ++i) s[i]->dead = true;
+    s[0]->c->stream_intact = false;
+    return rc;
+}
 bool group_list_ok(sd_stream* const* s, int64_t S)
 {
     if (!s || S < 1) return false;
@@ -554,6 +586,28 @@ extern "C" int sd_stream_info(const sd_stream* s, int64_t* n_samples, int64_t* c
     if (n_samples) *n_samples = s->b.n;
     if (chunks_sealed) *chunks_sealed = s->b.sealed;
     if (chunks_total) *chunks_total = sd_num_chunks(s->b.n, nullptr);
+    return SD_OK;
+}
+extern "C" int sd_stream_forget(sd_stream* s, int64_t keep_blocks)
+{
+    if (!s) return SD_ERR_ARG;
+    ENTER(s->c);
+    return guard(s, forget_impl(s, keep_blocks, "sd_stream_forget"));
+}
+extern "C" int sd_stream_set_window(sd_stream* s, int64_t keep_blocks)
+{
+    if (!s) return SD_ERR_ARG;
+    ENTER(s->c);
+    sd_ctx* c = s->c;
+    if (keep_blocks < -1) SD_FAIL(c, SD_ERR_ARG, "sd_stream_set_window: keep_blocks must be -1 (no window) or >= 0");
+    if (int rc = check_call(s, "sd_stream_set_window")) return rc;
+    s->window = keep_blocks;
+    return SD_OK;
+}
+extern "C" int sd_stream_origin(const sd_stream* s, int64_t* first_sample)
+{
+    if (!s || !first_sample) return SD_ERR_ARG;
+    *first_sample = s->b.origin;
     return SD_OK;
 }
 extern "C" int sd_stream_read(sd_stream* s, int64_t chunk_lo, int64_t chunk_hi, float* h_seg, float* h_emb)

@@ -28,6 +28,7 @@ struct StreamBook {
     float* seg = nullptr;          // [cache_cap][293][3]
     float* emb = nullptr;          // [cache_cap * 3][192]
     int64_t cache_cap = 0;         // chunks
+    int64_t origin = 0;            // samples forgotten in front of sample 0 of this book (book_forget); n, sealed and pending_n count from there
     int64_t tail_len() const { return n - sealed * SD_HOP; }
     float* tail_now() const { return tail[cur]; }
 };
@@ -90,6 +91,36 @@ template <class Dev> int book_seal(Dev& d, StreamBook& b, int64_t to)
     if (int rc = d.move_tail(b.tail[o], b.tail[b.cur] + drop, keep)) return rc;
     b.cur = o; b.sealed = to; b.pending_n = -1;
     if (b.tail_cap[1 - o] > SD_TAIL_SPARE_MAX) { d.release(b.tail[1 - o]); b.tail[1 - o] = nullptr; b.tail_cap[1 - o] = 0; }
+    return 0;
+}
+
+// The sliding window: all but the last keep_blocks sealed blocks go.  D = sealed - 32 * keep_blocks chunks (nothing where D <= 0): the sealed rows
+// behind them move to the front of fresh, smaller caches -- two different allocations, so a plain copy; the old ones are given back -- and the book
+// counts from sample D * 8000 on: n and sealed drop, origin rises.  The tail starts at sample sealed * 8000 before and after and is not touched.
+// D is a multiple of 32 chunks, so the blocks and the 96-item embedding batches lie where a book fed the kept samples alone has them.  The pending
+// rows are NOT kept: the kernels behind a pending chunk's score row depend on how many chunks lie in front of it in its segmentation batch
+// (stream.hip: segment_pending), which D changes; the next turns call infers them again, as it does after any push.
+// A failed allocation or copy leaves the book what it was.  Returns 0 or the Dev's code; *dropped (may be null) = D or 0.
+template <class Dev> int book_forget(Dev& d, StreamBook& b, int64_t keep_blocks, int64_t* dropped = nullptr)
+{
+    if (dropped) *dropped = 0;
+    if (keep_blocks < 0) return SD_ERR_ARG;
+    if (keep_blocks >= b.sealed / SD_SEAL_CHUNKS) return 0;
+    const int64_t D = b.sealed - SD_SEAL_CHUNKS * keep_blocks, keep = b.sealed - D;
+    const int64_t total = sd_chunk_rule(b.n - D * SD_HOP, nullptr);                  // the chunks of what stays: room for its pending rows too
+    const int64_t cap = total > 64 ? total : 64;
+    void *ps = nullptr, *pe = nullptr;
+    if (int rc = d.alloc(&ps, (size_t)(cap * SD_SEG_ROW) * sizeof(float))) return rc;
+    if (int rc = d.alloc(&pe, (size_t)(cap * SD_EMB_ROW) * sizeof(float))) { d.release(ps); return rc; }
+    if (keep > 0) {
+        int rc = d.copy(ps, b.seg + D * SD_SEG_ROW, (size_t)(keep * SD_SEG_ROW) * sizeof(float));
+        if (!rc) rc = d.copy(pe, b.emb + D * SD_EMB_ROW, (size_t)(keep * SD_EMB_ROW) * sizeof(float));
+        if (rc) { d.release(ps); d.release(pe); return rc; }
+    }
+    d.release(b.seg); d.release(b.emb);
+    b.seg = (float*)ps; b.emb = (float*)pe; b.cache_cap = cap;
+    b.n -= D * SD_HOP; b.sealed -= D; b.origin += D * SD_HOP; b.pending_n = -1;
+    if (dropped) *dropped = D;
     return 0;
 }
 

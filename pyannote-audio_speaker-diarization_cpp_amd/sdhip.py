@@ -64,7 +64,7 @@ EXPORTS = [
     "sd_test_lstm_rec", "sd_test_pool_norm", "sd_test_chunk_norm", "sd_test_classifier",
     "sd_activity_scores", "sd_activity_regions", "sd_activity", "sd_activity_dev", "sd_activity_f32", "sd_activity_wav", "sd_last_activity_scores",
     "sd_stream_open", "sd_stream_push", "sd_stream_push_dev", "sd_stream_push_f32", "sd_stream_turns", "sd_stream_info", "sd_stream_read",
-    "sd_stream_close", "sd_stream_sealed_chunks",
+    "sd_stream_close", "sd_stream_sealed_chunks", "sd_stream_forget", "sd_stream_set_window", "sd_stream_origin",
     "sd_stream_push_many", "sd_stream_push_many_dev", "sd_stream_push_many_f32", "sd_stream_turns_many",
     "sd_last_speakers", "sd_span_masks", "sd_voiceprint", "sd_voiceprint_dev", "sd_voiceprint_f32", "sd_voiceprint_wav", "sd_speaker_distances",
     "sd_match_speakers", "sd_read_voiceprints", "sd_write_voiceprints", "sd_free_voiceprints", "sd_voiceprints_error", "sd_write_rttm_named",
@@ -73,6 +73,7 @@ EXPORTS = [
     "sd_der", "sd_read_rttm", "sd_free_rttm_names", "sd_score_error",
     "sd_cut_open_dev", "sd_cut_open", "sd_cut_open_pcm_dev", "sd_cut_open_f32", "sd_cut_open_wav", "sd_cut_turns", "sd_cut_turns_many",
     "sd_cut_dendrogram", "sd_cut_info", "sd_cut_close",
+    "sd_sample_rows",
 ]
 # SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
 LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
@@ -212,6 +213,12 @@ def lib():
         L.sd_cut_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
         L.sd_cut_close.argtypes = [vp]
         L.sd_cut_close.restype = None
+    if hasattr(L, "sd_sample_rows"):      # (likewise)
+        L.sd_sample_rows.restype = i64
+        L.sd_sample_rows.argtypes = [vp, i64, i64, i64, vp]
+        L.sd_stream_forget.argtypes = [vp, i64]
+        L.sd_stream_set_window.argtypes = [vp, i64]
+        L.sd_stream_origin.argtypes = [vp, C.POINTER(i64)]
     L.sd_format_turn.argtypes = [C.POINTER(Turn), C.c_char_p, C.c_int]
     L.sd_stage_ms.argtypes = [vp, C.POINTER(dbl)]
     L.sd_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
@@ -332,6 +339,17 @@ def many_plan(lengths):
     if rc:
         raise SdError(rc, "sd_many_plan: bad argument")
     return base, total.value
+
+
+def sample_rows(rows, max_num, seed=0):
+    """sd_sample_rows (host-only): the rows of an ascending list that a clustering call under max_num_embeddings = max_num and clustering_seed = seed
+    keeps as its train rows (all of them under -1 or when there are no more than max_num), ascending, int32"""
+    r = np.ascontiguousarray(rows, np.int32).reshape(-1)
+    out = np.zeros(max(len(r), 1), np.int32)
+    m = lib().sd_sample_rows(_ptr(r) if len(r) else None, len(r), int(max_num), int(seed), _ptr(out))
+    if m < 0:
+        raise SdError(-m, "sd_sample_rows: bad argument (rows ascending, distinct and >= 0; max_num -1 or >= 1)")
+    return out[:m].copy()
 
 
 def convert_onnx(onnx_path, kind, out_path):
@@ -541,6 +559,20 @@ class Stream:
         self._d._chk(lib().sd_stream_info(self._handle(), C.byref(n), C.byref(sealed), C.byref(total)))
         return int(n.value), int(sealed.value), int(total.value)
 
+    def forget(self, keep_blocks):
+        """sd_stream_forget: all but the last keep_blocks sealed blocks of 32 chunks go; afterwards the stream is a new one fed the kept samples"""
+        self._d._chk(lib().sd_stream_forget(self._handle(), int(keep_blocks)))
+
+    def set_window(self, keep_blocks):
+        """sd_stream_set_window: every push that seals a block forgets down to keep_blocks blocks (-1: no window)"""
+        self._d._chk(lib().sd_stream_set_window(self._handle(), int(keep_blocks)))
+
+    def origin(self):
+        """sd_stream_origin: samples forgotten so far = the sample of everything pushed at which the stream's times start"""
+        o = C.c_int64(0)
+        self._d._chk(lib().sd_stream_origin(self._handle(), C.byref(o)))
+        return int(o.value)
+
     def read(self, lo, hi, seg=True, emb=True):
         """cached rows of chunks [lo, hi): (scores [hi-lo][293][3] or None, embeddings [(hi-lo)*3][192] or None)"""
         rows = max(int(hi) - int(lo), 0)
@@ -660,11 +692,18 @@ class Diarizer:
     def set_option_f64(self, key, value):
         self._chk(lib().sd_set_option_f64(self._h, key.encode(), float(value)))
 
-    def set_clustering(self, method="centroid", threshold=CLUSTERING_THRESHOLD_DEFAULT, min_cluster_size=15):
-        """the three hyper-parameters of clustering/Clustering.py:251-276; the defaults are the reference's constants"""
+    def set_clustering(self, method="centroid", threshold=CLUSTERING_THRESHOLD_DEFAULT, min_cluster_size=15, max_num_embeddings=None, seed=None):
+        """the three hyper-parameters of clustering/Clustering.py:251-276; the defaults are the reference's constants.  max_num_embeddings
+        (Clustering.py:12, 69-76: -1 or >= 1) and seed (option "clustering_seed"): None leaves the option as it is"""
         code = _method_code(method)
         if not 0 <= code < len(LINKAGE_METHODS) or not 0.0 <= float(threshold) <= 2.0 or int(min_cluster_size) < 1:      # all three or none: the context is shared
             raise SdError(1, "set_clustering: method %r, threshold %r, min_cluster_size %r" % (method, threshold, min_cluster_size))
+        if max_num_embeddings is not None and int(max_num_embeddings) != -1 and int(max_num_embeddings) < 1:
+            raise SdError(1, "set_clustering: max_num_embeddings must be -1 or at least 1 (got %r)" % (max_num_embeddings,))
+        if max_num_embeddings is not None:
+            self.set_option("max_num_embeddings", max_num_embeddings)
+        if seed is not None:
+            self.set_option("clustering_seed", seed)
         self.set_option("clustering_method", code)
         self.set_option_f64("clustering_threshold", threshold)
         self.set_option("min_cluster_size", min_cluster_size)
