@@ -14,6 +14,7 @@
 #include <vector>
 #include "../../include/sdhip_test.h"
 #include "cluster_host.h"
+#include "many_plan.h"
 
 #define SD_T 501          // STFT frames per item (1 + 80000/160), sd.cpp:1980-2008
 #define SD_TP 501         // rows per item in activation buffers (= T: no padding rows; a 128-row tile may span two items)
@@ -109,10 +110,7 @@ struct ConvArgs {
 #define ROWTAB_LAST(y) (((y) >> 10) & 1023)
 #define ROWTAB_ITEM(y) ((int)((unsigned)(y) >> 20))
 #define ROWTAB_MAX_ITEMS 4095
-// launch_conv_gemm (conv_gemm.hip): a plain f32 GEMM of at most this many rows goes to k_skinny_gemm, a larger one to the 128 x 128 tile, whose K order differs in
-// the last bits.  >= ROWTAB_MAX_ITEMS, so the per-utterance layers of an ECAPA batch always take the skinny kernel; PyanNet's dense layers have 293 rows per
-// chunk, so a batch of up to 13 chunks takes it too -- the stream's pending batch (stream.hip: segment_pending) reads this constant to stay on the whole path's kernel
-#define SD_SKINNY_MAX_ROWS 4096
+// SD_SKINNY_MAX_ROWS, the row count up to which launch_conv_gemm (conv_gemm.hip) takes k_skinny_gemm, is many_plan.h's, next to the side rule that rests on it
 
 struct EcapaWeights {
     bool loaded = false;
@@ -426,14 +424,17 @@ int turns_out(sd_ctx* c, const std::vector<sd_turn>& v, sd_turn** turns, int64_t
 // ---- many.hip: both networks once over a pack of slots (many_plan.h).  sd_diarize_many* packs recordings, stream.hip the ranges of a group of streams
 struct ManyRow { const void* src; int64_t n, base, len; };      // src[0, n) -> dst[base, base + n), zeros in dst[base + n, base + len)
 struct ManyGap { int64_t first, count; };                         // chunks [first, first + count) belong to nobody
-// one slot: a recording, or chunks [lo, lo + chunks) of a stream whose audio from sample lo * 8000 on is what the slot holds.  n, chunks, full and
-// last_len describe the slot's n samples as a recording of its own (sd_chunk_rule); its first `tile` full chunks are on the tile side of PyanNet's
-// dense layers in the path the slot has to equal, the other full ones on the skinny side in batches of seg_batch_chunks (many.hip: many_segment)
-struct PackRange { int64_t n, chunks, base, full, last_len, tile, lo; };
 dim3 many_grid(int64_t longest, int64_t table);      // x: a stride over the longest row of a table, y: a stride over the table; 256 threads
 // rows: one per slot that has a chunk, src on the device (is_f32: float samples, else 16-bit); total = many_plan's.  Leaves the scores [total][293][3]
 // and embeddings [total * 3][192] of the pack in workspaces; stage_ms[0] and [1] are counted from t0
 int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vector<PackRange>& rec, int64_t total, double t0, float** seg_out, float** emb_out);
+// the form of the samples an entry was handed, for the entries that come in three (sd_diarize_many*, sd_stream_push*, sd_stream_push_many*)
+enum SampleForm { SD_PCM_HOST, SD_PCM_DEV, SD_F32_HOST };
+// finalize, one job after the other, of a call with J outputs (sd_diarize_many*: recordings; sd_stream_turns_many: streams).  Presets turns / n_turns /
+// status / c->many_jobs to "no job" (SD_ERR_SHORT), lets `infer` run the networks and name the rows of every job (chunks <= 0: none), then finalizes in
+// list order: SD_ERR_NUMERIC is that job's own status, any other failure gives every turn list back and is returned; c->last is kept per job
+struct FinalJob { const float* seg; const float* emb; int64_t chunks, n; };
+int finalize_jobs(sd_ctx* c, int64_t J, sd_turn** turns, int64_t* n_turns, int32_t* status, const std::function<int(std::vector<FinalJob>&)>& infer);
 // ---- cut.hip: the tail of the sd_cut_open* entries (sdhip.h, "many cuts of one dendrogram"); refuses a gallery and a dump directory itself
 int cut_refusal(sd_ctx* c, const char* who);
 int cut_open_dev(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, sd_cut** out);

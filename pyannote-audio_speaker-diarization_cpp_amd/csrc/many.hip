@@ -7,9 +7,11 @@
 //   k_many_pack       one launch: the samples of every recording into its slot (16-bit: x 1/32768 as k_pcm_to_f32; f32: copied), zeros behind them
 //   k_many_gap_masks  one launch: zero mask rows for the gap chunks of every slot
 // Both walk a table indexed by recording; every store is guarded by the row's own slot length and by the length of the destination.
-// pack_infer, the inference over a filled table, is shared with the group calls of stream.hip, whose slots hold ranges of streams.
+// pack_infer, the inference over a filled table, and finalize_jobs, the finalize per output, are shared with the group calls of stream.hip, whose slots
+// hold ranges of streams.  A slot is a PackRange (many_plan.h) built by pack_range (stream_book.h): a recording is the pending range of a
+// stream with nothing sealed.  Which side of PyanNet's skinny limit a chunk is on is seg_tile_chunks' word (many_plan.h), here and in stream.hip.
 #include "common.h"
-#include "many_plan.h"
+#include "stream_book.h"
 #include <algorithm>
 #include <utility>
 
@@ -52,24 +54,15 @@ extern "C" int sd_many_plan(const int64_t* n, int64_t R, int64_t* chunk_base, in
 // ------------------------------------------------------------------ segmentation over the pack
 // A full chunk of a recording reads samples of that recording only, and packed chunk B_r + k starts where chunk k starts: run_segment on the pack
 // "as one recording" computes it from the same samples with the same kernels -- provided its batch is on the same side of the one threshold at
-// which PyanNet's kernels change with the batch size: up to SD_SKINNY_MAX_ROWS / 293 = 13 chunks the dense layers take k_skinny_gemm, above that
-// the 128 x 128 tile, and the two differ in the last bits (common.h; stream.hip minds the same thing).  So the plan keeps, for every chunk, the
-// side its batch has in the loop of single calls (batches of seg_batch_chunks from chunk 0 of the recording):
+// which PyanNet's kernels change with the batch size: up to SD_SKINNY_CHUNKS = 13 chunks the dense layers take k_skinny_gemm, above that the
+// 128 x 128 tile, and the two differ in the last bits (many_plan.h).  So the plan keeps, for every chunk, the side its batch has in the loop of
+// single calls (batches of seg_batch_chunks from chunk 0 of the recording; q.tile = seg_tile_chunks):
 //   tile side    chunks [0, T_r): ranges of neighbouring recordings are joined across the gap chunks between them (rows that nobody reads) and
 //                run in shared batches of seg_batch_chunks, each of 14 chunks or more;
 //   skinny side  chunks [T_r, full_r): the batches of the single path, one recording at a time (a batch of at most 13 chunks has no room for more);
 //   short last chunk (sd.cpp:1457-1480): the single path's own call on a view of the slot -- its frame count depends on its length, and the shared
 //                first convolution the single path takes for it is not the per-row form of run_segment_rows bit for bit (tests/test_next_rows.py)
-#define MANY_SKINNY_CHUNKS (SD_SKINNY_MAX_ROWS / SD_FRAMES)
 #define MANY_JOIN_CHUNKS 256      /* tile ranges at most this far apart are one range: up to 4096 chunks are one wave of LSTM workgroups, a launch sequence more costs more */
-
-// the side of the full chunks of a recording in the loop of single calls: the batches of seg_batch_chunks from chunk 0 on, the last one on the skinny
-// side when it has 13 chunks or fewer (stream_book.h: group_tile_chunks states the same rule, and a stream's exception to it)
-static int64_t many_tile_chunks(int64_t full, int64_t cb)
-{
-    const int64_t rem = full % cb;
-    return cb <= MANY_SKINNY_CHUNKS ? 0 : ((rem == 0 || rem > MANY_SKINNY_CHUNKS) ? full : full - rem);
-}
 
 // A slot of a stream's range (q.lo > 0, stream.hip) differs in two things.  Its tile side is what the caller says, and can be shorter than 14 chunks
 // (1 .. 13 pending chunks behind sealed ones): such a range reaches FORWARD into the zero chunks of its own slot -- at least 19 of them -- and the
@@ -94,9 +87,9 @@ static int many_segment(sd_ctx* c, const float* d_pack, int64_t total, const std
     for (const auto& t : tile)
         for (int64_t k = t.first; k < t.second; k += cb) {
             int64_t lo = k, hi = std::min(t.second, k + cb);
-            if (hi - lo <= MANY_SKINNY_CHUNKS) {
-                if (hi - (MANY_SKINNY_CHUNKS + 1) >= t.first) lo = hi - (MANY_SKINNY_CHUNKS + 1);      // the rest of a range: reaches back into chunks already computed (same bits) to stay on the tile side
-                else hi = lo + MANY_SKINNY_CHUNKS + 1;                                                   // a range shorter than that: forward, into its slot's zero chunks
+            if (hi - lo <= SD_SKINNY_CHUNKS) {
+                if (hi - (SD_SKINNY_CHUNKS + 1) >= t.first) lo = hi - (SD_SKINNY_CHUNKS + 1);      // the rest of a range: reaches back into chunks already computed (same bits) to stay on the tile side
+                else hi = lo + SD_SKINNY_CHUNKS + 1;                                                   // a range shorter than that: forward, into its slot's zero chunks
             }
             if (lo < 0 || hi > total - SD_MANY_GAP) SD_FAIL(c, SD_ERR_ARG, "packed segmentation batch [%lld,%lld) leaves the pack's %lld full chunks", (long long)lo, (long long)hi, (long long)(total - SD_MANY_GAP));
             if ((rc = run_segment(c, pack, lo, hi, d_seg + (size_t)lo * row))) return rc;
@@ -106,7 +99,7 @@ static int many_segment(sd_ctx* c, const float* d_pack, int64_t total, const std
     for (const PackRange& q : rec) {
         if (q.chunks <= 0 || q.full == q.chunks) continue;
         const DevWav view{d_pack + q.base * (int64_t)SD_HOP, q.n + q.lo * (int64_t)SD_HOP, q.lo * (int64_t)SD_HOP, true};      // zeros up to the end of the slot, at least 8000 of them behind a short last chunk
-        if ((rc = run_segment(c, view, q.lo + q.chunks - 1, q.lo + q.chunks, d_seg + (size_t)(q.base + q.chunks - 1) * row))) return rc;
+        if ((rc = run_segment(c, view, q.hi() - 1, q.hi(), d_seg + (size_t)(q.base + q.chunks - 1) * row))) return rc;
     }
     return SD_OK;
 }
@@ -118,10 +111,9 @@ int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vec
     int64_t longest = SD_WAV_PAD, longest_gap = 0;
     for (const PackRange& q : rec) {
         if (q.chunks <= 0) continue;
-        const int64_t slot = many_slot_chunks(q.n);
-        gaps.push_back(ManyGap{q.base + q.chunks, slot - q.chunks});
-        longest = std::max(longest, slot * (int64_t)SD_HOP);
-        longest_gap = std::max(longest_gap, slot - q.chunks);
+        gaps.push_back(ManyGap{q.base + q.chunks, q.slot() - q.chunks});
+        longest = std::max(longest, q.slot() * (int64_t)SD_HOP);
+        longest_gap = std::max(longest_gap, q.slot() - q.chunks);
     }
     rows.push_back(ManyRow{nullptr, 0, total * (int64_t)SD_HOP, SD_WAV_PAD});      // the zeroed floats behind the last slot (DevWav::padded)
 
@@ -156,9 +148,34 @@ int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vec
     return SD_OK;
 }
 
-// ------------------------------------------------------------------ the call
-enum { MANY_PCM_HOST, MANY_PCM_DEV, MANY_F32_HOST };
+// ------------------------------------------------------------------ finalize per output (common.h)
+int finalize_jobs(sd_ctx* c, int64_t J, sd_turn** turns, int64_t* n_turns, int32_t* status, const std::function<int(std::vector<FinalJob>&)>& infer)
+{
+    c->many_jobs.assign((size_t)J, ManyJob());
+    for (int64_t j = 0; j < J; ++j) { turns[j] = nullptr; n_turns[j] = 0; status[j] = SD_ERR_SHORT; c->many_jobs[(size_t)j].status = SD_ERR_SHORT; }
+    std::vector<FinalJob> jobs((size_t)J, FinalJob{nullptr, nullptr, 0, 0});
+    int rc;
+    if ((rc = infer(jobs))) return rc;
+    // one job after the other; what finalize leaves in the context is kept per job (sd_many_select)
+    for (int64_t j = 0; j < J; ++j) {
+        const FinalJob& q = jobs[(size_t)j];
+        if (q.chunks <= 0) continue;
+        std::vector<sd_turn> v;
+        rc = finalize(c, q.seg, q.emb, q.chunks, q.n, v);
+        ManyJob& job = c->many_jobs[(size_t)j];
+        status[j] = job.status = rc;
+        if (rc == SD_ERR_NUMERIC) continue;                    // this job's clustering; the others go on
+        if (rc == SD_OK) rc = turns_out(c, v, &turns[j], &n_turns[j]);
+        if (rc) {
+            for (int64_t k = 0; k < J; ++k) { sd_free_turns(turns[k]); turns[k] = nullptr; n_turns[k] = 0; }
+            return rc;
+        }
+        job.res = c->last;
+    }
+    return SD_OK;
+}
 
+// ------------------------------------------------------------------ the call
 static int many_run(sd_ctx* c, const void* const* src, int form, const int64_t* n, int64_t R, sd_turn** turns, int64_t* n_turns, int32_t* status, const char* who)
 {
     // refusals: nothing is touched
@@ -166,60 +183,41 @@ static int many_run(sd_ctx* c, const void* const* src, int form, const int64_t* 
     for (int64_t r = 0; r < R; ++r) if (!src[r]) SD_FAIL(c, SD_ERR_ARG, "%s: recording %lld is a null pointer", who, (long long)r);
     if (!c->dump_dir.empty()) SD_FAIL(c, SD_ERR_ARG, "%s: a dump directory is set (the step files describe one recording)", who);
     if (c->planted_n > 0) SD_FAIL(c, SD_ERR_ARG, "%s: a planted workload is set (its chunk range means one recording)", who);
-    std::vector<int64_t> base((size_t)R);
+    std::vector<PackRange> rec((size_t)R);      // a recording without a chunk: chunks = 0, no slot, status SD_ERR_SHORT
+    for (int64_t r = 0; r < R; ++r) { pack_range(n[r], 0, c->seg_batch_chunks, true, rec[(size_t)r]); rec[(size_t)r].owner = r; }
     int64_t total = 0;
-    if (many_plan(n, R, base.data(), &total)) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument (at most 2^20 recordings of at most 2^40 samples)", who);
+    if (pack_plan(rec.data(), R, &total)) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument (at most 2^20 recordings of at most 2^40 samples)", who);
     if (total > SD_MANY_MAX_CHUNKS) SD_FAIL(c, SD_ERR_ARG, "%s: %lld packed chunks (limit %d: the rows of one call are counted in int)", who, (long long)total, SD_MANY_MAX_CHUNKS);
     int rc;
     if ((rc = enrolled_refusal(c, SD_EMB_DIM, c->num_clusters, c->min_clusters, c->max_clusters))) return rc;
 
     const double t0 = now_ms();
     clear_stage_ms(c);
-    const int64_t cb = c->seg_batch_chunks < 1 ? 1 : c->seg_batch_chunks;
-    std::vector<PackRange> rec((size_t)R);
-    std::vector<ManyRow> rows;
-    int64_t src_samples = 0;
-    for (int64_t r = 0; r < R; ++r) {
-        PackRange& q = rec[(size_t)r];
-        q.n = n[r]; q.base = base[(size_t)r]; q.lo = 0;
-        q.chunks = sd_chunk_rule(q.n, &q.last_len);
-        q.full = (q.last_len > 0 && q.last_len < SD_CHUNK) ? q.chunks - 1 : q.chunks;
-        q.tile = q.chunks > 0 ? many_tile_chunks(q.full, cb) : 0;
-        if (q.chunks <= 0) continue;
-        rows.push_back(ManyRow{src[r], q.n, q.base * (int64_t)SD_HOP, many_slot_chunks(q.n) * (int64_t)SD_HOP});
-        src_samples += q.n;
-    }
-    c->many_jobs.assign((size_t)R, ManyJob());
-    for (int64_t r = 0; r < R; ++r) { turns[r] = nullptr; n_turns[r] = 0; status[r] = SD_ERR_SHORT; c->many_jobs[(size_t)r].status = SD_ERR_SHORT; }
-    if (total <= 0) { c->stage_ms[3] = now_ms() - t0; return SD_OK; }
-
-    if (form != MANY_PCM_DEV) {      // host rows: uploaded back to back, then packed like device rows
-        const size_t es = form == MANY_F32_HOST ? sizeof(float) : sizeof(int16_t);
-        WS(c, char, d_src, "many_src", (size_t)src_samples * es);
-        size_t off = 0;
-        for (ManyRow& w : rows) {
-            HIPCHK(c, hipMemcpyAsync(d_src + off, w.src, (size_t)w.n * es, hipMemcpyHostToDevice, c->stream));
-            w.src = d_src + off;
-            off += (size_t)w.n * es;
+    rc = finalize_jobs(c, R, turns, n_turns, status, [&](std::vector<FinalJob>& jobs) -> int {
+        if (total <= 0) return SD_OK;
+        std::vector<ManyRow> rows;
+        int64_t src_samples = 0;
+        for (const PackRange& q : rec) {
+            if (q.chunks <= 0) continue;
+            rows.push_back(ManyRow{src[q.owner], q.n, q.base * (int64_t)SD_HOP, q.slot() * (int64_t)SD_HOP});
+            src_samples += q.n;
         }
-    }
-    float *d_seg = nullptr, *d_emb = nullptr;
-    if ((rc = pack_infer(c, rows, form == MANY_F32_HOST ? 1 : 0, rec, total, t0, &d_seg, &d_emb))) return rc;
-
-    // finalize, one recording after the other; what it leaves in the context is kept per recording
-    auto give_back = [&]() { for (int64_t r = 0; r < R; ++r) { sd_free_turns(turns[r]); turns[r] = nullptr; n_turns[r] = 0; } };
-    for (int64_t r = 0; r < R; ++r) {
-        const PackRange& q = rec[(size_t)r];
-        if (q.chunks <= 0) continue;
-        std::vector<sd_turn> v;
-        rc = finalize(c, d_seg + (size_t)q.base * SD_FRAMES * 3, d_emb + (size_t)q.base * 3 * SD_EMB_DIM, q.chunks, q.n, v);
-        ManyJob& job = c->many_jobs[(size_t)r];
-        status[r] = job.status = rc;
-        if (rc == SD_ERR_NUMERIC) continue;                    // this recording's clustering; the others go on
-        if (rc == SD_OK) rc = turns_out(c, v, &turns[r], &n_turns[r]);
-        if (rc) { give_back(); return rc; }
-        job.res = c->last;
-    }
+        if (form != SD_PCM_DEV) {      // host rows: uploaded back to back, then packed like device rows
+            const size_t es = form == SD_F32_HOST ? sizeof(float) : sizeof(int16_t);
+            WS(c, char, d_src, "many_src", (size_t)src_samples * es);
+            size_t off = 0;
+            for (ManyRow& w : rows) {
+                HIPCHK(c, hipMemcpyAsync(d_src + off, w.src, (size_t)w.n * es, hipMemcpyHostToDevice, c->stream));
+                w.src = d_src + off;
+                off += (size_t)w.n * es;
+            }
+        }
+        float *d_seg = nullptr, *d_emb = nullptr;
+        if (int e = pack_infer(c, rows, form == SD_F32_HOST ? 1 : 0, rec, total, t0, &d_seg, &d_emb)) return e;
+        for (const PackRange& q : rec) jobs[(size_t)q.owner] = FinalJob{d_seg + (size_t)q.base * SD_FRAMES * 3, d_emb + (size_t)q.base * 3 * SD_EMB_DIM, q.chunks, q.n};
+        return SD_OK;
+    });
+    if (rc) return rc;
     c->stage_ms[3] = now_ms() - t0;
     return SD_OK;
 }
@@ -227,19 +225,19 @@ static int many_run(sd_ctx* c, const void* const* src, int form, const int64_t* 
 extern "C" int sd_diarize_many(sd_ctx* c, const int16_t* const* h_pcm, const int64_t* n, int64_t R, sd_turn** turns, int64_t* n_turns, int32_t* status)
 {
     ENTER(c);
-    return many_run(c, (const void* const*)h_pcm, MANY_PCM_HOST, n, R, turns, n_turns, status, "sd_diarize_many");
+    return many_run(c, (const void* const*)h_pcm, SD_PCM_HOST, n, R, turns, n_turns, status, "sd_diarize_many");
 }
 
 extern "C" int sd_diarize_many_dev(sd_ctx* c, const int16_t* const* d_pcm, const int64_t* n, int64_t R, sd_turn** turns, int64_t* n_turns, int32_t* status)
 {
     ENTER(c);
-    return many_run(c, (const void* const*)d_pcm, MANY_PCM_DEV, n, R, turns, n_turns, status, "sd_diarize_many_dev");
+    return many_run(c, (const void* const*)d_pcm, SD_PCM_DEV, n, R, turns, n_turns, status, "sd_diarize_many_dev");
 }
 
 extern "C" int sd_diarize_many_f32(sd_ctx* c, const float* const* h_wav, const int64_t* n, int64_t R, sd_turn** turns, int64_t* n_turns, int32_t* status)
 {
     ENTER(c);
-    return many_run(c, (const void* const*)h_wav, MANY_F32_HOST, n, R, turns, n_turns, status, "sd_diarize_many_f32");
+    return many_run(c, (const void* const*)h_wav, SD_F32_HOST, n, R, turns, n_turns, status, "sd_diarize_many_f32");
 }
 
 extern "C" int sd_many_select(sd_ctx* c, int64_t r)

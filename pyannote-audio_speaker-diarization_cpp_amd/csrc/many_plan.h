@@ -1,5 +1,7 @@
-// many_plan.h -- the host arithmetic of the packed layout of sd_diarize_many* (many.hip) and the list-file reader of `speakerDiarizer --many`.
-// Plain C++ without a GPU header: the library, the command line and the stand-alone sanitizer program (tools/many_plan_check.cpp) include the same text.
+// many_plan.h -- the host arithmetic of the packed layout of sd_diarize_many* (many.hip) and of the group calls of sd_stream (stream.hip): the slots,
+// the one record of a slot (PackRange) and the one statement of the skinny / tile side rule (seg_tile_chunks) with its constant; and the list-file
+// reader of `speakerDiarizer --many`.
+// Plain C++ without a GPU header: the library, the command line and the stand-alone sanitizer programs (tools/many_plan_check.cpp, tools/sanitize/) include the same text.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -38,6 +40,44 @@ inline int many_plan(const int64_t* n, int64_t R, int64_t* chunk_base, int64_t* 
     *total_chunks = base;
     return 0;
 }
+
+// launch_conv_gemm (conv_gemm.hip): a plain f32 GEMM of at most SD_SKINNY_MAX_ROWS rows goes to k_skinny_gemm, a larger one to the 128 x 128 tile, whose K
+// order differs in the last bits.  >= ROWTAB_MAX_ITEMS, so the per-utterance layers of an ECAPA batch always take the skinny kernel; PyanNet's dense
+// layers have 293 rows per chunk, so a batch of up to SD_SKINNY_CHUNKS = 13 chunks takes it too, and a chunk's last bits say which side its batch was on
+#define SD_SKINNY_MAX_ROWS 4096
+#define SD_SKINNY_CHUNKS (SD_SKINNY_MAX_ROWS / SD_FRAMES)
+#define SD_SEAL_CHUNKS 32      // a stream seals blocks of 32 chunks = 96 items = three whole reference embedding batches (sd.cpp:2429); the slots' unit too
+
+// The side rule: how many of the `full` full chunks from chunk lo of a recording on, counted from lo, are on the tile side in the path their rows have to
+// equal.  That path cuts them into batches of cb = seg_batch_chunks from lo on (run_segment); a batch of 13 chunks or fewer is on the skinny side.
+// The exception is the pending range of a stream (stream.hip: segment_pending): 1 .. 13 pending full chunks whose batch in the whole path -- it starts
+// at cb * (lo / cb) where cb is a multiple of 32 -- is past 13 chunks run in a batch padded to 14, on the tile side.  At lo = 0 it never fires: a
+// recording of a pack is the pending range of a stream with nothing sealed.
+inline int64_t seg_tile_chunks(int64_t lo, int64_t full, int64_t cb, bool pending)
+{
+    if (cb < 1) cb = 1;
+    if (full <= 0) return 0;
+    if (pending && full <= SD_SKINNY_CHUNKS) {
+        const int64_t whole = (cb >= SD_SEAL_CHUNKS && cb % SD_SEAL_CHUNKS == 0) ? lo + full - cb * (lo / cb) : full;      // (a cb that cuts blocks: no promise)
+        if (whole > SD_SKINNY_CHUNKS) return full;
+    }
+    if (cb <= SD_SKINNY_CHUNKS) return 0;
+    const int64_t rem = full % cb;
+    return (rem == 0 || rem > SD_SKINNY_CHUNKS) ? full : full - rem;
+}
+
+// One slot of a pack: a recording (lo = 0), or chunks [lo, lo + chunks) of a stream whose tail holds the audio from sample lo * 8000 on.  n, chunks,
+// full and last_len describe the slot's samples as a recording of its own (sd_chunk_rule); stream_book.h: pack_range builds one, pack_plan sets base
+struct PackRange {
+    int64_t owner;                 // index in the call's list: the recording, or the stream
+    int64_t lo, chunks;            // chunks of the owner
+    int64_t n;                     // samples of the range as a recording of its own
+    int64_t full, last_len;        // its full chunks; the length of its last chunk (80 000 unless short)
+    int64_t tile;                  // seg_tile_chunks: chunks [lo, lo + tile) are on the tile side, the other full ones on the skinny side (many.hip: many_segment)
+    int64_t base;                  // first chunk of the slot in the pack
+    int64_t hi() const { return lo + chunks; }
+    int64_t slot() const { return many_slot_chunks(n); }
+};
 
 // `speakerDiarizer --many LIST`: one wav path per line.  A trailing CR is dropped, an empty line and a line that starts with # are skipped; a NUL byte,
 // a line of more than 4096 bytes, an unreadable file or a list without a path is an error (false, message in err)

@@ -5,6 +5,8 @@
 // shard_infer on sub-ranges (pipeline.cpp); the device code here is the tail's compaction (16-bit pushes are appended by k_pcm_to_f32).
 // sd_stream_push_many* / sd_stream_turns_many serve many streams of one context in one call: the networks run over a pack of the streams' blocks and
 // pending ranges (many.hip: pack_infer), three table-driven copy kernels replace the per-stream launches; the single-stream entries keep their paths.
+// A range is a PackRange (many_plan.h) built by pack_range (stream_book.h), a copy a GroupRow (stream_book.h); which side of PyanNet's skinny limit a
+// chunk is on is seg_tile_chunks' word (many_plan.h) for the pack and for segment_pending alike; the finalize per stream is many.hip's finalize_jobs.
 #include "common.h"
 #include "stream_book.h"
 #include <algorithm>
@@ -32,8 +34,7 @@ __global__ void k_tail_move(const float* __restrict__ src, float* __restrict__ d
 //   k_group_append     the pushes of all streams to the ends of their tails, SD_TAIL_PAD zeros behind each (16-bit: x 1/32768 as k_pcm_to_f32; f32: copied)
 //   k_group_scatter    rows of the pack's scores / embeddings into the caches of the streams that own them
 //   k_group_tail_move  the compactions of all streams that sealed: k_tail_move per row
-// grid (x: a stride over the groups of a row, y: a stride over the table), 256 threads; 64-bit indices throughout
-struct GroupRow { const void* src; float* dst; int64_t len, room; };
+// grid (x: a stride over the groups of a row, y: a stride over the table), 256 threads; 64-bit indices throughout.  GroupRow: stream_book.h
 
 template <bool PCM> __device__ __forceinline__ float group_load(const void* src, int64_t j)
 {
@@ -84,8 +85,6 @@ __global__ void k_group_append(const GroupRow* __restrict__ rows, int R, int is_
 __global__ void k_group_scatter(const GroupRow* __restrict__ rows, int R) { group_copy<false>(rows, R, 0); }
 __global__ void k_group_tail_move(const GroupRow* __restrict__ rows, int R) { group_copy<false>(rows, R, SD_TAIL_PAD); }
 
-static_assert(SD_GROUP_SKINNY_CHUNKS == SD_SKINNY_MAX_ROWS / SD_FRAMES, "stream_book.h states the skinny limit of common.h without including it");
-
 struct sd_stream {
     sd_ctx* c = nullptr;
     StreamBook b;
@@ -115,14 +114,10 @@ struct HipDev {
     }
 };
 
-enum { PUSH_PCM_HOST, PUSH_PCM_DEV, PUSH_F32_HOST };
-
-// chunks of a PyanNet batch up to which its dense layers (LSTM layer 0's input projection, the two linear layers) take k_skinny_gemm, not the
-// 128 x 128 tile (common.h: SD_SKINNY_MAX_ROWS; 13); the two sum K in different orders, so a chunk's last bits say which one its batch took
-#define SD_SEG_SKINNY_CHUNKS (SD_SKINNY_MAX_ROWS / SD_FRAMES)
-
-// The segmentation step of the pending range [lo, hi), lo = sealed.  The whole path computes these chunks in a batch that starts at a multiple of
-// seg_batch_chunks; where that batch is past the skinny limit and the pending one alone is not, the pending chunks run in a batch padded to 14 chunks:
+// The segmentation step of the pending range [lo, hi), lo = sealed.  PyanNet's dense layers (LSTM layer 0's input projection, the two linear layers)
+// take k_skinny_gemm up to SD_SKINNY_CHUNKS = 13 chunks in a batch and the 128 x 128 tile above that; the two sum K in different orders.  The whole path
+// computes these chunks in a batch that starts at a multiple of seg_batch_chunks; where seg_tile_chunks (many_plan.h) says that batch is on the tile
+// side and the pending one alone is not, the pending chunks run in a batch padded to 14 chunks:
 // a scratch waveform with the pending full chunks' audio and zeros behind it, as a recording just long enough for 14 full chunks from lo on.  A row's
 // bits depend on its own chunk and on the kernels alone, so the real rows are the whole path's; the padding rows are thrown away.  The short last
 // chunk is a batch of one in both paths.
@@ -135,10 +130,8 @@ int segment_pending(sd_stream* s, const DevWav& tail, int64_t lo, int64_t hi)
     const int64_t total = sd_num_chunks(b.n, &last_len);
     const bool short_tail = hi == total && last_len > 0 && last_len < SD_CHUNK;
     const int64_t full_hi = short_tail ? hi - 1 : hi, mine = full_hi - lo;
-    const int64_t cb = c->seg_batch_chunks;
-    const int64_t whole = (cb >= SD_SEAL_CHUNKS && cb % SD_SEAL_CHUNKS == 0) ? full_hi - cb * (lo / cb) : mine;      // (a tuning value of seg_batch_chunks that cuts blocks: no promise)
-    if (mine <= 0 || mine > SD_SEG_SKINNY_CHUNKS || whole <= SD_SEG_SKINNY_CHUNKS) return run_segment(c, tail, lo, hi, d_seg);
-    const int64_t pad_hi = lo + SD_SEG_SKINNY_CHUNKS + 1;
+    if (mine <= 0 || mine > SD_SKINNY_CHUNKS || seg_tile_chunks(lo, mine, c->seg_batch_chunks, true) != mine) return run_segment(c, tail, lo, hi, d_seg);
+    const int64_t pad_hi = lo + SD_SKINNY_CHUNKS + 1;
     const int64_t n_pad = (pad_hi - 1) * SD_HOP + SD_CHUNK + 1;                      // the shortest recording whose chunks [lo, pad_hi) are all full
     const int64_t have = (full_hi - 1) * SD_HOP + SD_CHUNK - lo * SD_HOP;            // samples of the pending full chunks: all in the tail
     const int64_t len = n_pad - lo * SD_HOP;
@@ -216,12 +209,12 @@ int push_impl(sd_stream* s, const void* src, int64_t m, int kind, const char* wh
     int rc;
     if ((rc = book_reserve_tail(dev, b, m))) return rc;
     float* dst = b.tail_now() + b.tail_len();
-    if (kind == PUSH_F32_HOST) {
+    if (kind == SD_F32_HOST) {
         HIPCHK(c, hipMemcpyAsync(dst, src, (size_t)m * sizeof(float), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemsetAsync(dst + m, 0, SD_TAIL_PAD * sizeof(float), c->stream));
     } else {
         const int16_t* d_pcm = (const int16_t*)src;
-        if (kind == PUSH_PCM_HOST) {
+        if (kind == SD_PCM_HOST) {
             WS(c, int16_t, stage, "st_pcm", m);
             HIPCHK(c, hipMemcpyAsync(stage, src, (size_t)m * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
             d_pcm = stage;
@@ -307,16 +300,16 @@ int group_check(sd_ctx* c, sd_stream* const* s, int64_t S, const char* who)
 }
 
 // the ranges the streams contribute once stream i holds n_after[i] samples and `sealed[i]` sealed chunks, with their slots
-int group_ranges(sd_ctx* c, int64_t S, const int64_t* n_after, const int64_t* sealed, const char* wanted, bool pending, std::vector<GroupRange>& out, int64_t* total, const char* who)
+int group_ranges(sd_ctx* c, int64_t S, const int64_t* n_after, const int64_t* sealed, const char* wanted, bool pending, std::vector<PackRange>& out, int64_t* total, const char* who)
 {
     out.clear();
     for (int64_t i = 0; i < S; ++i) {
-        GroupRange r;
-        if (!wanted[i] || !group_range(n_after[i], sealed[i], c->seg_batch_chunks, pending, r)) continue;
-        r.stream = i;
+        PackRange r;
+        if (!wanted[i] || !pack_range(n_after[i], sealed[i], c->seg_batch_chunks, pending, r)) continue;
+        r.owner = i;
         out.push_back(r);
     }
-    if (group_plan(out.data(), (int64_t)out.size(), total)) SD_FAIL(c, SD_ERR_ARG, "%s: a range of more than 2^40 samples", who);
+    if (pack_plan(out.data(), (int64_t)out.size(), total)) SD_FAIL(c, SD_ERR_ARG, "%s: a range of more than 2^40 samples", who);
     if (*total > SD_MANY_MAX_CHUNKS) SD_FAIL(c, SD_ERR_ARG, "%s: %lld packed chunks (limit %d: the rows of one call are counted in int)", who, (long long)*total, SD_MANY_MAX_CHUNKS);
     return SD_OK;
 }
@@ -336,29 +329,23 @@ int group_launch(sd_ctx* c, int which, const GroupRow* d_rows, const std::vector
 
 // Both networks over the pack of these ranges, read from the tails; their rows into the owners' caches; and, for blocks that became sealed, the
 // compactions.  Tails, caches and compaction targets have their room (book_reserve_group).
-int group_infer(sd_ctx* c, sd_stream* const* s, const std::vector<GroupRange>& ranges, int64_t total, bool pending, bool window = false)
+int group_infer(sd_ctx* c, sd_stream* const* s, const std::vector<PackRange>& ranges, int64_t total, bool pending, bool window = false)
 {
     if (ranges.empty()) return SD_OK;
     const double t0 = now_ms();
     std::vector<ManyRow> rows;
-    std::vector<PackRange> rec;
-    for (const GroupRange& r : ranges) {
-        const StreamBook& b = s[r.stream]->b;
-        rows.push_back(ManyRow{b.tail_now(), r.n_eq, r.base * (int64_t)SD_HOP, r.slot * (int64_t)SD_HOP});
-        rec.push_back(PackRange{r.n_eq, r.hi - r.lo, r.base, r.full, r.last_len, r.tile, r.lo});
-    }
+    for (const PackRange& r : ranges) rows.push_back(ManyRow{s[r.owner]->b.tail_now(), r.n, r.base * (int64_t)SD_HOP, r.slot() * (int64_t)SD_HOP});
     float *d_seg = nullptr, *d_emb = nullptr;
     int rc;
-    if ((rc = pack_infer(c, rows, 1, rec, total, t0, &d_seg, &d_emb))) return rc;
+    if ((rc = pack_infer(c, rows, 1, ranges, total, t0, &d_seg, &d_emb))) return rc;
     std::vector<GroupRow> seg, emb, mov;
-    for (const GroupRange& r : ranges) {
-        StreamBook& b = s[r.stream]->b;
-        const int64_t cnt = r.hi - r.lo;
-        seg.push_back(GroupRow{d_seg + r.base * SD_SEG_ROW, b.seg + r.lo * SD_SEG_ROW, cnt * SD_SEG_ROW, (b.cache_cap - r.lo) * SD_SEG_ROW});
-        emb.push_back(GroupRow{d_emb + r.base * SD_EMB_ROW, b.emb + r.lo * SD_EMB_ROW, cnt * SD_EMB_ROW, (b.cache_cap - r.lo) * SD_EMB_ROW});
-        GroupMove mv;
+    for (const PackRange& r : ranges) {
+        StreamBook& b = s[r.owner]->b;
+        seg.push_back(GroupRow{d_seg + r.base * SD_SEG_ROW, b.seg + r.lo * SD_SEG_ROW, r.chunks * SD_SEG_ROW, (b.cache_cap - r.lo) * SD_SEG_ROW});
+        emb.push_back(GroupRow{d_emb + r.base * SD_EMB_ROW, b.emb + r.lo * SD_EMB_ROW, r.chunks * SD_EMB_ROW, (b.cache_cap - r.lo) * SD_EMB_ROW});
+        GroupRow mv;
         if (pending) b.pending_n = b.n;
-        else if (book_seal_planned(b, r.hi, mv)) mov.push_back(GroupRow{mv.src, mv.dst, mv.len, mv.room});
+        else if (book_seal_planned(b, r.hi(), mv)) mov.push_back(mv);
     }
     const size_t R = ranges.size();
     WS(c, GroupRow, d_tab, "stg_tab", 3 * R);
@@ -371,9 +358,9 @@ int group_infer(sd_ctx* c, sd_stream* const* s, const std::vector<GroupRange>& r
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!pending) {
         HipDev dev{c};
-        for (const GroupRange& r : ranges) book_seal_trim(dev, s[r.stream]->b);
-        for (const GroupRange& r : ranges)      // the window's policy, per stream, behind the group's launches
-            if (window && s[r.stream]->window >= 0 && (rc = forget_to(s[r.stream], s[r.stream]->window))) return rc;
+        for (const PackRange& r : ranges) book_seal_trim(dev, s[r.owner]->b);
+        for (const PackRange& r : ranges)      // the window's policy, per stream, behind the group's launches
+            if (window && s[r.owner]->window >= 0 && (rc = forget_to(s[r.owner], s[r.owner]->window))) return rc;
     }
     return SD_OK;
 }
@@ -392,7 +379,7 @@ int push_many_impl(sd_ctx* c, sd_stream* const* s, const void* const* src, const
     std::vector<int64_t> n_after((size_t)S), sealed((size_t)S);
     std::vector<char> wanted((size_t)S, 1);
     for (int64_t i = 0; i < S; ++i) { n_after[(size_t)i] = s[i]->b.n + n[i]; sealed[(size_t)i] = s[i]->b.sealed; }
-    std::vector<GroupRange> ranges;
+    std::vector<PackRange> ranges;
     int64_t total = 0;
     if ((rc = group_ranges(c, S, n_after.data(), sealed.data(), wanted.data(), false, ranges, &total, who))) return rc;
     if (pushed == 0) return SD_OK;
@@ -402,12 +389,12 @@ int push_many_impl(sd_ctx* c, sd_stream* const* s, const void* const* src, const
     // growth before the first kernel: a failed allocation leaves every stream what it was
     HipDev dev{c};
     std::vector<char> busy((size_t)S, 0);
-    for (const GroupRange& r : ranges) busy[(size_t)r.stream] = 1;
+    for (const PackRange& r : ranges) busy[(size_t)r.owner] = 1;
     for (int64_t i = 0; i < S; ++i)
         if ((n[i] > 0 || busy[(size_t)i]) && (rc = book_reserve_group(dev, s[i]->b, n[i]))) return rc;
 
     // the samples of all streams: host ones uploaded back to back (each placed so that it is as aligned as its place in the tail), one conversion launch
-    const size_t es = kind == PUSH_F32_HOST ? sizeof(float) : sizeof(int16_t);
+    const size_t es = kind == SD_F32_HOST ? sizeof(float) : sizeof(int16_t);
     std::vector<GroupRow> rows;
     std::vector<size_t> off;
     size_t stage_len = 0;
@@ -422,7 +409,7 @@ int push_many_impl(sd_ctx* c, sd_stream* const* s, const void* const* src, const
         stage_len += (size_t)n[i];
     }
     WS(c, GroupRow, d_tab, "stg_tab", rows.size());
-    if (kind != PUSH_PCM_DEV) {
+    if (kind != SD_PCM_DEV) {
         WS(c, char, stage, "stg_src", stage_len * es);
         for (size_t q = 0; q < rows.size(); ++q) {
             HIPCHK(c, hipMemcpyAsync(stage + off[q] * es, rows[q].src, (size_t)rows[q].len * es, hipMemcpyHostToDevice, c->stream));
@@ -430,7 +417,7 @@ int push_many_impl(sd_ctx* c, sd_stream* const* s, const void* const* src, const
         }
     }
     HIPCHK(c, hipMemcpy(d_tab, rows.data(), rows.size() * sizeof(GroupRow), hipMemcpyHostToDevice));
-    if ((rc = group_launch(c, 0, d_tab, rows, kind == PUSH_F32_HOST ? 1 : 0))) return rc;
+    if ((rc = group_launch(c, 0, d_tab, rows, kind == SD_F32_HOST ? 1 : 0))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));      // the callers' buffers may go: once for all streams
     for (int64_t i = 0; i < S; ++i) s[i]->b.n += n[i];
 
@@ -451,7 +438,7 @@ int turns_many_impl(sd_ctx* c, sd_stream* const* s, int64_t S, sd_turn** turns, 
     std::vector<int64_t> n_now((size_t)S), sealed((size_t)S);
     std::vector<char> all((size_t)S, 1), stale((size_t)S, 0);
     for (int64_t i = 0; i < S; ++i) { n_now[(size_t)i] = s[i]->b.n; sealed[(size_t)i] = s[i]->b.sealed; }
-    std::vector<GroupRange> to_seal, to_infer;      // (to_seal: nothing unless an earlier push failed half way)
+    std::vector<PackRange> to_seal, to_infer;      // (to_seal: nothing unless an earlier push failed half way)
     int64_t seal_total = 0, total = 0;
     if ((rc = group_ranges(c, S, n_now.data(), sealed.data(), all.data(), false, to_seal, &seal_total, who))) return rc;
     for (int64_t i = 0; i < S; ++i) {
@@ -463,29 +450,16 @@ int turns_many_impl(sd_ctx* c, sd_stream* const* s, int64_t S, sd_turn** turns, 
 
     const double t0 = now_ms();
     clear_stage_ms(c);
-    c->many_jobs.assign((size_t)S, ManyJob());
-    for (int64_t i = 0; i < S; ++i) { turns[i] = nullptr; n_turns[i] = 0; status[i] = SD_ERR_SHORT; c->many_jobs[(size_t)i].status = SD_ERR_SHORT; }
-    HipDev dev{c};
-    for (const GroupRange& r : to_seal) if ((rc = book_reserve_group(dev, s[r.stream]->b, 0))) return rc;
-    for (const GroupRange& r : to_infer) if ((rc = book_reserve_group(dev, s[r.stream]->b, 0))) return rc;
-    if ((rc = group_infer(c, s, to_seal, seal_total, false))) return rc;
-    if ((rc = group_infer(c, s, to_infer, total, true))) return rc;
-
-    // the unchanged finalize, one stream after the other; what it leaves in the context is kept per stream (sd_many_select)
-    auto give_back = [&]() { for (int64_t i = 0; i < S; ++i) { sd_free_turns(turns[i]); turns[i] = nullptr; n_turns[i] = 0; } };
-    for (int64_t i = 0; i < S; ++i) {
-        const StreamBook& b = s[i]->b;
-        const int64_t chunks = sd_num_chunks(b.n, nullptr);
-        if (chunks <= 0) continue;
-        std::vector<sd_turn> v;
-        rc = finalize(c, b.seg, b.emb, chunks, b.n, v);
-        ManyJob& job = c->many_jobs[(size_t)i];
-        status[i] = job.status = rc;
-        if (rc == SD_ERR_NUMERIC) continue;                    // this stream's clustering; the others go on
-        if (rc == SD_OK) rc = turns_out(c, v, &turns[i], &n_turns[i]);
-        if (rc) { give_back(); return rc; }
-        job.res = c->last;
-    }
+    rc = finalize_jobs(c, S, turns, n_turns, status, [&](std::vector<FinalJob>& jobs) -> int {
+        HipDev dev{c};
+        for (const PackRange& r : to_seal) if (int e = book_reserve_group(dev, s[r.owner]->b, 0)) return e;
+        for (const PackRange& r : to_infer) if (int e = book_reserve_group(dev, s[r.owner]->b, 0)) return e;
+        if (int e = group_infer(c, s, to_seal, seal_total, false)) return e;
+        if (int e = group_infer(c, s, to_infer, total, true)) return e;
+        for (int64_t i = 0; i < S; ++i) jobs[(size_t)i] = FinalJob{s[i]->b.seg, s[i]->b.emb, sd_num_chunks(s[i]->b.n, nullptr), s[i]->b.n};
+        return SD_OK;
+    });
+    if (rc) return rc;
     c->stage_ms[3] = now_ms() - t0;
     return SD_OK;
 }
@@ -509,19 +483,19 @@ extern "C" int sd_stream_push_many(sd_stream* const* s, const int16_t* const* h_
 {
     if (!group_list_ok(s, S)) return SD_ERR_ARG;
     ENTER(s[0]->c);
-    return group_guard(s, S, push_many_impl(s[0]->c, s, (const void* const*)h_pcm, n, S, PUSH_PCM_HOST, "sd_stream_push_many"));
+    return group_guard(s, S, push_many_impl(s[0]->c, s, (const void* const*)h_pcm, n, S, SD_PCM_HOST, "sd_stream_push_many"));
 }
 extern "C" int sd_stream_push_many_dev(sd_stream* const* s, const int16_t* const* d_pcm, const int64_t* n, int64_t S)
 {
     if (!group_list_ok(s, S)) return SD_ERR_ARG;
     ENTER(s[0]->c);
-    return group_guard(s, S, push_many_impl(s[0]->c, s, (const void* const*)d_pcm, n, S, PUSH_PCM_DEV, "sd_stream_push_many_dev"));
+    return group_guard(s, S, push_many_impl(s[0]->c, s, (const void* const*)d_pcm, n, S, SD_PCM_DEV, "sd_stream_push_many_dev"));
 }
 extern "C" int sd_stream_push_many_f32(sd_stream* const* s, const float* const* h_wav, const int64_t* n, int64_t S)
 {
     if (!group_list_ok(s, S)) return SD_ERR_ARG;
     ENTER(s[0]->c);
-    return group_guard(s, S, push_many_impl(s[0]->c, s, (const void* const*)h_wav, n, S, PUSH_F32_HOST, "sd_stream_push_many_f32"));
+    return group_guard(s, S, push_many_impl(s[0]->c, s, (const void* const*)h_wav, n, S, SD_F32_HOST, "sd_stream_push_many_f32"));
 }
 extern "C" int sd_stream_turns_many(sd_stream* const* s, int64_t S, sd_turn** turns, int64_t* n_turns, int32_t* status)
 {
@@ -560,19 +534,19 @@ extern "C" int sd_stream_push(sd_stream* s, const int16_t* h_pcm, int64_t n)
 {
     if (!s) return SD_ERR_ARG;
     ENTER(s->c);
-    return guard(s, push_impl(s, h_pcm, n, PUSH_PCM_HOST, "sd_stream_push"));
+    return guard(s, push_impl(s, h_pcm, n, SD_PCM_HOST, "sd_stream_push"));
 }
 extern "C" int sd_stream_push_dev(sd_stream* s, const int16_t* d_pcm, int64_t n)
 {
     if (!s) return SD_ERR_ARG;
     ENTER(s->c);
-    return guard(s, push_impl(s, d_pcm, n, PUSH_PCM_DEV, "sd_stream_push_dev"));
+    return guard(s, push_impl(s, d_pcm, n, SD_PCM_DEV, "sd_stream_push_dev"));
 }
 extern "C" int sd_stream_push_f32(sd_stream* s, const float* h_wav, int64_t n)
 {
     if (!s) return SD_ERR_ARG;
     ENTER(s->c);
-    return guard(s, push_impl(s, h_wav, n, PUSH_F32_HOST, "sd_stream_push_f32"));
+    return guard(s, push_impl(s, h_wav, n, SD_F32_HOST, "sd_stream_push_f32"));
 }
 extern "C" int sd_stream_turns(sd_stream* s, sd_turn** turns, int64_t* n_turns)
 {

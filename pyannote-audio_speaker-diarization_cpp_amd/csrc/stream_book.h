@@ -1,6 +1,7 @@
-// stream_book.h -- host bookkeeping of an sd_stream (stream.hip): the sealing rule, the offsets of the device tail and the growth of the
-// score / embedding cache.  No HIP in here: every device operation goes through the Dev parameter, so the same code runs against
-// malloc'd memory under AddressSanitizer in tools/sanitize/stream_book_main.cpp.
+// stream_book.h -- host bookkeeping of an sd_stream (stream.hip): the sealing rule, the offsets of the device tail, the growth of the
+// score / embedding cache, and the ranges of streams -- or recordings (many.hip) -- that share a pack: pack_range, pack_plan.  The record of a range
+// (PackRange) and the side rule (seg_tile_chunks) are many_plan.h's.  No HIP in here: every device operation goes through the Dev parameter, so the
+// same code runs against malloc'd memory under AddressSanitizer in tools/sanitize/stream_*_main.cpp.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -9,7 +10,6 @@
 #include "many_plan.h"
 
 #define SD_TAIL_PAD 512                                    // zeroed floats behind the last sample: SD_WAV_PAD, what DevWav::padded promises (common.h; stream.hip asserts the two agree)
-#define SD_SEAL_CHUNKS 32                                  // 96 items = three whole reference embedding batches (sd.cpp:2429)
 #define SD_SEG_ROW ((int64_t)SD_FRAMES * SD_SPEAKERS)      // floats of one chunk in the score cache
 #define SD_EMB_ROW ((int64_t)SD_SPEAKERS * SD_EMB_DIM)     // ... in the embedding cache
 #define SD_TAIL_SPARE_MAX ((int64_t)1 << 22)               // a spare tail buffer above this many floats is given back after a compaction
@@ -73,24 +73,50 @@ template <class Dev> int book_reserve_cache(Dev& d, StreamBook& b, int64_t chunk
     return 0;
 }
 
-// chunks [sealed, to) have their final rows: the audio in front of sample to * 8000 goes.  Source and destination of that move overlap
-// inside one buffer, so it goes to the second one and the two change places.
+// the second tail buffer, the compaction target, can take `keep` samples and their padding; what it held is nobody's
+template <class Dev> int book_reserve_spare(Dev& d, StreamBook& b, int64_t keep)
+{
+    const int o = 1 - b.cur;
+    if (b.tail_cap[o] >= keep + SD_TAIL_PAD) return 0;
+    if (b.tail[o]) d.release(b.tail[o]);
+    b.tail[o] = nullptr; b.tail_cap[o] = 0;
+    const int64_t cap = 2 * (keep + SD_TAIL_PAD);
+    void* p = nullptr;
+    if (int rc = d.alloc(&p, (size_t)cap * sizeof(float))) return rc;
+    b.tail[o] = (float*)p; b.tail_cap[o] = cap;
+    return 0;
+}
+
+// A copy as a row of a table (stream.hip: group_copy): dst[0, len) = src[0, len), zeros behind as the kernel says, nothing at or behind dst[room]
+struct GroupRow { const void* src; float* dst; int64_t len, room; };
+
+// chunks [sealed, to) have their final rows: the audio in front of sample to * 8000 goes.  Source and destination of that move overlap inside one
+// buffer, so it goes to the second one and the two change places.  In steps, so that a group call can make ONE launch of the moves of all its streams:
+// the move as a row (SD_TAIL_PAD zeros behind) and the book after it -- the target has its room (book_reserve_spare) -- ...
+inline bool book_seal_planned(StreamBook& b, int64_t to, GroupRow& mv)
+{
+    if (to <= b.sealed) return false;
+    const int64_t drop = (to - b.sealed) * SD_HOP, keep = b.tail_len() - drop;      // keep > 72 000: chunk to - 1 ends in front of n
+    const int o = 1 - b.cur;
+    mv = GroupRow{b.tail[b.cur] + drop, b.tail[o], keep, b.tail_cap[o]};
+    b.cur = o; b.sealed = to; b.pending_n = -1;
+    return true;
+}
+// ... and once the move has been issued: a spare buffer above SD_TAIL_SPARE_MAX floats is given back (release waits for the device)
+template <class Dev> void book_seal_trim(Dev& d, StreamBook& b)
+{
+    const int o = 1 - b.cur;
+    if (b.tail_cap[o] > SD_TAIL_SPARE_MAX) { d.release(b.tail[o]); b.tail[o] = nullptr; b.tail_cap[o] = 0; }
+}
+// the single stream's seal.  A failed allocation leaves n, sealed, cur, the tail's samples and the caches as they were
 template <class Dev> int book_seal(Dev& d, StreamBook& b, int64_t to)
 {
     if (to <= b.sealed) return 0;
-    const int64_t drop = (to - b.sealed) * SD_HOP, keep = b.tail_len() - drop;      // keep > 72 000: chunk to - 1 ends in front of n
-    const int o = 1 - b.cur;
-    if (b.tail_cap[o] < keep + SD_TAIL_PAD) {
-        if (b.tail[o]) d.release(b.tail[o]);
-        b.tail[o] = nullptr; b.tail_cap[o] = 0;
-        const int64_t cap = 2 * (keep + SD_TAIL_PAD);
-        void* p = nullptr;
-        if (int rc = d.alloc(&p, (size_t)cap * sizeof(float))) return rc;
-        b.tail[o] = (float*)p; b.tail_cap[o] = cap;
-    }
-    if (int rc = d.move_tail(b.tail[o], b.tail[b.cur] + drop, keep)) return rc;
-    b.cur = o; b.sealed = to; b.pending_n = -1;
-    if (b.tail_cap[1 - o] > SD_TAIL_SPARE_MAX) { d.release(b.tail[1 - o]); b.tail[1 - o] = nullptr; b.tail_cap[1 - o] = 0; }
+    if (int rc = book_reserve_spare(d, b, b.tail_len() - (to - b.sealed) * SD_HOP)) return rc;
+    GroupRow mv;
+    book_seal_planned(b, to, mv);
+    if (int rc = d.move_tail(mv.dst, (const float*)mv.src, mv.len)) return rc;
+    book_seal_trim(d, b);
     return 0;
 }
 
@@ -132,68 +158,42 @@ template <class Dev> void book_release(Dev& d, StreamBook& b)
     b.seg = b.emb = nullptr; b.cache_cap = 0;
 }
 
-// ------------------------------------------------------------------ groups of streams (sd_stream_push_many*, sd_stream_turns_many)
+// ------------------------------------------------------------------ ranges and their slots (sd_diarize_many*; sd_stream_push_many*, sd_stream_turns_many)
 // What a group call infers for one stream is a RANGE: chunks [lo, hi) of the stream, lo = sealed (a multiple of 32), audio in the tail from sample
 // lo * 8000 on.  A block that became sealed has full chunks only; the pending range ends at the stream's last chunk, which may be short.  A range
-// is packed as a recording of n_eq samples (many_plan.h): n_eq = the samples behind lo * 8000 for the pending range, (hi - lo + 9) * 8000 -- the
-// end of chunk hi - 1 -- for a sealed one, so sd_chunk_rule(n_eq) is hi - lo with the stream's own last length and the slot is roundup32(hi - lo + 9).
-#define SD_GROUP_SKINNY_CHUNKS 13      // chunks of a PyanNet batch up to which its dense layers take the skinny kernel (common.h: SD_SKINNY_MAX_ROWS / 293; stream.hip asserts it)
-struct GroupRange {
-    int64_t stream;                // index in the call's list
-    int64_t lo, hi;                // chunks of the stream
-    int64_t n_eq;                  // samples of the range as a recording of its own; all of them are in the tail
-    int64_t full, last_len;        // full chunks of the range; the length of its last chunk (80 000 unless short)
-    int64_t tile;                  // chunks [lo, lo + tile) are on the tile side of PyanNet's dense layers in the single-stream path, the other full ones on the skinny side
-    int64_t base, slot;            // chunks of the pack (group_plan)
-};
-
-// the side rule.  The single path cuts the full chunks of a range into batches of cb = seg_batch_chunks from lo on (run_segment); a batch of 13
-// chunks or fewer is on the skinny side.  The exception is segment_pending's: 1 .. 13 pending full chunks whose batch in the whole path -- it
-// starts at cb * (lo / cb) where cb is a multiple of 32 -- is past 13 chunks run in a batch padded to 14, on the tile side.
-inline int64_t group_tile_chunks(int64_t lo, int64_t full, int64_t cb, bool pending)
-{
-    if (cb < 1) cb = 1;
-    if (full <= 0) return 0;
-    if (pending && full <= SD_GROUP_SKINNY_CHUNKS) {
-        const int64_t whole = (cb >= SD_SEAL_CHUNKS && cb % SD_SEAL_CHUNKS == 0) ? lo + full - cb * (lo / cb) : full;
-        if (whole > SD_GROUP_SKINNY_CHUNKS) return full;
-    }
-    if (cb <= SD_GROUP_SKINNY_CHUNKS) return 0;
-    const int64_t rem = full % cb;
-    return (rem == 0 || rem > SD_GROUP_SKINNY_CHUNKS) ? full : full - rem;
-}
+// is packed as a recording of r.n samples (many_plan.h): the samples behind lo * 8000 for the pending range, (hi - lo + 9) * 8000 -- the end of
+// chunk hi - 1 -- for a sealed one, so sd_chunk_rule(r.n) is hi - lo with the stream's own last length and the slot is roundup32(hi - lo + 9).
+// A recording of sd_diarize_many* is the pending range of a stream with nothing sealed.
 
 // the range a stream of n samples with `sealed` sealed chunks contributes: pending = its chunks [sealed, total), else the blocks [sealed, sealed(n)).
-// false: none (no chunk yet / nothing became sealed)
-inline bool group_range(int64_t n, int64_t sealed, int64_t cb, bool pending, GroupRange& r)
+// false, and r.chunks = 0: none (no chunk yet / nothing became sealed)
+inline bool pack_range(int64_t n, int64_t sealed, int64_t cb, bool pending, PackRange& r)
 {
-    r = GroupRange{};
+    r = PackRange{};
     r.lo = sealed;
     if (pending) {
-        r.n_eq = n - sealed * SD_HOP;
-        const int64_t chunks = sd_chunk_rule(r.n_eq, &r.last_len);
-        if (n < 2 || chunks <= 0) return false;
-        r.hi = sealed + chunks;
-        r.full = (r.last_len > 0 && r.last_len < SD_CHUNK) ? chunks - 1 : chunks;
+        r.n = n - sealed * SD_HOP;
+        r.chunks = sd_chunk_rule(r.n, &r.last_len);
+        r.full = (r.last_len > 0 && r.last_len < SD_CHUNK) ? r.chunks - 1 : r.chunks;
     } else {
-        r.hi = stream_sealed_chunks(n);
-        if (r.hi <= sealed) return false;
-        r.n_eq = (r.hi - sealed + SD_MANY_GAP) * SD_HOP;
-        r.full = r.hi - sealed; r.last_len = SD_CHUNK;
+        r.chunks = stream_sealed_chunks(n) - sealed;
+        r.n = (r.chunks + SD_MANY_GAP) * SD_HOP;
+        r.full = r.chunks; r.last_len = SD_CHUNK;
     }
-    r.tile = group_tile_chunks(r.lo, r.full, cb, pending);
+    if (r.chunks <= 0) { r.chunks = 0; return false; }
+    r.tile = seg_tile_chunks(r.lo, r.full, cb, pending);
     return true;
 }
 
-// slots for the ranges by many_plan's rule; 0, or 1 where many_plan refuses
-inline int group_plan(GroupRange* r, int64_t count, int64_t* total_chunks)
+// slots for the ranges by many_plan's rule, base in place; 0, or 1 where many_plan refuses
+inline int pack_plan(PackRange* r, int64_t count, int64_t* total_chunks)
 {
     *total_chunks = 0;
     if (count < 1) return 0;
     std::vector<int64_t> n((size_t)count), base((size_t)count);
-    for (int64_t i = 0; i < count; ++i) n[(size_t)i] = r[i].n_eq;
+    for (int64_t i = 0; i < count; ++i) n[(size_t)i] = r[i].n;
     if (many_plan(n.data(), count, base.data(), total_chunks)) return 1;
-    for (int64_t i = 0; i < count; ++i) { r[i].base = base[(size_t)i]; r[i].slot = many_slot_chunks(r[i].n_eq); }
+    for (int64_t i = 0; i < count; ++i) r[i].base = base[(size_t)i];
     return 0;
 }
 
@@ -205,34 +205,5 @@ template <class Dev> int book_reserve_group(Dev& d, StreamBook& b, int64_t more)
     if (int rc = book_reserve_tail(d, b, more)) return rc;
     const int64_t n = b.n + more, to = stream_sealed_chunks(n);
     if (int rc = book_reserve_cache(d, b, sd_chunk_rule(n, nullptr))) return rc;
-    if (to <= b.sealed) return 0;
-    const int64_t keep = n - to * SD_HOP;
-    const int o = 1 - b.cur;
-    if (b.tail_cap[o] >= keep + SD_TAIL_PAD) return 0;
-    if (b.tail[o]) d.release(b.tail[o]);
-    b.tail[o] = nullptr; b.tail_cap[o] = 0;
-    const int64_t cap = 2 * (keep + SD_TAIL_PAD);
-    void* p = nullptr;
-    if (int rc = d.alloc(&p, (size_t)cap * sizeof(float))) return rc;
-    b.tail[o] = (float*)p; b.tail_cap[o] = cap;
-    return 0;
-}
-
-// book_seal in two steps around one launch for all streams: the move it would make, as a row of that launch's table (dst[0, len) = src[0, len),
-// SD_TAIL_PAD zeros behind, nothing at or behind dst[room]), and the book after it.  The target was reserved by book_reserve_group.
-struct GroupMove { const float* src; float* dst; int64_t len, room; };
-inline bool book_seal_planned(StreamBook& b, int64_t to, GroupMove& mv)
-{
-    if (to <= b.sealed) return false;
-    const int64_t drop = (to - b.sealed) * SD_HOP, keep = b.tail_len() - drop;
-    const int o = 1 - b.cur;
-    mv = GroupMove{b.tail[b.cur] + drop, b.tail[o], keep, b.tail_cap[o]};
-    b.cur = o; b.sealed = to; b.pending_n = -1;
-    return true;
-}
-// ... and once the launch has been issued: a spare buffer above SD_TAIL_SPARE_MAX floats is given back (release waits for the device)
-template <class Dev> void book_seal_trim(Dev& d, StreamBook& b)
-{
-    const int o = 1 - b.cur;
-    if (b.tail_cap[o] > SD_TAIL_SPARE_MAX) { d.release(b.tail[o]); b.tail[o] = nullptr; b.tail_cap[o] = 0; }
+    return to <= b.sealed ? 0 : book_reserve_spare(d, b, n - to * SD_HOP);
 }

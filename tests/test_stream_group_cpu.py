@@ -113,6 +113,30 @@ def cases():
     return out
 
 
+def test_the_one_side_rule_under_address_and_ub_sanitizers(tmp_path):
+    """seg_tile_chunks (csrc/many_plan.h), the one statement of the skinny / tile side rule that packs, groups and the single stream's pending batch
+    read, against tile_of above, case by case; and the fact that lets a recording of sd_diarize_many be the pending range of a stream with nothing
+    sealed: at lo = 0 the pending exception never fires"""
+    exe = str(tmp_path / "stream_group_asan")
+    b = subprocess.run(["bash", os.path.join(ROOT, "tools", "sanitize", "build_stream_group.sh"), exe], capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stderr[-3000:]
+    cs = [(lo, full, cb, p) for cb in (1, 7, 13, 14, 20, 32, 33, 64, 4096) for full in range(81) for lo in (0, 32, 64, 4064, 4096, 8192) for p in (0, 1)]
+    path = tmp_path / "tiles.txt"
+    path.write_text("".join("%d %d %d %d\n" % c for c in cs))
+    out = subprocess.run([exe, "tile", str(path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "Sanitizer" not in out.stderr and "runtime error" not in out.stderr, (out.stdout[-300:], out.stderr[-2000:])
+    lines = out.stdout.splitlines()
+    assert len(lines) == len(cs)
+    padded = 0
+    for line, (lo, full, cb, p) in zip(lines, cs):
+        want = tile_of(lo, full, cb, bool(p))
+        assert line == str(want), (lo, full, cb, p)
+        padded += 0 < want <= SKINNY
+        if lo == 0:
+            assert tile_of(0, full, cb, True) == tile_of(0, full, cb, False), (full, cb)
+    assert padded >= 1      # the batch padded to 14 occurs
+
+
 def test_group_planning_under_address_and_ub_sanitizers(tmp_path):
     """ranges to slots and the side of a range against the statement above, over random stream states and n at the exact sealing boundaries; growth
     before launch, the appended tails, the scattered rows and the planned compactions on malloc'd memory of exactly the size asked for: two seeds,

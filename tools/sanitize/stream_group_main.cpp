@@ -1,8 +1,9 @@
-// The host planning of the group calls of sd_stream (csrc/stream_book.h: group_range, group_tile_chunks, group_plan, book_reserve_group,
-// book_seal_planned, book_seal_trim) against malloc'd memory, for AddressSanitizer + UBSan.  CPU only; tools/sanitize/build_stream_group.sh builds it.
+// The host planning of the group calls of sd_stream (csrc/many_plan.h: seg_tile_chunks, PackRange; csrc/stream_book.h: pack_range, pack_plan,
+// book_reserve_group, book_seal_planned, book_seal_trim) against malloc'd memory, for AddressSanitizer + UBSan.  CPU only; tools/sanitize/build_stream_group.sh builds it.
 //   stream_group plan <file>   every line of <file> is a case "cb pending S  n_0 sealed_0 ... n_{S-1} sealed_{S-1}"; prints per case
 //                              "case <total> <ranges>" and per range "r <stream> <lo> <hi> <n_eq> <full> <last_len> <tile> <base> <slot>":
 //                              tests/test_stream_group_cpu.py compares them with its own statement of the rules
+//   stream_group tile <file>   every line of <file> is a case "lo full cb pending"; prints seg_tile_chunks of it, one line per case
 //   stream_group run [seed]    groups of streams through random rounds of pushes, what stream.hip does around the books with the device work done by
 //                              host loops that touch exactly the floats the table rows name -> "stream_group ok: ..." and exit 0, or the first mismatch
 #include <cstdio>
@@ -35,22 +36,32 @@ static int plan_file(const char* path)
     CHECK(f, "cannot open %s", path);
     long long cb, pending, S;
     while (fscanf(f, "%lld %lld %lld", &cb, &pending, &S) == 3) {
-        std::vector<GroupRange> ranges;
+        std::vector<PackRange> ranges;
         for (long long i = 0; i < S; ++i) {
             long long n, sealed;
             CHECK(fscanf(f, "%lld %lld", &n, &sealed) == 2, "short case");
-            GroupRange r;
-            if (!group_range(n, sealed, cb, pending != 0, r)) continue;
-            r.stream = i;
+            PackRange r;
+            if (!pack_range(n, sealed, cb, pending != 0, r)) continue;
+            r.owner = i;
             ranges.push_back(r);
         }
         int64_t total = 0;
-        CHECK(group_plan(ranges.data(), (int64_t)ranges.size(), &total) == 0, "group_plan refused a case");
+        CHECK(pack_plan(ranges.data(), (int64_t)ranges.size(), &total) == 0, "pack_plan refused a case");
         printf("case %lld %zu\n", (long long)total, ranges.size());
-        for (const GroupRange& r : ranges)
-            printf("r %lld %lld %lld %lld %lld %lld %lld %lld %lld\n", (long long)r.stream, (long long)r.lo, (long long)r.hi, (long long)r.n_eq, (long long)r.full,
-                   (long long)r.last_len, (long long)r.tile, (long long)r.base, (long long)r.slot);
+        for (const PackRange& r : ranges)
+            printf("r %lld %lld %lld %lld %lld %lld %lld %lld %lld\n", (long long)r.owner, (long long)r.lo, (long long)r.hi(), (long long)r.n, (long long)r.full,
+                   (long long)r.last_len, (long long)r.tile, (long long)r.base, (long long)r.slot());
     }
+    fclose(f);
+    return 0;
+}
+
+static int tile_file(const char* path)
+{
+    FILE* f = fopen(path, "r");
+    CHECK(f, "cannot open %s", path);
+    long long lo, full, cb, pending;
+    while (fscanf(f, "%lld %lld %lld %lld", &lo, &full, &cb, &pending) == 4) printf("%lld\n", (long long)seg_tile_chunks(lo, full, cb, pending != 0));
     fclose(f);
     return 0;
 }
@@ -63,39 +74,39 @@ static int run_case(std::mt19937_64& rng, int S, int rounds, int64_t max_push, i
     std::vector<std::vector<int64_t>> row_n((size_t)S);      // per stream and chunk: the n its cache row was computed at
 
     // the packed inference of these ranges: reads what the pack kernel reads of the tails, writes what the scatter kernel writes of the caches
-    auto infer = [&](std::vector<GroupRange>& ranges, bool pending) -> int {
+    auto infer = [&](std::vector<PackRange>& ranges, bool pending) -> int {
         int64_t total = 0;
-        CHECK(group_plan(ranges.data(), (int64_t)ranges.size(), &total) == 0, "group_plan refused");
+        CHECK(pack_plan(ranges.data(), (int64_t)ranges.size(), &total) == 0, "pack_plan refused");
         int64_t next = 0;
-        for (const GroupRange& r : ranges) {
-            StreamBook& k = b[(size_t)r.stream];
-            CHECK(r.base == next && r.base % 32 == 0 && r.slot == ((r.hi - r.lo + SD_MANY_GAP + 31) / 32) * 32, "slot of stream %lld", (long long)r.stream);
-            next = r.base + r.slot;
-            CHECK(r.lo == k.sealed && r.lo % 32 == 0 && r.n_eq <= k.tail_len() && r.n_eq <= r.slot * SD_HOP, "range of stream %lld", (long long)r.stream);
-            CHECK((r.hi - r.lo - 1) * SD_HOP + r.last_len <= r.n_eq && r.tile >= 0 && r.tile <= r.full && r.full <= r.hi - r.lo, "chunks of stream %lld", (long long)r.stream);
+        for (const PackRange& r : ranges) {
+            StreamBook& k = b[(size_t)r.owner];
+            CHECK(r.base == next && r.base % 32 == 0 && r.slot() == ((r.hi() - r.lo + SD_MANY_GAP + 31) / 32) * 32, "slot of stream %lld", (long long)r.owner);
+            next = r.base + r.slot();
+            CHECK(r.lo == k.sealed && r.lo % 32 == 0 && r.n <= k.tail_len() && r.n <= r.slot() * SD_HOP, "range of stream %lld", (long long)r.owner);
+            CHECK((r.hi() - r.lo - 1) * SD_HOP + r.last_len <= r.n && r.tile >= 0 && r.tile <= r.full && r.full <= r.hi() - r.lo, "chunks of stream %lld", (long long)r.owner);
             double sum = 0;
-            for (int64_t i = 0; i < r.n_eq; ++i) {
-                CHECK(k.tail_now()[i] == sample_of(r.stream, r.lo * SD_HOP + i), "sample %lld of the range of stream %lld", (long long)i, (long long)r.stream);
+            for (int64_t i = 0; i < r.n; ++i) {
+                CHECK(k.tail_now()[i] == sample_of(r.owner, r.lo * SD_HOP + i), "sample %lld of the range of stream %lld", (long long)i, (long long)r.owner);
                 sum += k.tail_now()[i];
             }
             (void)sum;
-            const int64_t cnt = r.hi - r.lo, room_seg = (k.cache_cap - r.lo) * SD_SEG_ROW, room_emb = (k.cache_cap - r.lo) * SD_EMB_ROW;
-            CHECK(cnt * SD_SEG_ROW <= room_seg && cnt * SD_EMB_ROW <= room_emb, "cache room of stream %lld", (long long)r.stream);
-            if ((int64_t)row_n[(size_t)r.stream].size() < r.hi) row_n[(size_t)r.stream].resize((size_t)r.hi, -1);
-            for (int64_t c = r.lo; c < r.hi; ++c) {
-                for (int64_t q = 0; q < SD_SEG_ROW; ++q) k.seg[c * SD_SEG_ROW + q] = row_of(r.stream, c, k.n);
-                for (int64_t q = 0; q < SD_EMB_ROW; ++q) k.emb[c * SD_EMB_ROW + q] = -row_of(r.stream, c, k.n);
-                row_n[(size_t)r.stream][(size_t)c] = k.n;
+            const int64_t cnt = r.hi() - r.lo, room_seg = (k.cache_cap - r.lo) * SD_SEG_ROW, room_emb = (k.cache_cap - r.lo) * SD_EMB_ROW;
+            CHECK(cnt * SD_SEG_ROW <= room_seg && cnt * SD_EMB_ROW <= room_emb, "cache room of stream %lld", (long long)r.owner);
+            if ((int64_t)row_n[(size_t)r.owner].size() < r.hi()) row_n[(size_t)r.owner].resize((size_t)r.hi(), -1);
+            for (int64_t c = r.lo; c < r.hi(); ++c) {
+                for (int64_t q = 0; q < SD_SEG_ROW; ++q) k.seg[c * SD_SEG_ROW + q] = row_of(r.owner, c, k.n);
+                for (int64_t q = 0; q < SD_EMB_ROW; ++q) k.emb[c * SD_EMB_ROW + q] = -row_of(r.owner, c, k.n);
+                row_n[(size_t)r.owner][(size_t)c] = k.n;
             }
         }
         CHECK(next == total, "total of the pack");
-        for (const GroupRange& r : ranges) {
-            StreamBook& k = b[(size_t)r.stream];
+        for (const PackRange& r : ranges) {
+            StreamBook& k = b[(size_t)r.owner];
             if (pending) { k.pending_n = k.n; continue; }
-            GroupMove mv;
+            GroupRow mv;
             const long before = dev.allocs;
-            CHECK(book_seal_planned(k, r.hi, mv), "nothing to seal in stream %lld", (long long)r.stream);
-            CHECK(mv.len + SD_TAIL_PAD <= mv.room, "compaction target of stream %lld: %lld floats for %lld", (long long)r.stream, (long long)mv.room, (long long)mv.len);
+            CHECK(book_seal_planned(k, r.hi(), mv), "nothing to seal in stream %lld", (long long)r.owner);
+            CHECK(mv.len + SD_TAIL_PAD <= mv.room, "compaction target of stream %lld: %lld floats for %lld", (long long)r.owner, (long long)mv.room, (long long)mv.len);
             memcpy(mv.dst, mv.src, (size_t)mv.len * sizeof(float));
             for (int q = 0; q < SD_TAIL_PAD; ++q) mv.dst[mv.len + q] = 0.0f;
             book_seal_trim(dev, k);
@@ -107,7 +118,7 @@ static int run_case(std::mt19937_64& rng, int S, int rounds, int64_t max_push, i
     for (int round = 0; round < rounds; ++round) {
         // sd_stream_push_many: plan, growth, append, packed inference of what became sealed, compactions
         std::vector<int64_t> m((size_t)S);
-        std::vector<GroupRange> ranges;
+        std::vector<PackRange> ranges;
         for (int i = 0; i < S; ++i) {
             int64_t v = 1 + (int64_t)(rng() % (uint64_t)max_push);
             const uint64_t how = rng() % 8;
@@ -119,11 +130,11 @@ static int run_case(std::mt19937_64& rng, int S, int rounds, int64_t max_push, i
             }
             if (how == 3) v = 2 * SD_SEAL_CHUNKS * SD_HOP + 5;      // two blocks at once
             m[(size_t)i] = v;
-            GroupRange r;
-            if (group_range(b[(size_t)i].n + v, b[(size_t)i].sealed, cb, false, r)) { r.stream = i; ranges.push_back(r); }
+            PackRange r;
+            if (pack_range(b[(size_t)i].n + v, b[(size_t)i].sealed, cb, false, r)) { r.owner = i; ranges.push_back(r); }
         }
         std::vector<char> busy((size_t)S, 0);
-        for (const GroupRange& r : ranges) busy[(size_t)r.stream] = 1;
+        for (const PackRange& r : ranges) busy[(size_t)r.owner] = 1;
         for (int i = 0; i < S; ++i)      // a stream with nothing to do in the call is not touched
             if (m[(size_t)i] > 0 || busy[(size_t)i]) CHECK(book_reserve_group(dev, b[(size_t)i], m[(size_t)i]) == 0, "reserve failed");
         const long before = dev.allocs;
@@ -140,12 +151,12 @@ static int run_case(std::mt19937_64& rng, int S, int rounds, int64_t max_push, i
         CHECK(dev.allocs == before, "an allocation behind the first kernel of a push");
         // sd_stream_turns_many, two rounds out of three
         if (rng() % 3) {
-            std::vector<GroupRange> pend;
+            std::vector<PackRange> pend;
             for (int i = 0; i < S; ++i) {
-                GroupRange r;
-                if (b[(size_t)i].pending_n != b[(size_t)i].n && group_range(b[(size_t)i].n, b[(size_t)i].sealed, cb, true, r)) { r.stream = i; pend.push_back(r); }
+                PackRange r;
+                if (b[(size_t)i].pending_n != b[(size_t)i].n && pack_range(b[(size_t)i].n, b[(size_t)i].sealed, cb, true, r)) { r.owner = i; pend.push_back(r); }
             }
-            for (const GroupRange& r : pend) CHECK(book_reserve_group(dev, b[(size_t)r.stream], 0) == 0, "reserve failed");
+            for (const PackRange& r : pend) CHECK(book_reserve_group(dev, b[(size_t)r.owner], 0) == 0, "reserve failed");
             const long at = dev.allocs;
             if (infer(pend, true)) return 1;
             CHECK(dev.allocs == at, "an allocation behind the first kernel of a turns call");
@@ -177,6 +188,7 @@ static int run_case(std::mt19937_64& rng, int S, int rounds, int64_t max_push, i
 int main(int argc, char** argv)
 {
     if (argc > 2 && !strcmp(argv[1], "plan")) return plan_file(argv[2]);
+    if (argc > 2 && !strcmp(argv[1], "tile")) return tile_file(argv[2]);
     std::mt19937_64 rng(argc > 2 ? strtoull(argv[2], nullptr, 10) : 20240911ull);
     long allocs = 0;
     if (run_case(rng, 5, 60, 40000, 4096, &allocs)) return 1;           // small pushes: steady state

@@ -62,7 +62,16 @@ static int push_single(HostDev& d, StreamBook& b, int64_t m, int64_t window)
     if (to <= b.sealed) return 0;
     if (int rc = book_reserve_cache(d, b, sd_chunk_rule(b.n, nullptr))) return rc;
     fill_rows(b, b.sealed, to, false);
-    if (int rc = book_seal(d, b, to)) return rc;
+    const StreamBook was = b;
+    d.fail_in = 0;      // the seal's one allocation, where it needs one, fails first: the book, the tail in use and the caches stay (the spare buffer is nobody's)
+    int rc = book_seal(d, b, to);
+    if (d.fail_in == -1) {
+        CHECK(rc == SD_ERR_HIP && b.n == was.n && b.sealed == was.sealed && b.pending_n == was.pending_n && b.cur == was.cur && b.tail_now() == was.tail_now() &&
+              b.tail_cap[b.cur] == was.tail_cap[was.cur] && b.seg == was.seg && b.emb == was.emb && b.cache_cap == was.cache_cap, "a failed allocation in seal changed the book");
+        rc = book_seal(d, b, to);
+    }
+    d.fail_in = -1;
+    if (rc) return rc;
     return window >= 0 ? book_forget(d, b, window) : 0;
 }
 
@@ -75,7 +84,7 @@ static int push_group(HostDev& d, StreamBook& b, int64_t m, int64_t window)
     const int64_t to = stream_sealed_chunks(b.n);
     if (to > b.sealed) {
         fill_rows(b, b.sealed, to, false);
-        GroupMove mv;
+        GroupRow mv;
         if (book_seal_planned(b, to, mv)) {
             CHECK(mv.len + SD_TAIL_PAD <= mv.room, "compaction target: %lld floats for %lld", (long long)mv.room, (long long)mv.len);
             memcpy(mv.dst, mv.src, (size_t)mv.len * sizeof(float));
