@@ -30,7 +30,8 @@ enum {
     SD_ERR_MODEL = 3,    /* weight file missing or malformed (reference: Ort::Exception) */
     SD_ERR_SHORT = 4,    /* audio too short for one segmentation frame (reference: UB, sd.cpp:2997) */
     SD_ERR_NUMERIC = 5,  /* zero-norm centroid (reference throws, sd.cpp:493-495) */
-    SD_ERR_COMM = 6      /* multi-GPU exchange failed or timed out; the communicator has been aborted */
+    SD_ERR_COMM = 6,     /* multi-GPU exchange failed or timed out; the communicator has been aborted */
+    SD_ERR_NOMEM = 7     /* a host allocation of a roster call failed; the roster is what it was (sd_roster_*) */
 };
 
 /* fixed geometry of the reference */
@@ -303,8 +304,9 @@ int64_t sd_stream_sealed_chunks(int64_t n_samples);
  * sd_stream_set_window(W >= 0) is the policy: every push, single or through sd_stream_push_many*, that seals a block then forgets down to W blocks
  * (in a group call per stream, after the group's launches); -1 = off, the default.  sd_stream_origin: the samples forgotten so far.
  * SD_ERR_ARG: keep_blocks < 0 (set_window: < -1), a stream that is unusable or whose precision options changed, as for the other calls.
- * What the window does NOT do: it carries no speakers over.  The labels of a windowed stream mean the same person from one update to the next only
- * under an enrolled gallery -- as for streams in general, whose every update clusters anew. */
+ * The window itself carries no speakers over: every update clusters anew, as for streams in general, and a raw label means the same person from one
+ * update to the next only under an enrolled gallery -- or with a roster attached (sd_stream_set_roster, below), which renames the labels of every
+ * update to ids that last, also for a talker who left the window and comes back. */
 int sd_stream_forget(sd_stream*, int64_t keep_blocks);                         /* sd.cpp:2937-3234, repeated */
 int sd_stream_set_window(sd_stream*, int64_t keep_blocks /* -1 = off, the default */);
 int sd_stream_origin(const sd_stream*, int64_t* first_sample);
@@ -330,6 +332,59 @@ int sd_stream_push_many(sd_stream* const* s /*[S]*/, const int16_t* const* h_pcm
 int sd_stream_push_many_dev(sd_stream* const* s /*[S]*/, const int16_t* const* d_pcm /*[S]*/, const int64_t* n /*[S]*/, int64_t S);     /* sd.cpp:2937-3234, 2950 */
 int sd_stream_push_many_f32(sd_stream* const* s /*[S]*/, const float* const* h_wav /*[S]*/, const int64_t* n /*[S]*/, int64_t S);     /* sd.cpp:2937-3234, 2948-2951 */
 int sd_stream_turns_many(sd_stream* const* s /*[S]*/, int64_t S, sd_turn** turns /*[S]*/, int64_t* n_turns /*[S]*/, int32_t* status /*[S]*/);     /* sd.cpp:2937-3234 */
+
+/* ---- a speaker roster: labels that keep their meaning.  The label of a turn is a raw cluster number (sd.cpp:3433-3441) and every update of a stream
+ * clusters anew, so "Speaker_1" of one update may be "Speaker_0" of the next.  A roster is a small host object that hands out persistent speaker ids.
+ * Attached to a stream (sd_stream_set_roster) it makes the labels of sd_stream_turns / sd_stream_turns_many roster ids; applied to the last job of a
+ * context (sd_roster_update_last) it links the speakers of separate recordings, the recordings of a sd_diarize_many pack for instance.  It only renames
+ * labels: times, order, confidences and centroids are the bytes they are without it, and nothing is launched on the device that was not launched before
+ * -- one update is K x P cosine distances of d doubles and a table over the job's rows, on the host.
+ * State: P entries; entry p holds a centroid c_p [d] (f64), a row count n_p and u_p, the index of the last update that gave p out (-1 for a loaded entry
+ * that never was); an update counter U.
+ * Input of one update: K label columns with centroids C [K][d] and train-row counts m [K] -- what sd_last_speakers returns; a row whose first element is
+ * NaN counts 0 --; optionally the job's hard labels rows [M] (the cluster of every (chunk, local speaker) row behind the inactive rule, < 0 = none) and the
+ * ids prev [Mp] that the previous update of the same stream gave the rows of its table (< 0 = none), with shift >= 0: row i of this job is row i + shift of
+ * the previous one (3 x the chunks forgotten in between); a threshold t.  Every k in [0, K) gets an id and two k never get the same one:
+ *  A rows: cnt[k][p] = the number of i with i + shift < Mp, rows[i] = k >= 0 and prev[i + shift] = p >= 0.  The pairs with cnt > 0 are sorted by
+ *    (-cnt, k, p); a pair is taken when both sides are still free.  Skipped when rows or prev is absent.  This is the hysteresis: a speaker keeps the id
+ *    his rows had, whatever the clustering renumbered.
+ *  B centroids: the k that are still free and whose centroid is not NaN against the entries p that this update has not given out and whose centroid is
+ *    not NaN, by the cosine distance of sd_speaker_distances (three sequential f64 sums, sd.cpp:476-498); the pairs with distance <= t (inclusive) are
+ *    sorted by (distance, k, p) and taken greedily: the rule of sd_match_speakers.  This brings back a speaker who was away from the window and names
+ *    speakers across recordings.  A zero-norm centroid on either side of this step (it reads all of both sides, or nothing when one side is empty):
+ *    SD_ERR_NUMERIC.
+ *  C the k that are still free get the new ids P, P + 1, ... in ascending k.
+ *  D refresh, for every k -> p: when p is new or m[k] >= n_p, c_p = C[k] and n_p = m[k] -- an entry keeps the estimate made from the most rows, a tie goes
+ *    to the later one --; u_p = U.  Then U += 1.
+ * Any error -- SD_ERR_ARG (a null pointer, a negative size, count or shift, rows[i] >= K, prev[i] >= P, a threshold outside [0, 2]), SD_ERR_NUMERIC,
+ * SD_ERR_NOMEM -- leaves the roster exactly as it was.  What a roster does not do: it never merges or expires entries, so a person whom an early update
+ * split into two ids stays two ids.
+ * sd_roster_open: host only, no context and no GPU, as sd_fcluster.  sd_roster_close: SD_ERR_ARG while a stream is attached; NULL is a no-op.
+ * sd_roster_load: entries 0 .. P - 1 into an EMPTY roster (SD_ERR_ARG otherwise), yesterday's roster or the rows of a voiceprint file for instance.
+ * sd_roster_speakers: at most cap entries; any of the three arrays may be NULL.  sd_roster_update: the rule; h_rows and h_prev may be NULL; a NaN
+ * threshold means the constant t * t / 2 of sd_match_speakers.  sd_roster_update_last: steps B - D on the last job of this context that clustered
+ * (SD_ERR_ARG when there is none or when its rows do not have the roster's d), with the context's "speaker_match_threshold"; at most cap ids are written;
+ * after sd_many_select(r) it names recording r of a pack.  sd_last_roster_ids: the id of every raw label k of the last job -- they name the rows of
+ * sd_last_speakers --, *K = 0 when no roster took part in it.  sd_relabel_turns_map: label k becomes ids[k]; a label outside [0, K) returns SD_ERR_ARG and
+ * nothing is written.
+ * sd_stream_set_roster (NULL detaches; the roster's d must be 192): from then on sd_stream_turns, and sd_stream_turns_many for this stream, run one update
+ * behind their successful finalize -- rows = that finalize's hard labels, prev = the ids the stream kept from its previous update, shift from the two
+ * origins (sd_stream_forget needs no call of its own), t = the context's option -- and relabel the turns in place; sd_last_roster_ids, also behind
+ * sd_many_select(i), gives the map.  A second call with nothing pushed gives the same ids.  A call that fails anywhere leaves the roster and what the stream
+ * kept as they were; in a group call a failing update ends the call as SD_ERR_HIP does, and the rosters are put back.  Several streams of one context may
+ * share a roster; detaching, or attaching another roster, drops what the stream kept.  An enrolled gallery and "max_num_embeddings" need no special case:
+ * the roster names whatever label columns and table rows the job has. */
+typedef struct sd_roster sd_roster;
+int sd_roster_open(int d, sd_roster** r);     /* no counterpart: the reference keeps no speaker between calls (sd.cpp:3433-3441) */
+int sd_roster_close(sd_roster*);     /* no counterpart (sd.cpp:3433-3441) */
+int sd_roster_load(sd_roster*, const double* h_cen /*[P][d]*/, const int64_t* h_counts /*[P]*/, int64_t P);     /* no counterpart (sd.cpp:3433-3441) */
+int sd_roster_info(const sd_roster*, int64_t* P, int64_t* updates, int* d);     /* any pointer may be NULL; no counterpart (sd.cpp:3433-3441) */
+int sd_roster_speakers(const sd_roster*, double* h_cen /*[cap][d]*/, int64_t* h_counts /*[cap]*/, int64_t* h_seen /*[cap]*/, int64_t cap, int64_t* P);     /* no counterpart (sd.cpp:3433-3441) */
+int sd_roster_update(sd_roster*, const double* h_cen /*[K][d]*/, const int64_t* h_counts /*[K]*/, int64_t K, const int32_t* h_rows /*[M] or NULL*/, int64_t M, const int32_t* h_prev /*[Mp] or NULL*/, int64_t Mp, int64_t shift, double threshold, int32_t* h_ids /*[K]*/);     /* sd.cpp:476-498, 3433-3441 */
+int sd_roster_update_last(sd_roster*, sd_ctx*, int32_t* h_ids /*[cap]*/, int64_t cap, int64_t* K);     /* sd.cpp:476-498, 3433-3441 */
+int sd_relabel_turns_map(sd_turn*, int64_t n_turns, const int32_t* ids /*[K]*/, int64_t K);     /* sd.cpp:3433-3441 */
+int sd_stream_set_roster(sd_stream*, sd_roster*);     /* sd.cpp:476-498, 3433-3441 */
+int sd_last_roster_ids(const sd_ctx*, int32_t* h_ids /*[cap]*/, int64_t cap, int64_t* K);     /* sd.cpp:3433-3441 */
 
 /* ---- known speakers: cluster numbers mean nothing outside one call; these entries give the clusters an identity that lasts.  The centroids that
  * assign_embeddings builds (sd.cpp:2149-2167; what pyannote hands out with return_embeddings=True, Clustering.py:97-164) come out of the last job, a

@@ -4,6 +4,7 @@
 #include "common.h"
 #include "many_plan.h"
 #include "wav_file.h"
+#include "roster.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -534,6 +535,35 @@ extern "C" int sd_last_enrolled(const sd_ctx* c, int32_t* h_rows, int64_t cap, i
     const int64_t k = c->last.cen_K;
     if (K) *K = k;
     for (int64_t i = 0; i < k && i < cap; ++i) if (h_rows) h_rows[i] = i < (int64_t)c->last.enrolled.size() ? c->last.enrolled[(size_t)i] : -1;
+    return SD_OK;
+}
+
+// ------------------------------------------------------------------ the speaker roster on the last job (the rule and the host-only entries: roster.cpp)
+// steps B - D on the centroids of the last job: no rows, the context's threshold.  Host arithmetic only: nothing is launched
+extern "C" int sd_roster_update_last(sd_roster* r, sd_ctx* c, int32_t* h_ids, int64_t cap, int64_t* K)
+{
+    if (!c) return SD_ERR_ARG;
+    c->err.clear();
+    if (!r || cap < 0) SD_FAIL(c, SD_ERR_ARG, "sd_roster_update_last: bad argument");
+    const JobResult& job = c->last;
+    if (job.cen_K < 1) SD_FAIL(c, SD_ERR_ARG, "sd_roster_update_last: no clustering call on this context yet");
+    if (job.cen_d != r->d) SD_FAIL(c, SD_ERR_ARG, "sd_roster_update_last: the last job has centroids of %d dimensions, the roster entries of %d", job.cen_d, r->d);
+    std::vector<int32_t> ids((size_t)job.cen_K);
+    const int rc = sd_roster_update(r, job.cen.data(), job.cen_counts.data(), job.cen_K, nullptr, 0, nullptr, 0, 0, c->speaker_match_threshold, ids.data());
+    if (rc == SD_ERR_NUMERIC) SD_FAIL(c, rc, "sd_roster_update_last: zero-magnitude centroid (reference throws, sd.cpp:493-495)");
+    if (rc) SD_FAIL(c, rc, "sd_roster_update_last: the roster update failed (%d)", rc);
+    if (K) *K = job.cen_K;
+    if (h_ids) for (int64_t k = 0; k < job.cen_K && k < cap; ++k) h_ids[k] = ids[(size_t)k];
+    c->last.roster_ids = std::move(ids);
+    return SD_OK;
+}
+
+extern "C" int sd_last_roster_ids(const sd_ctx* c, int32_t* h_ids, int64_t cap, int64_t* K)
+{
+    if (!c || cap < 0) return SD_ERR_ARG;
+    const int64_t k = (int64_t)c->last.roster_ids.size();
+    if (K) *K = k;
+    if (h_ids) for (int64_t i = 0; i < k && i < cap; ++i) h_ids[i] = c->last.roster_ids[(size_t)i];
     return SD_OK;
 }
 

@@ -457,6 +457,7 @@ int run_clustering(sd_ctx* c, const double* d_emb, int64_t M, int d, std::vector
     JobResult& res = c->last;
     res.cen_K = 0;                                                  // sd_last_speakers describes this call from its successful end on
     res.enrolled.clear();                                           // ... and sd_last_enrolled: -1 for every label unless the enrolled flow says otherwise
+    res.hard.clear(); res.roster_ids.clear();                       // ... and sd_last_roster_ids: no roster has named this job
     if (M <= 0) return SD_OK;
     int rc;
     std::vector<int> tidx;

@@ -156,7 +156,9 @@ struct StepStash {
 // What the last job leaves for sd_last_confidence / sd_last_speakers / sd_last_enrolled, as one value (sd_ctx::last).  conf: per-turn confidence, written at
 // the end of finalize / sd_cut_turns_many.  The last clustering call (run_clustering, or the last cut): its cen_K final centroids [cen_K][cen_d] -- row k = raw
 // label k -- and the train rows of each; cen_K = 0 before any and after one that failed.  enrolled: their gallery rows, -1 (or absent) where nobody enrolled.
-struct JobResult { std::vector<double> conf, cen; std::vector<int64_t> cen_counts; int cen_K = 0, cen_d = 0; std::vector<int32_t> enrolled; };
+// hard: finalize's [chunks * 3] assignment behind the inactive rule (the rows of a roster update; empty for a job that is no finalize).  roster_ids: the
+// roster id of every raw label, empty unless a roster took part (sd_last_roster_ids).
+struct JobResult { std::vector<double> conf, cen; std::vector<int64_t> cen_counts; int cen_K = 0, cen_d = 0; std::vector<int32_t> enrolled, hard, roster_ids; };
 
 // one recording of a sd_diarize_many* call (many.hip): what finalize left in the context for it; sd_many_select puts it back
 struct ManyJob { int status = SD_OK; JobResult res; };
@@ -432,9 +434,12 @@ int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vec
 enum SampleForm { SD_PCM_HOST, SD_PCM_DEV, SD_F32_HOST };
 // finalize, one job after the other, of a call with J outputs (sd_diarize_many*: recordings; sd_stream_turns_many: streams).  Presets turns / n_turns /
 // status / c->many_jobs to "no job" (SD_ERR_SHORT), lets `infer` run the networks and name the rows of every job (chunks <= 0: none), then finalizes in
-// list order: SD_ERR_NUMERIC is that job's own status, any other failure gives every turn list back and is returned; c->last is kept per job
+// list order: SD_ERR_NUMERIC is that job's own status, any other failure gives every turn list back and is returned; c->last is kept per job.
+// `named` (may be empty) sees every job that ended SD_OK, with its turns handed over and c->last describing it, before c->last is kept: the roster of a
+// stream renames the labels there (stream.hip); what it returns other than SD_OK ends the call like any other failure
 struct FinalJob { const float* seg; const float* emb; int64_t chunks, n; };
-int finalize_jobs(sd_ctx* c, int64_t J, sd_turn** turns, int64_t* n_turns, int32_t* status, const std::function<int(std::vector<FinalJob>&)>& infer);
+int finalize_jobs(sd_ctx* c, int64_t J, sd_turn** turns, int64_t* n_turns, int32_t* status, const std::function<int(std::vector<FinalJob>&)>& infer,
+                  const std::function<int(int64_t, sd_turn*, int64_t)>& named = nullptr);
 // ---- cut.hip: the tail of the sd_cut_open* entries (sdhip.h, "many cuts of one dendrogram"); refuses a gallery and a dump directory itself
 int cut_refusal(sd_ctx* c, const char* who);
 int cut_open_dev(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, sd_cut** out);

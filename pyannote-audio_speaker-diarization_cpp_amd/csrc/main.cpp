@@ -42,6 +42,10 @@
 //                   seals a block the stream forgets all but that many; the turns are those of the audio still held, printed with absolute times
 //                   (t + sd_stream_origin / 16000); the header of a --stream-updates block still gives the seconds pushed, its chunk counts are those of the
 //                   audio held.  Without --stream, or with a value that is not a number of seconds > 0: usage error (exit 2)
+//   --stream-roster   with --stream: a speaker roster on the stream (sd_roster_open, sd_stream_set_roster): every printed label -- in every --stream-updates
+//                   block as well -- is a roster id, which means the same person from one update to the next and, with --stream-window, for a talker
+//                   who left the window and came back.  Without --stream: usage error (exit 2); refused with --speakers and --relabel, which name
+//                   and renumber raw labels
 //   --speakers FILE [--speakers-threshold X]   after the diarization, match the centroids of the job's clusters (sd_last_speakers) against the voiceprints of
 //                   FILE (sd_read_voiceprints, sd_match_speakers): a matched cluster prints as [start -- end] --> NAME and goes into the RTTM under its name, an
 //                   unmatched one prints as without the flag.  X in [0, 2] = the largest cosine distance that still matches (option "speaker_match_threshold").
@@ -92,6 +96,7 @@ struct Args { const char* seg = nullptr; const char* emb = nullptr; const char* 
               long long stream_window = -1;                                                       // --stream-window: blocks kept (-1: no window)
               int activity = -1; double act[4] = {-1.0, -1.0, -1.0, -1.0}; bool act_hamming = false;      // --activity: SD_ACTIVITY_*; onset, offset, min on, min off (-1: default)
               long long stream_piece = 0; bool stream_updates = false;         // --stream: samples per piece (0: off)
+              bool stream_roster = false;                                      // --stream-roster: the labels are roster ids
               const char* speakers = nullptr; double speakers_threshold = -1.0; const char* enroll = nullptr; std::vector<sd_turn> enroll_spans; bool enrolled = false;
               const char* many = nullptr;         // --speakers FILE, its threshold (-1: default), --enroll NAME and its spans
               const char* score = nullptr; const char* tune = nullptr; double collar = 0.0; bool skip_overlap = false, uem_from_ref = false;      // --score / --tune REF.rttm and how to score
@@ -505,11 +510,13 @@ static int run_stream(const Args& a)
     sd_ctx* ctx = open_context(a);
     if (!ctx) return 1;
     sd_stream* st = nullptr;
+    sd_roster* roster = nullptr;
     StreamRun r{ctx, st, a};
-    auto leave = [&](int rc) { sd_free_turns(r.turns); sd_stream_close(r.st); sd_destroy(ctx); return rc; };      // every way out gives back what it holds
+    auto leave = [&](int rc) { sd_free_turns(r.turns); sd_stream_close(r.st); sd_roster_close(roster); sd_destroy(ctx); return rc; };      // every way out gives back what it holds
     if (a.enrolled) { if (!enrol_gallery(ctx, a, g)) return leave(1); r.gal = &g; }
     if (sd_stream_open(ctx, &r.st) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
     if (a.stream_window >= 0 && sd_stream_set_window(r.st, a.stream_window) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
+    if (a.stream_roster && (sd_roster_open(SD_EMB_DIM, &roster) != SD_OK || sd_stream_set_roster(r.st, roster) != SD_OK)) { fprintf(stderr, "--stream-roster: no roster (%s)\n", sd_last_error(ctx)); return leave(1); }
     const bool fed = std::string(a.wav) == "-" ? stream_stdin(r) : stream_file(r);
     if (!fed || !r.ask()) return leave(1);
     int64_t n = 0, total = 0;
@@ -676,6 +683,7 @@ int main(int argc, char* argv[])
             }
         }
         else if (s == "--stream-updates") a.stream_updates = true;
+        else if (s == "--stream-roster") a.stream_roster = true;
         else if (s == "--enrolled") a.enrolled = true;
         else if (s == "--stream") {
             if (i + 1 >= argc) { fprintf(stderr, "usage: --stream needs a value\n"); return 2; }
@@ -735,6 +743,8 @@ int main(int argc, char* argv[])
     if (a.stream_piece > 0 && a.dump_dir) { fprintf(stderr, "usage: --dump-steps describes one whole-path inference; --stream is refused with it\n"); return 2; }
     if (a.stream_window >= 0 && a.stream_piece <= 0) { fprintf(stderr, "usage: --stream-window needs --stream SECONDS\n"); return 2; }
     if (a.cl_max_num >= 1 && a.dump_dir) { fprintf(stderr, "usage: --dump-steps describes the reference's flow, which clusters every train row; --max-num-embeddings is refused with it\n"); return 2; }
+    if (a.stream_roster && a.stream_piece <= 0) { fprintf(stderr, "usage: --stream-roster needs --stream SECONDS\n"); return 2; }
+    if (a.stream_roster && (a.speakers || a.relabel)) { fprintf(stderr, "usage: --stream-roster prints roster ids; --speakers and --relabel name and renumber raw labels and are refused with it\n"); return 2; }
     if (a.stream_updates && a.stream_piece <= 0) { fprintf(stderr, "usage: --stream-updates needs --stream SECONDS\n"); return 2; }
     if (pos.size() >= 3 && std::string(pos[2]) == "-" && a.stream_piece <= 0) { fprintf(stderr, "usage: samples from stdin (-) need --stream SECONDS\n"); return 2; }
     if (a.enroll && !a.speakers) { fprintf(stderr, "usage: --enroll NAME needs --speakers FILE, the voiceprint file to write\n"); return 2; }

@@ -149,7 +149,8 @@ int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vec
 }
 
 // ------------------------------------------------------------------ finalize per output (common.h)
-int finalize_jobs(sd_ctx* c, int64_t J, sd_turn** turns, int64_t* n_turns, int32_t* status, const std::function<int(std::vector<FinalJob>&)>& infer)
+int finalize_jobs(sd_ctx* c, int64_t J, sd_turn** turns, int64_t* n_turns, int32_t* status, const std::function<int(std::vector<FinalJob>&)>& infer,
+                  const std::function<int(int64_t, sd_turn*, int64_t)>& named)
 {
     c->many_jobs.assign((size_t)J, ManyJob());
     for (int64_t j = 0; j < J; ++j) { turns[j] = nullptr; n_turns[j] = 0; status[j] = SD_ERR_SHORT; c->many_jobs[(size_t)j].status = SD_ERR_SHORT; }
@@ -166,6 +167,7 @@ int finalize_jobs(sd_ctx* c, int64_t J, sd_turn** turns, int64_t* n_turns, int32
         status[j] = job.status = rc;
         if (rc == SD_ERR_NUMERIC) continue;                    // this job's clustering; the others go on
         if (rc == SD_OK) rc = turns_out(c, v, &turns[j], &n_turns[j]);
+        if (rc == SD_OK && named) rc = named(j, turns[j], n_turns[j]);
         if (rc) {
             for (int64_t k = 0; k < J; ++k) { sd_free_turns(turns[k]); turns[k] = nullptr; n_turns[k] = 0; }
             return rc;

@@ -362,6 +362,7 @@ int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, 
     }
     { KernelStat& ks = c->stats["clusters_K"]; ks.launches++; ks.flops += (double)Kr; ks.bytes += (double)v.size(); }       // bench: K and turns per job
     turn_confidence(v, hard, soft_best, chunks, c->last.conf);
+    c->last.hard.assign(hard.begin(), hard.end());      // the rows of a roster update (roster.h)
     c->stage_ms[2] += now_ms() - t0;
     return SD_OK;
 }

@@ -7,8 +7,11 @@
 // pending ranges (many.hip: pack_infer), three table-driven copy kernels replace the per-stream launches; the single-stream entries keep their paths.
 // A range is a PackRange (many_plan.h) built by pack_range (stream_book.h), a copy a GroupRow (stream_book.h); which side of PyanNet's skinny limit a
 // chunk is on is seg_tile_chunks' word (many_plan.h) for the pack and for segment_pending alike; the finalize per stream is many.hip's finalize_jobs.
+// A roster attached to a stream (sd_stream_set_roster; the rule: roster.cpp) renames the labels behind a successful finalize: host arithmetic on what the
+// finalize left in the context, no launch of its own.
 #include "common.h"
 #include "stream_book.h"
+#include "roster.h"
 #include <algorithm>
 
 static_assert(SD_TAIL_PAD == SD_WAV_PAD, "the tail's padding is what DevWav::padded promises");
@@ -91,6 +94,10 @@ struct sd_stream {
     int ecapa_precision = 0, seg_precision = 0;      // fixed at sd_stream_open: a cache of mixed precision is nobody's answer
     bool dead = false;                               // after SD_ERR_HIP: every call but sd_stream_close is refused
     int64_t window = -1;                             // sd_stream_set_window: sealed blocks kept after a push that seals one (-1: all of them)
+    sd_roster* roster = nullptr;                     // sd_stream_set_roster: names the labels of every turns call (null: raw cluster numbers)
+    std::vector<int32_t> kept;                       // ... the roster id of every table row at the last update, -1 where the row had no label
+    int64_t kept_origin = 0;                         // ... and the origin then: row i of the table now was row i + 3 (origin - kept_origin) / 8000
+    bool has_kept = false;
 };
 
 namespace {
@@ -230,6 +237,29 @@ int push_impl(sd_stream* s, const void* src, int64_t m, int kind, const char* wh
     return SD_OK;
 }
 
+// The roster's update behind a finalize that succeeded: c->last describes that job, t[0, nt) are its turns with raw labels.  The rule runs on the
+// centroids and counts of the job, its hard labels, and the ids this stream kept from its previous update; then the labels of t become roster ids and
+// c->last carries the map.  `kept` receives ids[hard[i]] per row for the caller to commit.  Any failure leaves the roster, the stream and t untouched.
+int name_turns(sd_stream* s, sd_turn* t, int64_t nt, std::vector<int32_t>& kept)
+{
+    sd_ctx* c = s->c;
+    JobResult& job = c->last;
+    const int64_t K = job.cen_K, M = (int64_t)job.hard.size();
+    if (job.cen_d != s->roster->d) SD_FAIL(c, SD_ERR_ARG, "the roster's entries have %d dimensions, the job's centroids %d", s->roster->d, job.cen_d);
+    for (int64_t i = 0; i < nt; ++i) if (t[i].label < 0 || t[i].label >= K) SD_FAIL(c, SD_ERR_ARG, "turn label %d outside the job's %lld label columns", t[i].label, (long long)K);
+    const int64_t shift = SD_SPEAKERS * ((s->b.origin - s->kept_origin) / SD_HOP);
+    std::vector<int32_t> ids((size_t)K);
+    kept.resize((size_t)M);
+    const int rc = sd_roster_update(s->roster, job.cen.data(), job.cen_counts.data(), K, job.hard.data(), M, s->has_kept ? s->kept.data() : nullptr,
+                                    s->has_kept ? (int64_t)s->kept.size() : 0, s->has_kept ? shift : 0, c->speaker_match_threshold, ids.data());
+    if (rc == SD_ERR_NUMERIC) SD_FAIL(c, rc, "roster update: zero-magnitude centroid (reference throws, sd.cpp:493-495)");
+    if (rc) SD_FAIL(c, rc, "roster update failed (%d)", rc);
+    for (int64_t i = 0; i < M; ++i) kept[(size_t)i] = job.hard[(size_t)i] >= 0 ? ids[(size_t)job.hard[(size_t)i]] : -1;
+    (void)sd_relabel_turns_map(t, nt, ids.data(), K);      // (the labels were checked above)
+    job.roster_ids = std::move(ids);
+    return SD_OK;
+}
+
 int turns_impl(sd_stream* s, sd_turn** turns, int64_t* n_turns)
 {
     sd_ctx* c = s->c;
@@ -252,7 +282,16 @@ int turns_impl(sd_stream* s, sd_turn** turns, int64_t* n_turns)
     std::vector<sd_turn> v;
     if ((rc = finalize(c, b.seg, b.emb, total, b.n, v))) return rc;
     c->stage_ms[3] = now_ms() - t0;
-    return turns_out(c, v, turns, n_turns);
+    if (!s->roster) return turns_out(c, v, turns, n_turns);
+    // the turns are handed over first: the update is the last thing that can fail, and it changes nothing when it does
+    sd_turn* t = nullptr; int64_t nt = 0;
+    std::vector<int32_t> kept;
+    if ((rc = turns_out(c, v, &t, &nt))) return rc;
+    if ((rc = name_turns(s, t, nt, kept))) { sd_free_turns(t); return rc; }
+    s->kept.swap(kept); s->kept_origin = b.origin; s->has_kept = true;
+    c->stage_ms[3] = now_ms() - t0;
+    *turns = t; *n_turns = nt;
+    return SD_OK;
 }
 
 int read_impl(sd_stream* s, int64_t lo, int64_t hi, float* h_seg, float* h_emb)
@@ -448,6 +487,18 @@ int turns_many_impl(sd_ctx* c, sd_stream* const* s, int64_t S, sd_turn** turns, 
     }
     if ((rc = group_ranges(c, S, n_now.data(), sealed.data(), stale.data(), true, to_infer, &total, who))) return rc;
 
+    // rosters: a copy of each before the first update, put back if the call fails behind it; what the streams keep is committed at the end
+    std::vector<sd_roster*> rosters, saved;
+    for (int64_t i = 0; i < S; ++i) if (s[i]->roster && std::find(rosters.begin(), rosters.end(), s[i]->roster) == rosters.end()) rosters.push_back(s[i]->roster);
+    auto drop_saved = [&]() { for (sd_roster* q : saved) roster_free(q); saved.clear(); };
+    for (sd_roster* q : rosters) {
+        sd_roster* copy = nullptr;
+        if (roster_copy(q, &copy)) { drop_saved(); SD_FAIL(c, SD_ERR_NOMEM, "%s: out of host memory for the copy of a roster", who); }
+        saved.push_back(copy);
+    }
+    std::vector<std::vector<int32_t>> kept((size_t)S);
+    std::vector<char> named((size_t)S, 0);
+
     const double t0 = now_ms();
     clear_stage_ms(c);
     rc = finalize_jobs(c, S, turns, n_turns, status, [&](std::vector<FinalJob>& jobs) -> int {
@@ -458,8 +509,18 @@ int turns_many_impl(sd_ctx* c, sd_stream* const* s, int64_t S, sd_turn** turns, 
         if (int e = group_infer(c, s, to_infer, total, true)) return e;
         for (int64_t i = 0; i < S; ++i) jobs[(size_t)i] = FinalJob{s[i]->b.seg, s[i]->b.emb, sd_num_chunks(s[i]->b.n, nullptr), s[i]->b.n};
         return SD_OK;
+    }, [&](int64_t i, sd_turn* t, int64_t nt) -> int {
+        if (!s[i]->roster) return SD_OK;
+        named[(size_t)i] = 1;
+        return name_turns(s[i], t, nt, kept[(size_t)i]);
     });
-    if (rc) return rc;
+    if (rc) {
+        for (size_t q = 0; q < rosters.size(); ++q) roster_swap_tables(rosters[q], saved[q]);
+        drop_saved();
+        return rc;
+    }
+    drop_saved();
+    for (int64_t i = 0; i < S; ++i) if (named[(size_t)i]) { s[i]->kept.swap(kept[(size_t)i]); s[i]->kept_origin = s[i]->b.origin; s[i]->has_kept = true; }
     c->stage_ms[3] = now_ms() - t0;
     return SD_OK;
 }
@@ -526,6 +587,7 @@ extern "C" void sd_stream_close(sd_stream* s)
     (void)hipSetDevice(c->device);
     HipDev dev{c};
     book_release(dev, s->b);
+    if (s->roster) s->roster->attached -= 1;
     c->streams.erase(std::remove(c->streams.begin(), c->streams.end(), s), c->streams.end());
     delete s;
 }
@@ -576,6 +638,19 @@ extern "C" int sd_stream_set_window(sd_stream* s, int64_t keep_blocks)
     if (keep_blocks < -1) SD_FAIL(c, SD_ERR_ARG, "sd_stream_set_window: keep_blocks must be -1 (no window) or >= 0");
     if (int rc = check_call(s, "sd_stream_set_window")) return rc;
     s->window = keep_blocks;
+    return SD_OK;
+}
+extern "C" int sd_stream_set_roster(sd_stream* s, sd_roster* r)
+{
+    if (!s) return SD_ERR_ARG;
+    sd_ctx* c = s->c;
+    c->err.clear();
+    if (r && r->d != SD_EMB_DIM) SD_FAIL(c, SD_ERR_ARG, "sd_stream_set_roster: the roster's entries have %d dimensions, a stream's centroids %d", r->d, SD_EMB_DIM);
+    if (r == s->roster) return SD_OK;
+    if (s->roster) s->roster->attached -= 1;
+    if (r) r->attached += 1;
+    s->roster = r;
+    s->kept.clear(); s->kept_origin = 0; s->has_kept = false;      // what the stream kept were ids of the other roster
     return SD_OK;
 }
 extern "C" int sd_stream_origin(const sd_stream* s, int64_t* first_sample)

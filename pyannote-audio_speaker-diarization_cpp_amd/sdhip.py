@@ -74,6 +74,8 @@ EXPORTS = [
     "sd_cut_open_dev", "sd_cut_open", "sd_cut_open_pcm_dev", "sd_cut_open_f32", "sd_cut_open_wav", "sd_cut_turns", "sd_cut_turns_many",
     "sd_cut_dendrogram", "sd_cut_info", "sd_cut_close",
     "sd_sample_rows",
+    "sd_roster_open", "sd_roster_close", "sd_roster_load", "sd_roster_info", "sd_roster_speakers", "sd_roster_update", "sd_roster_update_last",
+    "sd_relabel_turns_map", "sd_stream_set_roster", "sd_last_roster_ids",
 ]
 # SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
 LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
@@ -219,6 +221,17 @@ def lib():
         L.sd_stream_forget.argtypes = [vp, i64]
         L.sd_stream_set_window.argtypes = [vp, i64]
         L.sd_stream_origin.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "sd_roster_open"):      # (likewise)
+        L.sd_roster_open.argtypes = [C.c_int, C.POINTER(vp)]
+        L.sd_roster_close.argtypes = [vp]
+        L.sd_roster_load.argtypes = [vp, vp, vp, i64]
+        L.sd_roster_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_int)]
+        L.sd_roster_speakers.argtypes = [vp, vp, vp, vp, i64, C.POINTER(i64)]
+        L.sd_roster_update.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, i64, dbl, vp]
+        L.sd_roster_update_last.argtypes = [vp, vp, vp, i64, C.POINTER(i64)]
+        L.sd_relabel_turns_map.argtypes = [C.POINTER(Turn), i64, vp, i64]
+        L.sd_stream_set_roster.argtypes = [vp, vp]
+        L.sd_last_roster_ids.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.sd_format_turn.argtypes = [C.POINTER(Turn), C.c_char_p, C.c_int]
     L.sd_stage_ms.argtypes = [vp, C.POINTER(dbl)]
     L.sd_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
@@ -496,6 +509,107 @@ def relabel_turns(turns, mode="pyannote"):
     return [(arr[i].start, arr[i].end, int(arr[i].label)) for i in range(len(turns))]
 
 
+def relabel_turns_map(turns, ids):
+    """sd_relabel_turns_map: the label k of every turn becomes ids[k] (Diarizer.last_roster_ids, Roster.update*); times and order stay.  A label outside
+    [0, len(ids)) raises SdError and nothing is renamed"""
+    arr = _turn_array(turns)
+    ids = np.ascontiguousarray(ids, np.int32)
+    rc = lib().sd_relabel_turns_map(arr, len(turns), _ptr(ids) if len(ids) else None, len(ids))
+    if rc:
+        raise SdError(rc, "sd_relabel_turns_map: a label outside the map")
+    return [(arr[i].start, arr[i].end, int(arr[i].label)) for i in range(len(turns))]
+
+
+class Roster:
+    """sd_roster_*: persistent speaker ids.  update() is the rule of include/sdhip.h on centroids and counts (and, optionally, row labels); update_last()
+    names the label columns of a Diarizer's last job; Stream.set_roster makes a stream's turns carry roster ids.  Host only: no GPU, no Diarizer needed."""
+
+    def __init__(self, d=EMB_DIM):
+        h = C.c_void_p(None)
+        rc = lib().sd_roster_open(int(d), C.byref(h))
+        if rc:
+            raise SdError(rc, "sd_roster_open: bad argument")
+        self._r = h
+        self.d = int(d)
+
+    def _handle(self):
+        if not self._r:
+            raise SdError(1, "the roster is closed")
+        return self._r
+
+    def close(self):
+        """sd_roster_close: raises SdError(1) while a stream still holds the roster"""
+        if self._r:
+            rc = lib().sd_roster_close(self._r)
+            if rc:
+                raise SdError(rc, "sd_roster_close: a stream is still attached")
+            self._r = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def load(self, centroids, counts):
+        """sd_roster_load: entries 0 .. P-1 into an empty roster"""
+        cen = np.ascontiguousarray(centroids, np.float64).reshape(-1, self.d)
+        cnt = np.ascontiguousarray(counts, np.int64)
+        if len(cnt) != len(cen):
+            raise SdError(1, "one count per centroid")
+        rc = lib().sd_roster_load(self._handle(), _ptr(cen) if len(cen) else None, _ptr(cnt) if len(cen) else None, len(cen))
+        if rc:
+            raise SdError(rc, "sd_roster_load: bad argument, or the roster is not empty")
+
+    def info(self):
+        """(entries P, updates so far, dimensions)"""
+        P, U, d = C.c_int64(0), C.c_int64(0), C.c_int(0)
+        lib().sd_roster_info(self._handle(), C.byref(P), C.byref(U), C.byref(d))
+        return int(P.value), int(U.value), int(d.value)
+
+    def speakers(self):
+        """sd_roster_speakers: (centroids [P][d] float64, counts [P] int64, seen [P] int64 = the index of the last update that gave the entry out, -1: never)"""
+        P = self.info()[0]
+        cen, cnt, seen = np.zeros((P, self.d), np.float64), np.zeros(P, np.int64), np.zeros(P, np.int64)
+        if P:
+            lib().sd_roster_speakers(self._handle(), _ptr(cen), _ptr(cnt), _ptr(seen), P, None)
+        return cen, cnt, seen
+
+    def update(self, centroids, counts, rows=None, prev=None, shift=0, threshold=None):
+        """sd_roster_update: ids [K] int32 of the K label columns; rows / prev = the hard labels of this job's rows and the ids the previous update gave
+        the rows of its table (row i now = row i + shift then); threshold None = the constant t * t / 2"""
+        cen = np.ascontiguousarray(centroids, np.float64).reshape(-1, self.d)
+        cnt = np.ascontiguousarray(counts, np.int64)
+        K = len(cen)
+        if len(cnt) != K:
+            raise SdError(1, "one count per centroid")
+        rows = None if rows is None else np.ascontiguousarray(rows, np.int32).reshape(-1)
+        prev = None if prev is None else np.ascontiguousarray(prev, np.int32).reshape(-1)
+        ids = np.zeros(K, np.int32)
+        keep = np.zeros(1, np.int32)                  # (an empty array has no address worth passing: absent and empty are different things here)
+        rc = lib().sd_roster_update(self._handle(), _ptr(cen) if K else None, _ptr(cnt) if K else None, K,
+                                    None if rows is None else _ptr(rows if len(rows) else keep), 0 if rows is None else len(rows),
+                                    None if prev is None else _ptr(prev if len(prev) else keep), 0 if prev is None else len(prev), int(shift),
+                                    float("nan") if threshold is None else float(threshold), _ptr(ids) if K else None)
+        if rc:
+            raise SdError(rc, "sd_roster_update: %s" % {1: "bad argument", 5: "zero-norm centroid", 7: "out of memory"}.get(rc, "failed"))
+        return ids
+
+    def update_last(self, diarizer):
+        """sd_roster_update_last: ids [K] int32 of the label columns of the diarizer's last job (after many_select(r): of recording r), by centroid alone"""
+        K = C.c_int64(0)
+        diarizer._chk(lib().sd_last_speakers(diarizer._h, None, 0, C.byref(K), None))
+        ids = np.zeros(max(K.value, 1), np.int32)
+        diarizer._chk(lib().sd_roster_update_last(self._handle(), diarizer._h, _ptr(ids), K.value, C.byref(K)))
+        return ids[:K.value].copy()
+
+
 def comm_unique_id():
     buf = C.create_string_buffer(COMM_ID_BYTES)
     rc = lib().sd_comm_unique_id(buf)
@@ -566,6 +680,11 @@ class Stream:
     def set_window(self, keep_blocks):
         """sd_stream_set_window: every push that seals a block forgets down to keep_blocks blocks (-1: no window)"""
         self._d._chk(lib().sd_stream_set_window(self._handle(), int(keep_blocks)))
+
+    def set_roster(self, roster):
+        """sd_stream_set_roster: from now on turns() carries the roster's ids (Diarizer.last_roster_ids gives the map); None detaches"""
+        self._d._chk(lib().sd_stream_set_roster(self._handle(), None if roster is None else roster._handle()))
+        self._roster = roster                  # (keeps the object alive as long as the stream names it)
 
     def origin(self):
         """sd_stream_origin: samples forgotten so far = the sample of everything pushed at which the stream's times start"""
@@ -916,6 +1035,14 @@ class Diarizer:
         rows = np.full(K.value, -1, np.int32)
         self._chk(lib().sd_last_enrolled(self._h, _ptr(rows) if K.value else None, K.value, C.byref(K)))
         return rows
+
+    def last_roster_ids(self):
+        """sd_last_roster_ids: [K] int32, the roster id of every raw label of the last job (they name last_speakers' rows); empty when no roster took part"""
+        K = C.c_int64(0)
+        self._chk(lib().sd_last_roster_ids(self._h, None, 0, C.byref(K)))
+        ids = np.zeros(K.value, np.int32)
+        self._chk(lib().sd_last_roster_ids(self._h, _ptr(ids) if K.value else None, K.value, C.byref(K)))
+        return ids
 
     # ---- a15-a17
     def reconstruct(self, seg, binarized, hard, count, n_samples):
