@@ -117,6 +117,37 @@ int sd_test_chunk_norm(sd_ctx*, const float* wav, int64_t n_wav, int64_t origin,
                        float w, float b, int stats_only, float canary, float* out);
 int sd_test_classifier(sd_ctx*, const float* y, const float* W, const float* bias, int64_t chunks, int F, float canary, float* seg_out);
 
+/* ---- test hooks (tests/test_ecapa_glue.py): ONE launch of one glue kernel of the embedding network (csrc/ecapa.hip) through the launcher run_ecapa_t
+ * calls, under the contract of the segmentation hooks above: host pointers, f32; every input followed by NaN (256 rows of the operand's row width, 256
+ * elements behind a vector); every output filled with `canary`, 256 slack rows behind it, back WHOLE; a case whose defined reads leave its operands is
+ * SD_ERR_ARG before any launch.  f16 = 1: the activations are _Float16: built in f32 as given, rounded by the product's own conversion kernel
+ * (k_rows_to_half), and an fp16 output comes back widened to f32.  Leading dimensions are multiples of 4.
+ *
+ * sd_test_ecapa_stats: kind 0 = k_masked_mean -> out [items + 256][C]; 1 = k_asp_stats, 2 = k_asp_pool -> out [items + 256][2 C] = (mean | std).
+ * x [rows][ld] (and logits [rows][ld], f32 in either mode, kind 2 only; else NULL), rows = rowoff[items] - row_base; item i's rows start at
+ * rowoff[i] - row_base and its frames < nvalid[i] are read: 1 <= nvalid[i] <= rowoff[i + 1] - rowoff[i].  rowoff [items + 1] ascending, rowoff[0] =
+ * row_base >= 0: the items of a larger plan in front of this batch.  C <= ld; the pad columns ld - C are the caller's (NaN in the tests).
+ * sd_test_se_apply: y = gate[item] * t2 + residual (k_se_apply) over the rows of space `os`.  off [4][items + 1]: prefix sums (off[s][0] = 0) of the rows
+ * each item stores in four row spaces; item i's frame t is row off[s][i] + t.  The row tables come from ecapa_build_rowtab on these sums.
+ * t2 [Mo][t2_ld], gate [items][C], C % 4 == 0, Mo = off[os][items].
+ * shared = 0 (the first block): res [off[rs][items]][res_ld] is a buffer of its own in space rs, mapped when rs != os; the output is column slice
+ * [out_col0, + C) of a [off[ys][items] + 256][y_ld] canary buffer, mapped when ys != os.  shared = 1 (the later blocks): res [off[ys][items]][C] is
+ * laid into column slice [res_col0, + C) of that same buffer (rs == ys, res_ld ignored; its 256 slack rows hold NaN), the output goes to slice
+ * [out_col0, + C), disjoint from it.  Every item must store at least as many rows in spaces rs and ys as in os.  y_out = the whole
+ * [off[ys][items] + 256][y_ld] buffer.
+ * sd_test_rowtab: k_build_rowtab; off_out / off_in [items + 1] prefix sums with bases base_out = off_out[0], base_in = off_in[0]; items <= 4095, at
+ * most 1024 rows per item.  tab_out [(off_out[items] - base_out + 128)][2] int32: the table and its 128 slack entries, preset to (canary, canary).
+ * sd_test_scatter_emb: k_scatter_emb; emb_c [n_c][192], cidx [items] (-1 = dropped, else < n_c) -> emb_out [items + 256][192].
+ * sd_test_to_half: kind 0 = k_feats_to_half: f [rows][96] -> h_out [rows + 256][128] fp16 bit patterns (the slack holds the bits of fp16(canary));
+ * kind 1 = k_rows_to_half: f [rows][width], width % 4 == 0 -> h_out [rows + 256][width]. */
+int sd_test_ecapa_stats(sd_ctx*, int kind, int f16, const float* x, const float* logits, const int32_t* nvalid, const int32_t* rowoff, int64_t items,
+                        int row_base, int C, int ld, float canary, float* out);
+int sd_test_se_apply(sd_ctx*, int f16, int shared, const float* t2, int t2_ld, const float* gate, const float* res, int res_ld, int res_col0, int out_col0,
+                     int y_ld, int C, const int32_t* off, int64_t items, int os, int rs, int ys, float canary, float* y_out);
+int sd_test_rowtab(sd_ctx*, const int32_t* off_out, const int32_t* off_in, int64_t items, int32_t canary, int32_t* tab_out);
+int sd_test_scatter_emb(sd_ctx*, const float* emb_c, int64_t n_c, const int32_t* cidx, int64_t items, float canary, float* emb_out);
+int sd_test_to_half(sd_ctx*, int kind, const float* f, int64_t rows, int width, float canary, uint16_t* h_out);
+
 #ifdef __cplusplus
 }
 #endif

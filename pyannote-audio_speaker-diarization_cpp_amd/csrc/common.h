@@ -381,6 +381,19 @@ int ecapa_need_rows(int nvalid, bool skip_dead_rows);             // rows of an 
 // row table of `items` items (k_build_rowtab): d_off_out / d_off_in = device prefix sums [items + 1] of the rows per item in the output / input space
 int ecapa_build_rowtab(sd_ctx* c, const int* d_off_out, int base_out, const int* d_off_in, int base_in, int64_t items, int2* d_rowtab);
 int ecapa_rows_to_half(sd_ctx* c, const float* d_f32, void* d_f16, int64_t n4);      // k_rows_to_half: n4 groups of four floats -> fp16 (the fp16 mode's conversion)
+int ecapa_feats_to_half(sd_ctx* c, const float* d_f32, void* d_f16, int64_t rows);   // k_feats_to_half: [rows][96] f32 -> [rows][128] fp16, columns 96 .. 127 zero
+int ecapa_scatter_emb(sd_ctx* c, const float* d_emb_c, const int* d_cidx, float* d_emb, int64_t items);   // k_scatter_emb: emb[i] = emb_c[cidx[i]], NaN where cidx[i] < 0
+// the launches of ecapa.hip's glue kernels, asynchronous on c->stream: grid, block and the instantiation (f16: the tensors marked void are _Float16, else
+// float) are computed here; run_ecapa_t and the test hooks of ecapa_test.hip call the same ones.  Item i's first row in x is rowoff[i] - row_base; the
+// statistics run over its frames < nvalid[i]; rows = the rows of the batch (the profile's bill).  masked_mean: out [items][C]; asp_stats / asp_pool:
+// ms / pooled [items][2 C] = (mean | std); logit [rows][ld] f32.  se_apply: y = gate[item] * t2 + res over the `rows` rows of t2's space (rowtab: a table
+// of that space); res_map / out_map: tables from t2's space into the residual's / the output's space, null = the same space; C % 4 == 0
+int launch_masked_mean(sd_ctx* c, bool f16, const void* x, int ld, const int* nvalid, const int* rowoff, int row_base, int64_t items, int64_t rows, float* out, int C);
+int launch_se_apply(sd_ctx* c, bool f16, const void* t2, int t2_ld, const float* gate, const void* res, int res_ld, void* y, int y_ld, int C, int64_t rows,
+                    const int2* rowtab, const int2* res_map, const int2* out_map);
+int launch_asp_stats(sd_ctx* c, bool f16, const void* x, int ld, const int* nvalid, const int* rowoff, int row_base, int64_t items, int64_t rows, float* ms, int C);
+int launch_asp_pool(sd_ctx* c, bool f16, const void* x, const float* logit, int ld, const int* nvalid, const int* rowoff, int row_base, int64_t items, int64_t rows,
+                    float* pooled, int C);
 int ecapa_row_plan(sd_ctx* c, const int* h_nvalid, int64_t n, EcapaRowPlan& plan, int* d_off /*[EC_SPACES][n + 1]*/);
 // items [a0, a1) of the plan; d_feats = space-0 rows of ALL the plan's items
 int run_ecapa(sd_ctx* c, const float* d_feats, const int* d_nvalid /*[n]*/, const EcapaRowPlan& plan, int64_t a0, int64_t a1, float* d_emb /*[n][192]*/);

@@ -168,6 +168,58 @@ int ecapa_rows_to_half(sd_ctx* c, const float* d_f32, void* d_f16, int64_t n4)
     KCHECK(c);
     return SD_OK;
 }
+int ecapa_feats_to_half(sd_ctx* c, const float* d_f32, void* d_f16, int64_t rows)
+{
+    hipLaunchKernelGGL(k_feats_to_half, GRID1(rows * 128), 0, c->stream, d_f32, (_Float16*)d_f16, rows);
+    KCHECK(c);
+    return SD_OK;
+}
+int ecapa_scatter_emb(sd_ctx* c, const float* d_emb_c, const int* d_cidx, float* d_emb, int64_t items)
+{
+    hipLaunchKernelGGL(k_scatter_emb, GRID1(items * SD_EMB_DIM), 0, c->stream, d_emb_c, d_cidx, d_emb, items);
+    KCHECK(c);
+    return SD_OK;
+}
+
+// the launches of the four glue kernels, asynchronous on c->stream: grid, block and the element type's instantiation are chosen here; run_ecapa_t and
+// the test hooks of ecapa_test.hip call the same ones.  rows = the rows of the batch in the kernel's space (the profile's byte bill)
+int launch_masked_mean(sd_ctx* c, bool f16, const void* x, int ld, const int* nvalid, const int* rowoff, int row_base, int64_t items, int64_t rows, float* out, int C)
+{
+    ProfScope ps(c, "se_mean", 0, (double)rows * C * 4.0);
+    const dim3 grid((C + 255) / 256, (unsigned)items), block(256);
+    if (f16) hipLaunchKernelGGL(k_masked_mean<_Float16>, grid, block, 0, c->stream, (const _Float16*)x, ld, nvalid, rowoff, row_base, out, C);
+    else hipLaunchKernelGGL(k_masked_mean<float>, grid, block, 0, c->stream, (const float*)x, ld, nvalid, rowoff, row_base, out, C);
+    KCHECK(c);
+    return SD_OK;
+}
+int launch_se_apply(sd_ctx* c, bool f16, const void* t2, int t2_ld, const float* gate, const void* res, int res_ld, void* y, int y_ld, int C, int64_t rows,
+                    const int2* rowtab, const int2* res_map, const int2* out_map)
+{
+    ProfScope ps(c, "se_apply", 0, (double)rows * C * 12.0);
+    if (f16) hipLaunchKernelGGL(k_se_apply<_Float16>, GRID1(rows * (C / 4)), 0, c->stream, (const _Float16*)t2, t2_ld, gate, (const _Float16*)res, res_ld, (_Float16*)y, y_ld, C, rows, rowtab, res_map, out_map);
+    else hipLaunchKernelGGL(k_se_apply<float>, GRID1(rows * (C / 4)), 0, c->stream, (const float*)t2, t2_ld, gate, (const float*)res, res_ld, (float*)y, y_ld, C, rows, rowtab, res_map, out_map);
+    KCHECK(c);
+    return SD_OK;
+}
+int launch_asp_stats(sd_ctx* c, bool f16, const void* x, int ld, const int* nvalid, const int* rowoff, int row_base, int64_t items, int64_t rows, float* ms, int C)
+{
+    ProfScope ps(c, "asp_stats", 0, (double)rows * C * 4.0);
+    const dim3 grid((C + 255) / 256, (unsigned)items), block(256);
+    if (f16) hipLaunchKernelGGL(k_asp_stats<_Float16>, grid, block, 0, c->stream, (const _Float16*)x, ld, nvalid, rowoff, row_base, ms, C);
+    else hipLaunchKernelGGL(k_asp_stats<float>, grid, block, 0, c->stream, (const float*)x, ld, nvalid, rowoff, row_base, ms, C);
+    KCHECK(c);
+    return SD_OK;
+}
+int launch_asp_pool(sd_ctx* c, bool f16, const void* x, const float* logit, int ld, const int* nvalid, const int* rowoff, int row_base, int64_t items, int64_t rows,
+                    float* pooled, int C)
+{
+    ProfScope ps(c, "asp_pool", 0, (double)rows * C * 8.0);
+    const dim3 grid((C + 255) / 256, (unsigned)items), block(256);
+    if (f16) hipLaunchKernelGGL(k_asp_pool<_Float16>, grid, block, 0, c->stream, (const _Float16*)x, logit, ld, nvalid, rowoff, row_base, pooled, C);
+    else hipLaunchKernelGGL(k_asp_pool<float>, grid, block, 0, c->stream, (const float*)x, logit, ld, nvalid, rowoff, row_base, pooled, C);
+    KCHECK(c);
+    return SD_OK;
+}
 
 // prec 0: f32 MFMA, float buffers.  prec 1 (ecapa_precision): fp16 MFMA, _Float16 buffers (X / Y leading dimensions in elements)
 static ConvArgs conv_args(const ConvLayer& L, const void* X, int x_ld, void* Y, int y_ld, int64_t M, bool per_item, int prec = 0)
@@ -251,7 +303,7 @@ static int run_ecapa_t(sd_ctx* c, const float* d_feats_all, const int* d_nvalid_
     WS(c, float, ib, "ec_ib", items * 128);
     WS(c, float, pooled, "ec_pooled", items * 2 * C3);
     int rc;
-    hipStream_t st = c->stream;
+    const bool f16 = sizeof(T) == 2;
     // row tables [output space][input space], built on first use
     int2* tabs[EC_SPACES][EC_SPACES] = {};
     auto tab = [&](int so, int si) -> int2* {
@@ -269,8 +321,7 @@ static int run_ecapa_t(sd_ctx* c, const float* d_feats_all, const int* d_nvalid_
     const void* f_in = d_feats; int f_ld = SD_FEAT_LD;
     if (sizeof(T) == 2) {
         WS(c, _Float16, fh, "ec_feats16", M * 128);
-        hipLaunchKernelGGL(k_feats_to_half, GRID1(M * 128), 0, st, d_feats, fh, M);
-        KCHECK(c);
+        if ((rc = ecapa_feats_to_half(c, d_feats, fh, M))) return rc;
         f_in = fh; f_ld = 128;
     }
     { TAB(t00, 0, 0); ConvArgs a = conv_args(E.block0, f_in, f_ld, x0, LD, M, true, P); a.act1 = 1; a.rowtab = t00; if ((rc = launch_conv_gemm(c, a, "block0"))) return rc; }
@@ -292,11 +343,7 @@ static int run_ecapa_t(sd_ctx* c, const float* d_feats_all, const int* d_nvalid_
             if ((rc = launch_conv_gemm(c, a, "res2net"))) return rc;
         }
         { ConvArgs a = conv_args(B.tdnn2, tr + C - S, LDT, t2, LD, Mo, true, P); a.act1 = 1; a.rowtab = t_oc; a.in_rows = (int)Mc; if ((rc = launch_conv_gemm(c, a, "tdnn2"))) return rc; }
-        {
-            ProfScope ps(c, "se_mean", 0, (double)Mo * C * 4.0);
-            hipLaunchKernelGGL(k_masked_mean<T>, dim3((C + 255) / 256, (unsigned)items), dim3(256), 0, st, t2, LD, d_nvalid, ro[os], rbase[os], se_s, C);
-            KCHECK(c);
-        }
+        if ((rc = launch_masked_mean(c, f16, t2, LD, d_nvalid, ro[os], rbase[os], items, Mo, se_s, C))) return rc;
         { ConvArgs a = conv_args(B.se1, se_s, C, se_h, 128, items, false); a.act1 = 1; if ((rc = launch_conv_gemm(c, a, "se1"))) return rc; }
         { ConvArgs a = conv_args(B.se2, se_h, 128, se_g, C, items, false); a.act2 = 2; if ((rc = launch_conv_gemm(c, a, "se2"))) return rc; }
         {
@@ -304,9 +351,7 @@ static int run_ecapa_t(sd_ctx* c, const float* d_feats_all, const int* d_nvalid_
             const int2* res_map = nullptr; const int2* out_map = nullptr;
             if (os != is) { TAB(m, os, is); res_map = m; }
             if (os != 1) { TAB(m, os, 1); out_map = m; }
-            ProfScope ps(c, "se_apply", 0, (double)Mo * C * 12.0);
-            hipLaunchKernelGGL(k_se_apply<T>, GRID1(Mo * (C / 4)), 0, st, t2, LD, se_g, xin, xin_ld, cat + (size_t)b * C, LD3, C, Mo, t_oc, res_map, out_map);
-            KCHECK(c);
+            if ((rc = launch_se_apply(c, f16, t2, LD, se_g, xin, xin_ld, cat + (size_t)b * C, LD3, C, Mo, t_oc, res_map, out_map))) return rc;
         }
     }
     // mfa: TDNNBlock(3C -> 3C, k1) over cat(x1,x2,x3)
@@ -326,12 +371,10 @@ static int run_ecapa_t(sd_ctx* c, const float* d_feats_all, const int* d_nvalid_
         if ((rc = ecapa_rows_to_half(c, mfa32, mfa, MN * LD3 / 4))) return rc;
     }
     // ASP with global context: cat[x, mean, std] @ W == x @ Wx + (mean,std) @ Wms  (per-item bias)
-    {
-        ProfScope ps(c, "asp_stats", 0, (double)MN * C3 * 4.0);
-        if (mfa32) hipLaunchKernelGGL(k_asp_stats<float>, dim3((C3 + 255) / 256, (unsigned)items), dim3(256), 0, st, mfa32, LD3, d_nvalid, ro[3], rbase[3], ms, C3);
-        else hipLaunchKernelGGL(k_asp_stats<T>, dim3((C3 + 255) / 256, (unsigned)items), dim3(256), 0, st, mfa, LD3, d_nvalid, ro[3], rbase[3], ms, C3);
-        KCHECK(c);
-    }
+    // (the pooling statistics read the f32 MFA output where the fp16 mode keeps one)
+    const void* pool_x = mfa32 ? (const void*)mfa32 : (const void*)mfa;
+    const bool pool_f16 = f16 && !mfa32;
+    if ((rc = launch_asp_stats(c, pool_f16, pool_x, LD3, d_nvalid, ro[3], rbase[3], items, MN, ms, C3))) return rc;
     { ConvArgs a = conv_args(E.asp_tdnn_ms, ms, 2 * C3, ib, 128, items, false); if ((rc = launch_conv_gemm(c, a, "asp_ms"))) return rc; }
     // attention logits stay f32 in either mode (they feed an exp: fp16's 3 decimal digits at |logit| ~ 30 would be percents of a weight).
     // f32 mode: cat is dead after mfa and large enough; fp16 mode: its own buffer
@@ -345,12 +388,7 @@ static int run_ecapa_t(sd_ctx* c, const float* d_feats_all, const int* d_nvalid_
         { ConvArgs a = conv_args(E.asp_tdnn_x, mfa, LD3, hid, 128, MN, true, P); a.act1 = 1; a.act2 = 1; a.item_bias = ib; a.ib_ld = 128; a.rowtab = t33; if ((rc = launch_conv_gemm(c, a, "asp_tdnn"))) return rc; }
         { ConvArgs a = conv_args(E.asp_conv, hid, 128, logits, LD3, MN, true, P); a.rowtab = t33; a.y_f32 = 1; if ((rc = launch_conv_gemm(c, a, "asp_conv"))) return rc; }
     }
-    {
-        ProfScope ps(c, "asp_pool", 0, (double)MN * C3 * 8.0);
-        if (mfa32) hipLaunchKernelGGL(k_asp_pool<float>, dim3((C3 + 255) / 256, (unsigned)items), dim3(256), 0, st, mfa32, logits, LD3, d_nvalid, ro[3], rbase[3], pooled, C3);
-        else hipLaunchKernelGGL(k_asp_pool<T>, dim3((C3 + 255) / 256, (unsigned)items), dim3(256), 0, st, mfa, logits, LD3, d_nvalid, ro[3], rbase[3], pooled, C3);
-        KCHECK(c);
-    }
+    if ((rc = launch_asp_pool(c, pool_f16, pool_x, logits, LD3, d_nvalid, ro[3], rbase[3], items, MN, pooled, C3))) return rc;
     // asp_bn folded into fc
     { ConvArgs a = conv_args(E.fc, pooled, 2 * C3, d_emb, SD_EMB_DIM, items, false); if ((rc = launch_conv_gemm(c, a, "fc"))) return rc; }
     return SD_OK;
@@ -564,7 +602,5 @@ int run_embed(sd_ctx* c, const DevWav& w, const float* d_masks, int64_t items, i
         }
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_scatter_emb, GRID1(items * SD_EMB_DIM), 0, c->stream, emb_c, cidx, d_emb, items);
-    KCHECK(c);
-    return SD_OK;
+    return ecapa_scatter_emb(c, emb_c, cidx, d_emb, items);
 }

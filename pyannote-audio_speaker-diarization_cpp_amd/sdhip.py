@@ -39,6 +39,8 @@ class ConvCase(C.Structure):
 
 CONV_SLACK_ROWS = 256      # guard rows behind the buffers of Diarizer.conv_case
 SEG_SLACK_ROWS = 256       # ... and behind those of Diarizer.lstm_rec_case / pool_norm_case / chunk_norm_case / classifier_case
+GLUE_SLACK_ROWS = 256      # ... and behind those of Diarizer.ecapa_stats_case / se_apply_case / scatter_emb_case / to_half_case
+ROWTAB_SLACK = 128         # slack entries behind the table of Diarizer.rowtab_case
 
 
 class SdError(RuntimeError):
@@ -62,6 +64,7 @@ EXPORTS = [
     "sd_fcluster", "sd_segment_chunks", "sd_embed_signals",
     "sd_linkage_ex", "sd_cluster_ex", "sd_set_option_f64", "sd_linkage_method_from_name", "sd_test_conv", "sd_test_emb_batches",
     "sd_test_lstm_rec", "sd_test_pool_norm", "sd_test_chunk_norm", "sd_test_classifier",
+    "sd_test_ecapa_stats", "sd_test_se_apply", "sd_test_rowtab", "sd_test_scatter_emb", "sd_test_to_half",
     "sd_activity_scores", "sd_activity_regions", "sd_activity", "sd_activity_dev", "sd_activity_f32", "sd_activity_wav", "sd_last_activity_scores",
     "sd_stream_open", "sd_stream_push", "sd_stream_push_dev", "sd_stream_push_f32", "sd_stream_turns", "sd_stream_info", "sd_stream_read",
     "sd_stream_close", "sd_stream_sealed_chunks", "sd_stream_forget", "sd_stream_set_window", "sd_stream_origin",
@@ -247,6 +250,11 @@ def lib():
     L.sd_test_pool_norm.argtypes = [vp, vp, i64, i64, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, vp]
     L.sd_test_chunk_norm.argtypes = [vp, vp, i64, i64, i64, i64, C.c_int, i64, C.c_float, C.c_float, C.c_int, C.c_float, vp]
     L.sd_test_classifier.argtypes = [vp, vp, vp, vp, i64, C.c_int, C.c_float, vp]
+    L.sd_test_ecapa_stats.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_float, vp]
+    L.sd_test_se_apply.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp] + [C.c_int] * 5 + [vp, i64, C.c_int, C.c_int, C.c_int, C.c_float, vp]
+    L.sd_test_rowtab.argtypes = [vp, vp, vp, i64, i32, vp]
+    L.sd_test_scatter_emb.argtypes = [vp, vp, i64, vp, i64, C.c_float, vp]
+    L.sd_test_to_half.argtypes = [vp, C.c_int, vp, i64, C.c_int, C.c_float, vp]
     L.sd_test_emb_batches.restype = i64
     L.sd_test_emb_batches.argtypes = [vp, i64, i64, C.c_int, C.c_int, vp, i64]
     _lib = L
@@ -1450,6 +1458,60 @@ class Diarizer:
         seg = np.zeros((chunks * FRAMES + SEG_SLACK_ROWS, 3), np.float32)
         self._chk(lib().sd_test_classifier(self._h, _ptr(y), _ptr(W), _ptr(b), chunks, F, canary, _ptr(seg)))
         return seg
+
+    # ---- one glue kernel of the embedding network alone (sdhip_test.h); each returns the WHOLE output buffer, guard rows included
+    def ecapa_stats_case(self, kind, x, nvalid, rowoff, C_, logits=None, f16=False, canary=-7776.0):
+        """sd_test_ecapa_stats: kind "mean" (k_masked_mean) -> [items + GLUE_SLACK_ROWS][C]; "stats" (k_asp_stats) / "pool" (k_asp_pool, with logits)
+        -> [items + GLUE_SLACK_ROWS][2 C].  x / logits [rows][ld], rows = rowoff[-1] - rowoff[0], row_base = rowoff[0]; C_ <= ld"""
+        x = np.ascontiguousarray(x, np.float32)
+        nv, off = np.ascontiguousarray(nvalid, np.int32), np.ascontiguousarray(rowoff, np.int32)
+        items = len(nv)
+        assert x.ndim == 2 and off.shape == (items + 1,) and x.shape[0] == off[-1] - off[0], (x.shape, off)
+        k = {"mean": 0, "stats": 1, "pool": 2}[kind]
+        if logits is not None:
+            logits = np.ascontiguousarray(logits, np.float32)
+            assert logits.shape == x.shape
+        out = np.zeros((items + GLUE_SLACK_ROWS, C_ if k == 0 else 2 * C_), np.float32)
+        self._chk(lib().sd_test_ecapa_stats(self._h, k, int(bool(f16)), _ptr(x), _ptr(logits) if logits is not None else None, _ptr(nv), _ptr(off), items,
+                                            int(off[0]), int(C_), x.shape[1], canary, _ptr(out)))
+        return out
+
+    def se_apply_case(self, t2, gate, res, off, os, rs, ys, *, shared, y_ld, out_col0, res_col0=0, f16=False, canary=-7776.0):
+        """sd_test_se_apply: t2 [Mo][t2_ld], gate [items][C], off [4][items + 1] prefix sums of the four row spaces; shared=False: res [rows of space rs][res_ld]
+        in a buffer of its own; shared=True: res [rows of space ys][C] becomes column slice res_col0 of the output buffer.
+        -> the whole [rows of space ys + GLUE_SLACK_ROWS][y_ld] buffer, the output in columns [out_col0, out_col0 + C)"""
+        t2, gate, res = (np.ascontiguousarray(a, np.float32) for a in (t2, gate, res))
+        off = np.ascontiguousarray(off, np.int32)
+        items, C_ = gate.shape
+        assert off.shape == (4, items + 1) and t2.shape[0] == off[os, -1] and res.shape[0] == off[rs, -1], (off.shape, t2.shape, res.shape)
+        assert res.shape[1] == C_ if shared else res.shape[1] >= C_
+        y = np.zeros((int(off[ys, -1]) + GLUE_SLACK_ROWS, y_ld), np.float32)
+        self._chk(lib().sd_test_se_apply(self._h, int(bool(f16)), int(bool(shared)), _ptr(t2), t2.shape[1], _ptr(gate), _ptr(res), res.shape[1], int(res_col0),
+                                         int(out_col0), int(y_ld), C_, _ptr(off), items, os, rs, ys, canary, _ptr(y)))
+        return y
+
+    def rowtab_case(self, off_out, off_in, canary=-7776):
+        """sd_test_rowtab: prefix sums [items + 1] of the output and the input space (their first entries are the bases) -> [rows + ROWTAB_SLACK][2] int32"""
+        oo, oi = np.ascontiguousarray(off_out, np.int32), np.ascontiguousarray(off_in, np.int32)
+        assert oo.ndim == 1 and oo.shape == oi.shape
+        tab = np.zeros((int(oo[-1] - oo[0]) + ROWTAB_SLACK, 2), np.int32)
+        self._chk(lib().sd_test_rowtab(self._h, _ptr(oo), _ptr(oi), len(oo) - 1, canary, _ptr(tab)))
+        return tab
+
+    def scatter_emb_case(self, emb_c, cidx, canary=-7776.0):
+        """sd_test_scatter_emb: emb_c [n_c][192], cidx [items] (-1 = dropped) -> [items + GLUE_SLACK_ROWS][192]"""
+        emb_c, cidx = np.ascontiguousarray(emb_c, np.float32).reshape(-1, EMB_DIM), np.ascontiguousarray(cidx, np.int32)
+        out = np.zeros((len(cidx) + GLUE_SLACK_ROWS, EMB_DIM), np.float32)
+        self._chk(lib().sd_test_scatter_emb(self._h, _ptr(emb_c) if len(emb_c) else None, len(emb_c), _ptr(cidx), len(cidx), canary, _ptr(out)))
+        return out
+
+    def to_half_case(self, f, feats=False, canary=-7776.0):
+        """sd_test_to_half: feats=True: k_feats_to_half, f [rows][96] -> fp16 [rows + GLUE_SLACK_ROWS][128]; else k_rows_to_half, f [rows][w] -> [rows + ...][w]"""
+        f = np.ascontiguousarray(f, np.float32)
+        rows, w = f.shape
+        out = np.zeros((rows + GLUE_SLACK_ROWS, 128 if feats else w), np.uint16)
+        self._chk(lib().sd_test_to_half(self._h, 0 if feats else 1, _ptr(f), rows, w, canary, _ptr(out)))
+        return out.view(np.float16)
 
     def read_ws(self, name, dtype, count, offset=0):
         """test hook: `count` elements of the named device workspace"""

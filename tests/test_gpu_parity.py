@@ -226,6 +226,78 @@ def test_frontend_parity(diarizer, weights):
     np.testing.assert_allclose(f_gpu[~bad], f_ref[~bad], rtol=RTOL, atol=ATOL)
 
 
+def _wide_mel(total, edge=False):
+    """a [201][80] filterbank whose stored runs (first to last non-zero bin of a filter, weights.cpp) total `total`: 79 triangular filters of
+    total // 79 or one more bins, spread over the spectrum; filter 40 has exact zeros inside its run, filter 79 is all zero.  edge: one more
+    weight, 1e-30, in front of the run of filter 20"""
+    mel = np.zeros((201, 80), np.float32)
+    runs = np.full(79, total // 79)
+    runs[:total % 79] += 1
+    lo20 = 0
+    for m in range(79):
+        r = int(runs[m])
+        lo = int(np.clip(round(2 + 196 * m / 78 - r / 2), 1, 200 - r))
+        mel[lo:lo + r, m] = 1.0 - np.abs(np.arange(r) - (r - 1) / 2) / (r / 2 + 1)
+        if m == 40:
+            mel[lo + 1:lo + r - 1:2, m] = 0.0
+        if m == 20:
+            lo20 = lo
+    if edge:
+        mel[lo20 - 1, 20] = 1e-30
+    stored = sum(int(np.ptp(np.flatnonzero(mel[:, m]))) + 1 for m in range(80) if mel[:, m].any())
+    assert stored == total + int(edge) and (mel[:, 40] == 0)[np.flatnonzero(mel[:, 40])[0]:np.flatnonzero(mel[:, 40])[-1]].any() and not mel[:, 79].any()
+    return mel
+
+
+def test_frontend_mel_weights_from_global_memory(weights, tmp_path):
+    """k_stft_fbank keeps up to 512 mel weights in LDS and reads a denser bank from global memory; the product's bank has 402, so only packs with
+    another fbank.matrix enter the second path.  Banks of 512 (the last LDS size), 513, 1000 and 1536 (the most the front end takes) stored
+    weights against stft_ref + fbank_norm_ref with the same matrix, on items that select everything, alternating frames, too little, and a chunk
+    that ends past the audio.  The 513 bank is the 512 bank plus one weight of 1e-30: the two paths must agree to the same bar.  A bank of 1537
+    is refused with SD_ERR_MODEL, and the context still segments afterwards."""
+    rng = np.random.default_rng(29)
+    wav, masks = _wav_and_masks(rng, 4)
+    wav = wav[:84000]                              # chunk 1 (item 3) ends 4000 samples past the audio
+    masks[0] = 1                                   # everything selected
+    masks[1, ::2] = 0; masks[1, 1::2] = 1          # alternating frames: many short runs
+    masks[2] = 0; masks[2, :2] = 1                 # 546 samples < 640: too short
+    sigs, lens, bad = _oracle_signals(wav, masks)
+    assert bad.tolist() == [False, False, True, False]
+    st = nn.stft_ref(sigs, weights[3]["stft.window"])
+
+    def run(mel, k=[0]):
+        ep = str(tmp_path / ("mel%d.sdw" % k[0])); k[0] += 1
+        nn.save_pack(ep, dict(weights[3], **{"fbank.matrix": mel}))
+        d = sdhip.Diarizer(weights[0], ep)
+        try:
+            return d.frontend(wav, masks)
+        finally:
+            d.close()
+
+    got = {}
+    for total, edge in ((512, False), (512, True), (1000, False), (1536, False)):
+        mel = _wide_mel(total, edge)
+        f_gpu, l_gpu = run(mel)
+        assert np.array_equal(l_gpu, lens)
+        f_ref = nn.fbank_norm_ref(st, lens, mel).numpy()
+        assert np.isfinite(f_gpu[~bad]).all()
+        np.testing.assert_allclose(f_gpu[~bad], f_ref[~bad], rtol=RTOL, atol=ATOL, err_msg="%d stored mel weights" % (total + edge))
+        got[total + edge] = f_gpu
+    np.testing.assert_allclose(got[513][~bad], got[512][~bad], rtol=RTOL, atol=ATOL)       # global-memory path == LDS path
+    # one weight too many
+    ep = str(tmp_path / "mel_dense.sdw")
+    nn.save_pack(ep, dict(weights[3], **{"fbank.matrix": _wide_mel(1536, True)}))
+    d = sdhip.Diarizer(weights[0], ep)
+    try:
+        with pytest.raises(sdhip.SdError) as e:
+            d.frontend(wav, masks)
+        assert e.value.code == 3 and "too dense" in str(e.value) and "1537" in str(e.value)      # SD_ERR_MODEL
+        seg = d.segment(wav)
+        assert seg.shape == (2, 293, 3) and np.isfinite(seg).all() and seg.any()
+    finally:
+        d.close()
+
+
 def test_ecapa_parity(diarizer, weights):
     rng = np.random.default_rng(3)
     feats = (3.0 * rng.standard_normal((6, 501, 80))).astype(np.float32)
