@@ -125,6 +125,14 @@ enum {
 enum { SD_METRIC_EUCLIDEAN = 0, SD_METRIC_COSINE = 1 };
 int sd_linkage_ex(sd_ctx*, const double* h_X, int64_t N, int d, int method, int metric, double* h_Z);     /* Clustering.py:251-276 / 317-333 */
 int sd_cluster_ex(sd_ctx*, const double* h_X, int64_t N, int d, int method, int metric, double cutoff, int32_t* h_labels1);     /* Clustering.py:251-276 / 317-333 */
+/* ---- a12 for J independent jobs in one call: the batch form of sd_linkage_ex.  h_X holds the rows of all jobs, job after job (N[j] rows of d each),
+ * h_Z the dendrograms in the same order, max(N[j] - 1, 0) rows of 4 each.  Z of job j is, byte for byte, what sd_linkage_ex gives for job j alone,
+ * whatever else is in the call and in whatever order, for every N: the jobs that sd_linkage_ex runs on one workgroup (N < 1500) share launches,
+ * one workgroup per job, the others take sd_linkage_ex's own route.  N[j] of 0 or 1 is legal: no rows, status SD_OK.  A job with a zero-norm row
+ * under the cosine metric gets status[j] = SD_ERR_NUMERIC and its rows of h_Z are left as they were; the others finish and the call returns SD_OK.
+ * SD_ERR_ARG before anything is written: a null pointer, J < 1, a negative N[j], d <= 0, more than 2^31 - 1 rows in all, an unknown method or
+ * metric, centroid / median / ward with the cosine metric. */
+int sd_linkage_many(sd_ctx*, const double* h_X /* rows of all jobs, job after job */, const int64_t* N /*[J]*/, int64_t J, int d, int method, int metric, double* h_Z /* sum(max(N[j]-1,0)) rows of 4 */, int32_t* status /*[J]*/);     /* cl.cpp:289-440; Clustering.py:251-276 / 317-333 */
 /* host-only: "single", "complete", "average", "centroid", "median", "ward", "weighted" -> its code, anything else -> -1 (Clustering.py:251-276 / 317-333) */
 int sd_linkage_method_from_name(const char* name);
 /* ---- a13 alone: Clustering::fcluster (cl.h:9-10, cl.cpp:442-457; criterion "distance", cl.cpp:121-232): Z [N-1][4] of N observations
@@ -599,7 +607,14 @@ int sd_stage_ms(const sd_ctx*, double* ms4);
  *   mode 0, identical turns on the planted hour and on the reference's 1-min wav),
  * "rank0_permille" (sd_diarize_sharded: share of the chunks rank 0 infers itself, -1 = equal),
  * "comm_timeout_ms" (deadline of the exchange step of a sharded job, default 600 000),
- * "activity_hamming" (0 / 1, see sd_activity* above).
+ * "activity_hamming" (0 / 1, see sd_activity* above),
+ * "linkage_batch" (0 (default) / 1; anything else SD_ERR_ARG): 1 = the group calls (sd_diarize_many*, sd_stream_turns_many) run the dendrograms of
+ *   their jobs ahead of the per-job finalize, in shared launches with one workgroup per job (what sd_linkage_many does), for every job that
+ *   clusters 2 .. 1499 train rows without an enrolled gallery; 0 = one job after the other.  Results are the same bytes either way; single-job
+ *   entries never look at it.  Worth setting where the jobs of a call are short (recordings or streams of a few minutes, or any length under
+ *   "max_num_embeddings" <= 1499): 64 streams at 1 min update in 31 ms instead of 106.  Off by default because jobs of 1500 train rows and more
+ *   -- a stream from about 10 minutes on -- take sd_linkage_ex's own route either way and gain nothing (README, "batched small-N linkage").  "linkage_batch_bytes" (>= 1, default 2 GiB): the device bytes the workspaces of one such group of jobs may take, here and
+ *   in sd_linkage_many; more jobs than fit run in several groups, and results do not depend on the grouping.
  * Test and tuning keys are listed in sdhip_test.h.  An unknown key returns SD_ERR_ARG. */
 int sd_set_option(sd_ctx*, const char* key, int64_t value);
 /* the real-valued keys: "clustering_threshold" (Clustering.py:251-276 / 317-333; outside [0, 2] or NaN: SD_ERR_ARG) and the four "activity_*" keys of

@@ -61,8 +61,9 @@ int64_t sd_test_emb_batches(const int32_t* nvalid, int64_t n, int64_t batch_item
  * "linkage_force_heap" (1 = skip the cooperative kernel: the heap replay on tie-free data), "linkage_hx_wide" (1 = k_linkage_hx's 32-bit key / position form, which
  * jobs above 65 535 rows take, on any size), "linkage_prefetch" (1 = k_linkage_rg's helper wave; measured: no gain), "ws_limit_mb" (test: PROCESS-WIDE, a workspace request above this many
  * MB fails as on an exhausted GPU; 0 = off), "emb_batch_default" (test: forget an explicit "emb_batch_items"; value = embedding calls the
- * context pretends to have made, 0 = the next one plans the small first-job arena) and "cut_group_bytes" (sd_cut_turns_many: the bytes the
- * activation tables of one group of cuts may take, default 1 GiB, at least 1; a cut that alone takes more is a group of one). */
+ * context pretends to have made, 0 = the next one plans the small first-job arena), "cut_group_bytes" (sd_cut_turns_many: the bytes the
+ * activation tables of one group of cuts may take, default 1 GiB, at least 1; a cut that alone takes more is a group of one) and
+ * "linkage_batch_threads" (k_linkage_heap_jobs: threads of the workgroup of a job; 0 auto (default: 256, the measured choice), 256 or 1024; same bits). */
 /* environment (diagnostic): SD_TRACE_CREATE=1 prints where sd_create's time goes; SD_TRACE_WS=1 makes sd_diarize_dev print the job's stage times and what the
  * process's workspace hipMalloc / hipFree calls have cost so far (count, GB, ms) with every workspace of 256 MB or more. */
 /* tuning hook (tools/): time one conv_gemm shape on scratch data (dbg = 100 * pad_units + 10 * (sched + 1); a non-zero last digit,

@@ -203,7 +203,27 @@ int cluster_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, in
     const int method = c->clustering_method;
     const bool euclid = method == SD_LINKAGE_CENTROID || method == SD_LINKAGE_MEDIAN || method == SD_LINKAGE_WARD;
     *Xout = X; *Xnout = Xn;
+    // a group call ran the dendrogram of these rows ahead of the job (finalize_jobs, many.hip: the same kernels on the same train rows); it is taken once
+    if (c->ahead_N == N && N >= 2) { Z.swap(c->ahead_Z); c->ahead_N = -1; return SD_OK; }
     return run_linkage_host(c, euclid ? Xn : X, N, d, method, euclid ? SD_METRIC_EUCLIDEAN : SD_METRIC_COSINE, Z);
+}
+
+// The rows cluster_rows hands to the linkage for the train rows idx of d_emb, into out [N][d] on the device (asynchronous): the same kernel, so the same bits
+int linkage_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, int d, double* out)
+{
+    const int64_t N = (int64_t)idx.size();
+    if (N < 1) return SD_OK;
+    WS(c, int, d_tidx, "cl_tidx", N);
+    HIPCHK(c, hipMemcpyAsync(d_tidx, idx.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    const int method = c->clustering_method;
+    if (method == SD_LINKAGE_CENTROID || method == SD_LINKAGE_MEDIAN || method == SD_LINKAGE_WARD)
+        hipLaunchKernelGGL(k_gather_normalize, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, c->stream, d_emb, d_tidx, N, d, (double*)nullptr, out);
+    else {
+        WS(c, double, Xn, "cl_Xn", N * d);
+        hipLaunchKernelGGL(k_gather_normalize, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, c->stream, d_emb, d_tidx, N, d, out, Xn);
+    }
+    KCHECK(c);
+    return SD_OK;
 }
 
 // a11: every small cluster goes to the nearest candidate -- first the G rows of `enrolled` (host, [G][d]; the enrolled flow), then the large clusters in

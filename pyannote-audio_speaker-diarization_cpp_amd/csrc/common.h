@@ -213,6 +213,10 @@ struct sd_ctx {
     bool linkage_force_heap = false;           // test / measurement: skip the cooperative kernel, go straight to the heap replay
     int64_t linkage_kernel = -1;               // -1 auto / 1: k_linkage_rg (linkage_rg.hip) for the square form where its geometry fits (1: with more threads than linkage_threads asks for where that makes it fit), else k_linkage_mw (linkage_mw.hip); 0: k_linkage_mw
     int64_t linkage_threads = 0;               // 0 auto (linkage_plan: k_linkage_rg 256, doubled until its geometry fits; k_linkage_mw 512 for N >= 8000 -- one XCD: N >= 16000 --, else 256), else rounded down to 128 / 256 / 512 / 1024 threads per cooperative workgroup
+    int64_t linkage_batch = 0;                 // group calls (finalize_jobs, many.hip): 1 = the dendrograms of the jobs that fit run ahead of the per-job finalize in shared launches (run_linkage_many), 0 = one job after the other (the default: profiles/linkage_many_times.txt)
+    int64_t linkage_batch_bytes = (int64_t)2 << 30;   // run_linkage_many: bytes the workspaces of one group of jobs may take
+    int64_t linkage_batch_threads = 0;         // run_linkage_many: threads of the workgroup of a job, 0 auto (256), else 256 or 1024; tuning
+    std::vector<double> ahead_Z; int64_t ahead_N = -1;      // finalize_jobs -> cluster_rows: the dendrogram of the job being finalized, from the pass ahead (ahead_N = its train rows; -1 = none)
     int num_cu = 256;
     bool constrained_assignment = false;        // Clustering.py:81-94 (one cluster per local speaker of a chunk)
     // the three hyper-parameters of Clustering.py:251-276; defaults = what the reference hard-codes (sd.cpp:2049-2056)
@@ -423,6 +427,7 @@ int launch_lstm_rec(sd_ctx* c, const float* G, const float* whh_f, const float* 
 int launch_classifier(sd_ctx* c, const float* y, const float* W, const float* bias, float* seg, int64_t chunks, int F);
 // ---- pipeline.cpp
 __global__ void k_pcm_to_f32(const int16_t* __restrict__ pcm, float* __restrict__ dst, int64_t n);   // dst[0, n) = pcm / 32768, dst[n, n + SD_WAV_PAD) = 0; grid GRID1(n + SD_WAV_PAD)
+__global__ void k_f32_to_f64(const float* __restrict__ a, double* __restrict__ b, int64_t n);          // embeddings widened before clustering (sd.cpp:2555); grid GRID1(n)
 // the two producers of workspace "wav_f32": *out = {n samples, origin 0, padded}; a caller that uploaded a slice of a longer recording sets n and origin itself
 int pcm_to_wav(sd_ctx* c, const int16_t* d_pcm, int64_t n, DevWav* out);
 int f32_to_wav(sd_ctx* c, const float* h_wav, int64_t n, DevWav* out);
@@ -469,6 +474,11 @@ int64_t closest_frame_host(double w_start, double w_step, double w_dur, double t
 // ---- linkage.hip
 int run_linkage(sd_ctx* c, const double* d_X, int64_t N, int d, double* d_Z, int method = SD_LINKAGE_CENTROID, int metric = SD_METRIC_EUCLIDEAN);
 int run_linkage_host(sd_ctx* c, const double* d_X, int64_t N, int d, int method, int metric, std::vector<double>& Z);      // cluster.hip: run_linkage, Z on the host
+// ---- linkage_batch.hip: J independent jobs, rows on the device, Z [N - 1][4] of each to the host.  The jobs run_linkage would give to its one-workgroup
+// kernel share launches (one workgroup per job, linkage_batch_plan.h), the others go through run_linkage; every Z is the bytes run_linkage gives for the
+// job alone.  status[j] = SD_OK, or SD_ERR_NUMERIC for a job with a zero-norm row under the cosine metric (its Z is left as it was); any other failure is returned
+struct LinkageManyJob { const double* d_X; int64_t N; double* h_Z; };
+int run_linkage_many(sd_ctx* c, const LinkageManyJob* jobs, int64_t J, int d, int method, int metric, int32_t* status);
 int run_clustering(sd_ctx* c, const double* d_emb /*[M][d] f64*/, int64_t M, int d, std::vector<int>& hard, int* K,
                    int num_clusters = -1, int min_clusters = -1, int max_clusters = -1, std::vector<double>* soft_best = nullptr);
 // ---- activity.hip
@@ -488,6 +498,7 @@ int run_nearest_gallery(sd_ctx* c, const double* d_E, const int* d_tidx /*[N] or
 // ---- cluster.hip: the steps of run_clustering that cut.hip shares: the front (train rows, X / Xn / dendrogram), the one finish of a cut, the centroids
 int train_rows(sd_ctx* c, const double* d_e64, int64_t M, int d, std::vector<int>& tidx);
 int cluster_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, int d, double** Xout, double** Xnout, std::vector<double>& Z);
+int linkage_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, int d, double* out /*[N][d], device*/);      // the rows cluster_rows gives the linkage (context's method); asynchronous
 int cluster_cut(sd_ctx* c, const std::vector<double>& Z, int64_t N, const double* X, int d, const ClusterSpec& spec, ClusterPlan& p, std::vector<int>* first_cut);
 int mean_of_rows(sd_ctx* c, const double* d_emb, int d, const std::vector<int>& tidx, std::vector<double>& h_cen);
 int final_means(sd_ctx* c, const double* X, int d, const std::vector<int>& lab, int nl, int G, std::vector<int>& order, std::vector<int>& off, double** cen_out);

@@ -202,15 +202,12 @@ struct LinkagePlan {
 static LinkagePlan linkage_plan(const sd_ctx* c, int64_t N, bool square_ok)
 {
     LinkagePlan p = {};
-    int G = (int)c->linkage_wgs;
     // auto geometry (measured on clustered data, profiles/r01_linkage_scaling.txt, r02_linkage_stamps.txt, r03_linkage_*.txt): up to N = 30 000
     // the one-XCD form with one workgroup on each of the XCD's 32 CUs; above, all XCDs
     // (r03, square form: one XCD wins up to N ~ 70 000 -- 384 ms against 443 at N = 50 158, 719 against 715 at N = 75 090 -- all XCDs above: 987 ms against 1 064 at
     // N = 100 174; all XCDs: 64 workgroups up to ~90 000 rows, 128 above)
-    const bool auto_onex = G < 0 && c->linkage_one_xcd != 0 && c->num_cu >= 256 && N >= 1500 && N < 70000;
-    if (auto_onex) G = 32;
-    if (G < 0) G = N >= 90000 ? 128 : N >= 8000 ? 64 : N >= 1500 ? 32 : 0;
-    if (G > c->num_cu) G = c->num_cu;
+    const bool auto_onex = (int)c->linkage_wgs < 0 && c->linkage_one_xcd != 0 && c->num_cu >= 256 && N >= 1500 && N < 70000;
+    int G = linkage_route_wgs(c->linkage_wgs, c->linkage_one_xcd, c->num_cu, N);      // linkage_batch_plan.h: the rule run_linkage_many's planner shares
     int TH = (int)c->linkage_threads;
     // measured (r03, square form, N = 12 602, one XCD, three boxes): 32 x 256 75.2 / 82.7 / 76.8 ms, 32 x 512 84.4 / 77.2 / 85.0 ms -- the
     // boxes disagree, 256 wins on two of three; all XCDs 128 x 512 0.99 s at N = 100 174 (128 x 256: 1.10 s)

@@ -1,10 +1,11 @@
 // linkage_dev.h -- device helpers shared by the linkage kernels (k_linkage_rg, k_linkage_mw, k_linkage_hx, k_linkage_heap: one file each, linkage_<name>.hip)
-// and the preparation kernels (linkage.hip), the words of the `sync` block they and the host talk through, and the launchers run_linkage (linkage.hip) drives.
+// and their batch forms (linkage_batch.hip), the preparation kernels (linkage.hip), the words of the `sync` block they and the host talk through, and the launchers run_linkage (linkage.hip) drives.
 // Translation units that include this file are compiled with -ffp-contract=off (Makefile EXACT; exact_fp.h refuses any other build): fp64 results
 // bit-identical to the reference's x86 build.
 #pragma once
 #include "common.h"
 #include "exact_fp.h"
+#include "linkage_batch_plan.h"
 #include <cfloat>
 #include <cmath>
 #include <type_traits>
@@ -137,6 +138,66 @@ template <class F> inline bool lw_dispatch(int method, F&& f)
     }
     return false;
 }
+
+// ---------------------------------------------------------------- shared by the one-workgroup heap kernels (k_linkage_heap, k_linkage_heap_jobs)
+// nearest active neighbour above row x, scanned by `nthreads` threads with U loads in flight per thread
+// (a plain strided loop keeps one load outstanding and is latency bound: ~1 us per element per thread)
+template <int U>
+__device__ __forceinline__ MinIdx scan_row_nn(const double* __restrict__ D, const int* __restrict__ size, int64_t N, int n, int x,
+                                              int first, int stride)
+{
+    MinIdx q; q.v = INFINITY; q.i = -1;
+    const double* row = D + cidx(N, x, (int64_t)x + 1) - (x + 1);       // row[j] = D[x, j]
+    for (int j0 = x + 1 + first; j0 < n; j0 += stride * U) {
+        double v[U]; int sz[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * stride;
+            const int jc = j < n ? j : n - 1;
+            v[u] = row[jc]; sz[u] = size[jc];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * stride;
+            if (j < n && sz[u] != 0 && v[u] < q.v) { q.v = v[u]; q.i = j; }
+        }
+    }
+    return q;
+}
+
+
+// the reference's indexed binary min-heap (cl.cpp:28-119), operation for operation; one thread runs them
+struct HeapRef { double* val; int* key; int* pos; int size; };
+__device__ __forceinline__ void hp_swap(HeapRef& h, int a, int b)                          // cl.cpp:70-78
+{
+    const double va = h.val[a], vb = h.val[b];
+    h.val[a] = vb; h.val[b] = va;
+    const int ka = h.key[a], kb = h.key[b];
+    h.key[a] = kb; h.key[b] = ka;
+    h.pos[ka] = b; h.pos[kb] = a;
+}
+__device__ __forceinline__ void hp_down(HeapRef& h, int idx)                                // cl.cpp:53-68
+{
+    int ch = 2 * idx + 1;
+    while (ch < h.size) {
+        if (ch + 1 < h.size && h.val[ch + 1] < h.val[ch]) ch += 1;
+        if (h.val[idx] > h.val[ch]) { hp_swap(h, idx, ch); idx = ch; ch = 2 * idx + 1; }
+        else break;
+    }
+}
+__device__ __forceinline__ void hp_up(HeapRef& h, int idx)                                  // cl.cpp:44-51
+{
+    int par = (idx - 1) >> 1;
+    while (idx > 0 && h.val[par] > h.val[idx]) { hp_swap(h, idx, par); idx = par; par = (idx - 1) >> 1; }
+}
+__device__ __forceinline__ void hp_change(HeapRef& h, int key, double v)                    // cl.cpp:108-117
+{
+    const int idx = h.pos[key];
+    const double old = h.val[idx];
+    h.val[idx] = v;
+    if (v < old) hp_up(h, idx); else hp_down(h, idx);
+}
+
 
 // A slot is a set of 8-byte granules {32-bit payload word, 32-bit round tag}: a reader that sees the tag of the round it waits for has the
 // payload of that round (8-byte stores are single transactions), so publishing needs no separate "ready" flag and no counter.

@@ -4,31 +4,7 @@
 #include "exact_fp.h"
 #include "linkage_dev.h"
 
-// nearest active neighbour above row x, scanned by `nthreads` threads with U loads in flight per thread
-// (a plain strided loop keeps one load outstanding and is latency bound: ~1 us per element per thread)
-template <int U>
-__device__ __forceinline__ MinIdx scan_row_nn(const double* __restrict__ D, const int* __restrict__ size, int64_t N, int n, int x,
-                                              int first, int stride)
-{
-    MinIdx q; q.v = INFINITY; q.i = -1;
-    const double* row = D + cidx(N, x, (int64_t)x + 1) - (x + 1);       // row[j] = D[x, j]
-    for (int j0 = x + 1 + first; j0 < n; j0 += stride * U) {
-        double v[U]; int sz[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = j0 + u * stride;
-            const int jc = j < n ? j : n - 1;
-            v[u] = row[jc]; sz[u] = size[jc];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = j0 + u * stride;
-            if (j < n && sz[u] != 0 && v[u] < q.v) { q.v = v[u]; q.i = j; }
-        }
-    }
-    return q;
-}
-
+// (scan_row_nn, the nearest-neighbour scan of a row, and the heap operations hp_* are linkage_dev.h's: k_linkage_heap_jobs shares them)
 #define LT 1024
 __device__ __forceinline__ MinIdx block_min(MinIdx m, MinIdx* sh)
 {
@@ -55,37 +31,7 @@ __device__ __forceinline__ MinIdx block_min(MinIdx m, MinIdx* sh)
 // The rows whose bound dropped are collected in an LDS bitmap and drained in ascending order by wave 0.
 // (no __restrict__: every array here is written by one thread and re-read by others across barriers)
 #define HEAP_LDS 2048
-struct HeapRef { double* val; int* key; int* pos; int size; };
-__device__ __forceinline__ void hp_swap(HeapRef& h, int a, int b)                          // cl.cpp:70-78
-{
-    const double va = h.val[a], vb = h.val[b];
-    h.val[a] = vb; h.val[b] = va;
-    const int ka = h.key[a], kb = h.key[b];
-    h.key[a] = kb; h.key[b] = ka;
-    h.pos[ka] = b; h.pos[kb] = a;
-}
-__device__ __forceinline__ void hp_down(HeapRef& h, int idx)                                // cl.cpp:53-68
-{
-    int ch = 2 * idx + 1;
-    while (ch < h.size) {
-        if (ch + 1 < h.size && h.val[ch + 1] < h.val[ch]) ch += 1;
-        if (h.val[idx] > h.val[ch]) { hp_swap(h, idx, ch); idx = ch; ch = 2 * idx + 1; }
-        else break;
-    }
-}
-__device__ __forceinline__ void hp_up(HeapRef& h, int idx)                                  // cl.cpp:44-51
-{
-    int par = (idx - 1) >> 1;
-    while (idx > 0 && h.val[par] > h.val[idx]) { hp_swap(h, idx, par); idx = par; par = (idx - 1) >> 1; }
-}
-__device__ __forceinline__ void hp_change(HeapRef& h, int key, double v)                    // cl.cpp:108-117
-{
-    const int idx = h.pos[key];
-    const double old = h.val[idx];
-    h.val[idx] = v;
-    if (v < old) hp_up(h, idx); else hp_down(h, idx);
-}
-
+static_assert(HEAP_LDS == LINKAGE_HEAP_LDS, "linkage_batch_plan.h batches the jobs whose heap fits this kernel's LDS heap");
 template <int METHOD>
 __global__ __launch_bounds__(LT) void k_linkage_heap(double* D, int n, int* size, int* cid, int* nb, double* md, double* Z,
                                                       double* g_hval, int* g_hkey, int* g_hpos)

@@ -12,6 +12,7 @@
 // stream with nothing sealed.  Which side of PyanNet's skinny limit a chunk is on is seg_tile_chunks' word (many_plan.h), here and in stream.hip.
 #include "common.h"
 #include "stream_book.h"
+#include "linkage_batch_plan.h"
 #include <algorithm>
 #include <utility>
 
@@ -148,6 +149,63 @@ int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vec
     return SD_OK;
 }
 
+// ------------------------------------------------------------------ the dendrograms of a group call, ahead of the per-job finalize
+// The per-job finalize spends most of its time in a one-workgroup linkage (N < 1500 train rows) while the rest of the device waits; the jobs of one call are
+// independent.  This pass forms, for every job, the rows cluster_rows would hand to the linkage -- with the kernels the finalize uses: k_f32_to_f64,
+// train_rows (the "max_num_embeddings" sample included), k_gather_normalize -- and runs all dendrograms in shared launches (run_linkage_many).  Z[j] /
+// ZN[j] (the train rows it belongs to; -1 = none) wait on the host for cluster_rows, which takes a Z only where it finds the same row count itself.
+// Jobs that skip the pass and run their linkage where they always did: under an enrolled gallery (the linkage is over the unclaimed rows), a trivial
+// number-of-clusters rule, fewer than two train rows, a job run_linkage would not give to its one-workgroup kernel (nothing to gain, and its Z would be held
+// for longer).  A job whose dendrogram fails with SD_ERR_NUMERIC keeps no Z: its finalize runs the linkage itself and reports what the sequential path reports.
+static int dendrograms_ahead(sd_ctx* c, const std::vector<FinalJob>& jobs, std::vector<std::vector<double>>& Z, std::vector<int64_t>& ZN)
+{
+    const size_t J = jobs.size();
+    Z.assign(J, std::vector<double>()); ZN.assign(J, -1);
+    if (c->linkage_batch == 0 || c->enr_M > 0 || J < 2) return SD_OK;
+    const double t0 = now_ms();
+    const int d = SD_EMB_DIM;
+    int64_t maxM = 0, pool = 0, live = 0;
+    for (const FinalJob& q : jobs) {
+        if (q.chunks <= 0) continue;
+        const int64_t M = q.chunks * SD_SPEAKERS;
+        maxM = std::max(maxM, M); pool += std::min<int64_t>(M, LINKAGE_HEAP_LDS + 1); live += 1;
+    }
+    if (live < 2) return SD_OK;
+    WS(c, double, d_e64, "lb_e64", maxM * d);
+    WS(c, double, d_X, "lb_X", pool * d);
+    const ClusterSpec spec = {c->clustering_threshold, c->min_cluster_size, c->num_clusters, c->min_clusters, c->max_clusters};
+    const LinkageRoute route = {c->linkage_wgs, c->linkage_one_xcd, c->num_cu};
+    std::vector<std::vector<int>> tidx(J);
+    std::vector<LinkageManyJob> lj;
+    std::vector<size_t> owner;
+    int64_t off = 0;
+    int rc;
+    for (size_t j = 0; j < J; ++j) {
+        const FinalJob& q = jobs[j];
+        if (q.chunks <= 0) continue;
+        const int64_t M = q.chunks * SD_SPEAKERS;
+        hipLaunchKernelGGL(k_f32_to_f64, GRID1(M * d), 0, c->stream, q.emb, d_e64, M * d);
+        KCHECK(c);
+        if ((rc = train_rows(c, d_e64, M, d, tidx[j]))) return rc;
+        const int64_t N = (int64_t)tidx[j].size();
+        if (!linkage_job_batched(route, N) || resolve_num_clusters(spec, N).trivial) continue;
+        if ((rc = linkage_rows(c, d_e64, tidx[j], d, d_X + (size_t)off * d))) return rc;
+        Z[j].resize((size_t)(N - 1) * 4);
+        lj.push_back(LinkageManyJob{d_X + (size_t)off * d, N, Z[j].data()});
+        owner.push_back(j);
+        off += N;
+    }
+    if (lj.size() >= 2) {
+        const int method = c->clustering_method;
+        const bool euclid = method == SD_LINKAGE_CENTROID || method == SD_LINKAGE_MEDIAN || method == SD_LINKAGE_WARD;
+        std::vector<int32_t> st(lj.size(), SD_OK);
+        if ((rc = run_linkage_many(c, lj.data(), (int64_t)lj.size(), d, method, euclid ? SD_METRIC_EUCLIDEAN : SD_METRIC_COSINE, st.data()))) return rc;
+        for (size_t k = 0; k < lj.size(); ++k) if (st[k] == SD_OK) ZN[owner[k]] = lj[k].N;
+    } else HIPCHK(c, hipStreamSynchronize(c->stream));      // one job alone gains nothing: its finalize runs the linkage (tidx of the last gather must outlive its upload)
+    c->stage_ms[2] += now_ms() - t0;
+    return SD_OK;
+}
+
 // ------------------------------------------------------------------ finalize per output (common.h)
 int finalize_jobs(sd_ctx* c, int64_t J, sd_turn** turns, int64_t* n_turns, int32_t* status, const std::function<int(std::vector<FinalJob>&)>& infer,
                   const std::function<int(int64_t, sd_turn*, int64_t)>& named)
@@ -157,12 +215,17 @@ int finalize_jobs(sd_ctx* c, int64_t J, sd_turn** turns, int64_t* n_turns, int32
     std::vector<FinalJob> jobs((size_t)J, FinalJob{nullptr, nullptr, 0, 0});
     int rc;
     if ((rc = infer(jobs))) return rc;
+    std::vector<std::vector<double>> Zs;
+    std::vector<int64_t> ZN;
+    if ((rc = dendrograms_ahead(c, jobs, Zs, ZN))) return rc;
     // one job after the other; what finalize leaves in the context is kept per job (sd_many_select)
     for (int64_t j = 0; j < J; ++j) {
         const FinalJob& q = jobs[(size_t)j];
         if (q.chunks <= 0) continue;
         std::vector<sd_turn> v;
+        c->ahead_N = ZN[(size_t)j]; c->ahead_Z.swap(Zs[(size_t)j]);      // cluster_rows takes it where it finds the same train rows
         rc = finalize(c, q.seg, q.emb, q.chunks, q.n, v);
+        c->ahead_N = -1; c->ahead_Z.clear();
         ManyJob& job = c->many_jobs[(size_t)j];
         status[j] = job.status = rc;
         if (rc == SD_ERR_NUMERIC) continue;                    // this job's clustering; the others go on

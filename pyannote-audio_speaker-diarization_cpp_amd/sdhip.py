@@ -79,6 +79,7 @@ EXPORTS = [
     "sd_sample_rows",
     "sd_roster_open", "sd_roster_close", "sd_roster_load", "sd_roster_info", "sd_roster_speakers", "sd_roster_update", "sd_roster_update_last",
     "sd_relabel_turns_map", "sd_stream_set_roster", "sd_last_roster_ids",
+    "sd_linkage_many",
 ]
 # SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
 LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
@@ -128,6 +129,7 @@ def lib():
     L.sd_cluster.argtypes = [vp, vp, i64, C.c_int, dbl, vp]
     L.sd_linkage_ex.argtypes = [vp, vp, i64, C.c_int, C.c_int, C.c_int, vp]
     L.sd_cluster_ex.argtypes = [vp, vp, i64, C.c_int, C.c_int, C.c_int, dbl, vp]
+    L.sd_linkage_many.argtypes = [vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, vp, vp]
     L.sd_set_option_f64.argtypes = [vp, C.c_char_p, dbl]
     L.sd_linkage_method_from_name.argtypes = [C.c_char_p]
     L.sd_clustering.argtypes = [vp, vp, i64, C.c_int, vp, C.POINTER(i32)]
@@ -923,6 +925,22 @@ class Diarizer:
         Z = np.zeros((max(N - 1, 0), 4), np.float64)
         self._chk(lib().sd_linkage_ex(self._h, _ptr(X), N, d, _method_code(method), int(metric), _ptr(Z)))
         return Z
+
+    def linkage_many(self, Xs, method, metric=METRIC_EUCLIDEAN):
+        """sd_linkage_many: Xs = a list of [N_j][d] arrays (N_j >= 0, one d) -> (list of Z [max(N_j - 1, 0)][4], status [J] int32).  The Z of a job whose
+        status is not 0 (a zero-norm row under the cosine metric) is all NaN"""
+        Xs = [np.ascontiguousarray(X, np.float64).reshape(len(X), -1) for X in Xs]
+        d = max([X.shape[1] for X in Xs if X.shape[0]] or [1])
+        if any(X.shape[0] and X.shape[1] != d for X in Xs):
+            raise ValueError("linkage_many: every job needs rows of the same length")
+        N = np.array([X.shape[0] for X in Xs], np.int64)
+        allX = np.ascontiguousarray(np.concatenate([X.reshape(-1, d) for X in Xs]) if len(Xs) else np.zeros((0, d)))
+        nz = np.maximum(N - 1, 0)
+        Z = np.full((int(nz.sum()) + 1, 4), np.nan)
+        status = np.zeros(len(Xs), np.int32)
+        self._chk(lib().sd_linkage_many(self._h, _ptr(allX), _ptr(N), len(Xs), d, _method_code(method), int(metric), _ptr(Z), _ptr(status)))
+        off = np.concatenate([[0], np.cumsum(nz)])
+        return [Z[off[j]:off[j + 1]].copy() for j in range(len(Xs))], status
 
     def cluster_ex(self, X, method, metric, cutoff):
         X = np.ascontiguousarray(X, np.float64)
