@@ -149,6 +149,34 @@ int sd_test_rowtab(sd_ctx*, const int32_t* off_out, const int32_t* off_in, int64
 int sd_test_scatter_emb(sd_ctx*, const float* emb_c, int64_t n_c, const int32_t* cidx, int64_t items, float canary, float* emb_out);
 int sd_test_to_half(sd_ctx*, int kind, const float* f, int64_t rows, int width, float canary, uint16_t* h_out);
 
+/* ---- test hooks (tests/test_frontend_kernels.py): the kernels of the embedding front end (csrc/frontend.hip) through the functions run_embed, sd_frontend
+ * and sd_embed_signals call, under the contract of the hooks above: host pointers; every input followed by 256 guard units of NaN; every output preset to a
+ * canary, 256 slack entries (rows) behind it, back WHOLE; a case whose defined reads leave its operands is SD_ERR_ARG before any launch.  The window, the
+ * twiddles and the sparse mel bank are the context's (weights.cpp): a case that needs others loads another pack.
+ *
+ * sd_test_frontend_prepare: frontend_prepare as run_embed (compact = 1) or sd_frontend (compact = 0) calls it: k_mask_prefix, k_wav_lens and, under
+ * compact, k_compact_active.  masks [items][293] (followed by 256 x 293 NaN), first_item a multiple of 32.  Out, each with 256 slack entries and preset to
+ * icanary (the float array: fcanary): prefix [items * 296 + 256] (columns 294 / 295 of a row are never written), counts, wav_lens, nnorm, nvalid, flags
+ * [items + 256] per ITEM; under compact also alist, cidx, nnorm_c, nvalid_c [items + 256] and n_active [4] (entry 0 written); with compact = 0 those five
+ * may be NULL and are not touched.
+ * sd_test_frontend_features: the first half of run_embed in its order: frontend_prepare(compact), ecapa_row_plan, frontend_features (k_stft_fbank),
+ * with option skip_dead_rows as given for this call.  wav [n_held] is the slice of a recording of n_total samples that starts at sample `origin`; it is
+ * uploaded with 256 NaN in front of it and 256 NaN behind it.  Refused: a live item whose chunk ((first_item + item) / 3) * 8000 starts before origin, or
+ * a slice that ends before min(n_total, end of the last live item's chunk).  feats_out [feat_rows][96], feat_rows = rows of all live items + 256 exactly
+ * (else SD_ERR_ARG: the caller knows the row plan it expects), preset to canary; rowoff_out [items + 1] (entries 0 .. n_active written), cidx_out [items];
+ * info_out [4] = n_active, rows_all, the grid frontend_features gave the k_stft_fbank launch (it records it in the context), compute units.
+ * sd_test_frontend_signals: the path of sd_embed_signals up to and including frontend_features (sig_mode): signals [B][80000] (256 NaN in front, 256 NaN
+ * behind), wav_lens [B] under sd_embed_signals' own rule.  prefix_out [B * 296 + 256] and counts_out [B + 256]: the tables of k_identity_prefix, preset to
+ * icanary.  The other outputs as above (cidx is the identity and is not returned). */
+int sd_test_frontend_prepare(sd_ctx*, const float* masks, int64_t items, int64_t first_item, int compact, int32_t icanary, float fcanary, int32_t* prefix,
+                             int32_t* counts, float* wav_lens, int32_t* nnorm, int32_t* nvalid, int32_t* flags, int32_t* alist, int32_t* cidx,
+                             int32_t* nnorm_c, int32_t* nvalid_c, int32_t* n_active);
+int sd_test_frontend_features(sd_ctx*, const float* wav, int64_t n_held, int64_t n_total, int64_t origin, int64_t first_item, const float* masks,
+                              int64_t items, int skip_dead_rows, float canary, float* feats_out, int64_t feat_rows, int32_t* rowoff_out,
+                              int32_t* cidx_out, int64_t* info_out);
+int sd_test_frontend_signals(sd_ctx*, const float* signals, const float* wav_lens, int64_t B, int skip_dead_rows, int32_t icanary, float canary,
+                             int32_t* prefix_out, int32_t* counts_out, float* feats_out, int64_t feat_rows, int32_t* rowoff_out, int64_t* info_out);
+
 #ifdef __cplusplus
 }
 #endif

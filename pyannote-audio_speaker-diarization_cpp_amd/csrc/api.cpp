@@ -283,15 +283,11 @@ extern "C" int sd_ecapa(sd_ctx* c, const float* h_feats, const float* h_lens, in
     return SD_OK;
 }
 
-// EmbeddingModel1::infer as the reference declares it (sd.cpp:1977-2040, calling _infer sd.cpp:1889-1970): B already compacted, zero-padded
-// signals of 80000 samples and their relative lengths -> [B][192].  No NaN rule here (getEmbedding applies it to the result, sd.cpp:2479-2549);
-// the STFT / fbank run over all 501 frames of every row as the reference's do, the network over the frames wav_lens leaves valid + its reach.
-extern "C" int sd_embed_signals(sd_ctx* c, const float* h_signals, const float* h_wav_lens, int64_t B, float* h_emb)
+// the frames wav_lens leaves an item of sd_embed_signals: nv = frames the network reads, nn = frames the mean runs over; refuses a length outside (0, 1]
+// or one that rounds to no frame at all
+int embed_signals_frames(sd_ctx* c, const float* h_wav_lens, int64_t B, std::vector<int>& nv, std::vector<int>& nn)
 {
-    ENTER(c);
-    if (!h_signals || !h_wav_lens || !h_emb || B <= 0) SD_FAIL(c, SD_ERR_ARG, "sd_embed_signals: bad argument");
-    if (!c->ew.loaded) SD_FAIL(c, SD_ERR_MODEL, "embedding model not loaded");
-    std::vector<int> nv((size_t)B), nn((size_t)B);
+    nv.assign((size_t)B, 0); nn.assign((size_t)B, 0);
     for (int64_t i = 0; i < B; ++i) {
         if (!(h_wav_lens[i] > 0.0f) || h_wav_lens[i] > 1.0f) SD_FAIL(c, SD_ERR_ARG, "sd_embed_signals: wav_lens[%lld] = %g (relative length in (0, 1])", (long long)i, (double)h_wav_lens[i]);
         const float lt = h_wav_lens[i] * (float)SD_T;                       // float32 product as in torch (k_wav_lens)
@@ -300,6 +296,19 @@ extern "C" int sd_embed_signals(sd_ctx* c, const float* h_signals, const float* 
         nv[(size_t)i] = v;
         if (nn[(size_t)i] < 1) SD_FAIL(c, SD_ERR_ARG, "sd_embed_signals: wav_lens[%lld] = %g leaves no frame to normalise over", (long long)i, (double)h_wav_lens[i]);
     }
+    return SD_OK;
+}
+
+// EmbeddingModel1::infer as the reference declares it (sd.cpp:1977-2040, calling _infer sd.cpp:1889-1970): B already compacted, zero-padded
+// signals of 80000 samples and their relative lengths -> [B][192].  No NaN rule here (getEmbedding applies it to the result, sd.cpp:2479-2549);
+// the STFT / fbank run over all 501 frames of every row as the reference's do, the network over the frames wav_lens leaves valid + its reach.
+extern "C" int sd_embed_signals(sd_ctx* c, const float* h_signals, const float* h_wav_lens, int64_t B, float* h_emb)
+{
+    ENTER(c);
+    if (!h_signals || !h_wav_lens || !h_emb || B <= 0) SD_FAIL(c, SD_ERR_ARG, "sd_embed_signals: bad argument");
+    if (!c->ew.loaded) SD_FAIL(c, SD_ERR_MODEL, "embedding model not loaded");
+    std::vector<int> nv, nn;
+    if (const int rc = embed_signals_frames(c, h_wav_lens, B, nv, nn)) return rc;
     const int64_t ns = B * (int64_t)SD_CHUNK;
     // persistent workspaces, not per-call allocations: the reference calls infer once per batch of 32 items (677 times per hour of audio)
     WS(c, float, dw, "sig_wav", ns + SD_WAV_PAD); WS(c, int, dv, "sig_nvalid", B); WS(c, int, dn, "sig_nnorm", B);

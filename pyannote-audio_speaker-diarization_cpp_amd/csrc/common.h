@@ -250,6 +250,7 @@ struct sd_ctx {
     int dump_level = 0;
     StepStash stash;
     std::string ws_failed;                      // ws_get: name of the workspace whose allocation failed last ("" = none); the embedding stage's retry reads it
+    int fe_last_grid = 0;                       // test hook (sd_test_frontend_*): workgroups of the last k_stft_fbank launch; set by frontend_features, host code only
     const char* last_conv_kernel = nullptr;     // test hook (sd_test_conv): which kernel the conv dispatch launched last; set by every launch site, host code only
     const float* planted_scores = nullptr;      // sd_set_planted: measurement / test hook
     const float* planted_emb = nullptr;
@@ -370,7 +371,8 @@ int frontend_prepare(sd_ctx* c, const float* d_masks, int64_t items, int64_t fir
                      int* d_flags, bool compact, int* h_n_active, int* d_cidx, std::vector<int>* h_nvalid = nullptr);
 int frontend_features(sd_ctx* c, const DevWav& w, int64_t first_item, int64_t run_items, bool compact, const int* d_nnorm,
                       const int* d_rowoff, float* d_feats /*[rowoff[run_items]][96]*/, bool sig_mode = false);
-int frontend_prepare_signals(sd_ctx* c, int64_t items);       // sd_embed_signals: identity gather tables for [items][80000] signal rows
+int embed_signals_frames(sd_ctx* c, const float* h_wav_lens, int64_t B, std::vector<int>& nv, std::vector<int>& nn);      // api.cpp: sd_embed_signals' nvalid / nnorm from wav_lens
+int frontend_prepare_signals(sd_ctx* c, int64_t items);     // sd_embed_signals: identity gather tables for [items][80000] signal rows
 // ---- ecapa.hip
 // Compact row spaces of the embedding network: space s stores the frames t < min(501, nvalid + EC_MARGIN[s]) of every item.
 // A layer is only computed where a later valid frame can see it (ecapa.hip): block0 / block 1 run in space 0, block 2 in space 1,

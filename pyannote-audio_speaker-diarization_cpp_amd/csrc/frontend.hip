@@ -336,6 +336,7 @@ int frontend_features(sd_ctx* c, const DevWav& w, int64_t first_item, int64_t ru
     int grid = 2 * c->num_cu;
     if (grid > run_items) grid = (int)run_items;
     WS(c, float, d_scratch, "fe_db", (size_t)grid * SD_T * SD_NMELS);
+    c->fe_last_grid = grid;
     {
         // algorithmic bytes (SURVEY 8d's per-item rule on what this launch really touches): the selected samples of every live item
         // + its 293 mask values read, its stored frames x 96 floats written; ~15 kFLOP fp64 per frame (FFT) + 32 kFLOP mel.  Callers

@@ -41,6 +41,7 @@ CONV_SLACK_ROWS = 256      # guard rows behind the buffers of Diarizer.conv_case
 SEG_SLACK_ROWS = 256       # ... and behind those of Diarizer.lstm_rec_case / pool_norm_case / chunk_norm_case / classifier_case
 GLUE_SLACK_ROWS = 256      # ... and behind those of Diarizer.ecapa_stats_case / se_apply_case / scatter_emb_case / to_half_case
 ROWTAB_SLACK = 128         # slack entries behind the table of Diarizer.rowtab_case
+FE_SLACK = 256             # slack entries (feature rows) behind every array of Diarizer.frontend_prepare_case / frontend_features_case / frontend_signals_case
 
 
 class SdError(RuntimeError):
@@ -65,6 +66,7 @@ EXPORTS = [
     "sd_linkage_ex", "sd_cluster_ex", "sd_set_option_f64", "sd_linkage_method_from_name", "sd_test_conv", "sd_test_emb_batches",
     "sd_test_lstm_rec", "sd_test_pool_norm", "sd_test_chunk_norm", "sd_test_classifier",
     "sd_test_ecapa_stats", "sd_test_se_apply", "sd_test_rowtab", "sd_test_scatter_emb", "sd_test_to_half",
+    "sd_test_frontend_prepare", "sd_test_frontend_features", "sd_test_frontend_signals",
     "sd_activity_scores", "sd_activity_regions", "sd_activity", "sd_activity_dev", "sd_activity_f32", "sd_activity_wav", "sd_last_activity_scores",
     "sd_stream_open", "sd_stream_push", "sd_stream_push_dev", "sd_stream_push_f32", "sd_stream_turns", "sd_stream_info", "sd_stream_read",
     "sd_stream_close", "sd_stream_sealed_chunks", "sd_stream_forget", "sd_stream_set_window", "sd_stream_origin",
@@ -257,6 +259,9 @@ def lib():
     L.sd_test_rowtab.argtypes = [vp, vp, vp, i64, i32, vp]
     L.sd_test_scatter_emb.argtypes = [vp, vp, i64, vp, i64, C.c_float, vp]
     L.sd_test_to_half.argtypes = [vp, C.c_int, vp, i64, C.c_int, C.c_float, vp]
+    L.sd_test_frontend_prepare.argtypes = [vp, vp, i64, i64, C.c_int, i32, C.c_float] + [vp] * 11
+    L.sd_test_frontend_features.argtypes = [vp, vp, i64, i64, i64, i64, vp, i64, C.c_int, C.c_float, vp, i64, vp, vp, vp]
+    L.sd_test_frontend_signals.argtypes = [vp, vp, vp, i64, C.c_int, i32, C.c_float, vp, vp, vp, i64, vp, vp]
     L.sd_test_emb_batches.restype = i64
     L.sd_test_emb_batches.argtypes = [vp, i64, i64, C.c_int, C.c_int, vp, i64]
     _lib = L
@@ -1530,6 +1535,52 @@ class Diarizer:
         out = np.zeros((rows + GLUE_SLACK_ROWS, 128 if feats else w), np.uint16)
         self._chk(lib().sd_test_to_half(self._h, 0 if feats else 1, _ptr(f), rows, w, canary, _ptr(out)))
         return out.view(np.float16)
+
+    # ---- the kernels of the embedding front end alone (sdhip_test.h); every array comes back WHOLE, its FE_SLACK entries (rows) included
+    def frontend_prepare_case(self, masks, first_item=0, compact=True, icanary=-7776, fcanary=-7776.0):
+        """sd_test_frontend_prepare: masks [items][293] -> dict of prefix [items * 296 + FE_SLACK], counts / wav_lens / nnorm / nvalid / flags
+        [items + FE_SLACK] per item and, under compact, alist / cidx / nnorm_c / nvalid_c [items + FE_SLACK] and n_active [4]"""
+        masks = np.ascontiguousarray(masks, np.float32)
+        items = masks.shape[0]
+        assert masks.shape == (items, 293)
+        n = items + FE_SLACK
+        out = {"prefix": np.zeros(items * 296 + FE_SLACK, np.int32), "wav_lens": np.zeros(n, np.float32)}
+        names = ["counts", "nnorm", "nvalid", "flags"] + (["alist", "cidx", "nnorm_c", "nvalid_c"] if compact else [])
+        for k in names:
+            out[k] = np.zeros(n, np.int32)
+        if compact:
+            out["n_active"] = np.zeros(4, np.int32)
+        p = lambda k: _ptr(out[k]) if k in out else None
+        self._chk(lib().sd_test_frontend_prepare(self._h, _ptr(masks), items, int(first_item), int(bool(compact)), int(icanary), float(fcanary), p("prefix"),
+                                                 p("counts"), p("wav_lens"), p("nnorm"), p("nvalid"), p("flags"), p("alist"), p("cidx"), p("nnorm_c"),
+                                                 p("nvalid_c"), p("n_active")))
+        return out
+
+    def frontend_features_case(self, wav, n_total, origin, first_item, masks, rows_all, skip_dead_rows=True, canary=-7776.0):
+        """sd_test_frontend_features: wav = samples [origin, origin + len(wav)) of a recording of n_total samples, masks [items][293], rows_all = the rows
+        the caller expects the live items to store -> feats [rows_all + FE_SLACK][96], rowoff [items + 1] (n_active + 1 written), cidx [items],
+        info dict (n_active, rows_all, grid, num_cu)"""
+        wav, masks = np.ascontiguousarray(wav, np.float32), np.ascontiguousarray(masks, np.float32)
+        items = masks.shape[0]
+        assert wav.ndim == 1 and masks.shape == (items, 293)
+        feats = np.zeros((int(rows_all) + FE_SLACK, 96), np.float32)
+        rowoff, cidx, info = np.full(items + 1, -1, np.int32), np.zeros(items, np.int32), np.zeros(4, np.int64)
+        self._chk(lib().sd_test_frontend_features(self._h, _ptr(wav), len(wav), int(n_total), int(origin), int(first_item), _ptr(masks), items,
+                                                  int(bool(skip_dead_rows)), canary, _ptr(feats), feats.shape[0], _ptr(rowoff), _ptr(cidx), _ptr(info)))
+        return feats, rowoff, cidx, dict(zip(("n_active", "rows_all", "grid", "num_cu"), (int(v) for v in info)))
+
+    def frontend_signals_case(self, signals, wav_lens, rows_all, skip_dead_rows=True, icanary=-7776, canary=-7776.0):
+        """sd_test_frontend_signals: signals [B][80000], wav_lens [B] -> feats [rows_all + FE_SLACK][96], rowoff [B + 1], info dict, and the tables of
+        k_identity_prefix: prefix [B * 296 + FE_SLACK], counts [B + FE_SLACK]"""
+        signals, wav_lens = np.ascontiguousarray(signals, np.float32), np.ascontiguousarray(wav_lens, np.float32)
+        B = signals.shape[0]
+        assert signals.shape == (B, 80000) and wav_lens.shape == (B,)
+        feats = np.zeros((int(rows_all) + FE_SLACK, 96), np.float32)
+        rowoff, info = np.full(B + 1, -1, np.int32), np.zeros(4, np.int64)
+        prefix, counts = np.zeros(B * 296 + FE_SLACK, np.int32), np.zeros(B + FE_SLACK, np.int32)
+        self._chk(lib().sd_test_frontend_signals(self._h, _ptr(signals), _ptr(wav_lens), B, int(bool(skip_dead_rows)), int(icanary), canary, _ptr(prefix),
+                                                 _ptr(counts), _ptr(feats), feats.shape[0], _ptr(rowoff), _ptr(info)))
+        return feats, rowoff, dict(zip(("n_active", "rows_all", "grid", "num_cu"), (int(v) for v in info))), prefix, counts
 
     def read_ws(self, name, dtype, count, offset=0):
         """test hook: `count` elements of the named device workspace"""
