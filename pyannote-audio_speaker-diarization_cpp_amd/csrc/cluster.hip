@@ -9,6 +9,7 @@
 // of a cut (number-of-clusters rules, re-cut, size split) are cluster_host.h; cluster_cut below is the one finish of a cut, for run_clustering and cut.hip.
 #include "common.h"
 #include "exact_fp.h"
+#include "cosine_rule.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -68,7 +69,7 @@ __global__ void k_cluster_means(const double* __restrict__ X, int d, const int* 
     cen[(size_t)k * d + q] = s / (double)(b - a);
 }
 
-// cosine distance with the reference's sequential sums (sd.cpp:476-498); soft = 2 - d; argmax first-max-wins
+// cosine distance with the reference's sequential sums (sd.cpp:476-498; cosine_rule.h); soft = 2 - d; argmax first-max-wins
 #define ASSIGN_TILE 1024
 __global__ __launch_bounds__(64) void k_assign(const double* __restrict__ E, int64_t M, int d, const double* __restrict__ cen, int K,
                                                int* __restrict__ hard, int* __restrict__ err, double* __restrict__ soft_out /*[M][K] or null*/,
@@ -86,8 +87,9 @@ __global__ __launch_bounds__(64) void k_assign(const double* __restrict__ E, int
             const double* cc = cen + (size_t)(k0 + k) * d;
             double dot = 0.0, m1 = 0.0, m2 = 0.0;
             for (int i = 0; i < d; ++i) { dot += e[i] * cc[i]; m1 += e[i] * e[i]; m2 += cc[i] * cc[i]; }
-            if (m1 == 0.0 || m2 == 0.0) { *err = 1; soft[k] = NAN; }
-            else soft[k] = 2.0 - (1.0 - (dot / (sqrt(m1) * sqrt(m2))));
+            bool zero = false;
+            soft[k] = 2.0 - cosine_distance(dot, m1, m2, &zero);
+            if (zero) *err = 1;
             if (soft_out) soft_out[(size_t)row * K + k0 + k] = soft[k];
         }
         __syncthreads();
@@ -182,8 +184,7 @@ static double cos_dist_host(const double* a, const double* b, int d, bool* err) 
 {
     double dot = 0.0, m1 = 0.0, m2 = 0.0;
     for (int i = 0; i < d; ++i) { dot += a[i] * b[i]; m1 += a[i] * a[i]; m2 += b[i] * b[i]; }
-    if (m1 == 0.0 || m2 == 0.0) { *err = true; return NAN; }
-    return 1.0 - (dot / (sqrt(m1) * sqrt(m2)));
+    return cosine_distance(dot, m1, m2, err);
 }
 
 // ---------------------------------------------------------------- the steps of run_clustering: the plain flow and the enrolled flow call the same ones
@@ -201,11 +202,11 @@ int cluster_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, in
     hipLaunchKernelGGL(k_gather_normalize, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, c->stream, d_emb, d_tidx, N, d, X, Xn);
     KCHECK(c);
     const int method = c->clustering_method;
-    const bool euclid = method == SD_LINKAGE_CENTROID || method == SD_LINKAGE_MEDIAN || method == SD_LINKAGE_WARD;
+    const int metric = linkage_metric_of(method);
     *Xout = X; *Xnout = Xn;
     // a group call ran the dendrogram of these rows ahead of the job (finalize_jobs, many.hip: the same kernels on the same train rows); it is taken once
     if (c->ahead_N == N && N >= 2) { Z.swap(c->ahead_Z); c->ahead_N = -1; return SD_OK; }
-    return run_linkage_host(c, euclid ? Xn : X, N, d, method, euclid ? SD_METRIC_EUCLIDEAN : SD_METRIC_COSINE, Z);
+    return run_linkage_host(c, metric == SD_METRIC_EUCLIDEAN ? Xn : X, N, d, method, metric, Z);
 }
 
 // The rows cluster_rows hands to the linkage for the train rows idx of d_emb, into out [N][d] on the device (asynchronous): the same kernel, so the same bits
@@ -215,8 +216,7 @@ int linkage_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, in
     if (N < 1) return SD_OK;
     WS(c, int, d_tidx, "cl_tidx", N);
     HIPCHK(c, hipMemcpyAsync(d_tidx, idx.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    const int method = c->clustering_method;
-    if (method == SD_LINKAGE_CENTROID || method == SD_LINKAGE_MEDIAN || method == SD_LINKAGE_WARD)
+    if (linkage_metric_of((int)c->clustering_method) == SD_METRIC_EUCLIDEAN)
         hipLaunchKernelGGL(k_gather_normalize, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, c->stream, d_emb, d_tidx, N, d, (double*)nullptr, out);
     else {
         WS(c, double, Xn, "cl_Xn", N * d);

@@ -8,6 +8,14 @@
 #include <cstdint>
 #include <cstdlib>
 #include <vector>
+#include "../../include/sdhip.h"
+
+// Clustering.py:317-333: centroid, median and ward are euclidean-only and run on the unit-normalised rows; the other four methods run on the rows as
+// they are with the cosine metric
+inline int linkage_metric_of(int method)
+{
+    return method == SD_LINKAGE_CENTROID || method == SD_LINKAGE_MEDIAN || method == SD_LINKAGE_WARD ? SD_METRIC_EUCLIDEAN : SD_METRIC_COSINE;
+}
 
 // fcluster(criterion="distance"), cl.cpp:121-232 + 442-457.  Node ids grow with merge order, so the
 // per-node max merge height is a forward pass; labels follow the reference's visiting order: internal

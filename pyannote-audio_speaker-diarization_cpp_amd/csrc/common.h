@@ -428,6 +428,9 @@ int launch_lstm_rec(sd_ctx* c, const float* G, const float* whh_f, const float* 
                     float* H, int64_t B, int F);
 int launch_classifier(sd_ctx* c, const float* y, const float* W, const float* bias, float* seg, int64_t chunks, int F);
 // ---- pipeline.cpp
+int check_method_metric(sd_ctx* c, int method, int metric);      // the refusals of an entry that takes a linkage method and a metric from its caller; SD_OK = fine
+// a 16-bit sample as the float the reference makes of it: sample * 1.0f / 32768.0 (sd.cpp:2948-2951); the division by 2^15 is exact in f32
+__host__ __device__ __forceinline__ float pcm_to_float(int16_t s) { return (float)s * (1.0f / 32768.0f); }
 __global__ void k_pcm_to_f32(const int16_t* __restrict__ pcm, float* __restrict__ dst, int64_t n);   // dst[0, n) = pcm / 32768, dst[n, n + SD_WAV_PAD) = 0; grid GRID1(n + SD_WAV_PAD)
 __global__ void k_f32_to_f64(const float* __restrict__ a, double* __restrict__ b, int64_t n);          // embeddings widened before clustering (sd.cpp:2555); grid GRID1(n)
 // the two producers of workspace "wav_f32": *out = {n samples, origin 0, padded}; a caller that uploaded a slice of a longer recording sets n and origin itself

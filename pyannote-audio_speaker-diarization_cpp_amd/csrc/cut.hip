@@ -3,11 +3,13 @@
 // scores, count, f64 embeddings, the gathered train rows and the dendrogram.  sd_cut_turns_many then calls run_clustering's own finish of a cut
 // (cluster_cut, cluster.hip) once per cut and runs the three stages that touch every embedding row or every frame ONCE for all cuts of a group:
 //   k_assign_cuts        k_assign + k_mark_inactive: every row against the centroids of all cuts (one concatenated table), arg-max inside each cut's segment
-//   k_activations_cuts   k_activations for all cuts: act[t][f][k], K_t columns for cut t
-//   k_topk_cuts          k_topk for all cuts
+//   k_activations_cuts   k_activations' activation_sum (recon_dev.h) for all cuts: act[t][f][k], K_t columns for cut t
+//   k_topk_cuts          k_topk's topk_row (recon_dev.h) for all cuts
 // followed by one copy of all binary matrices and reconstruct.hip's to_annotation_host per cut.
 #include "common.h"
 #include "exact_fp.h"
+#include "cosine_rule.h"
+#include "recon_dev.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -42,7 +44,7 @@ __global__ void k_cut_cen_norms(const double* __restrict__ cen, int K, int d, do
 
 // One wave per embedding row.  The centroids of the Tn cuts of a launch lie in one table, cut q in rows [coff[q], coff[q + 1]); the lanes spread over the
 // rows of the table (k_assign's lanes spread over one cut's K: 60 of 64 idle at K = 4), then over the cuts, each lane scanning the segment of its cuts in
-// ascending order.  Arithmetic of k_assign: dot, m1, m2 three sequential sums over d, 2 - (1 - dot / (sqrt * sqrt)), first maximum wins (strict >), a NaN
+// ascending order.  As in k_assign: dot, m1, m2 three sequential sums over d, 2 - cosine_distance (cosine_rule.h), first maximum wins (strict >), a NaN
 // row goes to cluster 0 with a NaN best score, a zero magnitude raises *err.  A table longer than the LDS tile is taken tile by tile; the one cut that
 // spans a tile boundary is carried in the registers of the lane that owns it (cut q belongs to lane q % 64 in every tile).
 // hard[slot[q]][row] = the arg-max inside cut q, or -2 where the row has no active frame (k_mark_inactive, sd.cpp:3172-3191); best[q][row] = its score.
@@ -67,8 +69,9 @@ __global__ __launch_bounds__(64) void k_assign_cuts(const double* __restrict__ E
             double dot = 0.0;
             for (int i = 0; i < d; ++i) dot += e[i] * cc[i];
             const double m2 = cen_m2[j0 + j];
-            if (m1 == 0.0 || m2 == 0.0) { *err = 1; soft[j] = NAN; }
-            else soft[j] = 2.0 - (1.0 - (dot / (sqrt(m1) * sqrt(m2))));
+            bool zero = false;
+            soft[j] = 2.0 - cosine_distance(dot, m1, m2, &zero);
+            if (zero) *err = 1;
         }
         __syncthreads();
         const int q_lo = seg_of(coff, Tn, 1, j0), q_hi = seg_of(coff, Tn, 1, j0 + kn - 1);
@@ -89,7 +92,7 @@ __global__ __launch_bounds__(64) void k_assign_cuts(const double* __restrict__ E
 }
 
 // k_activations (reconstruct.hip) for the Tg cuts of a group: element e of act = (cut t, frame f, cluster k) with act[t] = [nact][K_t] at koff[t] * nact,
-// K_t = koff[t + 1] - koff[t]; hard [Tg][chunks * 3].  The chunk window and the order of the sum are k_activations'.
+// K_t = koff[t + 1] - koff[t]; hard [Tg][chunks * 3]
 __global__ void k_activations_cuts(const float* __restrict__ seg, const int* __restrict__ hard_all, const int* __restrict__ sfr, int64_t chunks,
                                    const int* __restrict__ koff, int Tg, double* __restrict__ act, int64_t nact)
 {
@@ -100,23 +103,7 @@ __global__ void k_activations_cuts(const float* __restrict__ seg, const int* __r
     const int64_t r = idx - (int64_t)koff[t] * nact;
     const int64_t f = r / K;
     const int k = (int)(r - f * K);
-    const int* hard = hard_all + (size_t)t * chunks * SD_SPEAKERS;
-    const double per_chunk = 0.5 / 0.016875;
-    int64_t lo = (int64_t)((double)(f - (SD_FRAMES - 1)) / per_chunk) - 2; if (lo < 0) lo = 0;
-    int64_t hi = (int64_t)((double)f / per_chunk) + 2; if (hi > chunks - 1) hi = chunks - 1;
-    double sum = 0.0;
-    for (int64_t c = lo; c <= hi; ++c) {
-        const int64_t j = f - sfr[c];
-        if (j < 0 || j >= SD_FRAMES) continue;
-        const int* h = hard + c * SD_SPEAKERS;
-        const float* s = seg + (c * SD_FRAMES + j) * SD_SPEAKERS;
-        float mx = -INFINITY; bool any = false;
-#pragma unroll
-        for (int q = 0; q < SD_SPEAKERS; ++q)
-            if (h[q] == k) { any = true; mx = (mx < s[q]) ? s[q] : mx; }      // std::max semantics, sd.cpp:2779
-        if (any) sum += (double)mx;                                           // NaN entries are masked out, sd.cpp:1197-1201
-    }
-    act[idx] = sum;                                                           // skip_average, missing = 0.0 (sd.cpp:2651)
+    act[idx] = activation_sum(seg, hard_all + (size_t)t * chunks * SD_SPEAKERS, sfr, chunks, f, k);
 }
 
 // k_topk (reconstruct.hip) for the Tg cuts of a group: binary[t] = [rows][K_t] at koff[t] * rows
@@ -128,21 +115,7 @@ __global__ void k_topk_cuts(const double* __restrict__ act, const int32_t* __res
     const int t = (int)(id / rows);
     const int64_t i = id - (int64_t)t * rows;
     const int K = koff[t + 1] - koff[t];
-    const double* a = act + (int64_t)koff[t] * nact + (ar0 + i) * K;
-    uint8_t* b = binary + (int64_t)koff[t] * rows + i * K;
-    for (int k = 0; k < K; ++k) b[k] = 0;
-    if (i >= crow) return;
-    int c = count[cr0 + i];
-    if (c > K) c = K;                                                         // sd.cpp:2681
-    for (int j = 0; j < c; ++j) {
-        int best = -1; double bv = 0.0;
-        for (int k = 0; k < K; ++k) {
-            if (b[k]) continue;
-            const double v = -1.0 * a[k];                                     // argsort of negated values, sd.cpp:2727
-            if (best < 0 || v < bv) { best = k; bv = v; }
-        }
-        if (best >= 0) b[best] = 1;
-    }
+    topk_row(act + (int64_t)koff[t] * nact + (ar0 + i) * K, binary + (int64_t)koff[t] * rows + i * K, K, i < crow ? count[cr0 + i] : 0);
 }
 
 // ---------------------------------------------------------------- open

@@ -15,10 +15,8 @@
 #include <cstring>
 
 // ---------------------------------------------------------------- k_pdist (cl.cpp:408-431)
-// COS: the cosine metric, 1 - dot / (sqrt(m1) * sqrt(m2)) with the three sums sequential in q -- the reference's own cosine rule (sd.cpp:476-498, the
-// formula k_assign uses; Clustering.py:317-333 runs the single / complete / average / weighted linkages on it).  m1 / m2 depend on one row each and are
-// kept once per row of the tile: the same sums a per-pair loop would form.  A zero-norm row raises *err (the reference throws, sd.cpp:493-495).
-#define PT 64
+// The tile loop and the value of a pair are linkage_dev.h's pdist_tile and pdist_value (COS: the cosine metric); k_pdist_sq and k_pdist_jobs
+// (linkage_batch.hip) call the same two.  A zero-norm row under the cosine metric raises *err (the reference throws, sd.cpp:493-495).
 template <bool COS>
 __global__ __launch_bounds__(256) void k_pdist(const double* __restrict__ X, int64_t N, int d, double* __restrict__ D, int* __restrict__ err)
 {
@@ -26,52 +24,17 @@ __global__ __launch_bounds__(256) void k_pdist(const double* __restrict__ X, int
     if (tj < ti) return;
     __shared__ double Xi[PT][33], Xj[PT][33];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    double acc[4][4];
-    double ma[4] = {0.0, 0.0, 0.0, 0.0}, mb[4] = {0.0, 0.0, 0.0, 0.0};      // COS: squared norms of the tile's rows
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) acc[u][v] = 0.0;
-    for (int q0 = 0; q0 < d; q0 += 32) {
-        for (int e = tid; e < PT * 32; e += 256) {
-            const int r = e >> 5, q = e & 31;
-            int64_t gi = (int64_t)ti * PT + r; if (gi > N - 1) gi = N - 1;
-            int64_t gj = (int64_t)tj * PT + r; if (gj > N - 1) gj = N - 1;
-            const bool in = (q0 + q) < d;
-            Xi[r][q] = in ? X[(size_t)gi * d + q0 + q] : 0.0;
-            Xj[r][q] = in ? X[(size_t)gj * d + q0 + q] : 0.0;
-        }
-        __syncthreads();
-        for (int q = 0; q < 32; ++q) {          // sequential in q: same summation order as the reference
-            double a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { a[u] = Xi[ty + 16 * u][q]; b[u] = Xj[tx + 16 * u][q]; }
-            if constexpr (COS) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { ma[u] += a[u] * a[u]; mb[u] += b[u] * b[u]; }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) acc[u][v] += a[u] * b[v];
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) { const double df = a[u] - b[v]; acc[u][v] += df * df; }
-            }
-        }
-        __syncthreads();
-    }
+    double acc[4][4], ma[4], mb[4];
+    pdist_tile<COS>(X, N, d, ti, tj, Xi, Xj, acc, ma, mb);
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
             const int64_t i = (int64_t)ti * PT + ty + 16 * u, j = (int64_t)tj * PT + tx + 16 * v;
             if (i < j && j < N) {
-                if constexpr (COS) {
-                    if (ma[u] == 0.0 || mb[v] == 0.0) { *err = 1; D[cidx(N, i, j)] = NAN; }
-                    else D[cidx(N, i, j)] = 1.0 - (acc[u][v] / (sqrt(ma[u]) * sqrt(mb[v])));
-                } else D[cidx(N, i, j)] = sqrt(acc[u][v]);
+                bool zero_norm = false;
+                D[cidx(N, i, j)] = pdist_value<COS>(acc[u][v], ma[u], mb[v], &zero_norm);
+                if (zero_norm) *err = 1;
             }
         }
 }
@@ -86,42 +49,8 @@ __global__ __launch_bounds__(256) void k_pdist_sq(const double* __restrict__ X, 
     __shared__ double Xi[PT][33], Xj[PT][33];
     __shared__ double Tt[PT][PT + 1];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    double acc[4][4];
-    double ma[4] = {0.0, 0.0, 0.0, 0.0}, mb[4] = {0.0, 0.0, 0.0, 0.0};      // COS: squared norms of the tile's rows
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) acc[u][v] = 0.0;
-    for (int q0 = 0; q0 < d; q0 += 32) {
-        for (int e = tid; e < PT * 32; e += 256) {
-            const int r = e >> 5, q = e & 31;
-            int64_t gi = (int64_t)ti * PT + r; if (gi > N - 1) gi = N - 1;
-            int64_t gj = (int64_t)tj * PT + r; if (gj > N - 1) gj = N - 1;
-            const bool in = (q0 + q) < d;
-            Xi[r][q] = in ? X[(size_t)gi * d + q0 + q] : 0.0;
-            Xj[r][q] = in ? X[(size_t)gj * d + q0 + q] : 0.0;
-        }
-        __syncthreads();
-        for (int q = 0; q < 32; ++q) {          // sequential in q: same summation order as the reference (and as k_pdist)
-            double a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { a[u] = Xi[ty + 16 * u][q]; b[u] = Xj[tx + 16 * u][q]; }
-            if constexpr (COS) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { ma[u] += a[u] * a[u]; mb[u] += b[u] * b[u]; }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) acc[u][v] += a[u] * b[v];
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) { const double df = a[u] - b[v]; acc[u][v] += df * df; }
-            }
-        }
-        __syncthreads();
-    }
+    double acc[4][4], ma[4], mb[4];
+    pdist_tile<COS>(X, N, d, ti, tj, Xi, Xj, acc, ma, mb);
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -132,10 +61,11 @@ __global__ __launch_bounds__(256) void k_pdist_sq(const double* __restrict__ X, 
             if constexpr (COS) {
                 dv = 0.0;
                 if (i != j && i < N && j < N) {
-                    if (ma[u] == 0.0 || mb[v] == 0.0) { *err = 1; dv = NAN; }
-                    else dv = 1.0 - (acc[u][v] / (sqrt(ma[u]) * sqrt(mb[v])));
+                    bool zero_norm = false;
+                    dv = pdist_value<true>(acc[u][v], ma[u], mb[v], &zero_norm);
+                    if (zero_norm) *err = 1;
                 }
-            } else dv = (i == j) ? 0.0 : sqrt(acc[u][v]);
+            } else dv = (i == j) ? 0.0 : pdist_value<false>(acc[u][v], ma[u], mb[v], nullptr);
             Tt[li][lj] = dv;
             if (i < N && j < N && (ti != tj || i <= j)) D[(size_t)i * N + j] = dv;
         }

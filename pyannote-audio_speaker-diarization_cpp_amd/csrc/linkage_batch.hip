@@ -1,10 +1,10 @@
 // linkage_batch.hip -- run_linkage_many: the small linkage jobs of one call in shared launches, one workgroup per job.
 // The jobs of a group call (sd_diarize_many*, sd_stream_turns_many) and of sd_linkage_many are independent; below N = 1500 run_linkage gives each of them
 // to k_linkage_heap, one workgroup on one CU.  Here the jobs that would go there (linkage_batch_plan.h) are taken through the same three steps together:
-//   k_pdist_jobs<COS>            the condensed distance matrices of all jobs, blockIdx.z = job; per pair the arithmetic of k_pdist
+//   k_pdist_jobs<COS>            the condensed distance matrices of all jobs, blockIdx.z = job; k_pdist's pdist_tile and pdist_value
 //   k_prepare_jobs               sizes = 1, ids = iota, the exact nearest neighbour above each row by k_row_nn's rule
-//   k_linkage_heap_jobs<M, T>    one workgroup of T threads per job: the body of k_linkage_heap, heap in LDS
-// The algorithm of a job is the one of the single path, statement for statement, so its Z is the same bytes whatever else is in the launch.
+//   k_linkage_heap_jobs<M, T>    one workgroup of T threads per job: k_linkage_heap's heap_linkage, heap in LDS
+// The distances and the merges of a job come from the same functions (linkage_dev.h) as on the single path, so its Z is the same bytes whatever else is in the launch.
 // All three read a device table of LinkageDevJob; a job's error slot, raised by k_pdist_jobs for a zero-norm row under the cosine metric, stops the two
 // kernels behind it for that job alone (no linkage kernel ever sees a NaN distance).
 #include "common.h"
@@ -22,7 +22,6 @@ struct LinkageDevJob {
 };
 
 // ---------------------------------------------------------------- k_pdist_jobs: k_pdist (linkage.hip) per job
-#define PT 64
 template <bool COS>
 __global__ __launch_bounds__(256) void k_pdist_jobs(const LinkageDevJob* __restrict__ jobs, int d, int* __restrict__ errs)
 {
@@ -31,56 +30,20 @@ __global__ __launch_bounds__(256) void k_pdist_jobs(const LinkageDevJob* __restr
     const int tiles = (int)((N + PT - 1) / PT);
     const int ti = blockIdx.y, tj = blockIdx.x;
     if (ti >= tiles || tj >= tiles || tj < ti) return;      // beyond this job's own tiles, or below the diagonal
-    const double* __restrict__ X = jb.X;
     double* __restrict__ D = jb.D;
     __shared__ double Xi[PT][33], Xj[PT][33];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    double acc[4][4];
-    double ma[4] = {0.0, 0.0, 0.0, 0.0}, mb[4] = {0.0, 0.0, 0.0, 0.0};      // COS: squared norms of the tile's rows
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) acc[u][v] = 0.0;
-    for (int q0 = 0; q0 < d; q0 += 32) {
-        for (int e = tid; e < PT * 32; e += 256) {
-            const int r = e >> 5, q = e & 31;
-            int64_t gi = (int64_t)ti * PT + r; if (gi > N - 1) gi = N - 1;
-            int64_t gj = (int64_t)tj * PT + r; if (gj > N - 1) gj = N - 1;
-            const bool in = (q0 + q) < d;
-            Xi[r][q] = in ? X[(size_t)gi * d + q0 + q] : 0.0;
-            Xj[r][q] = in ? X[(size_t)gj * d + q0 + q] : 0.0;
-        }
-        __syncthreads();
-        for (int q = 0; q < 32; ++q) {          // sequential in q: same summation order as the reference (and as k_pdist)
-            double a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { a[u] = Xi[ty + 16 * u][q]; b[u] = Xj[tx + 16 * u][q]; }
-            if constexpr (COS) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { ma[u] += a[u] * a[u]; mb[u] += b[u] * b[u]; }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) acc[u][v] += a[u] * b[v];
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) { const double df = a[u] - b[v]; acc[u][v] += df * df; }
-            }
-        }
-        __syncthreads();
-    }
+    double acc[4][4], ma[4], mb[4];
+    pdist_tile<COS>(jb.X, N, d, ti, tj, Xi, Xj, acc, ma, mb);
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
             const int64_t i = (int64_t)ti * PT + ty + 16 * u, j = (int64_t)tj * PT + tx + 16 * v;
             if (i < j && j < N) {
-                if constexpr (COS) {
-                    if (ma[u] == 0.0 || mb[v] == 0.0) { errs[jb.err] = 1; D[cidx(N, i, j)] = NAN; }
-                    else D[cidx(N, i, j)] = 1.0 - (acc[u][v] / (sqrt(ma[u]) * sqrt(mb[v])));
-                } else D[cidx(N, i, j)] = sqrt(acc[u][v]);
+                bool zero_norm = false;
+                D[cidx(N, i, j)] = pdist_value<COS>(acc[u][v], ma[u], mb[v], &zero_norm);
+                if (zero_norm) errs[jb.err] = 1;
             }
         }
 }
@@ -107,131 +70,23 @@ __global__ __launch_bounds__(256) void k_prepare_jobs(const LinkageDevJob* __res
 }
 
 // ---------------------------------------------------------------- k_linkage_heap_jobs: k_linkage_heap (linkage_heap.hip) per job, T threads
-template <int T>
-__device__ __forceinline__ MinIdx block_min_t(MinIdx m, MinIdx* sh)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    m = wave_min(m);
-    __syncthreads();                 // sh may still be read from the previous use
-    if (lane == 0) sh[w] = m;
-    __syncthreads();
-    MinIdx r = sh[0];
-#pragma unroll
-    for (int k = 1; k < T / 64; ++k) r = better(r, sh[k]);
-    return r;
-}
-
-// fast_linkage (cl.cpp:289-406) with its heap replayed by thread 0, as k_linkage_heap does it (see there for the account of every step); what differs is
-// where the arrays come from (the job table), that the heap is always in LDS (the planner batches n - 1 <= LINKAGE_HEAP_LDS only) and the thread count.
-// Nothing the threads compute depends on T: the scans keep the lowest index among equal minima, the Lance-Williams update is per element, the rows whose
-// bound dropped are drained in ascending order.
+// heap_linkage (linkage_dev.h) as k_linkage_heap calls it; what differs is where the arrays come from (the job table), that the heap is always in LDS (the
+// planner batches n - 1 <= LINKAGE_HEAP_LDS only) and the thread count, on which nothing the function computes depends.
 #define JOBS_CHANGED_WORDS ((LINKAGE_HEAP_LDS + 1 + 31) / 32)
 template <int METHOD, int T>
 __global__ __launch_bounds__(T) void k_linkage_heap_jobs(const LinkageDevJob* jobs, const int* errs)
 {
     __shared__ unsigned changed[JOBS_CHANGED_WORDS];      // bitmap of the rows whose bound dropped in this merge
     __shared__ MinIdx sh[T / 64];
-    __shared__ int s_ok, s_x, s_y;
-    __shared__ double s_dist;
+    __shared__ HeapShared s;
     __shared__ double s_hv[LINKAGE_HEAP_LDS];
     __shared__ int s_hk[LINKAGE_HEAP_LDS], s_hp[LINKAGE_HEAP_LDS];
     const LinkageDevJob jb = jobs[blockIdx.x];
     const int n = jb.n;
     if (n < 2 || n - 1 > LINKAGE_HEAP_LDS || errs[jb.err]) return;
-    double* D = jb.D; int* size = jb.size; int* cid = jb.cid; int* nb = jb.nb; double* md = jb.md; double* Z = jb.Z;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int64_t N = n;
     HeapRef h;
     h.val = s_hv; h.key = s_hk; h.pos = s_hp; h.size = n - 1;
-    const int nwords = (n + 31) / 32;
-    for (int i = tid; i < nwords; i += T) changed[i] = 0u;
-    for (int i = tid; i < n - 1; i += T) { h.val[i] = md[i]; h.key[i] = i; h.pos[i] = i; }          // cl.cpp:80-91
-    __syncthreads();
-    if (tid == 0) for (int i = h.size / 2; i >= 0; --i) hp_down(h, i);                                // cl.cpp:94
-    __syncthreads();
-    for (int k = 0; k < n - 1; ++k) {
-        int x = 0, y = 0; double dist = 0.0;
-        for (int guard = 0; guard < n - k; ++guard) {                                                // cl.cpp:323
-            if (tid == 0) {
-                const int hx = h.key[0]; const double hd = h.val[0]; const int hy = nb[hx];          // get_min
-                s_x = hx; s_y = hy; s_dist = hd;
-                s_ok = (hy >= 0) && (hd == D[cidx(N, hx, hy)]);                                     // cl.cpp:329
-            }
-            __syncthreads();
-            x = s_x; y = s_y; dist = s_dist;
-            const int ok = s_ok;
-            __syncthreads();
-            if (ok) break;
-            // stale candidate: row x's true nearest neighbour (cl.cpp:333-338)
-            MinIdx q = scan_row_nn<4>(D, size, N, n, x, tid, T);
-            q = block_min_t<T>(q, sh);
-            y = q.i; dist = (q.i < 0) ? (double)INFINITY : q.v;
-            if (tid == 0) { nb[x] = y; md[x] = dist; hp_change(h, x, dist); }
-            __syncthreads();
-        }
-        if (tid == 0) { hp_swap(h, 0, h.size - 1); h.size -= 1; hp_down(h, 0); }                      // remove_min, cl.cpp:101-105
-        if (y < 0) { if (tid == 0) Z[(size_t)k * 4 + 3] = NAN; return; }                             // cannot happen while two clusters are active
-        const int nx = size[x], ny = size[y];
-        __syncthreads();
-        if (tid == 0) {
-            int ix = cid[x], iy = cid[y];
-            if (ix > iy) { const int t = ix; ix = iy; iy = t; }
-            Z[(size_t)k * 4 + 0] = (double)ix; Z[(size_t)k * 4 + 1] = (double)iy;
-            Z[(size_t)k * 4 + 2] = dist;       Z[(size_t)k * 4 + 3] = (double)(nx + ny);
-            size[x] = 0; size[y] = nx + ny; cid[y] = n + k;
-        }
-        __syncthreads();
-        for (int z0 = tid; z0 < n; z0 += T * 4) {                    // 4 rows per thread: all their loads issued together
-            double dzx[4], dzy[4], mdz[4]; int sz[4], nbz[4]; int64_t izy[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int z = z0 + u * T;
-                const int zc = (z < n && z != y) ? z : ((y > 0) ? 0 : 1);        // any valid row other than y
-                izy[u] = cidx(N, zc, y);
-                sz[u] = size[zc];
-                dzx[u] = (zc == x) ? 0.0 : D[cidx(N, zc, x)];
-                dzy[u] = D[izy[u]];
-                const int zr = zc < n - 1 ? zc : n - 2;
-                nbz[u] = nb[zr]; mdz[u] = md[zr];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int z = z0 + u * T;
-                if (z >= n || z == y || sz[u] == 0) continue;
-                const double nd = lw_update<METHOD>(dzx[u], dzy[u], dist, nx, ny, sz[u]);   // cl.cpp:367
-                D[izy[u]] = nd;
-                if (z < x && nbz[u] == x) nb[z] = y;                                    // cl.cpp:374-378
-                if (z < y && nd < mdz[u]) { nb[z] = y; md[z] = nd; atomicOr(&changed[z >> 5], 1u << (z & 31)); }   // cl.cpp:381-392
-            }
-        }
-        __syncthreads();
-        // change_value(z, D[z,y]) for the rows whose bound dropped, ascending z (cl.cpp:381-392): wave 0 walks the bitmap
-        if (tid < 64) {
-            for (int w0 = 0; w0 < nwords; w0 += 64) {
-                const int wi = w0 + lane;
-                const unsigned wd = wi < nwords ? changed[wi] : 0u;
-                unsigned long long live = __ballot(wd != 0u);
-                if (wd != 0u) changed[wi] = 0u;
-                while (live) {
-                    const int l = __builtin_ctzll(live);
-                    live &= live - 1;
-                    unsigned bits = (unsigned)__builtin_amdgcn_readlane((int)wd, l);
-                    while (bits) {
-                        const int z = (w0 + l) * 32 + __builtin_ctz(bits);
-                        bits &= bits - 1;
-                        if (lane == 0) hp_change(h, z, md[z]);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        if (y < n - 1) {                                                              // cl.cpp:395-404
-            MinIdx q = scan_row_nn<4>(D, size, N, n, y, tid, T);
-            q = block_min_t<T>(q, sh);
-            if (tid == 0 && q.i >= 0) { nb[y] = q.i; md[y] = q.v; hp_change(h, y, q.v); }
-        }
-        __syncthreads();
-    }
+    heap_linkage<METHOD, T>(jb.D, n, jb.size, jb.cid, jb.nb, jb.md, jb.Z, h, changed, sh, s);
 }
 
 // ---------------------------------------------------------------- the driver
@@ -356,10 +211,7 @@ extern "C" int sd_linkage_many(sd_ctx* c, const double* h_X, const int64_t* N, i
         rows += N[j];
         if (rows > 0x7fffffff) SD_FAIL(c, SD_ERR_ARG, "sd_linkage_many: more than 2^31 - 1 rows in one call");
     }
-    if (method < SD_LINKAGE_SINGLE || method > SD_LINKAGE_WEIGHTED) SD_FAIL(c, SD_ERR_ARG, "unknown linkage method %d (SD_LINKAGE_SINGLE .. SD_LINKAGE_WEIGHTED)", method);
-    if (metric != SD_METRIC_EUCLIDEAN && metric != SD_METRIC_COSINE) SD_FAIL(c, SD_ERR_ARG, "unknown metric %d (SD_METRIC_EUCLIDEAN, SD_METRIC_COSINE)", metric);
-    if (metric == SD_METRIC_COSINE && (method == SD_LINKAGE_CENTROID || method == SD_LINKAGE_MEDIAN || method == SD_LINKAGE_WARD))
-        SD_FAIL(c, SD_ERR_ARG, "centroid, median and ward linkage are defined for the euclidean metric only");
+    if (int rc = check_method_metric(c, method, metric)) return rc;
     DTMP(c, dx, (size_t)rows * d * sizeof(double));
     HIPCHK(c, hipMemcpyAsync(dx.p, h_X, (size_t)rows * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
     std::vector<LinkageManyJob> jobs((size_t)J);

@@ -5,6 +5,7 @@
 #pragma once
 #include "common.h"
 #include "exact_fp.h"
+#include "cosine_rule.h"
 #include "linkage_batch_plan.h"
 #include <cfloat>
 #include <cmath>
@@ -14,6 +15,63 @@ __host__ __device__ __forceinline__ int64_t cidx(int64_t n, int64_t i, int64_t j
 {
     if (i < j) return n * i - (i * (i + 1) / 2) + (j - i - 1);
     return n * j - (j * (j + 1) / 2) + (i - j - 1);
+}
+
+// ---------------------------------------------------------------- one tile of pairwise distances (cl.cpp:408-431): k_pdist, k_pdist_sq, k_pdist_jobs
+// 256 threads take the PT x PT tile (ti, tj) of rows of X[N][d]: thread (ty, tx) = (tid >> 4, tid & 15) accumulates the 4 x 4 pairs of rows
+// ti * PT + ty + 16 u and tj * PT + tx + 16 v through the LDS stages Xi / Xj, sequential in q: the summation order of the reference.  COS: acc holds the
+// dot products, ma / mb the squared norms of the thread's rows (one row each, kept once per row of the tile: the same sums a per-pair loop would form);
+// else acc holds the sums of squared differences and ma / mb stay 0.  Rows past N - 1 are read as row N - 1; the caller stores only pairs inside N.
+#define PT 64
+template <bool COS>
+__device__ __forceinline__ void pdist_tile(const double* __restrict__ X, int64_t N, int d, int ti, int tj, double (&Xi)[PT][33], double (&Xj)[PT][33],
+                                           double (&acc)[4][4], double (&ma)[4], double (&mb)[4])
+{
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        ma[u] = 0.0; mb[u] = 0.0;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) acc[u][v] = 0.0;
+    }
+    for (int q0 = 0; q0 < d; q0 += 32) {
+        for (int e = tid; e < PT * 32; e += 256) {
+            const int r = e >> 5, q = e & 31;
+            int64_t gi = (int64_t)ti * PT + r; if (gi > N - 1) gi = N - 1;
+            int64_t gj = (int64_t)tj * PT + r; if (gj > N - 1) gj = N - 1;
+            const bool in = (q0 + q) < d;
+            Xi[r][q] = in ? X[(size_t)gi * d + q0 + q] : 0.0;
+            Xj[r][q] = in ? X[(size_t)gj * d + q0 + q] : 0.0;
+        }
+        __syncthreads();
+        for (int q = 0; q < 32; ++q) {          // sequential in q: same summation order as the reference
+            double a[4], b[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { a[u] = Xi[ty + 16 * u][q]; b[u] = Xj[tx + 16 * u][q]; }
+            if constexpr (COS) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { ma[u] += a[u] * a[u]; mb[u] += b[u] * b[u]; }
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) acc[u][v] += a[u] * b[v];
+            } else {
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) { const double df = a[u] - b[v]; acc[u][v] += df * df; }
+            }
+        }
+        __syncthreads();
+    }
+}
+// the distance of one pair from its sums.  COS: the reference's own cosine rule (cosine_rule.h; Clustering.py:317-333 runs the single / complete / average /
+// weighted linkages on it), *zero_norm raised for a zero-norm row (the reference throws, sd.cpp:493-495); else the euclidean distance, zero_norm unused
+template <bool COS>
+__device__ __forceinline__ double pdist_value(double acc, double ma, double mb, bool* zero_norm)
+{
+    if constexpr (COS) return cosine_distance(acc, ma, mb, zero_norm);
+    else return sqrt(acc);
 }
 
 // ---------------------------------------------------------------- nearest active neighbour above a row (cl.cpp:259-276)
@@ -67,6 +125,20 @@ __device__ __forceinline__ MinIdx wave_min(MinIdx m)
     r.v = vmin;
     if (mask & (mask - 1)) r.i = wave_min_i(at ? m.i : 0x7fffffff);
     else r.i = __builtin_amdgcn_readlane(m.i, __builtin_amdgcn_readfirstlane(__ffsll((long long)mask) - 1));
+    return r;
+}
+// the same over a workgroup of T threads, all of them calling; sh: T / 64 entries of LDS.  Every thread returns the workgroup's minimum
+template <int T>
+__device__ __forceinline__ MinIdx block_min(MinIdx m, MinIdx* sh)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    m = wave_min(m);
+    __syncthreads();                 // sh may still be read from the previous use
+    if (lane == 0) sh[w] = m;
+    __syncthreads();
+    MinIdx r = sh[0];
+#pragma unroll
+    for (int k = 1; k < T / 64; ++k) r = better(r, sh[k]);
     return r;
 }
 
@@ -196,6 +268,118 @@ __device__ __forceinline__ void hp_change(HeapRef& h, int key, double v)        
     const double old = h.val[idx];
     h.val[idx] = v;
     if (v < old) hp_up(h, idx); else hp_down(h, idx);
+}
+
+// ---------------------------------------------------------------- heap_linkage: one workgroup of T threads, the reference's heap included
+// fast_linkage (cl.cpp:289-406) with its indexed binary min-heap (cl.cpp:28-119) kept bit for bit: thread 0 replays every
+// Heap operation the reference performs, in the reference's order -- heapify (cl.cpp:94), get_min / change_value in the lazy
+// validation loop (cl.cpp:323-339), remove_min (cl.cpp:340), change_value for the rows whose lower bound dropped IN ASCENDING z
+// (cl.cpp:381-392), change_value for row y (cl.cpp:395-404) -- while the O(n) parts of a merge (Lance-Williams update, neighbour
+// patches, nearest-neighbour scans) run on all threads.  Which of several rows with EXACTLY equal lower bounds the heap hands
+// out first depends on the whole history of its array, so nothing short of replaying it reproduces the reference's merge
+// order on data with ties (duplicate embeddings, lattice points); with it Z is bit-identical for any input.
+// The rows whose bound dropped are collected in the LDS bitmap `changed` ((n + 31) / 32 words) and drained in ascending order by wave 0.
+// Nothing the threads compute depends on T: the scans keep the lowest index among equal minima, the Lance-Williams update is per element, the rows whose
+// bound dropped are drained in ascending order.
+// The whole workgroup calls it with the same arguments: D the condensed matrix with exact nb / md, size = 1, cid = iota; h.val / key / pos with room for
+// n - 1 entries (LDS or global memory), h.size = n - 1; sh: T / 64 entries and s in LDS.  It returns for all threads together.
+// (no __restrict__: every array here is written by one thread and re-read by others across barriers)
+struct HeapShared { int ok, x, y; double dist; };      // thread 0's candidate of the validation loop, for everyone
+template <int METHOD, int T>
+__device__ __forceinline__ void heap_linkage(double* D, int n, int* size, int* cid, int* nb, double* md, double* Z, HeapRef h, unsigned* changed,
+                                             MinIdx* sh, HeapShared& s)
+{
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t N = n;
+    const int nwords = (n + 31) / 32;
+    for (int i = tid; i < nwords; i += T) changed[i] = 0u;
+    for (int i = tid; i < n - 1; i += T) { h.val[i] = md[i]; h.key[i] = i; h.pos[i] = i; }          // cl.cpp:80-91
+    __syncthreads();
+    if (tid == 0) for (int i = h.size / 2; i >= 0; --i) hp_down(h, i);                                // cl.cpp:94
+    __syncthreads();
+    for (int k = 0; k < n - 1; ++k) {
+        int x = 0, y = 0; double dist = 0.0;
+        for (int guard = 0; guard < n - k; ++guard) {                                                // cl.cpp:323
+            if (tid == 0) {
+                const int hx = h.key[0]; const double hd = h.val[0]; const int hy = nb[hx];          // get_min
+                s.x = hx; s.y = hy; s.dist = hd;
+                s.ok = (hy >= 0) && (hd == D[cidx(N, hx, hy)]);                                     // cl.cpp:329
+            }
+            __syncthreads();
+            x = s.x; y = s.y; dist = s.dist;
+            const int ok = s.ok;
+            __syncthreads();
+            if (ok) break;
+            // stale candidate: row x's true nearest neighbour (cl.cpp:333-338)
+            MinIdx q = scan_row_nn<4>(D, size, N, n, x, tid, T);
+            q = block_min<T>(q, sh);
+            y = q.i; dist = (q.i < 0) ? (double)INFINITY : q.v;
+            if (tid == 0) { nb[x] = y; md[x] = dist; hp_change(h, x, dist); }
+            __syncthreads();
+        }
+        if (tid == 0) { hp_swap(h, 0, h.size - 1); h.size -= 1; hp_down(h, 0); }                      // remove_min, cl.cpp:101-105
+        if (y < 0) { if (tid == 0) Z[(size_t)k * 4 + 3] = NAN; return; }                             // cannot happen while two clusters are active; y is the same in every thread
+        const int nx = size[x], ny = size[y];
+        __syncthreads();
+        if (tid == 0) {
+            int ix = cid[x], iy = cid[y];
+            if (ix > iy) { const int t = ix; ix = iy; iy = t; }
+            Z[(size_t)k * 4 + 0] = (double)ix; Z[(size_t)k * 4 + 1] = (double)iy;
+            Z[(size_t)k * 4 + 2] = dist;       Z[(size_t)k * 4 + 3] = (double)(nx + ny);
+            size[x] = 0; size[y] = nx + ny; cid[y] = n + k;
+        }
+        __syncthreads();
+        for (int z0 = tid; z0 < n; z0 += T * 4) {                    // 4 rows per thread: all their loads issued together
+            double dzx[4], dzy[4], mdz[4]; int sz[4], nbz[4]; int64_t izy[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int z = z0 + u * T;
+                const int zc = (z < n && z != y) ? z : ((y > 0) ? 0 : 1);        // any valid row other than y
+                izy[u] = cidx(N, zc, y);
+                sz[u] = size[zc];
+                dzx[u] = (zc == x) ? 0.0 : D[cidx(N, zc, x)];
+                dzy[u] = D[izy[u]];
+                const int zr = zc < n - 1 ? zc : n - 2;
+                nbz[u] = nb[zr]; mdz[u] = md[zr];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int z = z0 + u * T;
+                if (z >= n || z == y || sz[u] == 0) continue;
+                const double nd = lw_update<METHOD>(dzx[u], dzy[u], dist, nx, ny, sz[u]);   // cl.cpp:367
+                D[izy[u]] = nd;
+                if (z < x && nbz[u] == x) nb[z] = y;                                    // cl.cpp:374-378
+                if (z < y && nd < mdz[u]) { nb[z] = y; md[z] = nd; atomicOr(&changed[z >> 5], 1u << (z & 31)); }   // cl.cpp:381-392
+            }
+        }
+        __syncthreads();
+        // change_value(z, D[z,y]) for the rows whose bound dropped, ascending z (cl.cpp:381-392): wave 0 walks the bitmap
+        if (tid < 64) {
+            for (int w0 = 0; w0 < nwords; w0 += 64) {
+                const int wi = w0 + lane;
+                const unsigned wd = wi < nwords ? changed[wi] : 0u;
+                unsigned long long live = __ballot(wd != 0u);
+                if (wd != 0u) changed[wi] = 0u;
+                while (live) {
+                    const int l = __builtin_ctzll(live);
+                    live &= live - 1;
+                    unsigned bits = (unsigned)__builtin_amdgcn_readlane((int)wd, l);
+                    while (bits) {
+                        const int z = (w0 + l) * 32 + __builtin_ctz(bits);
+                        bits &= bits - 1;
+                        if (lane == 0) hp_change(h, z, md[z]);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        if (y < n - 1) {                                                              // cl.cpp:395-404
+            MinIdx q = scan_row_nn<4>(D, size, N, n, y, tid, T);
+            q = block_min<T>(q, sh);
+            if (tid == 0 && q.i >= 0) { nb[y] = q.i; md[y] = q.v; hp_change(h, y, q.v); }
+        }
+        __syncthreads();
+    }
 }
 
 

@@ -24,7 +24,7 @@ __global__ void k_many_pack(const ManyRow* __restrict__ rows, int R, int is_f32,
         const ManyRow row = rows[r];
         for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < row.len && row.base + i < dst_len; i += step) {
             float v = 0.0f;
-            if (i < row.n) v = is_f32 ? ((const float*)row.src)[i] : (float)((const int16_t*)row.src)[i] * (1.0f / 32768.0f);      // sd.cpp:2948-2951
+            if (i < row.n) v = is_f32 ? ((const float*)row.src)[i] : pcm_to_float(((const int16_t*)row.src)[i]);
             dst[row.base + i] = v;
         }
     }
@@ -197,9 +197,8 @@ static int dendrograms_ahead(sd_ctx* c, const std::vector<FinalJob>& jobs, std::
     }
     if (lj.size() >= 2) {
         const int method = c->clustering_method;
-        const bool euclid = method == SD_LINKAGE_CENTROID || method == SD_LINKAGE_MEDIAN || method == SD_LINKAGE_WARD;
         std::vector<int32_t> st(lj.size(), SD_OK);
-        if ((rc = run_linkage_many(c, lj.data(), (int64_t)lj.size(), d, method, euclid ? SD_METRIC_EUCLIDEAN : SD_METRIC_COSINE, st.data()))) return rc;
+        if ((rc = run_linkage_many(c, lj.data(), (int64_t)lj.size(), d, method, linkage_metric_of(method), st.data()))) return rc;
         for (size_t k = 0; k < lj.size(); ++k) if (st[k] == SD_OK) ZN[owner[k]] = lj[k].N;
     } else HIPCHK(c, hipStreamSynchronize(c->stream));      // one job alone gains nothing: its finalize runs the linkage (tidx of the last gather must outlive its upload)
     c->stage_ms[2] += now_ms() - t0;

@@ -7,11 +7,11 @@
 #include <cmath>
 #include <cstdlib>
 
-// a1 tail: input_wav[i] = sample * 1.0f / 32768.0 (sd.cpp:2948-2951); division by 2^15 is exact in f32
+// a1 tail: input_wav[i] = pcm_to_float(sample) (common.h)
 __global__ void k_pcm_to_f32(const int16_t* __restrict__ pcm, float* __restrict__ dst, int64_t n)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = (float)pcm[i] * (1.0f / 32768.0f);
+    if (i < n) dst[i] = pcm_to_float(pcm[i]);
     else if (i < n + SD_WAV_PAD) dst[i] = 0.0f;   // padding: SincNet's 256-tap rows read 4 samples past the last window (zero weights, finite data)
 }
 // embeddings are widened to double before clustering (sd.cpp:2555)
@@ -107,8 +107,8 @@ extern "C" int sd_postseg(sd_ctx* c, const float* h_seg, int64_t chunks, uint8_t
 }
 
 // ------------------------------------------------------------------ a12-a14
-// method / metric of the *_ex entries (Clustering.py:251-276 / 317-333); 0 = fine
-static int check_method_metric(sd_ctx* c, int method, int metric)
+// method / metric of the *_ex entries and sd_linkage_many (Clustering.py:251-276 / 317-333); 0 = fine
+int check_method_metric(sd_ctx* c, int method, int metric)
 {
     if (method < SD_LINKAGE_SINGLE || method > SD_LINKAGE_WEIGHTED) SD_FAIL(c, SD_ERR_ARG, "unknown linkage method %d (SD_LINKAGE_SINGLE .. SD_LINKAGE_WEIGHTED)", method);
     if (metric != SD_METRIC_EUCLIDEAN && metric != SD_METRIC_COSINE) SD_FAIL(c, SD_ERR_ARG, "unknown metric %d (SD_METRIC_EUCLIDEAN, SD_METRIC_COSINE)", metric);

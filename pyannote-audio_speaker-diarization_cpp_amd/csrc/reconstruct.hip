@@ -8,13 +8,14 @@
 // kernel picks the count[t] most active clusters per frame.
 #include "common.h"
 #include "exact_fp.h"
+#include "recon_dev.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 
 static const double kFrameStep = 0.016875, kFrameDur = 0.016875;      // sd.cpp:2430-2431
 
-// act[f][k] = sum over chunks c covering frame f of max_{s: hard[c][s]==k} seg[c][f-sfr[c]][s]   (0.0 if none)
+// act[f][k] = sum over chunks c covering frame f of max_{s: hard[c][s]==k} seg[c][f-sfr[c]][s]   (0.0 if none): activation_sum, recon_dev.h
 __global__ void k_activations(const float* __restrict__ seg, const int* __restrict__ hard, const int* __restrict__ sfr,
                               int64_t chunks, int K, double* __restrict__ act, int64_t nact)
 {
@@ -22,45 +23,16 @@ __global__ void k_activations(const float* __restrict__ seg, const int* __restri
     if (idx >= nact * K) return;
     const int64_t f = idx / K;
     const int k = (int)(idx - f * K);
-    const double per_chunk = 0.5 / 0.016875;
-    int64_t lo = (int64_t)((double)(f - (SD_FRAMES - 1)) / per_chunk) - 2; if (lo < 0) lo = 0;
-    int64_t hi = (int64_t)((double)f / per_chunk) + 2; if (hi > chunks - 1) hi = chunks - 1;
-    double sum = 0.0;
-    for (int64_t c = lo; c <= hi; ++c) {
-        const int64_t j = f - sfr[c];
-        if (j < 0 || j >= SD_FRAMES) continue;
-        const int* h = hard + c * SD_SPEAKERS;
-        const float* s = seg + (c * SD_FRAMES + j) * SD_SPEAKERS;
-        float mx = -INFINITY; bool any = false;
-#pragma unroll
-        for (int q = 0; q < SD_SPEAKERS; ++q)
-            if (h[q] == k) { any = true; mx = (mx < s[q]) ? s[q] : mx; }      // std::max semantics, sd.cpp:2779
-        if (any) sum += (double)mx;                                           // NaN entries are masked out, sd.cpp:1197-1201
-    }
-    act[idx] = sum;                                                           // skip_average, missing = 0.0 (sd.cpp:2651)
+    act[idx] = activation_sum(seg, hard, sfr, chunks, f, k);
 }
 
-// binary[i][k] = 1 for the count[i] clusters with the largest activation (stable order on ties), sd.cpp:2720-2759
+// binary[i][k] = 1 for the count[i] clusters with the largest activation (topk_row, recon_dev.h); rows from crow on have no count: zeros
 __global__ void k_topk(const double* __restrict__ act, const int32_t* __restrict__ count, int64_t ar0, int64_t cr0,
                        int64_t rows, int64_t crow, int K, uint8_t* __restrict__ binary)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows) return;
-    const double* a = act + (ar0 + i) * K;
-    uint8_t* b = binary + i * K;
-    for (int k = 0; k < K; ++k) b[k] = 0;
-    if (i >= crow) return;
-    int c = count[cr0 + i];
-    if (c > K) c = K;                                                         // sd.cpp:2681
-    for (int j = 0; j < c; ++j) {
-        int best = -1; double bv = 0.0;
-        for (int k = 0; k < K; ++k) {
-            if (b[k]) continue;
-            const double v = -1.0 * a[k];                                     // argsort of negated values, sd.cpp:2727
-            if (best < 0 || v < bv) { best = k; bv = v; }
-        }
-        if (best >= 0) b[best] = 1;
-    }
+    topk_row(act + (ar0 + i) * K, binary + i * K, K, i < crow ? count[cr0 + i] : 0);
 }
 
 // SlidingWindow::operator[] (sd.cpp:1092-1115): walks from 0.0, may bail out on short audio

@@ -41,7 +41,7 @@ __global__ void k_tail_move(const float* __restrict__ src, float* __restrict__ d
 
 template <bool PCM> __device__ __forceinline__ float group_load(const void* src, int64_t j)
 {
-    return PCM ? (float)((const int16_t*)src)[j] * (1.0f / 32768.0f) : ((const float*)src)[j];      // sd.cpp:2948-2951
+    return PCM ? pcm_to_float(((const int16_t*)src)[j]) : ((const float*)src)[j];
 }
 
 template <bool PCM> __device__ __forceinline__ void group_copy(const GroupRow* __restrict__ rows, int R, int64_t pad)
@@ -64,7 +64,7 @@ template <bool PCM> __device__ __forceinline__ void group_copy(const GroupRow* _
                 if (i + 4 <= n && wide) {
                     if (PCM) {
                         const short4 p = *reinterpret_cast<const short4*>((const int16_t*)row.src + i);
-                        v = make_float4((float)p.x * (1.0f / 32768.0f), (float)p.y * (1.0f / 32768.0f), (float)p.z * (1.0f / 32768.0f), (float)p.w * (1.0f / 32768.0f));
+                        v = make_float4(pcm_to_float(p.x), pcm_to_float(p.y), pcm_to_float(p.z), pcm_to_float(p.w));
                     } else v = *reinterpret_cast<const float4*>((const float*)row.src + i);
                 } else {
                     if (i < n) v.x = group_load<PCM>(row.src, i);

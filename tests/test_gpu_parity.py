@@ -831,6 +831,31 @@ def test_heap_linkage_with_global_heap_is_bit_identical(diarizer):
     assert np.array_equal(Z, Z_ref)
 
 
+@pytest.mark.parametrize("N", [2049, 2050])
+def test_heap_linkage_on_either_side_of_the_heap_storage_boundary(diarizer, N):
+    """k_linkage_heap keeps its heap in LDS up to 2048 entries (N = 2049, the last such size) and in global memory above (N = 2050, the first): one
+    function, heap_linkage, on both storages.  Centroid / euclidean against the oracle and average / cosine against scipy's generic algorithm, on
+    tie-free blobs and on the same rows with 100 of them duplicated (merges at height 0: the heap's own order among equal bounds)"""
+    import test_clustering_hyperparams as hp
+    rng = np.random.default_rng(N)
+    X = _blobs(rng, N, d=16)
+    Xd = X.copy()
+    dst = rng.choice(N, 100, replace=False)
+    Xd[dst] = X[rng.choice(np.setdiff1d(np.arange(N), dst), 100)]             # each a copy of a row that stays as it is
+    diarizer.set_option("linkage_wgs", 0)
+    try:
+        diarizer.reset_stats()
+        for name, Y in (("tie-free", X), ("duplicates", Xd)):
+            Zc = diarizer.linkage_ex(Y, "centroid", sdhip.METRIC_EUCLIDEAN)
+            Za = diarizer.linkage_ex(Y, "average", sdhip.METRIC_COSINE)
+            assert np.array_equal(Zc, orc.ahc(Y, orc.THRESH_F32)[1]), (name, N)
+            hp._assert_same_dendrogram(Za, hp._ref_linkage(Y, "average", "cosine"), "average")
+            assert ((Zc[:, 2] == 0).sum() >= 100) == (name == "duplicates")     # the case is what it claims to be
+        assert diarizer.kernel_stats("linkage_heap")["launches"] == 4         # it was this kernel every time
+    finally:
+        diarizer.set_option("linkage_wgs", -1)
+
+
 @pytest.mark.parametrize("square", [1, 0, 2])
 @pytest.mark.parametrize("N,d,G,T", [(2500, 3, 32, 256), (4000, 2, 16, 512), (3000, 8, 64, 256), (6000, 3, -1, 0)])
 def test_cooperative_linkage_on_unclustered_low_dimensional_data(diarizer, N, d, G, T, square):

@@ -91,6 +91,37 @@ def test_exact_ties_take_the_merge_order_of_the_heap(diarizer, method):
         assert same(Z[1], orc.linkage_centroid(orc.pdist(Xs[1]), len(Xs[1])))
 
 
+@pytest.mark.parametrize("metric", [sdhip.METRIC_EUCLIDEAN, sdhip.METRIC_COSINE])
+@pytest.mark.parametrize("N,d", [(65, 33), (129, 192), (64, 1)])
+def test_the_three_distance_kernels_agree(diarizer, N, d, metric):
+    """k_pdist (one job, condensed), k_pdist_jobs (a job among others) and k_pdist_sq (one job, the square matrix) share their tile loop and the value of
+    a pair: the dendrogram of the same rows is the same bytes behind each of them.  A tile edge, a row length that is no multiple of the 32-wide stage,
+    a single tile.  (The square matrix is the cooperative kernels': two workgroups, centroid.)"""
+    method = "centroid" if metric == sdhip.METRIC_EUCLIDEAN else "average"
+    rng = np.random.default_rng(1000 * N + d)
+    X, *others = [rng.standard_normal((n, d)) for n in (N, 40, 130, 7)]
+    if d == 1 and metric == sdhip.METRIC_COSINE:
+        X, others = np.abs(X) + 0.5, [np.abs(Y) + 0.5 for Y in others]      # (as above: all ties, rows away from zero)
+    ks = lambda name: diarizer.kernel_stats(name)["launches"]
+    diarizer.reset_stats()
+    alone = diarizer.linkage_ex(X, method, metric)
+    assert ks("pdist") == 1 and ks("linkage_heap") == 1 and ks("pdist_jobs") == 0
+    Z, st = diarizer.linkage_many([others[0], X, others[1], others[2]], method, metric)
+    assert not st.any() and ks("pdist_jobs") == 1 and ks("pdist") == 1
+    assert same(Z[1], alone)
+    if method == "centroid":
+        rg0 = ks("linkage_rg_launches")
+        try:
+            diarizer.set_option("linkage_wgs", 2)
+            diarizer.set_option("linkage_square", 1)
+            square = diarizer.linkage_ex(X, method, metric)
+        finally:
+            diarizer.set_option("linkage_wgs", -1)
+            diarizer.set_option("linkage_square", -1)
+        assert ks("linkage_rg_launches") == rg0 + 1 and ks("pdist") == 2 and ks("linkage_heap") == 1
+        assert same(square, alone)
+
+
 def test_more_workgroups_than_compute_units(diarizer):
     rng = np.random.default_rng(300)
     sizes = rng.integers(2, 25, 300)
