@@ -177,6 +177,55 @@ int sd_test_frontend_features(sd_ctx*, const float* wav, int64_t n_held, int64_t
 int sd_test_frontend_signals(sd_ctx*, const float* signals, const float* wav_lens, int64_t B, int skip_dead_rows, int32_t icanary, float canary,
                              int32_t* prefix_out, int32_t* counts_out, float* feats_out, int64_t feat_rows, int32_t* rowoff_out, int64_t* info_out);
 
+/* ---- test hooks (tests/test_backend_kernels.py): ONE launch of one kernel behind the two networks (csrc/postseg.hip, cluster.hip, reconstruct.hip, cut.hip and
+ * the casts of pipeline.cpp) through the function the product's stage calls (grid, block and LDS are the product's), under the contract of the hooks above:
+ * host pointers; every input is followed by 256 guard units -- NaN for floating-point operands, for integer and byte operands a value that would change
+ * a result (named per hook) --, a unit being a row where the operand has rows and an element otherwise; every output is preset to a canary (fcanary for
+ * float and double, icanary for int32, SD_TEST_BCANARY for bytes), has 256 slack units behind it and comes back WHOLE; a case whose defined reads leave
+ * its operands is SD_ERR_ARG before any launch.  An output pointer documented as optional may be NULL: the kernel then gets a null pointer, as in the product.
+ *
+ * sd_test_binarize: k_binarize_masks (run_postseg).  seg [chunks][293][3] -> bin [(chunks + 256) * 879] bytes, masks [(chunks + 256) * 3][293],
+ *   nact [(chunks + 256) * 3]; each optional.
+ * sd_test_count: k_count with run_count's geometry.  bin [chunks][293][3] bytes (guard bytes 0x55) -> count [sd_count_frames(chunks) + 256] and, optional,
+ *   avg of the same length.
+ * sd_test_gather_normalize: k_gather_normalize.  X [rows][d], tidx [N] in [0, rows) (guard: `rows`, the first NaN row) -> xout (optional) and xn [N + 256][d].
+ * sd_test_cluster_means: k_cluster_means.  X [rows][d], order [off[nl]] in [0, rows) (guard: `rows`), off [nl + 1] ascending from 0 (guard: 0)
+ *   -> cen [nl + 256][d].
+ * sd_test_assign: k_assign.  E [M][d], cen [K][d] -> hard [M + 256], err [1 + 256] (entry 0 cleared before the launch, as assign_all clears it), soft
+ *   [(M + 256) * K] (optional), best [M + 256] (optional).
+ * sd_test_constrained_argmax: k_constrained_argmax.  soft [chunks][3][K], 1 <= K <= 64, fill = the caller's (Clustering.py:83) -> hard [(chunks + 256) * 3].
+ * sd_test_activations: k_activations with reconstruct_frames' first frames.  seg [chunks][293][3], hard [chunks][3] (guard: 0) -> act [nact + 256][K];
+ *   *nact_out = the frames (rows of act that the kernel writes).
+ * sd_test_topk: k_topk.  act [act_rows][K], count [n_count] (guard: 0x7fffffff); 0 <= ar0, ar0 + rows <= act_rows, 0 <= crow <= rows, 0 <= cr0,
+ *   cr0 + crow <= n_count -> binary [(rows + 256) * K] bytes.
+ * sd_test_assign_cuts: k_cut_cen_norms, then k_assign_cuts.  E [M][d], cen [coff[Tn]][d], coff [Tn + 1] strictly ascending from 0 (guard: coff[Tn]), slot
+ *   [Tn] distinct in [0, n_slots) (guard: 0), nact [M] (guard: 0) -> m2 [coff[Tn] + 256], hard [n_slots * M + 256], best [Tn * M + 256], err [1 + 256].
+ * sd_test_recon_cuts: k_activations_cuts, then k_topk_cuts.  seg [chunks][293][3], hard [Tg][chunks * 3] (guard: 0), koff [Tg + 1] strictly ascending from 0
+ *   (guard: koff[Tg]), count [n_count] (guard: 0x7fffffff) -> act [nact * koff[Tg] + 256], binary [rows * koff[Tg] + 256] bytes.  act_in (optional,
+ *   [nact * koff[Tg]]): k_topk_cuts reads this table (NaN behind it) instead of the one k_activations_cuts wrote.  ar0 + rows <= nact, the rest as sd_test_topk.
+ * sd_test_pcm_to_f32: k_pcm_to_f32 (pcm_to_wav).  pcm [n] (guard: 0x7fff) -> wav [n + 512 + 256]: the samples, the 512 zeros, the canary.
+ * sd_test_f32_to_f64: k_f32_to_f64.  a [n] -> b [n + 256].
+ * sd_test_mark_inactive: k_mark_inactive.  hard [n] (in), nact [n] (guard: 0) -> hard_out [n + 256]: the table behind the rule, then icanary. */
+#define SD_TEST_BCANARY 0xA5
+int sd_test_binarize(sd_ctx*, const float* seg, int64_t chunks, float fcanary, int32_t icanary, uint8_t* bin_out, float* masks_out, int32_t* nact_out);
+int sd_test_count(sd_ctx*, const uint8_t* bin, int64_t chunks, float fcanary, int32_t icanary, int32_t* count_out, double* avg_out);
+int sd_test_gather_normalize(sd_ctx*, const double* X, int64_t rows, const int32_t* tidx, int64_t N, int d, float fcanary, double* xout, double* xn_out);
+int sd_test_cluster_means(sd_ctx*, const double* X, int64_t rows, int d, const int32_t* order, const int32_t* off, int nl, float fcanary, double* cen_out);
+int sd_test_assign(sd_ctx*, const double* E, int64_t M, int d, const double* cen, int K, float fcanary, int32_t icanary, int32_t* hard_out, int32_t* err_out,
+                   double* soft_out, double* best_out);
+int sd_test_constrained_argmax(sd_ctx*, const double* soft, int64_t chunks, int K, double fill, int32_t icanary, int32_t* hard_out);
+int sd_test_activations(sd_ctx*, const float* seg, const int32_t* hard, int64_t chunks, int K, float fcanary, double* act_out, int64_t act_cap, int64_t* nact_out);
+int sd_test_topk(sd_ctx*, const double* act, int64_t act_rows, const int32_t* count, int64_t n_count, int64_t ar0, int64_t cr0, int64_t rows, int64_t crow,
+                 int K, uint8_t* binary_out);
+int sd_test_assign_cuts(sd_ctx*, const double* E, int64_t M, int d, const double* cen, const int32_t* coff, const int32_t* slot, int Tn, int n_slots,
+                        const int32_t* nact, float fcanary, int32_t icanary, double* m2_out, int32_t* hard_out, double* best_out, int32_t* err_out);
+int sd_test_recon_cuts(sd_ctx*, const float* seg, const int32_t* hard, int64_t chunks, const int32_t* koff, int Tg, const double* act_in, const int32_t* count,
+                       int64_t n_count, int64_t ar0, int64_t cr0, int64_t rows, int64_t crow, float fcanary, double* act_out, int64_t act_cap,
+                       uint8_t* binary_out, int64_t* nact_out);
+int sd_test_pcm_to_f32(sd_ctx*, const int16_t* pcm, int64_t n, float fcanary, float* wav_out);
+int sd_test_f32_to_f64(sd_ctx*, const float* a, int64_t n, float fcanary, double* b_out);
+int sd_test_mark_inactive(sd_ctx*, const int32_t* hard, const int32_t* nact, int64_t n, int32_t icanary, int32_t* hard_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,14 @@ __global__ void k_gather_normalize(const double* __restrict__ X, const int* __re
     }
 }
 
+// the one launch of k_gather_normalize (cluster_rows, linkage_rows, the test hook): Xout may be null; asynchronous on c->stream
+int launch_gather_normalize(sd_ctx* c, const double* d_emb, const int* d_tidx, int64_t N, int d, double* Xout, double* Xn)
+{
+    hipLaunchKernelGGL(k_gather_normalize, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, c->stream, d_emb, d_tidx, N, d, Xout, Xn);
+    KCHECK(c);
+    return SD_OK;
+}
+
 // a12 with its copy back: the linkage matrix of the N >= 2 rows of d_Xn on the host ([N - 1][4]); fewer rows: no linkage runs and Z is empty
 int run_linkage_host(sd_ctx* c, const double* d_Xn, int64_t N, int d, int method, int metric, std::vector<double>& Z)
 {
@@ -53,20 +61,30 @@ int run_linkage_host(sd_ctx* c, const double* d_Xn, int64_t N, int d, int method
 __global__ void k_cluster_means(const double* __restrict__ X, int d, const int* __restrict__ order, const int* __restrict__ off,
                                 double* __restrict__ cen)
 {
-    const int k = blockIdx.x, q = threadIdx.x;
-    if (q >= d) return;
-    double s = 0.0;
+    const int k = blockIdx.x;
     const int a = off[k], b = off[k + 1];
-    int t = a;
-    for (; t + 16 <= b; t += 16) {          // 16 rows in flight, added in member order (the sum itself stays sequential)
-        double v[16];
+    for (int q = threadIdx.x; q < d; q += blockDim.x) {     // a block holds at most 1 024 threads: a thread walks q, q + blockDim.x, ..., each with a sum of its own
+        double s = 0.0;
+        int t = a;
+        for (; t + 16 <= b; t += 16) {          // 16 rows in flight, added in member order (the sum itself stays sequential)
+            double v[16];
 #pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = X[(size_t)order[t + u] * d + q];
+            for (int u = 0; u < 16; ++u) v[u] = X[(size_t)order[t + u] * d + q];
 #pragma unroll
-        for (int u = 0; u < 16; ++u) s += v[u];
+            for (int u = 0; u < 16; ++u) s += v[u];
+        }
+        for (; t < b; ++t) s += X[(size_t)order[t] * d + q];
+        cen[(size_t)k * d + q] = s / (double)(b - a);
     }
-    for (; t < b; ++t) s += X[(size_t)order[t] * d + q];
-    cen[(size_t)k * d + q] = s / (double)(b - a);
+}
+// the one launch of k_cluster_means (reassign_small, final_means, mean_of_rows, the test hook): one block per cluster, one thread per element up to the
+// 1 024 threads of a block; asynchronous on c->stream
+int launch_cluster_means(sd_ctx* c, const double* X, int d, const int* d_order, const int* d_off, int nl, double* d_cen)
+{
+    const int threads = std::min(((d + 63) / 64) * 64, 1024);
+    hipLaunchKernelGGL(k_cluster_means, dim3(nl), dim3(threads), 0, c->stream, X, d, d_order, d_off, d_cen);
+    KCHECK(c);
+    return SD_OK;
 }
 
 // cosine distance with the reference's sequential sums (sd.cpp:476-498; cosine_rule.h); soft = 2 - d; argmax first-max-wins
@@ -180,6 +198,20 @@ __global__ void k_constrained_argmax(const double* __restrict__ soft, int64_t ch
     hard[c * 3] = h[0]; hard[c * 3 + 1] = h[1]; hard[c * 3 + 2] = h[2];
 }
 
+// the launches of k_assign and k_constrained_argmax (assign_all, the test hooks): one wave per row / one thread per chunk; asynchronous on c->stream
+int launch_assign(sd_ctx* c, const double* E, int64_t M, int d, const double* cen, int K, int* hard, int* err, double* soft, double* best)
+{
+    hipLaunchKernelGGL(k_assign, dim3((unsigned)M), dim3(64), 0, c->stream, E, M, d, cen, K, hard, err, soft, best);
+    KCHECK(c);
+    return SD_OK;
+}
+int launch_constrained_argmax(sd_ctx* c, const double* soft, int64_t chunks, int K, double fill, int* hard)
+{
+    hipLaunchKernelGGL(k_constrained_argmax, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, c->stream, soft, chunks, K, fill, hard);
+    KCHECK(c);
+    return SD_OK;
+}
+
 static double cos_dist_host(const double* a, const double* b, int d, bool* err)      // sd.cpp:476-498
 {
     double dot = 0.0, m1 = 0.0, m2 = 0.0;
@@ -199,8 +231,7 @@ int cluster_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, in
     WS(c, double, X, "cl_X", N * d);
     WS(c, double, Xn, "cl_Xn", N * d);
     HIPCHK(c, hipMemcpyAsync(d_tidx, idx.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_gather_normalize, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, c->stream, d_emb, d_tidx, N, d, X, Xn);
-    KCHECK(c);
+    if (int rc = launch_gather_normalize(c, d_emb, d_tidx, N, d, X, Xn)) return rc;
     const int method = c->clustering_method;
     const int metric = linkage_metric_of(method);
     *Xout = X; *Xnout = Xn;
@@ -216,14 +247,9 @@ int linkage_rows(sd_ctx* c, const double* d_emb, const std::vector<int>& idx, in
     if (N < 1) return SD_OK;
     WS(c, int, d_tidx, "cl_tidx", N);
     HIPCHK(c, hipMemcpyAsync(d_tidx, idx.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    if (linkage_metric_of((int)c->clustering_method) == SD_METRIC_EUCLIDEAN)
-        hipLaunchKernelGGL(k_gather_normalize, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, c->stream, d_emb, d_tidx, N, d, (double*)nullptr, out);
-    else {
-        WS(c, double, Xn, "cl_Xn", N * d);
-        hipLaunchKernelGGL(k_gather_normalize, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, c->stream, d_emb, d_tidx, N, d, out, Xn);
-    }
-    KCHECK(c);
-    return SD_OK;
+    if (linkage_metric_of((int)c->clustering_method) == SD_METRIC_EUCLIDEAN) return launch_gather_normalize(c, d_emb, d_tidx, N, d, nullptr, out);
+    WS(c, double, Xn, "cl_Xn", N * d);
+    return launch_gather_normalize(c, d_emb, d_tidx, N, d, out, Xn);
 }
 
 // a11: every small cluster goes to the nearest candidate -- first the G rows of `enrolled` (host, [G][d]; the enrolled flow), then the large clusters in
@@ -239,8 +265,7 @@ static int reassign_small(sd_ctx* c, const double* X, int d, const std::vector<i
     WS(c, double, d_cen, "cl_cen", (size_t)nl * d);
     HIPCHK(c, hipMemcpyAsync(d_order, order.data(), N * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_off, off.data(), (size_t)(nl + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_cluster_means, dim3(nl), dim3(((d + 63) / 64) * 64), 0, c->stream, X, d, d_order, d_off, d_cen);   // means of UN-normalised rows (sd.cpp:2386)
-    KCHECK(c);
+    if (int rc = launch_cluster_means(c, X, d, d_order, d_off, nl, d_cen)) return rc;   // means of UN-normalised rows (sd.cpp:2386)
     std::vector<double> cen((size_t)nl * d);
     HIPCHK(c, hipMemcpyAsync(cen.data(), d_cen, cen.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -292,10 +317,8 @@ int final_means(sd_ctx* c, const double* X, int d, const std::vector<int>& lab, 
     WS(c, double, d_cen2, "cl_cen", (size_t)(G + nl) * d);
     HIPCHK(c, hipMemcpyAsync(d_order2, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_off2, off.data(), (size_t)(nl + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    if (nl > 0) {
-        hipLaunchKernelGGL(k_cluster_means, dim3(nl), dim3(((d + 63) / 64) * 64), 0, c->stream, X, d, d_order2, d_off2, d_cen2 + (size_t)G * d);
-        KCHECK(c);
-    }
+    if (nl > 0)
+        if (int rc = launch_cluster_means(c, X, d, d_order2, d_off2, nl, d_cen2 + (size_t)G * d)) return rc;
     *cen_out = d_cen2;
     return SD_OK;
 }
@@ -315,8 +338,7 @@ int assign_all(sd_ctx* c, const double* d_emb, int64_t M, int d, const double* d
     double* d_soft = nullptr; double* d_best = nullptr;
     if (constrained_assign || dumping) { WS(c, double, t_soft, "cl_soft", (size_t)M * K); d_soft = t_soft; }
     if (constrained_assign || soft_best) { WS(c, double, t_best, "cl_best", M); d_best = t_best; }
-    hipLaunchKernelGGL(k_assign, dim3((unsigned)M), dim3(64), 0, c->stream, d_emb, M, d, d_cen2, K, d_hard, d_err, d_soft, d_best);
-    KCHECK(c);
+    if (int rc = launch_assign(c, d_emb, M, d, d_cen2, K, d_hard, d_err, d_soft, d_best)) return rc;
     int herr = 0;
     HIPCHK(c, hipMemcpyAsync(hard.data(), d_hard, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&herr, d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -334,8 +356,7 @@ int assign_all(sd_ctx* c, const double* d_emb, int64_t M, int d, const double* d
         if (fill == INFINITY) fill = 0.0;
         const int64_t chunks = M / SD_SPEAKERS;
         if (K <= LSAP_MAXC) {
-            hipLaunchKernelGGL(k_constrained_argmax, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, c->stream, d_soft, chunks, K, fill, d_hard);
-            KCHECK(c);
+            if (int rc = launch_constrained_argmax(c, d_soft, chunks, K, fill, d_hard)) return rc;
             HIPCHK(c, hipMemcpyAsync(hard.data(), d_hard, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         } else SD_FAIL(c, SD_ERR_ARG, "constrained assignment supports up to %d clusters (found %d)", LSAP_MAXC, K);
@@ -455,8 +476,7 @@ int mean_of_rows(sd_ctx* c, const double* d_emb, int d, const std::vector<int>& 
     WS(c, double, d_cen1, "cl_cen", (size_t)d);
     HIPCHK(c, hipMemcpyAsync(d_order1, tidx.data(), N * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_off1, off1, sizeof(off1), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_cluster_means, dim3(1), dim3(((d + 63) / 64) * 64), 0, c->stream, d_emb, d, d_order1, d_off1, d_cen1);
-    KCHECK(c);
+    if (int rc = launch_cluster_means(c, d_emb, d, d_order1, d_off1, 1, d_cen1)) return rc;
     HIPCHK(c, hipMemcpyAsync(h_cen.data(), d_cen1, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SD_OK;

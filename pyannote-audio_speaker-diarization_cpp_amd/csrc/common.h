@@ -509,6 +509,27 @@ int mean_of_rows(sd_ctx* c, const double* d_emb, int d, const std::vector<int>& 
 int final_means(sd_ctx* c, const double* X, int d, const std::vector<int>& lab, int nl, int G, std::vector<int>& order, std::vector<int>& off, double** cen_out);
 int assign_all(sd_ctx* c, const double* d_emb, int64_t M, int d, const double* d_cen2, int K, const std::vector<int64_t>& counts,
                std::vector<int>& hard, int* Kout, std::vector<double>* soft_best, double** soft_out, JobResult& res);
+// ---- the launches of the back end's kernels, asynchronous on c->stream: grid, block and LDS are computed here, once; the stage functions above and
+// the test hooks of backend_test.hip call the same ones.  cluster.hip: gather_normalize (Xout may be null), cluster_means (nl blocks of min(d rounded
+// up to 64, 1 024) threads), assign (soft / best may be null), constrained_argmax (K <= 64)
+int launch_gather_normalize(sd_ctx* c, const double* d_emb, const int* d_tidx, int64_t N, int d, double* Xout, double* Xn);
+int launch_cluster_means(sd_ctx* c, const double* X, int d, const int* d_order, const int* d_off, int nl, double* d_cen);
+int launch_assign(sd_ctx* c, const double* E, int64_t M, int d, const double* cen, int K, int* hard, int* err, double* soft, double* best);
+int launch_constrained_argmax(sd_ctx* c, const double* soft, int64_t chunks, int K, double fill, int* hard);
+// reconstruct.hip: act [nact][K]; binary [rows][K] from rows [ar0, ar0 + rows) of act and entries [cr0, cr0 + crow) of count
+int launch_activations(sd_ctx* c, const float* d_seg, const int* d_hard, const int* d_sfr, int64_t chunks, int K, double* d_act, int64_t nact);
+int launch_topk(sd_ctx* c, const double* d_act, const int32_t* d_count, int64_t ar0, int64_t cr0, int64_t rows, int64_t crow, int K, uint8_t* d_binary);
+// cut.hip: the batched twins; total = coff[Tn] rows of the centroid table, sumK = koff[Tg] label columns
+int launch_cut_cen_norms(sd_ctx* c, const double* d_cen, int total, int d, double* d_m2);
+int launch_assign_cuts(sd_ctx* c, const double* E, int64_t M, int d, const double* d_cen, const double* d_m2, const int* d_coff, const int* d_slot, int Tn,
+                       const int* d_nact, int* d_hard, double* d_best, int* d_err);
+int launch_activations_cuts(sd_ctx* c, const float* d_seg, const int* d_hard, const int* d_sfr, int64_t chunks, const int* d_koff, int Tg, int64_t sumK,
+                            double* d_act, int64_t nact);
+int launch_topk_cuts(sd_ctx* c, const double* d_act, const int32_t* d_count, int64_t ar0, int64_t cr0, int64_t rows, int64_t crow, const int* d_koff, int Tg,
+                     int64_t nact, uint8_t* d_binary);
+// pipeline.cpp: the widening of the embeddings and the inactive rule (sd.cpp:2555, 3172-3191)
+int launch_f32_to_f64(sd_ctx* c, const float* d_a, double* d_b, int64_t n);
+int launch_mark_inactive(sd_ctx* c, int* d_hard, const int* d_nact, int64_t n);
 // ---- cluster.hip: the three refusals of a call that clusters under an enrolled gallery (SD_ERR_ARG; nothing is touched); SD_OK without a gallery
 int enrolled_refusal(sd_ctx* c, int d, int num_clusters, int min_clusters, int max_clusters);
 // ---- reconstruct.hip

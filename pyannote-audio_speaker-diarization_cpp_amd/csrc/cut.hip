@@ -118,6 +118,35 @@ __global__ void k_topk_cuts(const double* __restrict__ act, const int32_t* __res
     topk_row(act + (int64_t)koff[t] * nact + (ar0 + i) * K, binary + (int64_t)koff[t] * rows + i * K, K, i < crow ? count[cr0 + i] : 0);
 }
 
+// the launches of the four kernels (cut_group, the test hooks); asynchronous on c->stream
+int launch_cut_cen_norms(sd_ctx* c, const double* d_cen, int total, int d, double* d_m2)
+{
+    hipLaunchKernelGGL(k_cut_cen_norms, GRID1(total), 0, c->stream, d_cen, total, d, d_m2);
+    KCHECK(c);
+    return SD_OK;
+}
+int launch_assign_cuts(sd_ctx* c, const double* E, int64_t M, int d, const double* d_cen, const double* d_m2, const int* d_coff, const int* d_slot, int Tn,
+                       const int* d_nact, int* d_hard, double* d_best, int* d_err)
+{
+    hipLaunchKernelGGL(k_assign_cuts, dim3((unsigned)M), dim3(64), 0, c->stream, E, M, d, d_cen, d_m2, d_coff, d_slot, Tn, d_nact, d_hard, d_best, d_err);
+    KCHECK(c);
+    return SD_OK;
+}
+int launch_activations_cuts(sd_ctx* c, const float* d_seg, const int* d_hard, const int* d_sfr, int64_t chunks, const int* d_koff, int Tg, int64_t sumK,
+                            double* d_act, int64_t nact)
+{
+    hipLaunchKernelGGL(k_activations_cuts, dim3((unsigned)((nact * sumK + 255) / 256)), dim3(256), 0, c->stream, d_seg, d_hard, d_sfr, chunks, d_koff, Tg, d_act, nact);
+    KCHECK(c);
+    return SD_OK;
+}
+int launch_topk_cuts(sd_ctx* c, const double* d_act, const int32_t* d_count, int64_t ar0, int64_t cr0, int64_t rows, int64_t crow, const int* d_koff, int Tg,
+                     int64_t nact, uint8_t* d_binary)
+{
+    hipLaunchKernelGGL(k_topk_cuts, dim3((unsigned)((rows * Tg + 255) / 256)), dim3(256), 0, c->stream, d_act, d_count, ar0, cr0, rows, crow, d_koff, Tg, nact, d_binary);
+    KCHECK(c);
+    return SD_OK;
+}
+
 // ---------------------------------------------------------------- open
 int cut_refusal(sd_ctx* c, const char* who)
 {
@@ -260,12 +289,10 @@ int cut_group(sd_cut* k, std::vector<CutJob>& jobs, size_t g0, size_t g1, JobRes
         HIPCHK(c, hipMemcpyAsync(d_coff, coff.data(), (size_t)(Tn + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(d_slot, nontriv.data(), (size_t)Tn * sizeof(int), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemsetAsync(d_err, 0, sizeof(int), c->stream));
-        hipLaunchKernelGGL(k_cut_cen_norms, GRID1(total), 0, c->stream, d_cen, total, d, d_m2);
-        KCHECK(c);
+        if ((rc = launch_cut_cen_norms(c, d_cen, total, d, d_m2))) return rc;
         {
             ProfScope ps(c, "assign_cuts", 2.0 * (double)M * total * d, (double)M * d * 8.0 + (double)total * d * 8.0);
-            hipLaunchKernelGGL(k_assign_cuts, dim3((unsigned)M), dim3(64), 0, c->stream, e64, M, d, d_cen, d_m2, d_coff, d_slot, Tn, k->nact.as<int>(), d_hard, d_best, d_err);
-            KCHECK(c);
+            if ((rc = launch_assign_cuts(c, e64, M, d, d_cen, d_m2, d_coff, d_slot, Tn, k->nact.as<int>(), d_hard, d_best, d_err))) return rc;
         }
         int herr = 0;
         for (int q = 0; q < Tn; ++q) {
@@ -326,9 +353,7 @@ int cut_group(sd_cut* k, std::vector<CutJob>& jobs, size_t g0, size_t g1, JobRes
     HIPCHK(c, hipMemcpyAsync(d_koff, koff.data(), (size_t)(Tg + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     {
         ProfScope ps(c, "activations_cuts", 0, (double)chunks * SD_FRAMES * 3 * 4.0 + (double)nact * sumK * 8.0);
-        hipLaunchKernelGGL(k_activations_cuts, dim3((unsigned)((nact * sumK + 255) / 256)), dim3(256), 0, c->stream, k->seg.as<float>(), d_hard, k->sfr.as<int>(), chunks,
-                           d_koff, Tg, d_act, nact);
-        KCHECK(c);
+        if ((rc = launch_activations_cuts(c, k->seg.as<float>(), d_hard, k->sfr.as<int>(), chunks, d_koff, Tg, sumK, d_act, nact))) return rc;
     }
     if (rows <= 0) { HIPCHK(c, hipStreamSynchronize(c->stream)); return SD_OK; }    // reference would index an empty vector here (sd.cpp:2735)
     int64_t crow = g.crow_all;
@@ -336,9 +361,7 @@ int cut_group(sd_cut* k, std::vector<CutJob>& jobs, size_t g0, size_t g1, JobRes
     WS(c, uint8_t, d_binary, "cut_binary", (size_t)rows * sumK);
     {
         ProfScope ps(c, "topk_cuts", 0, (double)rows * sumK * 9.0);
-        hipLaunchKernelGGL(k_topk_cuts, dim3((unsigned)((rows * Tg + 255) / 256)), dim3(256), 0, c->stream, d_act, k->count.as<int32_t>(), g.ar0, g.cr0, rows, crow,
-                           d_koff, Tg, nact, d_binary);
-        KCHECK(c);
+        if ((rc = launch_topk_cuts(c, d_act, k->count.as<int32_t>(), g.ar0, g.cr0, rows, crow, d_koff, Tg, nact, d_binary))) return rc;
     }
     std::vector<uint8_t> binary((size_t)rows * sumK);
     HIPCHK(c, hipMemcpyAsync(binary.data(), d_binary, binary.size(), hipMemcpyDeviceToHost, c->stream));

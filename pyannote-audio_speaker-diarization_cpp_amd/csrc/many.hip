@@ -184,8 +184,7 @@ static int dendrograms_ahead(sd_ctx* c, const std::vector<FinalJob>& jobs, std::
         const FinalJob& q = jobs[j];
         if (q.chunks <= 0) continue;
         const int64_t M = q.chunks * SD_SPEAKERS;
-        hipLaunchKernelGGL(k_f32_to_f64, GRID1(M * d), 0, c->stream, q.emb, d_e64, M * d);
-        KCHECK(c);
+        if ((rc = launch_f32_to_f64(c, q.emb, d_e64, M * d))) return rc;
         if ((rc = train_rows(c, d_e64, M, d, tidx[j]))) return rc;
         const int64_t N = (int64_t)tidx[j].size();
         if (!linkage_job_batched(route, N) || resolve_num_clusters(spec, N).trivial) continue;

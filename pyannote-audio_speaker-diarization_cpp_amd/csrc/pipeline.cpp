@@ -26,6 +26,20 @@ __global__ void k_mark_inactive(int* __restrict__ hard, const int* __restrict__ 
     if (i < n && nact[i] == 0) hard[i] = -2;                                  // sd.cpp:3172-3191
 }
 
+// the launches of the two kernels above (finalize_front / finalize, many.hip, the test hooks); asynchronous on c->stream
+int launch_f32_to_f64(sd_ctx* c, const float* d_a, double* d_b, int64_t n)
+{
+    hipLaunchKernelGGL(k_f32_to_f64, GRID1(n), 0, c->stream, d_a, d_b, n);
+    KCHECK(c);
+    return SD_OK;
+}
+int launch_mark_inactive(sd_ctx* c, int* d_hard, const int* d_nact, int64_t n)
+{
+    hipLaunchKernelGGL(k_mark_inactive, GRID1(n), 0, c->stream, d_hard, d_nact, n);
+    KCHECK(c);
+    return SD_OK;
+}
+
 // planted workload (sd_set_planted): rows that are not NaN by the reference's rule take the planted embedding.
 // One 192-thread block per row: every thread reads element 0 before anyone overwrites it.
 __global__ void k_plant_emb(float* __restrict__ emb, const float* __restrict__ planted)
@@ -323,9 +337,7 @@ int finalize_front(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t ch
     int rc;
     if ((rc = run_postseg(c, d_seg, chunks, d_bin, nullptr, d_nact))) return rc;
     if ((rc = run_count(c, d_bin, chunks, d_count, count_frames_host(chunks), d_count_avg))) return rc;
-    hipLaunchKernelGGL(k_f32_to_f64, GRID1(M * SD_EMB_DIM), 0, c->stream, d_emb, d_e64, M * SD_EMB_DIM);
-    KCHECK(c);
-    return SD_OK;
+    return launch_f32_to_f64(c, d_emb, d_e64, M * SD_EMB_DIM);
 }
 
 int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, std::vector<sd_turn>& v)
@@ -347,8 +359,7 @@ int finalize(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, 
     std::vector<double> soft_best;
     if ((rc = run_clustering(c, d_e64, M, SD_EMB_DIM, hard, &K, c->num_clusters, c->min_clusters, c->max_clusters, &soft_best))) return rc;
     HIPCHK(c, hipMemcpyAsync(d_hard, hard.data(), (size_t)M * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_mark_inactive, GRID1(M), 0, c->stream, d_hard, d_nact, M);
-    KCHECK(c);
+    if ((rc = launch_mark_inactive(c, d_hard, d_nact, M))) return rc;
     HIPCHK(c, hipMemcpyAsync(hard.data(), d_hard, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int Kr = 0;

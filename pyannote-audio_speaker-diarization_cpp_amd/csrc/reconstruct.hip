@@ -35,6 +35,20 @@ __global__ void k_topk(const double* __restrict__ act, const int32_t* __restrict
     topk_row(act + (ar0 + i) * K, binary + i * K, K, i < crow ? count[cr0 + i] : 0);
 }
 
+// the launches of the two kernels (run_reconstruct, the test hooks); asynchronous on c->stream
+int launch_activations(sd_ctx* c, const float* d_seg, const int* d_hard, const int* d_sfr, int64_t chunks, int K, double* d_act, int64_t nact)
+{
+    hipLaunchKernelGGL(k_activations, dim3((unsigned)((nact * K + 255) / 256)), dim3(256), 0, c->stream, d_seg, d_hard, d_sfr, chunks, K, d_act, nact);
+    KCHECK(c);
+    return SD_OK;
+}
+int launch_topk(sd_ctx* c, const double* d_act, const int32_t* d_count, int64_t ar0, int64_t cr0, int64_t rows, int64_t crow, int K, uint8_t* d_binary)
+{
+    hipLaunchKernelGGL(k_topk, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, d_act, d_count, ar0, cr0, rows, crow, K, d_binary);
+    KCHECK(c);
+    return SD_OK;
+}
+
 // SlidingWindow::operator[] (sd.cpp:1092-1115): walks from 0.0, may bail out on short audio
 static double sw_index_start(double step, double dur, int64_t num_samples, int pos)
 {
@@ -151,8 +165,7 @@ int run_reconstruct(sd_ctx* c, const float* d_seg, const int* /*d_nact*/, const 
     HIPCHK(c, hipStreamSynchronize(c->stream));
     {
         ProfScope ps(c, "activations", 0, (double)chunks * SD_FRAMES * 3 * 4.0 + (double)nact * K * 8.0);
-        hipLaunchKernelGGL(k_activations, dim3((unsigned)((nact * K + 255) / 256)), dim3(256), 0, c->stream, d_seg, d_hard, d_sfr, chunks, K, d_act, nact);
-        KCHECK(c);
+        if (int rc = launch_activations(c, d_seg, d_hard, d_sfr, chunks, K, d_act, nact)) return rc;
     }
     int64_t crow = g.crow_all;
     if (rows <= 0) return SD_OK;                      // reference would index an empty vector here (sd.cpp:2735)
@@ -161,8 +174,7 @@ int run_reconstruct(sd_ctx* c, const float* d_seg, const int* /*d_nact*/, const 
     WS(c, uint8_t, d_binary, "rc_binary", rows * K);
     {
         ProfScope ps(c, "topk", 0, (double)rows * K * 9.0);
-        hipLaunchKernelGGL(k_topk, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, d_act, d_count, ar0, cr0, rows, crow, K, d_binary);
-        KCHECK(c);
+        if (int rc = launch_topk(c, d_act, d_count, ar0, cr0, rows, crow, K, d_binary)) return rc;
     }
     std::vector<uint8_t> binary((size_t)rows * K);
     HIPCHK(c, hipMemcpyAsync(binary.data(), d_binary, binary.size(), hipMemcpyDeviceToHost, c->stream));

@@ -41,6 +41,8 @@ CONV_SLACK_ROWS = 256      # guard rows behind the buffers of Diarizer.conv_case
 SEG_SLACK_ROWS = 256       # ... and behind those of Diarizer.lstm_rec_case / pool_norm_case / chunk_norm_case / classifier_case
 GLUE_SLACK_ROWS = 256      # ... and behind those of Diarizer.ecapa_stats_case / se_apply_case / scatter_emb_case / to_half_case
 ROWTAB_SLACK = 128         # slack entries behind the table of Diarizer.rowtab_case
+BE_SLACK = 256             # slack units behind every array of the Diarizer.*_case methods of the back end (binarize_case .. mark_inactive_case)
+BE_BCANARY = 0xA5          # SD_TEST_BCANARY: what their byte outputs are preset to
 FE_SLACK = 256             # slack entries (feature rows) behind every array of Diarizer.frontend_prepare_case / frontend_features_case / frontend_signals_case
 
 
@@ -67,6 +69,8 @@ EXPORTS = [
     "sd_test_lstm_rec", "sd_test_pool_norm", "sd_test_chunk_norm", "sd_test_classifier",
     "sd_test_ecapa_stats", "sd_test_se_apply", "sd_test_rowtab", "sd_test_scatter_emb", "sd_test_to_half",
     "sd_test_frontend_prepare", "sd_test_frontend_features", "sd_test_frontend_signals",
+    "sd_test_binarize", "sd_test_count", "sd_test_gather_normalize", "sd_test_cluster_means", "sd_test_assign", "sd_test_constrained_argmax",
+    "sd_test_activations", "sd_test_topk", "sd_test_assign_cuts", "sd_test_recon_cuts", "sd_test_pcm_to_f32", "sd_test_f32_to_f64", "sd_test_mark_inactive",
     "sd_activity_scores", "sd_activity_regions", "sd_activity", "sd_activity_dev", "sd_activity_f32", "sd_activity_wav", "sd_last_activity_scores",
     "sd_stream_open", "sd_stream_push", "sd_stream_push_dev", "sd_stream_push_f32", "sd_stream_turns", "sd_stream_info", "sd_stream_read",
     "sd_stream_close", "sd_stream_sealed_chunks", "sd_stream_forget", "sd_stream_set_window", "sd_stream_origin",
@@ -262,6 +266,19 @@ def lib():
     L.sd_test_frontend_prepare.argtypes = [vp, vp, i64, i64, C.c_int, i32, C.c_float] + [vp] * 11
     L.sd_test_frontend_features.argtypes = [vp, vp, i64, i64, i64, i64, vp, i64, C.c_int, C.c_float, vp, i64, vp, vp, vp]
     L.sd_test_frontend_signals.argtypes = [vp, vp, vp, i64, C.c_int, i32, C.c_float, vp, vp, vp, i64, vp, vp]
+    L.sd_test_binarize.argtypes = [vp, vp, i64, C.c_float, i32, vp, vp, vp]
+    L.sd_test_count.argtypes = [vp, vp, i64, C.c_float, i32, vp, vp]
+    L.sd_test_gather_normalize.argtypes = [vp, vp, i64, vp, i64, C.c_int, C.c_float, vp, vp]
+    L.sd_test_cluster_means.argtypes = [vp, vp, i64, C.c_int, vp, vp, C.c_int, C.c_float, vp]
+    L.sd_test_assign.argtypes = [vp, vp, i64, C.c_int, vp, C.c_int, C.c_float, i32, vp, vp, vp, vp]
+    L.sd_test_constrained_argmax.argtypes = [vp, vp, i64, C.c_int, dbl, i32, vp]
+    L.sd_test_activations.argtypes = [vp, vp, vp, i64, C.c_int, C.c_float, vp, i64, vp]
+    L.sd_test_topk.argtypes = [vp, vp, i64, vp, i64, i64, i64, i64, i64, C.c_int, vp]
+    L.sd_test_assign_cuts.argtypes = [vp, vp, i64, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, C.c_float, i32, vp, vp, vp, vp]
+    L.sd_test_recon_cuts.argtypes = [vp, vp, vp, i64, vp, C.c_int, vp, vp, i64, i64, i64, i64, i64, C.c_float, vp, i64, vp, vp]
+    L.sd_test_pcm_to_f32.argtypes = [vp, vp, i64, C.c_float, vp]
+    L.sd_test_f32_to_f64.argtypes = [vp, vp, i64, C.c_float, vp]
+    L.sd_test_mark_inactive.argtypes = [vp, vp, vp, i64, i32, vp]
     L.sd_test_emb_batches.restype = i64
     L.sd_test_emb_batches.argtypes = [vp, i64, i64, C.c_int, C.c_int, vp, i64]
     _lib = L
@@ -1581,6 +1598,146 @@ class Diarizer:
         self._chk(lib().sd_test_frontend_signals(self._h, _ptr(signals), _ptr(wav_lens), B, int(bool(skip_dead_rows)), int(icanary), canary, _ptr(prefix),
                                                  _ptr(counts), _ptr(feats), feats.shape[0], _ptr(rowoff), _ptr(info)))
         return feats, rowoff, dict(zip(("n_active", "rows_all", "grid", "num_cu"), (int(v) for v in info))), prefix, counts
+
+    # ---- the kernels behind the two networks alone (sdhip_test.h); every array comes back WHOLE, its BE_SLACK units included
+    def binarize_case(self, seg, want=("bin", "masks", "nact"), fcanary=-7776.0, icanary=-7776):
+        """sd_test_binarize: seg [chunks][293][3] -> dict of the arrays in `want`: bin [(chunks + BE_SLACK)][293][3] uint8, masks [(chunks + BE_SLACK) * 3][293],
+        nact [(chunks + BE_SLACK) * 3]"""
+        seg = np.ascontiguousarray(seg, np.float32)
+        ck = seg.shape[0]
+        assert seg.shape == (ck, 293, 3)
+        out = {}
+        if "bin" in want:
+            out["bin"] = np.zeros((ck + BE_SLACK, 293, 3), np.uint8)
+        if "masks" in want:
+            out["masks"] = np.zeros(((ck + BE_SLACK) * 3, 293), np.float32)
+        if "nact" in want:
+            out["nact"] = np.zeros((ck + BE_SLACK) * 3, np.int32)
+        p = lambda k: _ptr(out[k]) if k in out else None
+        self._chk(lib().sd_test_binarize(self._h, _ptr(seg), ck, fcanary, icanary, p("bin"), p("masks"), p("nact")))
+        return out
+
+    def count_case(self, binarized, want_avg=True, fcanary=-7776.0, icanary=-7776):
+        """sd_test_count: binarized [chunks][293][3] uint8 -> count [frames + BE_SLACK] int32, avg (or None) [frames + BE_SLACK] float64"""
+        b = np.ascontiguousarray(binarized, np.uint8)
+        ck = b.shape[0]
+        assert b.shape == (ck, 293, 3)
+        nf = int(lib().sd_count_frames(ck))
+        cnt = np.zeros(nf + BE_SLACK, np.int32)
+        avg = np.zeros(nf + BE_SLACK, np.float64) if want_avg else None
+        self._chk(lib().sd_test_count(self._h, _ptr(b), ck, fcanary, icanary, _ptr(cnt), _ptr(avg) if want_avg else None))
+        return cnt, avg
+
+    def gather_normalize_case(self, X, tidx, want_xout=True, fcanary=-7776.0):
+        """sd_test_gather_normalize: X [rows][d] float64, tidx [N] -> xout (or None), xn [N + BE_SLACK][d]"""
+        X, tidx = np.ascontiguousarray(X, np.float64), np.ascontiguousarray(tidx, np.int32)
+        rows, d = X.shape
+        N = len(tidx)
+        xn = np.zeros((N + BE_SLACK, d), np.float64)
+        xo = np.zeros((N + BE_SLACK, d), np.float64) if want_xout else None
+        self._chk(lib().sd_test_gather_normalize(self._h, _ptr(X), rows, _ptr(tidx), N, d, fcanary, _ptr(xo) if want_xout else None, _ptr(xn)))
+        return xo, xn
+
+    def cluster_means_case(self, X, order, off, fcanary=-7776.0):
+        """sd_test_cluster_means: X [rows][d] float64, order [off[-1]], off [nl + 1] -> cen [nl + BE_SLACK][d]"""
+        X, order, off = np.ascontiguousarray(X, np.float64), np.ascontiguousarray(order, np.int32), np.ascontiguousarray(off, np.int32)
+        rows, d = X.shape
+        nl = len(off) - 1
+        assert len(order) == off[-1]
+        cen = np.zeros((nl + BE_SLACK, d), np.float64)
+        self._chk(lib().sd_test_cluster_means(self._h, _ptr(X), rows, d, _ptr(order), _ptr(off), nl, fcanary, _ptr(cen)))
+        return cen
+
+    def assign_case(self, E, cen, want_soft=True, want_best=True, fcanary=-7776.0, icanary=-7776):
+        """sd_test_assign: E [M][d], cen [K][d] float64 -> hard [M + BE_SLACK], err [1 + BE_SLACK], soft [M + BE_SLACK][K] or None, best [M + BE_SLACK] or None"""
+        E, cen = np.ascontiguousarray(E, np.float64), np.ascontiguousarray(cen, np.float64)
+        (M, d), K = E.shape, cen.shape[0]
+        assert cen.shape == (K, d)
+        hard, err = np.zeros(M + BE_SLACK, np.int32), np.zeros(1 + BE_SLACK, np.int32)
+        soft = np.zeros((M + BE_SLACK, K), np.float64) if want_soft else None
+        best = np.zeros(M + BE_SLACK, np.float64) if want_best else None
+        self._chk(lib().sd_test_assign(self._h, _ptr(E), M, d, _ptr(cen), K, fcanary, icanary, _ptr(hard), _ptr(err), _ptr(soft) if want_soft else None,
+                                       _ptr(best) if want_best else None))
+        return hard, err, soft, best
+
+    def constrained_argmax_case(self, soft, fill, icanary=-7776):
+        """sd_test_constrained_argmax: soft [chunks][3][K] float64, fill = what NaN scores become -> hard [(chunks + BE_SLACK)][3]"""
+        soft = np.ascontiguousarray(soft, np.float64)
+        ck, S, K = soft.shape
+        assert S == 3
+        hard = np.zeros((ck + BE_SLACK, 3), np.int32)
+        self._chk(lib().sd_test_constrained_argmax(self._h, _ptr(soft), ck, K, float(fill), icanary, _ptr(hard)))
+        return hard
+
+    def activations_case(self, seg, hard, K, nact, fcanary=-7776.0):
+        """sd_test_activations: seg [chunks][293][3] float32, hard [chunks][3], nact = the frames the caller expects -> act [nact + BE_SLACK][K]"""
+        seg, hard = np.ascontiguousarray(seg, np.float32), np.ascontiguousarray(hard, np.int32)
+        ck = seg.shape[0]
+        assert seg.shape == (ck, 293, 3) and hard.shape == (ck, 3)
+        act, n = np.zeros((int(nact) + BE_SLACK, K), np.float64), C.c_int64(0)
+        self._chk(lib().sd_test_activations(self._h, _ptr(seg), _ptr(hard), ck, K, fcanary, _ptr(act), act.size, C.byref(n)))
+        assert n.value == nact
+        return act
+
+    def topk_case(self, act, count, ar0, cr0, rows, crow):
+        """sd_test_topk: act [act_rows][K] float64, count [n_count] int32 -> binary [rows + BE_SLACK][K] uint8 (slack: BE_BCANARY)"""
+        act, count = np.ascontiguousarray(act, np.float64), np.ascontiguousarray(count, np.int32)
+        ar, K = act.shape
+        out = np.zeros((max(int(rows), 0) + BE_SLACK, K), np.uint8)
+        self._chk(lib().sd_test_topk(self._h, _ptr(act), ar, _ptr(count) if len(count) else None, len(count), int(ar0), int(cr0), int(rows), int(crow), K, _ptr(out)))
+        return out
+
+    def assign_cuts_case(self, E, cen, coff, slot, n_slots, nact, fcanary=-7776.0, icanary=-7776):
+        """sd_test_assign_cuts: E [M][d], cen [coff[-1]][d], coff [Tn + 1], slot [Tn], nact [M] -> m2 [coff[-1] + BE_SLACK], hard [n_slots * M + BE_SLACK],
+        best [Tn * M + BE_SLACK], err [1 + BE_SLACK]"""
+        E, cen = np.ascontiguousarray(E, np.float64), np.ascontiguousarray(cen, np.float64)
+        coff, slot, nact = (np.ascontiguousarray(a, np.int32) for a in (coff, slot, nact))
+        (M, d), Tn = E.shape, len(slot)
+        assert cen.shape == (coff[-1], d) and len(coff) == Tn + 1 and len(nact) == M
+        m2, hard = np.zeros(int(coff[-1]) + BE_SLACK, np.float64), np.zeros(n_slots * M + BE_SLACK, np.int32)
+        best, err = np.zeros(Tn * M + BE_SLACK, np.float64), np.zeros(1 + BE_SLACK, np.int32)
+        self._chk(lib().sd_test_assign_cuts(self._h, _ptr(E), M, d, _ptr(cen), _ptr(coff), _ptr(slot), Tn, int(n_slots), _ptr(nact), fcanary, icanary,
+                                            _ptr(m2), _ptr(hard), _ptr(best), _ptr(err)))
+        return m2, hard, best, err
+
+    def recon_cuts_case(self, seg, hard, koff, nact, count, ar0, cr0, rows, crow, act_in=None, fcanary=-7776.0):
+        """sd_test_recon_cuts: seg [chunks][293][3], hard [Tg][chunks * 3], koff [Tg + 1], nact = the frames the caller expects, count [n_count] ->
+        act [nact * koff[-1] + BE_SLACK] float64, binary [rows * koff[-1] + BE_SLACK] uint8; act_in: the table k_topk_cuts reads instead of act"""
+        seg, hard = np.ascontiguousarray(seg, np.float32), np.ascontiguousarray(hard, np.int32)
+        koff, count = np.ascontiguousarray(koff, np.int32), np.ascontiguousarray(count, np.int32)
+        ck, Tg, sumK = seg.shape[0], len(koff) - 1, int(koff[-1])
+        assert seg.shape == (ck, 293, 3) and hard.shape == (Tg, ck * 3)
+        act, binary, n = np.zeros(int(nact) * sumK + BE_SLACK, np.float64), np.zeros(max(int(rows), 0) * sumK + BE_SLACK, np.uint8), C.c_int64(0)
+        if act_in is not None:
+            act_in = np.ascontiguousarray(act_in, np.float64)
+            assert act_in.size == int(nact) * sumK
+        self._chk(lib().sd_test_recon_cuts(self._h, _ptr(seg), _ptr(hard), ck, _ptr(koff), Tg, _ptr(act_in) if act_in is not None else None,
+                                           _ptr(count) if len(count) else None, len(count), int(ar0), int(cr0), int(rows), int(crow), fcanary, _ptr(act), act.size,
+                                           _ptr(binary), C.byref(n)))
+        assert n.value == nact
+        return act, binary
+
+    def pcm_to_f32_case(self, pcm, fcanary=-7776.0):
+        """sd_test_pcm_to_f32: pcm [n] int16 -> [n + 512 + BE_SLACK] float32: the samples, SD_WAV_PAD zeros, the canary"""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        out = np.zeros(len(pcm) + 512 + BE_SLACK, np.float32)
+        self._chk(lib().sd_test_pcm_to_f32(self._h, _ptr(pcm), len(pcm), fcanary, _ptr(out)))
+        return out
+
+    def f32_to_f64_case(self, a, fcanary=-7776.0):
+        """sd_test_f32_to_f64: a [n] float32 -> [n + BE_SLACK] float64"""
+        a = np.ascontiguousarray(a, np.float32)
+        out = np.zeros(len(a) + BE_SLACK, np.float64)
+        self._chk(lib().sd_test_f32_to_f64(self._h, _ptr(a), len(a), fcanary, _ptr(out)))
+        return out
+
+    def mark_inactive_case(self, hard, nact, icanary=-7776):
+        """sd_test_mark_inactive: hard [n], nact [n] int32 -> [n + BE_SLACK] int32"""
+        hard, nact = np.ascontiguousarray(hard, np.int32), np.ascontiguousarray(nact, np.int32)
+        assert hard.shape == nact.shape and hard.ndim == 1
+        out = np.zeros(len(hard) + BE_SLACK, np.int32)
+        self._chk(lib().sd_test_mark_inactive(self._h, _ptr(hard), _ptr(nact), len(hard), icanary, _ptr(out)))
+        return out
 
     def read_ws(self, name, dtype, count, offset=0):
         """test hook: `count` elements of the named device workspace"""

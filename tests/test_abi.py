@@ -27,7 +27,10 @@ def test_library_loads_and_exports_every_declared_symbol_without_lab_hooks():
     assert decl["sdhip_test.h"] == {"sd_set_planted", "sd_kernel_stats", "sd_reset_stats", "sd_bench_conv", "sd_debug_read_ws", "sd_test_pack_split_weights", "sd_test_conv", "sd_test_emb_batches",
                                     "sd_test_lstm_rec", "sd_test_pool_norm", "sd_test_chunk_norm", "sd_test_classifier",
                                     "sd_test_ecapa_stats", "sd_test_se_apply", "sd_test_rowtab", "sd_test_scatter_emb", "sd_test_to_half",
-                                    "sd_test_frontend_prepare", "sd_test_frontend_features", "sd_test_frontend_signals"}
+                                    "sd_test_frontend_prepare", "sd_test_frontend_features", "sd_test_frontend_signals",
+                                    "sd_test_binarize", "sd_test_count", "sd_test_gather_normalize", "sd_test_cluster_means", "sd_test_assign",
+                                    "sd_test_constrained_argmax", "sd_test_activations", "sd_test_topk", "sd_test_assign_cuts", "sd_test_recon_cuts",
+                                    "sd_test_pcm_to_f32", "sd_test_f32_to_f64", "sd_test_mark_inactive"}
     # the lab hooks of the linkage / barrier measurements are out of the product library, not just out of the header
     for name in ("sd_bench_barrier", "sd_bench_linkage_parts"):
         assert not hasattr(L, name), name
