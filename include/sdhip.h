@@ -128,7 +128,8 @@ int sd_cluster_ex(sd_ctx*, const double* h_X, int64_t N, int d, int method, int 
 /* ---- a12 for J independent jobs in one call: the batch form of sd_linkage_ex.  h_X holds the rows of all jobs, job after job (N[j] rows of d each),
  * h_Z the dendrograms in the same order, max(N[j] - 1, 0) rows of 4 each.  Z of job j is, byte for byte, what sd_linkage_ex gives for job j alone,
  * whatever else is in the call and in whatever order, for every N: the jobs that sd_linkage_ex runs on one workgroup (N < 1500) share launches,
- * one workgroup per job, the others take sd_linkage_ex's own route.  N[j] of 0 or 1 is legal: no rows, status SD_OK.  A job with a zero-norm row
+ * one workgroup per job and, under "linkage_batch_xcd", the jobs of the one-XCD cooperative class, eight to a launch; the others take sd_linkage_ex's
+ * own route.  N[j] of 0 or 1 is legal: no rows, status SD_OK.  A job with a zero-norm row
  * under the cosine metric gets status[j] = SD_ERR_NUMERIC and its rows of h_Z are left as they were; the others finish and the call returns SD_OK.
  * SD_ERR_ARG before anything is written: a null pointer, J < 1, a negative N[j], d <= 0, more than 2^31 - 1 rows in all, an unknown method or
  * metric, centroid / median / ward with the cosine metric. */
@@ -615,6 +616,12 @@ int sd_stage_ms(const sd_ctx*, double* ms4);
  *   "max_num_embeddings" <= 1499): 64 streams at 1 min update in 31 ms instead of 106.  Off by default because jobs of 1500 train rows and more
  *   -- a stream from about 10 minutes on -- take sd_linkage_ex's own route either way and gain nothing (README, "batched small-N linkage").  "linkage_batch_bytes" (>= 1, default 2 GiB): the device bytes the workspaces of one such group of jobs may take, here and
  *   in sd_linkage_many; more jobs than fit run in several groups, and results do not depend on the grouping.
+ * "linkage_batch_xcd" (0 (default) / 1; anything else SD_ERR_ARG): 1 = sd_linkage_many -- and with it, under "linkage_batch" = 1, the group calls -- runs
+ *   the jobs that sd_linkage_ex gives to its cooperative kernel on one XCD (1500 .. 15 999 rows on a device of 256 CUs; at least two in the call, each
+ *   within "linkage_batch_bytes": 8 N^2 bytes and a little) eight to a launch, one job per XCD, after a shared preparation.  A job that meets an exact tie
+ *   there, or whose launch is refused or times out, is run again alone; results are the same bytes either way.  0 = every call launches what it launched
+ *   before the key existed.  Measured: 8 .. 64 jobs of 1 500 .. 8 000 rows 5.2 - 6.4 x the loop of sd_linkage_ex.  Off by default because jobs with duplicate rows
+ *   -- every stream of the synthetic workload -- tie at height 0, are redone alone and gain nothing (README, "Mid-size linkage jobs, one per XCD").
  * Test and tuning keys are listed in sdhip_test.h.  An unknown key returns SD_ERR_ARG. */
 int sd_set_option(sd_ctx*, const char* key, int64_t value);
 /* the real-valued keys: "clustering_threshold" (Clustering.py:251-276 / 317-333; outside [0, 2] or NaN: SD_ERR_ARG) and the four "activity_*" keys of

@@ -39,8 +39,7 @@ __global__ __launch_bounds__(256) void k_pdist(const double* __restrict__ X, int
         }
 }
 
-// the same distances as the full N x N square (k_linkage_mw<*, true>): tile (ti, tj), ti <= tj, is computed once and written twice, the
-// mirror through an LDS transpose so that both writes are row-contiguous.  D[i][j] and D[j][i] are the same bits; the diagonal is 0.
+// the same distances as the full N x N square (k_linkage_mw<*, true>, k_linkage_rg): linkage_dev.h's pdist_sq_tile, which k_pdist_sq_jobs (linkage_batch.hip) calls too
 template <bool COS>
 __global__ __launch_bounds__(256) void k_pdist_sq(const double* __restrict__ X, int64_t N, int d, double* __restrict__ D, int* __restrict__ err)
 {
@@ -48,45 +47,16 @@ __global__ __launch_bounds__(256) void k_pdist_sq(const double* __restrict__ X, 
     if (tj < ti) return;
     __shared__ double Xi[PT][33], Xj[PT][33];
     __shared__ double Tt[PT][PT + 1];
-    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    double acc[4][4], ma[4], mb[4];
-    pdist_tile<COS>(X, N, d, ti, tj, Xi, Xj, acc, ma, mb);
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int li = ty + 16 * u, lj = tx + 16 * v;
-            const int64_t i = (int64_t)ti * PT + li, j = (int64_t)tj * PT + lj;
-            double dv;
-            if constexpr (COS) {
-                dv = 0.0;
-                if (i != j && i < N && j < N) {
-                    bool zero_norm = false;
-                    dv = pdist_value<true>(acc[u][v], ma[u], mb[v], &zero_norm);
-                    if (zero_norm) *err = 1;
-                }
-            } else dv = (i == j) ? 0.0 : pdist_value<false>(acc[u][v], ma[u], mb[v], nullptr);
-            Tt[li][lj] = dv;
-            if (i < N && j < N && (ti != tj || i <= j)) D[(size_t)i * N + j] = dv;
-        }
-    __syncthreads();
-    for (int e = tid; e < PT * PT; e += 256) {
-        const int lj = e >> 6, li = e & 63;                 // consecutive threads: consecutive i = consecutive addresses of row j
-        const int64_t i = (int64_t)ti * PT + li, j = (int64_t)tj * PT + lj;
-        if (i < N && j < N && i < j) D[(size_t)j * N + i] = Tt[li][lj];
-    }
+    pdist_sq_tile<COS>(X, N, d, ti, tj, D, err, Xi, Xj, Tt);
 }
 
+// exact nearest neighbour, bound and second bound above each row: a wave per row (row_min2, linkage_dev.h)
 __global__ __launch_bounds__(256) void k_row_nn(const double* __restrict__ D, int64_t n, int* __restrict__ nb, double* __restrict__ md, double* __restrict__ md2, int square)
 {
     const int lane = threadIdx.x & 63;
     const int64_t x = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (x >= n - 1) return;
-    const double* row = D + (square ? x * n + x + 1 : cidx(n, x, x + 1));
-    const int64_t cnt = n - 1 - x;
-    Min2 m; m.v = INFINITY; m.i = -1; m.v2 = INFINITY;
-    for (int64_t t = lane; t < cnt; t += 64) min2_acc(m, row[t], (int)(x + 1 + t));
-    m = wave_min2(m);
+    const Min2 m = row_min2(D + (square ? x * n + x + 1 : cidx(n, x, x + 1)), n - 1 - x, x);
     if (lane == 0) { nb[x] = m.i; md[x] = (m.i < 0) ? INFINITY : m.v; if (md2) md2[x] = (m.i < 0) ? INFINITY : m.v2; }
 }
 
@@ -132,44 +102,12 @@ struct LinkagePlan {
 static LinkagePlan linkage_plan(const sd_ctx* c, int64_t N, bool square_ok)
 {
     LinkagePlan p = {};
-    // auto geometry (measured on clustered data, profiles/r01_linkage_scaling.txt, r02_linkage_stamps.txt, r03_linkage_*.txt): up to N = 30 000
-    // the one-XCD form with one workgroup on each of the XCD's 32 CUs; above, all XCDs
-    // (r03, square form: one XCD wins up to N ~ 70 000 -- 384 ms against 443 at N = 50 158, 719 against 715 at N = 75 090 -- all XCDs above: 987 ms against 1 064 at
-    // N = 100 174; all XCDs: 64 workgroups up to ~90 000 rows, 128 above)
-    const bool auto_onex = (int)c->linkage_wgs < 0 && c->linkage_one_xcd != 0 && c->num_cu >= 256 && N >= 1500 && N < 70000;
-    int G = linkage_route_wgs(c->linkage_wgs, c->linkage_one_xcd, c->num_cu, N);      // linkage_batch_plan.h: the rule run_linkage_many's planner shares
-    int TH = (int)c->linkage_threads;
-    // measured (r03, square form, N = 12 602, one XCD, three boxes): 32 x 256 75.2 / 82.7 / 76.8 ms, 32 x 512 84.4 / 77.2 / 85.0 ms -- the
-    // boxes disagree, 256 wins on two of three; all XCDs 128 x 512 0.99 s at N = 100 174 (128 x 256: 1.10 s)
-    // one XCD, larger N: 512 threads (N = 18 867: 121 ms against 126; N = 25 274: 170 against 179; N = 50 158: 384 against 465)
-    if (TH <= 0) TH = auto_onex ? (N >= 16000 ? 512 : 256) : N >= 8000 ? 512 : 256;
-    TH = TH >= 1024 ? 1024 : TH >= 512 ? 512 : TH >= 256 ? 256 : 128;      // (not below 128: the kernels fill their G <= 128 candidate slots with `tid < G`)
-    p.G = G; p.TH = TH;
-    if (G <= 1) return p;
-    // square form (full N x N matrix, row-only bulk accesses) while the square fits beside everything else; the condensed form above that
-    const bool square = square_ok && (c->linkage_square < 0 ? (double)N * (double)N * 8.0 <= 170e9 : c->linkage_square != 0);
-    // k_linkage_rg's own automatic geometry (r05, planted embeddings, 256 threads; profiles/r05_linkage_rg.txt): one XCD with 32 workgroups only while a thread
-    // has one or two columns -- N = 12 602: 72.7 ms with 32 (one XCD), 72.6 with 64 (all XCDs); N = 18 867: 127.7 / 120.0; N = 25 274: 179.1 / 165.2 (128: 169.1;
-    // k_linkage_mw 170.2); N = 50 158: 462.8 / 372.8 (128: 366.3; k_linkage_mw 381.8); N = 100 174: 128 workgroups 819 ms (64: 875; k_linkage_mw 996)
-    if (c->linkage_wgs < 0 && square && c->linkage_kernel != 0 && N >= 1500) {
-        G = N < 16000 ? 32 : N < 45000 ? 64 : 128;
-        if (G > c->num_cu) G = c->num_cu;
-    }
-    if ((N + G - 1) / G > 3400) G = (int)((N + 3399) / 3400);      // active-row lists and bounds live in LDS: 32 B per owned row (109 KB + 43 KB static)
-    // one-XCD form while two workgroups per CU of one XCD (32 CUs) can hold the job; above, all XCDs' memory pipelines are worth more
-    const bool onex = c->linkage_one_xcd != 0 && G <= 32 && c->num_cu >= 256;
-    // square form: k_linkage_rg (register state, sizes / ty in the slots) where its geometry fits -- at most 4 columns per thread -- else k_linkage_mw
-    bool use_rg = square && c->linkage_kernel != 0;
-    // measured (r05, planted embeddings): N = 12 602, one XCD, 32 workgroups: 256 threads 72.7 ms, 512 threads 81.2, 128 threads 76.6 (k_linkage_mw 76.7);
-    // N = 100 174, all XCDs, 128 workgroups: 256 threads 819 ms, 512 threads 829 (k_linkage_mw 996); 64 x 512: 875
-    if (use_rg && c->linkage_threads <= 0) TH = 256;
-    if (use_rg && !linkage_rg_fits(N, G, TH)) {
-        int t2 = TH;
-        while (t2 < 1024 && !linkage_rg_fits(N, G, t2)) t2 *= 2;
-        if (linkage_rg_fits(N, G, t2) && (c->linkage_threads <= 0 || c->linkage_kernel > 0)) TH = t2; else use_rg = false;
-    }
-    p.G = G; p.TH = TH; p.cap = (int)((N + G - 1) / G) + 1;
-    p.square = square; p.use_rg = use_rg; p.onex = onex;
+    // the arithmetic is linkage_batch_plan.h's linkage_geometry, which run_linkage_many's planner shares
+    const LinkageGeom g = linkage_geometry(linkage_opts(c), N, square_ok);
+    p.G = g.G; p.TH = g.TH;
+    if (g.G <= 1) return p;
+    const bool square = g.square, use_rg = g.use_rg;
+    p.cap = g.cap; p.square = g.square; p.use_rg = g.use_rg; p.onex = g.onex;
     p.slot_gran = use_rg ? linkage_rg_slot_granules() : linkage_mw_slot_granules();
     if (square && c->linkage_tie_kernel != 0) {
         bool hx_onex = c->linkage_one_xcd != 0 && c->num_cu >= 256 && linkage_hx_fits(N, 31);

@@ -7,6 +7,11 @@
 // The distances and the merges of a job come from the same functions (linkage_dev.h) as on the single path, so its Z is the same bytes whatever else is in the launch.
 // All three read a device table of LinkageDevJob; a job's error slot, raised by k_pdist_jobs for a zero-norm row under the cosine metric, stops the two
 // kernels behind it for that job alone (no linkage kernel ever sees a NaN distance).
+// Under option linkage_batch_xcd the jobs run_linkage would take to the one-XCD form of k_linkage_rg (1500 <= N < 16 000) share launches too:
+//   k_pdist_sq_jobs<COS>         the square matrices of all jobs of a group, blockIdx.z = job; k_pdist_sq's pdist_sq_tile
+//   k_prepare_sq_jobs            ids = iota, nearest neighbour, bound and second bound above each row by k_row_nn's row_min2
+//   k_linkage_rg_jobs<M>         (linkage_rg.hip) up to eight jobs per cooperative launch, job x on the 32 CUs of XCD x: k_linkage_rg's own body
+// A job that meets an exact tie there, or whose launch is refused or times out, goes through run_linkage alone afterwards.
 #include "common.h"
 #include "exact_fp.h"
 #include "linkage_dev.h"
@@ -89,6 +94,37 @@ __global__ __launch_bounds__(T) void k_linkage_heap_jobs(const LinkageDevJob* jo
     heap_linkage<METHOD, T>(jb.D, n, jb.size, jb.cid, jb.nb, jb.md, jb.Z, h, changed, sh, s);
 }
 
+// ---------------------------------------------------------------- the preparation of the jobs that run one per XCD (k_linkage_rg_jobs, linkage_rg.hip)
+// k_pdist_sq_jobs<COS>: k_pdist_sq (linkage.hip) per job, blockIdx.z = job: pdist_sq_tile on the job's own N x N square
+template <bool COS>
+__global__ __launch_bounds__(256) void k_pdist_sq_jobs(const LinkageRgJob* __restrict__ jobs, int d, int* __restrict__ errs)
+{
+    const LinkageRgJob jb = jobs[blockIdx.z];
+    const int64_t N = jb.n;
+    const int tiles = (int)((N + PT - 1) / PT);
+    const int ti = blockIdx.y, tj = blockIdx.x;
+    if (ti >= tiles || tj >= tiles || tj < ti) return;      // beyond this job's own tiles, or below the diagonal
+    __shared__ double Xi[PT][33], Xj[PT][33];
+    __shared__ double Tt[PT][PT + 1];
+    pdist_sq_tile<COS>(jb.X, N, d, ti, tj, jb.D, errs + jb.err, Xi, Xj, Tt);
+}
+
+// k_prepare_sq_jobs: ids = iota and k_row_nn's scan (row_min2) on the square matrix per job: nb, md and md2 are the bits LinkageJob::prepare gives.  Grid as
+// k_prepare_jobs.  (No size array: k_linkage_rg keeps the cluster sizes in registers, 1 each at a fresh start.)
+__global__ __launch_bounds__(256) void k_prepare_sq_jobs(const LinkageRgJob* __restrict__ jobs, const int* __restrict__ errs)
+{
+    const LinkageRgJob jb = jobs[blockIdx.y];
+    const int64_t n = jb.n;
+    if ((int64_t)blockIdx.x * 4 >= n - 1 || errs[jb.err]) return;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < n) jb.cid[t] = (int)t;
+    const int lane = threadIdx.x & 63;
+    const int64_t x = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (x >= n - 1) return;
+    const Min2 m = row_min2(jb.D + x * n + x + 1, n - 1 - x, x);
+    if (lane == 0) { jb.nb[x] = m.i; jb.md[x] = (m.i < 0) ? INFINITY : m.v; jb.md2[x] = (m.i < 0) ? INFINITY : m.v2; }
+}
+
 // ---------------------------------------------------------------- the driver
 // Threads per job: 256.  Measured (tools/linkage_many_times.py, profiles/linkage_many_times.txt; 64 jobs, one per CU): 2.24 ms at N = 100, 16.00 at 400 and
 // 57.81 at 1000 with 256 threads against 2.20 / 16.66 / 58.12 with k_linkage_heap's 1024 -- no difference beyond the spread of the rounds: a merge is bound by
@@ -98,6 +134,7 @@ static int linkage_batch_threads(const sd_ctx* c) { return c->linkage_batch_thre
 
 struct LinkageManyRun {
     sd_ctx* c; const LinkageManyJob* jobs; int d, method, metric; int32_t* status;
+    bool xcd_off = false;       // a slot poll of k_linkage_rg_jobs timed out: no further launch of it in this call
 
     // the single route: run_linkage as it is, Z to the caller's rows.  SD_ERR_NUMERIC is the job's own status
     int single(int64_t j)
@@ -182,7 +219,125 @@ struct LinkageManyRun {
         }
         return SD_OK;
     }
+
+    // XCD-batched jobs xp.order[k0 .. k1) (of one group of the plan, or less), longest first: the preparation in shared launches, then k_linkage_rg_jobs on
+    // every launch of the plan that lies in the range.  A job whose sync block shows neither a timeout nor a tie is done; any other -- an exact tie, a poll
+    // timeout, a refused launch (all its jobs), a launch not made after a timeout -- is run again alone by run_linkage, from its rows, behind the group.
+    // Workspaces that cannot be allocated: the halves, down to single jobs
+    int xcd_group(const LinkageXcdPlan& xp, int64_t k0, int64_t k1)
+    {
+        const int64_t Gn = k1 - k0;
+        const int64_t* ord = xp.order.data() + k0;
+        int64_t nD = 0, nI = 0, nM = 0, nZ = 0, nG = 0;
+        for (int64_t k = 0; k < Gn; ++k) {
+            const int64_t N = jobs[ord[k]].N;
+            nD += N * N; nI += linkage_xcd_ints(N); nM += 2 * N; nZ += (N - 1) * 4; nG += (int64_t)2 * xp.key[(size_t)(k0 + k)].G * linkage_rg_slot_granules();
+        }
+        double* D = ws_get<double>(c, "lx_D", (size_t)nD);
+        int* I = D ? ws_get<int>(c, "lx_int", (size_t)nI) : nullptr;
+        double* M = I ? ws_get<double>(c, "lx_md", (size_t)nM) : nullptr;
+        double* Z = M ? ws_get<double>(c, "lx_Z", (size_t)nZ) : nullptr;
+        MwGran* gran = Z ? ws_get<MwGran>(c, "lx_gran", (size_t)nG) : nullptr;
+        unsigned* sync = gran ? ws_get<unsigned>(c, "lx_sync", (size_t)Gn * SYNC_HOST_WORDS) : nullptr;
+        LinkageRgJob* tab = sync ? ws_get<LinkageRgJob>(c, "lx_tab", (size_t)Gn) : nullptr;
+        int* errs = tab ? ws_get<int>(c, "lx_err", (size_t)Gn) : nullptr;
+        if (!errs) {
+            (void)hipGetLastError();
+            c->stats["linkage_batch_alloc_failed"].launches += 1;
+            if (Gn == 1) return single(ord[0]);
+            if (int rc = xcd_group(xp, k0, k0 + Gn / 2)) return rc;
+            return xcd_group(xp, k0 + Gn / 2, k1);
+        }
+        std::vector<LinkageRgJob> h((size_t)Gn);
+        std::vector<double> hZ((size_t)nZ);
+        std::vector<int> herr((size_t)Gn, 0);
+        std::vector<unsigned> hs((size_t)Gn * SYNC_HOST_WORDS, 0u);
+        std::vector<char> ran((size_t)Gn, 0);
+        int64_t oD = 0, oI = 0, oM = 0, oZ = 0, oG = 0;
+        for (int64_t k = 0; k < Gn; ++k) {
+            const LinkageManyJob& q = jobs[ord[k]];
+            const LinkageXcdKey& key = xp.key[(size_t)(k0 + k)];
+            const int64_t N = q.N, s = linkage_xcd_ints(N) / 2;
+            h[(size_t)k] = LinkageRgJob{q.d_X, D + oD, I + oI, I + oI + s, M + oM, M + oM + N, Z + oZ, gran + oG, sync + k * SYNC_HOST_WORDS,
+                                        (int)N, (int)((N + key.G - 1) / key.G) + 1, (int)k, 0};
+            oD += N * N; oI += 2 * s; oM += 2 * N; oZ += (N - 1) * 4; oG += (int64_t)2 * key.G * linkage_rg_slot_granules();
+        }
+        const int64_t longest = jobs[ord[0]].N;
+        const int tiles = (int)((longest + PT - 1) / PT);
+        HIPCHK(c, hipMemcpyAsync(tab, h.data(), (size_t)Gn * sizeof(LinkageRgJob), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(errs, 0, (size_t)Gn * sizeof(int), c->stream));
+        HIPCHK(c, hipMemsetAsync(gran, 0, (size_t)nG * sizeof(MwGran), c->stream));
+        HIPCHK(c, hipMemsetAsync(sync, 0, (size_t)Gn * SYNC_HOST_WORDS * sizeof(unsigned), c->stream));
+        {
+            ProfScope ps(c, "pdist_sq_jobs", (double)(nD - nM / 2) / 2.0 * d * 3.0, (double)nD * 8.0 + (double)(nM / 2) * d * 8.0);
+            if (metric == SD_METRIC_COSINE) hipLaunchKernelGGL(k_pdist_sq_jobs<true>, dim3(tiles, tiles, (unsigned)Gn), dim3(256), 0, c->stream, tab, d, errs);
+            else hipLaunchKernelGGL(k_pdist_sq_jobs<false>, dim3(tiles, tiles, (unsigned)Gn), dim3(256), 0, c->stream, tab, d, errs);
+            KCHECK(c);
+        }
+        {
+            ProfScope ps(c, "row_nn_sq_jobs", 0, (double)nD * 4.0);
+            hipLaunchKernelGGL(k_prepare_sq_jobs, dim3((unsigned)((longest - 1 + 3) / 4), (unsigned)Gn), dim3(256), 0, c->stream, tab, errs);
+            KCHECK(c);
+        }
+        // the launches of the plan inside [k0, k1): the words the host reads of all sync blocks of a launch come back in one copy
+        int64_t a = k0;
+        for (int64_t end : xp.launch_end) {
+            if (end <= k0) continue;
+            const int64_t b = std::min(end, k1);
+            if (a >= b || xcd_off) break;
+            const LinkageXcdKey& key = xp.key[(size_t)a];
+            int cap = 0;
+            for (int64_t k = a; k < b; ++k) cap = std::max(cap, h[(size_t)(k - k0)].cap);
+            hipError_t le;
+            {
+                ProfScope ps(c, "linkage_rg_jobs", 0, 24.0 * (double)jobs[ord[a - k0]].N * (double)jobs[ord[a - k0]].N * (double)(b - a));
+                le = linkage_rg_jobs_launch(c, method, key.G, key.TH, key.helper, tab + (a - k0), (int)(b - a), cap, errs);
+            }
+            if (le != hipSuccess) (void)hipGetLastError();      // refused: nothing ran, every job of the launch goes the single route
+            else {
+                unsigned* hw = hs.data() + (size_t)(a - k0) * SYNC_HOST_WORDS;
+                HIPCHK(c, hipMemcpyAsync(hw, sync + (a - k0) * SYNC_HOST_WORDS, (size_t)(b - a) * SYNC_HOST_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                bool timeout = false;
+                for (int64_t k = a; k < b; ++k) {
+                    ran[(size_t)(k - k0)] = 1;
+                    c->stats["linkage_retry_rounds"].flops += (double)hw[(k - a) * SYNC_HOST_WORDS + SYNC_ROUNDS];
+                    timeout = timeout || hw[(k - a) * SYNC_HOST_WORDS + SYNC_TIMEOUT] != 0;
+                }
+                if (timeout) { xcd_off = true; c->stats["linkage_xcd_timeouts"].launches += 1; }      // too few workgroups of some job found each other: not again in this call
+            }
+            a = b;
+            if (b == k1) break;
+        }
+        HIPCHK(c, hipMemcpyAsync(hZ.data(), Z, (size_t)nZ * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(herr.data(), errs, (size_t)Gn * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        std::vector<int64_t> redo;
+        oZ = 0;
+        for (int64_t k = 0; k < Gn; ++k) {
+            const LinkageManyJob& q = jobs[ord[k]];
+            const size_t nz = (size_t)(q.N - 1) * 4;
+            const unsigned* hw = hs.data() + (size_t)k * SYNC_HOST_WORDS;
+            if (herr[(size_t)k]) status[ord[k]] = SD_ERR_NUMERIC;      // zero-norm row under the cosine metric: its Z stays as it was (as in group())
+            else if (ran[(size_t)k] && !hw[SYNC_TIMEOUT] && !hw[SYNC_TIE]) {
+                status[ord[k]] = SD_OK; memcpy(q.h_Z, hZ.data() + oZ, nz * sizeof(double));
+                c->stats["linkage_xcd_jobs"].launches += 1;
+            }
+            else redo.push_back(ord[k]);
+            oZ += (int64_t)nz;
+        }
+        for (int64_t j : redo) {
+            c->stats["linkage_xcd_redone"].launches += 1;
+            if (int rc = single(j)) return rc;
+        }
+        return SD_OK;
+    }
 };
+
+bool linkage_job_shares_launches(const sd_ctx* c, int64_t N, int method)
+{
+    return linkage_job_batched(LinkageRoute{c->linkage_wgs, c->linkage_one_xcd, c->num_cu}, N) || linkage_job_xcd(linkage_xcd_opts(c, method), N);
+}
 
 // (method and metric are validated where they enter, as for run_linkage)
 int run_linkage_many(sd_ctx* c, const LinkageManyJob* jobs, int64_t J, int d, int method, int metric, int32_t* status)
@@ -191,13 +346,21 @@ int run_linkage_many(sd_ctx* c, const LinkageManyJob* jobs, int64_t J, int d, in
     for (int64_t j = 0; j < J; ++j) N[(size_t)j] = jobs[j].N;
     LinkageBatchPlan p;
     linkage_batch_plan(N.data(), J, LinkageRoute{c->linkage_wgs, c->linkage_one_xcd, c->num_cu}, c->linkage_batch_bytes, p);
-    LinkageManyRun r = {c, jobs, d, method, metric, status};
+    LinkageManyRun r = {c, jobs, d, method, metric, status, false};
     int64_t first = 0;
     for (int64_t end : p.group_end) {
         if (int rc = r.group(p.order.data() + first, end - first)) return rc;
         first = end;
     }
-    for (int64_t j : p.single) if (int rc = r.single(j)) return rc;
+    // of the jobs left: those of the one-XCD cooperative class eight to a launch (option linkage_batch_xcd), the others as ever, in list order
+    LinkageXcdPlan xp;
+    linkage_xcd_plan(N.data(), p.single, linkage_xcd_opts(c, method), xp);
+    first = 0;
+    for (int64_t end : xp.group_end) {
+        if (int rc = r.xcd_group(xp, first, end)) return rc;
+        first = end;
+    }
+    for (int64_t j : xp.single) if (int rc = r.single(j)) return rc;
     return SD_OK;
 }
 

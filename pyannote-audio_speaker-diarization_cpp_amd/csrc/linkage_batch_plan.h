@@ -6,6 +6,8 @@
 // automatic geometry, N < 2, a heap beyond LDS) is SINGLE and goes through run_linkage unchanged, in list order.
 // Batched jobs are sorted by descending N (stable: equal N keep list order) -- the launch issues its workgroups in that order, so its tail is short -- and cut,
 // in that order, into groups whose workspaces stay within a byte budget; a job that alone exceeds the budget is a group of its own.
+// Second half of the file: the cooperative geometry of one job (linkage_geometry, which linkage.hip's linkage_plan calls) and linkage_xcd_plan, which takes
+// the single jobs of the one-XCD cooperative class eight to a launch (tools/linkage_xcd_plan_check.cpp, tests/test_linkage_xcd_plan_cpu.py).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -55,4 +57,130 @@ inline void linkage_batch_plan(const int64_t* N, int64_t J, const LinkageRoute& 
         bytes += b;
     }
     if (!p.order.empty()) p.group_end.push_back((int64_t)p.order.size());
+}
+
+// ---------------------------------------------------------------- the cooperative geometry of one job, and the jobs that run one per XCD
+// What linkage_plan (linkage.hip, which calls this) decides by arithmetic alone: workgroups, threads, columns per workgroup, the matrix form, the kernel and
+// whether all workgroups sit on one XCD.  `square_ok` = false: the square matrix could not be allocated.  G <= 1: the one-workgroup heap kernel, the rest unused.
+// The limits of k_linkage_rg's geometry (linkage_rg.hip asserts that its own constants are these):
+constexpr int LINKAGE_RG_GMAX = 128, LINKAGE_RG_U = 4, LINKAGE_RG_T_MAX = 1024, LINKAGE_RG_SLOT = 40;
+constexpr int LINKAGE_SYNC_HOST_WORDS = 32;      // the words of a sync block the host reads (linkage_dev.h: SYNC_HOST_WORDS); all k_linkage_rg touches
+struct LinkageOpts { int64_t wgs, one_xcd, threads, square, kernel, prefetch; int num_cu; };      // the options linkage_* of those names; the device's CUs
+struct LinkageGeom { int G, TH, cap; bool square, use_rg, onex; };
+inline bool linkage_rg_fits_geom(int64_t N, int G, int TH)
+{
+    if (G < 2 || G > LINKAGE_RG_GMAX) return false;
+    const int64_t colsB = (N + G - 1) / G;
+    return colsB <= (int64_t)(TH <= 512 ? 8 : LINKAGE_RG_U) * TH && TH <= LINKAGE_RG_T_MAX;         // (8 columns per thread: the <= 512-thread forms only -- register budget)
+}
+// the form of k_linkage_rg a geometry takes: whether the helper wave runs, the threads launched with it, and whether a thread has more than 4 columns
+inline void linkage_rg_form(int G, int TH, int cap, int& helper, int& TT, bool& wide)
+{
+    if (helper && (TH > 448 || G > 64)) helper = 0;         // (one slot per lane in the helper's fold; 16 waves at most)
+    TT = TH + (helper ? 64 : 0);
+    wide = (int64_t)(cap - 1) > (int64_t)LINKAGE_RG_U * TH;
+}
+inline LinkageGeom linkage_geometry(const LinkageOpts& o, int64_t N, bool square_ok)
+{
+    LinkageGeom p = {};
+    // auto geometry (measured on clustered data, profiles/r01_linkage_scaling.txt, r02_linkage_stamps.txt, r03_linkage_*.txt): up to N = 30 000
+    // the one-XCD form with one workgroup on each of the XCD's 32 CUs; above, all XCDs
+    // (r03, square form: one XCD wins up to N ~ 70 000 -- 384 ms against 443 at N = 50 158, 719 against 715 at N = 75 090 -- all XCDs above: 987 ms against 1 064 at
+    // N = 100 174; all XCDs: 64 workgroups up to ~90 000 rows, 128 above)
+    const bool auto_onex = (int)o.wgs < 0 && o.one_xcd != 0 && o.num_cu >= 256 && N >= 1500 && N < 70000;
+    int G = linkage_route_wgs(o.wgs, o.one_xcd, o.num_cu, N);
+    int TH = (int)o.threads;
+    // measured (r03, square form, N = 12 602, one XCD, three boxes): 32 x 256 75.2 / 82.7 / 76.8 ms, 32 x 512 84.4 / 77.2 / 85.0 ms -- the
+    // boxes disagree, 256 wins on two of three; all XCDs 128 x 512 0.99 s at N = 100 174 (128 x 256: 1.10 s)
+    // one XCD, larger N: 512 threads (N = 18 867: 121 ms against 126; N = 25 274: 170 against 179; N = 50 158: 384 against 465)
+    if (TH <= 0) TH = auto_onex ? (N >= 16000 ? 512 : 256) : N >= 8000 ? 512 : 256;
+    TH = TH >= 1024 ? 1024 : TH >= 512 ? 512 : TH >= 256 ? 256 : 128;      // (not below 128: the kernels fill their G <= 128 candidate slots with `tid < G`)
+    p.G = G; p.TH = TH;
+    if (G <= 1) return p;
+    // square form (full N x N matrix, row-only bulk accesses) while the square fits beside everything else; the condensed form above that
+    const bool square = square_ok && (o.square < 0 ? (double)N * (double)N * 8.0 <= 170e9 : o.square != 0);
+    // k_linkage_rg's own automatic geometry (r05, planted embeddings, 256 threads; profiles/r05_linkage_rg.txt): one XCD with 32 workgroups only while a thread
+    // has one or two columns -- N = 12 602: 72.7 ms with 32 (one XCD), 72.6 with 64 (all XCDs); N = 18 867: 127.7 / 120.0; N = 25 274: 179.1 / 165.2 (128: 169.1;
+    // k_linkage_mw 170.2); N = 50 158: 462.8 / 372.8 (128: 366.3; k_linkage_mw 381.8); N = 100 174: 128 workgroups 819 ms (64: 875; k_linkage_mw 996)
+    if (o.wgs < 0 && square && o.kernel != 0 && N >= 1500) {
+        G = N < 16000 ? 32 : N < 45000 ? 64 : 128;
+        if (G > o.num_cu) G = o.num_cu;
+    }
+    if ((N + G - 1) / G > 3400) G = (int)((N + 3399) / 3400);      // active-row lists and bounds live in LDS: 32 B per owned row (109 KB + 43 KB static)
+    // one-XCD form while two workgroups per CU of one XCD (32 CUs) can hold the job; above, all XCDs' memory pipelines are worth more
+    const bool onex = o.one_xcd != 0 && G <= 32 && o.num_cu >= 256;
+    // square form: k_linkage_rg (register state, sizes / ty in the slots) where its geometry fits -- at most 4 columns per thread -- else k_linkage_mw
+    bool use_rg = square && o.kernel != 0;
+    // measured (r05, planted embeddings): N = 12 602, one XCD, 32 workgroups: 256 threads 72.7 ms, 512 threads 81.2, 128 threads 76.6 (k_linkage_mw 76.7);
+    // N = 100 174, all XCDs, 128 workgroups: 256 threads 819 ms, 512 threads 829 (k_linkage_mw 996); 64 x 512: 875
+    if (use_rg && o.threads <= 0) TH = 256;
+    if (use_rg && !linkage_rg_fits_geom(N, G, TH)) {
+        int t2 = TH;
+        while (t2 < 1024 && !linkage_rg_fits_geom(N, G, t2)) t2 *= 2;
+        if (linkage_rg_fits_geom(N, G, t2) && (o.threads <= 0 || o.kernel > 0)) TH = t2; else use_rg = false;
+    }
+    p.G = G; p.TH = TH; p.cap = (int)((N + G - 1) / G) + 1;
+    p.square = square; p.use_rg = use_rg; p.onex = onex;
+    return p;
+}
+
+// A job is XCD-BATCHED iff option linkage_batch_xcd is on, run_linkage would take it to the one-XCD form of k_linkage_rg<true, 256, 4, METHOD> -- its geometry
+// with the square matrix has G >= 2, use_rg, onex, at most 4 columns per thread and at most 256 threads with the helper wave; a method code k_linkage_rg is
+// built for; option linkage_force_heap off --, its workspaces fit the byte budget, and at least two such jobs of the call share (G, threads, helper): under the
+// automatic options 1500 <= N < 16 000 on a device of 256 CUs.  k_linkage_rg_jobs runs up to eight of them in one cooperative launch, job x on XCD x.
+struct LinkageXcdOpts { int64_t on; LinkageOpts o; int method; bool force_heap; int64_t budget_bytes; };
+struct LinkageXcdKey { int G, TH, helper; };
+inline bool operator==(const LinkageXcdKey& a, const LinkageXcdKey& b) { return a.G == b.G && a.TH == b.TH && a.helper == b.helper; }
+// device bytes of one XCD-batched job: the square matrix; ids and neighbours (int); the two bounds (double); Z; the two slot sets; one sync block
+inline int64_t linkage_xcd_ints(int64_t N) { return 2 * ((N + 1) & ~(int64_t)1); }
+inline int64_t linkage_xcd_bytes(int64_t N, int G)
+{
+    return N * N * 8 + linkage_xcd_ints(N) * 4 + 2 * N * 8 + (N - 1) * 32 + (int64_t)2 * G * LINKAGE_RG_SLOT * 8 + LINKAGE_SYNC_HOST_WORDS * 4;
+}
+// the class conditions of one job (all but "two of a kind"); key: its launch geometry
+inline bool linkage_job_xcd(const LinkageXcdOpts& x, int64_t N, LinkageXcdKey* key = nullptr)
+{
+    if (x.on == 0 || x.force_heap || x.method < 0 || x.method > 6 || N < 2 || N > 0x7fffffff / 4) return false;
+    const LinkageGeom g = linkage_geometry(x.o, N, true);
+    if (g.G < 2 || !g.use_rg || !g.onex) return false;
+    int helper = x.o.prefetch != 0 ? 1 : 0, TT; bool wide;
+    linkage_rg_form(g.G, g.TH, g.cap, helper, TT, wide);
+    if (wide || TT > 256 || linkage_xcd_bytes(N, g.G) > x.budget_bytes) return false;
+    if (key) *key = LinkageXcdKey{g.G, g.TH, helper};
+    return true;
+}
+
+constexpr int LINKAGE_XCD_JOBS = 8;             // jobs of one launch: one per XCD
+struct LinkageXcdPlan {
+    std::vector<int64_t> single;        // job numbers that keep run_linkage's route, in the order they came in
+    std::vector<int64_t> order;         // XCD-batched job numbers, descending N (stable)
+    std::vector<LinkageXcdKey> key;     // ... the launch geometry of each
+    std::vector<int64_t> group_end;     // groups (shared preparation, one set of workspaces) of order, as in LinkageBatchPlan
+    std::vector<int64_t> launch_end;    // launches of order: at most LINKAGE_XCD_JOBS consecutive jobs of one group and one key
+};
+// over `cand`, the jobs linkage_batch_plan left single (job numbers into N, in list order)
+inline void linkage_xcd_plan(const int64_t* N, const std::vector<int64_t>& cand, const LinkageXcdOpts& x, LinkageXcdPlan& p)
+{
+    p.single.clear(); p.order.clear(); p.key.clear(); p.group_end.clear(); p.launch_end.clear();
+    std::vector<LinkageXcdKey> keys(cand.size(), LinkageXcdKey{0, 0, 0});
+    std::vector<char> in(cand.size(), 0);
+    for (size_t a = 0; a < cand.size(); ++a) in[a] = linkage_job_xcd(x, N[cand[a]], &keys[a]) ? 1 : 0;
+    std::vector<size_t> pick;
+    for (size_t a = 0; a < cand.size(); ++a) {
+        int64_t alike = 0;
+        if (in[a]) for (size_t b = 0; b < cand.size(); ++b) alike += in[b] && keys[b] == keys[a];
+        if (alike >= 2) pick.push_back(a); else p.single.push_back(cand[a]);
+    }
+    std::stable_sort(pick.begin(), pick.end(), [&](size_t a, size_t b) { return N[cand[a]] > N[cand[b]]; });
+    int64_t bytes = 0, first = 0, lfirst = 0;
+    for (int64_t k = 0; k < (int64_t)pick.size(); ++k) {
+        const size_t a = pick[(size_t)k];
+        const int64_t b = linkage_xcd_bytes(N[cand[a]], keys[a].G);
+        const bool new_group = k > first && (bytes + b > x.budget_bytes || k - first >= LINKAGE_BATCH_MAX_JOBS);
+        if (new_group) { p.group_end.push_back(k); first = k; bytes = 0; }
+        if (k > lfirst && (new_group || k - lfirst >= LINKAGE_XCD_JOBS || !(keys[a] == p.key.back()))) { p.launch_end.push_back(k); lfirst = k; }
+        bytes += b;
+        p.order.push_back(cand[a]); p.key.push_back(keys[a]);
+    }
+    if (!pick.empty()) { p.group_end.push_back((int64_t)pick.size()); p.launch_end.push_back((int64_t)pick.size()); }
 }

@@ -74,6 +74,42 @@ __device__ __forceinline__ double pdist_value(double acc, double ma, double mb, 
     else return sqrt(acc);
 }
 
+// the same distances as the full N x N square: k_pdist_sq, k_pdist_sq_jobs.  Tile (ti, tj), ti <= tj, is computed once and written twice, the
+// mirror through the LDS transpose Tt so that both writes are row-contiguous.  D[i][j] and D[j][i] are the same bits; the diagonal is 0.
+// The whole workgroup (256 threads) calls it; a zero-norm row under the cosine metric raises *err.
+template <bool COS>
+__device__ __forceinline__ void pdist_sq_tile(const double* __restrict__ X, int64_t N, int d, int ti, int tj, double* __restrict__ D, int* __restrict__ err,
+                                              double (&Xi)[PT][33], double (&Xj)[PT][33], double (&Tt)[PT][PT + 1])
+{
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    double acc[4][4], ma[4], mb[4];
+    pdist_tile<COS>(X, N, d, ti, tj, Xi, Xj, acc, ma, mb);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int li = ty + 16 * u, lj = tx + 16 * v;
+            const int64_t i = (int64_t)ti * PT + li, j = (int64_t)tj * PT + lj;
+            double dv;
+            if constexpr (COS) {
+                dv = 0.0;
+                if (i != j && i < N && j < N) {
+                    bool zero_norm = false;
+                    dv = pdist_value<true>(acc[u][v], ma[u], mb[v], &zero_norm);
+                    if (zero_norm) *err = 1;
+                }
+            } else dv = (i == j) ? 0.0 : pdist_value<false>(acc[u][v], ma[u], mb[v], nullptr);
+            Tt[li][lj] = dv;
+            if (i < N && j < N && (ti != tj || i <= j)) D[(size_t)i * N + j] = dv;
+        }
+    __syncthreads();
+    for (int e = tid; e < PT * PT; e += 256) {
+        const int lj = e >> 6, li = e & 63;                 // consecutive threads: consecutive i = consecutive addresses of row j
+        const int64_t i = (int64_t)ti * PT + li, j = (int64_t)tj * PT + lj;
+        if (i < N && j < N && i < j) D[(size_t)j * N + i] = Tt[li][lj];
+    }
+}
+
 // ---------------------------------------------------------------- nearest active neighbour above a row (cl.cpp:259-276)
 struct MinIdx { double v; int i; };
 __device__ __forceinline__ MinIdx better(MinIdx a, MinIdx b)
@@ -171,6 +207,15 @@ __device__ __forceinline__ Min2 wave_min2(Min2 m)
     const bool win = m.i == w.i && m.i >= 0;
     r.v2 = wave_min_d(win ? m.v2 : (m.i >= 0 ? m.v : (double)INFINITY));
     return r;
+}
+
+// the exact bounds of row x from its `cnt` entries above the diagonal, row[t] = D[x, x + 1 + t]: one wave scans (k_row_nn, k_prepare_sq_jobs)
+__device__ __forceinline__ Min2 row_min2(const double* __restrict__ row, int64_t cnt, int64_t x)
+{
+    const int lane = threadIdx.x & 63;
+    Min2 m; m.v = INFINITY; m.i = -1; m.v2 = INFINITY;
+    for (int64_t t = lane; t < cnt; t += 64) min2_acc(m, row[t], (int)(x + 1 + t));
+    return wave_min2(m);
 }
 
 // Lance-Williams update of the distance between cluster i and the merge of x and y, the linkage method a compile-time parameter
@@ -394,7 +439,7 @@ constexpr int SYNC_MERGES = 3;                   // k_linkage_hx: merges done wh
 constexpr int SYNC_TIE = 5;                      // the closest pair was not unique: nothing more was merged
 constexpr int SYNC_TICKET = 6;                   // one-XCD forms: next ticket of the workgroups that found themselves on XCC 0
 constexpr int SYNC_TIE_LO = 26, SYNC_TIE_HI = 27;      // k_linkage_rg: the tie's height (bits of the double)
-constexpr int SYNC_HOST_WORDS = 32;              // what the host copies back
+constexpr int SYNC_HOST_WORDS = LINKAGE_SYNC_HOST_WORDS;      // what the host copies back (32; a job of k_linkage_rg_jobs has a block of just these)
 constexpr int SYNC_WORDS = 32 + 16 * 256;
 // arg-min candidate flags: bit 0 = the bound is exact; bit 1 (CAND_TIE) = some OTHER row holds exactly the same bound -- the case in which the
 // reference's heap, not the value, decides who comes first (k_linkage_heap)
@@ -416,6 +461,16 @@ template <bool ONEX, class T> __device__ __forceinline__ void STX(T* p, T v)
     else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// the linkage_* options and the device, as linkage_batch_plan.h's arithmetic takes them
+inline LinkageOpts linkage_opts(const sd_ctx* c)
+{
+    return LinkageOpts{c->linkage_wgs, c->linkage_one_xcd, c->linkage_threads, c->linkage_square, c->linkage_kernel, c->linkage_prefetch, c->num_cu};
+}
+inline LinkageXcdOpts linkage_xcd_opts(const sd_ctx* c, int method)
+{
+    return LinkageXcdOpts{c->linkage_batch_xcd, linkage_opts(c), method, c->linkage_force_heap, c->linkage_batch_bytes};
+}
+
 // ---------------------------------------------------------------- launchers run_linkage (linkage.hip) drives
 // linkage_rg.hip
 bool linkage_rg_fits(int64_t N, int G, int TH);
@@ -423,6 +478,20 @@ bool linkage_rg_has(int method, bool onex, int G, int TH, int cap, int helper);
 hipError_t linkage_rg_launch(sd_ctx* c, int method, bool onex, int G, int TH, double* D, int n, int* cid, const int* nb, const double* md, const double* md2,
                              double* Z, MwGran* gran, unsigned* sync, int cap, int helper, int k0 = 0, const int* sz0 = nullptr, const int* ty0 = nullptr);
 int linkage_rg_slot_granules();
+// k_linkage_rg_jobs: up to 8 fresh jobs of the one-XCD, 256-thread, 4-column form in one cooperative launch, job x on XCD x.  G and helper are
+// the launch's; the record holds what k_linkage_rg takes per job, the rows the two preparation kernels (linkage_batch.hip) build the matrix from, and the index
+// of the job's error slot (raised: no kernel behind the distances touches the job)
+struct LinkageRgJob {
+    const double* X;        // [n][d] rows
+    double* D;              // [n][n] square matrix
+    int* cid; int* nb;      // [n] each
+    double* md; double* md2;      // [n] each
+    double* Z;              // [n - 1][4]
+    MwGran* gran;           // [2][G][slot granules], zeroed
+    unsigned* sync;         // [SYNC_HOST_WORDS], zeroed
+    int n, cap, err, pad;
+};
+hipError_t linkage_rg_jobs_launch(sd_ctx* c, int method, int G, int TH, int helper, const LinkageRgJob* d_jobs, int nj, int max_cap, const int* d_errs);
 // linkage_mw.hip: centroid only; at most linkage_mw_max_workgroups() workgroups; size_all = what linkage_mw_prepare set up (workspace cl_size_all)
 bool linkage_mw_has(int method);
 int linkage_mw_max_workgroups();

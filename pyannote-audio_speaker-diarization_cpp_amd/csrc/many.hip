@@ -155,8 +155,8 @@ int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vec
 // train_rows (the "max_num_embeddings" sample included), k_gather_normalize -- and runs all dendrograms in shared launches (run_linkage_many).  Z[j] /
 // ZN[j] (the train rows it belongs to; -1 = none) wait on the host for cluster_rows, which takes a Z only where it finds the same row count itself.
 // Jobs that skip the pass and run their linkage where they always did: under an enrolled gallery (the linkage is over the unclaimed rows), a trivial
-// number-of-clusters rule, fewer than two train rows, a job run_linkage would not give to its one-workgroup kernel (nothing to gain, and its Z would be held
-// for longer).  A job whose dendrogram fails with SD_ERR_NUMERIC keeps no Z: its finalize runs the linkage itself and reports what the sequential path reports.
+// number-of-clusters rule, fewer than two train rows, a job run_linkage_many would run alone -- neither the one-workgroup kernel's nor, under option
+// linkage_batch_xcd, of the one-XCD cooperative class (linkage_job_shares_launches): nothing to gain, and its Z would be held for longer.  A job whose dendrogram fails with SD_ERR_NUMERIC keeps no Z: its finalize runs the linkage itself and reports what the sequential path reports.
 static int dendrograms_ahead(sd_ctx* c, const std::vector<FinalJob>& jobs, std::vector<std::vector<double>>& Z, std::vector<int64_t>& ZN)
 {
     const size_t J = jobs.size();
@@ -168,13 +168,12 @@ static int dendrograms_ahead(sd_ctx* c, const std::vector<FinalJob>& jobs, std::
     for (const FinalJob& q : jobs) {
         if (q.chunks <= 0) continue;
         const int64_t M = q.chunks * SD_SPEAKERS;
-        maxM = std::max(maxM, M); pool += std::min<int64_t>(M, LINKAGE_HEAP_LDS + 1); live += 1;
+        maxM = std::max(maxM, M); pool += c->linkage_batch_xcd ? M : std::min<int64_t>(M, LINKAGE_HEAP_LDS + 1); live += 1;      // (a job of the one-XCD class has up to M train rows)
     }
     if (live < 2) return SD_OK;
     WS(c, double, d_e64, "lb_e64", maxM * d);
     WS(c, double, d_X, "lb_X", pool * d);
     const ClusterSpec spec = {c->clustering_threshold, c->min_cluster_size, c->num_clusters, c->min_clusters, c->max_clusters};
-    const LinkageRoute route = {c->linkage_wgs, c->linkage_one_xcd, c->num_cu};
     std::vector<std::vector<int>> tidx(J);
     std::vector<LinkageManyJob> lj;
     std::vector<size_t> owner;
@@ -187,7 +186,7 @@ static int dendrograms_ahead(sd_ctx* c, const std::vector<FinalJob>& jobs, std::
         if ((rc = launch_f32_to_f64(c, q.emb, d_e64, M * d))) return rc;
         if ((rc = train_rows(c, d_e64, M, d, tidx[j]))) return rc;
         const int64_t N = (int64_t)tidx[j].size();
-        if (!linkage_job_batched(route, N) || resolve_num_clusters(spec, N).trivial) continue;
+        if (!linkage_job_shares_launches(c, N, c->clustering_method) || resolve_num_clusters(spec, N).trivial) continue;
         if ((rc = linkage_rows(c, d_e64, tidx[j], d, d_X + (size_t)off * d))) return rc;
         Z[j].resize((size_t)(N - 1) * 4);
         lj.push_back(LinkageManyJob{d_X + (size_t)off * d, N, Z[j].data()});
