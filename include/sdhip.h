@@ -129,7 +129,7 @@ int sd_cluster_ex(sd_ctx*, const double* h_X, int64_t N, int d, int method, int 
  * h_Z the dendrograms in the same order, max(N[j] - 1, 0) rows of 4 each.  Z of job j is, byte for byte, what sd_linkage_ex gives for job j alone,
  * whatever else is in the call and in whatever order, for every N: the jobs that sd_linkage_ex runs on one workgroup (N < 1500) share launches,
  * one workgroup per job and, under "linkage_batch_xcd", the jobs of the one-XCD cooperative class, eight to a launch; the others take sd_linkage_ex's
- * own route.  N[j] of 0 or 1 is legal: no rows, status SD_OK.  A job with a zero-norm row
+ * own route.  Under "linkage_batch_xcd_zero" a job of that class whose rows hold duplicates (a tie at height 0) stays in those launches too.  N[j] of 0 or 1 is legal: no rows, status SD_OK.  A job with a zero-norm row
  * under the cosine metric gets status[j] = SD_ERR_NUMERIC and its rows of h_Z are left as they were; the others finish and the call returns SD_OK.
  * SD_ERR_ARG before anything is written: a null pointer, J < 1, a negative N[j], d <= 0, more than 2^31 - 1 rows in all, an unknown method or
  * metric, centroid / median / ward with the cosine metric. */
@@ -622,6 +622,14 @@ int sd_stage_ms(const sd_ctx*, double* ms4);
  *   there, or whose launch is refused or times out, is run again alone; results are the same bytes either way.  0 = every call launches what it launched
  *   before the key existed.  Measured: 8 .. 64 jobs of 1 500 .. 8 000 rows 5.2 - 6.4 x the loop of sd_linkage_ex.  Off by default because jobs with duplicate rows
  *   -- every stream of the synthetic workload -- tie at height 0, are redone alone and gain nothing (README, "Mid-size linkage jobs, one per XCD").
+ * "linkage_batch_xcd_zero" (0 (default) / 1; anything else SD_ERR_ARG; read only where "linkage_batch_xcd" = 1): 1 = a job of such a launch that stops at
+ *   a tie at height 0 in front of its first merge -- duplicate rows: looped audio, digital silence, synthetic streams -- stays in the batch: the heap replay
+ *   takes the merges at height 0 and the cooperative kernel the rest, the three steps sd_linkage_ex takes for such a job alone, up to eight jobs to a launch,
+ *   one per XCD.  A tie above 0, a tie after a merge, a refused launch or a timeout still sends the job through sd_linkage_ex's route alone; results are
+ *   the same bytes either way, for every method and both metrics.  0 = every call launches what it launched before the key existed (a job that ties is
+ *   redone alone).  Measured: 8 .. 64 jobs of 1 500 .. 8 000 rows with 5 % copied rows 5.2 - 6.6 x the loop of sd_linkage_ex; 64 streams at 10 min update in
+ *   191 ms instead of 986 with "linkage_batch", "linkage_batch_xcd" and this key at 1.  Off by default because that behaviour of "linkage_batch_xcd" = 1 is
+ *   pinned by its tests and a default changes in a step of its own (README, "Ties at height 0 inside the XCD batch"; profiles/linkage_xcd_zero_times.txt).
  * Test and tuning keys are listed in sdhip_test.h.  An unknown key returns SD_ERR_ARG. */
 int sd_set_option(sd_ctx*, const char* key, int64_t value);
 /* the real-valued keys: "clustering_threshold" (Clustering.py:251-276 / 317-333; outside [0, 2] or NaN: SD_ERR_ARG) and the four "activity_*" keys of

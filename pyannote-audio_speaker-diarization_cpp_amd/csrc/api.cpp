@@ -125,6 +125,7 @@ extern "C" int sd_set_option(sd_ctx* c, const char* key, int64_t v)
     else if (k == "linkage_square") c->linkage_square = v;
     else if (k == "linkage_batch") { if (v != 0 && v != 1) SD_FAIL(c, SD_ERR_ARG, "linkage_batch must be 0 or 1"); c->linkage_batch = v; }
     else if (k == "linkage_batch_xcd") { if (v != 0 && v != 1) SD_FAIL(c, SD_ERR_ARG, "linkage_batch_xcd must be 0 or 1"); c->linkage_batch_xcd = v; }
+    else if (k == "linkage_batch_xcd_zero") { if (v != 0 && v != 1) SD_FAIL(c, SD_ERR_ARG, "linkage_batch_xcd_zero must be 0 or 1"); c->linkage_batch_xcd_zero = v; }
     else if (k == "linkage_batch_bytes") { if (v < 1) SD_FAIL(c, SD_ERR_ARG, "linkage_batch_bytes must be at least 1"); c->linkage_batch_bytes = v; }
     else if (k == "linkage_batch_threads") { if (v != 0 && v != 256 && v != 1024) SD_FAIL(c, SD_ERR_ARG, "linkage_batch_threads must be 0 (auto), 256 or 1024"); c->linkage_batch_threads = v; }
     else if (k == "skip_dead_rows") c->skip_dead_rows = v != 0;

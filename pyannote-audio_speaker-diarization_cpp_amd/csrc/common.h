@@ -216,6 +216,7 @@ struct sd_ctx {
     int64_t linkage_batch = 0;                 // group calls (finalize_jobs, many.hip): 1 = the dendrograms of the jobs that fit run ahead of the per-job finalize in shared launches (run_linkage_many), 0 = one job after the other (the default: profiles/linkage_many_times.txt)
     int64_t linkage_batch_bytes = (int64_t)2 << 30;   // run_linkage_many: bytes the workspaces of one group of jobs may take
     int64_t linkage_batch_xcd = 0;             // run_linkage_many: 1 = the jobs of the one-XCD cooperative class run eight to a launch, one per XCD (k_linkage_rg_jobs); 0 = one after the other (the default until profiles/linkage_xcd_times.txt says otherwise)
+    int64_t linkage_batch_xcd_zero = 0;        // run_linkage_many, read only under linkage_batch_xcd = 1: 1 = a job of an XCD launch that stops at a tie at height 0 before its first merge (duplicate rows) stays in the batch: k_linkage_hx_jobs takes the merges at height 0, k_linkage_rg_jobs<M, true> the rest; 0 = such a job is redone alone (the default: tests/test_linkage_xcd.py pins it, profiles/linkage_xcd_zero_times.txt)
     int64_t linkage_batch_threads = 0;         // run_linkage_many: threads of the workgroup of a job, 0 auto (256), else 256 or 1024; tuning
     std::vector<double> ahead_Z; int64_t ahead_N = -1;      // finalize_jobs -> cluster_rows: the dendrogram of the job being finalized, from the pass ahead (ahead_N = its train rows; -1 = none)
     int num_cu = 256;
@@ -482,7 +483,7 @@ int run_linkage(sd_ctx* c, const double* d_X, int64_t N, int d, double* d_Z, int
 int run_linkage_host(sd_ctx* c, const double* d_X, int64_t N, int d, int method, int metric, std::vector<double>& Z);      // cluster.hip: run_linkage, Z on the host
 // ---- linkage_batch.hip: J independent jobs, rows on the device, Z [N - 1][4] of each to the host.  The jobs run_linkage would give to its one-workgroup
 // kernel share launches (one workgroup per job, linkage_batch_plan.h), under option linkage_batch_xcd those of its one-XCD cooperative kernel too (eight to a
-// launch, one per XCD), the others go through run_linkage; every Z is the bytes run_linkage gives for the
+// launch, one per XCD; under option linkage_batch_xcd_zero those of them that tie at height 0 stay there), the others go through run_linkage; every Z is the bytes run_linkage gives for the
 // job alone.  status[j] = SD_OK, or SD_ERR_NUMERIC for a job with a zero-norm row under the cosine metric (its Z is left as it was); any other failure is returned
 struct LinkageManyJob { const double* d_X; int64_t N; double* h_Z; };
 int run_linkage_many(sd_ctx* c, const LinkageManyJob* jobs, int64_t J, int d, int method, int metric, int32_t* status);

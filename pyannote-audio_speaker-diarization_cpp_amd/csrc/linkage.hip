@@ -68,13 +68,7 @@ __global__ __launch_bounds__(256) void k_row_nn_mid(const double* __restrict__ D
     const int lane = threadIdx.x & 63;
     const int64_t x = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (x >= n - 1) return;
-    Min2 m; m.v = INFINITY; m.i = -1; m.v2 = INFINITY;
-    if (size[x] != 0) {
-        const int tx = ty[x];
-        for (int64_t j = x + 1 + lane; j < n; j += 64)
-            if (size[j] != 0) min2_acc(m, tx >= ty[j] ? D[x * n + j] : D[j * n + x], (int)j);
-    }
-    m = wave_min2(m);
+    const Min2 m = row_min2_mid(D, n, size, ty, x);
     if (lane == 0) { nb[x] = m.i; md[x] = (m.i < 0) ? INFINITY : m.v; md2[x] = (m.i < 0) ? INFINITY : m.v2; }
 }
 
@@ -109,13 +103,9 @@ static LinkagePlan linkage_plan(const sd_ctx* c, int64_t N, bool square_ok)
     const bool square = g.square, use_rg = g.use_rg;
     p.cap = g.cap; p.square = g.square; p.use_rg = g.use_rg; p.onex = g.onex;
     p.slot_gran = use_rg ? linkage_rg_slot_granules() : linkage_mw_slot_granules();
-    if (square && c->linkage_tie_kernel != 0) {
-        bool hx_onex = c->linkage_one_xcd != 0 && c->num_cu >= 256 && linkage_hx_fits(N, 31);
-        int workers = hx_onex ? 31 : (N >= 60000 ? 127 : 63);
-        if (c->linkage_tie_kernel > 1) { workers = (int)c->linkage_tie_kernel; hx_onex = hx_onex && workers <= 31; }
-        if (workers + 1 > c->num_cu) workers = c->num_cu - 1;
-        p.replay = linkage_hx_fits(N, workers); p.workers = workers; p.hx_onex = hx_onex;
-    }
+    // (linkage_batch_plan.h too: run_linkage_many asks the same question of a job that ties inside an XCD launch)
+    const LinkageTie t = linkage_tie_plan(c->linkage_tie_kernel, c->linkage_one_xcd, c->num_cu, N, square);
+    p.replay = t.replay; p.workers = t.workers; p.hx_onex = t.hx_onex;
     return p;
 }
 

@@ -12,6 +12,11 @@
 //   k_prepare_sq_jobs            ids = iota, nearest neighbour, bound and second bound above each row by k_row_nn's row_min2
 //   k_linkage_rg_jobs<M>         (linkage_rg.hip) up to eight jobs per cooperative launch, job x on the 32 CUs of XCD x: k_linkage_rg's own body
 // A job that meets an exact tie there, or whose launch is refused or times out, goes through run_linkage alone afterwards.
+// Under option linkage_batch_xcd_zero the jobs that tie at height 0 in front of their first merge (duplicate rows) stay in the batch instead:
+//   k_prepare_zero_jobs          size = 1, ty = -1
+//   k_linkage_hx_jobs<M>         (linkage_hx.hip) up to eight jobs per cooperative launch, job x on XCD x: k_linkage_hx's own body, the merges at height 0 only
+//   k_row_nn_mid_jobs            the exact bounds of the rows still there, by k_row_nn_mid's row_min2_mid
+//   k_linkage_rg_jobs<M, true>   k_linkage_rg's body from merge k0 on
 #include "common.h"
 #include "exact_fp.h"
 #include "linkage_dev.h"
@@ -125,6 +130,29 @@ __global__ __launch_bounds__(256) void k_prepare_sq_jobs(const LinkageRgJob* __r
     if (lane == 0) { jb.nb[x] = m.i; jb.md[x] = (m.i < 0) ? INFINITY : m.v; jb.md2[x] = (m.i < 0) ? INFINITY : m.v2; }
 }
 
+// ---------------------------------------------------------------- the jobs that tie at height 0 inside an XCD launch (option linkage_batch_xcd_zero)
+// k_prepare_zero_jobs: size = 1 and ty = -1 for the jobs of a zero launch (k_linkage_hx_jobs, linkage_hx.hip) -- what LinkageJob::prepare and ::replay fill for
+// k_linkage_hx alone; the first launches keep neither array.  Grid (ceil(longest n / 256), jobs)
+__global__ __launch_bounds__(256) void k_prepare_zero_jobs(const LinkageHxJob* __restrict__ jobs, const int* __restrict__ errs)
+{
+    const LinkageHxJob jb = jobs[blockIdx.y];
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < jb.n && !errs[jb.err]) { jb.size[t] = 1; jb.ty[t] = -1; }
+}
+
+// k_row_nn_mid_jobs: k_row_nn_mid (linkage.hip) per job, blockIdx.y = job, a wave per row: row_min2_mid over the clusters the zero launch left (sz0, ty0).
+// nb, md and md2 are the bits LinkageJob::continue_rg gets.  Grid (row quads of the longest job, jobs)
+__global__ __launch_bounds__(256) void k_row_nn_mid_jobs(const LinkageRgJob* __restrict__ jobs, const int* __restrict__ errs)
+{
+    const LinkageRgJob jb = jobs[blockIdx.y];
+    const int64_t n = jb.n;
+    const int lane = threadIdx.x & 63;
+    const int64_t x = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (x >= n - 1 || errs[jb.err]) return;
+    const Min2 m = row_min2_mid(jb.D, n, jb.sz0, jb.ty0, x);
+    if (lane == 0) { jb.nb[x] = m.i; jb.md[x] = (m.i < 0) ? INFINITY : m.v; jb.md2[x] = (m.i < 0) ? INFINITY : m.v2; }
+}
+
 // ---------------------------------------------------------------- the driver
 // Threads per job: 256.  Measured (tools/linkage_many_times.py, profiles/linkage_many_times.txt; 64 jobs, one per CU): 2.24 ms at N = 100, 16.00 at 400 and
 // 57.81 at 1000 with 256 threads against 2.20 / 16.66 / 58.12 with k_linkage_heap's 1024 -- no difference beyond the spread of the rounds: a merge is bound by
@@ -220,6 +248,129 @@ struct LinkageManyRun {
         return SD_OK;
     }
 
+    // Option linkage_batch_xcd_zero.  `open_k` / `open_j`: the jobs of an XCD group (numbers in the group, records `h`) that their first launch left
+    // unfinished, and how it ended.  Those that stopped at a tie at height 0 in front of their first merge (linkage_xcd_zero_plan) go through run_linkage's three
+    // steps for that case together, up to eight to a launch, one per XCD: k_linkage_hx_jobs takes the merges at height 0, k_row_nn_mid_jobs recomputes the exact
+    // bounds of the rows still there, k_linkage_rg_jobs<M, true> continues.  finished[a] = 1: job open_k[a] is done and its Z is with the caller; every other is the
+    // caller's to run again alone -- where LinkageJob::continue_rg falls through to the whole replay, and on a refused launch, a timeout or a refused allocation.
+    int zero_launches(const int64_t* ord, const std::vector<LinkageRgJob>& h, const std::vector<int64_t>& open_k, const std::vector<LinkageXcdZeroJob>& open_j,
+                      const int* errs, std::vector<char>& finished)
+    {
+        LinkageXcdZeroPlan zp;
+        linkage_xcd_zero_plan(open_j.data(), (int64_t)open_j.size(),
+                              LinkageXcdZeroOpts{c->linkage_batch_xcd_zero, c->linkage_zero_phase, c->linkage_tie_kernel, c->linkage_one_xcd, c->linkage_hx_wide, c->num_cu}, zp);
+        auto finish = [&](size_t a) {            // Z to the caller's rows (the stream is synchronised by the caller of finish's last use)
+            const LinkageManyJob& q = jobs[ord[open_k[a]]];
+            status[ord[open_k[a]]] = SD_OK; finished[a] = 1;
+            c->stats["linkage_xcd_zero_jobs"].launches += 1;
+            return hipMemcpyAsync(q.h_Z, h[(size_t)open_k[a]].Z, (size_t)(q.N - 1) * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        };
+        int64_t za = 0;
+        for (int64_t zb : zp.launch_end) {
+            const int nj = (int)(zb - za);
+            const int64_t first = za;
+            za = zb;
+            if (xcd_off) break;                  // a poll timed out in this call: what is left is redone alone
+            const int workers = zp.workers[(size_t)first];
+            const LinkageXcdKey key = open_j[(size_t)zp.order[(size_t)first]].key;
+            int64_t nI = 0, nF = 0, maxN = 0;
+            const int64_t nGr = linkage_xcd_zero_granules(workers);
+            for (int i = 0; i < nj; ++i) {
+                const int64_t N = open_j[(size_t)zp.order[(size_t)(first + i)]].N;
+                nI += linkage_xcd_zero_ints(N, workers); nF += linkage_xcd_zero_doubles(N, workers); maxN = std::max(maxN, N);
+            }
+            int* I = ws_get<int>(c, "lx_zero_int", (size_t)nI);
+            double* F = I ? ws_get<double>(c, "lx_zero_f64", (size_t)nF) : nullptr;
+            MwGran* gr = F ? ws_get<MwGran>(c, "lx_zero_gran", (size_t)(nGr * LINKAGE_XCD_JOBS)) : nullptr;
+            unsigned* zsync = gr ? ws_get<unsigned>(c, "lx_zero_sync", (size_t)LINKAGE_XCD_JOBS * SYNC_HOST_WORDS) : nullptr;
+            LinkageHxJob* ztab = zsync ? ws_get<LinkageHxJob>(c, "lx_zero_tab", (size_t)LINKAGE_XCD_JOBS) : nullptr;
+            LinkageRgJob* ctab = ztab ? ws_get<LinkageRgJob>(c, "lx_zero_cont", (size_t)LINKAGE_XCD_JOBS) : nullptr;
+            if (!ctab) { (void)hipGetLastError(); c->stats["linkage_batch_alloc_failed"].launches += 1; continue; }
+            // 1. the table
+            std::vector<LinkageHxJob> zh((size_t)nj);
+            size_t max_dyn = 0;
+            int64_t oI = 0, oF = 0;
+            for (int i = 0; i < nj; ++i) {
+                const LinkageRgJob& r = h[(size_t)open_k[(size_t)zp.order[(size_t)(first + i)]]];
+                const int64_t N = r.n, s = (N + 1) & ~(int64_t)1, cap = linkage_xcd_zero_cap(N, workers);
+                bool s16; int lc; size_t dyn;
+                linkage_hx_form(N, false, s16, lc, dyn);
+                max_dyn = std::max(max_dyn, dyn);
+                int* ip = I + oI; double* fp = F + oF;
+                zh[(size_t)i] = LinkageHxJob{r.D, r.cid, ip, ip + s, r.nb, r.md, r.Z, fp, ip + 2 * s, ip + 3 * s, gr + i * nGr, gr + i * nGr + 16, ip + 4 * s, fp + N,
+                                            zsync + i * SYNC_HOST_WORDS, (int)N, (int)cap, lc, r.err};
+                oI += linkage_xcd_zero_ints(N, workers); oF += linkage_xcd_zero_doubles(N, workers);
+            }
+            HIPCHK(c, hipMemcpyAsync(ztab, zh.data(), (size_t)nj * sizeof(LinkageHxJob), hipMemcpyHostToDevice, c->stream));
+            // 2. size = 1, ty = -1   3. granules and sync blocks
+            hipLaunchKernelGGL(k_prepare_zero_jobs, dim3((unsigned)((maxN + 255) / 256), (unsigned)nj), dim3(256), 0, c->stream, ztab, errs);
+            KCHECK(c);
+            HIPCHK(c, hipMemsetAsync(gr, 0, (size_t)(nGr * nj) * sizeof(MwGran), c->stream));
+            HIPCHK(c, hipMemsetAsync(zsync, 0, (size_t)nj * SYNC_HOST_WORDS * sizeof(unsigned), c->stream));
+            // 4. the merges at height 0
+            hipError_t le;
+            {
+                ProfScope ps(c, "linkage_hx_zero_jobs", 0, 24.0 * (double)maxN * (double)maxN * (double)nj);
+                le = linkage_hx_jobs_launch(c, method, workers, ztab, nj, max_dyn, errs);
+            }
+            if (le != hipSuccess) { (void)hipGetLastError(); c->stats["linkage_hx_refused"].launches += 1; continue; }      // refused: nothing ran
+            // 5. the sync words   6. who is done, who goes on
+            unsigned hw[LINKAGE_XCD_JOBS * SYNC_HOST_WORDS] = {0};
+            HIPCHK(c, hipMemcpyAsync(hw, zsync, (size_t)nj * SYNC_HOST_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            std::vector<LinkageRgJob> ch;        // the jobs of the continuation launch
+            std::vector<size_t> ca;              // ... their places in open_k
+            bool timeout = false;
+            int cap_rg = 0;
+            for (int i = 0; i < nj; ++i) {
+                const size_t a = (size_t)zp.order[(size_t)(first + i)];
+                const unsigned* w = hw + (size_t)i * SYNC_HOST_WORDS;
+                c->stats["linkage_hx_stale_scans"].flops += (double)w[SYNC_ROUNDS];
+                if (w[SYNC_TIMEOUT]) { timeout = true; continue; }
+                const int64_t k_done = (int64_t)w[SYNC_MERGES], N = open_j[a].N;
+                c->stats["linkage_xcd_zero_merges"].flops += (double)k_done;
+                if (k_done >= N - 1) { HIPCHK(c, finish(a)); continue; }
+                if (k_done <= 0) continue;
+                LinkageRgJob r = h[(size_t)open_k[a]];
+                r.sync = zsync + ch.size() * SYNC_HOST_WORDS; r.sz0 = zh[(size_t)i].size; r.ty0 = zh[(size_t)i].ty; r.k0 = (int)k_done;
+                cap_rg = std::max(cap_rg, r.cap);
+                ch.push_back(r); ca.push_back(a);
+            }
+            if (timeout) { xcd_off = true; c->stats["linkage_xcd_timeouts"].launches += 1; }
+            // 7. exact bounds of the rows still there, then k_linkage_rg's body from merge k0 on
+            if (!ch.empty() && !xcd_off) {
+                const int nc = (int)ch.size();
+                HIPCHK(c, hipMemcpyAsync(ctab, ch.data(), (size_t)nc * sizeof(LinkageRgJob), hipMemcpyHostToDevice, c->stream));
+                {
+                    ProfScope ps(c, "row_nn_mid_jobs", 0, (double)maxN * (double)maxN * 4.0 * (double)nc);
+                    hipLaunchKernelGGL(k_row_nn_mid_jobs, dim3((unsigned)((maxN - 1 + 3) / 4), (unsigned)nc), dim3(256), 0, c->stream, ctab, errs);
+                    KCHECK(c);
+                }
+                for (const LinkageRgJob& r : ch) HIPCHK(c, hipMemsetAsync(r.gran, 0, (size_t)2 * key.G * linkage_rg_slot_granules() * sizeof(MwGran), c->stream));
+                HIPCHK(c, hipMemsetAsync(zsync, 0, (size_t)nc * SYNC_HOST_WORDS * sizeof(unsigned), c->stream));
+                {
+                    ProfScope ps(c, "linkage_rg_cont_jobs", 0, 24.0 * (double)maxN * (double)maxN * (double)nc);
+                    le = linkage_rg_jobs_launch(c, method, key.G, key.TH, key.helper, ctab, nc, cap_rg, errs, true);
+                }
+                if (le != hipSuccess) (void)hipGetLastError();      // refused: redone alone
+                else {
+                    HIPCHK(c, hipMemcpyAsync(hw, zsync, (size_t)nc * SYNC_HOST_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+                    HIPCHK(c, hipStreamSynchronize(c->stream));
+                    timeout = false;
+                    for (int i = 0; i < nc; ++i) {
+                        const unsigned* w = hw + (size_t)i * SYNC_HOST_WORDS;
+                        c->stats["linkage_retry_rounds"].flops += (double)w[SYNC_ROUNDS];
+                        if (w[SYNC_TIMEOUT]) timeout = true;
+                        else if (!w[SYNC_TIE]) HIPCHK(c, finish(ca[(size_t)i]));
+                    }
+                    if (timeout) { xcd_off = true; c->stats["linkage_xcd_timeouts"].launches += 1; }
+                }
+            }
+            HIPCHK(c, hipStreamSynchronize(c->stream));      // the finished jobs' Z has arrived; the workspaces are free for the next launch
+        }
+        return SD_OK;
+    }
+
     // XCD-batched jobs xp.order[k0 .. k1) (of one group of the plan, or less), longest first: the preparation in shared launches, then k_linkage_rg_jobs on
     // every launch of the plan that lies in the range.  A job whose sync block shows neither a timeout nor a tie is done; any other -- an exact tie, a poll
     // timeout, a refused launch (all its jobs), a launch not made after a timeout -- is run again alone by run_linkage, from its rows, behind the group.
@@ -258,7 +409,7 @@ struct LinkageManyRun {
             const LinkageManyJob& q = jobs[ord[k]];
             const LinkageXcdKey& key = xp.key[(size_t)(k0 + k)];
             const int64_t N = q.N, s = linkage_xcd_ints(N) / 2;
-            h[(size_t)k] = LinkageRgJob{q.d_X, D + oD, I + oI, I + oI + s, M + oM, M + oM + N, Z + oZ, gran + oG, sync + k * SYNC_HOST_WORDS,
+            h[(size_t)k] = LinkageRgJob{q.d_X, D + oD, I + oI, I + oI + s, M + oM, M + oM + N, Z + oZ, gran + oG, sync + k * SYNC_HOST_WORDS, nullptr, nullptr,
                                         (int)N, (int)((N + key.G - 1) / key.G) + 1, (int)k, 0};
             oD += N * N; oI += 2 * s; oM += 2 * N; oZ += (N - 1) * 4; oG += (int64_t)2 * key.G * linkage_rg_slot_granules();
         }
@@ -268,6 +419,9 @@ struct LinkageManyRun {
         HIPCHK(c, hipMemsetAsync(errs, 0, (size_t)Gn * sizeof(int), c->stream));
         HIPCHK(c, hipMemsetAsync(gran, 0, (size_t)nG * sizeof(MwGran), c->stream));
         HIPCHK(c, hipMemsetAsync(sync, 0, (size_t)Gn * SYNC_HOST_WORDS * sizeof(unsigned), c->stream));
+        // option linkage_batch_xcd_zero: "has the kernel written anything?" is read from row 0 of a job's Z, as LinkageJob::coop reads it (size field >= 2 behind the first merge)
+        const bool zero_on = c->linkage_batch_xcd_zero == 1;
+        if (zero_on) HIPCHK(c, hipMemsetAsync(Z, 0, (size_t)nZ * sizeof(double), c->stream));
         {
             ProfScope ps(c, "pdist_sq_jobs", (double)(nD - nM / 2) / 2.0 * d * 3.0, (double)nD * 8.0 + (double)(nM / 2) * d * 8.0);
             if (metric == SD_METRIC_COSINE) hipLaunchKernelGGL(k_pdist_sq_jobs<true>, dim3(tiles, tiles, (unsigned)Gn), dim3(256), 0, c->stream, tab, d, errs);
@@ -313,6 +467,8 @@ struct LinkageManyRun {
         HIPCHK(c, hipMemcpyAsync(herr.data(), errs, (size_t)Gn * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         std::vector<int64_t> redo;
+        std::vector<int64_t> open_k;                 // jobs (numbers in the group) that neither failed nor finished, in plan order
+        std::vector<LinkageXcdZeroJob> open_j;       // ... and how their first launch ended
         oZ = 0;
         for (int64_t k = 0; k < Gn; ++k) {
             const LinkageManyJob& q = jobs[ord[k]];
@@ -323,8 +479,18 @@ struct LinkageManyRun {
                 status[ord[k]] = SD_OK; memcpy(q.h_Z, hZ.data() + oZ, nz * sizeof(double));
                 c->stats["linkage_xcd_jobs"].launches += 1;
             }
-            else redo.push_back(ord[k]);
+            else if (!zero_on) redo.push_back(ord[k]);
+            else {
+                open_k.push_back(k);
+                open_j.push_back(LinkageXcdZeroJob{q.N, xp.key[(size_t)(k0 + k)], ran[(size_t)k] != 0, hw[SYNC_TIMEOUT] != 0, hw[SYNC_TIE] != 0,
+                                                   ((uint64_t)hw[SYNC_TIE_HI] << 32) | hw[SYNC_TIE_LO], hZ[(size_t)oZ + 3] == 0.0});
+            }
             oZ += (int64_t)nz;
+        }
+        if (!open_k.empty()) {
+            std::vector<char> finished(open_k.size(), 0);
+            if (int rc = zero_launches(ord, h, open_k, open_j, errs, finished)) return rc;
+            for (size_t a = 0; a < open_k.size(); ++a) if (!finished[a]) redo.push_back(ord[open_k[a]]);
         }
         for (int64_t j : redo) {
             c->stats["linkage_xcd_redone"].launches += 1;

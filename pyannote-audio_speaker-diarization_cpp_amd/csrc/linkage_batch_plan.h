@@ -8,6 +8,8 @@
 // in that order, into groups whose workspaces stay within a byte budget; a job that alone exceeds the budget is a group of its own.
 // Second half of the file: the cooperative geometry of one job (linkage_geometry, which linkage.hip's linkage_plan calls) and linkage_xcd_plan, which takes
 // the single jobs of the one-XCD cooperative class eight to a launch (tools/linkage_xcd_plan_check.cpp, tests/test_linkage_xcd_plan_cpu.py).
+// Last part: what run_linkage's plan says about the heap replay (linkage_tie_plan, linkage_hx_form) and linkage_xcd_zero_plan, which keeps the jobs of an XCD
+// launch that tie at height 0 in the batch (tools/linkage_xcd_zero_plan_check.cpp, tests/test_linkage_xcd_zero_plan_cpu.py).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -183,4 +185,97 @@ inline void linkage_xcd_plan(const int64_t* N, const std::vector<int64_t>& cand,
         p.order.push_back(cand[a]); p.key.push_back(keys[a]);
     }
     if (!pick.empty()) { p.group_end.push_back((int64_t)pick.size()); p.launch_end.push_back((int64_t)pick.size()); }
+}
+
+// ---------------------------------------------------------------- ties at height 0 inside the XCD batch (option linkage_batch_xcd_zero)
+// The limits of k_linkage_hx's geometry (linkage_hx.hip asserts that its own constants are these) and what run_linkage's plan decides about the heap replay by
+// arithmetic alone (linkage.hip's linkage_plan calls linkage_tie_plan; linkage_hx_run calls linkage_hx_form).
+constexpr int LINKAGE_HX_T = 256, LINKAGE_HX_U = 4, LINKAGE_HX_GMAX = 128, LINKAGE_HX_LDS_HEAP = 8191;
+inline bool linkage_hx_fits_geom(int64_t N, int workers)
+{
+    if (workers < 1 || workers > LINKAGE_HX_GMAX || N < 3) return false;
+    return (N + workers - 1) / workers <= (int64_t)LINKAGE_HX_U * LINKAGE_HX_T;
+}
+// a tie can go to k_linkage_hx (square matrix, option linkage_tie_kernel, a geometry that fits): one XCD first, worker workgroups
+struct LinkageTie { bool replay, hx_onex; int workers; };
+inline LinkageTie linkage_tie_plan(int64_t tie_kernel, int64_t one_xcd, int num_cu, int64_t N, bool square)
+{
+    LinkageTie t = {false, false, 0};
+    if (!square || tie_kernel == 0) return t;
+    bool hx_onex = one_xcd != 0 && num_cu >= 256 && linkage_hx_fits_geom(N, 31);
+    int workers = hx_onex ? 31 : (N >= 60000 ? 127 : 63);
+    if (tie_kernel > 1) { workers = (int)tie_kernel; hx_onex = hx_onex && workers <= 31; }
+    if (workers + 1 > num_cu) workers = num_cu - 1;
+    t.replay = linkage_hx_fits_geom(N, workers); t.workers = workers; t.hx_onex = hx_onex;
+    return t;
+}
+// k_linkage_hx's dynamic LDS: 16-bit keys and positions of all entries (n <= 65 535) + as many heap values as fit beside them, at most levels 0-12.
+// The 16-bit form keeps 4 N bytes of keys and positions in LDS beside ~27 KB of static LDS: it is taken only while those leave room for at least
+// 1 024 heap values inside the budget (N <= 31 232); from there to 65 535 rows the request would exceed the CU's 160 KB and every cooperative launch
+// would be refused -- those sizes take the 32-bit form, as does every size under option linkage_hx_wide.  lc: heap values in LDS; the bytes to ask for.
+inline void linkage_hx_form(int64_t N, bool wide, bool& s16, int& lc, size_t& dyn)
+{
+    const size_t budget = 130 * 1024;
+    s16 = N <= 65535 && !wide && (size_t)4 * (size_t)N + 8 * 1024 <= budget;
+    const size_t kp_bytes = s16 ? (size_t)4 * (size_t)N : 0;
+    int64_t lc64 = kp_bytes < budget ? (int64_t)((budget - kp_bytes) / 8) : 0;
+    if (lc64 > LINKAGE_HX_LDS_HEAP) lc64 = LINKAGE_HX_LDS_HEAP;
+    if (lc64 > N - 1) lc64 = N - 1;
+    lc = (int)lc64;
+    dyn = (((size_t)lc * 8 + kp_bytes) + 15) & ~(size_t)15;
+}
+
+// A job of an XCD launch (linkage_xcd_plan) that did not finish there joins the ZERO SET iff option linkage_batch_xcd_zero is 1, it stopped at a tie whose
+// height has exactly the bits of 0.0, in front of its first merge (row 0 of its Z, zeroed before the launch, still has size 0 -- what LinkageJob::coop reads),
+// option linkage_zero_phase is on, its plan alone would send the tie to the one-XCD form of k_linkage_hx (replay && hx_onex), and option linkage_hx_wide is
+// off (only the 16-bit form of k_linkage_hx_jobs is built).  Everything else is redone alone, with the first reason that applies.
+struct LinkageXcdZeroOpts { int64_t on, zero_phase, tie_kernel, one_xcd; bool hx_wide; int num_cu; };
+struct LinkageXcdZeroJob { int64_t N; LinkageXcdKey key; bool ran, timeout, tie; uint64_t tie_bits; bool untouched; };      // a job and how its first launch ended
+enum LinkageZeroWhy { ZERO_IN = 0, ZERO_KEY_OFF, ZERO_NOT_RUN, ZERO_TIMEOUT, ZERO_NO_TIE, ZERO_TIE_ABOVE, ZERO_AFTER_MERGE, ZERO_PHASE_OFF, ZERO_NO_ONEX_REPLAY, ZERO_WIDE };
+inline LinkageZeroWhy linkage_job_xcd_zero(const LinkageXcdZeroOpts& o, const LinkageXcdZeroJob& j, int* workers = nullptr)
+{
+    if (o.on != 1) return ZERO_KEY_OFF;
+    if (!j.ran) return ZERO_NOT_RUN;
+    if (j.timeout) return ZERO_TIMEOUT;
+    if (!j.tie) return ZERO_NO_TIE;
+    if (j.tie_bits != 0) return ZERO_TIE_ABOVE;      // (-0.0 too: run_linkage compares the value, but a distance is a square root or a cosine rule's clamp, never -0)
+    if (!j.untouched) return ZERO_AFTER_MERGE;
+    if (o.zero_phase == 0) return ZERO_PHASE_OFF;
+    const LinkageTie t = linkage_tie_plan(o.tie_kernel, o.one_xcd, o.num_cu, j.N, true);
+    if (!t.replay || !t.hx_onex) return ZERO_NO_ONEX_REPLAY;
+    bool s16; int lc; size_t dyn;
+    linkage_hx_form(j.N, o.hx_wide, s16, lc, dyn);
+    if (!s16) return ZERO_WIDE;
+    if (workers) *workers = t.workers;
+    return ZERO_IN;
+}
+// device bytes a job needs beyond linkage_xcd_bytes to go through the zero launches: heap values, keys and positions; the command record and the workers'
+// reply records (granules); the workers' two change lists of `cap` entries each; size and ty.  Every part starts on a multiple of 8 bytes.
+inline int64_t linkage_xcd_zero_cap(int64_t N, int workers) { return (N + workers - 1) / workers; }
+inline int64_t linkage_xcd_zero_ints(int64_t N, int workers) { return 4 * ((N + 1) & ~(int64_t)1) + ((workers * linkage_xcd_zero_cap(N, workers) + 1) & ~(int64_t)1); }
+inline int64_t linkage_xcd_zero_doubles(int64_t N, int workers) { return N + workers * linkage_xcd_zero_cap(N, workers); }
+inline int64_t linkage_xcd_zero_granules(int workers) { return 16 + (int64_t)8 * workers; }
+inline int64_t linkage_xcd_zero_bytes(int64_t N, int workers)
+{
+    return linkage_xcd_zero_ints(N, workers) * 4 + linkage_xcd_zero_doubles(N, workers) * 8 + linkage_xcd_zero_granules(workers) * 8;
+}
+struct LinkageXcdZeroPlan {
+    std::vector<LinkageZeroWhy> why;    // per job of the input: ZERO_IN = in a launch, else why it is redone alone
+    std::vector<int64_t> order;         // the zero set: indices into the input, in input (= plan) order
+    std::vector<int> workers;           // ... the worker workgroups of each
+    std::vector<int64_t> launch_end;    // launches of order: at most LINKAGE_XCD_JOBS consecutive jobs with equal (G, TH, helper, workers)
+};
+inline void linkage_xcd_zero_plan(const LinkageXcdZeroJob* jobs, int64_t n, const LinkageXcdZeroOpts& o, LinkageXcdZeroPlan& p)
+{
+    p.why.assign((size_t)n, ZERO_KEY_OFF); p.order.clear(); p.workers.clear(); p.launch_end.clear();
+    int64_t lfirst = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        int w = 0;
+        p.why[(size_t)k] = linkage_job_xcd_zero(o, jobs[k], &w);
+        if (p.why[(size_t)k] != ZERO_IN) continue;
+        const int64_t at = (int64_t)p.order.size();
+        if (at > lfirst && (at - lfirst >= LINKAGE_XCD_JOBS || !(jobs[k].key == jobs[p.order.back()].key) || w != p.workers.back())) { p.launch_end.push_back(at); lfirst = at; }
+        p.order.push_back(k); p.workers.push_back(w);
+    }
+    if (!p.order.empty()) p.launch_end.push_back((int64_t)p.order.size());
 }

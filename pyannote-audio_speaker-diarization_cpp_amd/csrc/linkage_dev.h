@@ -218,6 +218,20 @@ __device__ __forceinline__ Min2 row_min2(const double* __restrict__ row, int64_t
     return wave_min2(m);
 }
 
+// the same for row x of a square matrix some merges into the job: only clusters still there (size != 0), and entry {x, j} from the row that was written
+// last (ty: the merge that rewrote a row last, -1 = never): one wave scans (k_row_nn_mid, k_row_nn_mid_jobs)
+__device__ __forceinline__ Min2 row_min2_mid(const double* __restrict__ D, int64_t n, const int* __restrict__ size, const int* __restrict__ ty, int64_t x)
+{
+    const int lane = threadIdx.x & 63;
+    Min2 m; m.v = INFINITY; m.i = -1; m.v2 = INFINITY;
+    if (size[x] != 0) {
+        const int tx = ty[x];
+        for (int64_t j = x + 1 + lane; j < n; j += 64)
+            if (size[j] != 0) min2_acc(m, tx >= ty[j] ? D[x * n + j] : D[j * n + x], (int)j);
+    }
+    return wave_min2(m);
+}
+
 // Lance-Williams update of the distance between cluster i and the merge of x and y, the linkage method a compile-time parameter
 // (clustering/Clustering.py:251-276 declares the seven; the codes are scipy's, also SD_LINKAGE_* in sdhip.h).  Formulas and operation order are
 // those of scipy's generic algorithm (_hierarchy_distance_update.pxi, one function per method behind fast_linkage); centroid is the
@@ -489,9 +503,11 @@ struct LinkageRgJob {
     double* Z;              // [n - 1][4]
     MwGran* gran;           // [2][G][slot granules], zeroed
     unsigned* sync;         // [SYNC_HOST_WORDS], zeroed
-    int n, cap, err, pad;
+    const int* sz0; const int* ty0;      // [n] each, read by the continuation launch only: cluster size (0 = gone) / last rewrite of every column after k0 merges
+    int n, cap, err, k0;    // k0: merges already done (the continuation launch; a first launch starts every job fresh whatever stands here)
 };
-hipError_t linkage_rg_jobs_launch(sd_ctx* c, int method, int G, int TH, int helper, const LinkageRgJob* d_jobs, int nj, int max_cap, const int* d_errs);
+// cont: the continuation launch k_linkage_rg_jobs<M, true> behind a zero launch of k_linkage_hx_jobs: every job goes on from its k0, sz0, ty0
+hipError_t linkage_rg_jobs_launch(sd_ctx* c, int method, int G, int TH, int helper, const LinkageRgJob* d_jobs, int nj, int max_cap, const int* d_errs, bool cont = false);
 // linkage_mw.hip: centroid only; at most linkage_mw_max_workgroups() workgroups; size_all = what linkage_mw_prepare set up (workspace cl_size_all)
 bool linkage_mw_has(int method);
 int linkage_mw_max_workgroups();
@@ -503,5 +519,20 @@ hipError_t linkage_mw_launch(sd_ctx* c, bool onex, bool square, int G, int TH, d
 bool linkage_hx_fits(int64_t N, int workers);
 int linkage_hx_run(sd_ctx* c, int method, bool onex, int workers, double* D, int64_t N, int* cid, int* size, int* tyv, int* nb, double* md, double* d_Z, bool* stopped,
                    double stop_above = (double)INFINITY, int64_t* merges_done = nullptr, bool* launched = nullptr);
+// k_linkage_hx_jobs: up to 8 jobs of the one-XCD, 16-bit form in one cooperative launch of 8 (workers + 1) workgroups, job x on XCD x, each up to its first
+// merge above height 0.  `workers` is the launch's; the record holds what k_linkage_hx takes per job -- every array the job's own -- and the index
+// of its error slot.  The caller has set size = 1, ty = -1, zeroed the granules and the sync block, and left matrix, bounds and ids as the preparation made them.
+struct LinkageHxJob {
+    double* D;              // [n][n] square matrix
+    int* cid; int* size; int* ty; int* nb;      // [n] each
+    double* md;             // [n]
+    double* Z;              // [n - 1][4]
+    double* hval; int* hkey; int* hpos;         // [n] each: the heap's lower tier (keys and positions: the 32-bit form's, unused by the 16-bit one)
+    MwGran* cmd; MwGran* rep;                   // [16], [workers][8], zeroed
+    int* chg_z; double* chg_v;                  // [workers][cap] each
+    unsigned* sync;         // [SYNC_HOST_WORDS], zeroed
+    int n, cap, lc, err;    // rows; columns per worker; heap values in LDS (linkage_hx_form); error slot
+};
+hipError_t linkage_hx_jobs_launch(sd_ctx* c, int method, int workers, const LinkageHxJob* d_jobs, int nj, size_t max_dyn, const int* d_errs);
 // linkage_heap.hip: the condensed matrix Dc with exact nb / md, size = 1, cid = iota; every method
 int linkage_heap_run(sd_ctx* c, int method, double* Dc, int64_t N, int* size, int* cid, int* nb, double* md, double* d_Z);

@@ -171,7 +171,10 @@ __global__ __launch_bounds__(TB) void k_linkage_rg(double* D, int n, int* cid, c
 // (STX<true>) needs every participant of a job on one XCD's L2: each of them has read that it sits on XCC x.  How the dispatcher deals the workgroups decides
 // only whether G of them arrive; if not, the bounded poll ends that job alone (SYNC_TIMEOUT in its block) and the host runs it again by itself.  A raised error
 // slot (a zero-norm row under the cosine metric): nobody touches the job.
-template <int METHOD>
+// CONT = false starts every job fresh (k0 = 0, no sz0 / ty0: the first launches).  CONT = true is the continuation launch behind k_linkage_hx_jobs:
+// a job goes on from the k0 merges the heap replay made at height 0, with the cluster sizes and last rewrites it left (sz0, ty0) and the bounds k_row_nn_mid_jobs
+// recomputed -- what LinkageJob::continue_rg hands k_linkage_rg alone, on the same body, G, threads and cap.
+template <int METHOD, bool CONT>
 __global__ __launch_bounds__(256) void k_linkage_rg_jobs(const LinkageRgJob* __restrict__ jobs, int nj, int G, int helper, const int* __restrict__ errs)
 {
     __shared__ int s_job;
@@ -187,7 +190,7 @@ __global__ __launch_bounds__(256) void k_linkage_rg_jobs(const LinkageRgJob* __r
     constexpr int UU = RG_U;
     double* D = jb.D; const int n = jb.n; int* cid = jb.cid; const int* nb0 = jb.nb; const double* md0 = jb.md; const double* md20 = jb.md2; double* Z = jb.Z;
     MwGran* gran = jb.gran; unsigned* sync = jb.sync; const int cap = jb.cap;
-    const int k0 = 0; const int* const sz0 = nullptr; const int* const ty0 = nullptr;       // a batch only ever starts jobs fresh
+    const int k0 = CONT ? jb.k0 : 0; const int* const sz0 = CONT ? jb.sz0 : nullptr; const int* const ty0 = CONT ? jb.ty0 : nullptr;
 #include "linkage_rg_body.inc"
 }
 
@@ -233,12 +236,13 @@ hipError_t linkage_rg_launch(sd_ctx* c, int method, bool onex, int G, int TH, do
     return hipLaunchCooperativeKernel(f, dim3(onex ? 8 * G : G), dim3(TT), args, dyn, c->stream);
 }
 // the caller (run_linkage_many) has planned the launch with linkage_job_xcd: the 256-thread, 4-column form, G <= 32, the helper wave counted in TH + 64 <= 256
-hipError_t linkage_rg_jobs_launch(sd_ctx* c, int method, int G, int TH, int helper, const LinkageRgJob* d_jobs, int nj, int max_cap, const int* d_errs)
+hipError_t linkage_rg_jobs_launch(sd_ctx* c, int method, int G, int TH, int helper, const LinkageRgJob* d_jobs, int nj, int max_cap, const int* d_errs, bool cont)
 {
     int TT; bool wide;
     linkage_rg_form(G, TH, max_cap, helper, TT, wide);
     const void* f = nullptr;
-    if (!wide && TT <= 256 && G >= 2 && G <= 32 && nj >= 1 && nj <= LINKAGE_XCD_JOBS) lw_dispatch(method, [&](auto M) { f = (const void*)k_linkage_rg_jobs<M.value>; });
+    if (!wide && TT <= 256 && G >= 2 && G <= 32 && nj >= 1 && nj <= LINKAGE_XCD_JOBS)
+        lw_dispatch(method, [&](auto M) { f = cont ? (const void*)k_linkage_rg_jobs<M.value, true> : (const void*)k_linkage_rg_jobs<M.value, false>; });
     if (!f) return hipErrorInvalidValue;
     const size_t dyn = (((size_t)max_cap * 9) + 15) & ~(size_t)15;      // the largest job's; a job lays its own cap out in it
     (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
