@@ -341,6 +341,40 @@ int sd_stream_push_many(sd_stream* const* s /*[S]*/, const int16_t* const* h_pcm
 int sd_stream_push_many_dev(sd_stream* const* s /*[S]*/, const int16_t* const* d_pcm /*[S]*/, const int64_t* n /*[S]*/, int64_t S);     /* sd.cpp:2937-3234, 2950 */
 int sd_stream_push_many_f32(sd_stream* const* s /*[S]*/, const float* const* h_wav /*[S]*/, const int64_t* n /*[S]*/, int64_t S);     /* sd.cpp:2937-3234, 2948-2951 */
 int sd_stream_turns_many(sd_stream* const* s /*[S]*/, int64_t S, sd_turn** turns /*[S]*/, int64_t* n_turns /*[S]*/, int32_t* status /*[S]*/);     /* sd.cpp:2937-3234 */
+/* ---- streams at any sample rate: call-centre audio arrives at 8 kHz, and sd_resample treats what it is given as a whole recording, with silence in
+ * front of it and behind it, so it cannot be called piece by piece.  After sd_stream_set_input_rate(s, in_sr) every push -- sd_stream_push / _dev / _f32
+ * and the stream's row of sd_stream_push_many* -- hands over samples at in_sr, and the stream resamples them itself (k_resample_jobs, csrc/resample.hip:
+ * the arithmetic of sd_resample on a window of the inputs).  L / M = 16000 / in_sr reduced, J the taps per wing of that pair (about 67 * max(1, M / L)),
+ * len(n) = sd_resample_len(n, in_sr, 16000).  Output m reads the inputs floor(m M / L) - J .. floor(m M / L) + J.  With n inputs pushed, output m is FINAL
+ * when no later input can change it and it belongs to the output of every longer input:
+ *     F(n) = min(len(n), #{m >= 0 : floor(m M / L) + J <= n - 1}) = min(len(n), n - 1 - J < 0 ? 0 : ((n - J) L - 1) / M + 1)      (integer division)
+ * -- by the kernel's reads, not by which taps happen to be zero.  len and F are non-decreasing: an emitted output is never taken back.
+ * sd_resample_final_len (host-only) computes F; -1 on bad arguments as sd_resample_len.
+ * The contract: with y_n = sd_resample(all n inputs so far, in_sr, 16000), after any sequence of pushes the stream is, bit for bit, a plain stream to
+ * which y_n[0 .. F(n)) was pushed with sd_stream_push_f32: sd_stream_info (which keeps counting 16 kHz samples), sd_stream_turns (turns, order, labels),
+ * sd_last_confidence, sd_last_speakers, sd_stream_read, sealing, window / forget and roster.  The stream lags the audio by the filter wing, len(n) - F(n)
+ * samples (at most 136 = 8.5 ms at 8 kHz, about 100 at the usual other rates): there are no provisional samples and the tail is never rewound.
+ * sd_stream_end_input closes the input: it emits y_n[F(n) .. len(n)) with silence behind the last input exactly as sd_resample has it, and from then on
+ * the stream is the plain stream to which all of sd_resample(x) was pushed -- sd_stream_turns is sd_diarize_f32(sd_resample(x)), what sd_diarize_wav
+ * with SD_WAV_RESAMPLE gives for the file.  Afterwards a push returns SD_ERR_ARG (in a group call: a row with n[i] > 0), a second sd_stream_end_input is
+ * SD_OK and does nothing, and sd_stream_turns, _read, _forget and the roster keep working.
+ * sd_stream_set_input_rate is legal only before the first sample is pushed; SD_ERR_ARG otherwise, for in_sr <= 0 and for a rate pair sd_resample
+ * refuses (tap table or a tile's input span too large; the stream's kernel keeps 1 KiB of the 160 KiB for its stores, so a span within 1 KiB of
+ * sd_resample's limit -- 40 705 .. 40 960 inputs per tile, rates near 1.7 MHz -- is refused here and not there).  16000 means no resampler: every push
+ * takes exactly the path of a stream without a rate, and sd_stream_end_input only closes the input -- SD_OK, pushes refused afterwards, closed = 1 -- so
+ * that a host which sets the rate from a variable ends every call the same way.
+ * A group call may hold streams with and without a rate and of different rates: still one upload, one conversion launch and one synchronisation, and
+ * at most ONE resampling launch whatever S and the rates.  An argument error leaves the stream, the inputs it holds included, as it was; so does a
+ * failed allocation of a single push before anything was launched (SD_ERR_HIP, the stream stays usable); any other SD_ERR_HIP makes the stream (in a
+ * group call: the streams of the call) unusable; a group call keeps the group's rule for a failed allocation too.  sd_stream_end_input on a stream on
+ * which no rate was ever set: SD_ERR_ARG.  Device memory per rated stream: the inputs since the buffer last turned over, in two buffers of up to
+ * 2 x (largest piece + 2 J + 512) floats each -- 1.3 MB for 10 s pieces at 8 kHz.
+ * sd_stream_input_info: the rate, the inputs pushed, the outputs final so far (F(n); len(n) once closed) and whether the input is closed; any pointer
+ * may be NULL; a stream without a rate reports 16000, n, n, 0 with n the samples pushed. */
+int sd_stream_set_input_rate(sd_stream*, int32_t in_sr);     /* frontend/resampler.cc:19-36 */
+int sd_stream_end_input(sd_stream*);     /* frontend/resampler.cc:19-36 (src_simple: end_of_input = 1) */
+int sd_stream_input_info(const sd_stream*, int32_t* in_sr, int64_t* n_in, int64_t* n_final, int32_t* closed);     /* frontend/resampler.cc:19-36 */
+int64_t sd_resample_final_len(int64_t n, int32_t in_sr, int32_t out_sr);     /* frontend/resampler.cc:19-36, 21-22 */
 
 /* ---- a speaker roster: labels that keep their meaning.  The label of a turn is a raw cluster number (sd.cpp:3433-3441) and every update of a stream
  * clusters anew, so "Speaker_1" of one update may be "Speaker_0" of the next.  A roster is a small host object that hands out persistent speaker ids.

@@ -470,6 +470,13 @@ int cut_refusal(sd_ctx* c, const char* who);
 int cut_open_dev(sd_ctx* c, const float* d_seg, const float* d_emb, int64_t chunks, int64_t n, sd_cut** out);
 // ---- resample.hip
 int resample_dev(sd_ctx* c, const float* d_in, int64_t n, int32_t in_sr, int32_t out_sr, float* d_out, int64_t n_out);
+// the windowed form behind sd_stream_set_input_rate (stream.hip; rows and plan: resample_book.h): the refusals of a rate pair, its cached tap table, and
+// ONE launch of k_resample_jobs for any number of rows
+struct ResamplePlan;
+struct ResampleJob;
+int resample_check(sd_ctx* c, int32_t in_sr, int32_t out_sr, ResamplePlan& p);
+int resample_taps(sd_ctx* c, int32_t in_sr, int32_t out_sr, const ResamplePlan& p, const float** taps);
+int resample_jobs(sd_ctx* c, const ResampleJob* rows, int64_t R);
 // ---- postseg.hip
 int run_postseg(sd_ctx* c, const float* d_seg, int64_t chunks, uint8_t* d_bin, float* d_masks, int* d_nact);
 int run_count(sd_ctx* c, const uint8_t* d_bin, int64_t chunks, int32_t* d_count, int64_t n_count, double* d_avg = nullptr);

@@ -38,6 +38,11 @@
 //                   per chunk as the audio comes in, the final turns are those of the run without the flag, bit for bit.  --stream-updates also prints,
 //                   after each piece, "== <seconds pushed> s, <sealed>/<total> chunks" and the turns so far.  With - as the wav path, headerless s16le
 //                   16 kHz mono samples are read from stdin until end of file (needs --stream).  Single GPU; not with --activity or --dump-steps
+//   --stream-rate HZ   with --stream and - : the samples on stdin are headerless s16le at HZ (an integer > 0), resampled inside the stream
+//                   (sd_stream_set_input_rate; 16000 = as without the flag); SECONDS are seconds of audio; sd_stream_end_input at end of file, before the
+//                   final turns.  The "== N s" header of a --stream-updates block counts the 16 kHz samples the stream holds so far, which trail the
+//                   audio pushed by the filter wing (8.5 ms at 8 kHz) until the end of the input.  Without
+//                   --stream, with a wav file instead of -, or with another value: usage error (exit 2)
 //   --stream-window SECONDS   with --stream: a sliding window (sd_stream_set_window with ceil(SECONDS / 16) blocks of 32 chunks): after every piece that
 //                   seals a block the stream forgets all but that many; the turns are those of the audio still held, printed with absolute times
 //                   (t + sd_stream_origin / 16000); the header of a --stream-updates block still gives the seconds pushed, its chunk counts are those of the
@@ -97,6 +102,7 @@ struct Args { const char* seg = nullptr; const char* emb = nullptr; const char* 
               int activity = -1; double act[4] = {-1.0, -1.0, -1.0, -1.0}; bool act_hamming = false;      // --activity: SD_ACTIVITY_*; onset, offset, min on, min off (-1: default)
               long long stream_piece = 0; bool stream_updates = false;         // --stream: samples per piece (0: off)
               bool stream_roster = false;                                      // --stream-roster: the labels are roster ids
+              long long stream_rate = 0; double stream_sec = 0.0;              // --stream-rate: the sample rate of stdin (0: 16 000); --stream's SECONDS as given
               const char* speakers = nullptr; double speakers_threshold = -1.0; const char* enroll = nullptr; std::vector<sd_turn> enroll_spans; bool enrolled = false;
               const char* many = nullptr;         // --speakers FILE, its threshold (-1: default), --enroll NAME and its spans
               const char* score = nullptr; const char* tune = nullptr; double collar = 0.0; bool skip_overlap = false, uem_from_ref = false;      // --score / --tune REF.rttm and how to score
@@ -480,7 +486,7 @@ static bool stream_file(StreamRun& r)
     return r.feed_f32(out.data(), (int64_t)out.size());
 }
 
-// headerless s16le 16 kHz mono samples from stdin, pushed as they arrive: reads of at most 2 MiB, an update block whenever a piece is complete
+// headerless s16le mono samples from stdin -- at 16 kHz, or at --stream-rate HZ -- pushed as they arrive: reads of at most 2 MiB, an update block whenever a piece is complete
 static bool stream_stdin(StreamRun& r)
 {
     const long long piece = r.a.stream_piece;
@@ -517,7 +523,13 @@ static int run_stream(const Args& a)
     if (sd_stream_open(ctx, &r.st) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
     if (a.stream_window >= 0 && sd_stream_set_window(r.st, a.stream_window) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
     if (a.stream_roster && (sd_roster_open(SD_EMB_DIM, &roster) != SD_OK || sd_stream_set_roster(r.st, roster) != SD_OK)) { fprintf(stderr, "--stream-roster: no roster (%s)\n", sd_last_error(ctx)); return leave(1); }
+    if (a.stream_rate > 0 && sd_stream_set_input_rate(r.st, (int32_t)a.stream_rate) != SD_OK) { fprintf(stderr, "--stream-rate %lld: %s\n", a.stream_rate, sd_last_error(ctx)); return leave(1); }
     const bool fed = std::string(a.wav) == "-" ? stream_stdin(r) : stream_file(r);
+    if (fed && a.stream_rate > 0) {      // the outputs behind the last final one, before the final turns
+        const int rc = sd_stream_end_input(r.st);
+        if (rc != SD_OK) { fprintf(stderr, "sd_stream_end_input failed (%d): %s\n", rc, sd_last_error(ctx)); return leave(1); }
+        r.bill();
+    }
     if (!fed || !r.ask()) return leave(1);
     int64_t n = 0, total = 0;
     sd_stream_info(r.st, &n, nullptr, &total);
@@ -692,6 +704,15 @@ int main(int argc, char* argv[])
             const double sec = strtod(v, &end);
             if (end == v || *end || !(sec > 0.0) || !(sec * SD_SAMPLE_RATE >= 1.0) || sec > 86400.0) { fprintf(stderr, "usage: --stream takes a number of seconds > 0, at least one sample and at most a day (got '%s')\n", v); return 2; }
             a.stream_piece = (long long)(sec * SD_SAMPLE_RATE + 0.5);
+            a.stream_sec = sec;
+        }
+        else if (s == "--stream-rate") {
+            if (i + 1 >= argc) { fprintf(stderr, "usage: --stream-rate needs a value\n"); return 2; }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            errno = 0;
+            a.stream_rate = strtoll(v, &end, 10);
+            if (end == v || *end || errno || a.stream_rate < 1 || a.stream_rate > 0x7fffffff) { fprintf(stderr, "usage: --stream-rate takes a sample rate in Hz, an integer > 0 (got '%s')\n", v); return 2; }
         }
         else if (s == "--speakers" || s == "--speakers-threshold" || s == "--enroll" || s == "--enroll-span") {
             // checked here as well: a usage error before any context is created
@@ -743,6 +764,8 @@ int main(int argc, char* argv[])
     if (a.stream_piece > 0 && a.dump_dir) { fprintf(stderr, "usage: --dump-steps describes one whole-path inference; --stream is refused with it\n"); return 2; }
     if (a.stream_window >= 0 && a.stream_piece <= 0) { fprintf(stderr, "usage: --stream-window needs --stream SECONDS\n"); return 2; }
     if (a.cl_max_num >= 1 && a.dump_dir) { fprintf(stderr, "usage: --dump-steps describes the reference's flow, which clusters every train row; --max-num-embeddings is refused with it\n"); return 2; }
+    if (a.stream_rate > 0 && (a.stream_piece <= 0 || pos.size() < 3 || std::string(pos[2]) != "-")) { fprintf(stderr, "usage: --stream-rate gives the rate of the samples on stdin: it needs --stream SECONDS and - in place of the wav file\n"); return 2; }
+    if (a.stream_rate > 0) { a.stream_piece = (long long)(a.stream_sec * (double)a.stream_rate + 0.5); if (a.stream_piece < 1) a.stream_piece = 1; }      // SECONDS are seconds of audio
     if (a.stream_roster && a.stream_piece <= 0) { fprintf(stderr, "usage: --stream-roster needs --stream SECONDS\n"); return 2; }
     if (a.stream_roster && (a.speakers || a.relabel)) { fprintf(stderr, "usage: --stream-roster prints roster ids; --speakers and --relabel name and renumber raw labels and are refused with it\n"); return 2; }
     if (a.stream_updates && a.stream_piece <= 0) { fprintf(stderr, "usage: --stream-updates needs --stream SECONDS\n"); return 2; }

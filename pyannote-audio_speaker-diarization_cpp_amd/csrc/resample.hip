@@ -16,15 +16,15 @@
 // oracle/resample_oracle.py evaluates the same definition in float64 with numpy; scipy.signal.resample_poly applies the same taps
 // independently.  One thread per output sample; the input span of a 256-output tile is staged in LDS (coalesced), the tap table
 // [tap][phase] (built on the host in double, stored as float) stays in L2: a wave reads 64 phases of one tap row.
+// That arithmetic is ONE device body, resample_point, under two kernels: k_resample (the whole recording) and k_resample_jobs (a table of windows of
+// recordings that are still arriving: the streams with an input rate of stream.hip; the rule of what is final and the rows: resample_book.h).
 #include "common.h"
+#include <algorithm>
 #include <cmath>
+#include <cstring>
+#include <vector>
 
-#define RS_ZEROS 64
-#define RS_CUTOFF 0.95
-#define RS_BETA 10.056
-#define RS_BLOCK 256
-
-static int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
+#include "resample_book.h"      // the plan of a rate pair, the two length rules, ResampleJob
 
 static double bessel_i0(double x)
 {
@@ -34,42 +34,30 @@ static double bessel_i0(double x)
     return s;
 }
 
-struct ResamplePlan { int64_t L, M; int J; int64_t span; double half, fc; };
+extern "C" int64_t sd_resample_len(int64_t n, int32_t in_sr, int32_t out_sr) { return resample_len(n, in_sr, out_sr); }
 
-static int make_plan(int32_t in_sr, int32_t out_sr, ResamplePlan& p)
+extern "C" int64_t sd_resample_final_len(int64_t n, int32_t in_sr, int32_t out_sr)
 {
-    if (in_sr <= 0 || out_sr <= 0) return 1;
-    const int64_t g = gcd64(in_sr, out_sr);
-    p.L = out_sr / g; p.M = in_sr / g;
-    const double fmax = (double)(p.L > p.M ? p.L : p.M);
-    p.fc = RS_CUTOFF / (2.0 * fmax);
-    p.half = (double)RS_ZEROS / (2.0 * p.fc);
-    p.J = (int)std::floor(p.half / (double)p.L) + 1;
-    p.span = ((RS_BLOCK - 1) * p.M) / p.L + 2 * (int64_t)p.J + 3;      // input samples a tile of RS_BLOCK outputs can touch
-    return 0;
+    ResamplePlan p;
+    if (n < 0 || make_plan(in_sr, out_sr, p)) return -1;
+    return resample_final_len(n, in_sr, out_sr, p);
 }
 
-extern "C" int64_t sd_resample_len(int64_t n, int32_t in_sr, int32_t out_sr)
+// The one device body of k_resample and k_resample_jobs: the 256 outputs from m0 on, thread per output, of which those in front of m_end exist.  The
+// tile's input span [base, base + span) is staged in LDS (coalesced; src[0] is input `first`, inputs outside [first, n_limit) read as zero), then
+// the taps of the output's phase run over it in a fixed order on two accumulators, and the sum goes to out[threadIdx.x]: the tile's place in the
+// recording for k_resample, LDS for k_resample_jobs.  A thread without an output stores nothing.
+__device__ __forceinline__ void resample_point(float* xs, const float* __restrict__ src, int64_t first, int64_t n_limit, int64_t m0, int64_t m_end,
+                                               const float* __restrict__ taps /*[2J+1][L]*/, int L, int M, int J, int span, float* __restrict__ out)
 {
-    if (n < 0 || in_sr <= 0 || out_sr <= 0) return -1;
-    const float ratio = (float)(1.0 * out_sr / in_sr);                  // resampler.cc:21 (float ratio)
-    return (int64_t)((float)(uint64_t)n * ratio);                       // resampler.cc:22: size_t * float -> float -> size_t
-}
-
-// y[m], m in [0, n_out): thread per output; xs = input samples [base, base + span) of the tile, zero outside [0, n_in)
-__global__ __launch_bounds__(RS_BLOCK) void k_resample(const float* __restrict__ x, int64_t n_in, float* __restrict__ y, int64_t n_out,
-                                                        const float* __restrict__ taps /*[2J+1][L]*/, int L, int M, int J, int span)
-{
-    extern __shared__ float xs[];
-    const int64_t m0 = (int64_t)blockIdx.x * RS_BLOCK;
     const int64_t base = (m0 * M) / L - J - 1;
     for (int i = threadIdx.x; i < span; i += RS_BLOCK) {
         const int64_t g = base + i;
-        xs[i] = (g >= 0 && g < n_in) ? x[g] : 0.0f;
+        xs[i] = (g >= first && g < n_limit) ? src[g - first] : 0.0f;
     }
     __syncthreads();
     const int64_t m = m0 + threadIdx.x;
-    if (m >= n_out) return;
+    if (m >= m_end) return;
     const int64_t t = m * M;
     const int64_t i0 = t / L;
     const int ph = (int)(t - i0 * L);
@@ -82,20 +70,57 @@ __global__ __launch_bounds__(RS_BLOCK) void k_resample(const float* __restrict__
         acc1 = fmaf(tp[(size_t)(j + J + 1) * L], xp[-j - 1], acc1);
     }
     if (j <= J) acc0 = fmaf(tp[(size_t)(j + J) * L], xp[-j], acc0);
-    y[m] = acc0 + acc1;
+    out[threadIdx.x] = acc0 + acc1;
 }
 
-// device-resident form used by sd_diarize_wav; d_out must hold sd_resample_len(n, in_sr, out_sr) floats
-int resample_dev(sd_ctx* c, const float* d_in, int64_t n, int32_t in_sr, int32_t out_sr, float* d_out, int64_t n_out)
+// y[m], m in [0, n_out): thread per output; xs = input samples [base, base + span) of the tile, zero outside [0, n_in)
+__global__ __launch_bounds__(RS_BLOCK) void k_resample(const float* __restrict__ x, int64_t n_in, float* __restrict__ y, int64_t n_out,
+                                                        const float* __restrict__ taps /*[2J+1][L]*/, int L, int M, int J, int span)
 {
-    ResamplePlan p;
+    extern __shared__ float xs[];
+    const int64_t m0 = (int64_t)blockIdx.x * RS_BLOCK;
+    resample_point(xs, x, 0, n_in, m0, n_out, taps, L, M, J, span, y + m0);
+}
+
+// Any number of windows in one launch: row r of the table (ResampleJob, resample_book.h) has tile0[r + 1] - tile0[r] tiles of RS_BLOCK outputs counted from
+// ITS first output; a block finds its row in the prefix table (cut.hip: seg_of) and runs the body on it.  Rows of different rate pairs share the launch:
+// dynamic LDS is the largest span of the call.  The tile's sums land in LDS; a full tile whose place in dst is 16-byte aligned leaves as 64 stores of
+// 16 bytes, any other tile as one float per thread; the row's last tile writes the `pad` zeros behind the last output.  64-bit indices throughout.
+__global__ __launch_bounds__(RS_BLOCK) void k_resample_jobs(const ResampleJob* __restrict__ rows, const int64_t* __restrict__ tile0 /*[R + 1]*/, int R)
+{
+    extern __shared__ float xs[];
+    __shared__ __align__(16) float ys[RS_BLOCK];
+    const int64_t tile = blockIdx.x;
+    int lo = 0, hi = R;                                                  // the last row with tile0[row] <= tile
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tile0[mid] <= tile) lo = mid; else hi = mid; }
+    const ResampleJob row = rows[lo];
+    const int64_t off = (tile - tile0[lo]) * RS_BLOCK;                   // this tile's outputs go to dst[off ...]
+    const int span = (int)(((int64_t)(RS_BLOCK - 1) * row.M) / row.L) + 2 * row.J + 3;
+    resample_point(xs, row.src, row.first, row.n_limit, row.m_first + off, row.m_first + row.count, row.taps, row.L, row.M, row.J, span, ys);
+    __syncthreads();
+    float* d = row.dst + off;
+    const int64_t left = row.count - off;                                // outputs of this tile and of the tiles behind it
+    if (left >= RS_BLOCK && ((uintptr_t)d & 15) == 0) {
+        if (threadIdx.x < RS_BLOCK / 4) reinterpret_cast<float4*>(d)[threadIdx.x] = reinterpret_cast<const float4*>(ys)[threadIdx.x];
+    } else if (threadIdx.x < left) d[threadIdx.x] = ys[threadIdx.x];
+    if (left <= RS_BLOCK) for (int64_t i = left + threadIdx.x; i < left + row.pad; i += RS_BLOCK) d[i] = 0.0f;
+}
+
+// the plan of a rate pair, or the refusals of sd_resample: a bad rate, a tap table or a tile's input span that is too large
+int resample_check(sd_ctx* c, int32_t in_sr, int32_t out_sr, ResamplePlan& p)
+{
     if (make_plan(in_sr, out_sr, p)) SD_FAIL(c, SD_ERR_ARG, "sd_resample: bad sample rate %d -> %d", in_sr, out_sr);
     const int64_t ntap = 2 * (int64_t)p.J + 1;
     if (ntap * p.L > (int64_t)64 << 20) SD_FAIL(c, SD_ERR_ARG, "sd_resample: %d -> %d Hz needs a %lld x %lld tap table (ratio %lld / %lld): unsupported rate pair",
                                                   in_sr, out_sr, (long long)ntap, (long long)p.L, (long long)p.L, (long long)p.M);
     if (p.span * (int64_t)sizeof(float) > 160 * 1024) SD_FAIL(c, SD_ERR_ARG, "sd_resample: %d -> %d Hz: a tile's input span (%lld samples) does not fit the LDS", in_sr, out_sr, (long long)p.span);
-    if (n_out <= 0) return SD_OK;
-    // tap table, double on the host, float on the device; cached per rate pair
+    return SD_OK;
+}
+
+// the tap table of a rate pair that resample_check accepted: double on the host, float on the device; cached per rate pair
+int resample_taps(sd_ctx* c, int32_t in_sr, int32_t out_sr, const ResamplePlan& p, const float** taps)
+{
+    const int64_t ntap = 2 * (int64_t)p.J + 1;
     char key[64];
     snprintf(key, sizeof(key), "rs_taps_%d_%d", in_sr, out_sr);
     // "filled" is recorded only after the upload has completed: a failed allocation or copy leaves no entry behind that a later call would trust
@@ -119,12 +144,63 @@ int resample_dev(sd_ctx* c, const float* d_in, int64_t n, int32_t in_sr, int32_t
         HIPCHK(c, hipStreamSynchronize(c->stream));                      // h goes out of scope
         c->rs_taps_filled.insert(key);
     }
+    *taps = d_taps;
+    return SD_OK;
+}
+
+// device-resident form used by sd_diarize_wav; d_out must hold sd_resample_len(n, in_sr, out_sr) floats
+int resample_dev(sd_ctx* c, const float* d_in, int64_t n, int32_t in_sr, int32_t out_sr, float* d_out, int64_t n_out)
+{
+    ResamplePlan p;
+    int rc;
+    if ((rc = resample_check(c, in_sr, out_sr, p))) return rc;
+    if (n_out <= 0) return SD_OK;
+    const float* d_taps = nullptr;
+    if ((rc = resample_taps(c, in_sr, out_sr, p, &d_taps))) return rc;
+    const int64_t ntap = 2 * (int64_t)p.J + 1;
     const size_t lds = (size_t)p.span * sizeof(float);
     if (lds > 64 * 1024) HIPCHK(c, hipFuncSetAttribute((const void*)k_resample, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int64_t blocks = (n_out + RS_BLOCK - 1) / RS_BLOCK;
     {
         ProfScope ps(c, "resample", 2.0 * (double)ntap * (double)n_out, 4.0 * (double)(n + n_out));
         hipLaunchKernelGGL(k_resample, dim3((unsigned)blocks), dim3(RS_BLOCK), lds, c->stream, d_in, n, d_out, n_out, d_taps, (int)p.L, (int)p.M, p.J, (int)p.span);
+    }
+    KCHECK(c);
+    return SD_OK;
+}
+
+// one k_resample_jobs launch for rows[0, R) (every count > 0; every rate pair accepted by resample_check); ordered on the context's stream
+int resample_jobs(sd_ctx* c, const ResampleJob* rows, int64_t R)
+{
+    if (R <= 0) return SD_OK;
+    std::vector<int64_t> tile0((size_t)R + 1, 0);
+    size_t lds = 0;
+    double flops = 0.0, bytes = 0.0;
+    for (int64_t r = 0; r < R; ++r) {
+        const ResampleJob& j = rows[r];
+        if (j.count <= 0 || j.L <= 0 || j.M <= 0 || j.J < 0 || j.pad < 0) SD_FAIL(c, SD_ERR_ARG, "resample_jobs: bad row %lld", (long long)r);
+        const int64_t span = ((int64_t)(RS_BLOCK - 1) * j.M) / j.L + 2 * (int64_t)j.J + 3;
+        if (span * (int64_t)sizeof(float) > 160 * 1024) SD_FAIL(c, SD_ERR_ARG, "resample_jobs: row %lld: a tile's input span (%lld samples) does not fit the LDS", (long long)r, (long long)span);
+        lds = std::max(lds, (size_t)span * sizeof(float));
+        tile0[(size_t)r + 1] = tile0[(size_t)r] + (j.count + RS_BLOCK - 1) / RS_BLOCK;
+        flops += 2.0 * (double)(2 * j.J + 1) * (double)j.count;
+        bytes += 4.0 * ((double)j.count * (double)j.M / (double)j.L + (double)j.count);
+    }
+    if (tile0[(size_t)R] > 0x7fffffff) SD_FAIL(c, SD_ERR_ARG, "resample_jobs: %lld tiles in one launch", (long long)tile0[(size_t)R]);
+    // the prefix table and the rows behind it: one workspace, one upload
+    static_assert(sizeof(ResampleJob) % sizeof(int64_t) == 0 && alignof(ResampleJob) <= alignof(int64_t), "the rows sit behind R + 1 int64");
+    const size_t head = ((size_t)R + 1) * sizeof(int64_t), tab_bytes = head + (size_t)R * sizeof(ResampleJob);
+    std::vector<char> tab(tab_bytes);
+    memcpy(tab.data(), tile0.data(), head);
+    memcpy(tab.data() + head, rows, (size_t)R * sizeof(ResampleJob));
+    WS(c, char, d_tab, "rs_jobs", tab_bytes);
+    HIPCHK(c, hipMemcpy(d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice));
+    const int64_t* d_tile0 = (const int64_t*)d_tab;
+    const ResampleJob* d_rows = (const ResampleJob*)(d_tab + head);
+    if (lds > 64 * 1024 - RS_BLOCK * sizeof(float)) HIPCHK(c, hipFuncSetAttribute((const void*)k_resample_jobs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    {
+        ProfScope ps(c, "resample_jobs", flops, bytes);
+        hipLaunchKernelGGL(k_resample_jobs, dim3((unsigned)tile0[(size_t)R]), dim3(RS_BLOCK), lds, c->stream, d_rows, d_tile0, (int)R);
     }
     KCHECK(c);
     return SD_OK;

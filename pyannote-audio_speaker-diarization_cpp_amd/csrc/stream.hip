@@ -9,12 +9,18 @@
 // chunk is on is seg_tile_chunks' word (many_plan.h) for the pack and for segment_pending alike; the finalize per stream is many.hip's finalize_jobs.
 // A roster attached to a stream (sd_stream_set_roster; the rule: roster.cpp) renames the labels behind a successful finalize: host arithmetic on what the
 // finalize left in the context, no launch of its own.
+// A stream with an input rate (sd_stream_set_input_rate) takes its samples at that rate: a push puts them behind the inputs the stream keeps
+// (resample_book.h) and one k_resample_jobs launch (resample.hip) writes the 16 kHz samples they made final straight behind the tail -- in a group call
+// one launch for all such streams, whatever their rates; everything behind the tail sees 16 kHz samples and is what it was.
 #include "common.h"
 #include "stream_book.h"
+#include "resample_book.h"
 #include "roster.h"
+#include "../../include/sdhip_stream_test.h"
 #include <algorithm>
 
 static_assert(SD_TAIL_PAD == SD_WAV_PAD, "the tail's padding is what DevWav::padded promises");
+static_assert(RS_HIST_SLACK >= SD_WAV_PAD, "k_pcm_to_f32 zeroes SD_WAV_PAD floats behind the inputs it converts into a stream's history");
 
 // compaction into the second buffer: dst[0, len) = src[0, len), zeros behind; four floats per thread (src sits a multiple of 8000 floats
 // behind its allocation's start, dst at the start of its own: both 16-byte aligned)
@@ -98,6 +104,7 @@ struct sd_stream {
     std::vector<int32_t> kept;                       // ... the roster id of every table row at the last update, -1 where the row had no label
     int64_t kept_origin = 0;                         // ... and the origin then: row i of the table now was row i + 3 (origin - kept_origin) / 8000
     bool has_kept = false;
+    RateBook r;                                      // sd_stream_set_input_rate: the inputs held and the outputs emitted (resample_book.h); in_sr 0 = a plain stream
 };
 
 namespace {
@@ -203,11 +210,118 @@ int check_call(sd_stream* s, const char* who)
     return SD_OK;
 }
 
+// A push to a stream with an input rate (sd_stream_set_input_rate): the piece goes behind the inputs the stream holds, ONE k_resample_jobs launch of one
+// row writes the outputs that piece made final -- [F(n), F(n')), resample_book.h -- straight behind the tail with their padding, and from there on it is
+// a push of those 16 kHz samples.  A push that makes no output final only extends the inputs held.  Growth comes first: a failed allocation leaves the
+// stream as it was, and usable.
+int push_rated(sd_stream* s, const void* src, int64_t m, int kind, const char* who)
+{
+    sd_ctx* c = s->c;
+    StreamBook& b = s->b;
+    RateBook& r = s->r;
+    if (r.closed) SD_FAIL(c, SD_ERR_ARG, "%s: the stream's input was closed by sd_stream_end_input", who);
+    if (m == 0) return SD_OK;
+    const double t0 = now_ms();
+    clear_stage_ms(c);
+    HipDev dev{c};
+    const RatePush q = rate_plan_push(r, m);
+    const float* taps = nullptr;
+    int rc;
+    if ((rc = resample_taps(c, r.in_sr, SD_SAMPLE_RATE, r.p, &taps))) return rc;      // (cached since sd_stream_set_input_rate)
+    if (!(rc = rate_reserve(dev, r, m)) && q.count > 0) rc = book_reserve_tail(dev, b, q.count);
+    if (rc) { if (dev.alloc_failed) c->stream_intact = true; return rc; }
+    float* in = r.buf[r.cur] + r.held();
+    if (kind == SD_F32_HOST) HIPCHK(c, hipMemcpyAsync(in, src, (size_t)m * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    else {
+        const int16_t* d_pcm = (const int16_t*)src;
+        if (kind == SD_PCM_HOST) {
+            WS(c, int16_t, stage, "st_pcm", m);
+            HIPCHK(c, hipMemcpyAsync(stage, src, (size_t)m * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+            d_pcm = stage;
+        }
+        hipLaunchKernelGGL(k_pcm_to_f32, GRID1(m + SD_WAV_PAD), 0, c->stream, d_pcm, in, m);      // (its zeros land in the slack behind the inputs)
+        KCHECK(c);
+    }
+    if (q.count > 0) {
+        const ResampleJob job = rate_job(r, q, b.tail_now() + b.tail_len(), taps, SD_TAIL_PAD);
+        if ((rc = resample_jobs(c, &job, 1))) return rc;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // the caller's buffer may go
+    rate_commit(r, q);
+    b.n += q.count;
+    if ((rc = seal_blocks(s, true))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->stage_ms[3] = now_ms() - t0;
+    return SD_OK;
+}
+
+// sd_stream_end_input: the outputs behind the last final one, [F(n), len(n)), with silence behind the last input as sd_resample has it; afterwards the
+// stream is a plain stream to which sd_resample of all its inputs was pushed, and takes no more
+int end_input_impl(sd_stream* s)
+{
+    sd_ctx* c = s->c;
+    const char* who = "sd_stream_end_input";
+    if (int rc = check_call(s, who)) return rc;
+    StreamBook& b = s->b;
+    RateBook& r = s->r;
+    if (!r.in_sr && !r.direct) SD_FAIL(c, SD_ERR_ARG, "%s: the stream has no input rate (sd_stream_set_input_rate)", who);
+    if (r.closed) return SD_OK;
+    if (r.direct) { r.closed = true; return SD_OK; }      // a rate of 16 000: nothing is held back, the input is just closed
+    const double t0 = now_ms();
+    clear_stage_ms(c);
+    HipDev dev{c};
+    const RatePush q = rate_plan_flush(r);
+    int rc;
+    if (q.count > 0) {
+        const float* taps = nullptr;
+        if ((rc = resample_taps(c, r.in_sr, SD_SAMPLE_RATE, r.p, &taps))) return rc;
+        if ((rc = book_reserve_tail(dev, b, q.count))) { if (dev.alloc_failed) c->stream_intact = true; return rc; }
+        const ResampleJob job = rate_job(r, q, b.tail_now() + b.tail_len(), taps, SD_TAIL_PAD);
+        if ((rc = resample_jobs(c, &job, 1))) return rc;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    rate_commit(r, q);
+    r.closed = true;
+    rate_release(dev, r);
+    b.n += q.count;
+    if ((rc = seal_blocks(s, true))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->stage_ms[3] = now_ms() - t0;
+    return SD_OK;
+}
+
+// sd_stream_set_input_rate: before the first sample only; 16 000 = no resampler (the stream only remembers that a rate was set, so that
+// sd_stream_end_input can close its input).  Nothing of the stream is touched by a refusal or a failure
+int set_rate_impl(sd_stream* s, int32_t in_sr)
+{
+    sd_ctx* c = s->c;
+    const char* who = "sd_stream_set_input_rate";
+    if (int rc = check_call(s, who)) return rc;
+    c->stream_intact = true;
+    if (in_sr <= 0) SD_FAIL(c, SD_ERR_ARG, "%s: bad sample rate %d", who, in_sr);
+    if (s->b.n > 0 || s->b.origin > 0 || s->r.n_in > 0 || s->r.closed) SD_FAIL(c, SD_ERR_ARG, "%s: samples have been pushed; the rate is set before the first one", who);
+    RateBook nb;
+    if (in_sr != SD_SAMPLE_RATE) {
+        int rc;
+        if ((rc = resample_check(c, in_sr, SD_SAMPLE_RATE, nb.p))) return rc;
+        if ((nb.p.span + RS_BLOCK) * (int64_t)sizeof(float) > 160 * 1024) SD_FAIL(c, SD_ERR_ARG, "%s: %d Hz: a tile's input span (%lld samples) does not fit the LDS", who, in_sr, (long long)nb.p.span);
+        const float* taps = nullptr;
+        if ((rc = resample_taps(c, in_sr, SD_SAMPLE_RATE, nb.p, &taps))) return rc;      // built here: no push pays for it
+        nb.in_sr = in_sr;
+    } else nb.direct = true;
+    HipDev dev{c};
+    rate_release(dev, s->r);
+    s->r = nb;
+    return SD_OK;
+}
+
 int push_impl(sd_stream* s, const void* src, int64_t m, int kind, const char* who)
 {
     sd_ctx* c = s->c;
     if (m < 0 || (m > 0 && !src)) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument", who);
     if (int rc = check_call(s, who)) return rc;
+    if (s->r.in_sr) return push_rated(s, src, m, kind, who);
+    if (s->r.closed) SD_FAIL(c, SD_ERR_ARG, "%s: the stream's input was closed by sd_stream_end_input", who);
     if (m == 0) return SD_OK;
     const double t0 = now_ms();
     clear_stage_ms(c);
@@ -415,9 +529,18 @@ int push_many_impl(sd_ctx* c, sd_stream* const* s, const void* const* src, const
     }
     int rc;
     if ((rc = group_check(c, s, S, who))) return rc;
+    // a stream with an input rate gains the outputs its piece makes final (push_rated), a plain one its piece: add[i] samples at 16 kHz
+    std::vector<RatePush> rated((size_t)S);
+    std::vector<int64_t> add(n, n + S);
+    for (int64_t i = 0; i < S; ++i) {
+        if (s[i]->r.closed && n[i] > 0) SD_FAIL(c, SD_ERR_ARG, "%s: the input of stream %lld was closed by sd_stream_end_input", who, (long long)i);
+        if (!s[i]->r.in_sr) continue;
+        rated[(size_t)i] = rate_plan_push(s[i]->r, n[i]);
+        add[(size_t)i] = rated[(size_t)i].count;
+    }
     std::vector<int64_t> n_after((size_t)S), sealed((size_t)S);
     std::vector<char> wanted((size_t)S, 1);
-    for (int64_t i = 0; i < S; ++i) { n_after[(size_t)i] = s[i]->b.n + n[i]; sealed[(size_t)i] = s[i]->b.sealed; }
+    for (int64_t i = 0; i < S; ++i) { n_after[(size_t)i] = s[i]->b.n + add[(size_t)i]; sealed[(size_t)i] = s[i]->b.sealed; }
     std::vector<PackRange> ranges;
     int64_t total = 0;
     if ((rc = group_ranges(c, S, n_after.data(), sealed.data(), wanted.data(), false, ranges, &total, who))) return rc;
@@ -429,10 +552,21 @@ int push_many_impl(sd_ctx* c, sd_stream* const* s, const void* const* src, const
     HipDev dev{c};
     std::vector<char> busy((size_t)S, 0);
     for (const PackRange& r : ranges) busy[(size_t)r.owner] = 1;
-    for (int64_t i = 0; i < S; ++i)
-        if ((n[i] > 0 || busy[(size_t)i]) && (rc = book_reserve_group(dev, s[i]->b, n[i]))) return rc;
+    for (int64_t i = 0; i < S; ++i) {
+        if ((add[(size_t)i] > 0 || busy[(size_t)i]) && (rc = book_reserve_group(dev, s[i]->b, add[(size_t)i]))) return rc;
+        if (s[i]->r.in_sr && n[i] > 0 && (rc = rate_reserve(dev, s[i]->r, n[i]))) return rc;
+    }
+    // the rows of the one k_resample_jobs launch: every stream whose piece makes an output final, whatever its rate (the tap tables are cached)
+    std::vector<ResampleJob> jobs;
+    for (int64_t i = 0; i < S; ++i) {
+        if (!s[i]->r.in_sr || add[(size_t)i] <= 0) continue;
+        const float* taps = nullptr;
+        if ((rc = resample_taps(c, s[i]->r.in_sr, SD_SAMPLE_RATE, s[i]->r.p, &taps))) return rc;
+        jobs.push_back(rate_job(s[i]->r, rated[(size_t)i], s[i]->b.tail_now() + s[i]->b.tail_len(), taps, SD_TAIL_PAD));
+    }
 
-    // the samples of all streams: host ones uploaded back to back (each placed so that it is as aligned as its place in the tail), one conversion launch
+    // the samples of all streams: host ones uploaded back to back (each placed so that it is as aligned as its place in the tail), one conversion launch;
+    // the piece of a stream with an input rate goes behind the inputs it holds, with no padding
     const size_t es = kind == SD_F32_HOST ? sizeof(float) : sizeof(int16_t);
     std::vector<GroupRow> rows;
     std::vector<size_t> off;
@@ -440,8 +574,9 @@ int push_many_impl(sd_ctx* c, sd_stream* const* s, const void* const* src, const
     for (int64_t i = 0; i < S; ++i) {
         if (n[i] <= 0) continue;
         StreamBook& b = s[i]->b;
-        float* dst = b.tail_now() + b.tail_len();
-        rows.push_back(GroupRow{src[i], dst, n[i], b.tail_cap[b.cur] - b.tail_len()});
+        const RateBook& r = s[i]->r;
+        float* dst = r.in_sr ? r.buf[r.cur] + r.held() : b.tail_now() + b.tail_len();
+        rows.push_back(GroupRow{src[i], dst, n[i], r.in_sr ? n[i] : b.tail_cap[b.cur] - b.tail_len()});
         const size_t head = (size_t)((16 - ((uintptr_t)dst & 15)) & 15) / 4;
         while ((stage_len + head) % 4 != 0) ++stage_len;
         off.push_back(stage_len);
@@ -457,8 +592,12 @@ int push_many_impl(sd_ctx* c, sd_stream* const* s, const void* const* src, const
     }
     HIPCHK(c, hipMemcpy(d_tab, rows.data(), rows.size() * sizeof(GroupRow), hipMemcpyHostToDevice));
     if ((rc = group_launch(c, 0, d_tab, rows, kind == SD_F32_HOST ? 1 : 0))) return rc;
+    if ((rc = resample_jobs(c, jobs.data(), (int64_t)jobs.size()))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));      // the callers' buffers may go: once for all streams
-    for (int64_t i = 0; i < S; ++i) s[i]->b.n += n[i];
+    for (int64_t i = 0; i < S; ++i) {
+        if (s[i]->r.in_sr) rate_commit(s[i]->r, rated[(size_t)i]);
+        s[i]->b.n += add[(size_t)i];
+    }
 
     if ((rc = group_infer(c, s, ranges, total, false, true))) return rc;
     c->stage_ms[3] = now_ms() - t0;
@@ -587,6 +726,7 @@ extern "C" void sd_stream_close(sd_stream* s)
     (void)hipSetDevice(c->device);
     HipDev dev{c};
     book_release(dev, s->b);
+    rate_release(dev, s->r);
     if (s->roster) s->roster->attached -= 1;
     c->streams.erase(std::remove(c->streams.begin(), c->streams.end(), s), c->streams.end());
     delete s;
@@ -664,4 +804,44 @@ extern "C" int sd_stream_read(sd_stream* s, int64_t chunk_lo, int64_t chunk_hi, 
     if (!s) return SD_ERR_ARG;
     ENTER(s->c);
     return guard(s, read_impl(s, chunk_lo, chunk_hi, h_seg, h_emb));
+}
+
+// ---- a stream at another sample rate (sdhip.h, "streams at any sample rate"; resample_book.h; resample.hip: k_resample_jobs)
+extern "C" int sd_stream_set_input_rate(sd_stream* s, int32_t in_sr)
+{
+    if (!s) return SD_ERR_ARG;
+    ENTER(s->c);
+    return guard(s, set_rate_impl(s, in_sr));
+}
+extern "C" int sd_stream_end_input(sd_stream* s)
+{
+    if (!s) return SD_ERR_ARG;
+    ENTER(s->c);
+    return guard(s, end_input_impl(s));
+}
+extern "C" int sd_stream_input_info(const sd_stream* s, int32_t* in_sr, int64_t* n_in, int64_t* n_final, int32_t* closed)
+{
+    if (!s) return SD_ERR_ARG;
+    const bool plain = s->r.in_sr == 0;      // its inputs are its samples: all of them final at once, those in front of the window's origin included
+    if (in_sr) *in_sr = plain ? SD_SAMPLE_RATE : s->r.in_sr;
+    if (n_in) *n_in = plain ? s->b.origin + s->b.n : s->r.n_in;
+    if (n_final) *n_final = plain ? s->b.origin + s->b.n : s->r.emitted;
+    if (closed) *closed = s->r.closed ? 1 : 0;
+    return SD_OK;
+}
+// test hook (sdhip_stream_test.h): the f32 samples the stream holds, from sample sealed * 8000 (counted from the origin) on
+extern "C" int sd_test_stream_tail(sd_stream* s, float* h_out, int64_t cap, int64_t* n, int64_t* first_sample)
+{
+    if (!s) return SD_ERR_ARG;
+    ENTER(s->c);
+    sd_ctx* c = s->c;
+    if (s->dead) SD_FAIL(c, SD_ERR_ARG, "sd_test_stream_tail: the stream is unusable after a HIP failure; close it");
+    const int64_t len = s->b.tail_len();
+    if (n) *n = len;
+    if (first_sample) *first_sample = s->b.origin + s->b.sealed * SD_HOP;
+    if (!h_out) return SD_OK;
+    if (cap < len) SD_FAIL(c, SD_ERR_ARG, "sd_test_stream_tail: the buffer holds %lld samples, %lld needed", (long long)cap, (long long)len);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (len > 0) HIPCHK(c, hipMemcpy(h_out, s->b.tail_now(), (size_t)len * sizeof(float), hipMemcpyDeviceToHost));
+    return SD_OK;
 }

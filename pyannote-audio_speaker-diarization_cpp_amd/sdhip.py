@@ -86,7 +86,10 @@ EXPORTS = [
     "sd_roster_open", "sd_roster_close", "sd_roster_load", "sd_roster_info", "sd_roster_speakers", "sd_roster_update", "sd_roster_update_last",
     "sd_relabel_turns_map", "sd_stream_set_roster", "sd_last_roster_ids",
     "sd_linkage_many",
+    "sd_stream_set_input_rate", "sd_stream_end_input", "sd_stream_input_info", "sd_resample_final_len",
 ]
+# the stream hook of include/sdhip_stream_test.h (sdhip_test.h's list is pinned name by name by tests/test_abi.py)
+STREAM_TEST_EXPORTS = ["sd_test_stream_tail"]
 # SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
 LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
 METRIC_EUCLIDEAN, METRIC_COSINE = 0, 1
@@ -243,6 +246,13 @@ def lib():
         L.sd_relabel_turns_map.argtypes = [C.POINTER(Turn), i64, vp, i64]
         L.sd_stream_set_roster.argtypes = [vp, vp]
         L.sd_last_roster_ids.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    if hasattr(L, "sd_stream_set_input_rate"):      # (likewise)
+        L.sd_stream_set_input_rate.argtypes = [vp, i32]
+        L.sd_stream_end_input.argtypes = [vp]
+        L.sd_stream_input_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]
+        L.sd_resample_final_len.restype = i64
+        L.sd_resample_final_len.argtypes = [i64, i32, i32]
+        L.sd_test_stream_tail.argtypes = [vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
     L.sd_format_turn.argtypes = [C.POINTER(Turn), C.c_char_p, C.c_int]
     L.sd_stage_ms.argtypes = [vp, C.POINTER(dbl)]
     L.sd_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
@@ -283,6 +293,12 @@ def lib():
     L.sd_test_emb_batches.argtypes = [vp, i64, i64, C.c_int, C.c_int, vp, i64]
     _lib = L
     return L
+
+
+def resample_final_len(n, in_sr, out_sr=16000):
+    """sd_resample_final_len: F(n), the outputs of n inputs at in_sr that no later input can change (include/sdhip.h, "streams at any sample rate");
+    -1 on bad arguments.  Host-only."""
+    return int(lib().sd_resample_final_len(int(n), int(in_sr), int(out_sr)))
 
 
 def linkage_method_from_name(name):
@@ -723,6 +739,29 @@ class Stream:
         o = C.c_int64(0)
         self._d._chk(lib().sd_stream_origin(self._handle(), C.byref(o)))
         return int(o.value)
+
+    def set_input_rate(self, sr):
+        """sd_stream_set_input_rate: from now on every push hands over samples at sr Hz (before the first sample only; 16000 = no resampler)"""
+        self._d._chk(lib().sd_stream_set_input_rate(self._handle(), int(sr)))
+
+    def end_input(self):
+        """sd_stream_end_input: the outputs behind the last final one, with silence behind the last input as Diarizer.resample has it; no push afterwards"""
+        self._d._chk(lib().sd_stream_end_input(self._handle()))
+
+    def input_info(self):
+        """sd_stream_input_info: (input rate, inputs pushed, outputs final so far, input closed)"""
+        sr, closed = C.c_int32(0), C.c_int32(0)
+        n_in, n_final = C.c_int64(0), C.c_int64(0)
+        self._d._chk(lib().sd_stream_input_info(self._handle(), C.byref(sr), C.byref(n_in), C.byref(n_final), C.byref(closed)))
+        return int(sr.value), int(n_in.value), int(n_final.value), int(closed.value)
+
+    def _tail(self):
+        """sd_test_stream_tail: (the f32 samples the stream holds on the device, from sample sealed * 8000 on; the index of the first of them)"""
+        n, first = C.c_int64(0), C.c_int64(0)
+        self._d._chk(lib().sd_test_stream_tail(self._handle(), None, 0, C.byref(n), C.byref(first)))
+        out = np.zeros(max(n.value, 1), np.float32)
+        self._d._chk(lib().sd_test_stream_tail(self._handle(), _ptr(out), len(out), C.byref(n), C.byref(first)))
+        return out[:n.value], int(first.value)
 
     def read(self, lo, hi, seg=True, emb=True):
         """cached rows of chunks [lo, hi): (scores [hi-lo][293][3] or None, embeddings [(hi-lo)*3][192] or None)"""
