@@ -226,6 +226,45 @@ int sd_test_pcm_to_f32(sd_ctx*, const int16_t* pcm, int64_t n, float fcanary, fl
 int sd_test_f32_to_f64(sd_ctx*, const float* a, int64_t n, float fcanary, double* b_out);
 int sd_test_mark_inactive(sd_ctx*, const int32_t* hard, const int32_t* nact, int64_t n, int32_t icanary, int32_t* hard_out);
 
+/* ---- test hooks (tests/test_input_kernels.py): the kernels IN FRONT of the two networks -- the resampler (csrc/resample.hip), the copy kernels of the streams
+ * (csrc/stream.hip), the pack and gap-mask kernels (csrc/many.hip) and the fp16 weight forms (csrc/weights_gpu.hip) -- through the function the product calls
+ * for the launch, under the contract of the hooks above: host pointers; every floating-point input is followed (for the resampler also preceded) by 256 NaN,
+ * 16-bit samples by 256 times 0x7fff; every output is preset to a canary, has 256 slack units behind it and comes back WHOLE; a case whose defined reads or
+ * writes leave its operands, or two of whose rows write the same place, is SD_ERR_ARG before any launch.
+ *
+ * sd_test_resample: k_resample through resample_dev.  x [n] at in_sr; n_out = -1 means sd_resample_len(n, in_sr, out_sr), else 0 .. that length ->
+ *   y_out [n_out + 256].  taps_out (optional): the tap table the context built and cached for the pair, [2J + 1][L], read back from the device; taps_cap
+ *   must be its size.
+ * sd_test_resample_jobs: ONE k_resample_jobs launch through resample_jobs for R rows to 16 kHz.  Row r holds inputs [first, first + held) of its
+ *   recording, given as x[x_off, x_off + held) of the shared host array x [x_len] and uploaded with 256 NaN on either side; inputs from n_limit
+ *   (<= first + held) on read as zero; outputs [m_first, m_first + count), count >= 1, and `pad` zeros go to arena[dst_off ...] of ONE destination arena
+ *   -> arena_out [arena + 256].  Tap tables come from resample_taps.  Refused: a row with first > 0 whose first summed input floor(m_first M / L) - J lies
+ *   in front of `first` (outside the kernel's contract).  When resample_jobs itself refuses the table (SD_ERR_ARG), the arena is downloaded all the same.
+ * sd_test_group_copy: which 0 = k_group_append (is_f32 = 0: src is int16), 1 = k_group_scatter, 2 = k_group_tail_move, all through group_launch; 3 =
+ *   k_tail_move, one row, through the function the single stream's seal calls.  is_f32 is read for which = 0 only.  src [src_len] floats or int16,
+ *   rows [R][4] = (src_off, dst_off, len, room) in elements, ONE destination arena -> dst_out [dst_len + 256].  Refused: src_off + len > src_len,
+ *   dst_off + room > dst_len, rows whose [dst_off, dst_off + room) overlap; for which = 3 src_off % 4 != 0, dst_off != 0 (the kernel's stated alignment) or
+ *   room < len + 512 (it has no room clamp).
+ * sd_test_many_pack: k_many_pack.  rows [R][4] = (src_off or -1 for a null source, n, base, len); a null source must have nothing to read
+ *   -> dst_out [dst_len + 256].
+ * sd_test_many_gap_masks: k_many_gap_masks.  gaps [G][2] = (first, count) -> masks_out [(total_chunks + 256) * 3][293].
+ * sd_test_weight_forms: form 0 = build_conv_w16 (k_w16_planes), 1 = build_conv_w16x (k_w_absmax, k_w16x) on a scratch layer of w [K][Cout][CinPad], CinPad a
+ *   multiple of 32, channels >= cin ignored.  halves_out: the fp16 bit patterns -- form 0: [2][K][Cout][roundup64(cin)], form 1: 2 * K * Cout * CinPad in the
+ *   layout of sd_test_pack_split_weights -- and 256 times `canary` behind them; halves_cap must be that size.  *inv_scale: 2^-e of form 1, 0 for form 0. */
+typedef struct sd_resample_case_row {
+    int32_t in_sr, pad;
+    int64_t first, held, n_limit, m_first, count, x_off, dst_off;
+} sd_resample_case_row;
+int sd_test_resample(sd_ctx*, const float* x, int64_t n, int32_t in_sr, int32_t out_sr, int64_t n_out, float canary, float* y_out, float* taps_out,
+                     int64_t taps_cap);
+int sd_test_resample_jobs(sd_ctx*, const sd_resample_case_row* rows, int64_t R, const float* x, int64_t x_len, int64_t arena, float canary, float* arena_out);
+int sd_test_group_copy(sd_ctx*, int which, int is_f32, const void* src, int64_t src_len, const int64_t* rows, int64_t R, int64_t dst_len, float canary,
+                       float* dst_out);
+int sd_test_many_pack(sd_ctx*, int is_f32, const void* src, int64_t src_len, const int64_t* rows, int64_t R, int64_t dst_len, float canary, float* dst_out);
+int sd_test_many_gap_masks(sd_ctx*, const int64_t* gaps, int64_t G, int64_t total_chunks, float canary, float* masks_out);
+int sd_test_weight_forms(sd_ctx*, const float* w, int K, int Cout, int CinPad, int cin, int form, uint16_t canary, uint16_t* halves_out, int64_t halves_cap,
+                         float* inv_scale);
+
 #ifdef __cplusplus
 }
 #endif

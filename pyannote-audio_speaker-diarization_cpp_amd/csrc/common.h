@@ -452,6 +452,14 @@ int turns_out(sd_ctx* c, const std::vector<sd_turn>& v, sd_turn** turns, int64_t
 struct ManyRow { const void* src; int64_t n, base, len; };      // src[0, n) -> dst[base, base + n), zeros in dst[base + n, base + len)
 struct ManyGap { int64_t first, count; };                         // chunks [first, first + count) belong to nobody
 dim3 many_grid(int64_t longest, int64_t table);      // x: a stride over the longest row of a table, y: a stride over the table; 256 threads
+// the launches of k_many_pack / k_many_gap_masks (d_rows / d_gaps: the table on the device, rows / gaps: the same table on the host, for the grid) and, in
+// stream.hip, of the copy kernels (which: 0 k_group_append, 1 k_group_scatter, 2 k_group_tail_move; k_tail_move: src 16-byte aligned, dst an allocation's
+// start): pack_infer, the stream stages and the hooks of input_test.hip call these
+int launch_many_pack(sd_ctx* c, const ManyRow* d_rows, const std::vector<ManyRow>& rows, int is_f32, float* d_dst, int64_t dst_len);
+int launch_many_gap_masks(sd_ctx* c, const ManyGap* d_gaps, const std::vector<ManyGap>& gaps, float* d_masks, int64_t total_chunks);
+struct GroupRow;
+int group_launch(sd_ctx* c, int which, const GroupRow* d_rows, const std::vector<GroupRow>& rows, int is_f32);
+int launch_tail_move(sd_ctx* c, float* dst, const float* src, int64_t len);
 // rows: one per slot that has a chunk, src on the device (is_f32: float samples, else 16-bit); total = many_plan's.  Leaves the scores [total][293][3]
 // and embeddings [total * 3][192] of the pack in workspaces; stage_ms[0] and [1] are counted from t0
 int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vector<PackRange>& rec, int64_t total, double t0, float** seg_out, float** emb_out);

@@ -47,6 +47,25 @@ dim3 many_grid(int64_t longest, int64_t table)
     return dim3((unsigned)gx, (unsigned)gy);
 }
 
+// the two launches, for pack_infer and for the hooks of input_test.hip: the x stride covers the longest row (gap) of the table, the y stride the table
+int launch_many_pack(sd_ctx* c, const ManyRow* d_rows, const std::vector<ManyRow>& rows, int is_f32, float* d_dst, int64_t dst_len)
+{
+    int64_t longest = 0;
+    for (const ManyRow& r : rows) longest = std::max(longest, r.len);
+    hipLaunchKernelGGL(k_many_pack, many_grid(longest, (int64_t)rows.size()), dim3(256), 0, c->stream, d_rows, (int)rows.size(), is_f32, d_dst, dst_len);
+    KCHECK(c);
+    return SD_OK;
+}
+int launch_many_gap_masks(sd_ctx* c, const ManyGap* d_gaps, const std::vector<ManyGap>& gaps, float* d_masks, int64_t total_chunks)
+{
+    int64_t longest_gap = 0;
+    for (const ManyGap& g : gaps) longest_gap = std::max(longest_gap, g.count);
+    hipLaunchKernelGGL(k_many_gap_masks, many_grid(longest_gap * SD_SPEAKERS * SD_FRAMES, (int64_t)gaps.size()), dim3(256), 0, c->stream, d_gaps, (int)gaps.size(),
+                       d_masks, total_chunks);
+    KCHECK(c);
+    return SD_OK;
+}
+
 extern "C" int sd_many_plan(const int64_t* n, int64_t R, int64_t* chunk_base, int64_t* total_chunks)
 {
     return many_plan(n, R, chunk_base, total_chunks) ? SD_ERR_ARG : SD_OK;
@@ -109,12 +128,9 @@ static int many_segment(sd_ctx* c, const float* d_pack, int64_t total, const std
 int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vector<PackRange>& rec, int64_t total, double t0, float** seg_out, float** emb_out)
 {
     std::vector<ManyGap> gaps;
-    int64_t longest = SD_WAV_PAD, longest_gap = 0;
     for (const PackRange& q : rec) {
         if (q.chunks <= 0) continue;
         gaps.push_back(ManyGap{q.base + q.chunks, q.slot() - q.chunks});
-        longest = std::max(longest, q.slot() * (int64_t)SD_HOP);
-        longest_gap = std::max(longest_gap, q.slot() - q.chunks);
     }
     rows.push_back(ManyRow{nullptr, 0, total * (int64_t)SD_HOP, SD_WAV_PAD});      // the zeroed floats behind the last slot (DevWav::padded)
 
@@ -127,16 +143,13 @@ int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vec
     WS(c, float, d_emb, "many_emb", total * 3 * SD_EMB_DIM);
     HIPCHK(c, hipMemcpy(d_tab, rows.data(), row_bytes, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d_tab + row_bytes, gaps.data(), gap_bytes, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_many_pack, many_grid(longest, (int64_t)rows.size()), dim3(256), 0, c->stream, (const ManyRow*)d_tab, (int)rows.size(), is_f32, d_pack, pack_len);
-    KCHECK(c);
-
     int rc;
+    if ((rc = launch_many_pack(c, (const ManyRow*)d_tab, rows, is_f32, d_pack, pack_len))) return rc;      // (a row is a slot, or the SD_WAV_PAD floats behind the last one)
+
     HIPCHK(c, hipMemsetAsync(d_seg, 0, (size_t)total * SD_FRAMES * 3 * sizeof(float), c->stream));      // gap rows: defined values for run_postseg
     if ((rc = many_segment(c, d_pack, total, rec, d_seg))) return rc;
     if ((rc = run_postseg(c, d_seg, total, nullptr, d_masks, nullptr))) return rc;
-    hipLaunchKernelGGL(k_many_gap_masks, many_grid(longest_gap * SD_SPEAKERS * SD_FRAMES, (int64_t)gaps.size()), dim3(256), 0, c->stream,
-                       (const ManyGap*)(d_tab + row_bytes), (int)gaps.size(), d_masks, total);
-    KCHECK(c);
+    if ((rc = launch_many_gap_masks(c, (const ManyGap*)(d_tab + row_bytes), gaps, d_masks, total))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const double t1 = now_ms();
     c->stage_ms[0] = t1 - t0;

@@ -169,7 +169,9 @@ int resample_dev(sd_ctx* c, const float* d_in, int64_t n, int32_t in_sr, int32_t
     return SD_OK;
 }
 
-// one k_resample_jobs launch for rows[0, R) (every count > 0; every rate pair accepted by resample_check); ordered on the context's stream
+// one k_resample_jobs launch for rows[0, R) (every count > 0; every rate pair accepted by resample_check); ordered on the context's stream.  A workgroup
+// holds a row's input span AND the static ys[RS_BLOCK] in LDS: a row whose span plus RS_BLOCK floats exceed 160 KB is refused with SD_ERR_ARG before
+// anything is uploaded or launched (the rule of sd_stream_set_input_rate; resample_check alone, which k_resample goes by, admits spans up to 160 KB)
 int resample_jobs(sd_ctx* c, const ResampleJob* rows, int64_t R)
 {
     if (R <= 0) return SD_OK;
@@ -180,7 +182,8 @@ int resample_jobs(sd_ctx* c, const ResampleJob* rows, int64_t R)
         const ResampleJob& j = rows[r];
         if (j.count <= 0 || j.L <= 0 || j.M <= 0 || j.J < 0 || j.pad < 0) SD_FAIL(c, SD_ERR_ARG, "resample_jobs: bad row %lld", (long long)r);
         const int64_t span = ((int64_t)(RS_BLOCK - 1) * j.M) / j.L + 2 * (int64_t)j.J + 3;
-        if (span * (int64_t)sizeof(float) > 160 * 1024) SD_FAIL(c, SD_ERR_ARG, "resample_jobs: row %lld: a tile's input span (%lld samples) does not fit the LDS", (long long)r, (long long)span);
+        if ((span + RS_BLOCK) * (int64_t)sizeof(float) > 160 * 1024)      // (the span and the kernel's static ys[RS_BLOCK]: sd_stream_set_input_rate's rule)
+            SD_FAIL(c, SD_ERR_ARG, "resample_jobs: row %lld: a tile's input span (%lld samples) and its %d outputs do not fit the LDS", (long long)r, (long long)span, RS_BLOCK);
         lds = std::max(lds, (size_t)span * sizeof(float));
         tile0[(size_t)r + 1] = tile0[(size_t)r] + (j.count + RS_BLOCK - 1) / RS_BLOCK;
         flops += 2.0 * (double)(2 * j.J + 1) * (double)j.count;

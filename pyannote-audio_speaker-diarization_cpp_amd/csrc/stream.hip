@@ -94,6 +94,27 @@ __global__ void k_group_append(const GroupRow* __restrict__ rows, int R, int is_
 __global__ void k_group_scatter(const GroupRow* __restrict__ rows, int R) { group_copy<false>(rows, R, 0); }
 __global__ void k_group_tail_move(const GroupRow* __restrict__ rows, int R) { group_copy<false>(rows, R, SD_TAIL_PAD); }
 
+// the launches of the four copy kernels, for the stages below and for the hooks of input_test.hip (common.h)
+int launch_tail_move(sd_ctx* c, float* dst, const float* src, int64_t len)
+{
+    hipLaunchKernelGGL(k_tail_move, GRID1((len + SD_TAIL_PAD + 3) / 4), 0, c->stream, src, dst, len);
+    KCHECK(c);
+    return SD_OK;
+}
+
+int group_launch(sd_ctx* c, int which, const GroupRow* d_rows, const std::vector<GroupRow>& rows, int is_f32)
+{
+    if (rows.empty()) return SD_OK;
+    int64_t longest = 1;
+    for (const GroupRow& r : rows) longest = std::max(longest, r.len + SD_TAIL_PAD);
+    const dim3 grid = many_grid(longest / 4 + 2, (int64_t)rows.size());
+    if (which == 0) hipLaunchKernelGGL(k_group_append, grid, dim3(256), 0, c->stream, d_rows, (int)rows.size(), is_f32);
+    else if (which == 1) hipLaunchKernelGGL(k_group_scatter, grid, dim3(256), 0, c->stream, d_rows, (int)rows.size());
+    else hipLaunchKernelGGL(k_group_tail_move, grid, dim3(256), 0, c->stream, d_rows, (int)rows.size());
+    KCHECK(c);
+    return SD_OK;
+}
+
 struct sd_stream {
     sd_ctx* c = nullptr;
     StreamBook b;
@@ -121,11 +142,7 @@ struct HipDev {
         HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
         return SD_OK;
     }
-    int move_tail(float* dst, const float* src, int64_t len) {
-        hipLaunchKernelGGL(k_tail_move, GRID1((len + SD_TAIL_PAD + 3) / 4), 0, c->stream, src, dst, len);
-        KCHECK(c);
-        return SD_OK;
-    }
+    int move_tail(float* dst, const float* src, int64_t len) { return launch_tail_move(c, dst, src, len); }
 };
 
 // The segmentation step of the pending range [lo, hi), lo = sealed.  PyanNet's dense layers (LSTM layer 0's input projection, the two linear layers)
@@ -464,19 +481,6 @@ int group_ranges(sd_ctx* c, int64_t S, const int64_t* n_after, const int64_t* se
     }
     if (pack_plan(out.data(), (int64_t)out.size(), total)) SD_FAIL(c, SD_ERR_ARG, "%s: a range of more than 2^40 samples", who);
     if (*total > SD_MANY_MAX_CHUNKS) SD_FAIL(c, SD_ERR_ARG, "%s: %lld packed chunks (limit %d: the rows of one call are counted in int)", who, (long long)*total, SD_MANY_MAX_CHUNKS);
-    return SD_OK;
-}
-
-int group_launch(sd_ctx* c, int which, const GroupRow* d_rows, const std::vector<GroupRow>& rows, int is_f32)
-{
-    if (rows.empty()) return SD_OK;
-    int64_t longest = 1;
-    for (const GroupRow& r : rows) longest = std::max(longest, r.len + SD_TAIL_PAD);
-    const dim3 grid = many_grid(longest / 4 + 2, (int64_t)rows.size());
-    if (which == 0) hipLaunchKernelGGL(k_group_append, grid, dim3(256), 0, c->stream, d_rows, (int)rows.size(), is_f32);
-    else if (which == 1) hipLaunchKernelGGL(k_group_scatter, grid, dim3(256), 0, c->stream, d_rows, (int)rows.size());
-    else hipLaunchKernelGGL(k_group_tail_move, grid, dim3(256), 0, c->stream, d_rows, (int)rows.size());
-    KCHECK(c);
     return SD_OK;
 }
 

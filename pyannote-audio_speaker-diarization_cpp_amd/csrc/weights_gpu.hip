@@ -40,7 +40,10 @@ __global__ void k_w16x(const float* __restrict__ W, _Float16* __restrict__ out, 
     if (idx >= rows * (size_t)cin) return;
     const size_t r = idx / (size_t)cin; const int i = (int)(idx - r * (size_t)cin);
     const float v = W[r * CinPad + i] * sc;
-    const _Float16 hi = (_Float16)v;
+    // hi takes its sign from v: the compiler contracts (_Float16)(W * sc) into ONE fused multiply-add with an addend of +0.0, which turns a weight of -0.0
+    // into +0.0 (and the residue below into -0.0) where the host conversion keeps -0.0 (tests/test_input_kernels.py: the all-zero layer showed it)
+    const unsigned short hb = (unsigned short)((__builtin_bit_cast(unsigned short, (_Float16)v) & 0x7fffu) | ((__float_as_uint(v) >> 16) & 0x8000u));
+    const _Float16 hi = __builtin_bit_cast(_Float16, hb);
     const size_t at = r * 2 * (size_t)CinPad + (size_t)(i / 32) * 64 + (size_t)((i % 32) / 8) * 16 + (size_t)(i % 8);
     out[at] = hi;
     out[at + 8] = (_Float16)(v - (float)hi);

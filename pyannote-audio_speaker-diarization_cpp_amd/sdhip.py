@@ -6,6 +6,7 @@ Names follow the reference's operator seams: segment ~ SegmentModel:
 embed ~ getEmbedding + EmbeddingModel1::infer, cluster ~ Clustering::cluster,
 diarize ~ speakerDiarization()."""
 import ctypes as C
+import math
 import os
 import numpy as np
 
@@ -43,7 +44,8 @@ GLUE_SLACK_ROWS = 256      # ... and behind those of Diarizer.ecapa_stats_case /
 ROWTAB_SLACK = 128         # slack entries behind the table of Diarizer.rowtab_case
 BE_SLACK = 256             # slack units behind every array of the Diarizer.*_case methods of the back end (binarize_case .. mark_inactive_case)
 BE_BCANARY = 0xA5          # SD_TEST_BCANARY: what their byte outputs are preset to
-FE_SLACK = 256             # slack entries (feature rows) behind every array of Diarizer.frontend_prepare_case / frontend_features_case / frontend_signals_case
+IN_SLACK = 256             # slack elements behind every array of Diarizer.resample_case .. weight_forms_case
+FE_SLACK = 256            # slack entries (feature rows) behind every array of Diarizer.frontend_prepare_case / frontend_features_case / frontend_signals_case
 
 
 class SdError(RuntimeError):
@@ -71,6 +73,7 @@ EXPORTS = [
     "sd_test_frontend_prepare", "sd_test_frontend_features", "sd_test_frontend_signals",
     "sd_test_binarize", "sd_test_count", "sd_test_gather_normalize", "sd_test_cluster_means", "sd_test_assign", "sd_test_constrained_argmax",
     "sd_test_activations", "sd_test_topk", "sd_test_assign_cuts", "sd_test_recon_cuts", "sd_test_pcm_to_f32", "sd_test_f32_to_f64", "sd_test_mark_inactive",
+    "sd_test_resample", "sd_test_resample_jobs", "sd_test_group_copy", "sd_test_many_pack", "sd_test_many_gap_masks", "sd_test_weight_forms",
     "sd_activity_scores", "sd_activity_regions", "sd_activity", "sd_activity_dev", "sd_activity_f32", "sd_activity_wav", "sd_last_activity_scores",
     "sd_stream_open", "sd_stream_push", "sd_stream_push_dev", "sd_stream_push_f32", "sd_stream_turns", "sd_stream_info", "sd_stream_read",
     "sd_stream_close", "sd_stream_sealed_chunks", "sd_stream_forget", "sd_stream_set_window", "sd_stream_origin",
@@ -289,6 +292,12 @@ def lib():
     L.sd_test_pcm_to_f32.argtypes = [vp, vp, i64, C.c_float, vp]
     L.sd_test_f32_to_f64.argtypes = [vp, vp, i64, C.c_float, vp]
     L.sd_test_mark_inactive.argtypes = [vp, vp, vp, i64, i32, vp]
+    L.sd_test_resample.argtypes = [vp, vp, i64, i32, i32, i64, C.c_float, vp, vp, i64]
+    L.sd_test_resample_jobs.argtypes = [vp, vp, i64, vp, i64, i64, C.c_float, vp]
+    L.sd_test_group_copy.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, i64, C.c_float, vp]
+    L.sd_test_many_pack.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, C.c_float, vp]
+    L.sd_test_many_gap_masks.argtypes = [vp, vp, i64, i64, C.c_float, vp]
+    L.sd_test_weight_forms.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint16, vp, i64, vp]
     L.sd_test_emb_batches.restype = i64
     L.sd_test_emb_batches.argtypes = [vp, i64, i64, C.c_int, C.c_int, vp, i64]
     _lib = L
@@ -1777,6 +1786,75 @@ class Diarizer:
         out = np.zeros(len(hard) + BE_SLACK, np.int32)
         self._chk(lib().sd_test_mark_inactive(self._h, _ptr(hard), _ptr(nact), len(hard), icanary, _ptr(out)))
         return out
+
+    # ---- the kernels in front of the networks (sd_test_* of include/sdhip_test.h, csrc/input_test.hip); IN_SLACK units of canary behind every output
+    def resample_case(self, x, in_sr, out_sr=16000, n_out=-1, want_taps=True, canary=-7776.0):
+        """sd_test_resample: x [n] float32 -> y [n_out + IN_SLACK] float32 and, with want_taps, the context's tap table [2J + 1][L] (else None)"""
+        x = np.ascontiguousarray(x, np.float32)
+        full = int(lib().sd_resample_len(len(x), int(in_sr), int(out_sr)))
+        no = full if n_out < 0 else int(n_out)
+        y = np.zeros(max(no, 0) + IN_SLACK, np.float32)
+        taps = None
+        if want_taps:
+            g = math.gcd(int(in_sr), int(out_sr))
+            Lr, Mr = out_sr // g, in_sr // g
+            J = int(np.floor(64.0 / (2.0 * (0.95 / (2.0 * max(Lr, Mr)))) / Lr)) + 1
+            taps = np.zeros((2 * J + 1, Lr), np.float32)
+        self._chk(lib().sd_test_resample(self._h, _ptr(x), len(x), int(in_sr), int(out_sr), int(n_out), canary, _ptr(y),
+                                         _ptr(taps) if want_taps else None, taps.size if want_taps else 0))
+        return y, taps
+
+    def resample_jobs_case(self, rows, x, arena, canary=-7776.0, refused=False):
+        """sd_test_resample_jobs: rows = (in_sr, pad, first, held, n_limit, m_first, count, x_off, dst_off) per row, x the shared inputs -> the arena
+        [arena + IN_SLACK] float32.  refused = True: resample_jobs must refuse the table with SD_ERR_ARG, and the arena comes back all the same."""
+        tab = np.zeros(len(rows), np.dtype([("in_sr", np.int32), ("pad", np.int32)] + [(k, np.int64) for k in ("first", "held", "n_limit", "m_first", "count", "x_off", "dst_off")]))
+        for i, r in enumerate(rows):
+            tab[i] = tuple(int(v) for v in r)
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.zeros(int(arena) + IN_SLACK, np.float32)
+        rc = lib().sd_test_resample_jobs(self._h, _ptr(tab), len(rows), _ptr(x), len(x), int(arena), canary, _ptr(out))
+        if refused:
+            assert rc == 1, rc                       # SD_ERR_ARG
+            return out
+        self._chk(rc)
+        return out
+
+    def group_copy_case(self, which, src, rows, dst_len, canary=-7776.0):
+        """sd_test_group_copy: which 0 k_group_append (src int16 or float32), 1 k_group_scatter, 2 k_group_tail_move, 3 k_tail_move; rows [R][4] =
+        (src_off, dst_off, len, room) -> [dst_len + IN_SLACK] float32"""
+        src = np.ascontiguousarray(src)
+        assert src.dtype in (np.float32, np.int16) and (src.dtype == np.float32 or which == 0)
+        rows = np.ascontiguousarray(rows, np.int64).reshape(-1, 4)
+        out = np.zeros(int(dst_len) + IN_SLACK, np.float32)
+        self._chk(lib().sd_test_group_copy(self._h, int(which), int(src.dtype == np.float32), _ptr(src), len(src), _ptr(rows), len(rows), int(dst_len), canary, _ptr(out)))
+        return out
+
+    def many_pack_case(self, src, rows, dst_len, canary=-7776.0):
+        """sd_test_many_pack: src int16 or float32, rows [R][4] = (src_off or -1, n, base, len) -> [dst_len + IN_SLACK] float32"""
+        src = np.ascontiguousarray(src)
+        assert src.dtype in (np.float32, np.int16)
+        rows = np.ascontiguousarray(rows, np.int64).reshape(-1, 4)
+        out = np.zeros(int(dst_len) + IN_SLACK, np.float32)
+        self._chk(lib().sd_test_many_pack(self._h, int(src.dtype == np.float32), _ptr(src), len(src), _ptr(rows), len(rows), int(dst_len), canary, _ptr(out)))
+        return out
+
+    def many_gap_masks_case(self, gaps, total_chunks, canary=-7776.0):
+        """sd_test_many_gap_masks: gaps [G][2] = (first, count) -> [(total_chunks + IN_SLACK) * 3][293] float32"""
+        gaps = np.ascontiguousarray(gaps, np.int64).reshape(-1, 2)
+        out = np.zeros(((int(total_chunks) + IN_SLACK) * 3, 293), np.float32)
+        self._chk(lib().sd_test_many_gap_masks(self._h, _ptr(gaps), len(gaps), int(total_chunks), canary, _ptr(out)))
+        return out
+
+    def weight_forms_case(self, w, cin, form, canary=0xC0DE):
+        """sd_test_weight_forms: w [K][Cout][CinPad] float32; form 0: the fp16 planes [2][K][Cout][roundup64(cin)], form 1: the split form of
+        sd_test_pack_split_weights -> (uint16 bit patterns with IN_SLACK canaries behind them, inverse scale)"""
+        w = np.ascontiguousarray(w, np.float32)
+        K, Cout, CinPad = w.shape
+        halves = 2 * K * Cout * (CinPad if form else (cin + 63) // 64 * 64)
+        out = np.zeros(halves + IN_SLACK, np.uint16)
+        inv = C.c_float(0.0)
+        self._chk(lib().sd_test_weight_forms(self._h, _ptr(w), K, Cout, CinPad, int(cin), int(form), canary, _ptr(out), out.size, C.byref(inv)))
+        return out, np.float32(inv.value)
 
     def read_ws(self, name, dtype, count, offset=0):
         """test hook: `count` elements of the named device workspace"""

@@ -30,7 +30,9 @@ def test_library_loads_and_exports_every_declared_symbol_without_lab_hooks():
                                     "sd_test_frontend_prepare", "sd_test_frontend_features", "sd_test_frontend_signals",
                                     "sd_test_binarize", "sd_test_count", "sd_test_gather_normalize", "sd_test_cluster_means", "sd_test_assign",
                                     "sd_test_constrained_argmax", "sd_test_activations", "sd_test_topk", "sd_test_assign_cuts", "sd_test_recon_cuts",
-                                    "sd_test_pcm_to_f32", "sd_test_f32_to_f64", "sd_test_mark_inactive"}
+                                    "sd_test_pcm_to_f32", "sd_test_f32_to_f64", "sd_test_mark_inactive",
+                                    "sd_test_resample", "sd_test_resample_jobs", "sd_test_group_copy", "sd_test_many_pack", "sd_test_many_gap_masks",
+                                    "sd_test_weight_forms"}
     # the lab hooks of the linkage / barrier measurements are out of the product library, not just out of the header
     for name in ("sd_bench_barrier", "sd_bench_linkage_parts"):
         assert not hasattr(L, name), name
