@@ -534,6 +534,44 @@ int sd_diarize_many_dev(sd_ctx*, const int16_t* const* d_pcm /*[R]*/, const int6
 int sd_diarize_many_f32(sd_ctx*, const float* const* h_wav /*[R]*/, const int64_t* n /*[R]*/, int64_t R, sd_turn** turns /*[R]*/, int64_t* n_turns /*[R]*/, int32_t* status /*[R]*/);     /* sd.cpp:2937-3234, 2948-2951 */
 int sd_many_select(sd_ctx*, int64_t r);     /* sd.cpp:2149-2167, 2191-2207 */
 
+/* ---- recordings in their own rate and encoding: the head of speakerDiarization() (sd.cpp:2937-2951: WavReader, / 32768) and the dormant resample leg
+ * (frontend/resampler.cc:19-36) for every recording of a pack, on the device.  Telephony files are 8 kHz, mostly G.711 at one byte per sample, often
+ * stereo with one party per channel; sd_diarize_many_audio* takes them as they are and fills the packed waveform in one kernel launch (k_many_ingest,
+ * csrc/ingest.hip) -- no per-recording sd_resample, no round trip.
+ * THE RULE.  A recording a defines 16 kHz mono floats y in three steps.
+ *   1. Decode.  SD_ENC_S16: v * 2^-15 (sd.cpp:2950).  SD_ENC_F32: the value itself.  SD_ENC_MULAW: with u = ~code, t = (((u & 15) << 3) + 132) <<
+ *      ((u >> 4) & 7), s = t - 132, negative when u & 0x80; the sample is s * 2^-15.  SD_ENC_ALAW: with a = code ^ 0x55, e = (a >> 4) & 7, m = a & 15,
+ *      s = e ? ((m << 4) + 264) << (e - 1) : (m << 4) + 8, positive when a & 0x80; the sample is s * 2^-15.  These are ITU-T G.711's tables;
+ *      sd_g711_decode (host-only) returns s for n codes.
+ *   2. Channel.  Channel c of frame i is element i * channels + c.  channel == -1 is SD_WAV_DOWNMIX's rule: s = +0.0f, s += x_q in channel order in
+ *      float, then s / (float)channels correctly rounded.
+ *   3. Rate.  At 16 000 Hz y is that sequence; at any other rate y = sd_resample(x, n, sample_rate, 16000), of length sd_resample_len(n, sample_rate,
+ *      16000).  sd_audio_len16 (host-only) returns that length, or -1 for a bad descriptor (n < 0 or n > 2^40, sample_rate <= 0, an unknown encoding,
+ *      channels < 1, channel outside [-1, channels)).
+ * THE CONTRACT.  Recording r gets, byte for byte, what sd_diarize_f32(ctx, y_r, len_r) gives for it alone -- turns, order, labels, confidences,
+ * sd_last_speakers and sd_last_enrolled after sd_many_select(r), status -- in any order of the pack and under every option sd_diarize_many_f32 honours.
+ * A recording whose y has no chunk (n == 0 included) gets SD_ERR_SHORT and the others go on.  _dev: data are device pointers.
+ * Refused with SD_ERR_ARG, nothing touched, the recording named: a null data with n > 0; a bad descriptor (above); a rate pair sd_resample refuses or
+ * whose tile span does not fit the LDS next to the tile's outputs (sd_stream_set_input_rate's rule); for _dev a pointer not aligned to its element; and
+ * everything sd_diarize_many refuses (a dump directory, a planted workload, the pack limits counted on sd_audio_len16, the enrolled refusals).
+ * sd_read_wav_audio (host-only): a wav file as such a recording -- format tag 1 with 16 bits, tag 7 (mu-law) or tag 6 (A-law) with 8 bits, any channel
+ * count and rate; *data = the raw data bytes, malloc'd (free), *desc filled with channel = 0.  Any other file is SD_ERR_ARG: the caller falls back to
+ * sd_read_wav / sd_read_wav_f32, which are unchanged. */
+enum { SD_ENC_S16 = 0, SD_ENC_F32 = 1, SD_ENC_MULAW = 2, SD_ENC_ALAW = 3 };
+typedef struct sd_audio {
+    const void* data;      /* n * channels interleaved elements: int16, float, or one G.711 code per byte */
+    int64_t n;             /* sample frames */
+    int32_t sample_rate;   /* > 0 */
+    int32_t encoding;      /* SD_ENC_* */
+    int32_t channels;      /* >= 1 */
+    int32_t channel;       /* 0 .. channels-1: that channel; -1: the mean of all (SD_WAV_DOWNMIX's rule) */
+} sd_audio;
+int64_t sd_audio_len16(const sd_audio*);     /* resampler.cc:21-22 */
+int sd_g711_decode(int32_t encoding, const uint8_t* codes, int64_t n, int16_t* out);     /* ITU-T G.711; the reference reads PCM only (wav.h:99-122) */
+int sd_read_wav_audio(const char* path, sd_audio* desc, void** data);     /* wav.h:62-126 */
+int sd_diarize_many_audio(sd_ctx*, const sd_audio* rec /*[R]*/, int64_t R, sd_turn** turns /*[R]*/, int64_t* n_turns /*[R]*/, int32_t* status /*[R]*/);     /* sd.cpp:2937-3234, 2948-2951; resampler.cc:19-36 */
+int sd_diarize_many_audio_dev(sd_ctx*, const sd_audio* rec /*[R]*/, int64_t R, sd_turn** turns /*[R]*/, int64_t* n_turns /*[R]*/, int32_t* status /*[R]*/);     /* sd.cpp:2937-3234, 2948-2951; resampler.cc:19-36 */
+
 /* ---- scoring against a ground truth (host-only, no context, no GPU).  The reference has no counterpart: it prints turns and measures nothing.
  * sd_der is the diarization error rate of pyannote.metrics' DiarizationErrorRate, restated:
  *  - the time line is cut at every start and end of a turn of ref and of hyp (and of a uem span and a collar zone, below).  In an elementary interval of

@@ -352,6 +352,7 @@ extern "C" int sd_read_wav_f32(const char* path, float** wav, int64_t* n, int32_
     return wav_read_f32(path, wav, n, sample_rate, channels, bits_per_sample);
 }
 extern "C" void sd_free_wav(float* p) { free(p); }
+extern "C" int sd_read_wav_audio(const char* path, sd_audio* desc, void** data) { return wav_read_audio(path, desc, data); }
 
 // ------------------------------------------------------------------ output formats
 // Relabelling.  The reference prints the raw cluster index (sd.cpp:3439).  pyannote.audio renames the clusters on the way

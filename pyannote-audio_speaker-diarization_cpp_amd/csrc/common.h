@@ -463,6 +463,11 @@ int launch_tail_move(sd_ctx* c, float* dst, const float* src, int64_t len);
 // rows: one per slot that has a chunk, src on the device (is_f32: float samples, else 16-bit); total = many_plan's.  Leaves the scores [total][293][3]
 // and embeddings [total * 3][192] of the pack in workspaces; stage_ms[0] and [1] are counted from t0
 int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vector<PackRange>& rec, int64_t total, double t0, float** seg_out, float** emb_out);
+// ---- ingest.hip: the fill step of sd_diarize_many_audio* (rows and plan: ingest_plan.h): the table as one block of bytes, [tile0: rows + 1 int64][rows],
+// and ONE launch of k_many_ingest over it; many.hip and the hook of ingest_test.hip call these
+struct IngestRow;
+std::vector<char> many_ingest_table(const std::vector<IngestRow>& rows, const std::vector<int64_t>& tile0);
+int launch_many_ingest(sd_ctx* c, const char* d_tab, const std::vector<IngestRow>& rows, const std::vector<int64_t>& tile0, int64_t max_span, float* d_dst, int64_t dst_len);
 // the form of the samples an entry was handed, for the entries that come in three (sd_diarize_many*, sd_stream_push*, sd_stream_push_many*)
 enum SampleForm { SD_PCM_HOST, SD_PCM_DEV, SD_F32_HOST };
 // finalize, one job after the other, of a call with J outputs (sd_diarize_many*: recordings; sd_stream_turns_many: streams).  Presets turns / n_turns /

@@ -63,8 +63,12 @@
 //                   (sd_voiceprint_wav) replaces or is appended as NAME in FILE (created when absent); prints "enrolled NAME from N windows".
 //                   A bad value of any of these is a usage error (exit 2) before anything touches the GPU
 //   --many LIST     instead of the wav argument: LIST names one wav file per line (empty lines and lines that start with # are skipped); all of them go
-//                   through the two networks together (sd_diarize_many_f32) and each gets the turns of a run of its own, bit for bit.  Every file is read
-//                   with the --resample / --downmix / --assume-16k rules of the single-file path.  Output: a line "== <path>" and that file's turns, in
+//                   through the two networks together (sd_diarize_many_audio) and each gets the turns of a run of its own, bit for bit.  Every file is read
+//                   with the --resample / --downmix / --assume-16k rules of the single-file path.  16-bit PCM, mu-law (format tag 7) and A-law (tag 6)
+//                   files of any rate and channel count go to the GPU as they are and are decoded, downmixed and resampled there while the packed
+//                   waveform is filled -- no sd_resample per file; a multi-channel G.711 file needs --downmix and is refused without it, an off-rate
+//                   file without --resample is refused as in the single-file path.  8- and 32-bit PCM, and multi-channel PCM without --downmix (read
+//                   as the reference reads it), go through the host readers into the same call.  Output: a line "== <path>" and that file's turns, in
 //                   list order; a file that cannot be read, is refused or is too short gets "== <path>: <message>" and the exit status is 1.
 //                   --rttm DIR writes DIR/<file name without .wav>.rttm per recording; --speakers (with or without --enrolled) and --relabel work per
 //                   recording.  Refused with --gpus N > 1, --stream, --activity, --dump-steps and --enroll
@@ -369,6 +373,29 @@ static bool many_load(sd_ctx* ctx, const char* path, int flags, std::vector<floa
     return true;
 }
 
+// ---- --many: a file sd_read_wav_audio can describe -- 16-bit PCM, mu-law, A-law -- goes to sd_diarize_many_audio as it is: decoded, downmixed and resampled on
+// the device while the pack is filled, no sd_resample per file.  true: desc / data are set (the caller frees data); false with an empty msg: not such a
+// file, or multi-channel PCM without --downmix, whose "first n interleaved samples" reading stays many_load's; false with a msg: refused
+static bool many_describe(const char* path, int flags, sd_audio& desc, void*& data, std::string& msg)
+{
+    data = nullptr;
+    if (sd_read_wav_audio(path, &desc, &data) != SD_OK) return false;
+    auto drop = [&]() { free(data); data = nullptr; return false; };
+    const bool g711 = desc.encoding != SD_ENC_S16;
+    if (desc.channels > 1 && !(flags & SD_WAV_DOWNMIX)) {
+        if (g711) msg = std::to_string(desc.channels) + " channels of G.711; pass --downmix to diarize their mean (one channel of a file: sd_diarize_many_audio)";
+        return drop();
+    }
+    if (desc.channels > 1) desc.channel = -1;
+    if (flags & SD_WAV_ASSUME_16K) desc.sample_rate = 16000;
+    if (desc.sample_rate != 16000 && !(flags & SD_WAV_RESAMPLE)) {
+        if (g711) msg = "sample rate " + std::to_string(desc.sample_rate) + " Hz; the pipeline needs 16000 -- pass SD_WAV_RESAMPLE / --resample (or SD_WAV_ASSUME_16K / --assume-16k)";
+        return drop();      // (a PCM file: many_load refuses it with wav_load's own line)
+    }
+    if (desc.n <= 0) { msg = "holds no samples"; return drop(); }
+    return true;
+}
+
 static int run_many(const Args& a)
 {
     std::vector<std::string> paths; std::string err;
@@ -377,21 +404,26 @@ static int run_many(const Args& a)
     if (a.speakers && !g.read(a.speakers)) return 1;
     sd_ctx* ctx = open_context(a);
     if (!ctx) return 1;
-    auto leave = [&](int rc) { sd_destroy(ctx); return rc; };
-    if (a.enrolled && !enrol_gallery(ctx, a, g)) return leave(1);
     const size_t P = paths.size();
     std::vector<std::vector<float>> wav(P);
+    std::vector<void*> raw(P, nullptr);
+    auto leave = [&](int rc) { for (void* p : raw) free(p); sd_destroy(ctx); return rc; };
+    if (a.enrolled && !enrol_gallery(ctx, a, g)) return leave(1);
     std::vector<std::string> msg(P);
-    std::vector<const float*> rows; std::vector<int64_t> lens; std::vector<size_t> who;      // the files that were read
-    for (size_t i = 0; i < P; ++i)
-        if (many_load(ctx, paths[i].c_str(), a.wav_flags, wav[i], msg[i])) {
+    std::vector<sd_audio> rows; std::vector<int64_t> lens; std::vector<size_t> who;      // the files that were read
+    for (size_t i = 0; i < P; ++i) {
+        sd_audio d{};
+        if (many_describe(paths[i].c_str(), a.wav_flags, d, raw[i], msg[i])) { rows.push_back(d); lens.push_back(sd_audio_len16(&d)); who.push_back(i); continue; }
+        if (!msg[i].empty()) continue;
+        if (many_load(ctx, paths[i].c_str(), a.wav_flags, wav[i], msg[i])) {      // the rest: 16 kHz mono floats from the host readers, in the same call
             if (wav[i].empty()) { msg[i] = "holds no samples"; continue; }
-            rows.push_back(wav[i].data()); lens.push_back((int64_t)wav[i].size()); who.push_back(i);
+            rows.push_back(sd_audio{wav[i].data(), (int64_t)wav[i].size(), 16000, SD_ENC_F32, 1, 0}); lens.push_back((int64_t)wav[i].size()); who.push_back(i);
         }
+    }
     const size_t R = rows.size();
     std::vector<sd_turn*> turns(R ? R : 1, nullptr); std::vector<int64_t> nt(R ? R : 1, 0); std::vector<int32_t> status(R ? R : 1, SD_OK);
     if (R > 0) {
-        const int rc = sd_diarize_many_f32(ctx, rows.data(), lens.data(), (int64_t)R, turns.data(), nt.data(), status.data());
+        const int rc = sd_diarize_many_audio(ctx, rows.data(), (int64_t)R, turns.data(), nt.data(), status.data());
         if (rc != SD_OK) { fprintf(stderr, "diarization failed (%d): %s\n", rc, sd_last_error(ctx)); return leave(1); }
         double ms[4]; sd_stage_ms(ctx, ms);
         fprintf(stderr, "%zu recordings: segmentation %.1f ms, embedding %.1f ms, clustering %.1f ms, call %.1f ms\n", R, ms[0], ms[1], ms[2], ms[3]);

@@ -6,6 +6,7 @@
 // nobody's: their masks are zeroed, frontend_prepare drops their items as dead, finalize never sees their rows.
 //   k_many_pack       one launch: the samples of every recording into its slot (16-bit: x 1/32768 as k_pcm_to_f32; f32: copied), zeros behind them
 //   k_many_gap_masks  one launch: zero mask rows for the gap chunks of every slot
+//   (sd_diarize_many_audio*: k_many_ingest, ingest.hip, fills the pack instead -- recordings in their own rate and encoding)
 // Both walk a table indexed by recording; every store is guarded by the row's own slot length and by the length of the destination.
 // pack_infer, the inference over a filled table, and finalize_jobs, the finalize per output, are shared with the group calls of stream.hip, whose slots
 // hold ranges of streams.  A slot is a PackRange (many_plan.h) built by pack_range (stream_book.h): a recording is the pending range of a
@@ -13,6 +14,8 @@
 #include "common.h"
 #include "stream_book.h"
 #include "linkage_batch_plan.h"
+#include "ingest_plan.h"
+#include "resample_book.h"
 #include <algorithm>
 #include <utility>
 
@@ -125,26 +128,27 @@ static int many_segment(sd_ctx* c, const float* d_pack, int64_t total, const std
 }
 
 // ------------------------------------------------------------------ both networks once over the pack (shard_infer's steps; the segmentation step is many_segment)
-int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vector<PackRange>& rec, int64_t total, double t0, float** seg_out, float** emb_out)
+// The fill step is the caller's: it is handed `fill_bytes` of table workspace on the device (the gaps' table sits behind them), the pack and its length,
+// uploads its table and launches the kernel that writes every slot and the SD_WAV_PAD floats behind the last one -- launch_many_pack for
+// sd_diarize_many* and the stream group calls, launch_many_ingest for sd_diarize_many_audio*.  Everything behind it is the same code.
+static int pack_infer_fill(sd_ctx* c, size_t fill_bytes, const std::function<int(char*, float*, int64_t)>& fill, const std::vector<PackRange>& rec, int64_t total, double t0,
+                           float** seg_out, float** emb_out)
 {
     std::vector<ManyGap> gaps;
     for (const PackRange& q : rec) {
         if (q.chunks <= 0) continue;
         gaps.push_back(ManyGap{q.base + q.chunks, q.slot() - q.chunks});
     }
-    rows.push_back(ManyRow{nullptr, 0, total * (int64_t)SD_HOP, SD_WAV_PAD});      // the zeroed floats behind the last slot (DevWav::padded)
-
     const int64_t pack_len = total * (int64_t)SD_HOP + SD_WAV_PAD;
-    const size_t row_bytes = rows.size() * sizeof(ManyRow), gap_bytes = gaps.size() * sizeof(ManyGap);
+    const size_t row_bytes = (fill_bytes + 15) / 16 * 16, gap_bytes = gaps.size() * sizeof(ManyGap);
     WS(c, float, d_pack, "many_wav", pack_len);
     WS(c, char, d_tab, "many_tab", row_bytes + gap_bytes);
     WS(c, float, d_seg, "many_seg", total * SD_FRAMES * 3);
     WS(c, float, d_masks, "many_masks", total * 3 * SD_FRAMES);
     WS(c, float, d_emb, "many_emb", total * 3 * SD_EMB_DIM);
-    HIPCHK(c, hipMemcpy(d_tab, rows.data(), row_bytes, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d_tab + row_bytes, gaps.data(), gap_bytes, hipMemcpyHostToDevice));
     int rc;
-    if ((rc = launch_many_pack(c, (const ManyRow*)d_tab, rows, is_f32, d_pack, pack_len))) return rc;      // (a row is a slot, or the SD_WAV_PAD floats behind the last one)
+    if ((rc = fill(d_tab, d_pack, pack_len))) return rc;
 
     HIPCHK(c, hipMemsetAsync(d_seg, 0, (size_t)total * SD_FRAMES * 3 * sizeof(float), c->stream));      // gap rows: defined values for run_postseg
     if ((rc = many_segment(c, d_pack, total, rec, d_seg))) return rc;
@@ -160,6 +164,16 @@ int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vec
     c->stage_ms[1] = now_ms() - t1;
     *seg_out = d_seg; *emb_out = d_emb;
     return SD_OK;
+}
+
+int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vector<PackRange>& rec, int64_t total, double t0, float** seg_out, float** emb_out)
+{
+    rows.push_back(ManyRow{nullptr, 0, total * (int64_t)SD_HOP, SD_WAV_PAD});      // the zeroed floats behind the last slot (DevWav::padded)
+    const size_t row_bytes = rows.size() * sizeof(ManyRow);
+    return pack_infer_fill(c, row_bytes, [&](char* d_tab, float* d_pack, int64_t pack_len) -> int {
+        HIPCHK(c, hipMemcpy(d_tab, rows.data(), row_bytes, hipMemcpyHostToDevice));
+        return launch_many_pack(c, (const ManyRow*)d_tab, rows, is_f32, d_pack, pack_len);      // (a row is a slot, or the SD_WAV_PAD floats behind the last one)
+    }, rec, total, t0, seg_out, emb_out);
 }
 
 // ------------------------------------------------------------------ the dendrograms of a group call, ahead of the per-job finalize
@@ -313,6 +327,96 @@ extern "C" int sd_diarize_many_f32(sd_ctx* c, const float* const* h_wav, const i
 {
     ENTER(c);
     return many_run(c, (const void* const*)h_wav, SD_F32_HOST, n, R, turns, n_turns, status, "sd_diarize_many_f32");
+}
+
+// ------------------------------------------------------------------ recordings in their own rate and encoding
+// The second front of the pack: the slots are planned on len16 (ingest_plan.h), the sources go up as they are -- every one at a 16-byte aligned offset of
+// one workspace, only the bytes the rule reads -- and ONE k_many_ingest launch (ingest.hip) decodes, picks or averages the channels, resamples and pads
+// them into the pack.  The tap tables come from resample_taps, once per distinct rate of the call and before the launch; no k_resample* launch and no
+// synchronisation stands in front of the pack.  Behind the fill it is pack_infer_fill and finalize_jobs, as for sd_diarize_many*.
+static_assert(SD_TAIL_PAD == SD_WAV_PAD, "ingest_plan.h sizes the pad row by SD_TAIL_PAD");
+static int many_audio_run(sd_ctx* c, const sd_audio* a, bool dev, int64_t R, sd_turn** turns, int64_t* n_turns, int32_t* status, const char* who)
+{
+    // refusals: nothing is touched
+    if (!a || !turns || !n_turns || !status || R < 1) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument (R >= 1)", who);
+    if (!c->dump_dir.empty()) SD_FAIL(c, SD_ERR_ARG, "%s: a dump directory is set (the step files describe one recording)", who);
+    if (c->planted_n > 0) SD_FAIL(c, SD_ERR_ARG, "%s: a planted workload is set (its chunk range means one recording)", who);
+    IngestPlan plan;
+    const int why = ingest_plan(a, R, c->seg_batch_chunks, true, plan);
+    const long long bad = (long long)plan.bad;
+    switch (why) {
+    case INGEST_OK: break;
+    case INGEST_BAD_DESC: SD_FAIL(c, SD_ERR_ARG, "%s: recording %lld: bad descriptor (n >= 0, sample_rate > 0, an SD_ENC_* encoding, channels >= 1, channel in [-1, channels))", who, bad);
+    case INGEST_NULL_DATA: SD_FAIL(c, SD_ERR_ARG, "%s: recording %lld is a null pointer", who, bad);
+    case INGEST_RATE_TABLE: {
+        ResamplePlan p;
+        const int rc = resample_check(c, a[plan.bad].sample_rate, SD_SAMPLE_RATE, p);      // its own message, the recording in front of it
+        const std::string msg = c->err;
+        SD_FAIL(c, SD_ERR_ARG, "%s: recording %lld: %s", who, bad, rc ? msg.c_str() : "unsupported rate pair");
+    }
+    case INGEST_RATE_LDS: SD_FAIL(c, SD_ERR_ARG, "%s: recording %lld: %d -> %d Hz: a tile's input span and its %d outputs do not fit the LDS", who, bad, a[plan.bad].sample_rate, SD_SAMPLE_RATE, RS_BLOCK);
+    case INGEST_BYTES: SD_FAIL(c, SD_ERR_ARG, "%s: recording %lld holds more than 2^42 bytes", who, bad);
+    case INGEST_PACK_LIMITS:
+        if (plan.bad >= 0) SD_FAIL(c, SD_ERR_ARG, "%s: recording %lld: more than 2^40 samples at 16 kHz", who, bad);
+        if (plan.total > SD_MANY_MAX_CHUNKS) SD_FAIL(c, SD_ERR_ARG, "%s: %lld packed chunks (limit %d: the rows of one call are counted in int)", who, (long long)plan.total, SD_MANY_MAX_CHUNKS);
+        SD_FAIL(c, SD_ERR_ARG, "%s: bad argument (at most 2^20 recordings of at most 2^40 samples)", who);
+    default: SD_FAIL(c, SD_ERR_ARG, "%s: the pack has too many tiles for one launch", who);
+    }
+    if (dev)
+        for (int64_t r = 0; r < R; ++r)
+            if (a[r].n > 0 && ((uintptr_t)a[r].data % (uintptr_t)ingest_elem_bytes(a[r].encoding)) != 0)
+                SD_FAIL(c, SD_ERR_ARG, "%s: recording %lld: the device pointer is not aligned to its %d-byte elements", who, (long long)r, ingest_elem_bytes(a[r].encoding));
+    int rc;
+    if ((rc = enrolled_refusal(c, SD_EMB_DIM, c->num_clusters, c->min_clusters, c->max_clusters))) return rc;
+
+    const double t0 = now_ms();
+    clear_stage_ms(c);
+    const std::vector<PackRange>& rec = plan.rec;
+    const int64_t total = plan.total;
+    rc = finalize_jobs(c, R, turns, n_turns, status, [&](std::vector<FinalJob>& jobs) -> int {
+        if (total <= 0) return SD_OK;
+        const size_t S = plan.owner.size();      // rows with a source; the pad row is behind them
+        // tap tables first: building one synchronises, a cached one costs nothing
+        for (size_t k = 0; k < S; ++k) {
+            IngestRow& w = plan.rows[k];
+            if (w.L == w.M) continue;
+            const int32_t sr = a[plan.owner[k]].sample_rate;
+            ResamplePlan p;
+            if (int e = resample_check(c, sr, SD_SAMPLE_RATE, p)) return e;
+            if (int e = resample_taps(c, sr, SD_SAMPLE_RATE, p, &w.taps)) return e;
+        }
+        if (dev) for (size_t k = 0; k < S; ++k) plan.rows[k].src = a[plan.owner[k]].data;
+        else {
+            WS(c, char, d_src, "many_src", (size_t)plan.upload_bytes);
+            for (size_t k = 0; k < S; ++k) {
+                HIPCHK(c, hipMemcpyAsync(d_src + plan.src_off[k], a[plan.owner[k]].data, (size_t)plan.src_bytes[k], hipMemcpyHostToDevice, c->stream));
+                plan.rows[k].src = d_src + plan.src_off[k];
+            }
+        }
+        const std::vector<char> tab = many_ingest_table(plan.rows, plan.tile0);
+        float *d_seg = nullptr, *d_emb = nullptr;
+        if (int e = pack_infer_fill(c, tab.size(), [&](char* d_tab, float* d_pack, int64_t pack_len) -> int {
+                HIPCHK(c, hipMemcpy(d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice));
+                return launch_many_ingest(c, d_tab, plan.rows, plan.tile0, plan.max_span, d_pack, pack_len);
+            }, rec, total, t0, &d_seg, &d_emb)) return e;
+        for (const PackRange& q : rec) jobs[(size_t)q.owner] = FinalJob{d_seg + (size_t)q.base * SD_FRAMES * 3, d_emb + (size_t)q.base * 3 * SD_EMB_DIM, q.chunks, q.n};
+        return SD_OK;
+    });
+    if (rc) return rc;
+    c->stage_ms[3] = now_ms() - t0;
+    return SD_OK;
+}
+
+extern "C" int sd_diarize_many_audio(sd_ctx* c, const sd_audio* rec, int64_t R, sd_turn** turns, int64_t* n_turns, int32_t* status)
+{
+    ENTER(c);
+    return many_audio_run(c, rec, false, R, turns, n_turns, status, "sd_diarize_many_audio");
+}
+
+extern "C" int sd_diarize_many_audio_dev(sd_ctx* c, const sd_audio* rec, int64_t R, sd_turn** turns, int64_t* n_turns, int32_t* status)
+{
+    ENTER(c);
+    return many_audio_run(c, rec, true, R, turns, n_turns, status, "sd_diarize_many_audio_dev");
 }
 
 extern "C" int sd_many_select(sd_ctx* c, int64_t r)

@@ -43,35 +43,8 @@ extern "C" int64_t sd_resample_final_len(int64_t n, int32_t in_sr, int32_t out_s
     return resample_final_len(n, in_sr, out_sr, p);
 }
 
-// The one device body of k_resample and k_resample_jobs: the 256 outputs from m0 on, thread per output, of which those in front of m_end exist.  The
-// tile's input span [base, base + span) is staged in LDS (coalesced; src[0] is input `first`, inputs outside [first, n_limit) read as zero), then
-// the taps of the output's phase run over it in a fixed order on two accumulators, and the sum goes to out[threadIdx.x]: the tile's place in the
-// recording for k_resample, LDS for k_resample_jobs.  A thread without an output stores nothing.
-__device__ __forceinline__ void resample_point(float* xs, const float* __restrict__ src, int64_t first, int64_t n_limit, int64_t m0, int64_t m_end,
-                                               const float* __restrict__ taps /*[2J+1][L]*/, int L, int M, int J, int span, float* __restrict__ out)
-{
-    const int64_t base = (m0 * M) / L - J - 1;
-    for (int i = threadIdx.x; i < span; i += RS_BLOCK) {
-        const int64_t g = base + i;
-        xs[i] = (g >= first && g < n_limit) ? src[g - first] : 0.0f;
-    }
-    __syncthreads();
-    const int64_t m = m0 + threadIdx.x;
-    if (m >= m_end) return;
-    const int64_t t = m * M;
-    const int64_t i0 = t / L;
-    const int ph = (int)(t - i0 * L);
-    const float* xp = xs + (i0 - base);                                 // xp[-j] = x[i0 - j]
-    const float* tp = taps + ph;
-    float acc0 = 0.0f, acc1 = 0.0f;
-    int j = -J;
-    for (; j + 1 <= J; j += 2) {
-        acc0 = fmaf(tp[(size_t)(j + J) * L], xp[-j], acc0);
-        acc1 = fmaf(tp[(size_t)(j + J + 1) * L], xp[-j - 1], acc1);
-    }
-    if (j <= J) acc0 = fmaf(tp[(size_t)(j + J) * L], xp[-j], acc0);
-    out[threadIdx.x] = acc0 + acc1;
-}
+// The one device body of k_resample and k_resample_jobs (and of the off-rate tiles of k_many_ingest, ingest.hip): resample_point
+#include "resample_dev.h"
 
 // y[m], m in [0, n_out): thread per output; xs = input samples [base, base + span) of the tile, zero outside [0, n_in)
 __global__ __launch_bounds__(RS_BLOCK) void k_resample(const float* __restrict__ x, int64_t n_in, float* __restrict__ y, int64_t n_out,
@@ -79,7 +52,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_resample(const float* __restrict__
 {
     extern __shared__ float xs[];
     const int64_t m0 = (int64_t)blockIdx.x * RS_BLOCK;
-    resample_point(xs, x, 0, n_in, m0, n_out, taps, L, M, J, span, y + m0);
+    resample_point(xs, RsLoadF32{x}, 0, n_in, m0, n_out, taps, L, M, J, span, y + m0);
 }
 
 // Any number of windows in one launch: row r of the table (ResampleJob, resample_book.h) has tile0[r + 1] - tile0[r] tiles of RS_BLOCK outputs counted from
@@ -96,7 +69,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_resample_jobs(const ResampleJob* _
     const ResampleJob row = rows[lo];
     const int64_t off = (tile - tile0[lo]) * RS_BLOCK;                   // this tile's outputs go to dst[off ...]
     const int span = (int)(((int64_t)(RS_BLOCK - 1) * row.M) / row.L) + 2 * row.J + 3;
-    resample_point(xs, row.src, row.first, row.n_limit, row.m_first + off, row.m_first + row.count, row.taps, row.L, row.M, row.J, span, ys);
+    resample_point(xs, RsLoadF32{row.src}, row.first, row.n_limit, row.m_first + off, row.m_first + row.count, row.taps, row.L, row.M, row.J, span, ys);
     __syncthreads();
     float* d = row.dst + off;
     const int64_t left = row.count - off;                                // outputs of this tile and of the tiles behind it

@@ -127,6 +127,44 @@ inline int wav_read_f32(const char* path, float** wav, int64_t* n, int32_t* samp
     return SD_OK;
 }
 
+// sd_read_wav_audio: the file as it is, for sd_diarize_many_audio -- the header walk of wav_open_data, but the format tag (h + 20) is read: tag 1 with 16
+// bits (SD_ENC_S16), tag 7 with 8 bits (mu-law), tag 6 with 8 bits (A-law); any channel count >= 1, any rate > 0; the data bytes counted by
+// data_bytes_present, whole frames only.  *data = the malloc'd raw bytes (free), *desc filled with data = *data and channel = 0.  Any other file --
+// other tags or depths (WAVE_FORMAT_EXTENSIBLE, float, 24-bit, 8-bit PCM), a header that ends early -- is SD_ERR_ARG with nothing allocated.
+inline int wav_read_audio(const char* path, sd_audio* desc, void** data)
+{
+    if (!path || !desc || !data) return SD_ERR_ARG;
+    *data = nullptr;
+    unsigned char h[22];
+    uint16_t tag = 0;
+    {
+        FILE* f0 = fopen(path, "rb");
+        if (!f0) return SD_ERR_ARG;
+        const size_t got = fread(h, 1, 22, f0);
+        fclose(f0);
+        if (got != 22) return SD_ERR_ARG;
+        memcpy(&tag, h + 20, 2);
+    }
+    uint32_t sr, dsz; uint16_t ch, bits;
+    FILE* fp = wav_open_data(path, &sr, &ch, &bits, &dsz);
+    if (!fp) return SD_ERR_ARG;
+    int32_t enc;
+    if (tag == 1 && bits == 16) enc = SD_ENC_S16;
+    else if (tag == 7 && bits == 8) enc = SD_ENC_MULAW;
+    else if (tag == 6 && bits == 8) enc = SD_ENC_ALAW;
+    else { fclose(fp); return SD_ERR_ARG; }
+    if (ch < 1 || sr == 0 || sr > 0x7fffffffu) { fclose(fp); return SD_ERR_ARG; }
+    const int64_t frame = (int64_t)ch * (bits / 8), n = (int64_t)dsz / frame, bytes = n * frame;
+    unsigned char* buf = (unsigned char*)malloc((size_t)(bytes > 0 ? bytes : 1));
+    if (!buf) { fclose(fp); return SD_ERR_ARG; }
+    const size_t got = fread(buf, 1, (size_t)bytes, fp);
+    fclose(fp);
+    if (got < (size_t)bytes) memset(buf + got, enc == SD_ENC_S16 ? 0 : enc == SD_ENC_MULAW ? 0xff : 0xd5, (size_t)bytes - got);      // (cannot happen: the bytes were counted; silence in each law)
+    *data = buf;
+    desc->data = buf; desc->n = n; desc->sample_rate = (int32_t)sr; desc->encoding = enc; desc->channels = ch; desc->channel = 0;
+    return SD_OK;
+}
+
 // ---- the loading rule of sd_diarize_wav / sd_activity_wav / sd_voiceprint_wav and of the command line (flags = SD_WAV_*):
 //   the 16-bit reader's int16 samples when the rate is 16 000 (or ASSUME_16K: the reference's behaviour, sd.cpp:2940-2942) and the file is not
 //   multi-channel under DOWNMIX -- the common case stays int16 up to the GPU;

@@ -48,6 +48,33 @@ IN_SLACK = 256             # slack elements behind every array of Diarizer.resam
 FE_SLACK = 256            # slack entries (feature rows) behind every array of Diarizer.frontend_prepare_case / frontend_features_case / frontend_signals_case
 
 
+ENC_S16, ENC_F32, ENC_MULAW, ENC_ALAW = 0, 1, 2, 3      # SD_ENC_*
+_ENC_DTYPES = {ENC_S16: np.int16, ENC_F32: np.float32, ENC_MULAW: np.uint8, ENC_ALAW: np.uint8}
+
+
+class AudioDesc(C.Structure):
+    """sd_audio"""
+    _fields_ = [("data", C.c_void_p), ("n", C.c_int64), ("sample_rate", C.c_int32), ("encoding", C.c_int32), ("channels", C.c_int32), ("channel", C.c_int32)]
+
+
+class Audio:
+    """One recording of Diarizer.diarize_many_audio (sd_audio): data = the interleaved elements as they arrive -- int16 (ENC_S16), float32 (ENC_F32) or
+    one G.711 code per uint8 (ENC_MULAW / ENC_ALAW) --, n frames of `channels` elements at sample_rate Hz; channel = the one to take, -1 = the mean of all.
+    For diarize_many_audio_dev data is a device pointer (an int) and n must be given."""
+
+    def __init__(self, data, sample_rate=16000, encoding=ENC_S16, channels=1, channel=0, n=None):
+        self.sample_rate, self.encoding, self.channels, self.channel = int(sample_rate), int(encoding), int(channels), int(channel)
+        if isinstance(data, (int, np.integer)):
+            self.data, self.ptr, self.n = None, int(data), int(n)
+        else:
+            self.data = np.ascontiguousarray(data, _ENC_DTYPES.get(self.encoding, np.uint8)).reshape(-1)
+            self.n = len(self.data) // max(self.channels, 1) if n is None else int(n)
+            self.ptr = self.data.ctypes.data if self.data.size else 0
+
+    def desc(self):
+        return AudioDesc(self.ptr or None, self.n, self.sample_rate, self.encoding, self.channels, self.channel)
+
+
 class SdError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libsdhip error %d: %s" % (code, msg))
@@ -90,9 +117,12 @@ EXPORTS = [
     "sd_relabel_turns_map", "sd_stream_set_roster", "sd_last_roster_ids",
     "sd_linkage_many",
     "sd_stream_set_input_rate", "sd_stream_end_input", "sd_stream_input_info", "sd_resample_final_len",
+    "sd_audio_len16", "sd_g711_decode", "sd_read_wav_audio", "sd_diarize_many_audio", "sd_diarize_many_audio_dev",
 ]
 # the stream hook of include/sdhip_stream_test.h (sdhip_test.h's list is pinned name by name by tests/test_abi.py)
 STREAM_TEST_EXPORTS = ["sd_test_stream_tail"]
+# the hook of k_many_ingest, include/sdhip_ingest_test.h (likewise)
+INGEST_TEST_EXPORTS = ["sd_test_many_ingest"]
 # SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
 LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
 METRIC_EUCLIDEAN, METRIC_COSINE = 0, 1
@@ -256,6 +286,14 @@ def lib():
         L.sd_resample_final_len.restype = i64
         L.sd_resample_final_len.argtypes = [i64, i32, i32]
         L.sd_test_stream_tail.argtypes = [vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
+    if hasattr(L, "sd_diarize_many_audio"):      # (likewise)
+        L.sd_audio_len16.restype = i64
+        L.sd_audio_len16.argtypes = [C.POINTER(AudioDesc)]
+        L.sd_g711_decode.argtypes = [i32, vp, i64, vp]
+        L.sd_read_wav_audio.argtypes = [C.c_char_p, C.POINTER(AudioDesc), C.POINTER(vp)]
+        for f in (L.sd_diarize_many_audio, L.sd_diarize_many_audio_dev):
+            f.argtypes = [vp, C.POINTER(AudioDesc), i64, vp, vp, vp]
+        L.sd_test_many_ingest.argtypes = [vp, vp, i64, vp, i64, i64, C.c_float, vp]
     L.sd_format_turn.argtypes = [C.POINTER(Turn), C.c_char_p, C.c_int]
     L.sd_stage_ms.argtypes = [vp, C.POINTER(dbl)]
     L.sd_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
@@ -459,6 +497,35 @@ def read_wav_f32(path):
     arr = np.ctypeslib.as_array(p, shape=(total,)).copy()
     lib().sd_free_wav(p)
     return arr[:n.value], sr.value, ch.value, bits.value
+
+
+def g711_decode(encoding, codes):
+    """sd_g711_decode (host-only): uint8 codes of ENC_MULAW / ENC_ALAW -> the int16 values of ITU-T G.711's tables"""
+    codes = np.ascontiguousarray(codes, np.uint8).reshape(-1)
+    out = np.zeros(len(codes), np.int16)
+    rc = lib().sd_g711_decode(int(encoding), _ptr(codes) if len(codes) else None, len(codes), _ptr(out) if len(codes) else None)
+    if rc != 0:
+        raise SdError(rc, "sd_g711_decode: bad argument")
+    return out
+
+
+def audio_len16(audio):
+    """sd_audio_len16 (host-only): the 16 kHz samples an Audio defines, -1 for a bad descriptor"""
+    d = audio.desc()
+    return int(lib().sd_audio_len16(C.byref(d)))
+
+
+def read_wav_audio(path):
+    """sd_read_wav_audio (host-only): a wav of 16-bit PCM, mu-law or A-law as an Audio holding the file's own bytes (channel = 0)"""
+    d, p = AudioDesc(), C.c_void_p()
+    rc = lib().sd_read_wav_audio(str(path).encode(), C.byref(d), C.byref(p))
+    if rc != 0:
+        raise SdError(rc, "cannot read wav as audio " + str(path))
+    dt = _ENC_DTYPES[d.encoding]
+    count = d.n * d.channels
+    data = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(max(count * np.dtype(dt).itemsize, 1),))[:count * np.dtype(dt).itemsize].copy().view(dt)
+    lib().sd_free_pcm(C.cast(p, C.POINTER(C.c_int16)))
+    return Audio(data, d.sample_rate, d.encoding, d.channels, d.channel, n=d.n)
 
 
 def _turn_array(turns):
@@ -1232,6 +1299,29 @@ class Diarizer:
         """sd_diarize_many_dev: device pointers of int16 recordings and their lengths"""
         return self._many(lib().sd_diarize_many_dev, [int(p) for p in d_pcm_ptrs], lengths)
 
+    def _many_audio(self, fn, recordings):
+        R = len(recordings)
+        arr = (AudioDesc * max(R, 1))(*[a.desc() for a in recordings])
+        turns = (C.POINTER(Turn) * max(R, 1))()
+        nt = (C.c_int64 * max(R, 1))()
+        status = (C.c_int32 * max(R, 1))()
+        self._chk(fn(self._h, arr, R, turns, nt, status))
+        self._last_d = EMB_DIM
+        out = []
+        for r in range(R):
+            t = self._turns(turns[r], C.c_int64(nt[r]))
+            out.append(t if status[r] == 0 else int(status[r]))
+        return out
+
+    def diarize_many_audio(self, recordings):
+        """sd_diarize_many_audio: a list of Audio in their own rate, encoding and channel layout -> list of (turns | error code), each what diarize_f32
+        gives for that recording's 16 kHz mono samples alone"""
+        return self._many_audio(lib().sd_diarize_many_audio, recordings)
+
+    def diarize_many_audio_dev(self, recordings):
+        """sd_diarize_many_audio_dev: the same for Audio whose data are device pointers"""
+        return self._many_audio(lib().sd_diarize_many_audio_dev, recordings)
+
     def many_select(self, r):
         """sd_many_select: recording r of the last diarize_many* call becomes the last job of last_confidence / last_speakers / last_enrolled"""
         self._chk(lib().sd_many_select(self._h, int(r)))
@@ -1836,6 +1926,19 @@ class Diarizer:
         rows = np.ascontiguousarray(rows, np.int64).reshape(-1, 4)
         out = np.zeros(int(dst_len) + IN_SLACK, np.float32)
         self._chk(lib().sd_test_many_pack(self._h, int(src.dtype == np.float32), _ptr(src), len(src), _ptr(rows), len(rows), int(dst_len), canary, _ptr(out)))
+        return out
+
+    def many_ingest_case(self, rows, src, dst_len, canary=-7776.0, refused=False):
+        """sd_test_many_ingest (include/sdhip_ingest_test.h): rows [R][8] = (encoding, channels, channel, sample_rate, n, src_off in bytes or -1, base, len),
+        src = the bytes of all sources -> [dst_len + IN_SLACK] float32.  refused = True: the hook must refuse the table with SD_ERR_ARG before any launch."""
+        src = np.ascontiguousarray(src).view(np.uint8).reshape(-1)
+        rows = np.ascontiguousarray(rows, np.int64).reshape(-1, 8)
+        out = np.zeros(int(dst_len) + IN_SLACK, np.float32)
+        rc = lib().sd_test_many_ingest(self._h, _ptr(rows), len(rows), _ptr(src) if src.size else None, src.size, int(dst_len), canary, _ptr(out))
+        if refused:
+            assert rc == 1, rc                       # SD_ERR_ARG
+            return out
+        self._chk(rc)
         return out
 
     def many_gap_masks_case(self, gaps, total_chunks, canary=-7776.0):
