@@ -53,6 +53,8 @@ int64_t sd_test_emb_batches(const int32_t* nvalid, int64_t n, int64_t batch_item
  * same bits as "conv_glds"; default 1), "conv_stagger" (128 x 128 f32 kernel: half of
  * the workgroups start half a tile late; 0 off (default, no effect measured), 1 / 2), "conv_w256_kmin" (shortest contraction that tile
  * takes), "conv_pn" / "conv_pn128" (column tiles per super-block), "ecapa_ld_pad" (elements added to the activation rows, multiple of 8),
+ * "conv_res2_ws" (f32 Res2Net convs -- Cin = Cout = 128, 3 taps, a row table over one row space, M >= 2 048 -- on the weight-stationary kernel,
+ * conv_res2.hip; 0 = on the 128 x 128 kernel as before; same bits; default 1), "conv_res2_wgs" (that kernel's workgroups, 0 .. 4 096; 0 = one per CU (default); same bits),
  * "seg_shared_conv0" (1 = SincNet's first convolution once over the waveform instead of once per overlapping chunk), "seg_wide_ih" (1 = LSTM input
  * projections of layers 1-3 on the 256 x 256 tile), "linkage_square" (-1 auto, 0 condensed, 1 full N x N distance matrix), "ecapa_f16_hp" /
  * "ecapa_keep_cat" (precision diagnostics of tools/diag_fp16_layers.py), "linkage_kernel" (-1 auto / 1: k_linkage_rg for the square matrix where its geometry fits,

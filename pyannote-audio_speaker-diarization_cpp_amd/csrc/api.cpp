@@ -137,6 +137,8 @@ extern "C" int sd_set_option(sd_ctx* c, const char* key, int64_t v)
     else if (k == "conv_rot") { if (v < 0 || v > 3) return SD_ERR_ARG; c->conv_rot = (int)v; }
     else if (k == "conv_stagger") { if (v < 0 || v > 2) return SD_ERR_ARG; c->conv_stagger = (int)v; }
     else if (k == "conv_w256_f32") c->conv_w256_f32 = v != 0;
+    else if (k == "conv_res2_ws") c->conv_res2_ws = v != 0;      // f32 Res2Net convs on the weight-stationary kernel (conv_res2.hip); 0 = the 128 x 128 kernel; same bits
+    else if (k == "conv_res2_wgs") { if (v < 0 || v > 4096) return SD_ERR_ARG; c->conv_res2_wgs = (int)v; }
     else if (k == "conv_pn") c->conv_pn = (int)v;
     else if (k == "ecapa_ld_pad") { if (v < 0 || v > 1024 || ((int64_t)v & 7)) return SD_ERR_ARG; c->ecapa_ld_pad = (int)v; }
     else if (k == "seg_shared_conv0") c->seg_shared_conv0 = v != 0;

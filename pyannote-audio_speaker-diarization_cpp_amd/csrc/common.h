@@ -39,7 +39,7 @@ inline std::atomic<long long> g_ws_alloc_us{0}, g_ws_free_us{0};
 inline std::atomic<size_t> g_ws_alloc_bytes{0}, g_ws_allocs{0};
 inline std::atomic<size_t> g_ws_limit{0};          // test hook (option ws_limit_mb): a workspace request above this many bytes fails like an exhausted GPU; 0 = off
 // per-device "dynamic-LDS attribute set" masks of the wide conv kernels (the attribute belongs to the device's code object, the launch to a context)
-inline std::atomic<unsigned> g_attr_w256{0}, g_attr_g256{0}, g_attr_pp{0};
+inline std::atomic<unsigned> g_attr_w256{0}, g_attr_g256{0}, g_attr_pp{0}, g_attr_res2{0};
 struct DevBuf {
     void* p = nullptr; size_t cap = 0;
     int reserve(size_t bytes) {
@@ -199,6 +199,8 @@ struct sd_ctx {
     int conv_mfma16 = 1;                        // fp16 LDS-DMA wide kernel on v_mfma_f32_16x16x32_f16 (higher clock under load) instead of 32x32x16; conv_gemm_g.hip
     int conv_rot = 3;                           // LDS-DMA wide kernel: the workgroups that share a row panel request its quarters in rotated order (conv_gemm_g.hip); tuning
     int conv_stagger = 0;                       // 128 x 128 f32 kernel: start half of the workgroups half a tile late (0 off, 1 odd, 2 upper half); tuning
+    bool conv_res2_ws = true;                   // f32 Res2Net convs (Cin = Cout = 128, 3 taps, M >= 2 048): the weight-stationary kernel (conv_res2.hip); 0 = the 128 x 128 kernel; same bits; A-B
+    int conv_res2_wgs = 0;                      // ... its workgroups (0 = one per CU); tuning / test: the bits do not depend on it
     bool conv_glds_f32 = false;                 // f32: the LDS-DMA staged form of the wide tile (conv_gemm_g.hip, P = 0): bit-identical, measured slower; A-B only
     bool conv_pp = true;                        // fp16 mode: the never-drained kernel for the wide layers (conv_gemm_p.hip, round 6); 0 = conv_gemm_g.hip; A-B
     bool conv_glds = true;                      // fp16 mode: ... staged by LDS-DMA (conv_gemm_g.hip) instead of through registers; tuning / A-B
@@ -340,7 +342,7 @@ struct ConvProfWide {
           prec(c, std::string("conv_gemm_") + p, b.flops, b.bytes), wide(c, std::string("conv_w256_") + p, b.flops, b.bytes),
           caller(c, strcmp(tag, "lstm_ih") == 0 ? "conv_w256_seg" : "conv_w256_ecapa", b.flops, b.bytes) {}
 };
-// ---- conv_gemm.hip: picks the kernel (pp -> g256 -> w256 -> skinny -> 128 x 128); the launchers below are its steps and get `a` with w_ld already defaulted
+// ---- conv_gemm.hip: picks the kernel (pp -> g256 -> w256 -> skinny -> res2ws -> 128 x 128); the launchers below are its steps and get `a` with w_ld already defaulted
 int launch_conv_gemm(sd_ctx* c, const ConvArgs& a, const char* tag);
 // ---- conv_gemm_h.hip (fp16 mode, Cout >= 256: 256 x 256 tile; returns 1 = not applicable)
 int launch_conv_gemm_h256(sd_ctx* c, const ConvArgs& a, const char* tag);
@@ -348,6 +350,8 @@ int launch_conv_gemm_h256(sd_ctx* c, const ConvArgs& a, const char* tag);
 int launch_conv_gemm_g256(sd_ctx* c, const ConvArgs& a, const char* tag);
 // ---- conv_gemm_p.hip (fp16 mode, Cout % 256 == 0, K >= 512, M >= 2 048: the never-drained form of round 6; returns 1 = not applicable)
 int launch_conv_gemm_pp(sd_ctx* c, const ConvArgs& a, const char* tag);
+// ---- conv_res2.hip (f32 Res2Net shape: weights in registers, row panel in LDS; launches only, launch_conv_gemm bills it; returns 1 = not applicable)
+int launch_conv_res2ws(sd_ctx* c, const ConvArgs& a);
 // ---- api.cpp: the precision PyanNet's LSTM runs in: the option, or -- left at auto -- the split-operand form whenever the caller selected an fp16-pipe
 // mode for ECAPA (scores within 1e-6 of the f32 path's, identical turns: tests/test_gpu_parity.py, tests/test_planted.py; 86 -> 58 ms per hour)
 int seg_prec(const sd_ctx* c);

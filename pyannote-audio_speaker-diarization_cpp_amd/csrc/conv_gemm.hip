@@ -561,6 +561,8 @@ int launch_conv_gemm(sd_ctx* c, const ConvArgs& in, const char* tag)
     const ConvBill bill = conv_bill(a, rows, f16, a.X2 ? 2 : 1);
     ProfScope ps(c, c->profile_detail ? std::string("conv_gemm:") + tag : std::string("conv_gemm"), bill.flops, bill.bytes);
     ProfScope ps16(c, f16 ? "conv_gemm_f16" : x3 ? "conv_gemm_x3" : "conv_gemm_f32", bill.flops, bill.bytes);        // per precision (bench: roofline of the fp16 instantiations alone)
+    // the f32 Res2Net shape: weights in registers, every row staged once (conv_res2.hip; option conv_res2_ws); same bits, billed as above
+    { const int r = launch_conv_res2ws(c, a); if (r != 1) return r; }
     c->last_conv_kernel = f16 ? (a.X2 ? "gemm128_f16_x2" : "gemm128_f16") : x3 ? (a.X2 ? "gemm128_x3_x2" : "gemm128_x3") : (a.X2 ? "gemm128_f32_x2" : "gemm128_f32");
     if (f16) {
         if (a.X2) hipLaunchKernelGGL((k_conv_gemm<true, 1>), dim3(grid), dim3(256), 0, c->stream, a);
