@@ -572,6 +572,41 @@ int sd_read_wav_audio(const char* path, sd_audio* desc, void** data);     /* wav
 int sd_diarize_many_audio(sd_ctx*, const sd_audio* rec /*[R]*/, int64_t R, sd_turn** turns /*[R]*/, int64_t* n_turns /*[R]*/, int32_t* status /*[R]*/);     /* sd.cpp:2937-3234, 2948-2951; resampler.cc:19-36 */
 int sd_diarize_many_audio_dev(sd_ctx*, const sd_audio* rec /*[R]*/, int64_t R, sd_turn** turns /*[R]*/, int64_t* n_turns /*[R]*/, int32_t* status /*[R]*/);     /* sd.cpp:2937-3234, 2948-2951; resampler.cc:19-36 */
 
+/* ---- streams in their own encoding: a live call is 8 kHz G.711 at one byte per sample, often interleaved stereo with one party per channel.  After
+ * sd_stream_set_input_format(s, encoding, channels, channel) the stream takes its audio as it arrives, through the four _audio pushes, and decodes it
+ * on the device (k_group_ingest, csrc/stream_ingest.hip) -- no host decode, no de-interleaving, and both legs of a stereo call from one upload.
+ * THE RULE.  A stream with a format receives interleaved frames of `channels` elements.  Frame i becomes one float by steps 1 (decode) and 2 (channel)
+ * of the rule of sd_audio above, the same text on the device as sd_diarize_many_audio* runs.  Step 3 (rate) is the stream's own: it follows
+ * sd_stream_set_input_rate, which may be called before or after the format; both are set before the first sample.
+ * THE CONTRACT.  Let x be the mono float sequence that steps 1 and 2 define on all frames pushed so far.  After any sequence of single and group
+ * pushes the stream is, bit for bit, the stream with the same input rate (or none) to which x was pushed with sd_stream_push_f32: sd_stream_info,
+ * sd_stream_input_info (n_in counts frames), sd_stream_turns (turns, order, labels), sd_last_confidence, sd_last_speakers, sd_stream_read, sealing,
+ * window / forget and the roster.  So after sd_stream_end_input the turns are those of sd_diarize_many_audio for the sd_audio that describes
+ * everything pushed.
+ * A stream without a format keeps every path it has: sd_stream_push / _dev / _f32 and sd_stream_push_many / _dev / _f32 launch what they launched.  A
+ * stream with a format takes only the _audio pushes: a typed push on it is SD_ERR_ARG, and so is its row of a typed group call with n[i] > 0; an _audio
+ * push on a stream without a format is SD_ERR_ARG (in a group call: its row with frames[i] > 0).  The format (SD_ENC_S16, 1, 0) is legal and gives the
+ * bytes of sd_stream_push, so that a host which sets the format from a variable ends every call the same way.
+ * sd_stream_push_many_audio*: S streams of one context, of any formats and rates; frames[i] == 0 with any pointer is legal.  Host form: one upload per
+ * DISTINCT SOURCE -- rows whose data pointer, frames, encoding and channels are equal (the legs of one stereo call, which differ in `channel` only) share
+ * one upload and read the same device bytes -- and only the bytes the rule reads go up (for channel c of the last frame nothing behind element c; for
+ * rows that share, the largest count among them).  Then one table upload, ONE k_group_ingest launch, at most ONE k_resample_jobs launch and one
+ * synchronisation whatever S, the formats and the rates, and the packed inference of sd_stream_push_many.  A single push is sd_stream_push with the same
+ * kernel on a table of one row as its conversion launch.
+ * Refused with SD_ERR_ARG before anything is touched (a group call names the stream): sd_stream_set_input_format after a sample was pushed or the input
+ * was closed, for an unknown encoding, channels < 1 or a channel outside [-1, channels); a push of frames < 0 or frames > 2^40, of a null pointer with
+ * frames > 0, of a piece whose bytes exceed 2^42, in the _dev forms of a pointer not aligned to its element, on a closed input, and everything
+ * sd_stream_push and sd_stream_push_many refuse.  An argument error, or a failed allocation of the staging workspaces (before the first launch), leaves
+ * the stream usable and exactly what it was, the inputs held by a rated stream included; any other SD_ERR_HIP makes the stream (in a group call: the
+ * streams of the call) unusable, as for the typed pushes.
+ * sd_stream_input_format: the format and whether one was set; any pointer may be NULL; a stream without one reports SD_ENC_S16, 1, 0, 0. */
+int sd_stream_set_input_format(sd_stream*, int32_t encoding /*SD_ENC_**/, int32_t channels, int32_t channel /* -1: the mean */);     /* wav.h:99-122, sd.cpp:2948-2951 */
+int sd_stream_input_format(const sd_stream*, int32_t* encoding, int32_t* channels, int32_t* channel, int32_t* is_set);     /* wav.h:99-122 */
+int sd_stream_push_audio(sd_stream*, const void* h_data, int64_t frames);     /* wav.h:99-122, sd.cpp:2948-2951; resampler.cc:19-36 */
+int sd_stream_push_audio_dev(sd_stream*, const void* d_data, int64_t frames);     /* wav.h:99-122, sd.cpp:2948-2951; resampler.cc:19-36 */
+int sd_stream_push_many_audio(sd_stream* const* s /*[S]*/, const void* const* h_data /*[S]*/, const int64_t* frames /*[S]*/, int64_t S);     /* sd.cpp:2937-3234, 2948-2951; resampler.cc:19-36 */
+int sd_stream_push_many_audio_dev(sd_stream* const* s /*[S]*/, const void* const* d_data /*[S]*/, const int64_t* frames /*[S]*/, int64_t S);     /* sd.cpp:2937-3234, 2948-2951; resampler.cc:19-36 */
+
 /* ---- scoring against a ground truth (host-only, no context, no GPU).  The reference has no counterpart: it prints turns and measures nothing.
  * sd_der is the diarization error rate of pyannote.metrics' DiarizationErrorRate, restated:
  *  - the time line is cut at every start and end of a turn of ref and of hyp (and of a uem span and a collar zone, below).  In an elementary interval of

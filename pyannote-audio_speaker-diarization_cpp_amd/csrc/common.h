@@ -472,8 +472,13 @@ int pack_infer(sd_ctx* c, std::vector<ManyRow>& rows, int is_f32, const std::vec
 struct IngestRow;
 std::vector<char> many_ingest_table(const std::vector<IngestRow>& rows, const std::vector<int64_t>& tile0);
 int launch_many_ingest(sd_ctx* c, const char* d_tab, const std::vector<IngestRow>& rows, const std::vector<int64_t>& tile0, int64_t max_span, float* d_dst, int64_t dst_len);
-// the form of the samples an entry was handed, for the entries that come in three (sd_diarize_many*, sd_stream_push*, sd_stream_push_many*)
-enum SampleForm { SD_PCM_HOST, SD_PCM_DEV, SD_F32_HOST };
+// the form of the samples an entry was handed, for the entries that come in three (sd_diarize_many*, sd_stream_push*, sd_stream_push_many*); the two
+// _AUDIO forms are the frames of a stream with an input format (sd_stream_push_audio*, sd_stream_push_many_audio*), on the host or on the device
+enum SampleForm { SD_PCM_HOST, SD_PCM_DEV, SD_F32_HOST, SD_AUDIO_HOST, SD_AUDIO_DEV };
+// ---- stream_ingest.hip: ONE launch of k_group_ingest over a table (rows: stream_ingest_plan.h) with `pad` zeros behind every row; stream.hip and the
+// hook of stream_ingest_test.hip call this
+struct StreamIngestRow;
+int launch_group_ingest(sd_ctx* c, const StreamIngestRow* d_rows, const std::vector<StreamIngestRow>& rows, int64_t pad);
 // finalize, one job after the other, of a call with J outputs (sd_diarize_many*: recordings; sd_stream_turns_many: streams).  Presets turns / n_turns /
 // status / c->many_jobs to "no job" (SD_ERR_SHORT), lets `infer` run the networks and name the rows of every job (chunks <= 0: none), then finalizes in
 // list order: SD_ERR_NUMERIC is that job's own status, any other failure gives every turn list back and is returned; c->last is kept per job.

@@ -1,6 +1,6 @@
 // ingest.hip -- k_many_ingest: the packed waveform of sd_diarize_many_audio* (many.hip) filled in ONE launch straight from the recordings as
 // they arrive -- int16, float, mu-law or A-law elements, any channel count, any sample rate -- by the rule of include/sdhip.h ("recordings in their own
-// rate and encoding"): decode, channel, rate.  The decode is ingest_plan.h's text (the host entries run the same), the rate step is resample_dev.h's
+// rate and encoding"): decode, channel, rate.  The decode is ingest_plan.h's text (the host entries run the same) behind ingest_dev.h's IngestLoad, the rate step is resample_dev.h's
 // resample_point, the body of k_resample and k_resample_jobs, with the staging load as its parameter: no tap arithmetic is restated here.
 //
 // The table (IngestRow, ingest_plan.h) has one row per slot and one for the SD_WAV_PAD floats behind the last slot; row r has tile0[r + 1] - tile0[r]
@@ -16,32 +16,9 @@
 #include "common.h"
 #include "ingest_plan.h"
 #include "resample_dev.h"
+#include "ingest_dev.h"      // IngestLoad: the staging load, steps 1 and 2 of the rule
 #include <algorithm>
 #include <cstring>
-
-// The staging load of a recording: frame i -> the float of the rule's steps 1 and 2.
-// The mean of the channels is wav_load's loop (wav_file.h): s = +0.0f, s += x_q in channel order, s / (float)channels.  The division must be the
-// correctly rounded one, as the host's is: __fdiv_rn is IEEE division under hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt (the Makefile
-// passes neither -ffast-math nor -fno-hip-fp32-correctly-rounded-divide-sqrt); a reciprocal multiply differs at 3 channels.
-struct IngestLoad {
-    const void* __restrict__ src; int enc, channels, channel;
-    __device__ __forceinline__ float elem(int64_t e) const
-    {
-        switch (enc) {
-        case SD_ENC_S16: return pcm_to_float(((const int16_t*)src)[e]);
-        case SD_ENC_F32: return ((const float*)src)[e];
-        case SD_ENC_MULAW: return pcm_to_float((int16_t)g711_mulaw(((const uint8_t*)src)[e]));
-        default: return pcm_to_float((int16_t)g711_alaw(((const uint8_t*)src)[e]));
-        }
-    }
-    __device__ __forceinline__ float operator()(int64_t i) const
-    {
-        if (channel >= 0) return elem(i * channels + channel);
-        float s = 0.0f;
-        for (int q = 0; q < channels; ++q) s += elem(i * channels + q);
-        return __fdiv_rn(s, (float)channels);
-    }
-};
 
 // dynamic LDS: [RS_BLOCK] the tile's outputs, 16-byte aligned at the base of the region (no static LDS in front of it) | the staging span of the call's
 // largest rate pair

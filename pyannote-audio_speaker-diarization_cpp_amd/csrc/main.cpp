@@ -43,6 +43,11 @@
 //                   final turns.  The "== N s" header of a --stream-updates block counts the 16 kHz samples the stream holds so far, which trail the
 //                   audio pushed by the filter wing (8.5 ms at 8 kHz) until the end of the input.  Without
 //                   --stream, with a wav file instead of -, or with another value: usage error (exit 2)
+//   --stream-encoding s16|f32|mulaw|alaw   --stream-channels N   --stream-channel C|mean   with --stream and - : stdin holds headerless interleaved
+//                   frames of N elements (default 1) in that encoding (default s16; little-endian int16 or float, or one G.711 code per byte), of
+//                   which the stream takes channel C (default 0) or their mean (sd_stream_set_input_format, sd_stream_push_audio), at --stream-rate HZ
+//                   or 16 kHz; a piece is SECONDS x rate frames.  Bytes of a partial frame carry over to the next read; a partial frame at end of
+//                   file is dropped with a line on stderr.  Without --stream and -, or with a bad value (N < 1, C outside 0 .. N-1): usage error (exit 2)
 //   --stream-window SECONDS   with --stream: a sliding window (sd_stream_set_window with ceil(SECONDS / 16) blocks of 32 chunks): after every piece that
 //                   seals a block the stream forgets all but that many; the turns are those of the audio still held, printed with absolute times
 //                   (t + sd_stream_origin / 16000); the header of a --stream-updates block still gives the seconds pushed, its chunk counts are those of the
@@ -107,6 +112,8 @@ struct Args { const char* seg = nullptr; const char* emb = nullptr; const char* 
               long long stream_piece = 0; bool stream_updates = false;         // --stream: samples per piece (0: off)
               bool stream_roster = false;                                      // --stream-roster: the labels are roster ids
               long long stream_rate = 0; double stream_sec = 0.0;              // --stream-rate: the sample rate of stdin (0: 16 000); --stream's SECONDS as given
+              bool stream_fmt = false;                                         // --stream-encoding / -channels / -channel: stdin holds frames in that format
+              int stream_enc = SD_ENC_S16; long long stream_channels = 1, stream_channel = 0;
               const char* speakers = nullptr; double speakers_threshold = -1.0; const char* enroll = nullptr; std::vector<sd_turn> enroll_spans; bool enrolled = false;
               const char* many = nullptr;         // --speakers FILE, its threshold (-1: default), --enroll NAME and its spans
               const char* score = nullptr; const char* tune = nullptr; double collar = 0.0; bool skip_overlap = false, uem_from_ref = false;      // --score / --tune REF.rttm and how to score
@@ -518,26 +525,34 @@ static bool stream_file(StreamRun& r)
     return r.feed_f32(out.data(), (int64_t)out.size());
 }
 
-// headerless s16le mono samples from stdin -- at 16 kHz, or at --stream-rate HZ -- pushed as they arrive: reads of at most 2 MiB, an update block whenever a piece is complete
+// headerless samples from stdin -- s16le mono at 16 kHz or at --stream-rate HZ, or interleaved frames in the format of --stream-encoding / -channels /
+// -channel -- pushed as they arrive: reads of at most 2 MiB, an update block whenever a piece is complete
 static bool stream_stdin(StreamRun& r)
 {
     const long long piece = r.a.stream_piece;
-    std::vector<int16_t> buf((size_t)(piece < (1 << 20) ? piece : (1 << 20)));
+    const size_t bpf = r.a.stream_fmt ? (size_t)(r.a.stream_enc == SD_ENC_S16 ? 2 : r.a.stream_enc == SD_ENC_F32 ? 4 : 1) * (size_t)r.a.stream_channels : 2;      // bytes of a frame
+    const long long most = (long long)((size_t)(2 << 20) / bpf > 0 ? (size_t)(2 << 20) / bpf : 1);
+    const long long cap = piece < most ? piece : most;      // frames of one read
+    std::vector<unsigned char> buf((size_t)cap * bpf);
     size_t have = 0;                                 // bytes of buf filled
-    long long in_piece = 0;                          // samples of the current piece pushed so far
+    long long in_piece = 0;                          // frames of the current piece pushed so far
     for (;;) {
-        const long long room = piece - in_piece;     // samples the current piece still takes
-        const size_t want = (size_t)(room < (long long)buf.size() ? room : (long long)buf.size()) * 2;
-        const ssize_t got = read(0, (char*)buf.data() + have, want - have);
+        const long long room = piece - in_piece;     // frames the current piece still takes
+        const size_t want = (size_t)(room < cap ? room : cap) * bpf;
+        const ssize_t got = read(0, (char*)buf.data() + have, want - have);      // (bytes of a partial frame stay in buf for the next read)
         if (got < 0) { if (errno == EINTR) continue; perror("stdin"); return false; }
         have += (size_t)got;
-        if (have == want || (got == 0 && have >= 2)) {
-            const long long m = (long long)(have / 2);
-            if (!r.part(sd_stream_push(r.st, buf.data(), m))) return false;
-            in_piece += m; have = 0;                 // (an odd byte at the end of the input is dropped)
+        if (have == want || (got == 0 && have >= bpf)) {
+            const long long m = (long long)(have / bpf);
+            if (!r.part(r.a.stream_fmt ? sd_stream_push_audio(r.st, buf.data(), m) : sd_stream_push(r.st, (const int16_t*)buf.data(), m))) return false;
+            have -= (size_t)m * bpf;                 // (only at the end of the input: a partial frame, which is dropped)
+            in_piece += m;
             if (in_piece == piece) { if (!r.piece_done()) return false; in_piece = 0; }
         }
-        if (got == 0) return in_piece == 0 || r.piece_done();      // end of input: the last piece is a partial one
+        if (got == 0) {                              // end of input: the last piece is a partial one
+            if (have > 0 && r.a.stream_fmt) fprintf(stderr, "stdin: %zu bytes of a partial frame at the end of the input are dropped\n", have);
+            return in_piece == 0 || r.piece_done();
+        }
     }
 }
 
@@ -556,6 +571,7 @@ static int run_stream(const Args& a)
     if (a.stream_window >= 0 && sd_stream_set_window(r.st, a.stream_window) != SD_OK) { fprintf(stderr, "%s\n", sd_last_error(ctx)); return leave(1); }
     if (a.stream_roster && (sd_roster_open(SD_EMB_DIM, &roster) != SD_OK || sd_stream_set_roster(r.st, roster) != SD_OK)) { fprintf(stderr, "--stream-roster: no roster (%s)\n", sd_last_error(ctx)); return leave(1); }
     if (a.stream_rate > 0 && sd_stream_set_input_rate(r.st, (int32_t)a.stream_rate) != SD_OK) { fprintf(stderr, "--stream-rate %lld: %s\n", a.stream_rate, sd_last_error(ctx)); return leave(1); }
+    if (a.stream_fmt && sd_stream_set_input_format(r.st, a.stream_enc, (int32_t)a.stream_channels, (int32_t)a.stream_channel) != SD_OK) { fprintf(stderr, "--stream-encoding / --stream-channels / --stream-channel: %s\n", sd_last_error(ctx)); return leave(1); }
     const bool fed = std::string(a.wav) == "-" ? stream_stdin(r) : stream_file(r);
     if (fed && a.stream_rate > 0) {      // the outputs behind the last final one, before the final turns
         const int rc = sd_stream_end_input(r.st);
@@ -746,6 +762,34 @@ int main(int argc, char* argv[])
             a.stream_rate = strtoll(v, &end, 10);
             if (end == v || *end || errno || a.stream_rate < 1 || a.stream_rate > 0x7fffffff) { fprintf(stderr, "usage: --stream-rate takes a sample rate in Hz, an integer > 0 (got '%s')\n", v); return 2; }
         }
+        else if (s == "--stream-encoding") {
+            if (i + 1 >= argc) { fprintf(stderr, "usage: --stream-encoding needs a value\n"); return 2; }
+            const std::string v = argv[++i];
+            if (v == "s16") a.stream_enc = SD_ENC_S16; else if (v == "f32") a.stream_enc = SD_ENC_F32; else if (v == "mulaw") a.stream_enc = SD_ENC_MULAW; else if (v == "alaw") a.stream_enc = SD_ENC_ALAW;
+            else { fprintf(stderr, "usage: --stream-encoding takes s16, f32, mulaw or alaw (got '%s')\n", v.c_str()); return 2; }
+            a.stream_fmt = true;
+        }
+        else if (s == "--stream-channels") {
+            if (i + 1 >= argc) { fprintf(stderr, "usage: --stream-channels needs a value\n"); return 2; }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            errno = 0;
+            a.stream_channels = strtoll(v, &end, 10);
+            if (end == v || *end || errno || a.stream_channels < 1 || a.stream_channels > 65535) { fprintf(stderr, "usage: --stream-channels takes a channel count, an integer from 1 to 65535 (got '%s')\n", v); return 2; }
+            a.stream_fmt = true;
+        }
+        else if (s == "--stream-channel") {
+            if (i + 1 >= argc) { fprintf(stderr, "usage: --stream-channel needs a value\n"); return 2; }
+            const char* v = argv[++i];
+            char* end = nullptr;
+            errno = 0;
+            if (std::string(v) == "mean") a.stream_channel = -1;
+            else {
+                a.stream_channel = strtoll(v, &end, 10);
+                if (end == v || *end || errno || a.stream_channel < 0 || a.stream_channel > 65534) { fprintf(stderr, "usage: --stream-channel takes a channel, an integer >= 0, or mean (got '%s')\n", v); return 2; }
+            }
+            a.stream_fmt = true;
+        }
         else if (s == "--speakers" || s == "--speakers-threshold" || s == "--enroll" || s == "--enroll-span") {
             // checked here as well: a usage error before any context is created
             const int need = s == "--enroll-span" ? 2 : 1;
@@ -797,6 +841,8 @@ int main(int argc, char* argv[])
     if (a.stream_window >= 0 && a.stream_piece <= 0) { fprintf(stderr, "usage: --stream-window needs --stream SECONDS\n"); return 2; }
     if (a.cl_max_num >= 1 && a.dump_dir) { fprintf(stderr, "usage: --dump-steps describes the reference's flow, which clusters every train row; --max-num-embeddings is refused with it\n"); return 2; }
     if (a.stream_rate > 0 && (a.stream_piece <= 0 || pos.size() < 3 || std::string(pos[2]) != "-")) { fprintf(stderr, "usage: --stream-rate gives the rate of the samples on stdin: it needs --stream SECONDS and - in place of the wav file\n"); return 2; }
+    if (a.stream_fmt && (a.stream_piece <= 0 || pos.size() < 3 || std::string(pos[2]) != "-")) { fprintf(stderr, "usage: --stream-encoding, --stream-channels and --stream-channel give the format of the frames on stdin: they need --stream SECONDS and - in place of the wav file\n"); return 2; }
+    if (a.stream_fmt && a.stream_channel >= a.stream_channels) { fprintf(stderr, "usage: --stream-channel %lld is outside the %lld channels of --stream-channels\n", a.stream_channel, a.stream_channels); return 2; }
     if (a.stream_rate > 0) { a.stream_piece = (long long)(a.stream_sec * (double)a.stream_rate + 0.5); if (a.stream_piece < 1) a.stream_piece = 1; }      // SECONDS are seconds of audio
     if (a.stream_roster && a.stream_piece <= 0) { fprintf(stderr, "usage: --stream-roster needs --stream SECONDS\n"); return 2; }
     if (a.stream_roster && (a.speakers || a.relabel)) { fprintf(stderr, "usage: --stream-roster prints roster ids; --speakers and --relabel name and renumber raw labels and are refused with it\n"); return 2; }

@@ -12,9 +12,13 @@
 // A stream with an input rate (sd_stream_set_input_rate) takes its samples at that rate: a push puts them behind the inputs the stream keeps
 // (resample_book.h) and one k_resample_jobs launch (resample.hip) writes the 16 kHz samples they made final straight behind the tail -- in a group call
 // one launch for all such streams, whatever their rates; everything behind the tail sees 16 kHz samples and is what it was.
+// A stream with an input format (sd_stream_set_input_format) takes interleaved frames in its own encoding through the _audio pushes: k_group_ingest
+// (stream_ingest.hip) on the table stream_ingest_plan.h makes of them is the conversion launch, of one row in a single call and of all streams' rows in a
+// group call, where the legs of one stereo call share one upload; behind it the push is the typed push of the floats it decoded.
 #include "common.h"
 #include "stream_book.h"
 #include "resample_book.h"
+#include "stream_ingest_plan.h"
 #include "roster.h"
 #include "../../include/sdhip_stream_test.h"
 #include <algorithm>
@@ -108,7 +112,7 @@ int group_launch(sd_ctx* c, int which, const GroupRow* d_rows, const std::vector
     int64_t longest = 1;
     for (const GroupRow& r : rows) longest = std::max(longest, r.len + SD_TAIL_PAD);
     const dim3 grid = many_grid(longest / 4 + 2, (int64_t)rows.size());
-    if (which == 0) hipLaunchKernelGGL(k_group_append, grid, dim3(256), 0, c->stream, d_rows, (int)rows.size(), is_f32);
+    if (which == 0) { ProfScope ps(c, "group_append"); hipLaunchKernelGGL(k_group_append, grid, dim3(256), 0, c->stream, d_rows, (int)rows.size(), is_f32); }
     else if (which == 1) hipLaunchKernelGGL(k_group_scatter, grid, dim3(256), 0, c->stream, d_rows, (int)rows.size());
     else hipLaunchKernelGGL(k_group_tail_move, grid, dim3(256), 0, c->stream, d_rows, (int)rows.size());
     KCHECK(c);
@@ -126,6 +130,7 @@ struct sd_stream {
     int64_t kept_origin = 0;                         // ... and the origin then: row i of the table now was row i + 3 (origin - kept_origin) / 8000
     bool has_kept = false;
     RateBook r;                                      // sd_stream_set_input_rate: the inputs held and the outputs emitted (resample_book.h); in_sr 0 = a plain stream
+    StreamFormat f;                                  // sd_stream_set_input_format: the frames the _audio pushes hand over (stream_ingest_plan.h); not set = the typed pushes
 };
 
 namespace {
@@ -227,6 +232,45 @@ int check_call(sd_stream* s, const char* who)
     return SD_OK;
 }
 
+inline bool audio_kind(int kind) { return kind == SD_AUDIO_HOST || kind == SD_AUDIO_DEV; }
+
+const char* ingest_refusal_text(int e)
+{
+    switch (e) {
+    case SI_NO_FORMAT: return "the stream has no input format (sd_stream_set_input_format)";
+    case SI_FRAMES: return "a bad number of frames";
+    case SI_NULL_DATA: return "a null pointer with frames to read";
+    case SI_BYTES: return "a piece beyond SD_INGEST_MAX_BYTES";
+    default: return "a device pointer that is not aligned to its element";
+    }
+}
+
+// The conversion launch of the _audio pushes: the table of a plan on the device -- for the host form behind the uploads, one per distinct source, into one
+// workspace -- and ONE k_group_ingest launch.  A failed allocation comes before the first launch and leaves every stream what it was.
+int ingest_rows(sd_ctx* c, StreamIngestPlan& plan, bool host)
+{
+    if (plan.rows.empty()) return SD_OK;
+    StreamIngestRow* d_tab = ws_get<StreamIngestRow>(c, "stg_itab", plan.rows.size());
+    char* stage = host ? ws_get<char>(c, "stg_src", (size_t)plan.upload_bytes + 16) : nullptr;
+    if (!d_tab || (host && !stage)) { c->stream_intact = true; SD_FAIL(c, SD_ERR_HIP, "hipMalloc of the staging workspaces of %zu rows (%lld bytes) failed", plan.rows.size(), (long long)plan.upload_bytes); }
+    if (host) {
+        for (size_t u = 0; u < plan.up_src.size(); ++u)
+            HIPCHK(c, hipMemcpyAsync(stage + plan.up_off[u], plan.up_src[u], (size_t)plan.up_bytes[u], hipMemcpyHostToDevice, c->stream));
+        for (size_t q = 0; q < plan.rows.size(); ++q) plan.rows[q].src = stage + plan.up_off[(size_t)plan.cls[q]];
+    }
+    HIPCHK(c, hipMemcpy(d_tab, plan.rows.data(), plan.rows.size() * sizeof(StreamIngestRow), hipMemcpyHostToDevice));
+    return launch_group_ingest(c, d_tab, plan.rows, SD_TAIL_PAD);
+}
+
+// ... of a single push: a table of one row
+int ingest_one(sd_stream* s, const void* src, int64_t m, int kind, float* dst, int64_t room)
+{
+    const StreamPiece p{src, m, s->f};
+    StreamIngestPlan plan;
+    stream_ingest_plan(&p, &dst, &room, 1, kind == SD_AUDIO_HOST, plan);
+    return ingest_rows(s->c, plan, kind == SD_AUDIO_HOST);
+}
+
 // A push to a stream with an input rate (sd_stream_set_input_rate): the piece goes behind the inputs the stream holds, ONE k_resample_jobs launch of one
 // row writes the outputs that piece made final -- [F(n), F(n')), resample_book.h -- straight behind the tail with their padding, and from there on it is
 // a push of those 16 kHz samples.  A push that makes no output final only extends the inputs held.  Growth comes first: a failed allocation leaves the
@@ -248,7 +292,8 @@ int push_rated(sd_stream* s, const void* src, int64_t m, int kind, const char* w
     if (!(rc = rate_reserve(dev, r, m)) && q.count > 0) rc = book_reserve_tail(dev, b, q.count);
     if (rc) { if (dev.alloc_failed) c->stream_intact = true; return rc; }
     float* in = r.buf[r.cur] + r.held();
-    if (kind == SD_F32_HOST) HIPCHK(c, hipMemcpyAsync(in, src, (size_t)m * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (audio_kind(kind)) { if ((rc = ingest_one(s, src, m, kind, in, m))) return rc; }      // (room = m: nothing behind the inputs)
+    else if (kind == SD_F32_HOST) HIPCHK(c, hipMemcpyAsync(in, src, (size_t)m * sizeof(float), hipMemcpyHostToDevice, c->stream));
     else {
         const int16_t* d_pcm = (const int16_t*)src;
         if (kind == SD_PCM_HOST) {
@@ -256,7 +301,10 @@ int push_rated(sd_stream* s, const void* src, int64_t m, int kind, const char* w
             HIPCHK(c, hipMemcpyAsync(stage, src, (size_t)m * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
             d_pcm = stage;
         }
-        hipLaunchKernelGGL(k_pcm_to_f32, GRID1(m + SD_WAV_PAD), 0, c->stream, d_pcm, in, m);      // (its zeros land in the slack behind the inputs)
+        {
+            ProfScope ps(c, "pcm_to_f32");
+            hipLaunchKernelGGL(k_pcm_to_f32, GRID1(m + SD_WAV_PAD), 0, c->stream, d_pcm, in, m);      // (its zeros land in the slack behind the inputs)
+        }
         KCHECK(c);
     }
     if (q.count > 0) {
@@ -332,11 +380,31 @@ int set_rate_impl(sd_stream* s, int32_t in_sr)
     return SD_OK;
 }
 
+// sd_stream_set_input_format: before the first sample only, like the rate, and in either order with it.  Nothing of the stream is touched by a refusal
+int set_format_impl(sd_stream* s, int32_t enc, int32_t channels, int32_t channel)
+{
+    sd_ctx* c = s->c;
+    const char* who = "sd_stream_set_input_format";
+    if (int rc = check_call(s, who)) return rc;
+    c->stream_intact = true;
+    if (!stream_format_ok(enc, channels, channel)) SD_FAIL(c, SD_ERR_ARG, "%s: bad format (encoding %d, %d channels, channel %d)", who, enc, channels, channel);
+    if (s->b.n > 0 || s->b.origin > 0 || s->r.n_in > 0 || s->r.closed) SD_FAIL(c, SD_ERR_ARG, "%s: samples have been pushed or the input is closed; the format is set before the first sample", who);
+    s->f.enc = enc; s->f.channels = channels; s->f.channel = channel; s->f.set = true;
+    return SD_OK;
+}
+
 int push_impl(sd_stream* s, const void* src, int64_t m, int kind, const char* who)
 {
     sd_ctx* c = s->c;
     if (m < 0 || (m > 0 && !src)) SD_FAIL(c, SD_ERR_ARG, "%s: bad argument", who);
     if (int rc = check_call(s, who)) return rc;
+    if (audio_kind(kind) != s->f.set)
+        SD_FAIL(c, SD_ERR_ARG, s->f.set ? "%s: the stream has an input format (sd_stream_set_input_format) and takes the _audio pushes only" : "%s: the stream has no input format (sd_stream_set_input_format)", who);
+    if (audio_kind(kind)) {
+        const StreamPiece p{src, m, s->f};
+        int64_t bad = -1;
+        if (const int e = stream_ingest_check(&p, 1, kind == SD_AUDIO_DEV, &bad)) SD_FAIL(c, SD_ERR_ARG, "%s: %s", who, ingest_refusal_text(e));
+    }
     if (s->r.in_sr) return push_rated(s, src, m, kind, who);
     if (s->r.closed) SD_FAIL(c, SD_ERR_ARG, "%s: the stream's input was closed by sd_stream_end_input", who);
     if (m == 0) return SD_OK;
@@ -347,7 +415,8 @@ int push_impl(sd_stream* s, const void* src, int64_t m, int kind, const char* wh
     int rc;
     if ((rc = book_reserve_tail(dev, b, m))) return rc;
     float* dst = b.tail_now() + b.tail_len();
-    if (kind == SD_F32_HOST) {
+    if (audio_kind(kind)) { if ((rc = ingest_one(s, src, m, kind, dst, b.tail_cap[b.cur] - b.tail_len()))) return rc; }
+    else if (kind == SD_F32_HOST) {
         HIPCHK(c, hipMemcpyAsync(dst, src, (size_t)m * sizeof(float), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemsetAsync(dst + m, 0, SD_TAIL_PAD * sizeof(float), c->stream));
     } else {
@@ -357,7 +426,10 @@ int push_impl(sd_stream* s, const void* src, int64_t m, int kind, const char* wh
             HIPCHK(c, hipMemcpyAsync(stage, src, (size_t)m * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
             d_pcm = stage;
         }
-        hipLaunchKernelGGL(k_pcm_to_f32, GRID1(m + SD_TAIL_PAD), 0, c->stream, d_pcm, dst, m);
+        {
+            ProfScope ps(c, "pcm_to_f32");
+            hipLaunchKernelGGL(k_pcm_to_f32, GRID1(m + SD_TAIL_PAD), 0, c->stream, d_pcm, dst, m);
+        }
         KCHECK(c);
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));      // the caller's buffer may go
@@ -522,6 +594,24 @@ int group_infer(sd_ctx* c, sd_stream* const* s, const std::vector<PackRange>& ra
     return SD_OK;
 }
 
+// what a group push does behind its conversion launch, whatever the form of the samples: the one k_resample_jobs launch, the one synchronisation, the
+// books, and the packed inference of the blocks that became sealed
+int push_many_tail(sd_ctx* c, sd_stream* const* s, int64_t S, const std::vector<ResampleJob>& jobs, const std::vector<RatePush>& rated,
+                   const std::vector<int64_t>& add, const std::vector<PackRange>& ranges, int64_t total, double t0)
+{
+    int rc;
+    if ((rc = resample_jobs(c, jobs.data(), (int64_t)jobs.size()))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // the callers' buffers may go: once for all streams
+    for (int64_t i = 0; i < S; ++i) {
+        if (s[i]->r.in_sr) rate_commit(s[i]->r, rated[(size_t)i]);
+        s[i]->b.n += add[(size_t)i];
+    }
+
+    if ((rc = group_infer(c, s, ranges, total, false, true))) return rc;
+    c->stage_ms[3] = now_ms() - t0;
+    return SD_OK;
+}
+
 int push_many_impl(sd_ctx* c, sd_stream* const* s, const void* const* src, const int64_t* n, int64_t S, int kind, const char* who)
 {
     // refusals: nothing is touched
@@ -533,6 +623,15 @@ int push_many_impl(sd_ctx* c, sd_stream* const* s, const void* const* src, const
     }
     int rc;
     if ((rc = group_check(c, s, S, who))) return rc;
+    // a stream with an input format takes the _audio calls only, a stream without one the typed calls; a row that hands nothing over is legal in both
+    const bool audio = audio_kind(kind);
+    std::vector<StreamPiece> pieces;
+    if (audio) {
+        for (int64_t i = 0; i < S; ++i) pieces.push_back(StreamPiece{src[i], n[i], s[i]->f});
+        int64_t bad = -1;
+        if (const int e = stream_ingest_check(pieces.data(), S, kind == SD_AUDIO_DEV, &bad)) SD_FAIL(c, SD_ERR_ARG, "%s: stream %lld: %s", who, (long long)bad, ingest_refusal_text(e));
+    } else
+        for (int64_t i = 0; i < S; ++i) if (n[i] > 0 && s[i]->f.set) SD_FAIL(c, SD_ERR_ARG, "%s: stream %lld has an input format (sd_stream_set_input_format) and takes the _audio pushes only", who, (long long)i);
     // a stream with an input rate gains the outputs its piece makes final (push_rated), a plain one its piece: add[i] samples at 16 kHz
     std::vector<RatePush> rated((size_t)S);
     std::vector<int64_t> add(n, n + S);
@@ -571,6 +670,21 @@ int push_many_impl(sd_ctx* c, sd_stream* const* s, const void* const* src, const
 
     // the samples of all streams: host ones uploaded back to back (each placed so that it is as aligned as its place in the tail), one conversion launch;
     // the piece of a stream with an input rate goes behind the inputs it holds, with no padding
+    if (audio) {      // the frames of all streams: one upload per distinct source, one table, ONE k_group_ingest launch
+        std::vector<float*> dst((size_t)S, nullptr);
+        std::vector<int64_t> room((size_t)S, 0);
+        for (int64_t i = 0; i < S; ++i) {
+            if (n[i] <= 0) continue;
+            StreamBook& b = s[i]->b;
+            const RateBook& r = s[i]->r;
+            dst[(size_t)i] = r.in_sr ? r.buf[r.cur] + r.held() : b.tail_now() + b.tail_len();
+            room[(size_t)i] = r.in_sr ? n[i] : b.tail_cap[b.cur] - b.tail_len();
+        }
+        StreamIngestPlan plan;
+        stream_ingest_plan(pieces.data(), dst.data(), room.data(), S, kind == SD_AUDIO_HOST, plan);
+        if ((rc = ingest_rows(c, plan, kind == SD_AUDIO_HOST))) return rc;
+        return push_many_tail(c, s, S, jobs, rated, add, ranges, total, t0);
+    }
     const size_t es = kind == SD_F32_HOST ? sizeof(float) : sizeof(int16_t);
     std::vector<GroupRow> rows;
     std::vector<size_t> off;
@@ -596,16 +710,7 @@ int push_many_impl(sd_ctx* c, sd_stream* const* s, const void* const* src, const
     }
     HIPCHK(c, hipMemcpy(d_tab, rows.data(), rows.size() * sizeof(GroupRow), hipMemcpyHostToDevice));
     if ((rc = group_launch(c, 0, d_tab, rows, kind == SD_F32_HOST ? 1 : 0))) return rc;
-    if ((rc = resample_jobs(c, jobs.data(), (int64_t)jobs.size()))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // the callers' buffers may go: once for all streams
-    for (int64_t i = 0; i < S; ++i) {
-        if (s[i]->r.in_sr) rate_commit(s[i]->r, rated[(size_t)i]);
-        s[i]->b.n += add[(size_t)i];
-    }
-
-    if ((rc = group_infer(c, s, ranges, total, false, true))) return rc;
-    c->stage_ms[3] = now_ms() - t0;
-    return SD_OK;
+    return push_many_tail(c, s, S, jobs, rated, add, ranges, total, t0);
 }
 
 int turns_many_impl(sd_ctx* c, sd_stream* const* s, int64_t S, sd_turn** turns, int64_t* n_turns, int32_t* status)
@@ -808,6 +913,47 @@ extern "C" int sd_stream_read(sd_stream* s, int64_t chunk_lo, int64_t chunk_hi, 
     if (!s) return SD_ERR_ARG;
     ENTER(s->c);
     return guard(s, read_impl(s, chunk_lo, chunk_hi, h_seg, h_emb));
+}
+
+// ---- a stream in its own encoding (sdhip.h, "streams in their own encoding"; stream_ingest_plan.h; stream_ingest.hip: k_group_ingest)
+extern "C" int sd_stream_set_input_format(sd_stream* s, int32_t encoding, int32_t channels, int32_t channel)
+{
+    if (!s) return SD_ERR_ARG;
+    ENTER(s->c);
+    return guard(s, set_format_impl(s, encoding, channels, channel));
+}
+extern "C" int sd_stream_input_format(const sd_stream* s, int32_t* encoding, int32_t* channels, int32_t* channel, int32_t* is_set)
+{
+    if (!s) return SD_ERR_ARG;
+    if (encoding) *encoding = s->f.enc;
+    if (channels) *channels = s->f.channels;
+    if (channel) *channel = s->f.channel;
+    if (is_set) *is_set = s->f.set ? 1 : 0;
+    return SD_OK;
+}
+extern "C" int sd_stream_push_audio(sd_stream* s, const void* h_data, int64_t frames)
+{
+    if (!s) return SD_ERR_ARG;
+    ENTER(s->c);
+    return guard(s, push_impl(s, h_data, frames, SD_AUDIO_HOST, "sd_stream_push_audio"));
+}
+extern "C" int sd_stream_push_audio_dev(sd_stream* s, const void* d_data, int64_t frames)
+{
+    if (!s) return SD_ERR_ARG;
+    ENTER(s->c);
+    return guard(s, push_impl(s, d_data, frames, SD_AUDIO_DEV, "sd_stream_push_audio_dev"));
+}
+extern "C" int sd_stream_push_many_audio(sd_stream* const* s, const void* const* h_data, const int64_t* frames, int64_t S)
+{
+    if (!group_list_ok(s, S)) return SD_ERR_ARG;
+    ENTER(s[0]->c);
+    return group_guard(s, S, push_many_impl(s[0]->c, s, h_data, frames, S, SD_AUDIO_HOST, "sd_stream_push_many_audio"));
+}
+extern "C" int sd_stream_push_many_audio_dev(sd_stream* const* s, const void* const* d_data, const int64_t* frames, int64_t S)
+{
+    if (!group_list_ok(s, S)) return SD_ERR_ARG;
+    ENTER(s[0]->c);
+    return group_guard(s, S, push_many_impl(s[0]->c, s, d_data, frames, S, SD_AUDIO_DEV, "sd_stream_push_many_audio_dev"));
 }
 
 // ---- a stream at another sample rate (sdhip.h, "streams at any sample rate"; resample_book.h; resample.hip: k_resample_jobs)

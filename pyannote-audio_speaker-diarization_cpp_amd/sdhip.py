@@ -118,11 +118,15 @@ EXPORTS = [
     "sd_linkage_many",
     "sd_stream_set_input_rate", "sd_stream_end_input", "sd_stream_input_info", "sd_resample_final_len",
     "sd_audio_len16", "sd_g711_decode", "sd_read_wav_audio", "sd_diarize_many_audio", "sd_diarize_many_audio_dev",
+    "sd_stream_set_input_format", "sd_stream_input_format", "sd_stream_push_audio", "sd_stream_push_audio_dev",
+    "sd_stream_push_many_audio", "sd_stream_push_many_audio_dev",
 ]
 # the stream hook of include/sdhip_stream_test.h (sdhip_test.h's list is pinned name by name by tests/test_abi.py)
 STREAM_TEST_EXPORTS = ["sd_test_stream_tail"]
 # the hook of k_many_ingest, include/sdhip_ingest_test.h (likewise)
 INGEST_TEST_EXPORTS = ["sd_test_many_ingest"]
+# the hook of k_group_ingest, include/sdhip_stream_ingest_test.h (likewise)
+STREAM_INGEST_TEST_EXPORTS = ["sd_test_group_ingest"]
 # SD_LINKAGE_* (scipy's method codes) and SD_METRIC_*
 LINKAGE_METHODS = ("single", "complete", "average", "centroid", "median", "ward", "weighted")
 METRIC_EUCLIDEAN, METRIC_COSINE = 0, 1
@@ -294,6 +298,14 @@ def lib():
         for f in (L.sd_diarize_many_audio, L.sd_diarize_many_audio_dev):
             f.argtypes = [vp, C.POINTER(AudioDesc), i64, vp, vp, vp]
         L.sd_test_many_ingest.argtypes = [vp, vp, i64, vp, i64, i64, C.c_float, vp]
+    if hasattr(L, "sd_stream_set_input_format"):      # (likewise)
+        L.sd_stream_set_input_format.argtypes = [vp, i32, i32, i32]
+        L.sd_stream_input_format.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+        for f in (L.sd_stream_push_audio, L.sd_stream_push_audio_dev):
+            f.argtypes = [vp, vp, i64]
+        for f in (L.sd_stream_push_many_audio, L.sd_stream_push_many_audio_dev):
+            f.argtypes = [vp, vp, vp, i64]
+        L.sd_test_group_ingest.argtypes = [vp, vp, i64, vp, i64, i64, C.c_float, vp]
     L.sd_format_turn.argtypes = [C.POINTER(Turn), C.c_char_p, C.c_int]
     L.sd_stage_ms.argtypes = [vp, C.POINTER(dbl)]
     L.sd_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(dbl), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
@@ -830,6 +842,41 @@ class Stream:
         n_in, n_final = C.c_int64(0), C.c_int64(0)
         self._d._chk(lib().sd_stream_input_info(self._handle(), C.byref(sr), C.byref(n_in), C.byref(n_final), C.byref(closed)))
         return int(sr.value), int(n_in.value), int(n_final.value), int(closed.value)
+
+    def set_input_format(self, encoding, channels=1, channel=0):
+        """sd_stream_set_input_format: from now on the stream takes interleaved frames of `channels` elements in `encoding` (ENC_*) through push_audio*,
+        one channel of them or, with channel -1, their mean (before the first sample only, in either order with set_input_rate)"""
+        self._d._chk(lib().sd_stream_set_input_format(self._handle(), int(encoding), int(channels), int(channel)))
+
+    def input_format(self):
+        """sd_stream_input_format: (encoding, channels, channel, whether a format was set)"""
+        v = [C.c_int32(0) for _ in range(4)]
+        self._d._chk(lib().sd_stream_input_format(self._handle(), *[C.byref(q) for q in v]))
+        return tuple(int(q.value) for q in v)
+
+    def _frames_of(self, data):
+        """(the array, flat and contiguous; the frames it holds).  Nothing is converted: on a stream with a format an array of another dtype than the
+        format's (int16, float32, uint8 for G.711) or one that ends in a partial frame is refused here with SD_ERR_ARG, and an array that is already
+        contiguous is not copied, so the same array gives the same pointer.  A stream without a format hands its elements on as they are, for the
+        library to refuse."""
+        enc, channels, _, is_set = self.input_format()
+        data = np.asarray(data)
+        if is_set and data.dtype != _ENC_DTYPES[enc]:
+            raise SdError(1, "push_audio: the stream's format takes %s elements, the array holds %s" % (np.dtype(_ENC_DTYPES[enc]).name, data.dtype.name))
+        data = np.ascontiguousarray(data).reshape(-1)
+        if is_set and len(data) % channels:
+            raise SdError(1, "push_audio: %d elements are no whole number of frames of %d channels" % (len(data), channels))
+        return data, len(data) // channels if is_set else len(data)
+
+    def push_audio(self, data):
+        """sd_stream_push_audio: whole interleaved frames in the stream's format, in an array of the format's dtype (int16, float32, or one G.711
+        code per uint8); another dtype or a partial frame is refused, nothing is converted"""
+        data, frames = self._frames_of(data)
+        self._d._chk(lib().sd_stream_push_audio(self._handle(), _ptr(data) if data.size else None, frames))
+
+    def push_audio_dev(self, d_ptr, frames):
+        """sd_stream_push_audio_dev: a device pointer to `frames` interleaved frames in the stream's format"""
+        self._d._chk(lib().sd_stream_push_audio_dev(self._handle(), C.c_void_p(d_ptr or None), int(frames)))
 
     def _tail(self):
         """sd_test_stream_tail: (the f32 samples the stream holds on the device, from sample sealed * 8000 on; the index of the first of them)"""
@@ -1388,6 +1435,19 @@ class Diarizer:
         """sd_stream_push_many_dev: device pointers of int16 samples and their lengths"""
         self._push_many(lib().sd_stream_push_many_dev, streams, d_pcm_ptrs, lengths)
 
+    def stream_push_many_audio(self, streams, datas):
+        """sd_stream_push_many_audio: interleaved frames for every stream of the list, each in its stream's format (an empty array: nothing for that
+        stream), in an array of the format's dtype (another dtype or a partial frame is refused; nothing is converted or, for a contiguous array,
+        copied).  The SAME array passed for two streams is the same pointer: the legs of one stereo call, uploaded once"""
+        if len(streams) != len(datas):
+            raise SdError(1, "one array per stream")
+        rows = [s._frames_of(d) for s, d in zip(streams, datas)]      # (an array of the right type and layout is not copied: its pointer is the caller's)
+        self._push_many(lib().sd_stream_push_many_audio, streams, [a.ctypes.data if a.size else 0 for a, _ in rows], [f for _, f in rows])
+
+    def stream_push_many_audio_dev(self, streams, d_ptrs, frames):
+        """sd_stream_push_many_audio_dev: device pointers of interleaved frames, each in its stream's format, and their frame counts"""
+        self._push_many(lib().sd_stream_push_many_audio_dev, streams, d_ptrs, frames)
+
     def stream_turns_many(self, streams):
         """sd_stream_turns_many: per stream the turns Stream.turns gives, or the error code (SD_ERR_SHORT = 4, SD_ERR_NUMERIC = 5) it ended with;
         many_select(i) then makes stream i the last job"""
@@ -1935,6 +1995,19 @@ class Diarizer:
         rows = np.ascontiguousarray(rows, np.int64).reshape(-1, 8)
         out = np.zeros(int(dst_len) + IN_SLACK, np.float32)
         rc = lib().sd_test_many_ingest(self._h, _ptr(rows), len(rows), _ptr(src) if src.size else None, src.size, int(dst_len), canary, _ptr(out))
+        if refused:
+            assert rc == 1, rc                       # SD_ERR_ARG
+            return out
+        self._chk(rc)
+        return out
+
+    def group_ingest_case(self, rows, src, dst_len, canary=-7776.0, refused=False):
+        """sd_test_group_ingest (include/sdhip_stream_ingest_test.h): rows [R][7] = (encoding, channels, channel, n, src_off in bytes, dst_off, room),
+        src = the bytes of all sources -> [dst_len + IN_SLACK] float32.  refused = True: the hook must refuse the table with SD_ERR_ARG before any launch."""
+        src = np.ascontiguousarray(src).view(np.uint8).reshape(-1)
+        rows = np.ascontiguousarray(rows, np.int64).reshape(-1, 7)
+        out = np.zeros(int(dst_len) + IN_SLACK, np.float32)
+        rc = lib().sd_test_group_ingest(self._h, _ptr(rows), len(rows), _ptr(src) if src.size else None, src.size, int(dst_len), canary, _ptr(out))
         if refused:
             assert rc == 1, rc                       # SD_ERR_ARG
             return out
